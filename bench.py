@@ -11,20 +11,27 @@ State, actions and observations are resident in HBM when the timed region starts
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (HBM write
-roofline of the step kernel, HIP-event timed on the kernel's own stream; `traffic` = HBM bytes
-per launch from the PMC counters, measured by the run itself at N = 1: two short
-`rocprofv3 --pmc` passes of this script as child processes, after the timed region) and
-`cpu_baseline` (the CPU oracle — a C restatement of the reference, kind "port" — timed on
-this box's host cores on a bounded sample of the same workload).  A default run takes 20-40 s:
-a few seconds for the GPU part, ~6-12 s each for the two counter passes (bounded at 60 s each; a pass
-that fails or runs out of time says so on stderr and the committed figure is used, labelled), ~15 s for
-the CPU baseline.
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times
+the K steps, writes its outputs (--dump-outputs DIR) and prints the headline: `value`, `ms_per_step`
+and the configuration.  --full adds what takes runs of its own, after the timed region: `roofline`
+(HBM write roofline of the step kernel, HIP-event timed on the kernel's own stream in a second pass
+over the same steps; `traffic` = HBM bytes per launch from the PMC counters, measured by the run
+itself at N = 1: two short `rocprofv3 --pmc` passes of this script as child processes), `top_view`
+(with --top-view), `cpu_baseline` (the CPU oracle — a C restatement of the reference, kind "port" —
+timed on this box's host cores on a bounded sample of the same workload) and, at N > 1, `gather`.
+A --full run takes 20-40 s: a few seconds for the GPU part, ~6-12 s each for the two counter passes
+(bounded at 60 s each; a pass that fails or runs out of time says so on stderr and the committed
+figure is used, labelled), ~15 s for the CPU baseline.
+
+--dump-outputs DIR: what the timed path computed in its last step, as a caller of RCW.act! receives
+it (the camera view, and the top view with --top-view, of a fixed seeded sample of agents; every
+agent's position, direction, goal, reward and done), as DIR/<name>.npy in float32 / float64, under
+64 MB in all.  Seeds are fixed, so the same arguments give the same inputs on every run.
 
 N > 1: every rank stops its own clock after its own synchronisation — no collective inside the timed
 region —; the per-rank times are gathered afterwards, `value` uses the slowest rank (MAX), and the line
-carries `ms_per_step_min` / `ms_per_step_max` over ranks and `roofline.per_rank` (every rank's fill-kernel
-launch time), so that a straggling GPU shows.
+carries `ms_per_step_min` / `ms_per_step_max` over ranks and, with --full, `roofline.per_rank` (every
+rank's fill-kernel launch time), so that a straggling GPU shows.  --dump-outputs writes rank 0's agents.
 """
 import argparse
 import json
@@ -161,6 +168,34 @@ def top_view_scratch_bytes(H, W, pu, B):
     pixel), the player's pixel (8 B an agent) and the 2-bit tile codes (8 B per tile column and 256-row run)."""
     Ht, Wt = H * pu, W * pu
     return B * (Ht * Wt // 8 + 8 + 8 * W * ((Ht + 255) // 256))
+
+
+DUMP_IMAGE_BYTES = 48 << 20   # the sampled images, as float64; the per-agent arrays add B x 56 bytes
+
+
+def dump_outputs(env, directory, top_view=False):
+    """--dump-outputs: the state a caller of RCW.act! reads after the last step, as DIR/<name>.npy.  The images (uint32 pixels:
+    float64 holds them exactly) of a fixed seeded sample of agents, as many as fit DUMP_IMAGE_BYTES; every agent's small arrays."""
+    os.makedirs(directory, exist_ok=True)
+    B = env.batch
+    sample = lambda b: [env.camera_view_host(b, 1)] + ([env.top_view_host(b, 1)] if top_view else [])
+    per_agent = sum(a.size for a in sample(0)) * 8
+    agents = np.sort(np.random.default_rng(0).choice(B, size=max(1, min(B, DUMP_IMAGE_BYTES // per_agent)), replace=False))
+    images = [sample(int(b)) for b in agents]
+    w = env.world
+    out = {
+        "camera_view_sample": np.concatenate([im[0] for im in images]).astype(np.float64),
+        "sample_agents": agents.astype(np.float64),
+        "player_position_wu": w.player_position_wu.astype(np.float32),
+        "player_direction_au": w.player_direction_au.astype(np.float64),
+        "goal_position": w.goal_position.astype(np.float64),
+        "reward": w.reward.astype(np.float32),
+        "done": w.done.astype(np.float32),
+    }
+    if top_view:
+        out["top_view_sample"] = np.concatenate([im[1] for im in images]).astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def live_traffic(workload, batch, kernel, seconds=60.0, extra_args=()):
@@ -303,6 +338,11 @@ def main(argv=None, rt=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="agents per GPU (default: the workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own after the timed region: the per-kernel HIP-event pass and the roofline "
+                         "(and top_view) block it feeds, roofline.traffic, the CPU baseline and, at N > 1, the observation gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0's agents; images of a seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=10.0, help="about how long the all-cores leg of the CPU baseline runs")
     ap.add_argument("--traffic", default="live", choices=["live", "committed", "off"],
@@ -315,10 +355,10 @@ def main(argv=None, rt=None):
                          "configuration), two-launches = the cast kernel followed by the fill kernel (rounds 1-5), for the comparison")
     ap.add_argument("--top-view", action="store_true",
                     help="also render the reference's top view every step (update_top_view! SR:446-483, opt-in in the "
-                         "engine) and report that kernel's own roofline block; NOT the headline workload")
+                         "engine) and, with --full, report that kernel's own roofline block; NOT the headline workload")
     ap.add_argument("--gather", action="store_true",
                     help="also time the optional observation gather (RCCL all-gather of descriptors / frames) after the "
-                         "timed region; on by default when --gpus > 1, with one GPU it runs a one-rank process group")
+                         "timed region; on with --full when --gpus > 1, with one GPU it runs a one-rank process group")
     ap.add_argument("--api", default="raw", choices=["raw", "rlbase"],
                     help="raw: time RCW.act!(env, actions) alone (the headline).  rlbase: ALSO time the loop of the reference's own "
                          "test (test/runtests.jl:26-33: RLBase.state -> env(action) -> RLBase.reward -> RLBase.is_terminated every step, "
@@ -420,15 +460,20 @@ def main(argv=None, rt=None):
     rt.synchronize()
     dt = time.perf_counter() - t0  # this rank's own clock, stopped behind its own synchronisation: NO collective inside dt
     barrier()
-    # Outside the timed region: the same steps again with HIP events around each kernel, to
-    # read the dominant (fill) kernel's own launch duration for the roofline block.
-    nprof = min(args.steps, 200)
-    env.profile(True)
-    for s in range(args.warmup, args.warmup + nprof):
-        RCW.act_(env, actions[s])
-    cast_ms, top_ms, fill_ms, nrec = env.profile_read()
-    env.profile(False)
-    sync_counting_bounds_errors()
+    if args.dump_outputs and rank == 0:              # (before anything below steps the agents again)
+        dump_outputs(env, args.dump_outputs, top_view=args.top_view)
+    cast_ms = top_ms = fill_ms = 0.0
+    nrec = 0
+    if args.full:
+        # Outside the timed region: the same steps again with HIP events around each kernel, to
+        # read the dominant (fill) kernel's own launch duration for the roofline block.
+        nprof = min(args.steps, 200)
+        env.profile(True)
+        for s in range(args.warmup, args.warmup + nprof):
+            RCW.act_(env, actions[s])
+        cast_ms, top_ms, fill_ms, nrec = env.profile_read()
+        env.profile(False)
+        sync_counting_bounds_errors()
     # the ranks' own figures, gathered; the job's are the slowest rank's (MAX), the spread goes into the line
     ranks = reduce_rank_times(gather_rows([dt, kernel_ms, cast_ms, fill_ms, top_ms]), args.steps)
     dt, kernel_ms, cast_ms, fill_ms, top_ms = (ranks[k] for k in ("dt", "kernel_ms", "cast_ms", "fill_ms", "top_ms"))
@@ -479,7 +524,7 @@ def main(argv=None, rt=None):
     fill_kernel = env.fill_kernel_name()
     top_pu, top_form = env.cfg.pu_per_tu, env.top_view_form()
 
-    def build_line(gather):
+    def roofline_block():                                 # (--full: the per-kernel pass has run)
         frame_bytes = 4 * Hc * N                          # bytes per env-step
         bytes_per_launch = frame_bytes * B                # one fill launch = B agents
         launch_note = None
@@ -514,6 +559,34 @@ def main(argv=None, rt=None):
                                           + (f" ({world} ranks: each rank runs the same per-GPU workload)" if world > 1 else ""))
                 except Exception:
                     traffic = None
+        roofline = {
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "traffic_source": traffic_source,
+            "kernel": fill_kernel,
+            "bytes_per_launch": bytes_per_launch,
+            "launch_ms": fill_ms,
+            "launches_timed": nrec,
+            "per_rank": ranks["per_rank"],
+            "whole_step": {
+                "kernels": ("rcw_fill256_cast_kernel alone: the fill workgroups write the frames the actions select among the successors the "
+                            "previous launch cast, the casting workgroups commit the actions and cast the next successors beside them"
+                            if step_form == "one-launch" else "rcw_cast_kernel + fill kernel"),
+                "launch_ms": step_s * 1e3,
+                "cast_ms": cast_ms,
+                "achieved": step_achieved,
+                "frac": step_achieved / HBM_PEAK_GBS,
+            },
+        }
+        if launch_note:
+            roofline["launch_note"] = launch_note
+        return roofline
+
+    def build_line(gather):
         out = {
             "metric": "env-steps/sec (whole node) + frames/sec, SingleRoom batch=4096 cols=256",
             "value": world * B * args.steps / dt,
@@ -542,39 +615,17 @@ def main(argv=None, rt=None):
                 "step_form": step_form,
             },
             "frames_per_s": world * B * args.steps / dt,
-            "roofline": {
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_source": traffic_source,
-                "kernel": fill_kernel,
-                "bytes_per_launch": bytes_per_launch,
-                "launch_ms": fill_ms,
-                "launches_timed": nrec,
-                "per_rank": ranks["per_rank"],
-                "whole_step": {
-                    "kernels": ("rcw_fill256_cast_kernel alone: the fill workgroups write the frames the actions select among the successors the "
-                                "previous launch cast, the casting workgroups commit the actions and cast the next successors beside them"
-                                if step_form == "one-launch" else "rcw_cast_kernel + fill kernel"),
-                    "launch_ms": step_s * 1e3,
-                    "cast_ms": cast_ms,
-                    "achieved": step_achieved,
-                    "frac": step_achieved / HBM_PEAK_GBS,
-                },
-            },
         }
-        if launch_note:
-            out["roofline"]["launch_note"] = launch_note
+        if args.full:
+            out["roofline"] = roofline_block()
         if gather is not None:
             out["gather"] = gather
         if args.top_view:
+            out["config"]["render_top_view"] = True
+        if args.top_view and args.full:
             pu = top_pu
             top_bytes = 4 * (kw["height_tile_map_tu"] * pu) * (kw["width_tile_map_tu"] * pu) * B
             top_gbs = top_bytes / (top_ms / 1e3) / 1e9
-            out["config"]["render_top_view"] = True
             form = top_form
             out["top_view"] = {
                 "form": form,
@@ -603,7 +654,7 @@ def main(argv=None, rt=None):
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(line_dict) + "\n").encode())
 
-    if dist is not None:
+    if dist is not None and (args.gather or args.full):
         import threading
 
         rehearsal = args.rehearse_on_one_gpu
@@ -691,10 +742,10 @@ def main(argv=None, rt=None):
         pending["what"] = "nothing (the gather is over)"
 
     if rank == 0:
-        if world == 1 and args.traffic == "live":
+        if args.full and world == 1 and args.traffic == "live":
             traffic_live = live_traffic(args.workload, B, fill_kernel, extra_args=(["--top-view"] if args.top_view else []) + ["--step-form", args.step_form])
         out = build_line(gather)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0's own host cores, outside every timed region, at any N (the other ranks wait at the closing barrier)
             out["cpu_baseline"] = cpu_baseline(kw, B, args.cpu_baseline_seconds)
         emit(out)

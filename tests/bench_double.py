@@ -81,7 +81,9 @@ class EnvDouble:
     def __init__(self, batch, num_rays, **kw):
         self.batch, self.N, self.Hc = batch, num_rays, 256
         self.cfg = types.SimpleNamespace(pu_per_tu=32)
-        self.world = types.SimpleNamespace(status=np.zeros(batch, np.int32))
+        self.world = types.SimpleNamespace(status=np.zeros(batch, np.int32), player_position_wu=np.full((batch, 2), 1.5, np.float32),
+                                           player_direction_au=np.arange(batch, dtype=np.int32) % 64, goal_position=np.full((batch, 2), 2, np.int32),
+                                           reward=np.zeros(batch, np.float32), done=np.zeros(batch, bool))
         self._form = "one-launch"
         self._h = torch.zeros((batch, num_rays), dtype=torch.int32)
         self._c = torch.zeros((batch, num_rays), dtype=torch.uint8)
@@ -103,6 +105,9 @@ class EnvDouble:
     def columns_device(self): return DeviceArrayDouble(self._h), DeviceArrayDouble(self._c)
     @property
     def camera_view(self): return DeviceArrayDouble(self._obs)
+    def camera_view_host(self, first, count):       # (--dump-outputs: pixels above 2**24 tell whether the dump keeps them exact)
+        CALLS.setdefault("steps_at_dump", CALLS["steps"])
+        return np.full((count, self.N, self.Hc), 0xFF000000 + first, np.uint32)
     def expand_columns(self, h, c, out=None): CALLS["expand_columns"] += 1
     def close(self): pass
 

@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -119,7 +121,7 @@ def test_the_multi_rank_control_flow_runs_on_doubles(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("LOCAL_RANK",)}
     env.update(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", BENCH_DOUBLE_LOG=str(tmp_path / "calls.json"))
     res = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_double.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-                          "--batch", "8", "--cpu-baseline-seconds", "0.3", "--api", "rlbase"], env=env, capture_output=True, text=True, timeout=600)
+                          "--batch", "8", "--cpu-baseline-seconds", "0.3", "--api", "rlbase", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, res.stdout
@@ -137,3 +139,39 @@ def test_the_multi_rank_control_flow_runs_on_doubles(tmp_path):
     assert calls["all_gather"] >= 4 and calls["barrier"] >= 4 and calls["destroyed"] == 1
     assert calls["steps"] == 2 + 6 + 6 + 2 + 6                       # warm-up + timed + per-kernel events + the API loop's two
     assert calls["collectives_inside_timed_regions"] == 0
+
+
+def test_a_plain_run_times_the_steps_and_dumps_the_last_ones_outputs(tmp_path):
+    """bench.py without --full (what is run for every change): warm-up, the K timed steps, the outputs of the last one, the headline
+    line — no per-kernel pass, no CPU baseline, no counter passes.  --dump-outputs writes the state right after the timed steps as
+    .npy files in float32 / float64 (pixels exactly), the images of a seeded sample of agents, under 64 MB."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", BENCH_DOUBLE_LOG=str(tmp_path / "calls.json"))
+    dump = tmp_path / "out"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_double.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                          "--dump-outputs", str(dump)], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, res.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 4096 * 7 / (d["ms_per_step"] * 7 / 1e3)) < 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "gather", "top_view", "api_loop"):
+        assert k not in d, k
+    calls = json.load(open(tmp_path / "calls.json"))
+    assert calls["steps"] == 3 + 7 and calls["steps_at_dump"] == 3 + 7
+    files = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert set(files) == {"camera_view_sample", "sample_agents", "player_position_wu", "player_direction_au", "goal_position", "reward", "done"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in dump.glob("*.npy")) <= 64 * 10 ** 6
+    agents = files["sample_agents"].astype(np.int64)
+    assert len(agents) == 96 and len(set(agents)) == 96 and (np.diff(agents) > 0).all()         # 48 MiB of 256 x 256 float64 images
+    assert files["camera_view_sample"].shape == (96, 256, 256)
+    assert (files["camera_view_sample"] == (0xFF000000 + agents)[:, None, None]).all()
+    assert files["player_position_wu"].shape == (4096, 2) and (files["player_direction_au"] == np.arange(4096) % 64).all()
+    again = tmp_path / "again"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_double.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                          "--dump-outputs", str(again)], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and (np.load(again / "sample_agents.npy") == files["sample_agents"]).all()   # the same sample every run

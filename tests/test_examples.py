@@ -46,7 +46,7 @@ def test_bench_modes(flags):
     default invocation is what the round-end driver runs)."""
     import json
 
-    out = _run(["bench.py", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--traffic", "off"] + flags)
+    out = _run(["bench.py", "--full", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--traffic", "off"] + flags)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out
     d = json.loads(lines[0])
@@ -68,3 +68,26 @@ def test_bench_modes(flags):
         assert d["roofline"]["kernel"] != "rcw_fill256_draw_kernel" and "launch_note" not in d["roofline"]
     if flags == ["--gather"]:
         assert "gather" in d and "error" not in d["gather"], d.get("gather")
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """The plain invocation (no --full) prints the headline alone, and --dump-outputs writes the state after the last timed step:
+    the sampled frames are the engine's own pixels, exactly, and two runs with the same arguments write the same arrays."""
+    import json
+
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        out = _run(["bench.py", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / f"run{k}")])
+        lines = [l for l in out.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out
+        d = json.loads(lines[0])
+        assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+        assert "roofline" not in d and "cpu_baseline" not in d
+        dumps.append({p.stem: np.load(p) for p in (tmp_path / f"run{k}").glob("*.npy")})
+    a, b = dumps
+    assert set(a) == set(b) and "camera_view_sample" in a and a["player_position_wu"].shape == (4096, 2)
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.array_equal(a[name], b[name]), name
+    assert a["camera_view_sample"].shape == (len(a["sample_agents"]), 256, 256) and (a["camera_view_sample"] != 0).all()

@@ -129,7 +129,7 @@ def test_bench_rehearsal_with_four_ranks(rcw, tmp_path):
         env.pop(k, None)
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
                           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "5", "--warmup", "2",
-                          "--rehearse-on-one-gpu", "--cpu-baseline-seconds", "1"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--rehearse-on-one-gpu", "--full", "--cpu-baseline-seconds", "1"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + "\n" + res.stderr[-6000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, res.stdout[-3000:]
@@ -159,7 +159,7 @@ def test_a_hung_gather_looks_hung(rcw):
         env.pop(k, None)
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--batch", "256", "--rehearse-on-one-gpu", "--watchdog-seconds", "4", "--hang-rank", "1"],
+                          "--batch", "256", "--rehearse-on-one-gpu", "--full", "--watchdog-seconds", "4", "--hang-rank", "1"],
                          env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode != 0, "a hung gather ended with exit code 0"
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

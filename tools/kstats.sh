@@ -4,6 +4,7 @@
 tag=$1; shift
 export TMPDIR=/tmp; R=$PWD
 rm -rf $R/gpurun_out/$tag
+set -- --full "$@"             # (the summary below reads the roofline block)
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$tag -- python3 $R/bench.py --no-cpu-baseline "$@" > $R/gpurun_out/$tag.log 2>&1) || { echo "rocprofv3 failed: $tag"; tail -5 $R/gpurun_out/$tag.log; exit 1; }
 python3 - "$R/gpurun_out/$tag" "$R/gpurun_out/$tag.log" <<'PY'
 import csv, glob, json, re, sys

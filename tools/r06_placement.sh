@@ -27,7 +27,7 @@ PY
   rm -f $C/x_nops.hip $D/*.o
   for k in $(seq 0 15); do echo -n "k=$k: "; python3 tools/loop_lines.py $D/librcw_hip_nops_$k.so rcw_fill256_cast_kernelIfLb0ELb0ELb0 | sed 's/.*chunk loops/chunk loops/;s/; march.*//'; done
 else
-  run() { RCW_LIBRARY=$D/librcw_hip_nops_$2.so python bench.py --workload $1 --steps 100 --warmup 10 --no-cpu-baseline --traffic off 2>/dev/null | python -c "
+  run() { RCW_LIBRARY=$D/librcw_hip_nops_$2.so python bench.py --full --workload $1 --steps 100 --warmup 10 --no-cpu-baseline --traffic off 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$1 nops %2d' % $2, round(d['ms_per_step']*1e3,1), round(d['roofline']['launch_ms']*1e3,1))"; }
   for rep in 1 2; do for k in $(seq 0 15); do run cfg3 $k; done; done

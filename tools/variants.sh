@@ -14,7 +14,7 @@ for v in default $(ls tools/_build/variants/*.so 2>/dev/null); do
   if [ "$v" = default ]; then unset RCW_LIBRARY; else export RCW_LIBRARY="$PWD/$v"; fi
   n=$(basename "$v" .so)
   case $mode in
-    bench)   timeout -k 10 120 python bench.py --no-cpu-baseline "$@" 2>/dev/null | python tools/bench_brief.py "$n" || exit 1 ;;
+    bench)   timeout -k 10 120 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python tools/bench_brief.py "$n" || exit 1 ;;
     stats)   echo "== $n"; timeout -k 10 300 tools/kstats.sh "vs_$n" "$@" || exit 1 ;;
     kernels) timeout -k 10 260 tools/kprof.sh "$n" "$@" || exit 1 ;;
     dist)    timeout -k 10 260 tools/kdist.sh "$n" "$@" || exit 1 ;;
