@@ -252,7 +252,8 @@ RCW_API int rcw_sync(rcw_handle* h);
 RCW_API int rcw_clear_error(rcw_handle* h);
 
 /* RLBase.state(env) SR:576: the camera view batch, aliased — the pointer is stable for
- * the handle's lifetime (or until rcw_bind_obs) and is overwritten by the next step. */
+ * the handle's lifetime (or until rcw_bind_obs) and is overwritten by the next step.  With a learner view set with
+ * RCW_VIEW_ONLY (below) steps do not write it: it holds the last frames rendered until rcw_update_camera_view. */
 RCW_API int rcw_obs_device_ptr(rcw_handle* h, void** device_ptr);
 /* Copy frames of agents [first, first+count) to host: UInt32 (H_cam, N, count). */
 RCW_API int rcw_obs_copy(rcw_handle* h, uint32_t* out_host, int32_t first, int32_t count);
@@ -308,6 +309,45 @@ RCW_API int rcw_columns_device_ptr(rcw_handle* h, void** height_line_pu, void** 
  * the receiving side of the compact observation gather. */
 RCW_API int rcw_expand_columns(rcw_handle* h, const int32_t* height_line_pu_device,
                        const uint8_t* colour_id_device, int32_t count, void* frames_device);
+
+/* ---- the learner view: a uint8 observation a learner consumes, rendered from the column descriptors -----------------------
+ * Opt-in per handle.  Once set, every rcw_reset / rcw_set_state / rcw_step / rcw_step_device also renders it, on the handle's
+ * stream behind the camera view (a masked reset or set_state: the masked agents only); a handle that never sets it runs what it
+ * ran before.  Pixel contract (exact, integer), with H = height_camera_view_pu, N = num_rays and the frame of agent b as the
+ * camera view holds it (image column k, row y, row 0 at the top):
+ *   size (h, w) with 1 <= h <= H and 1 <= w <= N (no up-sampling); output row r covers rows [floor(r H / h), floor((r+1) H / h)),
+ *   output column c covers columns [floor(c N / w), floor((c+1) N / w)) — never empty, not all of one size;
+ *   RCW_VIEW_RGB8: R = (p >> 16) & 0xFF, G = (p >> 8) & 0xFF, B = p & 0xFF of each pixel p, each channel (S + floor(n/2)) / n over
+ *                  the box's n pixels (S their sum: round half up);
+ *   RCW_VIEW_GRAY8: Y = (77 R + 150 G + 29 B + 128) >> 8 of each pixel, averaged the same way (reference colours: ceiling 255,
+ *                  floor 64, walls 128 / 192, goal 39 / 58);
+ *   at (h, w) = (H, N) the RGB view is the camera view's bytes, transposed to rows first.  The handle's configured colours apply.
+ * Layouts: RCW_VIEW_CHW (B, C, h, w) or RCW_VIEW_HWC (B, h, w, C), C order (Julia sees (w, h, C, B) / (C, w, h, B)); gray has
+ * C = 1 and both layouts are the same bytes.
+ * RCW_VIEW_ONLY: a step is the cast kernel followed by the view kernel — the UInt32 camera view is NOT written by steps (see
+ * rcw_obs_device_ptr; rcw_update_camera_view renders it on demand), the step takes two launches (rcw_step_form) and
+ * rcw_set_step_form(h, RCW_STEP_ONE_LAUNCH) returns RCW_ERR_UNSUPPORTED.  The top view, if enabled, is rendered as before.
+ *   rcw_set_learner_view         allocates the B*C*h*w bytes and renders the current state into them at once; RCW_VIEW_OFF
+ *                                frees them.  A bad argument or an allocation failure leaves the previous view as it was.
+ *   rcw_learner_view_info        the current settings (format RCW_VIEW_OFF and zeros when there is none).
+ *   rcw_learner_view_device_ptr  the view batch in DEVICE memory, aliased: stable until the next rcw_set_learner_view.
+ *   rcw_learner_view_copy        agents [first, first+count) to host memory (waits for the stream).
+ *   rcw_expand_columns_view      the handle's learner view (format, layout, size) of `count` agents' descriptors in DEVICE memory
+ *                                (e.g. gathered from other GPUs) into view_device (count*C*h*w bytes), stream-ordered like
+ *                                rcw_expand_columns. */
+#define RCW_VIEW_OFF   0
+#define RCW_VIEW_RGB8  1
+#define RCW_VIEW_GRAY8 2
+#define RCW_VIEW_CHW   0
+#define RCW_VIEW_HWC   1
+#define RCW_VIEW_ONLY  1   /* flag: no camera view in the step */
+RCW_API int rcw_set_learner_view(rcw_handle* h, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags);
+RCW_API int rcw_learner_view_info(rcw_handle* h, int32_t* format, int32_t* layout, int32_t* height, int32_t* width,
+                                  int32_t* flags);
+RCW_API int rcw_learner_view_device_ptr(rcw_handle* h, void** device_ptr);
+RCW_API int rcw_learner_view_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32_t count);
+RCW_API int rcw_expand_columns_view(rcw_handle* h, const int32_t* height_line_pu_device, const uint8_t* colour_id_device,
+                                    int32_t count, void* view_device);
 
 /* ---- multi-GPU: the observation gather north_star names, for a host without torch (Julia) ---------------
  * Agents shard by rank (cfg.agent_id_offset); stepping needs no communication.  The only exchange is the

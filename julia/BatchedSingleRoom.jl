@@ -41,6 +41,12 @@ const NUM_ACTIONS = 4   # src/single_room.jl:19
 const RCW_UNIQUE_ID_BYTES = 128
 const RCW_GATHER_COLUMNS = Int32(0)
 const RCW_GATHER_FRAMES = Int32(1)
+const RCW_VIEW_OFF = Int32(0)      # rcw_set_learner_view: format
+const RCW_VIEW_RGB8 = Int32(1)
+const RCW_VIEW_GRAY8 = Int32(2)
+const RCW_VIEW_CHW = Int32(0)      # ... layout (C order; Julia sees the axes reversed)
+const RCW_VIEW_HWC = Int32(1)
+const RCW_VIEW_ONLY = Int32(1)     # ... flag: steps skip the UInt32 camera view
 # R of SingleRoom(; R = ...) single_room.jl:266  <->  rcw_config.reward_type
 const REWARD_TYPES = (Float32, Float64, Int32, Int64)
 
@@ -441,6 +447,52 @@ expand_columns!(env::BatchedSingleRoom, height_line_pu_device::Ptr{Int32}, colou
                 frames_device::Ptr{Cvoid}) =
     check(ccall((:rcw_expand_columns, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{UInt8}, Int32, Ptr{Cvoid}),
                 env.handle, height_line_pu_device, colour_id_device, count, frames_device))
+
+#####
+##### the learner view: UInt8 RGB / gray, area-averaged to (h, w), rendered by every reset / step (include/rcw.h)
+#####
+
+# format = :gray | :rgb | :off; size = (h, w) with h <= height_camera_view_pu, w <= num_rays; layout = :chw | :hwc;
+# camera_view = false: steps skip the UInt32 camera view (RCW_VIEW_ONLY).  Renders the current state at once.
+function set_learner_view!(env::BatchedSingleRoom; format::Symbol = :gray,
+                           size::Tuple{Integer, Integer} = (env.config.height_camera_view_pu, env.config.num_rays),
+                           layout::Symbol = :chw, camera_view::Bool = true)
+    fmt = format === :gray ? RCW_VIEW_GRAY8 : format === :rgb ? RCW_VIEW_RGB8 : format === :off ? RCW_VIEW_OFF :
+          throw(ArgumentError("format must be :gray, :rgb or :off"))
+    lay = layout === :chw ? RCW_VIEW_CHW : layout === :hwc ? RCW_VIEW_HWC : throw(ArgumentError("layout must be :chw or :hwc"))
+    check(ccall((:rcw_set_learner_view, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32),
+                env.handle, fmt, lay, size[1], size[2], camera_view ? Int32(0) : RCW_VIEW_ONLY))
+end
+function learner_view_info(env::BatchedSingleRoom)
+    f = Ref{Int32}(0); l = Ref{Int32}(0); h = Ref{Int32}(0); w = Ref{Int32}(0); fl = Ref{Int32}(0)
+    check(ccall((:rcw_learner_view_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}),
+                env.handle, f, l, h, w, fl))
+    return (format = f[], layout = l[], height = h[], width = w[], flags = fl[])
+end
+# The column-major shape Julia sees of the C-order (B, C, h, w) / (B, h, w, C) batch: (w, h, C, B) for :chw, (C, w, h, B) for :hwc
+function learner_view_dims(env::BatchedSingleRoom)
+    v = learner_view_info(env)
+    v.format == RCW_VIEW_OFF && error("no learner view: call set_learner_view! first")
+    C = v.format == RCW_VIEW_RGB8 ? 3 : 1
+    return v.layout == RCW_VIEW_CHW ? (Int(v.width), Int(v.height), C, env.batch) : (C, Int(v.width), Int(v.height), env.batch)
+end
+function learner_view_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_learner_view_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p))
+    return p[]
+end
+# agents [first, first + count) of the learner view on the host, in learner_view_dims' shape
+function learner_view(env::BatchedSingleRoom; first::Integer = 0, count::Integer = env.batch - first)
+    dims = learner_view_dims(env)
+    out = Array{UInt8, 4}(undef, dims[1], dims[2], dims[3], count)
+    check(ccall((:rcw_learner_view_copy, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int32, Int32), env.handle, out, first, count))
+    return out
+end
+# descriptors (device pointers) -> this handle's learner view of them (device pointer, count * C * h * w bytes)
+expand_columns_view!(env::BatchedSingleRoom, height_line_pu_device::Ptr{Int32}, colour_id_device::Ptr{UInt8}, count::Integer,
+                     view_device::Ptr{Cvoid}) =
+    check(ccall((:rcw_expand_columns_view, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{UInt8}, Int32, Ptr{Cvoid}),
+                env.handle, height_line_pu_device, colour_id_device, count, view_device))
 
 #####
 ##### streams, device memory, timing, introspection

@@ -29,6 +29,9 @@ RCW_GATHER_COLUMNS, RCW_GATHER_FRAMES = 0, 1
 RCW_UNIQUE_ID_BYTES = 128
 RCW_TOP_VIEW_NONE, RCW_TOP_VIEW_IN_PLACE, RCW_TOP_VIEW_ONE_KERNEL, RCW_TOP_VIEW_TWO_KERNELS = 0, 1, 2, 3
 RCW_STEP_TWO_LAUNCHES, RCW_STEP_ONE_LAUNCH = 1, 2   # rcw_step_form / rcw_set_step_form
+RCW_VIEW_OFF, RCW_VIEW_RGB8, RCW_VIEW_GRAY8 = 0, 1, 2   # rcw_set_learner_view: format
+RCW_VIEW_CHW, RCW_VIEW_HWC = 0, 1                      # ... layout
+RCW_VIEW_ONLY = 1                                      # ... flag: no camera view in the step
 
 
 class RcwConfig(C.Structure):
@@ -128,6 +131,11 @@ SIGNATURES = {
     "rcw_columns": [_vp, _i32, _i32, _vp, _vp],
     "rcw_columns_device_ptr": [_vp, C.POINTER(_vp), C.POINTER(_vp)],
     "rcw_expand_columns": [_vp, _vp, _vp, _i32, _vp],
+    "rcw_set_learner_view": [_vp, _i32, _i32, _i32, _i32, _i32],
+    "rcw_learner_view_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
+    "rcw_learner_view_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_learner_view_copy": [_vp, _vp, _i32, _i32],
+    "rcw_expand_columns_view": [_vp, _vp, _vp, _i32, _vp],
     "rcw_ray_table": [_vp, _vp],
     "rcw_direction_table": [_vp, _vp],
     "rcw_timer_start": [_vp],

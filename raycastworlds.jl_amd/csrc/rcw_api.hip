@@ -123,6 +123,10 @@ struct rcw_handle {
     std::vector<float> ray_table;   // (N, 5, nd)
     std::vector<double> dir_table64;   //              T = Float64
     std::vector<double> ray_table64;
+    // the learner view (rcw_set_learner_view): settings, the view batch and its box tables (rows [h + 1] then columns [w + 1])
+    int32_t view_fmt = RCW_VIEW_OFF, view_layout = RCW_VIEW_CHW, view_h = 0, view_w = 0, view_flags = 0;
+    void* d_view = nullptr; void* d_view_tab = nullptr;
+    RcwView view{};
 };
 
 namespace {
@@ -226,7 +230,7 @@ hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool 
 // it: before the fill with the one-kernel form, around it with the two-kernel form).  With profiling on,
 // HIP events bracket each kernel (what bench.py's roofline block reads the fill kernel's
 // duration from): start | after cast | after the top view (one-kernel form) or the fill (two-kernel form) | end.
-hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev)
+hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev)
 {
     const RcwDev& d = h->dev;
     const bool prof = h->profiling && h->prof_count < kProfileSlots;
@@ -297,6 +301,37 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     return hipSuccess;
 }
 
+bool view_only(const rcw_handle* h) { return h->view_fmt != RCW_VIEW_OFF && (h->view_flags & RCW_VIEW_ONLY) != 0; }
+
+// the learner view of the handle's current descriptors (the unmasked agents' only), on the handle's stream
+hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev)
+{
+    return rcw_launch_view(h->dev, h->view, h->dev.col_h, h->dev.col_c, h->B, mask_dev, (uint8_t*)h->d_view, h->stream);
+}
+
+// A step, reset! or set_state's render: the camera view (launch_step_camera), then the learner view where the handle has one.  With
+// RCW_VIEW_ONLY the cast kernel is followed by the view kernel alone (the top view, if any, in its stand-alone form between them);
+// profiling events: start | after cast | after the top view | after the view kernel.
+hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev)
+{
+    if (!view_only(h)) {
+        const hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
+        return e == hipSuccess && h->view_fmt != RCW_VIEW_OFF ? launch_view(h, mask_dev) : e;
+    }
+    const bool prof = h->profiling && h->prof_count < kProfileSlots;
+    hipEvent_t* ev = prof ? &h->prof_ev[4 * h->prof_count] : nullptr;
+    hipError_t e;
+    if (prof && (e = hipEventRecord(ev[0], h->stream)) != hipSuccess) return e;
+    if ((e = rcw_launch_cast(h->dev, actions_dev, mask_dev, h->stream)) != hipSuccess) return e;
+    if (!mask_dev) h->cols_stale = false;
+    if (prof && (e = hipEventRecord(ev[1], h->stream)) != hipSuccess) return e;
+    if (h->dev.top_view && (e = launch_top_view(h, mask_dev, false, [](hipStream_t) { return hipSuccess; })) != hipSuccess) return e;
+    if (prof && (e = hipEventRecord(ev[2], h->stream)) != hipSuccess) return e;
+    if ((e = launch_view(h, mask_dev)) != hipSuccess) return e;
+    if (prof) { if ((e = hipEventRecord(ev[3], h->stream)) != hipSuccess) return e; h->prof_count++; }
+    return hipSuccess;
+}
+
 void free_all(rcw_handle* h)
 {
     void** ptrs[] = {&h->d_pos, &h->d_dir, &h->d_goal, &h->d_reward, &h->d_done, &h->d_episode,
@@ -325,6 +360,9 @@ void free_all(rcw_handle* h)
     if (h->d_gather_h) (void)hipFree(h->d_gather_h);
     if (h->d_gather_c) (void)hipFree(h->d_gather_c);
     h->d_gather_h = h->d_gather_c = nullptr;
+    if (h->d_view) (void)hipFree(h->d_view);
+    if (h->d_view_tab) (void)hipFree(h->d_view_tab);
+    h->d_view = h->d_view_tab = nullptr;
     for (hipEvent_t ev : h->prof_ev) (void)hipEventDestroy(ev);
     h->prof_ev.clear();
     if (h->ev_start) (void)hipEventDestroy(h->ev_start);
@@ -648,6 +686,11 @@ int plan_step_form(rcw_handle* h, int want)
 {
     RcwDev& d = h->dev;
     const bool eligible = rcw_step_spec_eligible(d) != 0;
+    if (view_only(h)) {                                // (the cast kernel followed by the view kernel: no camera fill to fuse)
+        if (want == RCW_STEP_ONE_LAUNCH) return fail(RCW_ERR_UNSUPPORTED, "the handle's learner view is set with RCW_VIEW_ONLY: a step is the cast kernel and the view kernel");
+        h->spec_on = 0; h->spec_primed = false; h->step_form_want = want;
+        return RCW_OK;
+    }
     if (want == RCW_STEP_ONE_LAUNCH && !eligible)
         return fail(RCW_ERR_UNSUPPORTED, "this handle does not take the one-launch step (a camera view of 256 k, 128 or 64 rows — up to 8191 — without a top view, fewer than 2^29 view columns)");
     const bool on = want == RCW_STEP_TWO_LAUNCHES ? false : (want == RCW_STEP_ONE_LAUNCH ? true : eligible && !h->step_captured && step_one_launch_pays(d));
@@ -1479,6 +1522,112 @@ int rcw_expand_columns(rcw_handle* h, const int32_t* height_line_pu_device, cons
         return fail(RCW_ERR_INVALID_ARGUMENT, "bad argument");
     if ((uintptr_t)frames_device & 15u) return fail(RCW_ERR_INVALID_ARGUMENT, "frames must be 16-byte aligned");
     RCW_HIP(rcw_launch_expand(h->dev, height_line_pu_device, colour_id_device, count, (uint32_t*)frames_device, h->stream));
+    return RCW_OK;
+}
+
+// ---- the learner view ---------------------------------------------------------------------------------------
+int rcw_set_learner_view(rcw_handle* h, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    const int Hc = h->cfg.height_camera_view_pu, N = h->cfg.num_rays;
+    if (format != RCW_VIEW_OFF && format != RCW_VIEW_RGB8 && format != RCW_VIEW_GRAY8)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "format must be RCW_VIEW_OFF / RCW_VIEW_RGB8 / RCW_VIEW_GRAY8 (got %d)", format);
+    if (flags & ~RCW_VIEW_ONLY) return fail(RCW_ERR_INVALID_ARGUMENT, "unknown learner view flags 0x%x", (unsigned)flags);
+    if (format == RCW_VIEW_OFF && flags) return fail(RCW_ERR_INVALID_ARGUMENT, "RCW_VIEW_ONLY needs a format");
+    const bool was_only = view_only(h);
+    void* view = nullptr; void* tab = nullptr;
+    RcwView v{};
+    if (format != RCW_VIEW_OFF) {
+        if (layout != RCW_VIEW_CHW && layout != RCW_VIEW_HWC)
+            return fail(RCW_ERR_INVALID_ARGUMENT, "layout must be RCW_VIEW_CHW or RCW_VIEW_HWC (got %d)", layout);
+        if (height < 1 || height > Hc || width < 1 || width > N)
+            return fail(RCW_ERR_INVALID_ARGUMENT, "learner view size %d x %d outside 1..%d x 1..%d (no up-sampling)", height, width, Hc, N);
+        v.C = format == RCW_VIEW_RGB8 ? 3 : 1;
+        v.hwc = layout == RCW_VIEW_HWC ? 1 : 0;
+        v.h = height; v.w = width;
+        std::vector<int32_t> t;
+        try { t.resize((size_t)height + width + 2); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+        long long max_rows = 0, max_cols = 0;
+        for (int r = 0; r <= height; ++r) t[r] = (int32_t)((long long)r * Hc / height);
+        for (int c = 0; c <= width; ++c) t[(size_t)height + 1 + c] = (int32_t)((long long)c * N / width);
+        for (int r = 0; r < height; ++r) max_rows = std::max<long long>(max_rows, t[r + 1] - t[r]);
+        for (int c = 0; c < width; ++c) max_cols = std::max<long long>(max_cols, t[(size_t)height + 2 + c] - t[(size_t)height + 1 + c]);
+        const long long n = max_rows * max_cols;
+        v.wide = n * 256 + n >= (1ll << 31) ? 1 : 0;          // (a box's channel sum + n/2 must stay below 2^31 for 32-bit sums)
+        v.full_ok = height == Hc && width == N && rcw_view_full_eligible(h->dev, v.C, v.hwc) ? 1 : 0;
+        const size_t bytes = (size_t)h->B * v.C * (size_t)height * width;
+        hipError_t e = hipMalloc(&view, bytes);
+        if (e == hipSuccess) e = hipMalloc(&tab, t.size() * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemcpy(tab, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {                                     // the handle keeps its previous view
+            if (view) (void)hipFree(view);
+            if (tab) (void)hipFree(tab);
+            return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "learner view buffer of %zu bytes: %s", bytes, hipGetErrorString(e));
+        }
+        v.rows = (const int32_t*)tab;
+        v.cols = (const int32_t*)tab + height + 1;
+    }
+    RCW_HIP(hipStreamSynchronize(h->stream));                     // (the old buffers may be in use by queued work)
+    if (h->d_view) (void)hipFree(h->d_view);
+    if (h->d_view_tab) (void)hipFree(h->d_view_tab);
+    h->d_view = view; h->d_view_tab = tab; h->view = v;
+    h->view_fmt = format;
+    h->view_layout = format != RCW_VIEW_OFF ? layout : RCW_VIEW_CHW;
+    h->view_h = format != RCW_VIEW_OFF ? height : 0;
+    h->view_w = format != RCW_VIEW_OFF ? width : 0;
+    h->view_flags = flags;
+    if (format != RCW_VIEW_OFF) {
+        // the view kernel reads the descriptors: every step of the handle refreshes them from now on (as for rcw_columns_device_ptr)
+        h->cols_live = true;
+        rc = ensure_columns(h); if (rc) return rc;
+    }
+    if (view_only(h)) {                                           // (a caller's one-launch request gives way: the step has no camera fill)
+        if (h->step_form_want == RCW_STEP_ONE_LAUNCH) h->step_form_want = 0;
+        rc = plan_step_form(h, h->step_form_want); if (rc) return rc;
+    }
+    else if (was_only) {                                          // back to the camera view in the step: its form by the rule, its frames now
+        rc = plan_step_form(h, h->step_form_want); if (rc) return rc;
+        RCW_HIP(rcw_launch_fill(h->dev, h->dev.col_h, h->dev.col_c, h->dev.obs, (long long)h->dev.B * h->dev.N, nullptr, h->stream));
+    }
+    if (format != RCW_VIEW_OFF) RCW_HIP(launch_view(h, nullptr));
+    return RCW_OK;
+}
+
+int rcw_learner_view_info(rcw_handle* h, int32_t* format, int32_t* layout, int32_t* height, int32_t* width, int32_t* flags)
+{
+    if (!h || !format || !layout || !height || !width || !flags) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    *format = h->view_fmt; *layout = h->view_layout; *height = h->view_h; *width = h->view_w; *flags = h->view_flags;
+    return RCW_OK;
+}
+
+int rcw_learner_view_device_ptr(rcw_handle* h, void** device_ptr)
+{
+    if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (h->view_fmt == RCW_VIEW_OFF) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
+    *device_ptr = h->d_view;
+    return RCW_OK;
+}
+
+int rcw_learner_view_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32_t count)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    if (h->view_fmt == RCW_VIEW_OFF) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
+    if (!out_host || first < 0 || count < 0 || first + (int64_t)count > h->B)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
+    rc = sync_and_check(h);
+    const size_t per = (size_t)h->view.C * h->view_h * h->view_w;
+    RCW_HIP(hipMemcpy(out_host, (uint8_t*)h->d_view + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int rcw_expand_columns_view(rcw_handle* h, const int32_t* height_line_pu_device, const uint8_t* colour_id_device,
+                            int32_t count, void* view_device)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    if (h->view_fmt == RCW_VIEW_OFF) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
+    if (!height_line_pu_device || !colour_id_device || !view_device || count < 1)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "bad argument");
+    RCW_HIP(rcw_launch_view(h->dev, h->view, height_line_pu_device, colour_id_device, count, nullptr, (uint8_t*)view_device, h->stream));
     return RCW_OK;
 }
 

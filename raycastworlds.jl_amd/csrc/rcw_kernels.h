@@ -157,3 +157,19 @@ hipError_t rcw_launch_rays(const RcwDev& p, int32_t first, int32_t count, RcwRay
                            hipStream_t s);
 hipError_t rcw_launch_expand(const RcwDev& p, const int32_t* col_h, const uint8_t* col_c,
                              int32_t count, uint32_t* frames, hipStream_t s);
+
+// The learner view (rcw_set_learner_view, rcw_view.hip): uint8 RGB or gray, area-averaged to (h, w), computed from the column
+// descriptors.  Output row r averages camera rows [rows[r], rows[r+1]), column c image columns [cols[c], cols[c+1]).
+struct RcwView {
+    int32_t C;               // channels: 1 (gray) or 3 (RGB)
+    int32_t hwc;             // layout: 0 = (B, C, h, w), 1 = (B, h, w, C)
+    int32_t h, w;            // output size, 1 <= h <= Hc, 1 <= w <= N
+    const int32_t* rows;     // [h + 1] floor(r * Hc / h)
+    const int32_t* cols;     // [w + 1] floor(c * N / w)
+    int32_t wide;            // a box's channel sums may pass 2^31: 64-bit sums and divisions
+    int32_t full_ok;         // (h, w) = (Hc, N) and the geometry rcw_view_full_kernel takes
+};
+// the view of agents [0, count) of the descriptors col_h / col_c (N a agent) into out (count * C * h * w bytes); mask: NULL = all
+hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,
+                           const uint8_t* mask_dev, uint8_t* out, hipStream_t s);
+int rcw_view_full_eligible(const RcwDev& p, int C, int hwc);   // the full-resolution kernel takes this geometry and layout

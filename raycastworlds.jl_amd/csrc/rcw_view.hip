@@ -1,0 +1,313 @@
+// The learner view (rcw_set_learner_view): a uint8 RGB or gray image of every agent, area-averaged to (h, w), computed from the
+// compact column descriptors (height_line_pu, colour id) the cast kernel leaves — the UInt32 camera view is never read.
+//
+// Contract (include/rcw.h, DESIGN.md §learner view): output row r averages camera rows [⌊r·Hc/h⌋, ⌊(r+1)·Hc/h⌋), output column c
+// image columns [⌊c·N/w⌋, ⌊(c+1)·N/w⌋); a channel is (S + ⌊n/2⌋) / n over the box's n pixels, S the sum of R, G, B = the bytes of
+// 0x00RRGGBB, or of Y = (77 R + 150 G + 29 B + 128) >> 8 for gray.  Image column k of agent a is ceiling on rows [0, pad), its
+// colour on [pad, Hc - pad) and floor from max(pad, Hc - pad) on (pad = column_padding, SR:433-439), so a box's sums follow from
+// interval overlaps — O(box width) a pixel, whatever the box's height.
+//
+// Three kernels:
+//   rcw_view_full_kernel   (h, w) = (Hc, N), one byte a pixel per plane (gray, or RGB in CHW), N a power of two from 16 to 4096,
+//                          Hc < 32768: write-bandwidth bound like the camera fill.  A lane owns 16 image columns of one plane and
+//                          walks rows, one 16-byte store a row; its 16 columns' (ceiling end, floor start, colour value) are loaded once
+//                          an item as 16-bit pairs, and a pair of pixels is two packed subtractions, two shifts and two bit selects.
+//                          The items — (agent, plane, block of rows) — are swept by a small fixed grid in order, so the chip writes one
+//                          compact moving window; the next item's descriptors are loaded before the current item's stores.
+//   rcw_view_agent_kernel  every other size whose per-agent tables fit in LDS (3 words a view column + the box bounds) and whose box
+//                          sums fit 32 bits: a workgroup per agent stages (ceiling end, floor start, colour channels) per column once,
+//                          then a lane per output pixel (all C channels), 32-bit arithmetic on LDS, byte stores the wavefront coalesces.
+//   rcw_view_box_kernel    the rest (huge boxes, huge views): a lane per output pixel reading the descriptor arrays directly, 64-bit
+//                          sums where a box's could pass 2^31.
+#include "rcw_device.h"
+
+#include <algorithm>
+#include <type_traits>
+
+namespace {
+
+constexpr int kViewFullPasses = 8;   // rows a lane stores an item (an item = 8 x 4 KiB of one plane)
+
+// the channel k of a colour: R, G, B bytes, or the luma Y for gray
+template <int C>
+__device__ __forceinline__ uint32_t view_channel(uint32_t colour, int k)
+{
+    const uint32_t R = (colour >> 16) & 0xFFu, G = (colour >> 8) & 0xFFu, B = colour & 0xFFu;
+    if (C == 1) return (77u * R + 150u * G + 29u * B + 128u) >> 8;
+    return k == 0 ? R : (k == 1 ? G : B);
+}
+
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+
+// column_padding in 32-bit arithmetic for Hc < 32768 (a height far below zero pads the whole column, as there)
+__device__ __forceinline__ int padding32(int Hc, int h)
+{
+    return h >= Hc - 1 ? 0 : min((Hc - max(h, -Hc)) >> 1, Hc);
+}
+
+__device__ __forceinline__ uint32_t pack16(int lo, int hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
+
+// 16 columns of one agent: ceiling end, floor start, colour value as 16-bit pairs (column 2j low, 2j + 1 high)
+struct FullCols { uint32_t lo[8], hi[8], vm[8]; };
+
+__device__ __forceinline__ void full_cols(FullCols& f, const int4 (&hq)[4], uint4 ids, int Hc, uint32_t vm4)
+{
+    const uint32_t idw[4] = {ids.x, ids.y, ids.z, ids.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int4 q = hq[j >> 1];
+        const int h0 = (j & 1) ? q.z : q.x, h1 = (j & 1) ? q.w : q.y;
+        const int p0 = padding32(Hc, h0), p1 = padding32(Hc, h1);
+        f.lo[j] = pack16(p0, p1);
+        f.hi[j] = pack16(max(p0, Hc - p0), max(p1, Hc - p1));
+        const uint32_t id0 = (idw[j >> 1] >> ((j & 1) * 16)) & 3u, id1 = (idw[j >> 1] >> ((j & 1) * 16 + 8)) & 3u;
+        f.vm[j] = pack16((int)((vm4 >> (8 * id0)) & 0xFFu), (int)((vm4 >> (8 * id1)) & 0xFFu));
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(kBlock) void rcw_view_full_kernel(const RcwDev p, const int32_t* __restrict__ col_h,
+                                                               const uint8_t* __restrict__ col_c, u32x4* __restrict__ out,
+                                                               int32_t count, const uint8_t* __restrict__ mask, int l_shift,
+                                                               int blocks_per_plane)
+{
+    const int N = p.N, Hc = p.Hc;
+    const int L = 1 << l_shift;                               // lanes a row: N / 16
+    const int tid = threadIdx.x;
+    const int cb = tid & (L - 1);                             // this lane's columns [16 cb, 16 cb + 16)
+    const int rows_pass = kBlock >> l_shift;
+    const int row_lane = tid >> l_shift;
+    const uint32_t items = (uint32_t)count * C * (uint32_t)blocks_per_plane;   // (< 2^31: rcw_launch_view)
+    uint32_t vc[C], vf[C], vm4[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        vc[k] = view_channel<C>(p.ceiling_color, k) * 0x00010001u;
+        vf[k] = view_channel<C>(p.floor_color, k) * 0x00010001u;
+        vm4[k] = 0u;
+#pragma unroll
+        for (int id = 0; id < 4; ++id) vm4[k] |= view_channel<C>(p.colour[id], k) << (8 * id);
+    }
+    uint32_t it = blockIdx.x;
+    int4 hq[4];
+    uint4 ids;
+    auto load = [&](uint32_t item) {                         // the raw descriptors of the item's agent, this lane's columns
+        const long long a = item / ((uint32_t)C * (uint32_t)blocks_per_plane);
+        const int4* hsrc = reinterpret_cast<const int4*>(col_h + a * N + cb * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) hq[q] = hsrc[q];
+        ids = *reinterpret_cast<const uint4*>(col_c + a * N + cb * 16);
+    };
+    if (it < items) load(it);
+    for (; it < items; it += gridDim.x) {
+        const uint32_t pl = it / (uint32_t)blocks_per_plane;
+        const int blk = (int)(it - pl * (uint32_t)blocks_per_plane);
+        const uint32_t a = pl / C;
+        const int ch = (int)(pl - a * C);
+        uint32_t vmc = vm4[0], vcc = vc[0], vfc = vf[0];
+#pragma unroll
+        for (int k = 1; k < C; ++k) if (ch == k) { vmc = vm4[k]; vcc = vc[k]; vfc = vf[k]; }
+        FullCols f;
+        full_cols(f, hq, ids, Hc, vmc);
+        if (it + gridDim.x < items) load(it + gridDim.x);    // (in flight during this item's stores)
+        if (mask != nullptr && mask[a] == 0) continue;
+        u32x4* const dst = out + (unsigned long long)pl * (unsigned long long)Hc * L + cb;
+        const int r0 = blk * rows_pass * kViewFullPasses + row_lane;
+#pragma unroll 2
+        for (int q = 0; q < kViewFullPasses; ++q) {
+            const int r = r0 + q * rows_pass;
+            if (r >= Hc) break;
+            const s16x2 rr = {(short)r, (short)r};
+            uint32_t val[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const s16x2 dc = (rr - __builtin_bit_cast(s16x2, f.lo[j])) >> (short)15;   // 0xFFFF where r < ceiling end
+                const s16x2 df = (rr - __builtin_bit_cast(s16x2, f.hi[j])) >> (short)15;   // 0xFFFF where r < floor start
+                const uint32_t mc = __builtin_bit_cast(uint32_t, dc), mf = __builtin_bit_cast(uint32_t, df);
+                const uint32_t t = (mf & f.vm[j]) | (~mf & vfc);
+                val[j] = (mc & vcc) | (~mc & t);
+            }
+            u32x4 v;
+            v.x = __builtin_amdgcn_perm(val[1], val[0], 0x06040200u);
+            v.y = __builtin_amdgcn_perm(val[3], val[2], 0x06040200u);
+            v.z = __builtin_amdgcn_perm(val[5], val[4], 0x06040200u);
+            v.w = __builtin_amdgcn_perm(val[7], val[6], 0x06040200u);
+            store16<false>(dst + (long long)r * L, v);
+        }
+    }
+}
+
+// (S + ⌊n/2⌋) / n: the Float32 quotient corrected by one either way (fast_div, rcw_device.h: S + n/2 < 2^31, quotient <= 255)
+__device__ __forceinline__ uint32_t view_div(uint32_t s, uint32_t n)
+{
+    return (uint32_t)fast_div((int)(s + (n >> 1)), (int)n, __builtin_amdgcn_rcpf((float)n));
+}
+__device__ __forceinline__ uint32_t view_div(unsigned long long s, unsigned long long n) { return (uint32_t)((s + (n >> 1)) / n); }
+
+template <int C, bool HWC, bool WIDE>
+__global__ __launch_bounds__(kBlock) void rcw_view_box_kernel(const RcwDev p, const RcwView v, const int32_t* __restrict__ col_h,
+                                                              const uint8_t* __restrict__ col_c, int32_t count,
+                                                              const uint8_t* __restrict__ mask, uint8_t* __restrict__ out)
+{
+    typedef typename std::conditional<WIDE, unsigned long long, uint32_t>::type Acc;
+    const int N = p.N, Hc = p.Hc, h = v.h, w = v.w;
+    const long long hw = (long long)h * w;
+    const long long total = (long long)count * hw;
+    const long long S = (long long)gridDim.x * kBlock;
+    long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= total) return;
+    // (agent, row, column) of this lane's pixel, moved on by S pixels a trip without a division
+    long long a = i / hw;
+    int r = (int)((i - a * hw) / w), c = (int)(i - a * hw - (long long)r * w);
+    const long long Sa = S / hw;
+    const int Sr = (int)((S - Sa * hw) / w), Sc = (int)(S - Sa * hw - (long long)Sr * w);
+    uint32_t vc[C], vf[C], vm4[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        vc[k] = view_channel<C>(p.ceiling_color, k);
+        vf[k] = view_channel<C>(p.floor_color, k);
+        vm4[k] = 0u;
+#pragma unroll
+        for (int id = 0; id < 4; ++id) vm4[k] |= view_channel<C>(p.colour[id], k) << (8 * id);
+    }
+    for (; i < total; i += S) {
+        if (mask == nullptr || mask[a] != 0) {
+            const int r0 = v.rows[r], r1 = v.rows[r + 1], c0 = v.cols[c], c1 = v.cols[c + 1];
+            const int nr = r1 - r0;
+            Acc acc[C];
+#pragma unroll
+            for (int k = 0; k < C; ++k) acc[k] = 0;
+            const int32_t* const hp = col_h + a * N;
+            const uint8_t* const cp = col_c + a * N;
+#pragma unroll 4
+            for (int j = c0; j < c1; ++j) {
+                const int pad = column_padding(Hc, hp[j]);
+                const uint32_t sh = 8u * (cp[j] & 3u);
+                const int nc = max(0, min(r1, pad) - r0);                    // ceiling rows [0, pad)
+                const int nf = max(0, r1 - max(r0, max(pad, Hc - pad)));    // floor rows [max(pad, Hc - pad), Hc)
+                const int nm = nr - nc - nf;                                 // the colour's rows between
+#pragma unroll
+                for (int k = 0; k < C; ++k)
+                    acc[k] += (Acc)nc * vc[k] + (Acc)nm * ((vm4[k] >> sh) & 0xFFu) + (Acc)nf * vf[k];
+            }
+            const Acc n = (Acc)nr * (Acc)(c1 - c0);
+            if (HWC) {
+                uint8_t* const o = out + ((unsigned long long)(a * h + r) * w + c) * C;
+#pragma unroll
+                for (int k = 0; k < C; ++k) o[k] = (uint8_t)view_div(acc[k], n);
+            } else {
+#pragma unroll
+                for (int k = 0; k < C; ++k) out[((unsigned long long)(a * C + k) * h + r) * w + c] = (uint8_t)view_div(acc[k], n);
+            }
+        }
+        c += Sc; if (c >= w) { c -= w; r += 1; }
+        r += Sr; if (r >= h) { r -= h; a += 1; }
+        a += Sa;
+    }
+}
+
+// A workgroup per agent for the reduced sizes whose tables fit in LDS: the agent's columns are turned into (ceiling end, floor start,
+// packed colour channels) once, the box bounds staged beside them, and every output pixel of the agent is then 32-bit arithmetic on LDS.
+template <int C, bool HWC>
+__global__ __launch_bounds__(kBlock) void rcw_view_agent_kernel(const RcwDev p, const RcwView v, const int32_t* __restrict__ col_h,
+                                                                const uint8_t* __restrict__ col_c, const uint8_t* __restrict__ mask,
+                                                                uint8_t* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t lds_v[];
+    const int N = p.N, Hc = p.Hc, h = v.h, w = v.w, tid = threadIdx.x;
+    const long long a = blockIdx.x;
+    if (mask != nullptr && mask[a] == 0) return;
+    int32_t* const s_pad = lds_v;
+    int32_t* const s_fs = s_pad + N;
+    uint32_t* const s_vm = reinterpret_cast<uint32_t*>(s_fs + N);        // the colour's C channel values, a byte each
+    int32_t* const s_rows = reinterpret_cast<int32_t*>(s_vm + N);
+    int32_t* const s_cols = s_rows + h + 1;
+    uint32_t vc[C], vf[C], vm4[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        vc[k] = view_channel<C>(p.ceiling_color, k);
+        vf[k] = view_channel<C>(p.floor_color, k);
+        vm4[k] = 0u;
+#pragma unroll
+        for (int id = 0; id < 4; ++id) vm4[k] |= view_channel<C>(p.colour[id], k) << (8 * id);
+    }
+    for (int j = tid; j < N; j += kBlock) {
+        const int pad = column_padding(Hc, col_h[a * N + j]);
+        const uint32_t sh = 8u * (col_c[a * N + j] & 3u);
+        uint32_t m = 0u;
+#pragma unroll
+        for (int k = 0; k < C; ++k) m |= ((vm4[k] >> sh) & 0xFFu) << (8 * k);
+        s_pad[j] = pad; s_fs[j] = max(pad, Hc - pad); s_vm[j] = m;
+    }
+    for (int j = tid; j <= h; j += kBlock) s_rows[j] = v.rows[j];
+    for (int j = tid; j <= w; j += kBlock) s_cols[j] = v.cols[j];
+    __syncthreads();
+    const int hw = h * w;
+    const float inv_w = 1.0f / (float)w;
+    uint8_t* const o = out + (unsigned long long)a * C * hw;
+    for (int i = tid; i < hw; i += kBlock) {
+        const int r = fast_div(i, w, inv_w), c = i - r * w;                   // (hw < 2^23: rcw_launch_view)
+        const int r0 = s_rows[r], r1 = s_rows[r + 1], c0 = s_cols[c], c1 = s_cols[c + 1];
+        const int nr = r1 - r0;
+        uint32_t acc[C];
+#pragma unroll
+        for (int k = 0; k < C; ++k) acc[k] = 0u;
+        for (int j = c0; j < c1; ++j) {
+            const int pad = s_pad[j], fs = s_fs[j];
+            const uint32_t m = s_vm[j];
+            const uint32_t nc = (uint32_t)max(0, min(r1, pad) - r0);
+            const uint32_t nf = (uint32_t)max(0, r1 - max(r0, fs));
+            const uint32_t nm = (uint32_t)nr - nc - nf;
+#pragma unroll
+            for (int k = 0; k < C; ++k) acc[k] += nc * vc[k] + nm * ((m >> (8 * k)) & 0xFFu) + nf * vf[k];
+        }
+        const uint32_t n = (uint32_t)nr * (uint32_t)(c1 - c0);
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            const uint8_t q = (uint8_t)view_div(acc[k], n);
+            if (HWC) o[(unsigned)i * C + k] = q; else o[(unsigned)(k * hw + i)] = q;
+        }
+    }
+}
+
+}  // namespace
+
+int rcw_view_full_eligible(const RcwDev& p, int C, int hwc)
+{
+    return (C == 1 || !hwc) && p.N >= 16 && p.N <= 4096 && (p.N & (p.N - 1)) == 0 && p.Hc < 32768 ? 1 : 0;
+}
+
+hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,
+                           const uint8_t* mask_dev, uint8_t* out, hipStream_t s)
+{
+    if (count < 1) return hipSuccess;
+    const bool aligned = (((uintptr_t)col_h | (uintptr_t)col_c | (uintptr_t)out) & 15u) == 0;
+    if (v.full_ok && aligned && (long long)count * v.C * ((p.Hc + 7) / 8) < (1ll << 31)) {
+        int l_shift = 0;
+        while ((16 << l_shift) < p.N) ++l_shift;
+        const int rows_item = (kBlock >> l_shift) * kViewFullPasses;
+        const int blocks_per_plane = (p.Hc + rows_item - 1) / rows_item;
+        const long long items = (long long)count * v.C * blocks_per_plane;
+        const int grid = (int)std::min<long long>(items, 4ll * p.fill_grid);
+        u32x4* const o4 = reinterpret_cast<u32x4*>(out);
+        if (v.C == 1) hipLaunchKernelGGL(rcw_view_full_kernel<1>, dim3(grid), dim3(kBlock), 0, s, p, col_h, col_c, o4, count, mask_dev, l_shift, blocks_per_plane);
+        else          hipLaunchKernelGGL(rcw_view_full_kernel<3>, dim3(grid), dim3(kBlock), 0, s, p, col_h, col_c, o4, count, mask_dev, l_shift, blocks_per_plane);
+        return hipGetLastError();
+    }
+    const size_t lds = ((size_t)3 * p.N + v.h + v.w + 2) * sizeof(int32_t);
+    if (!v.wide && (long long)v.h * v.w < (1ll << 23) && lds <= 64 * 1024) {
+#define RCW_VIEW_AGENT(CC, HH) hipLaunchKernelGGL((rcw_view_agent_kernel<CC, HH>), dim3(count), dim3(kBlock), lds, s, p, v, col_h, col_c, mask_dev, out)
+        if (v.C == 1) RCW_VIEW_AGENT(1, false);
+        else if (v.hwc) RCW_VIEW_AGENT(3, true);
+        else RCW_VIEW_AGENT(3, false);
+#undef RCW_VIEW_AGENT
+        return hipGetLastError();
+    }
+    const long long total = (long long)count * v.h * v.w;
+    const int grid = (int)std::min<long long>((total + kBlock - 1) / kBlock, 1ll << 24);   // (a lane a pixel: every load of the batch in flight at once)
+#define RCW_VIEW_BOX(CC, HH, WW) hipLaunchKernelGGL((rcw_view_box_kernel<CC, HH, WW>), dim3(grid), dim3(kBlock), 0, s, p, v, col_h, col_c, count, mask_dev, out)
+    if (v.C == 1) { if (v.wide) RCW_VIEW_BOX(1, false, true); else RCW_VIEW_BOX(1, false, false); }
+    else if (v.hwc) { if (v.wide) RCW_VIEW_BOX(3, true, true); else RCW_VIEW_BOX(3, true, false); }
+    else { if (v.wide) RCW_VIEW_BOX(3, false, true); else RCW_VIEW_BOX(3, false, false); }
+#undef RCW_VIEW_BOX
+    return hipGetLastError();
+}

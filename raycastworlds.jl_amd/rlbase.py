@@ -8,8 +8,13 @@ from . import single_room as _sr
 class RLBaseEnv:
     """`struct RLBaseEnv{E} <: RLBase.AbstractEnv; env::E; end` (rlbase.jl:1-3)."""
 
-    def __init__(self, env: "_sr.SingleRoom"):
+    def __init__(self, env: "_sr.SingleRoom", observation: str = "camera_view"):
+        """`observation`: what `state(env)` returns — "camera_view" (the reference's, default) or "learner_view" (the uint8
+        view `env.set_learner_view` configured)."""
+        if observation not in ("camera_view", "learner_view"):
+            raise ValueError(f"observation must be \"camera_view\" or \"learner_view\" (got {observation!r})")
         self.env = env
+        self.observation = observation
 
     def __call__(self, action):
         """`(env::RLBaseEnv)(action) = RCW.act!(env.env, action)` SR:581."""
@@ -23,8 +28,14 @@ class RLBaseEnv:
 
 def state(env: RLBaseEnv):
     """`RLBase.state(env)` SR:576: `env.env.camera_view`, ALIASED device memory (no copy, no synchronisation);
-    it is overwritten in place by the next action, as in the reference.  The same object until `bind_obs` moves it."""
+    it is overwritten in place by the next action, as in the reference.  The same object until `bind_obs` moves it.
+    With `observation="learner_view"`: `env.env.learner_view`, aliased the same way."""
     e = env.env
+    if getattr(env, "observation", "camera_view") == "learner_view":
+        return e.learner_view
+    if getattr(e, "_view_only", False):
+        raise RuntimeError("the environment's steps do not render the camera view (set_learner_view(camera_view=False)): "
+                           "use RLBaseEnv(env, observation=\"learner_view\"), or update_camera_view_(env) for a frame")
     cv = getattr(e, "_state_alias", None)
     if cv is None or cv.ptr != e._obs_ptr():
         cv = e._state_alias = e.camera_view

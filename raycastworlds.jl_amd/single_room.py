@@ -457,7 +457,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_state_alias", "_constant_action_buffers"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -555,6 +555,88 @@ class SingleRoom:
         cross = self._order_behind_torch()
         self._check(self._lib.rcw_expand_columns(self._h, C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), n,
                                                  C.c_void_p(out.data_ptr())))
+        if cross:
+            self._release_after_use(h, c, out)
+        return out
+
+    # ---- the learner view (rcw_set_learner_view) ------------------------------------------------------------------
+    def set_learner_view(self, format: Optional[str] = "gray", size=None, layout: str = "chw", camera_view: bool = True) -> None:
+        """Also render a uint8 observation a learner consumes at every reset / set_state / step: `format` "gray" or "rgb"
+        (None: off), `size` (h, w) with h <= height_camera_view_pu and w <= num_rays (None: full size; each output pixel is
+        the rounded mean of its box of camera pixels), `layout` "chw" (B, C, h, w) or "hwc" (B, h, w, C).
+        `camera_view=False` (RCW_VIEW_ONLY): steps skip the uint32 camera view — `camera_view` then holds the last frames
+        rendered until `update_camera_view_(env)`.  Renders the current state at once."""
+        formats = {None: _capi.RCW_VIEW_OFF, "rgb": _capi.RCW_VIEW_RGB8, "gray": _capi.RCW_VIEW_GRAY8}
+        layouts = {"chw": _capi.RCW_VIEW_CHW, "hwc": _capi.RCW_VIEW_HWC}
+        if format not in formats:
+            raise ValueError(f"unknown learner view format {format!r} (\"gray\", \"rgb\" or None)")
+        if layout not in layouts:
+            raise ValueError(f"unknown learner view layout {layout!r} (\"chw\" or \"hwc\")")
+        if format is None and not camera_view:
+            raise ValueError("camera_view=False needs a learner view format")
+        h, w = (self.cfg.height_camera_view_pu, self.cfg.num_rays) if size is None else (int(size[0]), int(size[1]))
+        flags = 0 if camera_view else _capi.RCW_VIEW_ONLY
+        self._check(self._lib.rcw_set_learner_view(self._h, formats[format], layouts[layout], h, w, flags))
+        self._view_only = not camera_view                # (RLBase.state refuses the stale camera view of such a handle)
+        self.__dict__.pop("_learner_view_alias", None)
+
+    def learner_view_info(self) -> dict:
+        """The current learner view settings (rcw_learner_view_info): format, layout, size, camera_view."""
+        v = [C.c_int32() for _ in range(5)]
+        self._check(self._lib.rcw_learner_view_info(self._h, *[C.byref(x) for x in v]))
+        fmt, lay, h, w, flags = (x.value for x in v)
+        return {"format": {_capi.RCW_VIEW_OFF: None, _capi.RCW_VIEW_RGB8: "rgb", _capi.RCW_VIEW_GRAY8: "gray"}[fmt],
+                "layout": "hwc" if lay == _capi.RCW_VIEW_HWC else "chw", "size": (h, w),
+                "camera_view": not (flags & _capi.RCW_VIEW_ONLY)}
+
+    def _learner_view_shape(self, n: int, info: Optional[dict] = None):
+        info = info or self.learner_view_info()
+        if info["format"] is None:
+            raise RuntimeError("this environment has no learner view: call set_learner_view first")
+        c = 3 if info["format"] == "rgb" else 1
+        h, w = info["size"]
+        return (n, c, h, w) if info["layout"] == "chw" else (n, h, w, c)
+
+    @property
+    def learner_view(self) -> DeviceArray:
+        """The learner view batch, aliased device memory: uint8 (B, C, h, w) or (B, h, w, C), rewritten in place by every
+        step in stream order (`.torch(sync=False)` for a consumer on the GPU)."""
+        shape = self._learner_view_shape(self.batch)
+        p = C.c_void_p()
+        self._check(self._lib.rcw_learner_view_device_ptr(self._h, C.byref(p)))
+        alias = self.__dict__.get("_learner_view_alias")
+        if alias is None or alias.ptr != p.value or alias.shape != shape:
+            alias = self._learner_view_alias = DeviceArray(p.value, shape, np.uint8, self, self._sync,
+                                                           host_getter=lambda: self.learner_view_host())
+        return alias
+
+    def learner_view_host(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Agents [first, first + count) of the learner view, copied to the host (waits for the engine's stream)."""
+        n = self.batch - first if count is None else count
+        out = np.empty(self._learner_view_shape(n), dtype=np.uint8)
+        self._check(self._lib.rcw_learner_view_copy(self._h, _as_ptr(out), first, n))
+        return out
+
+    def expand_columns_view(self, height_line_pu, colour_id, out=None):
+        """Descriptors (CUDA tensors (n, N) int32 / uint8) -> this environment's learner view of them, a uint8 torch CUDA
+        tensor in the view's shape (rcw_expand_columns_view).  Stream-ordered like `expand_columns`."""
+        import torch
+
+        n = int(height_line_pu.shape[0])
+        if tuple(height_line_pu.shape) != (n, self.cfg.num_rays) or tuple(colour_id.shape) != (n, self.cfg.num_rays):
+            raise ValueError("descriptor shape must be (n, num_rays)")
+        if height_line_pu.dtype != torch.int32 or colour_id.dtype != torch.uint8:
+            raise ValueError("descriptors must be int32 / uint8")
+        shape = self._learner_view_shape(n)
+        h = height_line_pu.contiguous()
+        c = colour_id.contiguous()
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device}")
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape}")
+        cross = self._order_behind_torch()
+        self._check(self._lib.rcw_expand_columns_view(self._h, C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), n,
+                                                      C.c_void_p(out.data_ptr())))
         if cross:
             self._release_after_use(h, c, out)
         return out

@@ -1,0 +1,87 @@
+"""Env-steps/s of the learner view's cases at BASELINE cfg-2 (8x8 map, 256 view columns, 4096 agents), timed like bench.py:
+device-resident U{1..4} actions, HIP events on the engine's stream around `--steps` steps after `--warmup`.  Each case runs
+`--repeats` times (interleaved, so drift hits every case alike); the JSON line carries every run, the median and the range.
+
+    python tools/learner_view_bench.py --steps 200 --warmup 20 --repeats 5
+
+Cases: plain (the camera view only), plus_gray84 (camera view + gray 84x84), only_gray84 / only_gray_full / only_rgb_chw_full
+(RCW_VIEW_ONLY: the cast kernel and the view kernel).  The view kernel's own duration comes from a separate rocprofv3 run
+(--case NAME runs one case alone, for `rocprofv3 --kernel-trace --stats -- python tools/learner_view_bench.py --case ...`)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CASES = {
+    "plain": None,
+    "plus_gray84": dict(format="gray", size=(84, 84), layout="chw", camera_view=True),
+    "only_gray84": dict(format="gray", size=(84, 84), layout="chw", camera_view=False),
+    "only_gray_full": dict(format="gray", size=None, layout="chw", camera_view=False),
+    "only_rgb_chw_full": dict(format="rgb", size=None, layout="chw", camera_view=False),
+}
+
+
+def run_case(RCW, torch, name, batch, steps, warmup, actions):
+    env = RCW.SingleRoomModule.SingleRoom(batch=batch, seed=0, auto_reset=True, height_tile_map_tu=8, width_tile_map_tu=8,
+                                          num_rays=256)
+    if CASES[name] is not None:
+        env.set_learner_view(**CASES[name])
+    stream = torch.cuda.Stream()
+    env.set_stream(stream.cuda_stream)
+    with torch.cuda.stream(stream):
+        for s in range(warmup):
+            RCW.act_(env, actions[s % len(actions)])
+        stream.synchronize()
+        env.timer_start()
+        for s in range(steps):
+            RCW.act_(env, actions[(warmup + s) % len(actions)])
+        ms = env.timer_stop()
+        stream.synchronize()
+    form = env.step_form()
+    try:
+        env.sync()
+    except IndexError:
+        env.clear_error()
+    env.close()
+    return ms, form
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--case", choices=sorted(CASES), default=None, help="run this case only (for a profiler)")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+
+    import raycastworlds_jl_amd as RCW
+
+    g = torch.Generator().manual_seed(0)
+    actions = [torch.randint(1, 5, (args.batch,), dtype=torch.uint8, generator=g).cuda() for _ in range(64)]
+    names = [args.case] if args.case else list(CASES)
+    runs = {n: [] for n in names}
+    forms = {}
+    for _ in range(args.repeats):
+        for n in names:
+            ms, forms[n] = run_case(RCW, torch, n, args.batch, args.steps, args.warmup, actions)
+            runs[n].append(args.batch * args.steps / (ms / 1000.0))
+    out = {"metric": "env-steps/s", "config": "cfg-2: 8x8 map, 256 view columns, 256 rows", "batch": args.batch,
+           "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats, "cases": {}}
+    for n in names:
+        r = np.array(runs[n])
+        out["cases"][n] = {"median": float(np.median(r)), "min": float(r.min()), "max": float(r.max()),
+                           "us_per_step_median": float(args.batch / np.median(r) * 1e6), "step_form": forms[n],
+                           "runs": [float(x) for x in r]}
+    if "plain" in runs and "only_gray84" in runs:
+        out["only_gray84_over_plain"] = out["cases"]["only_gray84"]["median"] / out["cases"]["plain"]["median"]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
