@@ -13,12 +13,12 @@
         RcwDev dd = d;
         dd.top_epoch = ++h->top_epoch;                       // (the counters wrap with it: the comparison is modulo 2^32)
         dd.top_signal = 1; dd.top_follow = 1;
-        if ((e = hipEventRecord(h->ev_top_fork, h->stream)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(h->top_stream, h->ev_top_fork, 0)) != hipSuccess) return e;
-        e = rcw_launch_top_draw(dd, nullptr, 0, d.B, h->top_stream, beside ? 0 : d.top_draw_block_alone);
-        const hipError_t rec = hipEventRecord(h->ev_top_join[0], h->top_stream);
+        if ((e = hipEventRecord(h->ev_top_fork.get(), h->stream)) != hipSuccess) return e;
+        if ((e = hipStreamWaitEvent(h->top_stream.get(), h->ev_top_fork.get(), 0)) != hipSuccess) return e;
+        e = rcw_launch_top_draw(dd, nullptr, 0, d.B, h->top_stream.get(), beside ? 0 : d.top_draw_block_alone);
+        const hipError_t rec = hipEventRecord(h->ev_top_join[0].get(), h->top_stream.get());
         if (e == hipSuccess) e = between(h->stream);
         if (e == hipSuccess) e = rcw_launch_top_store(dd, nullptr, 0, d.B, h->stream);
-        if (rec == hipSuccess) { const hipError_t w = hipStreamWaitEvent(h->stream, h->ev_top_join[0], 0); if (e == hipSuccess) e = w; }
+        if (rec == hipSuccess) { const hipError_t w = hipStreamWaitEvent(h->stream, h->ev_top_join[0].get(), 0); if (e == hipSuccess) e = w; }
         return e == hipSuccess ? rec : e;
     }

@@ -1,5 +1,5 @@
 // Development build only (-DRCW_DEV_SWITCHES): RCW_TOP_FOLLOW — the counters' block size and where the store kernel may follow the draw kernel.  A fragment of rcw_api.hip (plan_top_view), included where it stood.
-        d.top_flags = (uint32_t*)h->d_top_flags;
+        d.top_flags = h->d_top_flags.get<uint32_t>();
         while ((((size_t)h->B + ((size_t)1 << d.top_blk_shift) - 1) >> d.top_blk_shift) > 1024) ++d.top_blk_shift;   // at most 1024 blocks: sixteen looks of a wavefront see them all
         // the store kernel follows the draw kernel (no event between them) where their workgroups fit on a CU together:
         // bit 0 inside a step (side-stream form, one run), bit 1 in rcw_update_top_view alone

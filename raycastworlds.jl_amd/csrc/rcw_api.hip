@@ -3,6 +3,7 @@
 // operation and must be compiled with -ffp-contract=off (see Makefile).
 #include "../../include/rcw.h"
 #include "rcw_kernels.h"
+#include "rcw_owned.h"
 
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -43,12 +45,16 @@ int fail_at(int line, int code, const char* fmt, A... args)
 #define fail(...) fail_at(__LINE__, __VA_ARGS__)
 #endif
 
+// The text of a failed runtime call, which is thereby REPORTED: the runtime also keeps the code as the thread's last error, and the launchers'
+// hipGetLastError() would hand it out as their own (a create that ran out of memory made the next rcw_create fail in its first launch).
+const char* hip_failure(hipError_t e) { (void)hipGetLastError(); return hipGetErrorString(e); }
+
 #define RCW_HIP(expr)                                                                   \
     do {                                                                                \
         hipError_t e_ = (expr);                                                         \
         if (e_ != hipSuccess)                                                           \
             return fail(e_ == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, \
-                        "%s failed: %s", #expr, hipGetErrorString(e_));                 \
+                        "%s failed: %s", #expr, hip_failure(e_));                 \
     } while (0)
 
 }  // namespace
@@ -62,43 +68,38 @@ extern "C" __attribute__((visibility("default"))) int rcw_dev_fail_sites(unsigne
 }
 #endif
 
+// OWNERSHIP: every device buffer, pinned buffer, stream and event of a handle is a member of one of rcw_owned.h's types; nothing else frees
+// them.  ~rcw_handle waits for all the handle's streams and then lets the members go in reverse order of declaration: the two STREAMS ARE
+// DECLARED FIRST, so buffers and events go before the streams that used them.  A live handle gives a buffer up through replace_buffers().
 struct rcw_handle {
     rcw_config cfg{};
-    int32_t B = 0, device = 0, nchunks = 0, num_cus = 256;
+    int32_t B = 0, device = 0, nchunks = 0;
     RcwHw hw{256, 160 * 1024, 32};     // the device's CUs, LDS bytes and wavefront slots a CU (hipDeviceProp_t: rcw_create)
     RcwDev dev{};
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    RcwStream own_stream, top_stream;  // (top_stream: the side stream of the two-kernel top view)
+    hipStream_t stream = nullptr;      // the caller's (rcw_set_stream) or own_stream: not owned
+    RcwEvent ev_start, ev_stop;
     // device allocations
-    void* d_pos = nullptr; void* d_dir = nullptr; void* d_goal = nullptr; void* d_reward = nullptr;
-    void* d_done = nullptr; void* d_episode = nullptr; void* d_tile_map = nullptr;
-    void* d_dir_table = nullptr; void* d_ray_table = nullptr; void* d_obs = nullptr;
-    void* d_col_h = nullptr; void* d_col_c = nullptr; void* d_err = nullptr; void* d_status = nullptr;
-    void* d_top_view = nullptr;
+    RcwBuf d_pos, d_dir, d_goal, d_reward, d_done, d_episode, d_tile_map, d_dir_table, d_ray_table, d_obs, d_col_h, d_col_c, d_err, d_status, d_top_view;
     // two-kernel top view: planes / player pixels / tile codes in HBM, the side stream the draw kernel runs on
-    void* d_top_plane = nullptr; void* d_top_hdr = nullptr; void* d_top_codes = nullptr;
-    void* d_top_flags = nullptr; uint32_t top_epoch = 0;   // the store kernel follows the draw kernel (dev/top_follow_publish.inc)
+    RcwBuf d_top_plane, d_top_hdr, d_top_codes;
+    RcwBuf d_top_flags; uint32_t top_epoch = 0;   // the store kernel follows the draw kernel (dev/top_follow_publish.inc)
     // Several draw workgroups an agent (top_parts > 1) OR their bits into the agent's plane in HBM, and only rcw_top_store_kernel — which reads
     // every plane word exactly once — leaves the zero the next drawing needs: a drawing whose store did not follow (a failed launch in
     // between, the development build's skip-the-store switch) leaves bits behind that every later frame would carry.  Set in front of such a
     // drawing, cleared behind its store's launch; a drawing that finds it set clears the planes first.
     bool top_plane_dirty = false;
-    hipStream_t top_stream = nullptr;
-    hipEvent_t ev_top_fork = nullptr;
-    hipEvent_t ev_top_join[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // one per run of agents
-    void* d_actions = nullptr; void* d_mask = nullptr;
-    void* d_in_goal = nullptr; void* d_in_pos = nullptr; void* d_in_dir = nullptr;
-    int32_t* h_err = nullptr;   // pinned
-    uint8_t* h_actions[2] = {nullptr, nullptr};   // pinned staging ring for rcw_step
-    hipEvent_t ev_actions[2] = {nullptr, nullptr};
+    RcwEvent ev_top_fork, ev_top_join[8];   // (a join event per run of agents)
+    RcwBuf d_actions, d_mask, d_in_goal, d_in_pos, d_in_dir;
+    RcwPinned h_err, h_actions[2];     // the error word (int32_t); the staging ring of rcw_step (uint8_t)
+    RcwEvent ev_actions[2];
     int action_slot = 0;
     bool profiling = false;
     int step_pieces = 1;               // development experiment only (RCW_STEP_PIECES)
-    void* d_step_flags = nullptr; void* d_step_hc = nullptr; uint32_t step_epoch = 0;   // development experiment only (RCW_STEP_FUSED)
+    RcwBuf d_step_flags, d_step_hc; uint32_t step_epoch = 0;   // development experiment only (RCW_STEP_FUSED)
     // the one-launch step (rcw_fill256_cast_kernel): two buffers of [B][5][N] packed column words — d_spec[spec_cur] holds the frames of the
     // CURRENT state (slot 0) and of its four successors (slots 1..4), written by the last casting launch; spec_primed: for every agent
-    void* d_spec[2] = {nullptr, nullptr}; int spec_cur = 0; bool spec_primed = false;
+    RcwBuf d_spec[2]; int spec_cur = 0; bool spec_primed = false;
     int spec_on = 0;                   // a step is ONE launch (rcw_fill256_cast_kernel)
     // The (height_line_pu, colour id) descriptors of the current frames (d_col_h / d_col_c) are what the two-launch step hands from its cast
     // kernel to its fill kernel; the one-launch step's fill reads the slots instead, and every store of the casting workgroups costs the
@@ -109,14 +110,14 @@ struct rcw_handle {
     int step_form_want = 0;            // rcw_set_step_form: 0 = the rule, or RCW_STEP_TWO_LAUNCHES / RCW_STEP_ONE_LAUNCH
     bool step_captured = false;        // a step of this handle was captured into a graph: it keeps the two-launch form from then on
     int prof_count = 0;
-    std::vector<hipEvent_t> prof_ev;   // 4 per recorded step: start | after cast | after top view | after fill
-    void* d_rays[4] = {nullptr, nullptr, nullptr, nullptr};   // rcw_rays scratch (grow-only)
+    std::vector<RcwEvent> prof_ev;     // 4 per recorded step: start | after cast | after top view | after fill
+    RcwBuf d_rays[4];                  // rcw_rays scratch (grow-only)
     size_t rays_cap[4] = {0, 0, 0, 0};
     size_t reward_size = sizeof(float);
     // RCCL (loaded on demand): the observation gather
     void* comm = nullptr;              // ncclComm_t
     int32_t comm_rank = 0, comm_world = 0;
-    void* d_gather_h = nullptr; void* d_gather_c = nullptr;   // gathered descriptors (B * world columns)
+    RcwBuf d_gather_h, d_gather_c;     // gathered descriptors (B * world columns)
     bool real64 = false;            // world-unit type T = Float64 (cfg.world_unit_bits = 64)
     size_t real_size = sizeof(float);
     std::vector<float> dir_table;   // (2, nd)        T = Float32
@@ -125,8 +126,9 @@ struct rcw_handle {
     std::vector<double> ray_table64;
     // the learner view (rcw_set_learner_view): settings, the view batch and its box tables (rows [h + 1] then columns [w + 1])
     int32_t view_fmt = RCW_VIEW_OFF, view_layout = RCW_VIEW_CHW, view_h = 0, view_w = 0, view_flags = 0;
-    void* d_view = nullptr; void* d_view_tab = nullptr;
+    RcwBuf d_view, d_view_tab;
     RcwView view{};
+    ~rcw_handle();
 };
 
 namespace {
@@ -149,7 +151,7 @@ hipError_t launch_top_view(rcw_handle* h, const uint8_t* mask_dev, bool beside, 
         return between(h->stream);
     }
     if (d.top_parts > 1) {                                   // (see rcw_handle::top_plane_dirty; every order below forks from the handle's stream behind this)
-        if (h->top_plane_dirty && (e = hipMemsetAsync(h->d_top_plane, 0, rcw_top_plane_bytes(d), h->stream)) != hipSuccess) return e;
+        if (h->top_plane_dirty && (e = hipMemsetAsync(h->d_top_plane.get(), 0, rcw_top_plane_bytes(d), h->stream)) != hipSuccess) return e;
         h->top_plane_dirty = true;
         struct Clean { rcw_handle* h; hipError_t* e; ~Clean() { if (*e == hipSuccess && !(h->dev.top_debug & 2)) h->top_plane_dirty = false; } };
         hipError_t result = hipErrorUnknown;
@@ -189,37 +191,37 @@ hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool 
         // against 6 us after the cast kernel's end), and the store kernel behind the join another 13 us after the drawing's end — with the
         // drawing on the side stream both lie on the step's critical path wherever the drawing outlasts the fill.  This way the late start
         // is the fill's, which has the drawing's whole time to spare, and the join at the end waits for a fill that ended long ago.
-        if ((e = hipEventRecord(h->ev_top_fork, h->stream)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(h->top_stream, h->ev_top_fork, 0)) != hipSuccess) return e;
-        e = between(h->top_stream);                              // (its profiling event is recorded on that stream too)
-        const hipError_t rec = hipEventRecord(h->ev_top_join[0], h->top_stream);
+        if ((e = hipEventRecord(h->ev_top_fork.get(), h->stream)) != hipSuccess) return e;
+        if ((e = hipStreamWaitEvent(h->top_stream.get(), h->ev_top_fork.get(), 0)) != hipSuccess) return e;
+        e = between(h->top_stream.get());                              // (its profiling event is recorded on that stream too)
+        const hipError_t rec = hipEventRecord(h->ev_top_join[0].get(), h->top_stream.get());
         if (e == hipSuccess) e = rcw_launch_top_draw(d, mask_dev, 0, d.B, h->stream);
         if (e == hipSuccess) e = rcw_launch_top_store(d, mask_dev, 0, d.B, h->stream);
-        if (rec == hipSuccess) { const hipError_t w = hipStreamWaitEvent(h->stream, h->ev_top_join[0], 0); if (e == hipSuccess) e = w; }
+        if (rec == hipSuccess) { const hipError_t w = hipStreamWaitEvent(h->stream, h->ev_top_join[0].get(), 0); if (e == hipSuccess) e = w; }
         return e == hipSuccess ? rec : e;
     }
-    if ((e = hipEventRecord(h->ev_top_fork, h->stream)) != hipSuccess) return e;
-    if ((e = hipStreamWaitEvent(h->top_stream, h->ev_top_fork, 0)) != hipSuccess) return e;
+    if ((e = hipEventRecord(h->ev_top_fork.get(), h->stream)) != hipSuccess) return e;
+    if ((e = hipStreamWaitEvent(h->top_stream.get(), h->ev_top_fork.get(), 0)) != hipSuccess) return e;
     // The batch goes in d.top_runs runs of agents (one, unless the batch is several GiB of top view AND the drawing is
     // long against the camera fill): the side stream draws run after run without waiting for anything, the handle's
     // stream stores run r as soon as it is drawn — so what of the drawing does not fit beside the camera fill runs beside
     // the (HBM-bound) storing of earlier runs.
     // From here on the side stream may hold work: whatever fails, the handle's stream joins it again (every recorded
     // event is waited for), so that nothing runs on the side stream that the handle's stream does not wait for — a
-    // later rcw_destroy / rcw_set_stream synchronises the handle's stream only, and a capture must end joined.
+    // later rcw_set_stream synchronises the handle's stream only, and a capture must end joined.
     const int runs = d.top_runs > 1 ? d.top_runs : 1;
     int recorded = 0;
     for (int r = 0; r < runs && e == hipSuccess; ++r) {
         const int first = (int)((long long)d.B * r / runs), count = (int)((long long)d.B * (r + 1) / runs) - first;
-        e = rcw_launch_top_draw(d, mask_dev, first, count, h->top_stream);
-        const hipError_t rec = hipEventRecord(h->ev_top_join[r], h->top_stream);    // (also after a failed launch: earlier runs' draws are queued)
+        e = rcw_launch_top_draw(d, mask_dev, first, count, h->top_stream.get());
+        const hipError_t rec = hipEventRecord(h->ev_top_join[r].get(), h->top_stream.get());    // (also after a failed launch: earlier runs' draws are queued)
         if (rec == hipSuccess) recorded = r + 1;
         if (e == hipSuccess) e = rec;
     }
     if (e == hipSuccess) e = between(h->stream);
     for (int r = 0; r < recorded; ++r) {
         const int first = (int)((long long)d.B * r / runs), count = (int)((long long)d.B * (r + 1) / runs) - first;
-        const hipError_t w = hipStreamWaitEvent(h->stream, h->ev_top_join[r], 0);
+        const hipError_t w = hipStreamWaitEvent(h->stream, h->ev_top_join[r].get(), 0);
         if (e == hipSuccess) e = w;
         if (e == hipSuccess) e = rcw_launch_top_store(d, mask_dev, first, count, h->stream);
     }
@@ -234,7 +236,7 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
 {
     const RcwDev& d = h->dev;
     const bool prof = h->profiling && h->prof_count < kProfileSlots;
-    hipEvent_t* ev = prof ? &h->prof_ev[4 * h->prof_count] : nullptr;
+    const RcwEvent* ev = prof ? &h->prof_ev[4 * h->prof_count] : nullptr;
     hipError_t e;
     if (h->spec_on) {
         // The one-launch step keeps its place in the slot buffers on the HOST (which of the two the next launch reads): a graph would replay
@@ -243,18 +245,18 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { h->spec_on = 0; h->step_captured = true; h->spec_primed = false; }
     }
-    if (prof && (e = hipEventRecord(ev[0], h->stream)) != hipSuccess) return e;
+    if (prof && (e = hipEventRecord(ev[0].get(), h->stream)) != hipSuccess) return e;
     if (h->spec_on) {
-        uint16_t* const cur = (uint16_t*)h->d_spec[h->spec_cur];
+        uint16_t* const cur = h->d_spec[h->spec_cur].get<uint16_t>();
         if (actions_dev && !mask_dev && h->spec_primed) {
             // act!(env, a) SR:333-340 in ONE launch: the fill workgroups write the frames the actions select among the successors the last
             // casting launch left in `cur`; the casting workgroups commit the actions and cast the new states' successors into the other buffer
-            uint16_t* const next = (uint16_t*)h->d_spec[h->spec_cur ^ 1];
-            if (prof && ((e = hipEventRecord(ev[1], h->stream)) != hipSuccess || (e = hipEventRecord(ev[2], h->stream)) != hipSuccess)) return e;
+            uint16_t* const next = h->d_spec[h->spec_cur ^ 1].get<uint16_t>();
+            if (prof && ((e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess || (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess)) return e;
             if ((e = rcw_launch_step_spec(d, actions_dev, nullptr, cur, next, true, h->cols_live, h->stream)) != hipSuccess) return e;
             h->spec_cur ^= 1;
             if (!h->cols_live) h->cols_stale = true;
-            if (prof) { if ((e = hipEventRecord(ev[3], h->stream)) != hipSuccess) return e; h->prof_count++; }
+            if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
             return hipSuccess;
         }
         // reset! / set_state (no action, maybe a mask) or a first step: the casting workgroups alone — dynamics if any, the current frame's
@@ -262,9 +264,9 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
         if ((e = rcw_launch_step_spec(d, actions_dev, mask_dev, nullptr, cur, false, true, h->stream)) != hipSuccess) return e;
         if (!mask_dev) h->cols_stale = false;                 // (with a mask: the masked agents' descriptors are fresh — the fill below reads only those —, the others' as stale as before)
         if (!mask_dev) h->spec_primed = true;
-        if (prof && ((e = hipEventRecord(ev[1], h->stream)) != hipSuccess || (e = hipEventRecord(ev[2], h->stream)) != hipSuccess)) return e;
+        if (prof && ((e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess || (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess)) return e;
         if ((e = rcw_launch_fill(d, d.col_h, d.col_c, d.obs, (long long)d.B * d.N, mask_dev, h->stream)) != hipSuccess) return e;
-        if (prof) { if ((e = hipEventRecord(ev[3], h->stream)) != hipSuccess) return e; h->prof_count++; }
+        if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
         return hipSuccess;
     }
 #ifdef RCW_DEV_SWITCHES
@@ -273,29 +275,29 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
 #ifdef RCW_DEV_SWITCHES
     if (d.step_fused && rcw_step_fusable(d)) {
         // Development experiment (RCW_STEP_FUSED=1, docs/experiments.md): cast and camera fill in ONE launch
-        if (prof && ((e = hipEventRecord(ev[1], h->stream)) != hipSuccess || (e = hipEventRecord(ev[2], h->stream)) != hipSuccess)) return e;
+        if (prof && ((e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess || (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess)) return e;
         h->dev.step_epoch = ++h->step_epoch;
         if ((e = rcw_launch_step256(d, actions_dev, mask_dev, h->step_epoch, h->stream)) != hipSuccess) return e;
-        if (prof) { if ((e = hipEventRecord(ev[3], h->stream)) != hipSuccess) return e; h->prof_count++; }
+        if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
         return hipSuccess;
     }
 #endif
     if ((e = rcw_launch_cast(d, actions_dev, mask_dev, h->stream)) != hipSuccess) return e;
-    if (prof && (e = hipEventRecord(ev[1], h->stream)) != hipSuccess) return e;
+    if (prof && (e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess) return e;
     auto fill = [&](hipStream_t fs) -> hipError_t {            // (fs: the handle's stream, or its side stream: launch_top_view)
         hipError_t f;
-        if (prof && !d.top_split && (f = hipEventRecord(ev[2], fs)) != hipSuccess) return f;
+        if (prof && !d.top_split && (f = hipEventRecord(ev[2].get(), fs)) != hipSuccess) return f;
         if ((f = rcw_launch_fill(d, d.col_h, d.col_c, d.obs, (long long)d.B * d.N, mask_dev, fs)) != hipSuccess) return f;
-        if (prof && d.top_split && (f = hipEventRecord(ev[2], fs)) != hipSuccess) return f;
+        if (prof && d.top_split && (f = hipEventRecord(ev[2].get(), fs)) != hipSuccess) return f;
         return hipSuccess;
     };
-    if (d.top_view) { if ((e = launch_top_view(h, mask_dev, true, fill, prof ? ev[2] : nullptr)) != hipSuccess) return e; }   // SR:337
+    if (d.top_view) { if ((e = launch_top_view(h, mask_dev, true, fill, prof ? ev[2].get() : nullptr)) != hipSuccess) return e; }   // SR:337
     else {
-        if (prof && (e = hipEventRecord(ev[2], h->stream)) != hipSuccess) return e;
+        if (prof && (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess) return e;
         if ((e = rcw_launch_fill(d, d.col_h, d.col_c, d.obs, (long long)d.B * d.N, mask_dev, h->stream)) != hipSuccess) return e;
     }
     if (prof) {
-        if ((e = hipEventRecord(ev[3], h->stream)) != hipSuccess) return e;
+        if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e;
         h->prof_count++;
     }
     return hipSuccess;
@@ -306,7 +308,7 @@ bool view_only(const rcw_handle* h) { return h->view_fmt != RCW_VIEW_OFF && (h->
 // the learner view of the handle's current descriptors (the unmasked agents' only), on the handle's stream
 hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev)
 {
-    return rcw_launch_view(h->dev, h->view, h->dev.col_h, h->dev.col_c, h->B, mask_dev, (uint8_t*)h->d_view, h->stream);
+    return rcw_launch_view(h->dev, h->view, h->dev.col_h, h->dev.col_c, h->B, mask_dev, h->d_view.get<uint8_t>(), h->stream);
 }
 
 // A step, reset! or set_state's render: the camera view (launch_step_camera), then the learner view where the handle has one.  With
@@ -319,57 +321,36 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
         return e == hipSuccess && h->view_fmt != RCW_VIEW_OFF ? launch_view(h, mask_dev) : e;
     }
     const bool prof = h->profiling && h->prof_count < kProfileSlots;
-    hipEvent_t* ev = prof ? &h->prof_ev[4 * h->prof_count] : nullptr;
+    const RcwEvent* ev = prof ? &h->prof_ev[4 * h->prof_count] : nullptr;
     hipError_t e;
-    if (prof && (e = hipEventRecord(ev[0], h->stream)) != hipSuccess) return e;
+    if (prof && (e = hipEventRecord(ev[0].get(), h->stream)) != hipSuccess) return e;
     if ((e = rcw_launch_cast(h->dev, actions_dev, mask_dev, h->stream)) != hipSuccess) return e;
     if (!mask_dev) h->cols_stale = false;
-    if (prof && (e = hipEventRecord(ev[1], h->stream)) != hipSuccess) return e;
+    if (prof && (e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess) return e;
     if (h->dev.top_view && (e = launch_top_view(h, mask_dev, false, [](hipStream_t) { return hipSuccess; })) != hipSuccess) return e;
-    if (prof && (e = hipEventRecord(ev[2], h->stream)) != hipSuccess) return e;
+    if (prof && (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess) return e;
     if ((e = launch_view(h, mask_dev)) != hipSuccess) return e;
-    if (prof) { if ((e = hipEventRecord(ev[3], h->stream)) != hipSuccess) return e; h->prof_count++; }
+    if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
     return hipSuccess;
 }
 
-void free_all(rcw_handle* h)
+// Every stream that may hold work of the handle — the side stream, its own, the caller's current one — is waited for; the first failure comes back.
+hipError_t wait_all_streams(rcw_handle* h)
 {
-    void** ptrs[] = {&h->d_pos, &h->d_dir, &h->d_goal, &h->d_reward, &h->d_done, &h->d_episode,
-                     &h->d_tile_map, &h->d_dir_table, &h->d_ray_table, &h->d_obs, &h->d_col_h,
-                     &h->d_col_c, &h->d_err, &h->d_status, &h->d_top_view, &h->d_actions, &h->d_mask, &h->d_in_goal,
-                     &h->d_in_pos, &h->d_in_dir};
-    for (void** p : ptrs) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    if (h->h_err) (void)hipHostFree(h->h_err);
-    h->h_err = nullptr;
-    for (int k = 0; k < 2; ++k) {
-        if (h->h_actions[k]) (void)hipHostFree(h->h_actions[k]);
-        if (h->ev_actions[k]) (void)hipEventDestroy(h->ev_actions[k]);
-        h->h_actions[k] = nullptr;
-        h->ev_actions[k] = nullptr;
-    }
-    for (int k = 0; k < 4; ++k) { if (h->d_rays[k]) (void)hipFree(h->d_rays[k]); h->d_rays[k] = nullptr; h->rays_cap[k] = 0; }
-    if (h->top_stream) (void)hipStreamSynchronize(h->top_stream);          // (a draw kernel of a failed step may still run)
-    for (void** q : {&h->d_top_plane, &h->d_top_hdr, &h->d_top_codes, &h->d_top_flags, &h->d_step_flags, &h->d_step_hc, &h->d_spec[0], &h->d_spec[1]}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-    if (h->ev_top_fork) (void)hipEventDestroy(h->ev_top_fork);
-    for (hipEvent_t& q : h->ev_top_join) { if (q) (void)hipEventDestroy(q); q = nullptr; }
-    if (h->top_stream) (void)hipStreamDestroy(h->top_stream);
-    h->ev_top_fork = nullptr; h->top_stream = nullptr;
-    if (h->d_gather_h) (void)hipFree(h->d_gather_h);
-    if (h->d_gather_c) (void)hipFree(h->d_gather_c);
-    h->d_gather_h = h->d_gather_c = nullptr;
-    if (h->d_view) (void)hipFree(h->d_view);
-    if (h->d_view_tab) (void)hipFree(h->d_view_tab);
-    h->d_view = h->d_view_tab = nullptr;
-    for (hipEvent_t ev : h->prof_ev) (void)hipEventDestroy(ev);
-    h->prof_ev.clear();
-    if (h->ev_start) (void)hipEventDestroy(h->ev_start);
-    if (h->ev_stop) (void)hipEventDestroy(h->ev_stop);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    h->ev_start = h->ev_stop = nullptr;
-    h->own_stream = nullptr;
+    hipError_t e = hipSuccess;
+    for (hipStream_t s : {h->top_stream.get(), h->own_stream.get(), h->stream != h->own_stream.get() ? h->stream : nullptr})
+        if (s) { const hipError_t r = hipStreamSynchronize(s); if (e == hipSuccess) e = r; }
+    return e;
+}
+
+// THE way a buffer of a live handle is given up: wait_all_streams (queued work may still use the old ones), then each of `old` takes
+// over its partner in `fresh` (allocated by the caller beforehand, where the old one must survive a failure) or, without one, is dropped.
+hipError_t replace_buffers(rcw_handle* h, std::initializer_list<RcwBuf*> old, std::initializer_list<RcwBuf*> fresh = {})
+{
+    const hipError_t e = wait_all_streams(h);
+    auto f = fresh.begin();
+    if (e == hipSuccess) for (RcwBuf* q : old) *q = f != fresh.end() ? std::move(**f++) : RcwBuf();
+    return e;
 }
 
 // directions_wu  SR:65-69: theta = (i-1)*2*pi/nd in Float64, components converted to T
@@ -438,8 +419,8 @@ int upload_tables(rcw_handle* h)
     const void* dirs = h->real64 ? (const void*)h->dir_table64.data() : (const void*)h->dir_table.data();
     const void* rays = h->real64 ? (const void*)h->ray_table64.data() : (const void*)h->ray_table.data();
     const size_t nd2 = (size_t)2 * h->cfg.num_directions, nr = (size_t)h->cfg.num_directions * RCW_TABLE_ROWS * h->cfg.num_rays;
-    RCW_HIP(hipMemcpyAsync(h->d_dir_table, dirs, nd2 * h->real_size, hipMemcpyHostToDevice, h->stream));
-    RCW_HIP(hipMemcpyAsync(h->d_ray_table, rays, nr * h->real_size, hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipMemcpyAsync(h->d_dir_table.get(), dirs, nd2 * h->real_size, hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipMemcpyAsync(h->d_ray_table.get(), rays, nr * h->real_size, hipMemcpyHostToDevice, h->stream));
     RCW_HIP(hipStreamSynchronize(h->stream));
     return RCW_OK;
 }
@@ -629,38 +610,37 @@ int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient)
 {
     RcwDev& d = h->dev;
     const size_t B = (size_t)h->B;
-    if (h->top_stream) RCW_HIP(hipStreamSynchronize(h->top_stream));
-    for (void** q : {&h->d_top_plane, &h->d_top_hdr, &h->d_top_codes, &h->d_top_flags}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    RCW_HIP(replace_buffers(h, {&h->d_top_plane, &h->d_top_hdr, &h->d_top_codes, &h->d_top_flags}));
     d.top_plane = nullptr; d.top_hdr = nullptr; d.top_codes = nullptr; d.top_flags = nullptr; h->top_epoch = 0;
     int rc = top_view_rule(d, &h->cfg, B, h->hw, want_form, want_runs, lenient);
     if (rc != RCW_OK || !h->cfg.render_top_view) return rc;
     if (d.top_split) {
-        hipError_t e = hipMalloc(&h->d_top_plane, rcw_top_plane_bytes(d));
+        hipError_t e = h->d_top_plane.hipMalloc(rcw_top_plane_bytes(d));
         // The planes start out ZERO.  The flat store kernel ORs the plane words of two neighbouring agents' regions in a chunk
         // that holds pixels of both and relies on a region's bits outside its own image being zero — true of every region the
         // draw kernel has written, but a masked render right after rcw_set_top_view_form (whose own re-render may be the
         // one-kernel form, which writes no planes) draws the masked agents only and reads their neighbours' regions as they lie.
         // (stream-ordered on the handle's stream: every later launch of the handle comes behind it, the side stream's draw
         // kernel through the fork event)
-        if (e == hipSuccess) e = hipMemsetAsync(h->d_top_plane, 0, rcw_top_plane_bytes(d), h->stream);
-        if (e == hipSuccess) e = hipMalloc(&h->d_top_hdr, (size_t)h->B * sizeof(int2));
-        if (e == hipSuccess) e = hipMemsetAsync(h->d_top_hdr, 0, (size_t)h->B * sizeof(int2), h->stream);
-        if (e == hipSuccess) e = hipMalloc(&h->d_top_codes, rcw_top_codes_bytes(d));
+        if (e == hipSuccess) e = hipMemsetAsync(h->d_top_plane.get(), 0, rcw_top_plane_bytes(d), h->stream);
+        if (e == hipSuccess) e = h->d_top_hdr.hipMalloc((size_t)h->B * sizeof(int2));
+        if (e == hipSuccess) e = hipMemsetAsync(h->d_top_hdr.get(), 0, (size_t)h->B * sizeof(int2), h->stream);
+        if (e == hipSuccess) e = h->d_top_codes.hipMalloc(rcw_top_codes_bytes(d));
 #ifdef RCW_DEV_SWITCHES
-        if (e == hipSuccess) e = hipMalloc(&h->d_top_flags, (size_t)h->B * sizeof(uint32_t));                      // (experiment RCW_TOP_FOLLOW)
-        if (e == hipSuccess) e = hipMemsetAsync(h->d_top_flags, 0, (size_t)h->B * sizeof(uint32_t), h->stream);
+        if (e == hipSuccess) e = h->d_top_flags.hipMalloc((size_t)h->B * sizeof(uint32_t));                      // (experiment RCW_TOP_FOLLOW)
+        if (e == hipSuccess) e = hipMemsetAsync(h->d_top_flags.get(), 0, (size_t)h->B * sizeof(uint32_t), h->stream);
 #endif
-        if (e == hipSuccess && !h->top_stream) e = hipStreamCreateWithFlags(&h->top_stream, hipStreamNonBlocking);
-        if (e == hipSuccess && !h->ev_top_fork) e = hipEventCreateWithFlags(&h->ev_top_fork, hipEventDisableTiming);
-        for (hipEvent_t& q : h->ev_top_join) if (e == hipSuccess && !q) e = hipEventCreateWithFlags(&q, hipEventDisableTiming);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "top view planes: %s", hipGetErrorString(e));
-        d.top_plane = (uint32_t*)h->d_top_plane; d.top_hdr = (int2*)h->d_top_hdr; d.top_codes = (uint2*)h->d_top_codes;
+        if (e == hipSuccess && !h->top_stream.get()) e = h->top_stream.hipStreamCreate();
+        if (e == hipSuccess && !h->ev_top_fork.get()) e = h->ev_top_fork.hipEventCreate(hipEventDisableTiming);
+        for (RcwEvent& q : h->ev_top_join) if (e == hipSuccess && !q.get()) e = q.hipEventCreate(hipEventDisableTiming);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "top view planes: %s", hip_failure(e));
+        d.top_plane = h->d_top_plane.get<uint32_t>(); d.top_hdr = h->d_top_hdr.get<int2>(); d.top_codes = h->d_top_codes.get<uint2>();
 #ifdef RCW_DEV_SWITCHES
 #include "dev/api_top_follow_plan.inc"   // RCW_TOP_FOLLOW: the counters' block size and where the store kernel may follow the draw kernel
 #endif
     }
     hipError_t e = rcw_prepare_top_view(d, h->device);
-    if (e != hipSuccess) return fail(RCW_ERR_HIP, "top view kernel attribute: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(RCW_ERR_HIP, "top view kernel attribute: %s", hip_failure(e));
     return RCW_OK;
 }
 
@@ -696,9 +676,9 @@ int plan_step_form(rcw_handle* h, int want)
     const bool on = want == RCW_STEP_TWO_LAUNCHES ? false : (want == RCW_STEP_ONE_LAUNCH ? true : eligible && !h->step_captured && step_one_launch_pays(d));
     if (on) {
         for (int k = 0; k < 2; ++k) {
-            if (h->d_spec[k]) continue;
-            const hipError_t e = hipMalloc(&h->d_spec[k], rcw_step_spec_slot_bytes(d));
-            if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "one-launch step, slot buffers: %s", hipGetErrorString(e));
+            if (h->d_spec[k].get()) continue;
+            const hipError_t e = h->d_spec[k].hipMalloc(rcw_step_spec_slot_bytes(d));
+            if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "one-launch step, slot buffers: %s", hip_failure(e));
         }
         if (want == RCW_STEP_ONE_LAUNCH) h->step_captured = false;
     }
@@ -777,9 +757,9 @@ int ensure_columns(rcw_handle* h)
 // Wait for the stream, then surface the sticky device error word.
 int sync_and_check(rcw_handle* h)
 {
-    RCW_HIP(hipMemcpyAsync(h->h_err, h->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    RCW_HIP(hipMemcpyAsync(h->h_err.get(), h->d_err.get(), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     RCW_HIP(hipStreamSynchronize(h->stream));
-    const int32_t e = h->h_err[0];
+    const int32_t e = h->h_err.get<int32_t>()[0];
     if (e == RCW_ERR_INVALID_ACTION) return fail(e, "invalid action (must be in 1..%d); the agents it was given to were not stepped (rcw_status)", RCW_NUM_ACTIONS);
     if (e == RCW_ERR_OUT_OF_BOUNDS) return fail(e, "a tile index left the tile map (BoundsError in the reference)");
     if (e == RCW_ERR_HIP) return fail(e, "a kernel gave up waiting for another one after about a second (the top view's store kernel for its draw kernel): the images of that call are not valid");
@@ -806,10 +786,10 @@ int upload_mask(rcw_handle* h, const uint8_t* mask_host, const uint8_t** mask_de
 {
     *mask_dev = nullptr;
     if (!mask_host) return RCW_OK;
-    RCW_HIP(hipMemcpyAsync(h->d_mask, mask_host, (size_t)h->B, hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipMemcpyAsync(h->d_mask.get(), mask_host, (size_t)h->B, hipMemcpyHostToDevice, h->stream));
     // the host buffer may be pageable and reused by the caller right away
     RCW_HIP(hipStreamSynchronize(h->stream));
-    *mask_dev = (const uint8_t*)h->d_mask;
+    *mask_dev = h->d_mask.get<uint8_t>();
     return RCW_OK;
 }
 
@@ -891,6 +871,15 @@ int need_comm(rcw_handle* h, const char* fn)
 
 }  // namespace
 
+// The one teardown (rcw_destroy, and a failed rcw_create through its unique_ptr): nothing is freed before all three streams were waited
+// for (a failed wait is ignored: the handle goes either way); the members follow in reverse order of declaration, the streams last.
+rcw_handle::~rcw_handle()
+{
+    (void)hipSetDevice(device);
+    (void)wait_all_streams(this);
+    if (comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy((ncclComm_t)comm);
+}
+
 extern "C" {
 
 int rcw_abi_version(void) { return RCW_ABI_VERSION; }
@@ -952,7 +941,7 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
         return fail(RCW_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
     RCW_HIP(hipSetDevice(device));
 
-    rcw_handle* h = new (std::nothrow) rcw_handle();
+    std::unique_ptr<rcw_handle> h(new (std::nothrow) rcw_handle());   // (whichever return leaves from here on: ~rcw_handle, which waits for what was queued first)
     if (!h) return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation failed");
     h->cfg = *cfg;
     h->B = batch;
@@ -964,51 +953,39 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     h->real_size = h->real64 ? sizeof(double) : sizeof(float);
     const size_t B = (size_t)batch;
 
-#define RCW_TRY(expr)                                       \
-    do {                                                    \
-        hipError_t e_ = (expr);                             \
-        if (e_ != hipSuccess) {                             \
-            free_all(h);                                    \
-            delete h;                                       \
-            return fail(e_ == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, \
-                        "%s failed: %s", #expr, hipGetErrorString(e_)); \
-        }                                                   \
-    } while (0)
-
-    RCW_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    h->stream = h->own_stream;
-    RCW_TRY(hipEventCreate(&h->ev_start));
-    RCW_TRY(hipEventCreate(&h->ev_stop));
-    RCW_TRY(hipMalloc(&h->d_pos, B * 2 * h->real_size));
-    RCW_TRY(hipMalloc(&h->d_dir, B * sizeof(int32_t)));
-    RCW_TRY(hipMalloc(&h->d_goal, B * sizeof(int2)));
+    RCW_HIP(h->own_stream.hipStreamCreate());
+    h->stream = h->own_stream.get();
+    RCW_HIP(h->ev_start.hipEventCreate());
+    RCW_HIP(h->ev_stop.hipEventCreate());
+    RCW_HIP(h->d_pos.hipMalloc(B * 2 * h->real_size));
+    RCW_HIP(h->d_dir.hipMalloc(B * sizeof(int32_t)));
+    RCW_HIP(h->d_goal.hipMalloc(B * sizeof(int2)));
     h->reward_size = (cfg->reward_type == RCW_REWARD_FLOAT64 || cfg->reward_type == RCW_REWARD_INT64) ? 8 : 4;
-    RCW_TRY(hipMalloc(&h->d_reward, B * h->reward_size));
-    RCW_TRY(hipMalloc(&h->d_done, B));
-    RCW_TRY(hipMalloc(&h->d_episode, B * sizeof(uint32_t)));
-    RCW_TRY(hipMalloc(&h->d_tile_map, B * (size_t)h->nchunks * sizeof(uint64_t) + 16));   // (+ 2 words: the flat top store kernel reads three words from any word of a map)
-    RCW_TRY(hipMalloc(&h->d_dir_table, (size_t)nd * 2 * h->real_size));
-    RCW_TRY(hipMalloc(&h->d_ray_table, (size_t)nd * RCW_TABLE_ROWS * N * h->real_size));
-    RCW_TRY(hipMalloc(&h->d_obs, B * (size_t)N * Hc * sizeof(uint32_t)));
-    RCW_TRY(hipMalloc(&h->d_col_h, B * (size_t)N * sizeof(int32_t)));
-    RCW_TRY(hipMalloc(&h->d_col_c, B * (size_t)N));
+    RCW_HIP(h->d_reward.hipMalloc(B * h->reward_size));
+    RCW_HIP(h->d_done.hipMalloc(B));
+    RCW_HIP(h->d_episode.hipMalloc(B * sizeof(uint32_t)));
+    RCW_HIP(h->d_tile_map.hipMalloc(B * (size_t)h->nchunks * sizeof(uint64_t) + 16));   // (+ 2 words: the flat top store kernel reads three words from any word of a map)
+    RCW_HIP(h->d_dir_table.hipMalloc((size_t)nd * 2 * h->real_size));
+    RCW_HIP(h->d_ray_table.hipMalloc((size_t)nd * RCW_TABLE_ROWS * N * h->real_size));
+    RCW_HIP(h->d_obs.hipMalloc(B * (size_t)N * Hc * sizeof(uint32_t)));
+    RCW_HIP(h->d_col_h.hipMalloc(B * (size_t)N * sizeof(int32_t)));
+    RCW_HIP(h->d_col_c.hipMalloc(B * (size_t)N));
     if (cfg->render_top_view)
-        RCW_TRY(hipMalloc(&h->d_top_view, B * (size_t)H * W * cfg->pu_per_tu * cfg->pu_per_tu * sizeof(uint32_t)));
-    RCW_TRY(hipMalloc(&h->d_err, sizeof(int32_t)));
-    RCW_TRY(hipMalloc(&h->d_status, B * sizeof(int32_t)));
-    RCW_TRY(hipMalloc(&h->d_actions, B));
-    RCW_TRY(hipMalloc(&h->d_mask, B));
-    RCW_TRY(hipMalloc(&h->d_in_goal, B * sizeof(int2)));
-    RCW_TRY(hipMalloc(&h->d_in_pos, B * 2 * h->real_size));
-    RCW_TRY(hipMalloc(&h->d_in_dir, B * sizeof(int32_t)));
-    RCW_TRY(hipHostMalloc((void**)&h->h_err, sizeof(int32_t), hipHostMallocDefault));
+        RCW_HIP(h->d_top_view.hipMalloc(B * (size_t)H * W * cfg->pu_per_tu * cfg->pu_per_tu * sizeof(uint32_t)));
+    RCW_HIP(h->d_err.hipMalloc(sizeof(int32_t)));
+    RCW_HIP(h->d_status.hipMalloc(B * sizeof(int32_t)));
+    RCW_HIP(h->d_actions.hipMalloc(B));
+    RCW_HIP(h->d_mask.hipMalloc(B));
+    RCW_HIP(h->d_in_goal.hipMalloc(B * sizeof(int2)));
+    RCW_HIP(h->d_in_pos.hipMalloc(B * 2 * h->real_size));
+    RCW_HIP(h->d_in_dir.hipMalloc(B * sizeof(int32_t)));
+    RCW_HIP(h->h_err.hipHostMalloc(sizeof(int32_t)));
     for (int k = 0; k < 2; ++k) {
-        RCW_TRY(hipHostMalloc((void**)&h->h_actions[k], B, hipHostMallocDefault));
-        RCW_TRY(hipEventCreateWithFlags(&h->ev_actions[k], hipEventDisableTiming));
+        RCW_HIP(h->h_actions[k].hipHostMalloc(B));
+        RCW_HIP(h->ev_actions[k].hipEventCreate(hipEventDisableTiming));
     }
-    RCW_TRY(hipMemsetAsync(h->d_err, 0, sizeof(int32_t), h->stream));
-    RCW_TRY(hipMemsetAsync(h->d_status, 0, B * sizeof(int32_t), h->stream));
-#undef RCW_TRY
+    RCW_HIP(hipMemsetAsync(h->d_err.get(), 0, sizeof(int32_t), h->stream));
+    RCW_HIP(hipMemsetAsync(h->d_status.get(), 0, B * sizeof(int32_t), h->stream));
 
     RcwDev& d = h->dev;
     set_geometry(d, cfg, batch);
@@ -1036,22 +1013,21 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     d.auto_reset = cfg->auto_reset ? 1 : 0;
     d.agent_id_offset = cfg->agent_id_offset;
     d.seed = seed;
-    d.pos = (float2*)h->d_pos; d.pos64 = (double2*)h->d_pos; d.dir = (int32_t*)h->d_dir; d.goal = (int2*)h->d_goal;
-    d.reward = h->d_reward; d.done = (uint8_t*)h->d_done; d.episode = (uint32_t*)h->d_episode;
-    d.tile_map = (uint32_t*)h->d_tile_map;
-    d.dir_table = (const float2*)h->d_dir_table; d.ray_table = (const float*)h->d_ray_table;
-    d.dir_table64 = (const double2*)h->d_dir_table; d.ray_table64 = (const double*)h->d_ray_table;
-    d.obs = (uint32_t*)h->d_obs; d.col_h = (int32_t*)h->d_col_h; d.col_c = (uint8_t*)h->d_col_c;
-    d.err = (int32_t*)h->d_err;
-    d.top_view = (uint32_t*)h->d_top_view;
-    d.status = (int32_t*)h->d_status;
+    d.pos = h->d_pos.get<float2>(); d.pos64 = h->d_pos.get<double2>(); d.dir = h->d_dir.get<int32_t>(); d.goal = h->d_goal.get<int2>();
+    d.reward = h->d_reward.get(); d.done = h->d_done.get<uint8_t>(); d.episode = h->d_episode.get<uint32_t>();
+    d.tile_map = h->d_tile_map.get<uint32_t>();
+    d.dir_table = h->d_dir_table.get<float2>(); d.ray_table = h->d_ray_table.get<float>();
+    d.dir_table64 = h->d_dir_table.get<double2>(); d.ray_table64 = h->d_ray_table.get<double>();
+    d.obs = h->d_obs.get<uint32_t>(); d.col_h = h->d_col_h.get<int32_t>(); d.col_c = h->d_col_c.get<uint8_t>();
+    d.err = h->d_err.get<int32_t>();
+    d.top_view = h->d_top_view.get<uint32_t>();
+    d.status = h->d_status.get<int32_t>();
     d.oob_empty = cfg->out_of_bounds == RCW_OOB_TREAT_EMPTY;
-    h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    h->hw.cus = h->num_cus;
+    h->hw.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (prop.sharedMemPerBlock >= 64 * 1024) h->hw.lds_per_cu = (int)prop.sharedMemPerBlock;           // (gfx950: 160 KiB, the whole CU's)
     if (prop.maxThreadsPerMultiProcessor >= 64) h->hw.waves_per_cu = prop.maxThreadsPerMultiProcessor / 64;
     // fill kernel: one workgroup per CU (256 on an MI355X in SPX mode; a partitioned device reports fewer)
-    d.fill_grid = h->num_cus; d.fill_plain = 0; d.fill_flat = 0;
+    d.fill_grid = h->hw.cus; d.fill_plain = 0; d.fill_flat = 0;
     // lanes per agent in the cast kernel: four rays a lane once the batch fills the chip (measured, µs: 512 columns 45.6 vs 51.4
     // with two a lane, 256 columns 12.3 vs 12.7; 1024 columns take 256 lanes either way), two a lane for small batches, where
     // an agent's own latency is what counts
@@ -1081,21 +1057,21 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     d.step_fused = 0; d.step_flags = nullptr; d.step_hc = nullptr; d.step_epoch = 0;
     if (const char* v = RCW_DEV_ENV("RCW_STEP_FUSED")) {
         if (std::atoi(v)) {
-            hipError_t e = hipMalloc(&h->d_step_flags, B * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMalloc(&h->d_step_hc, B * (size_t)N * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemset(h->d_step_flags, 0, B * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemset(h->d_step_hc, 0, B * (size_t)N * sizeof(uint32_t));
-            if (e != hipSuccess) { free_all(h); delete h; return fail(RCW_ERR_OUT_OF_MEMORY, "fused step: %s", hipGetErrorString(e)); }
-            d.step_flags = (uint32_t*)h->d_step_flags; d.step_hc = (uint32_t*)h->d_step_hc; d.step_fused = std::atoi(v) == 2 ? 2 : 1; d.step_epoch = 0;
+            hipError_t e = h->d_step_flags.hipMalloc(B * sizeof(uint32_t));
+            if (e == hipSuccess) e = h->d_step_hc.hipMalloc(B * (size_t)N * sizeof(uint32_t));
+            if (e == hipSuccess) e = hipMemset(h->d_step_flags.get(), 0, B * sizeof(uint32_t));
+            if (e == hipSuccess) e = hipMemset(h->d_step_hc.get(), 0, B * (size_t)N * sizeof(uint32_t));
+            if (e != hipSuccess) return fail(RCW_ERR_OUT_OF_MEMORY, "fused step: %s", hip_failure(e));
+            d.step_flags = h->d_step_flags.get<uint32_t>(); d.step_hc = h->d_step_hc.get<uint32_t>(); d.step_fused = std::atoi(v) == 2 ? 2 : 1; d.step_epoch = 0;
         }
     }
     if (const char* v = RCW_DEV_ENV("RCW_STEP_PIECES")) {
         h->step_pieces = std::atoi(v) == 2 ? 2 : 1;
         if (h->step_pieces == 2) {                                                            // the side stream and its two events
-            hipError_t e = hipStreamCreateWithFlags(&h->top_stream, hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_top_fork, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_top_join[0], hipEventDisableTiming);
-            if (e != hipSuccess) { free_all(h); delete h; return fail(RCW_ERR_HIP, "side stream: %s", hipGetErrorString(e)); }
+            hipError_t e = h->top_stream.hipStreamCreate();
+            if (e == hipSuccess) e = h->ev_top_fork.hipEventCreate(hipEventDisableTiming);
+            if (e == hipSuccess) e = h->ev_top_join[0].hipEventCreate(hipEventDisableTiming);
+            if (e != hipSuccess) return fail(RCW_ERR_HIP, "side stream: %s", hip_failure(e));
         }
     }
     {
@@ -1103,13 +1079,10 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
         if (const char* v = RCW_DEV_ENV("RCW_TOP_SPLIT")) { const int f = std::atoi(v); if (!f) want_form = RCW_TOP_VIEW_ONE_KERNEL; else if (f == 2) want_form = RCW_TOP_VIEW_TWO_KERNELS; }
         if (const char* v = RCW_DEV_ENV("RCW_TOP_INPLACE")) { if (std::atoi(v)) want_form = RCW_TOP_VIEW_IN_PLACE; }
         if (const char* v = RCW_DEV_ENV("RCW_TOP_RUNS")) { const int r = std::atoi(v); if (r >= 1 && r <= 8 && r <= batch) want_runs = r; }
-        rc = plan_top_view(h, want_form, want_runs, /*lenient=*/true);
-        if (rc != RCW_OK) { free_all(h); delete h; return rc; }
+        rc = plan_top_view(h.get(), want_form, want_runs, /*lenient=*/true); if (rc) return rc;
     }
-    if (rcw_step_lds_bytes(d) > 64 * 1024) {
-        free_all(h); delete h;
+    if (rcw_step_lds_bytes(d) > 64 * 1024)
         return fail(RCW_ERR_UNSUPPORTED, "tile map + column buffer need %zu B of LDS (> 64 KiB)", rcw_step_lds_bytes(d));
-    }
 #ifdef RCW_DEV_SWITCHES
     d.spec_debug = 0;
     if (const char* v = RCW_DEV_ENV("RCW_SPEC_DEBUG")) d.spec_debug = std::atoi(v);
@@ -1118,38 +1091,27 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
         int want = 0;
         if (const char* v = RCW_DEV_ENV("RCW_STEP_FORM")) { const int f = std::atoi(v); if (f == RCW_STEP_TWO_LAUNCHES) want = f; }
         if (d.step_fused || h->step_pieces == 2) want = RCW_STEP_TWO_LAUNCHES;          // (development experiments on the two-launch step)
-        rc = plan_step_form(h, want);
-        if (rc != RCW_OK) { free_all(h); delete h; return rc; }
+        rc = plan_step_form(h.get(), want); if (rc) return rc;
     }
 
     try {
         if (h->real64) build_direction_table<double>(nd, h->dir_table64); else build_direction_table<float>(nd, h->dir_table);
-        rebuild_ray_table(h);
+        rebuild_ray_table(h.get());
     } catch (const std::bad_alloc&) {
-        free_all(h); delete h;
         return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the (direction, ray) table failed");
     }
-    rc = upload_tables(h);
-    if (rc == RCW_OK) {
-        hipError_t e = rcw_launch_init_tile_map(d, h->stream);
-        if (e != hipSuccess) rc = fail(RCW_ERR_HIP, "init_tile_map launch: %s", hipGetErrorString(e));
-    }
-    if (rc == RCW_OK) rc = rcw_reset(h, nullptr, seed);
-    if (rc == RCW_OK) rc = sync_and_check(h);
-    if (rc != RCW_OK) { free_all(h); delete h; return rc; }
-    *out = h;
+    rc = upload_tables(h.get()); if (rc) return rc;
+    const hipError_t e = rcw_launch_init_tile_map(d, h->stream);
+    if (e != hipSuccess) return fail(RCW_ERR_HIP, "init_tile_map launch: %s", hip_failure(e));
+    rc = rcw_reset(h.get(), nullptr, seed); if (rc) return rc;
+    rc = sync_and_check(h.get()); if (rc) return rc;
+    *out = h.release();
     return RCW_OK;
 }
 
 int rcw_destroy(rcw_handle* h)
 {
-    if (!h) return RCW_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy((ncclComm_t)h->comm);
-    h->comm = nullptr;
-    free_all(h);
-    delete h;
+    delete h;            // (NULL: nothing; everything a handle owns goes in ~rcw_handle)
     return RCW_OK;
 }
 
@@ -1188,7 +1150,7 @@ int rcw_set_stream(rcw_handle* h, void* hip_stream)
 {
     int rc = check_handle(h); if (rc) return rc;
     RCW_HIP(hipStreamSynchronize(h->stream));
-    h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
+    h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream.get();
     return RCW_OK;
 }
 
@@ -1206,7 +1168,7 @@ int rcw_bind_obs(rcw_handle* h, void* device_ptr)
         return fail(RCW_ERR_INVALID_ARGUMENT, "observation buffer must be 16-byte aligned");
     // No synchronisation: the pointer travels in the kernel arguments of the launches that follow,
     // work already enqueued keeps the buffer it was launched with (double-buffered observations).
-    h->dev.obs = device_ptr ? (uint32_t*)device_ptr : (uint32_t*)h->d_obs;
+    h->dev.obs = device_ptr ? (uint32_t*)device_ptr : h->d_obs.get<uint32_t>();
     return RCW_OK;
 }
 
@@ -1246,11 +1208,11 @@ int set_state_impl(rcw_handle* h, const int32_t* goal_ij, const T* position_wu, 
     const uint8_t* mask_dev = nullptr;
     int rc = upload_mask(h, mask_host, &mask_dev); if (rc) return rc;
     const size_t B = (size_t)h->B;
-    RCW_HIP(hipMemcpyAsync(h->d_in_goal, goal_ij, B * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    RCW_HIP(hipMemcpyAsync(h->d_in_pos, position_wu, B * 2 * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    RCW_HIP(hipMemcpyAsync(h->d_in_dir, direction_au, B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipMemcpyAsync(h->d_in_goal.get(), goal_ij, B * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipMemcpyAsync(h->d_in_pos.get(), position_wu, B * 2 * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipMemcpyAsync(h->d_in_dir.get(), direction_au, B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     RCW_HIP(hipStreamSynchronize(h->stream));
-    RCW_HIP(rcw_launch_set_state(h->dev, (const int2*)h->d_in_goal, h->d_in_pos, (const int32_t*)h->d_in_dir, mask_dev,
+    RCW_HIP(rcw_launch_set_state(h->dev, h->d_in_goal.get<int2>(), h->d_in_pos.get(), h->d_in_dir.get<int32_t>(), mask_dev,
                                  h->stream));
     RCW_HIP(launch_step(h, nullptr, mask_dev));
     return RCW_OK;
@@ -1284,11 +1246,11 @@ int rcw_step(rcw_handle* h, const uint8_t* actions_host)
     // previous step, which is still reading d_actions.
     const int slot = h->action_slot;
     h->action_slot ^= 1;
-    RCW_HIP(hipEventSynchronize(h->ev_actions[slot]));
-    std::memcpy(h->h_actions[slot], actions_host, (size_t)h->B);
-    RCW_HIP(hipMemcpyAsync(h->d_actions, h->h_actions[slot], (size_t)h->B, hipMemcpyHostToDevice, h->stream));
-    RCW_HIP(hipEventRecord(h->ev_actions[slot], h->stream));
-    RCW_HIP(launch_step(h, (const uint8_t*)h->d_actions, nullptr));
+    RCW_HIP(hipEventSynchronize(h->ev_actions[slot].get()));
+    std::memcpy(h->h_actions[slot].get(), actions_host, (size_t)h->B);
+    RCW_HIP(hipMemcpyAsync(h->d_actions.get(), h->h_actions[slot].get(), (size_t)h->B, hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipEventRecord(h->ev_actions[slot].get(), h->stream));
+    RCW_HIP(launch_step(h, h->d_actions.get<uint8_t>(), nullptr));
     return RCW_OK;
 }
 
@@ -1319,7 +1281,7 @@ int rcw_update_camera_view(rcw_handle* h)
 int rcw_update_top_view(rcw_handle* h)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (!h->d_top_view) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
+    if (!h->d_top_view.get()) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
     RCW_HIP(launch_top_view(h, nullptr, false, [](hipStream_t) { return hipSuccess; }));
     return RCW_OK;
 }
@@ -1333,8 +1295,8 @@ int rcw_sync(rcw_handle* h)
 int rcw_clear_error(rcw_handle* h)
 {
     int rc = check_handle(h); if (rc) return rc;
-    RCW_HIP(hipMemsetAsync(h->d_err, 0, sizeof(int32_t), h->stream));
-    RCW_HIP(hipMemsetAsync(h->d_status, 0, (size_t)h->B * sizeof(int32_t), h->stream));
+    RCW_HIP(hipMemsetAsync(h->d_err.get(), 0, sizeof(int32_t), h->stream));
+    RCW_HIP(hipMemsetAsync(h->d_status.get(), 0, (size_t)h->B * sizeof(int32_t), h->stream));
     RCW_HIP(hipStreamSynchronize(h->stream));
     return RCW_OK;
 }
@@ -1361,20 +1323,20 @@ int rcw_obs_copy(rcw_handle* h, uint32_t* out_host, int32_t first, int32_t count
 int rcw_top_view_device_ptr(rcw_handle* h, void** device_ptr)
 {
     if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!h->d_top_view) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
-    *device_ptr = h->d_top_view;
+    if (!h->d_top_view.get()) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
+    *device_ptr = h->d_top_view.get();
     return RCW_OK;
 }
 
 int rcw_top_view_copy(rcw_handle* h, uint32_t* out_host, int32_t first, int32_t count)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (!h->d_top_view) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
+    if (!h->d_top_view.get()) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
     if (!out_host || first < 0 || count < 0 || first + (int64_t)count > h->B)
         return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
     rc = sync_and_check(h);
     const size_t frame = (size_t)h->cfg.height_tile_map_tu * h->cfg.width_tile_map_tu * h->cfg.pu_per_tu * h->cfg.pu_per_tu;
-    RCW_HIP(hipMemcpy(out_host, (uint32_t*)h->d_top_view + (size_t)first * frame, (size_t)count * frame * sizeof(uint32_t),
+    RCW_HIP(hipMemcpy(out_host, h->d_top_view.get<uint32_t>() + (size_t)first * frame, (size_t)count * frame * sizeof(uint32_t),
                       hipMemcpyDeviceToHost));
     return rc;
 }
@@ -1384,48 +1346,48 @@ int rcw_reward(rcw_handle* h, float* out)
     int rc = check_handle(h); if (rc) return rc;
     if (h->cfg.reward_type != RCW_REWARD_FLOAT32)
         return fail(RCW_ERR_UNSUPPORTED, "rcw_reward: the handle's reward type is not Float32; use rcw_reward_typed");
-    return copy_out(h, out, h->d_reward, (size_t)h->B);
+    return copy_out(h, out, h->d_reward.get(), (size_t)h->B);
 }
 int rcw_reward_typed(rcw_handle* h, void* out)
 {
     int rc = check_handle(h); if (rc) return rc;
-    return copy_out(h, static_cast<uint8_t*>(out), h->d_reward, (size_t)h->B * h->reward_size);
+    return copy_out(h, static_cast<uint8_t*>(out), h->d_reward.get(), (size_t)h->B * h->reward_size);
 }
-int rcw_done(rcw_handle* h, uint8_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_done, (size_t)h->B); }
+int rcw_done(rcw_handle* h, uint8_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_done.get(), (size_t)h->B); }
 int rcw_position(rcw_handle* h, float* out)
 {
     int rc = check_handle(h); if (rc) return rc;
     rc = check_real(h, false, "rcw_position"); if (rc) return rc;
-    return copy_out(h, out, h->d_pos, (size_t)2 * h->B);
+    return copy_out(h, out, h->d_pos.get(), (size_t)2 * h->B);
 }
 int rcw_position64(rcw_handle* h, double* out)
 {
     int rc = check_handle(h); if (rc) return rc;
     rc = check_real(h, true, "rcw_position64"); if (rc) return rc;
-    return copy_out(h, out, h->d_pos, (size_t)2 * h->B);
+    return copy_out(h, out, h->d_pos.get(), (size_t)2 * h->B);
 }
-int rcw_direction(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_dir, (size_t)h->B); }
-int rcw_goal(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_goal, (size_t)2 * h->B); }
-int rcw_episode(rcw_handle* h, uint32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_episode, (size_t)h->B); }
+int rcw_direction(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_dir.get(), (size_t)h->B); }
+int rcw_goal(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_goal.get(), (size_t)2 * h->B); }
+int rcw_episode(rcw_handle* h, uint32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_episode.get(), (size_t)h->B); }
 
 int rcw_status(rcw_handle* h, int32_t* out)
 {
     int rc = check_handle(h); if (rc) return rc;
     if (!out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL output pointer");
     RCW_HIP(hipStreamSynchronize(h->stream));
-    RCW_HIP(hipMemcpy(out, h->d_status, (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    RCW_HIP(hipMemcpy(out, h->d_status.get(), (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToHost));
     return RCW_OK;
 }
 
 int rcw_reward_device_ptr(rcw_handle* h, void** p)
 {
     if (!h || !p) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    *p = h->d_reward; return RCW_OK;
+    *p = h->d_reward.get(); return RCW_OK;
 }
 int rcw_done_device_ptr(rcw_handle* h, void** p)
 {
     if (!h || !p) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    *p = h->d_done; return RCW_OK;
+    *p = h->d_done.get(); return RCW_OK;
 }
 
 int rcw_tile_map_num_chunks(rcw_handle* h, int32_t* out)
@@ -1436,7 +1398,7 @@ int rcw_tile_map_num_chunks(rcw_handle* h, int32_t* out)
 int rcw_tile_map_chunks(rcw_handle* h, uint64_t* out)
 {
     int rc = check_handle(h); if (rc) return rc;
-    return copy_out(h, out, h->d_tile_map, (size_t)h->nchunks * h->B);
+    return copy_out(h, out, h->d_tile_map.get(), (size_t)h->nchunks * h->B);
 }
 
 extern "C++" {
@@ -1453,20 +1415,20 @@ int rays_impl(rcw_handle* h, int32_t first, int32_t count, int64_t* stop_ij, int
                             distance_wu ? n * sizeof(T) : 0, directions_wu ? 2 * n * sizeof(T) : 0};
     for (int k = 0; k < 4; ++k) {
         if (want[k] <= h->rays_cap[k]) continue;
-        if (h->d_rays[k]) { RCW_HIP(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_rays[k]); h->d_rays[k] = nullptr; h->rays_cap[k] = 0; }
-        RCW_HIP(hipMalloc(&h->d_rays[k], want[k]));
+        RcwBuf larger; RCW_HIP(larger.hipMalloc(want[k]));
+        RCW_HIP(replace_buffers(h, {&h->d_rays[k]}, {&larger}));
         h->rays_cap[k] = want[k];
     }
-    if (stop_ij) out.stop_ij = (int64_t*)h->d_rays[0];
-    if (hit_dimension) out.hit_dim = (int64_t*)h->d_rays[1];
-    if (distance_wu) out.dist = h->d_rays[2];
-    if (directions_wu) out.dirs = h->d_rays[3];
+    if (stop_ij) out.stop_ij = h->d_rays[0].get<int64_t>();
+    if (hit_dimension) out.hit_dim = h->d_rays[1].get<int64_t>();
+    if (distance_wu) out.dist = h->d_rays[2].get();
+    if (directions_wu) out.dirs = h->d_rays[3].get();
     RCW_HIP(rcw_launch_rays(h->dev, first, count, out, h->stream));
     RCW_HIP(hipStreamSynchronize(h->stream));
-    if (stop_ij) RCW_HIP(hipMemcpy(stop_ij, h->d_rays[0], want[0], hipMemcpyDeviceToHost));
-    if (hit_dimension) RCW_HIP(hipMemcpy(hit_dimension, h->d_rays[1], want[1], hipMemcpyDeviceToHost));
-    if (distance_wu) RCW_HIP(hipMemcpy(distance_wu, h->d_rays[2], want[2], hipMemcpyDeviceToHost));
-    if (directions_wu) RCW_HIP(hipMemcpy(directions_wu, h->d_rays[3], want[3], hipMemcpyDeviceToHost));
+    if (stop_ij) RCW_HIP(hipMemcpy(stop_ij, h->d_rays[0].get(), want[0], hipMemcpyDeviceToHost));
+    if (hit_dimension) RCW_HIP(hipMemcpy(hit_dimension, h->d_rays[1].get(), want[1], hipMemcpyDeviceToHost));
+    if (distance_wu) RCW_HIP(hipMemcpy(distance_wu, h->d_rays[2].get(), want[2], hipMemcpyDeviceToHost));
+    if (directions_wu) RCW_HIP(hipMemcpy(directions_wu, h->d_rays[3].get(), want[3], hipMemcpyDeviceToHost));
     return RCW_OK;
 }
 }  // extern "C++"
@@ -1495,9 +1457,9 @@ int rcw_columns(rcw_handle* h, int32_t first, int32_t count, int32_t* height_lin
     rc = sync_and_check(h);
     const size_t N = (size_t)h->cfg.num_rays;
     if (height_line_pu)
-        RCW_HIP(hipMemcpy(height_line_pu, (int32_t*)h->d_col_h + (size_t)first * N, (size_t)count * N * sizeof(int32_t), hipMemcpyDeviceToHost));
+        RCW_HIP(hipMemcpy(height_line_pu, h->d_col_h.get<int32_t>() + (size_t)first * N, (size_t)count * N * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (colour_id)
-        RCW_HIP(hipMemcpy(colour_id, (uint8_t*)h->d_col_c + (size_t)first * N, (size_t)count * N, hipMemcpyDeviceToHost));
+        RCW_HIP(hipMemcpy(colour_id, h->d_col_c.get<uint8_t>() + (size_t)first * N, (size_t)count * N, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -1509,8 +1471,8 @@ int rcw_columns_device_ptr(rcw_handle* h, void** height_line_pu, void** colour_i
         h->cols_live = true;
         rc = ensure_columns(h); if (rc) return rc;
     }
-    if (height_line_pu) *height_line_pu = h->d_col_h;
-    if (colour_id) *colour_id = h->d_col_c;
+    if (height_line_pu) *height_line_pu = h->d_col_h.get();
+    if (colour_id) *colour_id = h->d_col_c.get();
     return RCW_OK;
 }
 
@@ -1535,7 +1497,7 @@ int rcw_set_learner_view(rcw_handle* h, int32_t format, int32_t layout, int32_t 
     if (flags & ~RCW_VIEW_ONLY) return fail(RCW_ERR_INVALID_ARGUMENT, "unknown learner view flags 0x%x", (unsigned)flags);
     if (format == RCW_VIEW_OFF && flags) return fail(RCW_ERR_INVALID_ARGUMENT, "RCW_VIEW_ONLY needs a format");
     const bool was_only = view_only(h);
-    void* view = nullptr; void* tab = nullptr;
+    RcwBuf view, tab;
     RcwView v{};
     if (format != RCW_VIEW_OFF) {
         if (layout != RCW_VIEW_CHW && layout != RCW_VIEW_HWC)
@@ -1556,21 +1518,16 @@ int rcw_set_learner_view(rcw_handle* h, int32_t format, int32_t layout, int32_t 
         v.wide = n * 256 + n >= (1ll << 31) ? 1 : 0;          // (a box's channel sum + n/2 must stay below 2^31 for 32-bit sums)
         v.full_ok = height == Hc && width == N && rcw_view_full_eligible(h->dev, v.C, v.hwc) ? 1 : 0;
         const size_t bytes = (size_t)h->B * v.C * (size_t)height * width;
-        hipError_t e = hipMalloc(&view, bytes);
-        if (e == hipSuccess) e = hipMalloc(&tab, t.size() * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemcpy(tab, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {                                     // the handle keeps its previous view
-            if (view) (void)hipFree(view);
-            if (tab) (void)hipFree(tab);
-            return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "learner view buffer of %zu bytes: %s", bytes, hipGetErrorString(e));
-        }
-        v.rows = (const int32_t*)tab;
-        v.cols = (const int32_t*)tab + height + 1;
+        hipError_t e = view.hipMalloc(bytes);
+        if (e == hipSuccess) e = tab.hipMalloc(t.size() * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemcpy(tab.get(), t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess)                                       // the handle keeps its previous view
+            return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "learner view buffer of %zu bytes: %s", bytes, hip_failure(e));
+        v.rows = tab.get<int32_t>();
+        v.cols = tab.get<int32_t>() + height + 1;
     }
-    RCW_HIP(hipStreamSynchronize(h->stream));                     // (the old buffers may be in use by queued work)
-    if (h->d_view) (void)hipFree(h->d_view);
-    if (h->d_view_tab) (void)hipFree(h->d_view_tab);
-    h->d_view = view; h->d_view_tab = tab; h->view = v;
+    RCW_HIP(replace_buffers(h, {&h->d_view, &h->d_view_tab}, {&view, &tab}));   // (the new ones, or none: the view switched off)
+    h->view = v;
     h->view_fmt = format;
     h->view_layout = format != RCW_VIEW_OFF ? layout : RCW_VIEW_CHW;
     h->view_h = format != RCW_VIEW_OFF ? height : 0;
@@ -1604,7 +1561,7 @@ int rcw_learner_view_device_ptr(rcw_handle* h, void** device_ptr)
 {
     if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
     if (h->view_fmt == RCW_VIEW_OFF) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
-    *device_ptr = h->d_view;
+    *device_ptr = h->d_view.get();
     return RCW_OK;
 }
 
@@ -1616,7 +1573,7 @@ int rcw_learner_view_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32
         return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
     rc = sync_and_check(h);
     const size_t per = (size_t)h->view.C * h->view_h * h->view_w;
-    RCW_HIP(hipMemcpy(out_host, (uint8_t*)h->d_view + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
+    RCW_HIP(hipMemcpy(out_host, h->d_view.get<uint8_t>() + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -1662,13 +1619,10 @@ int rcw_comm_destroy(rcw_handle* h)
 {
     int rc = check_handle(h); if (rc) return rc;
     if (!h->comm) return RCW_OK;
-    RCW_HIP(hipStreamSynchronize(h->stream));
+    // the gathered-descriptor scratch is sized by the world: a later rcw_comm_init may have another (and the wait is the communicator's too)
+    RCW_HIP(replace_buffers(h, {&h->d_gather_h, &h->d_gather_c}));
     RCW_NCCL(g_rccl.CommDestroy((ncclComm_t)h->comm));
     h->comm = nullptr; h->comm_rank = 0; h->comm_world = 0;
-    // the gathered-descriptor scratch is sized by the world: a later rcw_comm_init may have another
-    if (h->d_gather_h) (void)hipFree(h->d_gather_h);
-    if (h->d_gather_c) (void)hipFree(h->d_gather_c);
-    h->d_gather_h = h->d_gather_c = nullptr;
     return RCW_OK;
 }
 
@@ -1688,8 +1642,8 @@ int rcw_gather_columns(rcw_handle* h, int32_t* height_all, uint8_t* colour_all)
     const size_t n = (size_t)h->B * h->cfg.num_rays;
     // one fused group: the two all-gathers progress together on the handle's stream, behind the step
     RCW_NCCL(g_rccl.GroupStart());
-    ncclResult_t r1 = g_rccl.AllGather(h->d_col_h, height_all, n, ncclInt32, (ncclComm_t)h->comm, h->stream);
-    ncclResult_t r2 = g_rccl.AllGather(h->d_col_c, colour_all, n, ncclUint8, (ncclComm_t)h->comm, h->stream);
+    ncclResult_t r1 = g_rccl.AllGather(h->d_col_h.get(), height_all, n, ncclInt32, (ncclComm_t)h->comm, h->stream);
+    ncclResult_t r2 = g_rccl.AllGather(h->d_col_c.get(), colour_all, n, ncclUint8, (ncclComm_t)h->comm, h->stream);
     RCW_NCCL(g_rccl.GroupEnd());
     RCW_NCCL(r1); RCW_NCCL(r2);
     return RCW_OK;
@@ -1709,10 +1663,10 @@ int rcw_gather_observations(rcw_handle* h, int32_t mode, void* frames_all)
     if (mode != RCW_GATHER_COLUMNS) return fail(RCW_ERR_INVALID_ARGUMENT, "unknown gather mode %d", mode);
     const size_t all = (size_t)h->B * h->comm_world;
     if ((long long)all > 0x7fffffffll) return fail(RCW_ERR_UNSUPPORTED, "global batch too large");
-    if (!h->d_gather_h) RCW_HIP(hipMalloc(&h->d_gather_h, all * N * sizeof(int32_t)));
-    if (!h->d_gather_c) RCW_HIP(hipMalloc(&h->d_gather_c, all * N));
-    rc = rcw_gather_columns(h, (int32_t*)h->d_gather_h, (uint8_t*)h->d_gather_c); if (rc) return rc;
-    RCW_HIP(rcw_launch_expand(h->dev, (const int32_t*)h->d_gather_h, (const uint8_t*)h->d_gather_c, (int32_t)all,
+    if (!h->d_gather_h.get()) RCW_HIP(h->d_gather_h.hipMalloc(all * N * sizeof(int32_t)));
+    if (!h->d_gather_c.get()) RCW_HIP(h->d_gather_c.hipMalloc(all * N));
+    rc = rcw_gather_columns(h, h->d_gather_h.get<int32_t>(), h->d_gather_c.get<uint8_t>()); if (rc) return rc;
+    RCW_HIP(rcw_launch_expand(h->dev, h->d_gather_h.get<int32_t>(), h->d_gather_c.get<uint8_t>(), (int32_t)all,
                               (uint32_t*)frames_all, h->stream));
     return RCW_OK;
 }
@@ -1774,16 +1728,16 @@ int rcw_direction_table64(rcw_handle* h, double* out)
 int rcw_timer_start(rcw_handle* h)
 {
     int rc = check_handle(h); if (rc) return rc;
-    RCW_HIP(hipEventRecord(h->ev_start, h->stream));
+    RCW_HIP(hipEventRecord(h->ev_start.get(), h->stream));
     return RCW_OK;
 }
 int rcw_timer_stop(rcw_handle* h, float* elapsed_ms)
 {
     int rc = check_handle(h); if (rc) return rc;
     if (!elapsed_ms) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    RCW_HIP(hipEventRecord(h->ev_stop, h->stream));
-    RCW_HIP(hipEventSynchronize(h->ev_stop));
-    RCW_HIP(hipEventElapsedTime(elapsed_ms, h->ev_start, h->ev_stop));
+    RCW_HIP(hipEventRecord(h->ev_stop.get(), h->stream));
+    RCW_HIP(hipEventSynchronize(h->ev_stop.get()));
+    RCW_HIP(hipEventElapsedTime(elapsed_ms, h->ev_start.get(), h->ev_stop.get()));
     return RCW_OK;
 }
 
@@ -1792,8 +1746,8 @@ int rcw_profile(rcw_handle* h, int32_t enable)
     int rc = check_handle(h); if (rc) return rc;
     RCW_HIP(hipStreamSynchronize(h->stream));
     if (enable && h->prof_ev.empty()) {
-        h->prof_ev.resize(4 * kProfileSlots, nullptr);
-        for (auto& ev : h->prof_ev) RCW_HIP(hipEventCreate(&ev));
+        h->prof_ev.resize(4 * kProfileSlots);
+        for (RcwEvent& ev : h->prof_ev) RCW_HIP(ev.hipEventCreate());
     }
     h->profiling = enable != 0;
     h->prof_count = 0;
@@ -1808,9 +1762,9 @@ int rcw_profile_read(rcw_handle* h, float* cast_ms, float* top_view_ms, float* f
     double c = 0.0, t = 0.0, f = 0.0;
     for (int k = 0; k < h->prof_count; ++k) {
         float a = 0.0f, b = 0.0f, d = 0.0f;
-        RCW_HIP(hipEventElapsedTime(&a, h->prof_ev[4 * k], h->prof_ev[4 * k + 1]));
-        RCW_HIP(hipEventElapsedTime(&b, h->prof_ev[4 * k + 1], h->prof_ev[4 * k + 2]));
-        RCW_HIP(hipEventElapsedTime(&d, h->prof_ev[4 * k + 2], h->prof_ev[4 * k + 3]));
+        RCW_HIP(hipEventElapsedTime(&a, h->prof_ev[4 * k].get(), h->prof_ev[4 * k + 1].get()));
+        RCW_HIP(hipEventElapsedTime(&b, h->prof_ev[4 * k + 1].get(), h->prof_ev[4 * k + 2].get()));
+        RCW_HIP(hipEventElapsedTime(&d, h->prof_ev[4 * k + 2].get(), h->prof_ev[4 * k + 3].get()));
         c += a;
         if (h->dev.top_split) { f += b; t += d; } else { t += b; f += d; }      // two-kernel top view: cast | fill (+ draw beside it) | store
     }
@@ -1840,12 +1794,11 @@ int rcw_update_top_view_form(rcw_handle* h, int32_t* form)
 int rcw_set_top_view_form(rcw_handle* h, int32_t form, int32_t runs)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (!h->d_top_view) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
+    if (!h->d_top_view.get()) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
     if (form != 0 && form != RCW_TOP_VIEW_IN_PLACE && form != RCW_TOP_VIEW_ONE_KERNEL && form != RCW_TOP_VIEW_TWO_KERNELS)
         return fail(RCW_ERR_INVALID_ARGUMENT, "form must be 0 (automatic) or RCW_TOP_VIEW_IN_PLACE / ONE_KERNEL / TWO_KERNELS (got %d)", form);
     if (runs < 0 || runs > 8) return fail(RCW_ERR_INVALID_ARGUMENT, "runs must be 0 (automatic) or 1..8 (got %d)", runs);
-    RCW_HIP(hipStreamSynchronize(h->stream));        // the scratch of the current form may be in use
-    rc = plan_top_view(h, form, runs, /*lenient=*/false);
+    rc = plan_top_view(h, form, runs, /*lenient=*/false);   // (waits for every stream first: the scratch of the current form may be in use)
     if (rc != RCW_OK) {                               // leave a usable handle behind: back to the automatic choice
         const int rc2 = plan_top_view(h, 0, 0, true);
         return rc2 != RCW_OK ? rc2 : rc;

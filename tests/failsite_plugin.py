@@ -16,7 +16,7 @@ def pytest_sessionfinish(session, exitstatus):
     n = lib.rcw_dev_fail_sites(buf, 4096)
     hit = {i for i in range(n) if buf[i]}
     src = open(os.path.join(ROOT, "raycastworlds.jl_amd", "csrc", "rcw_api.hip")).read().splitlines()
-    sites = [i + 1 for i, l in enumerate(src) if re.search(r"\bfail\(|RCW_HIP\(|RCW_TRY\(|RCW_NCCL\(", l) and not l.lstrip().startswith(("#define", "//", "int fail", "return fail(code"))]
+    sites = [i + 1 for i, l in enumerate(src) if re.search(r"\bfail\(|RCW_HIP\(|RCW_NCCL\(", l) and not l.lstrip().startswith(("#define", "//", "int fail", "return fail(code"))]
     tag = os.environ.get("FAILCOV_TAG", "run")
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", f"failcov_{tag}.txt"), "w") as f:

@@ -1410,6 +1410,41 @@ def test_create_destroy_cycles_leave_device_memory_unchanged(rcw):
     assert free0 - free1 <= 8 << 20, f"device memory shrank by {(free0 - free1) / 2**20:.1f} MiB over 25 cycles"
 
 
+def test_create_failing_midway_returns_what_it_took(rcw, oracle):
+    """rcw_create that fails AFTER some of its allocations succeeded (nothing else in the suite takes that path): a configuration
+    validate_config accepts whose camera-view batch alone is 64 TiB (4096 agents x 4096 columns x 2^20 rows x 4 B), behind a stream,
+    two events and nine buffers of a few hundred KiB in all.  The runtime refuses the allocation — an error return, provoked once —:
+    RCW_ERR_OUT_OF_MEMORY, a NULL handle, a message that names the hipMalloc, free device memory back where it was (the tolerance of
+    the cycles test above), and an ordinary handle created right after steps bit-exactly."""
+    import ctypes as C
+
+    torch = pytest.importorskip("torch")
+    from raycastworlds_jl_amd import _capi
+
+    lib = _capi.load()
+    env, orc = _make(rcw, oracle, 32, seed=5, **CFG1)       # (the first handle of a process loads the code objects: not what is measured)
+    env.close()
+    gc.collect()
+    torch.cuda.synchronize()
+    free0, _ = torch.cuda.mem_get_info()
+    cfg = _capi.RcwConfig()
+    assert lib.rcw_config_default(C.byref(cfg)) == 0
+    cfg.num_rays, cfg.num_directions, cfg.height_camera_view_pu = 4096, 4, 1 << 20
+    h = C.c_void_p()
+    rc = lib.rcw_create(C.byref(cfg), 4096, 0, 1, C.byref(h))
+    msg = _capi.last_error(lib)
+    assert rc == _capi.RCW_ERR_OUT_OF_MEMORY, (rc, msg)
+    assert not h.value
+    assert "hipMalloc" in msg and "d_obs" in msg, msg
+    torch.cuda.synchronize()
+    free1, _ = torch.cuda.mem_get_info()
+    assert free0 - free1 <= 8 << 20, f"the failed rcw_create kept {(free0 - free1) / 2**20:.1f} MiB of device memory"
+    env, orc = _make(rcw, oracle, 32, seed=6, **CFG1)
+    assert_state_equal(env, orc, rays=True, where="after the failed create")
+    _rollout(rcw, env, orc, 20, np.random.default_rng(11), check_every=1)
+    env.close()
+
+
 def test_dropped_environment_is_finalised_and_its_memory_returned(rcw):
     """with the RLBase tensors made (reward / is_terminated / state, the cached aliases), an environment
     that is simply dropped — no close() — is collected and its device memory returned; while one of its tensors lives,
