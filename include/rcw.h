@@ -252,8 +252,13 @@ RCW_API int rcw_sync(rcw_handle* h);
 RCW_API int rcw_clear_error(rcw_handle* h);
 
 /* RLBase.state(env) SR:576: the camera view batch, aliased — the pointer is stable for
- * the handle's lifetime (or until rcw_bind_obs) and is overwritten by the next step.  With a learner view set with
- * RCW_VIEW_ONLY (below) steps do not write it: it holds the last frames rendered until rcw_update_camera_view. */
+ * the handle's lifetime (or until rcw_bind_obs).  The buffer is the library's between calls: after every step it
+ * equals the reference's camera_view for every agent, and a step may leave untouched the frames of agents whose view
+ * it did not change (the one-launch step does not store them again).  A caller that writes into the buffer calls
+ * rcw_update_camera_view or rcw_bind_obs before the next step; rcw_bind_obs — also with the pointer the handle already
+ * has — makes the next step store every frame, so callers that alternate two buffers get every step written in full.
+ * With a learner view set with RCW_VIEW_ONLY (below) steps do not write it: it holds the last frames rendered until
+ * rcw_update_camera_view. */
 RCW_API int rcw_obs_device_ptr(rcw_handle* h, void** device_ptr);
 /* Copy frames of agents [first, first+count) to host: UInt32 (H_cam, N, count). */
 RCW_API int rcw_obs_copy(rcw_handle* h, uint32_t* out_host, int32_t first, int32_t count);

@@ -382,6 +382,9 @@ end
 
 # Device pointer of the observation batch (aliased, stable): for AMDGPU.jl users
 #   unsafe_wrap(ROCArray{UInt32,3}, Ptr{UInt32}(ptr), (H_cam, N, B))
+# The buffer is the library's between calls.  After every step it equals the reference's `camera_view` for every agent.
+# A step may leave untouched the frames of agents whose view it did not change.  A caller that writes into the buffer
+# calls `RCW.update_camera_view!(env)` or `bind_obs!` before the next step.
 function camera_view_device_ptr(env::BatchedSingleRoom)
     p = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:rcw_obs_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
@@ -395,7 +398,9 @@ function camera_view(env::BatchedSingleRoom)
     end
     return env.camera_view
 end
-# Render into caller-owned device memory instead (double-buffered observations); C_NULL restores the library's buffer
+# Render into caller-owned device memory instead (double-buffered observations); C_NULL restores the library's buffer.
+# The step after a `bind_obs!` — also with the pointer the handle already has — stores every frame: callers that alternate
+# two buffers get every step written in full.
 bind_obs!(env::BatchedSingleRoom, device_ptr::Ptr{Cvoid}) =
     check(ccall((:rcw_bind_obs, librcw), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), env.handle, device_ptr))
 

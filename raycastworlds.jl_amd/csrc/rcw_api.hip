@@ -99,7 +99,11 @@ struct rcw_handle {
     RcwBuf d_step_flags, d_step_hc; uint32_t step_epoch = 0;   // development experiment only (RCW_STEP_FUSED)
     // the one-launch step (rcw_fill256_cast_kernel): two buffers of [B][5][N] packed column words — d_spec[spec_cur] holds the frames of the
     // CURRENT state (slot 0) and of its four successors (slots 1..4), written by the last casting launch; spec_primed: for every agent
-    RcwBuf d_spec[2]; int spec_cur = 0; bool spec_primed = false;
+    // (each buffer ends in one byte per agent: which of its slots hold the very frame slot 0 holds — rcw_cast.hip, cast_body).
+    // obs_current: dev.obs holds, for EVERY agent, the frame of the state the primed slots were cast from — the one-launch step may then leave
+    // the frames of agents whose view it does not change as they are.  Set by obs_is_current() only, cleared by obs_unknown() / spec_forget()
+    // only (next to launch_step_camera); false costs nothing but the skip: the next one-launch step writes every pixel and sets it again.
+    RcwBuf d_spec[2]; int spec_cur = 0; bool spec_primed = false, obs_current = false;
     int spec_on = 0;                   // a step is ONE launch (rcw_fill256_cast_kernel)
     // The (height_line_pu, colour id) descriptors of the current frames (d_col_h / d_col_c) are what the two-launch step hands from its cast
     // kernel to its fill kernel; the one-launch step's fill reads the slots instead, and every store of the casting workgroups costs the
@@ -228,6 +232,11 @@ hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool 
     return e;
 }
 
+// rcw_handle::obs_current and spec_primed: the only places that write them, besides the priming path of launch_step_camera (spec_primed = true)
+void obs_is_current(rcw_handle* h) { h->obs_current = true; }
+void obs_unknown(rcw_handle* h) { h->obs_current = false; }
+void spec_forget(rcw_handle* h) { h->spec_primed = false; h->obs_current = false; }   // the slots describe nothing any more: so do their bytes
+
 // One step = cast kernel + fill kernel, back to back on the handle's stream (+ the top view when the handle renders
 // it: before the fill with the one-kernel form, around it with the two-kernel form).  With profiling on,
 // HIP events bracket each kernel (what bench.py's roofline block reads the fill kernel's
@@ -235,6 +244,9 @@ hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool 
 hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev)
 {
     const RcwDev& d = h->dev;
+    // Whatever fails below, and every form but the one-launch step and what primes it, leaves the fact cleared.
+    const bool was_current = h->obs_current && h->spec_primed;
+    obs_unknown(h);
     const bool prof = h->profiling && h->prof_count < kProfileSlots;
     const RcwEvent* ev = prof ? &h->prof_ev[4 * h->prof_count] : nullptr;
     hipError_t e;
@@ -243,7 +255,7 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
         // one launch's pointers for ever.  A handle whose step is captured keeps the two-launch form from then on (replays advance the
         // state behind the library's back, so its slots can never be trusted again): rcw_step_form says so.
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { h->spec_on = 0; h->step_captured = true; h->spec_primed = false; }
+        if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { h->spec_on = 0; h->step_captured = true; spec_forget(h); }
     }
     if (prof && (e = hipEventRecord(ev[0].get(), h->stream)) != hipSuccess) return e;
     if (h->spec_on) {
@@ -253,19 +265,22 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
             // casting launch left in `cur`; the casting workgroups commit the actions and cast the new states' successors into the other buffer
             uint16_t* const next = h->d_spec[h->spec_cur ^ 1].get<uint16_t>();
             if (prof && ((e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess || (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess)) return e;
-            if ((e = rcw_launch_step_spec(d, actions_dev, nullptr, cur, next, true, h->cols_live, h->stream)) != hipSuccess) return e;
+            if ((e = rcw_launch_step_spec(d, actions_dev, nullptr, cur, next, true, h->cols_live, was_current, h->stream)) != hipSuccess) return e;
             h->spec_cur ^= 1;
+            obs_is_current(h);                                    // (skipped or not: every agent's frame is the new state's)
             if (!h->cols_live) h->cols_stale = true;
             if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
             return hipSuccess;
         }
         // reset! / set_state (no action, maybe a mask) or a first step: the casting workgroups alone — dynamics if any, the current frame's
         // descriptors, and the (masked) agents' slots in place —, then the camera fill as a launch of its own
-        if ((e = rcw_launch_step_spec(d, actions_dev, mask_dev, nullptr, cur, false, true, h->stream)) != hipSuccess) return e;
+        if ((e = rcw_launch_step_spec(d, actions_dev, mask_dev, nullptr, cur, false, true, false, h->stream)) != hipSuccess) return e;
         if (!mask_dev) h->cols_stale = false;                 // (with a mask: the masked agents' descriptors are fresh — the fill below reads only those —, the others' as stale as before)
         if (!mask_dev) h->spec_primed = true;
         if (prof && ((e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess || (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess)) return e;
         if ((e = rcw_launch_fill(d, d.col_h, d.col_c, d.obs, (long long)d.B * d.N, mask_dev, h->stream)) != hipSuccess) return e;
+        // every agent painted and every slot primed — or, with a mask, exactly the agents repainted whose slots were rewritten: as it was
+        if (h->spec_primed && (!mask_dev || was_current)) obs_is_current(h);
         if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
         return hipSuccess;
     }
@@ -320,6 +335,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
         const hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
         return e == hipSuccess && h->view_fmt != RCW_VIEW_OFF ? launch_view(h, mask_dev) : e;
     }
+    obs_unknown(h);                                               // (RCW_VIEW_ONLY: the camera view is not painted)
     const bool prof = h->profiling && h->prof_count < kProfileSlots;
     const RcwEvent* ev = prof ? &h->prof_ev[4 * h->prof_count] : nullptr;
     hipError_t e;
@@ -668,7 +684,7 @@ int plan_step_form(rcw_handle* h, int want)
     const bool eligible = rcw_step_spec_eligible(d) != 0;
     if (view_only(h)) {                                // (the cast kernel followed by the view kernel: no camera fill to fuse)
         if (want == RCW_STEP_ONE_LAUNCH) return fail(RCW_ERR_UNSUPPORTED, "the handle's learner view is set with RCW_VIEW_ONLY: a step is the cast kernel and the view kernel");
-        h->spec_on = 0; h->spec_primed = false; h->step_form_want = want;
+        h->spec_on = 0; spec_forget(h); h->step_form_want = want;
         return RCW_OK;
     }
     if (want == RCW_STEP_ONE_LAUNCH && !eligible)
@@ -682,7 +698,7 @@ int plan_step_form(rcw_handle* h, int want)
         }
         if (want == RCW_STEP_ONE_LAUNCH) h->step_captured = false;
     }
-    if (on && !h->spec_on) h->spec_primed = false;
+    if (on != (h->spec_on != 0)) spec_forget(h);                    // (a change of form, either way)
     h->spec_on = on ? 1 : 0;
     h->step_form_want = want;
     return RCW_OK;
@@ -1169,6 +1185,7 @@ int rcw_bind_obs(rcw_handle* h, void* device_ptr)
     // No synchronisation: the pointer travels in the kernel arguments of the launches that follow,
     // work already enqueued keeps the buffer it was launched with (double-buffered observations).
     h->dev.obs = device_ptr ? (uint32_t*)device_ptr : h->d_obs.get<uint32_t>();
+    obs_unknown(h);      // (also with the pointer it had: the caller may have written into the buffer — the next step stores every frame)
     return RCW_OK;
 }
 
@@ -1180,7 +1197,7 @@ int rcw_reset(rcw_handle* h, const uint8_t* mask_host, uint64_t seed)
     // (the seed is the HANDLE's: an agent that is done under auto_reset and NOT in the mask is re-sampled by its next action with the new
     // seed — but the one-launch step has already cast that agent's successors from a preview drawn with the old one: every agent's slots are
     // cast again by the next step, as a launch of its own)
-    if (seed != h->dev.seed && h->dev.auto_reset && mask_dev) h->spec_primed = false;
+    if (seed != h->dev.seed && h->dev.auto_reset && mask_dev) spec_forget(h);
     h->dev.seed = seed;
     RCW_HIP(rcw_launch_reset(h->dev, mask_dev, h->stream));            // SR:110-132
     RCW_HIP(launch_step(h, nullptr, mask_dev));    // SR:134, SR:329
@@ -1273,8 +1290,10 @@ int rcw_cast_rays(rcw_handle* h)
 int rcw_update_camera_view(rcw_handle* h)
 {
     int rc = check_handle(h); if (rc) return rc;
+    obs_unknown(h);
     rc = ensure_columns(h); if (rc) return rc;
     RCW_HIP(rcw_launch_fill(h->dev, h->dev.col_h, h->dev.col_c, h->dev.obs, (long long)h->dev.B * h->dev.N, nullptr, h->stream));
+    if (h->spec_on && h->spec_primed) obs_is_current(h);            // every agent's current frame, which is what slot 0 of the primed slots holds
     return RCW_OK;
 }
 

@@ -114,14 +114,20 @@ __device__ __forceinline__ void spec_derive_rows(T hx, T hy, const T* r_dx, cons
 // slots of an agent lie together, [B][5][N]: what the casting workgroups write is ONE stream through memory beside the fill's);
 // COLS && col_h_a: also the (height_line_pu, colour id) descriptors of the current frame, as cast_column.  hx, hy: the heading's
 // direction vector (for the columns beyond kCastCols a lane, whose entries are loaded and derived here).  Returns whether a ray left the map.
+// Which successor frames EQUAL the current one (the fill of the next launch need not store them): the current state's fan (COLS) keeps
+// this lane's words of its first kCastCols columns in w0[]; every later fan compares its word with the current one of the same column and
+// ORs `slots` into `differs` where they differ — in registers: a vector memory operation of the casting half costs the launch several
+// times its bytes, a vector instruction next to nothing.  Only the columns beyond kCastCols a lane (more than 1024 view columns) re-read
+// the slot-0 word, which this very thread stored earlier in program order.
 template <typename T, bool TIE_LE, bool DIST_PRE, bool COLS>
 __device__ __forceinline__ bool spec_fan(const RcwDev& p, const uint8_t* tb, int tid, int nthr, T x, T y,
                                          const T* r_dx, const T* r_dy, const T* r_ddx, const T* r_ddy, const T* r_dot, const T* tab, T hx, T hy,
-                                         int32_t* col_h_a, uint8_t* col_c_a, uint16_t* slot_a, uint32_t stride, uint32_t slots)
+                                         int32_t* col_h_a, uint8_t* col_c_a, uint16_t* slot_a, uint32_t stride, uint32_t slots,
+                                         uint16_t* w0, uint32_t& differs)
 {
     const int N = p.N;
     bool left = false;
-    auto column = [&](int i, T dx, T dy, T ddx, T ddy, T dot) {
+    auto column = [&](int i, T dx, T dy, T ddx, T ddy, T dot) -> uint16_t {
         const RayHit<T> r = cast_ray_guarded<T, TIE_LE, DIST_PRE>(tb, p.H, p.W, x, y, dx, dy, ddx, ddy);
         const int hl = height_line_pu<T>(p, r.dist, dot);
         const int h = r.oob ? p.Hc : hl;
@@ -138,16 +144,21 @@ __device__ __forceinline__ bool spec_fan(const RcwDev& p, const uint8_t* tb, int
         const uint16_t w = (uint16_t)spec_word(p.Hc, h, cid);
         uint16_t* const q = slot_a + k;
 #ifdef RCW_DEV_SWITCHES
-        if (p.spec_debug & 4) { asm volatile("" :: "v"(w)); left |= r.oob; return; }   // (timing probe: no slot stores)
+        if (p.spec_debug & 4) { asm volatile("" :: "v"(w)); left |= r.oob; return w; }   // (timing probe: no slot stores)
 #endif
 #pragma unroll
         for (int s = 0; s < 5; ++s) if (slots & (1u << s)) q[(uint32_t)s * stride] = w;   // (wave-uniform)
         left |= r.oob;
+        return w;
     };
 #pragma unroll
     for (int k = 0; k < kCastCols; ++k) {
         const int i = tid + k * nthr;
-        if (i < N) column(i, r_dx[k], r_dy[k], r_ddx[k], r_ddy[k], r_dot[k]);
+        if (i < N) {
+            const uint16_t w = column(i, r_dx[k], r_dy[k], r_ddx[k], r_ddy[k], r_dot[k]);
+            if (COLS) w0[k] = w;
+            else if (w != w0[k]) differs |= slots;
+        }
     }
     if (N > kCastCols * nthr) {                                             // more than kCastCols columns a lane
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
@@ -155,7 +166,8 @@ __device__ __forceinline__ bool spec_fan(const RcwDev& p, const uint8_t* tb, int
             const T dx = tab[i], dy = tab[N + i];
             T ddx, ddy, dot;
             spec_derive<T>(dx, dy, hx, hy, ddx, ddy, dot);
-            column(i, dx, dy, ddx, ddy, dot);
+            const uint16_t w = column(i, dx, dy, ddx, ddy, dot);
+            if (!COLS && w != slot_a[N - 1 - i]) differs |= slots;          // (slot 0 of the same image column)
         }
     }
     return left;
@@ -270,6 +282,8 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
     for (int k = tid + nthr; k < 2 * H; k += nthr) (k < H ? tb - H + k : tb + HW + (k - H))[0] = 1;
     T* const s_pose = reinterpret_cast<T*>(lds + ((HW + 2 * H + 15) / 16) * 4);       // [2] + the heading (auto-reset)
     int& s_pose_d = *reinterpret_cast<int*>(s_pose + 2);
+    uint32_t& s_differs = *(reinterpret_cast<uint32_t*>(s_pose) + 6);                 // (SPEC, a workgroup per agent: which successor frames differ from the current one)
+    if (SPEC && !WAVE && tid == 0) s_differs = 0u;
 #pragma unroll
     for (int k = 0; k < kCastTiles; ++k) {                                  // (as stage_tile_bytes: the last tile reads as an obstacle)
         const int t = tid + k * nthr;
@@ -368,13 +382,15 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
             b_free = cb.wall == 0 && cb.goal == 0;
         }
         const uint32_t stay = 1u | (!reborn && !f_free ? 2u : 0u) | (!reborn && !b_free ? 4u : 0u);
-        left_the_map = spec_fan<T, TIE_LE, DIST_PRE, true>(p, tb, tid, nthr, x, y, r_dx, r_dy, r_ddx, r_ddy, r_dot, tab, dvn.x, dvn.y, ch, col_c_a, slot_a, stride, stay);
+        uint16_t w0[kCastCols];                                             // this lane's words of the current frame
+        uint32_t differs = 0u;                                              // bit s: a word of slot s differs from slot 0's (this lane's columns)
+        left_the_map = spec_fan<T, TIE_LE, DIST_PRE, true>(p, tb, tid, nthr, x, y, r_dx, r_dy, r_ddx, r_ddy, r_dot, tab, dvn.x, dvn.y, ch, col_c_a, slot_a, stride, stay, w0, differs);
 #ifdef RCW_DEV_SWITCHES
         if (p.spec_debug & 16) return;                                      // (timing probe: the current state's fan only)
 #endif
         if (!reborn) {
-            if (f_free) (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, xf, yf, r_dx, r_dy, r_ddx, r_ddy, r_dot, tab, dvn.x, dvn.y, nullptr, nullptr, slot_a, stride, 2u);
-            if (b_free) (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, xb, yb, r_dx, r_dy, r_ddx, r_ddy, r_dot, tab, dvn.x, dvn.y, nullptr, nullptr, slot_a, stride, 4u);
+            if (f_free) (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, xf, yf, r_dx, r_dy, r_ddx, r_ddy, r_dot, tab, dvn.x, dvn.y, nullptr, nullptr, slot_a, stride, 2u, w0, differs);
+            if (b_free) (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, xb, yb, r_dx, r_dy, r_ddx, r_ddy, r_dot, tab, dvn.x, dvn.y, nullptr, nullptr, slot_a, stride, 4u, w0, differs);
 #pragma unroll
             for (int turn = 0; turn < 2; ++turn) {
                 const int dt = turn == 0 ? (d_new + 1 >= p.nd ? 0 : d_new + 1) : (d_new - 1 < 0 ? p.nd - 1 : d_new - 1);   // UT:13-14
@@ -385,7 +401,7 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
 #endif
                 spec_load_rows<T>(tt, tid, nthr, N, r_dx, r_dy);
                 spec_derive_rows<T>(dvt.x, dvt.y, r_dx, r_dy, r_ddx, r_ddy, r_dot);
-                (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, x, y, r_dx, r_dy, r_ddx, r_ddy, r_dot, tt, dvt.x, dvt.y, nullptr, nullptr, slot_a, stride, turn == 0 ? 8u : 16u);
+                (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, x, y, r_dx, r_dy, r_ddx, r_ddy, r_dot, tt, dvt.x, dvt.y, nullptr, nullptr, slot_a, stride, turn == 0 ? 8u : 16u, w0, differs);
             }
         } else {
             agent_sync<WAVE>();                                             // (every lane has read the tile bytes of the done state)
@@ -400,8 +416,20 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
             const vec2 dvr = Real<T>::dir_table(p)[dr];
             spec_load_rows<T>(tt, tid, nthr, N, r_dx, r_dy);
             spec_derive_rows<T>(dvr.x, dvr.y, r_dx, r_dy, r_ddx, r_ddy, r_dot);
-            (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, xr, yr, r_dx, r_dy, r_ddx, r_ddy, r_dot, tt, dvr.x, dvr.y, nullptr, nullptr, slot_a, stride, 30u);
+            (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, xr, yr, r_dx, r_dy, r_ddx, r_ddy, r_dot, tt, dvr.x, dvr.y, nullptr, nullptr, slot_a, stride, 30u, w0, differs);
         }
+        // One byte per agent behind the slots ([B][5][N] words | [B] bytes): bit s set <=> all N words of slot s equal slot 0's — the frame
+        // the action s selects is the one the observation buffer holds (bit 0 and the `stay` slots by construction).
+        uint32_t any = 0u;
+        if (WAVE) {
+#pragma unroll
+            for (int s = 1; s < 5; ++s) any |= __builtin_amdgcn_ballot_w64((differs >> s) & 1u) != 0ull ? 1u << s : 0u;
+        } else {
+            if (differs) atomicOr(&s_differs, differs);
+            agent_sync<WAVE>();
+            any = s_differs;
+        }
+        if (tid == 0) (reinterpret_cast<uint8_t*>(spec_out + (size_t)5 * (size_t)p.B * (size_t)N))[a] = (uint8_t)(~any & 31u);
         if (left_the_map) { p.err[0] = RCW_ERR_OUT_OF_BOUNDS; p.status[a] = RCW_ERR_OUT_OF_BOUNDS; }   // (Julia: BoundsError in cast_ray)
         return;
     }
@@ -464,8 +492,11 @@ __global__ __launch_bounds__(kBlock) void rcw_cast_kernel(const RcwDev p,
 // casting half alone: it PRIMES the slots behind a reset / set_state (or a first step), the camera fill following as a launch of its own.
 template <bool PLAIN>
 __device__ __forceinline__ void fill256_spec_body(const RcwDev& p, const uint8_t* __restrict__ actions, const uint16_t* __restrict__ slots,
-                                                  u32x4* __restrict__ out, long long total_cols, int block, int blocks, int n_shift)
+                                                  u32x4* __restrict__ out, long long total_cols, int block, int blocks, int n_shift, uint32_t keep)
 {
+    // keep = 1: the observation buffer holds every agent's CURRENT frame (the handle says so: rcw_api.hip, obs_current) — the chunks of an
+    // agent whose selected successor frame equals it (the casting half's byte behind the slots) are not stored again; 0: every pixel is written.
+    const uint8_t* const same = reinterpret_cast<const uint8_t*>(slots + (size_t)5 * (size_t)p.B * (size_t)p.N);
     // (Raising the fill wavefronts' priority over the casting ones — s_setprio 3 — changes nothing: what the casting half costs this
     // launch is its memory operations, not its issue slots: profiles/r06_step_forms.txt.)
     const int lane = threadIdx.x & 63;
@@ -482,12 +513,14 @@ __device__ __forceinline__ void fill256_spec_body(const RcwDev& p, const uint8_t
             // the chunk's agent (the launcher takes this form below 2^29 columns), its action, the slot the action names
             const uint32_t a = n_shift >= 0 ? (uint32_t)mine >> n_shift : (uint32_t)mine / (uint32_t)p.N;   // (n_shift: log2(N) where N is a power of two, else -1)
             const uint32_t act = actions[a];
-            asm volatile("" :: "v"(act) : "memory");
+            const uint32_t eq = same[a];        // (its address depends on `a` only: in flight with the action)
+            asm volatile("" :: "v"(act), "v"(eq) : "memory");
             const uint32_t sel = act - 1u < (uint32_t)RCW_NUM_ACTIONS ? act : 0u;   // (an action outside 1..4: the agent is not stepped, SR:140)
             const uint32_t w = slots[(size_t)mine + (size_t)(4u * a + sel) * (size_t)p.N];   // [B][5][N]: (5 a + sel) N + (mine - a N)
             asm volatile("" :: "v"(w) : "memory");
             pad_l = (int)(w & 0x1fffu);
             colour_l = p.colour[(w >> 13) & 3u];
+            if ((eq >> sel) & keep) pad_l = -1; // the frame is there already
         }
 #pragma unroll 4
         for (int l = 0; l < 64; ++l) {
@@ -509,8 +542,9 @@ __device__ __forceinline__ void fill256_spec_body(const RcwDev& p, const uint8_t
 // 2 M-byte load).  The launcher takes this form below 2^31 chunks.
 template <int M>
 __device__ __forceinline__ void fill_window_spec_body(const RcwDev& p, const uint8_t* __restrict__ actions, const uint16_t* __restrict__ slots,
-                                                      u32x4* __restrict__ out, long long total_chunks, int block, int blocks, int n_shift)
+                                                      u32x4* __restrict__ out, long long total_chunks, int block, int blocks, int n_shift, uint32_t keep)
 {
+    const uint8_t* const same = reinterpret_cast<const uint8_t*>(slots + (size_t)5 * (size_t)p.B * (size_t)p.N);   // (as fill256_spec_body)
     const int lane = threadIdx.x & 63;
     const long long G = (long long)blocks * (kBlock / 64);
     const long long g = (long long)block * (kBlock / 64) + (threadIdx.x >> 6);
@@ -530,7 +564,8 @@ __device__ __forceinline__ void fill_window_spec_body(const RcwDev& p, const uin
             const uint32_t a = n_shift >= 0 ? col0 >> n_shift : col0 / (uint32_t)p.N;              // (a chunk never spans two agents: N H_cam % 256 == 0 here)
             rb_l = M == 1 ? (int)((uint32_t)mine - col0 * k) * 256 : 0;
             const uint32_t act = actions[a];
-            asm volatile("" :: "v"(act) : "memory");
+            const uint32_t eq = same[a];
+            asm volatile("" :: "v"(act), "v"(eq) : "memory");
             const uint32_t sel = act - 1u < (uint32_t)RCW_NUM_ACTIONS ? act : 0u;
             struct __attribute__((aligned(2 * M))) Words { uint16_t w[M]; };
             const Words ws = *reinterpret_cast<const Words*>(slots + ((size_t)col0 + (size_t)(4u * a + sel) * (size_t)p.N));   // [B][5][N]
@@ -540,6 +575,7 @@ __device__ __forceinline__ void fill_window_spec_body(const RcwDev& p, const uin
                 pad_l[j] = (int)(ws.w[j] & 0x1fffu);
                 colour_l[j] = p.colour[(ws.w[j] >> 13) & 3u];
             }
+            if ((eq >> sel) & keep) pad_l[0] = -1;   // the frame is there already (the chunk's M columns are one agent's)
         }
 #pragma unroll 4
         for (int l = 0; l < 64; ++l) {
@@ -584,13 +620,13 @@ __device__ __forceinline__ void cast_successors(const RcwDev& p, const uint8_t* 
 template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE>
 __global__ __launch_bounds__(kBlock) void rcw_fill256_cast_kernel(const RcwDev p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask,
                                                                   u32x4* __restrict__ out, long long total_cols, int fill_blocks,
-                                                                  const uint16_t* __restrict__ slots_in, uint16_t* __restrict__ slots_out, int lds_words, int n_shift, int cols)
+                                                                  const uint16_t* __restrict__ slots_in, uint16_t* __restrict__ slots_out, int lds_words, int n_shift, int cols, int keep)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 #ifdef RCW_DEV_SWITCHES
     if (p.spec_debug & ((int)blockIdx.x < fill_blocks ? 2 : 1)) return;     // (timing probes: one half of the launch alone)
 #endif
-    if ((int)blockIdx.x < fill_blocks) { fill256_spec_body<false>(p, actions, slots_in, out, total_cols, (int)blockIdx.x, fill_blocks, n_shift); return; }
+    if ((int)blockIdx.x < fill_blocks) { fill256_spec_body<false>(p, actions, slots_in, out, total_cols, (int)blockIdx.x, fill_blocks, n_shift, (uint32_t)keep); return; }
     cast_successors<T, TIE_LE, DIST_PRE, WAVE>(p, actions, mask, (int)blockIdx.x - fill_blocks, slots_out, lds, lds_words, cols);
 }
 
@@ -603,13 +639,13 @@ template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE>
 __global__ __launch_bounds__(kBlock) void rcw_fill_window_cast_kernel(const RcwDev p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask,
                                                                       u32x4* __restrict__ out, long long total_chunks, int fill_blocks,
                                                                       const uint16_t* __restrict__ slots_in, uint16_t* __restrict__ slots_out, int lds_words, int n_shift, int cols,
-                                                                      int window)
+                                                                      int window, int keep)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     if ((int)blockIdx.x < fill_blocks) {
-        if (window == 1) fill_window_spec_body<1>(p, actions, slots_in, out, total_chunks, (int)blockIdx.x, fill_blocks, n_shift);
-        else if (window == 2) fill_window_spec_body<2>(p, actions, slots_in, out, total_chunks, (int)blockIdx.x, fill_blocks, n_shift);
-        else fill_window_spec_body<4>(p, actions, slots_in, out, total_chunks, (int)blockIdx.x, fill_blocks, n_shift);
+        if (window == 1) fill_window_spec_body<1>(p, actions, slots_in, out, total_chunks, (int)blockIdx.x, fill_blocks, n_shift, (uint32_t)keep);
+        else if (window == 2) fill_window_spec_body<2>(p, actions, slots_in, out, total_chunks, (int)blockIdx.x, fill_blocks, n_shift, (uint32_t)keep);
+        else fill_window_spec_body<4>(p, actions, slots_in, out, total_chunks, (int)blockIdx.x, fill_blocks, n_shift, (uint32_t)keep);
         return;
     }
     cast_successors<T, TIE_LE, DIST_PRE, WAVE>(p, actions, mask, (int)blockIdx.x - fill_blocks, slots_out, lds, lds_words, cols);
@@ -752,11 +788,16 @@ int rcw_step_spec_eligible(const RcwDev& p)
     if (rcw_fill_window_columns(p, cols) < 0) return 0;                                                           // another fill kernel's camera height
     return cols * p.Hc / 256 < (1ll << 31) ? 1 : 0;                                                              // chunk ids in 32 bits
 }
-size_t rcw_step_spec_slot_bytes(const RcwDev& p) { return (size_t)5 * (size_t)p.B * (size_t)p.N * sizeof(uint16_t); }
+// ([B][5][N] words, then one byte per agent: which of its slots hold the frame slot 0 holds)
+size_t rcw_step_spec_slot_bytes(const RcwDev& p) { return (size_t)5 * (size_t)p.B * (size_t)p.N * sizeof(uint16_t) + (((size_t)p.B + 15) & ~(size_t)15); }
 hipError_t rcw_launch_step_spec(const RcwDev& p, const uint8_t* actions_dev, const uint8_t* mask_dev, const uint16_t* slots_in,
-                                uint16_t* slots_out, bool with_fill, bool cols, hipStream_t s)
+                                uint16_t* slots_out, bool with_fill, bool cols, bool keep, hipStream_t s)
 {
     const int icols = cols ? 1 : 0;
+    int ikeep = keep ? 1 : 0;
+#ifdef RCW_DEV_SWITCHES
+    if (p.spec_debug & 32) ikeep = 0;                                       // (A/B measurement: every pixel stored, as before the skip)
+#endif
     const size_t per_agent = (rcw_cast_lds_bytes(p) + 15) & ~(size_t)15;
     const int fill_blocks = with_fill ? p.fill_grid : 0;
     const long long total_cols = (long long)p.B * p.N;
@@ -773,14 +814,14 @@ hipError_t rcw_launch_step_spec(const RcwDev& p, const uint8_t* actions_dev, con
         if (window < 0) return hipErrorInvalidValue;
         if (window == 0) {
             if (wave) RCW_DISPATCH_W(rcw_fill256_cast_kernel, true, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
-                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols);
+                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, ikeep);
             else      RCW_DISPATCH_W(rcw_fill256_cast_kernel, false, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
-                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols);
+                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, ikeep);
         } else {
             if (wave) RCW_DISPATCH_W(rcw_fill_window_cast_kernel, true, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
-                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, window);
+                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, window, ikeep);
             else      RCW_DISPATCH_W(rcw_fill_window_cast_kernel, false, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
-                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, window);
+                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, window, ikeep);
         }
     } else {
         if (wave) RCW_DISPATCH_W(rcw_cast_successors_kernel, true, dim3(cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev, slots_out, lds_words);

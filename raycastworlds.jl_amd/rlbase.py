@@ -28,7 +28,10 @@ class RLBaseEnv:
 
 def state(env: RLBaseEnv):
     """`RLBase.state(env)` SR:576: `env.env.camera_view`, ALIASED device memory (no copy, no synchronisation);
-    it is overwritten in place by the next action, as in the reference.  The same object until `bind_obs` moves it.
+    it is updated in place by the next action, as in the reference.  The same object until `bind_obs` moves it.
+    The buffer is the library's between calls: after every step it equals the reference's `camera_view` for every agent,
+    and a step may leave untouched the frames of agents whose view it did not change.  A caller that writes into the
+    buffer calls `update_camera_view_(env.env)` or `env.env.bind_obs(...)` before the next step.
     With `observation="learner_view"`: `env.env.learner_view`, aliased the same way."""
     e = env.env
     if getattr(env, "observation", "camera_view") == "learner_view":
