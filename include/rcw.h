@@ -332,11 +332,31 @@ RCW_API int rcw_expand_columns(rcw_handle* h, const int32_t* height_line_pu_devi
  * RCW_VIEW_ONLY: a step is the cast kernel followed by the view kernel — the UInt32 camera view is NOT written by steps (see
  * rcw_obs_device_ptr; rcw_update_camera_view renders it on demand), the step takes two launches (rcw_step_form) and
  * rcw_set_step_form(h, RCW_STEP_ONE_LAUNCH) returns RCW_ERR_UNSUPPORTED.  The top view, if enabled, is rendered as before.
+ * The frame stack (rcw_set_learner_view_stack, frames = k, 1 <= k <= RCW_VIEW_MAX_FRAMES): the view batch is uint8 (B, k C, h, w), C
+ * order; channel s C + c is channel c of frame slot s, slot 0 the OLDEST frame and slot k - 1 the newest, and each slot holds exactly
+ * the bytes the single-frame view of that state holds.  k > 1 requires RCW_VIEW_CHW (RCW_VIEW_HWC: RCW_ERR_UNSUPPORTED); k = 1 is
+ * rcw_set_learner_view in every respect (kernels, launches, buffer, bytes).  The stack follows each agent's episode on the device:
+ *   setting the view                          all k slots of every agent hold the view of the current state;
+ *   rcw_reset / rcw_set_state / _set_state64  all k slots of every agent the call touches (its mask, not the episode counter, decides)
+ *     (and rcw_set_direction_table*)          hold the new frame; an agent outside the mask keeps every byte;
+ *   rcw_step / rcw_step_device                one push per agent per call: an agent whose episode counter (rcw_episode) differs from the
+ *                                             value recorded at its previous push — auto_reset re-sampled it in this step — has all k
+ *                                             slots set to the new frame; otherwise slot s takes slot s + 1 (s = 0 .. k - 2) and slot
+ *                                             k - 1 the new frame.  The step in which an agent reaches its goal is an ordinary push (the
+ *                                             terminal frame is the newest slot; the restart follows one step later, as `done` does);
+ *                                             an agent whose device action is invalid is not stepped, yet its unchanged frame is pushed;
+ *   rcw_cast_rays, rcw_update_camera_view, rcw_update_top_view, rcw_expand_columns_view (single-frame), rcw_set_step_form and every
+ *   getter                                    do not touch the stack.
+ * A replay of a captured step is a push like any other: nothing about the stack alternates on the host, and the device pointer is
+ * stable until the next rcw_set_learner_view*.  RCW_VIEW_ONLY changes nothing of this.
  *   rcw_set_learner_view         allocates the B*C*h*w bytes and renders the current state into them at once; RCW_VIEW_OFF
  *                                frees them.  A bad argument or an allocation failure leaves the previous view as it was.
+ *   rcw_set_learner_view_stack   the same with `frames` slots an agent (B*frames*C*h*w bytes); frames outside 1..RCW_VIEW_MAX_FRAMES:
+ *                                RCW_ERR_INVALID_ARGUMENT.  rcw_set_learner_view is this call with frames = 1.
  *   rcw_learner_view_info        the current settings (format RCW_VIEW_OFF and zeros when there is none).
- *   rcw_learner_view_device_ptr  the view batch in DEVICE memory, aliased: stable until the next rcw_set_learner_view.
- *   rcw_learner_view_copy        agents [first, first+count) to host memory (waits for the stream).
+ *   rcw_learner_view_stack       the current number of frame slots, 0 when there is no view.
+ *   rcw_learner_view_device_ptr  the view batch (the whole stack) in DEVICE memory, aliased: stable until the next rcw_set_learner_view*.
+ *   rcw_learner_view_copy        agents [first, first+count) to host memory, frames*C*h*w bytes each (waits for the stream).
  *   rcw_expand_columns_view      the handle's learner view (format, layout, size) of `count` agents' descriptors in DEVICE memory
  *                                (e.g. gathered from other GPUs) into view_device (count*C*h*w bytes), stream-ordered like
  *                                rcw_expand_columns. */
@@ -346,7 +366,11 @@ RCW_API int rcw_expand_columns(rcw_handle* h, const int32_t* height_line_pu_devi
 #define RCW_VIEW_CHW   0
 #define RCW_VIEW_HWC   1
 #define RCW_VIEW_ONLY  1   /* flag: no camera view in the step */
+#define RCW_VIEW_MAX_FRAMES 16
 RCW_API int rcw_set_learner_view(rcw_handle* h, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags);
+RCW_API int rcw_set_learner_view_stack(rcw_handle* h, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags,
+                                       int32_t frames);
+RCW_API int rcw_learner_view_stack(rcw_handle* h, int32_t* frames);
 RCW_API int rcw_learner_view_info(rcw_handle* h, int32_t* format, int32_t* layout, int32_t* height, int32_t* width,
                                   int32_t* flags);
 RCW_API int rcw_learner_view_device_ptr(rcw_handle* h, void** device_ptr);

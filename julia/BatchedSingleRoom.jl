@@ -459,14 +459,25 @@ expand_columns!(env::BatchedSingleRoom, height_line_pu_device::Ptr{Int32}, colou
 
 # format = :gray | :rgb | :off; size = (h, w) with h <= height_camera_view_pu, w <= num_rays; layout = :chw | :hwc;
 # camera_view = false: steps skip the UInt32 camera view (RCW_VIEW_ONLY).  Renders the current state at once.
+# stack = k (1 .. 16, :chw only): the view holds each agent's last k frames, slot 1 the oldest (Julia sees (w, h, k C, B)); the engine
+# shifts it at every step and fills all k slots with the new frame at reset!, set_state! and when auto_reset restarts the agent.
 function set_learner_view!(env::BatchedSingleRoom; format::Symbol = :gray,
                            size::Tuple{Integer, Integer} = (env.config.height_camera_view_pu, env.config.num_rays),
-                           layout::Symbol = :chw, camera_view::Bool = true)
+                           layout::Symbol = :chw, camera_view::Bool = true, stack::Integer = 1)
     fmt = format === :gray ? RCW_VIEW_GRAY8 : format === :rgb ? RCW_VIEW_RGB8 : format === :off ? RCW_VIEW_OFF :
           throw(ArgumentError("format must be :gray, :rgb or :off"))
     lay = layout === :chw ? RCW_VIEW_CHW : layout === :hwc ? RCW_VIEW_HWC : throw(ArgumentError("layout must be :chw or :hwc"))
-    check(ccall((:rcw_set_learner_view, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32),
-                env.handle, fmt, lay, size[1], size[2], camera_view ? Int32(0) : RCW_VIEW_ONLY))
+    flags = camera_view ? Int32(0) : RCW_VIEW_ONLY
+    stack == 1 && return check(ccall((:rcw_set_learner_view, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32),
+                                     env.handle, fmt, lay, size[1], size[2], flags))
+    check(ccall((:rcw_set_learner_view_stack, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32, Int32),
+                env.handle, fmt, lay, size[1], size[2], flags, stack))
+end
+# the number of frame slots of the learner view (0: no view)
+function learner_view_stack(env::BatchedSingleRoom)
+    k = Ref{Int32}(0)
+    check(ccall((:rcw_learner_view_stack, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}), env.handle, k))
+    return Int(k[])
 end
 function learner_view_info(env::BatchedSingleRoom)
     f = Ref{Int32}(0); l = Ref{Int32}(0); h = Ref{Int32}(0); w = Ref{Int32}(0); fl = Ref{Int32}(0)
@@ -474,12 +485,12 @@ function learner_view_info(env::BatchedSingleRoom)
                 env.handle, f, l, h, w, fl))
     return (format = f[], layout = l[], height = h[], width = w[], flags = fl[])
 end
-# The column-major shape Julia sees of the C-order (B, C, h, w) / (B, h, w, C) batch: (w, h, C, B) for :chw, (C, w, h, B) for :hwc
+# The column-major shape Julia sees of the C-order (B, k C, h, w) / (B, h, w, C) batch: (w, h, k C, B) for :chw, (C, w, h, B) for :hwc
 function learner_view_dims(env::BatchedSingleRoom)
     v = learner_view_info(env)
     v.format == RCW_VIEW_OFF && error("no learner view: call set_learner_view! first")
     C = v.format == RCW_VIEW_RGB8 ? 3 : 1
-    return v.layout == RCW_VIEW_CHW ? (Int(v.width), Int(v.height), C, env.batch) : (C, Int(v.width), Int(v.height), env.batch)
+    return v.layout == RCW_VIEW_CHW ? (Int(v.width), Int(v.height), learner_view_stack(env) * C, env.batch) : (C, Int(v.width), Int(v.height), env.batch)
 end
 function learner_view_device_ptr(env::BatchedSingleRoom)
     p = Ref{Ptr{Cvoid}}(C_NULL)

@@ -32,6 +32,7 @@ RCW_STEP_TWO_LAUNCHES, RCW_STEP_ONE_LAUNCH = 1, 2   # rcw_step_form / rcw_set_st
 RCW_VIEW_OFF, RCW_VIEW_RGB8, RCW_VIEW_GRAY8 = 0, 1, 2   # rcw_set_learner_view: format
 RCW_VIEW_CHW, RCW_VIEW_HWC = 0, 1                      # ... layout
 RCW_VIEW_ONLY = 1                                      # ... flag: no camera view in the step
+RCW_VIEW_MAX_FRAMES = 16                               # rcw_set_learner_view_stack: frames
 
 
 class RcwConfig(C.Structure):
@@ -132,6 +133,8 @@ SIGNATURES = {
     "rcw_columns_device_ptr": [_vp, C.POINTER(_vp), C.POINTER(_vp)],
     "rcw_expand_columns": [_vp, _vp, _vp, _i32, _vp],
     "rcw_set_learner_view": [_vp, _i32, _i32, _i32, _i32, _i32],
+    "rcw_set_learner_view_stack": [_vp, _i32, _i32, _i32, _i32, _i32, _i32],
+    "rcw_learner_view_stack": [_vp, C.POINTER(_i32)],
     "rcw_learner_view_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
     "rcw_learner_view_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_learner_view_copy": [_vp, _vp, _i32, _i32],

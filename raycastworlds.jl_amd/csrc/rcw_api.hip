@@ -130,7 +130,10 @@ struct rcw_handle {
     std::vector<double> ray_table64;
     // the learner view (rcw_set_learner_view): settings, the view batch and its box tables (rows [h + 1] then columns [w + 1])
     int32_t view_fmt = RCW_VIEW_OFF, view_layout = RCW_VIEW_CHW, view_h = 0, view_w = 0, view_flags = 0;
-    RcwBuf d_view, d_view_tab;
+    // frames = k > 1 (rcw_set_learner_view_stack): d_view is the staging frame the view kernels write, d_view_stack the B * k frames the
+    // caller sees, d_view_episode each agent's episode counter as of its last push (uint32 [B]); k = 1: d_view is the view, the two are empty
+    int32_t view_frames = 0;
+    RcwBuf d_view, d_view_tab, d_view_stack, d_view_episode;
     RcwView view{};
     ~rcw_handle();
 };
@@ -320,20 +323,29 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
 
 bool view_only(const rcw_handle* h) { return h->view_fmt != RCW_VIEW_OFF && (h->view_flags & RCW_VIEW_ONLY) != 0; }
 
-// the learner view of the handle's current descriptors (the unmasked agents' only), on the handle's stream
-hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev)
+// What a render does to the k-frame stack (include/rcw.h, "the frame stack"): a step pushes, reset! / set_state / a new view or direction
+// table refill the (masked) agents' slots, a re-render of the very same frames (rcw_set_step_form) leaves it alone.
+enum StackOp { kStackPush, kStackRefill, kStackKeep };
+
+// the learner view of the handle's current descriptors (the unmasked agents' only), on the handle's stream; with a frame stack the view
+// kernel's frame is the staging batch and the push kernel follows it
+hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
 {
-    return rcw_launch_view(h->dev, h->view, h->dev.col_h, h->dev.col_c, h->B, mask_dev, h->d_view.get<uint8_t>(), h->stream);
+    if (h->view_frames < 2 || op == kStackKeep)
+        return rcw_launch_view(h->dev, h->view, h->dev.col_h, h->dev.col_c, h->B, mask_dev, h->d_view.get<uint8_t>(), h->stream);
+    return rcw_launch_view_stack(h->dev, h->view, h->dev.col_h, h->dev.col_c, h->B, h->view_frames, mask_dev, h->d_view.get<uint8_t>(),
+                                 h->d_view_stack.get<uint8_t>(), h->dev.episode, h->d_view_episode.get<uint32_t>(), op == kStackRefill,
+                                 h->stream);
 }
 
 // A step, reset! or set_state's render: the camera view (launch_step_camera), then the learner view where the handle has one.  With
 // RCW_VIEW_ONLY the cast kernel is followed by the view kernel alone (the top view, if any, in its stand-alone form between them);
 // profiling events: start | after cast | after the top view | after the view kernel.
-hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev)
+hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op)
 {
     if (!view_only(h)) {
         const hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
-        return e == hipSuccess && h->view_fmt != RCW_VIEW_OFF ? launch_view(h, mask_dev) : e;
+        return e == hipSuccess && h->view_fmt != RCW_VIEW_OFF ? launch_view(h, mask_dev, op) : e;
     }
     obs_unknown(h);                                               // (RCW_VIEW_ONLY: the camera view is not painted)
     const bool prof = h->profiling && h->prof_count < kProfileSlots;
@@ -345,7 +357,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if (prof && (e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess) return e;
     if (h->dev.top_view && (e = launch_top_view(h, mask_dev, false, [](hipStream_t) { return hipSuccess; })) != hipSuccess) return e;
     if (prof && (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess) return e;
-    if ((e = launch_view(h, mask_dev)) != hipSuccess) return e;
+    if ((e = launch_view(h, mask_dev, op)) != hipSuccess) return e;
     if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
     return hipSuccess;
 }
@@ -1144,7 +1156,7 @@ int set_direction_table_impl(rcw_handle* h, const T* directions_wu, std::vector<
         return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the (direction, ray) table failed");
     }
     int rc = upload_tables(h); if (rc) return rc;
-    RCW_HIP(launch_step(h, nullptr, nullptr));   // re-render
+    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));   // re-render
     return RCW_OK;
 }
 }  // extern "C++"
@@ -1200,7 +1212,7 @@ int rcw_reset(rcw_handle* h, const uint8_t* mask_host, uint64_t seed)
     if (seed != h->dev.seed && h->dev.auto_reset && mask_dev) spec_forget(h);
     h->dev.seed = seed;
     RCW_HIP(rcw_launch_reset(h->dev, mask_dev, h->stream));            // SR:110-132
-    RCW_HIP(launch_step(h, nullptr, mask_dev));    // SR:134, SR:329
+    RCW_HIP(launch_step(h, nullptr, mask_dev, kStackRefill));    // SR:134, SR:329
     return RCW_OK;
 }
 
@@ -1231,7 +1243,7 @@ int set_state_impl(rcw_handle* h, const int32_t* goal_ij, const T* position_wu, 
     RCW_HIP(hipStreamSynchronize(h->stream));
     RCW_HIP(rcw_launch_set_state(h->dev, h->d_in_goal.get<int2>(), h->d_in_pos.get(), h->d_in_dir.get<int32_t>(), mask_dev,
                                  h->stream));
-    RCW_HIP(launch_step(h, nullptr, mask_dev));
+    RCW_HIP(launch_step(h, nullptr, mask_dev, kStackRefill));
     return RCW_OK;
 }
 }  // extern "C++"
@@ -1267,7 +1279,7 @@ int rcw_step(rcw_handle* h, const uint8_t* actions_host)
     std::memcpy(h->h_actions[slot].get(), actions_host, (size_t)h->B);
     RCW_HIP(hipMemcpyAsync(h->d_actions.get(), h->h_actions[slot].get(), (size_t)h->B, hipMemcpyHostToDevice, h->stream));
     RCW_HIP(hipEventRecord(h->ev_actions[slot].get(), h->stream));
-    RCW_HIP(launch_step(h, h->d_actions.get<uint8_t>(), nullptr));
+    RCW_HIP(launch_step(h, h->d_actions.get<uint8_t>(), nullptr, kStackPush));
     return RCW_OK;
 }
 
@@ -1275,7 +1287,7 @@ int rcw_step_device(rcw_handle* h, const uint8_t* actions_device)
 {
     int rc = check_handle(h); if (rc) return rc;
     if (!actions_device) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL actions");
-    RCW_HIP(launch_step(h, actions_device, nullptr));
+    RCW_HIP(launch_step(h, actions_device, nullptr, kStackPush));
     return RCW_OK;
 }
 
@@ -1509,20 +1521,31 @@ int rcw_expand_columns(rcw_handle* h, const int32_t* height_line_pu_device, cons
 // ---- the learner view ---------------------------------------------------------------------------------------
 int rcw_set_learner_view(rcw_handle* h, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags)
 {
+    return rcw_set_learner_view_stack(h, format, layout, height, width, flags, 1);
+}
+
+int rcw_set_learner_view_stack(rcw_handle* h, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags, int32_t frames)
+{
     int rc = check_handle(h); if (rc) return rc;
     const int Hc = h->cfg.height_camera_view_pu, N = h->cfg.num_rays;
     if (format != RCW_VIEW_OFF && format != RCW_VIEW_RGB8 && format != RCW_VIEW_GRAY8)
         return fail(RCW_ERR_INVALID_ARGUMENT, "format must be RCW_VIEW_OFF / RCW_VIEW_RGB8 / RCW_VIEW_GRAY8 (got %d)", format);
     if (flags & ~RCW_VIEW_ONLY) return fail(RCW_ERR_INVALID_ARGUMENT, "unknown learner view flags 0x%x", (unsigned)flags);
     if (format == RCW_VIEW_OFF && flags) return fail(RCW_ERR_INVALID_ARGUMENT, "RCW_VIEW_ONLY needs a format");
+    if (frames < 1 || frames > RCW_VIEW_MAX_FRAMES)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "frames must be in 1..%d (got %d)", RCW_VIEW_MAX_FRAMES, frames);
     const bool was_only = view_only(h);
-    RcwBuf view, tab;
+    RcwBuf view, tab, stack, last_episode;
     RcwView v{};
     if (format != RCW_VIEW_OFF) {
         if (layout != RCW_VIEW_CHW && layout != RCW_VIEW_HWC)
             return fail(RCW_ERR_INVALID_ARGUMENT, "layout must be RCW_VIEW_CHW or RCW_VIEW_HWC (got %d)", layout);
         if (height < 1 || height > Hc || width < 1 || width > N)
             return fail(RCW_ERR_INVALID_ARGUMENT, "learner view size %d x %d outside 1..%d x 1..%d (no up-sampling)", height, width, Hc, N);
+        if (frames > 1 && (long long)(format == RCW_VIEW_RGB8 ? 3 : 1) * height * width >= (1ll << 31))
+            return fail(RCW_ERR_UNSUPPORTED, "a stack of frames of 2 GiB or more");
+        if (frames > 1 && layout != RCW_VIEW_CHW)
+            return fail(RCW_ERR_UNSUPPORTED, "a stack of %d frames needs RCW_VIEW_CHW (slot s is channels [s C, (s + 1) C))", frames);
         v.C = format == RCW_VIEW_RGB8 ? 3 : 1;
         v.hwc = layout == RCW_VIEW_HWC ? 1 : 0;
         v.h = height; v.w = width;
@@ -1540,13 +1563,16 @@ int rcw_set_learner_view(rcw_handle* h, int32_t format, int32_t layout, int32_t 
         hipError_t e = view.hipMalloc(bytes);
         if (e == hipSuccess) e = tab.hipMalloc(t.size() * sizeof(int32_t));
         if (e == hipSuccess) e = hipMemcpy(tab.get(), t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess && frames > 1) e = stack.hipMalloc(bytes * (size_t)frames);
+        if (e == hipSuccess && frames > 1) e = last_episode.hipMalloc((size_t)h->B * sizeof(uint32_t));
         if (e != hipSuccess)                                       // the handle keeps its previous view
-            return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "learner view buffer of %zu bytes: %s", bytes, hip_failure(e));
+            return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "learner view buffer of %zu bytes: %s", bytes * (size_t)frames, hip_failure(e));
         v.rows = tab.get<int32_t>();
         v.cols = tab.get<int32_t>() + height + 1;
     }
-    RCW_HIP(replace_buffers(h, {&h->d_view, &h->d_view_tab}, {&view, &tab}));   // (the new ones, or none: the view switched off)
+    RCW_HIP(replace_buffers(h, {&h->d_view, &h->d_view_tab, &h->d_view_stack, &h->d_view_episode}, {&view, &tab, &stack, &last_episode}));   // (the new ones, or none: the view switched off)
     h->view = v;
+    h->view_frames = format != RCW_VIEW_OFF ? frames : 0;
     h->view_fmt = format;
     h->view_layout = format != RCW_VIEW_OFF ? layout : RCW_VIEW_CHW;
     h->view_h = format != RCW_VIEW_OFF ? height : 0;
@@ -1565,7 +1591,14 @@ int rcw_set_learner_view(rcw_handle* h, int32_t format, int32_t layout, int32_t 
         rc = plan_step_form(h, h->step_form_want); if (rc) return rc;
         RCW_HIP(rcw_launch_fill(h->dev, h->dev.col_h, h->dev.col_c, h->dev.obs, (long long)h->dev.B * h->dev.N, nullptr, h->stream));
     }
-    if (format != RCW_VIEW_OFF) RCW_HIP(launch_view(h, nullptr));
+    if (format != RCW_VIEW_OFF) RCW_HIP(launch_view(h, nullptr, kStackRefill));
+    return RCW_OK;
+}
+
+int rcw_learner_view_stack(rcw_handle* h, int32_t* frames)
+{
+    if (!h || !frames) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    *frames = h->view_frames;
     return RCW_OK;
 }
 
@@ -1580,7 +1613,7 @@ int rcw_learner_view_device_ptr(rcw_handle* h, void** device_ptr)
 {
     if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
     if (h->view_fmt == RCW_VIEW_OFF) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
-    *device_ptr = h->d_view.get();
+    *device_ptr = h->view_frames > 1 ? h->d_view_stack.get() : h->d_view.get();
     return RCW_OK;
 }
 
@@ -1591,8 +1624,9 @@ int rcw_learner_view_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32
     if (!out_host || first < 0 || count < 0 || first + (int64_t)count > h->B)
         return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
     rc = sync_and_check(h);
-    const size_t per = (size_t)h->view.C * h->view_h * h->view_w;
-    RCW_HIP(hipMemcpy(out_host, h->d_view.get<uint8_t>() + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
+    const size_t per = (size_t)h->view_frames * h->view.C * h->view_h * h->view_w;
+    const uint8_t* const src = h->view_frames > 1 ? h->d_view_stack.get<uint8_t>() : h->d_view.get<uint8_t>();
+    RCW_HIP(hipMemcpy(out_host, src + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -1839,7 +1873,7 @@ int rcw_set_step_form(rcw_handle* h, int32_t form)
         return fail(RCW_ERR_INVALID_ARGUMENT, "form must be 0 (automatic) or RCW_STEP_TWO_LAUNCHES / RCW_STEP_ONE_LAUNCH (got %d)", form);
     const bool was_on = h->spec_on != 0;
     rc = plan_step_form(h, form); if (rc) return rc;
-    if (h->spec_on && !was_on) RCW_HIP(launch_step(h, nullptr, nullptr));   // prime the slots (re-renders the current frames: the same pixels)
+    if (h->spec_on && !was_on) RCW_HIP(launch_step(h, nullptr, nullptr, kStackKeep));   // prime the slots (re-renders the current frames: the same pixels)
     return RCW_OK;
 }
 

@@ -172,4 +172,11 @@ struct RcwView {
 // the view of agents [0, count) of the descriptors col_h / col_c (N a agent) into out (count * C * h * w bytes); mask: NULL = all
 hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,
                            const uint8_t* mask_dev, uint8_t* out, hipStream_t s);
+// The view with a k-frame stack (frames = k > 1, layout CHW): the frame of agents [0, count) pushed into (refill: written to all of) their
+// `frames` slots of stack; episode / last_episode: the agents' counters now / as of their previous push (updated); mask: NULL = all.
+// At the sizes rcw_view_agent_kernel takes: rcw_view_agent_push_kernel, the one kernel that does both and leaves `staged` alone; otherwise
+// rcw_launch_view into `staged` (count * C * h * w bytes) and rcw_view_push_kernel behind it.
+hipError_t rcw_launch_view_stack(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count, int frames,
+                                 const uint8_t* mask_dev, uint8_t* staged, uint8_t* stack, const uint32_t* episode, uint32_t* last_episode,
+                                 bool refill, hipStream_t s);
 int rcw_view_full_eligible(const RcwDev& p, int C, int hwc);   // the full-resolution kernel takes this geometry and layout

@@ -19,6 +19,11 @@
 //                          then a lane per output pixel (all C channels), 32-bit arithmetic on LDS, byte stores the wavefront coalesces.
 //   rcw_view_box_kernel    the rest (huge boxes, huge views): a lane per output pixel reading the descriptor arrays directly, 64-bit
 //                          sums where a box's could pass 2^31.
+// and, for a stack of the last k frames an agent (rcw_set_learner_view_stack, k > 1, layout CHW):
+//   rcw_view_agent_push_kernel  rcw_view_agent_kernel with the push inside: the old slots move down one while the tables are staged, the
+//                          pixels go to the newest slot (or to all k: a refill, an episode that restarted in this step).
+//   rcw_view_push_kernel   behind the other two kernels, which write a staging frame: a workgroup an agent shifts the slots and appends
+//                          the staged frame (or writes it k times), 16-byte chunks where a frame is a multiple of 16 bytes.
 #include "rcw_device.h"
 
 #include <algorithm>
@@ -205,6 +210,23 @@ __global__ __launch_bounds__(kBlock) void rcw_view_box_kernel(const RcwDev p, co
     }
 }
 
+// Slots 0 .. k - 2 of one agent (per_v chunks each) take their successors: a lane moves the same chunk of every slot in ascending slot
+// order — four loads, then their four stores — and no other lane touches that chunk, so the shift in place needs no barrier.
+template <typename V>
+__device__ __forceinline__ void shift_slots(V* base, int per_v, int k, int tid)
+{
+    for (int i = tid; i < per_v; i += kBlock) {
+        V* const c = base + i;
+        for (int s = 0; s + 1 < k; s += 4) {
+            V t[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (s + j + 1 < k) t[j] = c[(long long)(s + j + 1) * per_v];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (s + j + 1 < k) c[(long long)(s + j) * per_v] = t[j];
+        }
+    }
+}
+
 // A workgroup per agent for the reduced sizes whose tables fit in LDS: the agent's columns are turned into (ceiling end, floor start,
 // packed colour channels) once, the box bounds staged beside them, and every output pixel of the agent is then 32-bit arithmetic on LDS.
 template <int C, bool HWC>
@@ -269,7 +291,141 @@ __global__ __launch_bounds__(kBlock) void rcw_view_agent_kernel(const RcwDev p, 
     }
 }
 
+// rcw_view_agent_kernel with the k-frame stack's push inside (rcw_set_learner_view_stack at these sizes, layout CHW): `stack` is the batch of
+// k slots an agent.  While the tables are staged the old slots move down one (shift_slots); the barrier the staging needs anyway also puts
+// every read of slot k - 1 in front of the stores that follow; each pixel, computed once as above, goes to slot k - 1 — or to all k slots on a
+// refill or when the agent's episode counter is not the one recorded at its previous push (rcw_view_push_kernel below states the rule).
+// Against that kernel behind rcw_view_agent_kernel this saves a launch, and the staged frame's store and load.
+struct RcwViewStack {
+    int k, refill;                  // slots an agent; 1: reset / set_state / a new view — all k slots take the frame
+    const uint32_t* episode;        // the agents' episode counters now
+    uint32_t* last_episode;         // ... as of their previous push (updated)
+};
+
+template <int C>
+__global__ __launch_bounds__(kBlock) void rcw_view_agent_push_kernel(const RcwDev p, const RcwView v, const int32_t* __restrict__ col_h,
+                                                                     const uint8_t* __restrict__ col_c, const uint8_t* __restrict__ mask,
+                                                                     uint8_t* __restrict__ stack, const RcwViewStack st)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t lds_v[];
+    const int N = p.N, Hc = p.Hc, h = v.h, w = v.w, tid = threadIdx.x;
+    const long long a = blockIdx.x;
+    if (mask != nullptr && mask[a] == 0) return;
+    const uint32_t ep = st.episode[a];
+    const bool all = st.refill || st.last_episode[a] != ep;
+    int32_t* const s_pad = lds_v;
+    int32_t* const s_fs = s_pad + N;
+    uint32_t* const s_vm = reinterpret_cast<uint32_t*>(s_fs + N);
+    int32_t* const s_rows = reinterpret_cast<int32_t*>(s_vm + N);
+    int32_t* const s_cols = s_rows + h + 1;
+    uint32_t vc[C], vf[C], vm4[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        vc[k] = view_channel<C>(p.ceiling_color, k);
+        vf[k] = view_channel<C>(p.floor_color, k);
+        vm4[k] = 0u;
+#pragma unroll
+        for (int id = 0; id < 4; ++id) vm4[k] |= view_channel<C>(p.colour[id], k) << (8 * id);
+    }
+    for (int j = tid; j < N; j += kBlock) {
+        const int pad = column_padding(Hc, col_h[a * N + j]);
+        const uint32_t sh = 8u * (col_c[a * N + j] & 3u);
+        uint32_t m = 0u;
+#pragma unroll
+        for (int k = 0; k < C; ++k) m |= ((vm4[k] >> sh) & 0xFFu) << (8 * k);
+        s_pad[j] = pad; s_fs[j] = max(pad, Hc - pad); s_vm[j] = m;
+    }
+    for (int j = tid; j <= h; j += kBlock) s_rows[j] = v.rows[j];
+    for (int j = tid; j <= w; j += kBlock) s_cols[j] = v.cols[j];
+    const int hw = h * w, per = C * hw;
+    uint8_t* const base = stack + (unsigned long long)a * st.k * per;
+    if (!all) {
+        if ((per & 15) == 0) shift_slots(reinterpret_cast<u32x4*>(base), per >> 4, st.k, tid);   // (the batch is 16-byte aligned: rcw_launch_view_stack)
+        else shift_slots(base, per, st.k, tid);
+    }
+    __syncthreads();
+    if (tid == 0) st.last_episode[a] = ep;
+    const float inv_w = 1.0f / (float)w;
+    uint8_t* const o = all ? base : base + (unsigned long long)(st.k - 1) * per;
+    const int copies = all ? st.k : 1;
+    for (int i = tid; i < hw; i += kBlock) {
+        const int r = fast_div(i, w, inv_w), c = i - r * w;
+        const int r0 = s_rows[r], r1 = s_rows[r + 1], c0 = s_cols[c], c1 = s_cols[c + 1];
+        const int nr = r1 - r0;
+        uint32_t acc[C];
+#pragma unroll
+        for (int k = 0; k < C; ++k) acc[k] = 0u;
+        for (int j = c0; j < c1; ++j) {
+            const int pad = s_pad[j], fs = s_fs[j];
+            const uint32_t m = s_vm[j];
+            const uint32_t nc = (uint32_t)max(0, min(r1, pad) - r0);
+            const uint32_t nf = (uint32_t)max(0, r1 - max(r0, fs));
+            const uint32_t nm = (uint32_t)nr - nc - nf;
+#pragma unroll
+            for (int k = 0; k < C; ++k) acc[k] += nc * vc[k] + nm * ((m >> (8 * k)) & 0xFFu) + nf * vf[k];
+        }
+        const uint32_t n = (uint32_t)nr * (uint32_t)(c1 - c0);
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            const uint8_t q = (uint8_t)view_div(acc[k], n);
+            for (int s = 0; s < copies; ++s) o[(unsigned)(s * per + k * hw + i)] = q;
+        }
+    }
+}
+
+// The k-frame stack (rcw_set_learner_view_stack, frames = k > 1): the view kernels above keep writing the single frame into the staging
+// batch; this kernel, behind them, moves it into the agent's k slots of `per` bytes each (slot 0 the oldest).  A refill (reset / set_state /
+// setting the view: the masked agents) or an agent whose episode counter differs from the one recorded at its previous push (auto_reset
+// re-sampled it in this step) takes the staged frame k times; every other agent's slot s takes slot s + 1 and slot k - 1 the staged frame.
+// A workgroup owns an agent: all its lanes read the recorded counter, the barrier, then lane 0 records the new one.  A lane moves the
+// SAME chunk of every slot in ascending slot order (four loads, then their four stores) and no other lane touches that chunk: the shift
+// in place needs no barrier.  V: 16-byte chunks where per is a multiple of 16, bytes otherwise.
+template <typename V>
+__global__ __launch_bounds__(kBlock) void rcw_view_push_kernel(const V* __restrict__ staged, V* stack, const uint32_t* __restrict__ episode,
+                                                               uint32_t* last_episode, const uint8_t* __restrict__ mask, int per_v, int k,
+                                                               int refill)
+{
+    const long long a = blockIdx.x;
+    if (mask != nullptr && mask[a] == 0) return;
+    const uint32_t ep = episode[a];
+    const bool all = refill || last_episode[a] != ep;
+    __syncthreads();
+    if (threadIdx.x == 0) last_episode[a] = ep;
+    const V* const src = staged + a * per_v;
+    V* const dst = stack + a * k * per_v;
+    for (int i = threadIdx.x; i < per_v; i += kBlock) {
+        V* const c = dst + i;
+        const V f = src[i];
+        if (all) {
+            for (int s = 0; s < k; ++s) c[(long long)s * per_v] = f;
+            continue;
+        }
+        for (int s = 0; s < k; s += 4) {
+            V t[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (s + j < k) t[j] = s + j + 1 < k ? c[(long long)(s + j + 1) * per_v] : f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (s + j < k) c[(long long)(s + j) * per_v] = t[j];
+        }
+    }
+}
+
 }  // namespace
+
+// the LDS bytes of rcw_view_agent_kernel's tables for this view, 0 where it does not take it (the tables beyond 64 KiB, 64-bit box sums)
+static size_t view_agent_lds(const RcwDev& p, const RcwView& v)
+{
+    const size_t lds = ((size_t)3 * p.N + v.h + v.w + 2) * sizeof(int32_t);
+    return !v.wide && (long long)v.h * v.w < (1ll << 23) && lds <= 64 * 1024 ? lds : 0;
+}
+
+// rcw_launch_view's first choice: the full-size kernel, for 16-byte aligned buffers and fewer than 2^31 items
+static bool view_takes_full_kernel(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,
+                                   const uint8_t* out)
+{
+    const bool aligned = (((uintptr_t)col_h | (uintptr_t)col_c | (uintptr_t)out) & 15u) == 0;
+    return v.full_ok && aligned && (long long)count * v.C * ((p.Hc + 7) / 8) < (1ll << 31);
+}
 
 int rcw_view_full_eligible(const RcwDev& p, int C, int hwc)
 {
@@ -280,8 +436,7 @@ hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col
                            const uint8_t* mask_dev, uint8_t* out, hipStream_t s)
 {
     if (count < 1) return hipSuccess;
-    const bool aligned = (((uintptr_t)col_h | (uintptr_t)col_c | (uintptr_t)out) & 15u) == 0;
-    if (v.full_ok && aligned && (long long)count * v.C * ((p.Hc + 7) / 8) < (1ll << 31)) {
+    if (view_takes_full_kernel(p, v, col_h, col_c, count, out)) {
         int l_shift = 0;
         while ((16 << l_shift) < p.N) ++l_shift;
         const int rows_item = (kBlock >> l_shift) * kViewFullPasses;
@@ -293,8 +448,8 @@ hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col
         else          hipLaunchKernelGGL(rcw_view_full_kernel<3>, dim3(grid), dim3(kBlock), 0, s, p, col_h, col_c, o4, count, mask_dev, l_shift, blocks_per_plane);
         return hipGetLastError();
     }
-    const size_t lds = ((size_t)3 * p.N + v.h + v.w + 2) * sizeof(int32_t);
-    if (!v.wide && (long long)v.h * v.w < (1ll << 23) && lds <= 64 * 1024) {
+    const size_t lds = view_agent_lds(p, v);
+    if (lds != 0) {
 #define RCW_VIEW_AGENT(CC, HH) hipLaunchKernelGGL((rcw_view_agent_kernel<CC, HH>), dim3(count), dim3(kBlock), lds, s, p, v, col_h, col_c, mask_dev, out)
         if (v.C == 1) RCW_VIEW_AGENT(1, false);
         else if (v.hwc) RCW_VIEW_AGENT(3, true);
@@ -309,5 +464,30 @@ hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col
     else if (v.hwc) { if (v.wide) RCW_VIEW_BOX(3, true, true); else RCW_VIEW_BOX(3, true, false); }
     else { if (v.wide) RCW_VIEW_BOX(3, false, true); else RCW_VIEW_BOX(3, false, false); }
 #undef RCW_VIEW_BOX
+    return hipGetLastError();
+}
+
+hipError_t rcw_launch_view_stack(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count, int frames,
+                                 const uint8_t* mask_dev, uint8_t* staged, uint8_t* stack, const uint32_t* episode, uint32_t* last_episode,
+                                 bool refill, hipStream_t s)
+{
+    if (count < 1 || frames < 2) return hipSuccess;
+    const bool full = view_takes_full_kernel(p, v, col_h, col_c, count, staged);
+    const size_t lds = view_agent_lds(p, v);
+    if (!full && lds != 0 && !v.hwc && ((uintptr_t)stack & 15u) == 0) {
+        const RcwViewStack st{frames, refill ? 1 : 0, episode, last_episode};
+        if (v.C == 1) hipLaunchKernelGGL(rcw_view_agent_push_kernel<1>, dim3(count), dim3(kBlock), lds, s, p, v, col_h, col_c, mask_dev, stack, st);
+        else          hipLaunchKernelGGL(rcw_view_agent_push_kernel<3>, dim3(count), dim3(kBlock), lds, s, p, v, col_h, col_c, mask_dev, stack, st);
+        return hipGetLastError();
+    }
+    const hipError_t e = rcw_launch_view(p, v, col_h, col_c, count, mask_dev, staged, s);
+    if (e != hipSuccess) return e;
+    const long long per = (long long)v.C * v.h * v.w;           // (< 2^31: a frame of at most 2^20 x num_rays pixels — rcw_set_learner_view_stack)
+    if ((per & 15) == 0 && (((uintptr_t)staged | (uintptr_t)stack) & 15u) == 0)
+        hipLaunchKernelGGL(rcw_view_push_kernel<u32x4>, dim3(count), dim3(kBlock), 0, s, reinterpret_cast<const u32x4*>(staged),
+                           reinterpret_cast<u32x4*>(stack), episode, last_episode, mask_dev, (int)(per >> 4), frames, refill ? 1 : 0);
+    else
+        hipLaunchKernelGGL(rcw_view_push_kernel<uint8_t>, dim3(count), dim3(kBlock), 0, s, staged, stack, episode, last_episode, mask_dev,
+                           (int)per, frames, refill ? 1 : 0);
     return hipGetLastError();
 }

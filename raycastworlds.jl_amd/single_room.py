@@ -560,12 +560,17 @@ class SingleRoom:
         return out
 
     # ---- the learner view (rcw_set_learner_view) ------------------------------------------------------------------
-    def set_learner_view(self, format: Optional[str] = "gray", size=None, layout: str = "chw", camera_view: bool = True) -> None:
+    def set_learner_view(self, format: Optional[str] = "gray", size=None, layout: str = "chw", camera_view: bool = True,
+                         stack: int = 1) -> None:
         """Also render a uint8 observation a learner consumes at every reset / set_state / step: `format` "gray" or "rgb"
         (None: off), `size` (h, w) with h <= height_camera_view_pu and w <= num_rays (None: full size; each output pixel is
         the rounded mean of its box of camera pixels), `layout` "chw" (B, C, h, w) or "hwc" (B, h, w, C).
         `camera_view=False` (RCW_VIEW_ONLY): steps skip the uint32 camera view — `camera_view` then holds the last frames
-        rendered until `update_camera_view_(env)`.  Renders the current state at once."""
+        rendered until `update_camera_view_(env)`.  Renders the current state at once.
+        `stack=k` (1..16, "chw" only): the view holds each agent's last k frames, uint8 (B, k C, h, w), slot 0 (channels
+        [0, C)) the oldest and slot k - 1 the newest.  The engine keeps it per episode on the device: a step shifts the slots
+        and appends the new frame; reset_, set_state and the step in which auto_reset restarts an agent fill all k slots of
+        that agent with its new frame, so no frame of a finished episode shows in the next one (include/rcw.h)."""
         formats = {None: _capi.RCW_VIEW_OFF, "rgb": _capi.RCW_VIEW_RGB8, "gray": _capi.RCW_VIEW_GRAY8}
         layouts = {"chw": _capi.RCW_VIEW_CHW, "hwc": _capi.RCW_VIEW_HWC}
         if format not in formats:
@@ -576,7 +581,11 @@ class SingleRoom:
             raise ValueError("camera_view=False needs a learner view format")
         h, w = (self.cfg.height_camera_view_pu, self.cfg.num_rays) if size is None else (int(size[0]), int(size[1]))
         flags = 0 if camera_view else _capi.RCW_VIEW_ONLY
-        self._check(self._lib.rcw_set_learner_view(self._h, formats[format], layouts[layout], h, w, flags))
+        stack = int(stack)
+        if stack == 1:
+            self._check(self._lib.rcw_set_learner_view(self._h, formats[format], layouts[layout], h, w, flags))
+        else:
+            self._check(self._lib.rcw_set_learner_view_stack(self._h, formats[format], layouts[layout], h, w, flags, stack))
         self._view_only = not camera_view                # (RLBase.state refuses the stale camera view of such a handle)
         self.__dict__.pop("_learner_view_alias", None)
 
@@ -589,17 +598,25 @@ class SingleRoom:
                 "layout": "hwc" if lay == _capi.RCW_VIEW_HWC else "chw", "size": (h, w),
                 "camera_view": not (flags & _capi.RCW_VIEW_ONLY)}
 
-    def _learner_view_shape(self, n: int, info: Optional[dict] = None):
+    @property
+    def learner_view_stack(self) -> int:
+        """The number of frame slots of the learner view (rcw_learner_view_stack): `set_learner_view`'s `stack`, 0 without a view."""
+        k = C.c_int32()
+        self._check(self._lib.rcw_learner_view_stack(self._h, C.byref(k)))
+        return k.value
+
+    def _learner_view_shape(self, n: int, info: Optional[dict] = None, stack: Optional[int] = None):
         info = info or self.learner_view_info()
         if info["format"] is None:
             raise RuntimeError("this environment has no learner view: call set_learner_view first")
         c = 3 if info["format"] == "rgb" else 1
         h, w = info["size"]
-        return (n, c, h, w) if info["layout"] == "chw" else (n, h, w, c)
+        k = self.learner_view_stack if stack is None else stack
+        return (n, k * c, h, w) if info["layout"] == "chw" else (n, h, w, c)
 
     @property
     def learner_view(self) -> DeviceArray:
-        """The learner view batch, aliased device memory: uint8 (B, C, h, w) or (B, h, w, C), rewritten in place by every
+        """The learner view batch, aliased device memory: uint8 (B, stack * C, h, w) or (B, h, w, C), rewritten in place by every
         step in stream order (`.torch(sync=False)` for a consumer on the GPU)."""
         shape = self._learner_view_shape(self.batch)
         p = C.c_void_p()
@@ -627,7 +644,7 @@ class SingleRoom:
             raise ValueError("descriptor shape must be (n, num_rays)")
         if height_line_pu.dtype != torch.int32 or colour_id.dtype != torch.uint8:
             raise ValueError("descriptors must be int32 / uint8")
-        shape = self._learner_view_shape(n)
+        shape = self._learner_view_shape(n, stack=1)              # (single-frame, whatever the handle's stack)
         h = height_line_pu.contiguous()
         c = colour_id.contiguous()
         if out is None:

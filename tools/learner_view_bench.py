@@ -5,7 +5,11 @@ device-resident U{1..4} actions, HIP events on the engine's stream around `--ste
     python tools/learner_view_bench.py --steps 200 --warmup 20 --repeats 5
 
 Cases: plain (the camera view only), plus_gray84 (camera view + gray 84x84), only_gray84 / only_gray_full / only_rgb_chw_full
-(RCW_VIEW_ONLY: the cast kernel and the view kernel).  The view kernel's own duration comes from a separate rocprofv3 run
+(RCW_VIEW_ONLY: the cast kernel and the view kernel); plus_gray84_stack4 / only_gray84_stack4 (the engine's 4-frame stack,
+set_learner_view(stack=4)) against plus_gray84_torch_stack4 / only_gray84_torch_stack4: the single-frame view plus a stack kept by torch
+ops on the same stream with the same semantics — the done flags of before the step copied, the slots shifted by a cat, all four taken
+from the new frame by a where on the agents that were done (those auto_reset re-samples in the step): three launches and two fresh
+tensors a step, no host synchronisation.  The view kernel's own duration comes from a separate rocprofv3 run
 (--case NAME runs one case alone, for `rocprofv3 --kernel-trace --stats -- python tools/learner_view_bench.py --case ...`)."""
 import argparse
 import json
@@ -21,23 +25,41 @@ CASES = {
     "only_gray84": dict(format="gray", size=(84, 84), layout="chw", camera_view=False),
     "only_gray_full": dict(format="gray", size=None, layout="chw", camera_view=False),
     "only_rgb_chw_full": dict(format="rgb", size=None, layout="chw", camera_view=False),
+    "plus_gray84_stack4": dict(format="gray", size=(84, 84), layout="chw", camera_view=True, stack=4),
+    "only_gray84_stack4": dict(format="gray", size=(84, 84), layout="chw", camera_view=False, stack=4),
+    "plus_gray84_torch_stack4": dict(format="gray", size=(84, 84), layout="chw", camera_view=True, torch_stack=4),
+    "only_gray84_torch_stack4": dict(format="gray", size=(84, 84), layout="chw", camera_view=False, torch_stack=4),
 }
 
 
 def run_case(RCW, torch, name, batch, steps, warmup, actions):
     env = RCW.SingleRoomModule.SingleRoom(batch=batch, seed=0, auto_reset=True, height_tile_map_tu=8, width_tile_map_tu=8,
                                           num_rays=256)
-    if CASES[name] is not None:
-        env.set_learner_view(**CASES[name])
+    kw = dict(CASES[name] or {})
+    k = kw.pop("torch_stack", 0)
+    if kw:
+        env.set_learner_view(**kw)
     stream = torch.cuda.Stream()
     env.set_stream(stream.cuda_stream)
     with torch.cuda.stream(stream):
+        if k:                                                   # the stack a user keeps in torch today, on the engine's stream
+            view = env.learner_view.torch(sync=False)           # (B, 1, h, w), rewritten in place by every step
+            done = env.done_device(as_bool=True).torch(sync=False)
+            stack = [view.repeat(1, k, 1, 1)]
+
+            def act(a):
+                restarted = done.clone()[:, None, None, None]   # done before the step: re-sampled by it
+                RCW.act_(env, a)
+                stack[0] = torch.where(restarted, view, torch.cat((stack[0][:, 1:], view), 1))
+        else:
+            def act(a):
+                RCW.act_(env, a)
         for s in range(warmup):
-            RCW.act_(env, actions[s % len(actions)])
+            act(actions[s % len(actions)])
         stream.synchronize()
         env.timer_start()
         for s in range(steps):
-            RCW.act_(env, actions[(warmup + s) % len(actions)])
+            act(actions[(warmup + s) % len(actions)])
         ms = env.timer_stop()
         stream.synchronize()
     form = env.step_form()
@@ -78,6 +100,11 @@ def main():
         out["cases"][n] = {"median": float(np.median(r)), "min": float(r.min()), "max": float(r.max()),
                            "us_per_step_median": float(args.batch / np.median(r) * 1e6), "step_form": forms[n],
                            "runs": [float(x) for x in r]}
+    for n in names:                                                # the engine's stack against the torch one: faster, and the ranges apart?
+        t = n.replace("_stack4", "_torch_stack4")
+        if n.endswith("_stack4") and t != n and t in runs:
+            e, b = out["cases"][n], out["cases"][t]
+            out[n + "_over_torch"] = {"median_ratio": e["median"] / b["median"], "ranges_apart": bool(e["min"] > b["max"])}
     if "plain" in runs and "only_gray84" in runs:
         out["only_gray84_over_plain"] = out["cases"]["only_gray84"]["median"] / out["cases"]["plain"]["median"]
     print(json.dumps(out))
