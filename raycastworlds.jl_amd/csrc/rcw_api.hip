@@ -128,13 +128,18 @@ struct rcw_handle {
     std::vector<float> ray_table;   // (N, 5, nd)
     std::vector<double> dir_table64;   //              T = Float64
     std::vector<double> ray_table64;
-    // the learner view (rcw_set_learner_view): settings, the view batch and its box tables (rows [h + 1] then columns [w + 1])
-    int32_t view_fmt = RCW_VIEW_OFF, view_layout = RCW_VIEW_CHW, view_h = 0, view_w = 0, view_flags = 0;
-    // frames = k > 1 (rcw_set_learner_view_stack): d_view is the staging frame the view kernels write, d_view_stack the B * k frames the
-    // caller sees, d_view_episode each agent's episode counter as of its last push (uint32 [B]); k = 1: d_view is the view, the two are empty
-    int32_t view_frames = 0;
-    RcwBuf d_view, d_view_tab, d_view_stack, d_view_episode;
-    RcwView view{};
+    // The learner view (rcw_set_learner_view*): what the caller set, the view kernels' arguments, the buffers.  frames = k > 1: `frame` is the
+    // staging batch the view kernels write, `stack` the B * k frames the caller sees, `last_episode` each agent's episode counter as of its
+    // last push (uint32 [B]); k = 1: `frame` is the view, the two are empty.  tab: the box tables (rows [h + 1], then columns [w + 1]).
+    struct LearnerView {
+        struct Settings { int32_t fmt = RCW_VIEW_OFF, layout = RCW_VIEW_CHW, h = 0, w = 0, flags = 0, frames = 0; } set;
+        RcwBuf frame, tab, stack, last_episode;
+        RcwView view{};
+        bool on() const { return set.fmt != RCW_VIEW_OFF; }
+        bool only() const { return on() && (set.flags & RCW_VIEW_ONLY) != 0; }       // the step paints no camera view
+        size_t agent_bytes() const { return (size_t)set.frames * view.C * set.h * set.w; }   // one agent's whole output: its k frames
+        uint8_t* batch() const { return set.frames > 1 ? stack.get<uint8_t>() : frame.get<uint8_t>(); }   // what the caller sees
+    } learner;
     ~rcw_handle();
 };
 
@@ -321,8 +326,6 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
     return hipSuccess;
 }
 
-bool view_only(const rcw_handle* h) { return h->view_fmt != RCW_VIEW_OFF && (h->view_flags & RCW_VIEW_ONLY) != 0; }
-
 // What a render does to the k-frame stack (include/rcw.h, "the frame stack"): a step pushes, reset! / set_state / a new view or direction
 // table refill the (masked) agents' slots, a re-render of the very same frames (rcw_set_step_form) leaves it alone.
 enum StackOp { kStackPush, kStackRefill, kStackKeep };
@@ -331,11 +334,11 @@ enum StackOp { kStackPush, kStackRefill, kStackKeep };
 // kernel's frame is the staging batch and the push kernel follows it
 hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
 {
-    if (h->view_frames < 2 || op == kStackKeep)
-        return rcw_launch_view(h->dev, h->view, h->dev.col_h, h->dev.col_c, h->B, mask_dev, h->d_view.get<uint8_t>(), h->stream);
-    return rcw_launch_view_stack(h->dev, h->view, h->dev.col_h, h->dev.col_c, h->B, h->view_frames, mask_dev, h->d_view.get<uint8_t>(),
-                                 h->d_view_stack.get<uint8_t>(), h->dev.episode, h->d_view_episode.get<uint32_t>(), op == kStackRefill,
-                                 h->stream);
+    const rcw_handle::LearnerView& lv = h->learner;
+    if (lv.set.frames < 2 || op == kStackKeep)
+        return rcw_launch_view(h->dev, lv.view, h->dev.col_h, h->dev.col_c, h->B, mask_dev, lv.frame.get<uint8_t>(), h->stream);
+    return rcw_launch_view_stack(h->dev, lv.view, h->dev.col_h, h->dev.col_c, h->B, lv.set.frames, mask_dev, lv.frame.get<uint8_t>(),
+                                 lv.stack.get<uint8_t>(), h->dev.episode, lv.last_episode.get<uint32_t>(), op == kStackRefill, h->stream);
 }
 
 // A step, reset! or set_state's render: the camera view (launch_step_camera), then the learner view where the handle has one.  With
@@ -343,9 +346,9 @@ hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
 // profiling events: start | after cast | after the top view | after the view kernel.
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op)
 {
-    if (!view_only(h)) {
+    if (!h->learner.only()) {
         const hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
-        return e == hipSuccess && h->view_fmt != RCW_VIEW_OFF ? launch_view(h, mask_dev, op) : e;
+        return e == hipSuccess && h->learner.on() ? launch_view(h, mask_dev, op) : e;
     }
     obs_unknown(h);                                               // (RCW_VIEW_ONLY: the camera view is not painted)
     const bool prof = h->profiling && h->prof_count < kProfileSlots;
@@ -694,7 +697,7 @@ int plan_step_form(rcw_handle* h, int want)
 {
     RcwDev& d = h->dev;
     const bool eligible = rcw_step_spec_eligible(d) != 0;
-    if (view_only(h)) {                                // (the cast kernel followed by the view kernel: no camera fill to fuse)
+    if (h->learner.only()) {                           // (the cast kernel followed by the view kernel: no camera fill to fuse)
         if (want == RCW_STEP_ONE_LAUNCH) return fail(RCW_ERR_UNSUPPORTED, "the handle's learner view is set with RCW_VIEW_ONLY: a step is the cast kernel and the view kernel");
         h->spec_on = 0; spec_forget(h); h->step_form_want = want;
         return RCW_OK;
@@ -1524,66 +1527,84 @@ int rcw_set_learner_view(rcw_handle* h, int32_t format, int32_t layout, int32_t 
     return rcw_set_learner_view_stack(h, format, layout, height, width, flags, 1);
 }
 
-int rcw_set_learner_view_stack(rcw_handle* h, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags, int32_t frames)
+extern "C++" {
+namespace {
+// What rcw_set_learner_view_stack's arguments ask of this geometry — the kernels' RcwView (rows / cols: the caller's, once `tab` is on the
+// device) and the box tables — or the refusal.  Host arithmetic only: no HIP call, and nothing of a handle changes.
+struct ViewPlan {
+    RcwView v{};
+    std::vector<int32_t> tab;      // rows [h + 1], then columns [w + 1]; empty: RCW_VIEW_OFF
+};
+
+int plan_learner_view(const rcw_config& cfg, const RcwDev& dev, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags,
+                      int32_t frames, ViewPlan* plan)
 {
-    int rc = check_handle(h); if (rc) return rc;
-    const int Hc = h->cfg.height_camera_view_pu, N = h->cfg.num_rays;
+    const int Hc = cfg.height_camera_view_pu, N = cfg.num_rays;
     if (format != RCW_VIEW_OFF && format != RCW_VIEW_RGB8 && format != RCW_VIEW_GRAY8)
         return fail(RCW_ERR_INVALID_ARGUMENT, "format must be RCW_VIEW_OFF / RCW_VIEW_RGB8 / RCW_VIEW_GRAY8 (got %d)", format);
     if (flags & ~RCW_VIEW_ONLY) return fail(RCW_ERR_INVALID_ARGUMENT, "unknown learner view flags 0x%x", (unsigned)flags);
     if (format == RCW_VIEW_OFF && flags) return fail(RCW_ERR_INVALID_ARGUMENT, "RCW_VIEW_ONLY needs a format");
     if (frames < 1 || frames > RCW_VIEW_MAX_FRAMES)
         return fail(RCW_ERR_INVALID_ARGUMENT, "frames must be in 1..%d (got %d)", RCW_VIEW_MAX_FRAMES, frames);
-    const bool was_only = view_only(h);
-    RcwBuf view, tab, stack, last_episode;
-    RcwView v{};
+    if (format == RCW_VIEW_OFF) return RCW_OK;
+    if (layout != RCW_VIEW_CHW && layout != RCW_VIEW_HWC)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "layout must be RCW_VIEW_CHW or RCW_VIEW_HWC (got %d)", layout);
+    if (height < 1 || height > Hc || width < 1 || width > N)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "learner view size %d x %d outside 1..%d x 1..%d (no up-sampling)", height, width, Hc, N);
+    if (frames > 1 && (long long)(format == RCW_VIEW_RGB8 ? 3 : 1) * height * width >= (1ll << 31))
+        return fail(RCW_ERR_UNSUPPORTED, "a stack of frames of 2 GiB or more");
+    if (frames > 1 && layout != RCW_VIEW_CHW)
+        return fail(RCW_ERR_UNSUPPORTED, "a stack of %d frames needs RCW_VIEW_CHW (slot s is channels [s C, (s + 1) C))", frames);
+    RcwView& v = plan->v;
+    v.C = format == RCW_VIEW_RGB8 ? 3 : 1;
+    v.hwc = layout == RCW_VIEW_HWC ? 1 : 0;
+    v.h = height; v.w = width;
+    std::vector<int32_t>& t = plan->tab;
+    try { t.resize((size_t)height + width + 2); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    long long max_rows = 0, max_cols = 0;
+    for (int r = 0; r <= height; ++r) t[r] = (int32_t)((long long)r * Hc / height);
+    for (int c = 0; c <= width; ++c) t[(size_t)height + 1 + c] = (int32_t)((long long)c * N / width);
+    for (int r = 0; r < height; ++r) max_rows = std::max<long long>(max_rows, t[r + 1] - t[r]);
+    for (int c = 0; c < width; ++c) max_cols = std::max<long long>(max_cols, t[(size_t)height + 2 + c] - t[(size_t)height + 1 + c]);
+    const long long n = max_rows * max_cols;
+    v.wide = n * 256 + n >= (1ll << 31) ? 1 : 0;          // (a box's channel sum + n/2 must stay below 2^31 for 32-bit sums)
+    v.full_ok = height == Hc && width == N && rcw_view_full_eligible(dev, v.C, v.hwc) ? 1 : 0;
+    return RCW_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rcw_set_learner_view_stack(rcw_handle* h, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags, int32_t frames)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    ViewPlan plan;
+    rc = plan_learner_view(h->cfg, h->dev, format, layout, height, width, flags, frames, &plan); if (rc) return rc;
+    rcw_handle::LearnerView& lv = h->learner;
+    const bool was_only = lv.only();
+    rcw_handle::LearnerView fresh;
     if (format != RCW_VIEW_OFF) {
-        if (layout != RCW_VIEW_CHW && layout != RCW_VIEW_HWC)
-            return fail(RCW_ERR_INVALID_ARGUMENT, "layout must be RCW_VIEW_CHW or RCW_VIEW_HWC (got %d)", layout);
-        if (height < 1 || height > Hc || width < 1 || width > N)
-            return fail(RCW_ERR_INVALID_ARGUMENT, "learner view size %d x %d outside 1..%d x 1..%d (no up-sampling)", height, width, Hc, N);
-        if (frames > 1 && (long long)(format == RCW_VIEW_RGB8 ? 3 : 1) * height * width >= (1ll << 31))
-            return fail(RCW_ERR_UNSUPPORTED, "a stack of frames of 2 GiB or more");
-        if (frames > 1 && layout != RCW_VIEW_CHW)
-            return fail(RCW_ERR_UNSUPPORTED, "a stack of %d frames needs RCW_VIEW_CHW (slot s is channels [s C, (s + 1) C))", frames);
-        v.C = format == RCW_VIEW_RGB8 ? 3 : 1;
-        v.hwc = layout == RCW_VIEW_HWC ? 1 : 0;
-        v.h = height; v.w = width;
-        std::vector<int32_t> t;
-        try { t.resize((size_t)height + width + 2); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-        long long max_rows = 0, max_cols = 0;
-        for (int r = 0; r <= height; ++r) t[r] = (int32_t)((long long)r * Hc / height);
-        for (int c = 0; c <= width; ++c) t[(size_t)height + 1 + c] = (int32_t)((long long)c * N / width);
-        for (int r = 0; r < height; ++r) max_rows = std::max<long long>(max_rows, t[r + 1] - t[r]);
-        for (int c = 0; c < width; ++c) max_cols = std::max<long long>(max_cols, t[(size_t)height + 2 + c] - t[(size_t)height + 1 + c]);
-        const long long n = max_rows * max_cols;
-        v.wide = n * 256 + n >= (1ll << 31) ? 1 : 0;          // (a box's channel sum + n/2 must stay below 2^31 for 32-bit sums)
-        v.full_ok = height == Hc && width == N && rcw_view_full_eligible(h->dev, v.C, v.hwc) ? 1 : 0;
-        const size_t bytes = (size_t)h->B * v.C * (size_t)height * width;
-        hipError_t e = view.hipMalloc(bytes);
-        if (e == hipSuccess) e = tab.hipMalloc(t.size() * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemcpy(tab.get(), t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess && frames > 1) e = stack.hipMalloc(bytes * (size_t)frames);
-        if (e == hipSuccess && frames > 1) e = last_episode.hipMalloc((size_t)h->B * sizeof(uint32_t));
+        fresh.set = {format, layout, height, width, flags, frames};
+        fresh.view = plan.v;
+        const size_t bytes = (size_t)h->B * plan.v.C * (size_t)height * width, tab_bytes = plan.tab.size() * sizeof(int32_t);
+        hipError_t e = fresh.frame.hipMalloc(bytes);
+        if (e == hipSuccess) e = fresh.tab.hipMalloc(tab_bytes);
+        if (e == hipSuccess) e = hipMemcpy(fresh.tab.get(), plan.tab.data(), tab_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && frames > 1) e = fresh.stack.hipMalloc(bytes * (size_t)frames);
+        if (e == hipSuccess && frames > 1) e = fresh.last_episode.hipMalloc((size_t)h->B * sizeof(uint32_t));
         if (e != hipSuccess)                                       // the handle keeps its previous view
             return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "learner view buffer of %zu bytes: %s", bytes * (size_t)frames, hip_failure(e));
-        v.rows = tab.get<int32_t>();
-        v.cols = tab.get<int32_t>() + height + 1;
+        fresh.view.rows = fresh.tab.get<int32_t>();
+        fresh.view.cols = fresh.tab.get<int32_t>() + height + 1;
     }
-    RCW_HIP(replace_buffers(h, {&h->d_view, &h->d_view_tab, &h->d_view_stack, &h->d_view_episode}, {&view, &tab, &stack, &last_episode}));   // (the new ones, or none: the view switched off)
-    h->view = v;
-    h->view_frames = format != RCW_VIEW_OFF ? frames : 0;
-    h->view_fmt = format;
-    h->view_layout = format != RCW_VIEW_OFF ? layout : RCW_VIEW_CHW;
-    h->view_h = format != RCW_VIEW_OFF ? height : 0;
-    h->view_w = format != RCW_VIEW_OFF ? width : 0;
-    h->view_flags = flags;
-    if (format != RCW_VIEW_OFF) {
+    RCW_HIP(replace_buffers(h, {&lv.frame, &lv.tab, &lv.stack, &lv.last_episode}, {&fresh.frame, &fresh.tab, &fresh.stack, &fresh.last_episode}));   // (the new ones, or none: the view switched off)
+    lv.set = fresh.set;
+    lv.view = fresh.view;
+    if (lv.on()) {
         // the view kernel reads the descriptors: every step of the handle refreshes them from now on (as for rcw_columns_device_ptr)
         h->cols_live = true;
         rc = ensure_columns(h); if (rc) return rc;
     }
-    if (view_only(h)) {                                           // (a caller's one-launch request gives way: the step has no camera fill)
+    if (lv.only()) {                                              // (a caller's one-launch request gives way: the step has no camera fill)
         if (h->step_form_want == RCW_STEP_ONE_LAUNCH) h->step_form_want = 0;
         rc = plan_step_form(h, h->step_form_want); if (rc) return rc;
     }
@@ -1591,42 +1612,42 @@ int rcw_set_learner_view_stack(rcw_handle* h, int32_t format, int32_t layout, in
         rc = plan_step_form(h, h->step_form_want); if (rc) return rc;
         RCW_HIP(rcw_launch_fill(h->dev, h->dev.col_h, h->dev.col_c, h->dev.obs, (long long)h->dev.B * h->dev.N, nullptr, h->stream));
     }
-    if (format != RCW_VIEW_OFF) RCW_HIP(launch_view(h, nullptr, kStackRefill));
+    if (lv.on()) RCW_HIP(launch_view(h, nullptr, kStackRefill));
     return RCW_OK;
 }
 
 int rcw_learner_view_stack(rcw_handle* h, int32_t* frames)
 {
     if (!h || !frames) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    *frames = h->view_frames;
+    *frames = h->learner.set.frames;
     return RCW_OK;
 }
 
 int rcw_learner_view_info(rcw_handle* h, int32_t* format, int32_t* layout, int32_t* height, int32_t* width, int32_t* flags)
 {
     if (!h || !format || !layout || !height || !width || !flags) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    *format = h->view_fmt; *layout = h->view_layout; *height = h->view_h; *width = h->view_w; *flags = h->view_flags;
+    const auto& set = h->learner.set;
+    *format = set.fmt; *layout = set.layout; *height = set.h; *width = set.w; *flags = set.flags;
     return RCW_OK;
 }
 
 int rcw_learner_view_device_ptr(rcw_handle* h, void** device_ptr)
 {
     if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (h->view_fmt == RCW_VIEW_OFF) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
-    *device_ptr = h->view_frames > 1 ? h->d_view_stack.get() : h->d_view.get();
+    if (!h->learner.on()) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
+    *device_ptr = h->learner.batch();
     return RCW_OK;
 }
 
 int rcw_learner_view_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32_t count)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (h->view_fmt == RCW_VIEW_OFF) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
+    if (!h->learner.on()) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
     if (!out_host || first < 0 || count < 0 || first + (int64_t)count > h->B)
         return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
     rc = sync_and_check(h);
-    const size_t per = (size_t)h->view_frames * h->view.C * h->view_h * h->view_w;
-    const uint8_t* const src = h->view_frames > 1 ? h->d_view_stack.get<uint8_t>() : h->d_view.get<uint8_t>();
-    RCW_HIP(hipMemcpy(out_host, src + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
+    const size_t per = h->learner.agent_bytes();
+    RCW_HIP(hipMemcpy(out_host, h->learner.batch() + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -1634,10 +1655,10 @@ int rcw_expand_columns_view(rcw_handle* h, const int32_t* height_line_pu_device,
                             int32_t count, void* view_device)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (h->view_fmt == RCW_VIEW_OFF) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
+    if (!h->learner.on()) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
     if (!height_line_pu_device || !colour_id_device || !view_device || count < 1)
         return fail(RCW_ERR_INVALID_ARGUMENT, "bad argument");
-    RCW_HIP(rcw_launch_view(h->dev, h->view, height_line_pu_device, colour_id_device, count, nullptr, (uint8_t*)view_device, h->stream));
+    RCW_HIP(rcw_launch_view(h->dev, h->learner.view, height_line_pu_device, colour_id_device, count, nullptr, (uint8_t*)view_device, h->stream));
     return RCW_OK;
 }
 

@@ -7,7 +7,7 @@
 // colour on [pad, Hc - pad) and floor from max(pad, Hc - pad) on (pad = column_padding, SR:433-439), so a box's sums follow from
 // interval overlaps — O(box width) a pixel, whatever the box's height.
 //
-// Three kernels:
+// Five kernels.  The four that compute pixels share the palette (ViewPalette), the two stack kernels the slot shift (shift_chunk).
 //   rcw_view_full_kernel   (h, w) = (Hc, N), one byte a pixel per plane (gray, or RGB in CHW), N a power of two from 16 to 4096,
 //                          Hc < 32768: write-bandwidth bound like the camera fill.  A lane owns 16 image columns of one plane and
 //                          walks rows, one 16-byte store a row; its 16 columns' (ceiling end, floor start, colour value) are loaded once
@@ -41,6 +41,23 @@ __device__ __forceinline__ uint32_t view_channel(uint32_t colour, int k)
     if (C == 1) return (77u * R + 150u * G + 29u * B + 128u) >> 8;
     return k == 0 ? R : (k == 1 ? G : B);
 }
+
+// the channel values every pixel kernel works with: ceiling, floor, and the four colours' a byte each (colour id `id` at bits [8 id, 8 id + 8))
+template <int C>
+struct ViewPalette {
+    uint32_t vc[C], vf[C], vm4[C];
+    __device__ __forceinline__ explicit ViewPalette(const RcwDev& p)
+    {
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            vc[k] = view_channel<C>(p.ceiling_color, k);
+            vf[k] = view_channel<C>(p.floor_color, k);
+            vm4[k] = 0u;
+#pragma unroll
+            for (int id = 0; id < 4; ++id) vm4[k] |= view_channel<C>(p.colour[id], k) << (8 * id);
+        }
+    }
+};
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 
@@ -83,15 +100,10 @@ __global__ __launch_bounds__(kBlock) void rcw_view_full_kernel(const RcwDev p, c
     const int rows_pass = kBlock >> l_shift;
     const int row_lane = tid >> l_shift;
     const uint32_t items = (uint32_t)count * C * (uint32_t)blocks_per_plane;   // (< 2^31: rcw_launch_view)
-    uint32_t vc[C], vf[C], vm4[C];
+    const ViewPalette<C> pal(p);
+    uint32_t vc[C], vf[C];                                    // ceiling and floor in both halves of a 16-bit pair
 #pragma unroll
-    for (int k = 0; k < C; ++k) {
-        vc[k] = view_channel<C>(p.ceiling_color, k) * 0x00010001u;
-        vf[k] = view_channel<C>(p.floor_color, k) * 0x00010001u;
-        vm4[k] = 0u;
-#pragma unroll
-        for (int id = 0; id < 4; ++id) vm4[k] |= view_channel<C>(p.colour[id], k) << (8 * id);
-    }
+    for (int k = 0; k < C; ++k) { vc[k] = pal.vc[k] * 0x00010001u; vf[k] = pal.vf[k] * 0x00010001u; }
     uint32_t it = blockIdx.x;
     int4 hq[4];
     uint4 ids;
@@ -108,9 +120,9 @@ __global__ __launch_bounds__(kBlock) void rcw_view_full_kernel(const RcwDev p, c
         const int blk = (int)(it - pl * (uint32_t)blocks_per_plane);
         const uint32_t a = pl / C;
         const int ch = (int)(pl - a * C);
-        uint32_t vmc = vm4[0], vcc = vc[0], vfc = vf[0];
+        uint32_t vmc = pal.vm4[0], vcc = vc[0], vfc = vf[0];
 #pragma unroll
-        for (int k = 1; k < C; ++k) if (ch == k) { vmc = vm4[k]; vcc = vc[k]; vfc = vf[k]; }
+        for (int k = 1; k < C; ++k) if (ch == k) { vmc = pal.vm4[k]; vcc = vc[k]; vfc = vf[k]; }
         FullCols f;
         full_cols(f, hq, ids, Hc, vmc);
         if (it + gridDim.x < items) load(it + gridDim.x);    // (in flight during this item's stores)
@@ -165,15 +177,7 @@ __global__ __launch_bounds__(kBlock) void rcw_view_box_kernel(const RcwDev p, co
     int r = (int)((i - a * hw) / w), c = (int)(i - a * hw - (long long)r * w);
     const long long Sa = S / hw;
     const int Sr = (int)((S - Sa * hw) / w), Sc = (int)(S - Sa * hw - (long long)Sr * w);
-    uint32_t vc[C], vf[C], vm4[C];
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-        vc[k] = view_channel<C>(p.ceiling_color, k);
-        vf[k] = view_channel<C>(p.floor_color, k);
-        vm4[k] = 0u;
-#pragma unroll
-        for (int id = 0; id < 4; ++id) vm4[k] |= view_channel<C>(p.colour[id], k) << (8 * id);
-    }
+    const ViewPalette<C> pal(p);
     for (; i < total; i += S) {
         if (mask == nullptr || mask[a] != 0) {
             const int r0 = v.rows[r], r1 = v.rows[r + 1], c0 = v.cols[c], c1 = v.cols[c + 1];
@@ -192,7 +196,7 @@ __global__ __launch_bounds__(kBlock) void rcw_view_box_kernel(const RcwDev p, co
                 const int nm = nr - nc - nf;                                 // the colour's rows between
 #pragma unroll
                 for (int k = 0; k < C; ++k)
-                    acc[k] += (Acc)nc * vc[k] + (Acc)nm * ((vm4[k] >> sh) & 0xFFu) + (Acc)nf * vf[k];
+                    acc[k] += (Acc)nc * pal.vc[k] + (Acc)nm * ((pal.vm4[k] >> sh) & 0xFFu) + (Acc)nf * pal.vf[k];
             }
             const Acc n = (Acc)nr * (Acc)(c1 - c0);
             if (HWC) {
@@ -210,21 +214,25 @@ __global__ __launch_bounds__(kBlock) void rcw_view_box_kernel(const RcwDev p, co
     }
 }
 
-// Slots 0 .. k - 2 of one agent (per_v chunks each) take their successors: a lane moves the same chunk of every slot in ascending slot
-// order — four loads, then their four stores — and no other lane touches that chunk, so the shift in place needs no barrier.
+// One chunk of every slot of an agent's stack (slot s at c + s * per_v): slots 0 .. k - 2 take their successors in ascending order, four
+// loads, then their four stores.  A lane moves the SAME chunk of every slot and no other lane touches that chunk, so the shift in place
+// needs no barrier.  shift_slots: every chunk of the agent's stack, a lane a chunk.
+template <typename V>
+__device__ __forceinline__ void shift_chunk(V* c, int per_v, int k)
+{
+    for (int s = 0; s + 1 < k; s += 4) {
+        V t[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (s + j + 1 < k) t[j] = c[(long long)(s + j + 1) * per_v];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (s + j + 1 < k) c[(long long)(s + j) * per_v] = t[j];
+    }
+}
+
 template <typename V>
 __device__ __forceinline__ void shift_slots(V* base, int per_v, int k, int tid)
 {
-    for (int i = tid; i < per_v; i += kBlock) {
-        V* const c = base + i;
-        for (int s = 0; s + 1 < k; s += 4) {
-            V t[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (s + j + 1 < k) t[j] = c[(long long)(s + j + 1) * per_v];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (s + j + 1 < k) c[(long long)(s + j) * per_v] = t[j];
-        }
-    }
+    for (int i = tid; i < per_v; i += kBlock) shift_chunk(base + i, per_v, k);
 }
 
 // A workgroup per agent for the reduced sizes whose tables fit in LDS: the agent's columns are turned into (ceiling end, floor start,
@@ -243,21 +251,13 @@ __global__ __launch_bounds__(kBlock) void rcw_view_agent_kernel(const RcwDev p, 
     uint32_t* const s_vm = reinterpret_cast<uint32_t*>(s_fs + N);        // the colour's C channel values, a byte each
     int32_t* const s_rows = reinterpret_cast<int32_t*>(s_vm + N);
     int32_t* const s_cols = s_rows + h + 1;
-    uint32_t vc[C], vf[C], vm4[C];
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-        vc[k] = view_channel<C>(p.ceiling_color, k);
-        vf[k] = view_channel<C>(p.floor_color, k);
-        vm4[k] = 0u;
-#pragma unroll
-        for (int id = 0; id < 4; ++id) vm4[k] |= view_channel<C>(p.colour[id], k) << (8 * id);
-    }
+    const ViewPalette<C> pal(p);
     for (int j = tid; j < N; j += kBlock) {
         const int pad = column_padding(Hc, col_h[a * N + j]);
         const uint32_t sh = 8u * (col_c[a * N + j] & 3u);
         uint32_t m = 0u;
 #pragma unroll
-        for (int k = 0; k < C; ++k) m |= ((vm4[k] >> sh) & 0xFFu) << (8 * k);
+        for (int k = 0; k < C; ++k) m |= ((pal.vm4[k] >> sh) & 0xFFu) << (8 * k);
         s_pad[j] = pad; s_fs[j] = max(pad, Hc - pad); s_vm[j] = m;
     }
     for (int j = tid; j <= h; j += kBlock) s_rows[j] = v.rows[j];
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(kBlock) void rcw_view_agent_kernel(const RcwDev p, 
             const uint32_t nf = (uint32_t)max(0, r1 - max(r0, fs));
             const uint32_t nm = (uint32_t)nr - nc - nf;
 #pragma unroll
-            for (int k = 0; k < C; ++k) acc[k] += nc * vc[k] + nm * ((m >> (8 * k)) & 0xFFu) + nf * vf[k];
+            for (int k = 0; k < C; ++k) acc[k] += nc * pal.vc[k] + nm * ((m >> (8 * k)) & 0xFFu) + nf * pal.vf[k];
         }
         const uint32_t n = (uint32_t)nr * (uint32_t)(c1 - c0);
 #pragma unroll
@@ -296,6 +296,9 @@ __global__ __launch_bounds__(kBlock) void rcw_view_agent_kernel(const RcwDev p, 
 // every read of slot k - 1 in front of the stores that follow; each pixel, computed once as above, goes to slot k - 1 — or to all k slots on a
 // refill or when the agent's episode counter is not the one recorded at its previous push (rcw_view_push_kernel below states the rule).
 // Against that kernel behind rcw_view_agent_kernel this saves a launch, and the staged frame's store and load.
+// The staging and the pixel loop are rcw_view_agent_kernel's, COPIED — a fix to one is owed to the other.  Behind any function boundary the
+// gray instantiations of both kernels take 74 VGPRs for 62 / 63, six waves a SIMD for eight: the compiler's 16-wide form of the column
+// loop sits at that edge and its schedule follows the order of the blocks around it.
 struct RcwViewStack {
     int k, refill;                  // slots an agent; 1: reset / set_state / a new view — all k slots take the frame
     const uint32_t* episode;        // the agents' episode counters now
@@ -318,21 +321,13 @@ __global__ __launch_bounds__(kBlock) void rcw_view_agent_push_kernel(const RcwDe
     uint32_t* const s_vm = reinterpret_cast<uint32_t*>(s_fs + N);
     int32_t* const s_rows = reinterpret_cast<int32_t*>(s_vm + N);
     int32_t* const s_cols = s_rows + h + 1;
-    uint32_t vc[C], vf[C], vm4[C];
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-        vc[k] = view_channel<C>(p.ceiling_color, k);
-        vf[k] = view_channel<C>(p.floor_color, k);
-        vm4[k] = 0u;
-#pragma unroll
-        for (int id = 0; id < 4; ++id) vm4[k] |= view_channel<C>(p.colour[id], k) << (8 * id);
-    }
+    const ViewPalette<C> pal(p);
     for (int j = tid; j < N; j += kBlock) {
         const int pad = column_padding(Hc, col_h[a * N + j]);
         const uint32_t sh = 8u * (col_c[a * N + j] & 3u);
         uint32_t m = 0u;
 #pragma unroll
-        for (int k = 0; k < C; ++k) m |= ((vm4[k] >> sh) & 0xFFu) << (8 * k);
+        for (int k = 0; k < C; ++k) m |= ((pal.vm4[k] >> sh) & 0xFFu) << (8 * k);
         s_pad[j] = pad; s_fs[j] = max(pad, Hc - pad); s_vm[j] = m;
     }
     for (int j = tid; j <= h; j += kBlock) s_rows[j] = v.rows[j];
@@ -362,7 +357,7 @@ __global__ __launch_bounds__(kBlock) void rcw_view_agent_push_kernel(const RcwDe
             const uint32_t nf = (uint32_t)max(0, r1 - max(r0, fs));
             const uint32_t nm = (uint32_t)nr - nc - nf;
 #pragma unroll
-            for (int k = 0; k < C; ++k) acc[k] += nc * vc[k] + nm * ((m >> (8 * k)) & 0xFFu) + nf * vf[k];
+            for (int k = 0; k < C; ++k) acc[k] += nc * pal.vc[k] + nm * ((m >> (8 * k)) & 0xFFu) + nf * pal.vf[k];
         }
         const uint32_t n = (uint32_t)nr * (uint32_t)(c1 - c0);
 #pragma unroll
@@ -376,10 +371,9 @@ __global__ __launch_bounds__(kBlock) void rcw_view_agent_push_kernel(const RcwDe
 // The k-frame stack (rcw_set_learner_view_stack, frames = k > 1): the view kernels above keep writing the single frame into the staging
 // batch; this kernel, behind them, moves it into the agent's k slots of `per` bytes each (slot 0 the oldest).  A refill (reset / set_state /
 // setting the view: the masked agents) or an agent whose episode counter differs from the one recorded at its previous push (auto_reset
-// re-sampled it in this step) takes the staged frame k times; every other agent's slot s takes slot s + 1 and slot k - 1 the staged frame.
-// A workgroup owns an agent: all its lanes read the recorded counter, the barrier, then lane 0 records the new one.  A lane moves the
-// SAME chunk of every slot in ascending slot order (four loads, then their four stores) and no other lane touches that chunk: the shift
-// in place needs no barrier.  V: 16-byte chunks where per is a multiple of 16, bytes otherwise.
+// re-sampled it in this step) takes the staged frame k times; every other agent's slots shift (shift_chunk) and slot k - 1 takes the
+// staged frame.  A workgroup owns an agent: all its lanes read the recorded counter, the barrier, then lane 0 records the new one.
+// V: 16-byte chunks where per is a multiple of 16, bytes otherwise.
 template <typename V>
 __global__ __launch_bounds__(kBlock) void rcw_view_push_kernel(const V* __restrict__ staged, V* stack, const uint32_t* __restrict__ episode,
                                                                uint32_t* last_episode, const uint8_t* __restrict__ mask, int per_v, int k,
@@ -400,13 +394,8 @@ __global__ __launch_bounds__(kBlock) void rcw_view_push_kernel(const V* __restri
             for (int s = 0; s < k; ++s) c[(long long)s * per_v] = f;
             continue;
         }
-        for (int s = 0; s < k; s += 4) {
-            V t[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (s + j < k) t[j] = s + j + 1 < k ? c[(long long)(s + j + 1) * per_v] : f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (s + j < k) c[(long long)(s + j) * per_v] = t[j];
-        }
+        shift_chunk(c, per_v, k);
+        c[(long long)(k - 1) * per_v] = f;
     }
 }
 
@@ -432,6 +421,15 @@ int rcw_view_full_eligible(const RcwDev& p, int C, int hwc)
     return (C == 1 || !hwc) && p.N >= 16 && p.N <= 4096 && (p.N & (p.N - 1)) == 0 && p.Hc < 32768 ? 1 : 0;
 }
 
+// launch(C, HWC) as integral constants: the (C, HWC) the agent and box kernels exist for (gray's two layouts coincide: HWC = false)
+template <typename Launch>
+static void view_instance(const RcwView& v, Launch launch)
+{
+    if (v.C == 1) launch(std::integral_constant<int, 1>{}, std::false_type{});
+    else if (v.hwc) launch(std::integral_constant<int, 3>{}, std::true_type{});
+    else launch(std::integral_constant<int, 3>{}, std::false_type{});
+}
+
 hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,
                            const uint8_t* mask_dev, uint8_t* out, hipStream_t s)
 {
@@ -450,20 +448,19 @@ hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col
     }
     const size_t lds = view_agent_lds(p, v);
     if (lds != 0) {
-#define RCW_VIEW_AGENT(CC, HH) hipLaunchKernelGGL((rcw_view_agent_kernel<CC, HH>), dim3(count), dim3(kBlock), lds, s, p, v, col_h, col_c, mask_dev, out)
-        if (v.C == 1) RCW_VIEW_AGENT(1, false);
-        else if (v.hwc) RCW_VIEW_AGENT(3, true);
-        else RCW_VIEW_AGENT(3, false);
-#undef RCW_VIEW_AGENT
+        view_instance(v, [&](auto c, auto hwc) {
+            hipLaunchKernelGGL((rcw_view_agent_kernel<decltype(c)::value, decltype(hwc)::value>), dim3(count), dim3(kBlock), lds, s, p, v, col_h, col_c, mask_dev, out);
+        });
         return hipGetLastError();
     }
     const long long total = (long long)count * v.h * v.w;
     const int grid = (int)std::min<long long>((total + kBlock - 1) / kBlock, 1ll << 24);   // (a lane a pixel: every load of the batch in flight at once)
-#define RCW_VIEW_BOX(CC, HH, WW) hipLaunchKernelGGL((rcw_view_box_kernel<CC, HH, WW>), dim3(grid), dim3(kBlock), 0, s, p, v, col_h, col_c, count, mask_dev, out)
-    if (v.C == 1) { if (v.wide) RCW_VIEW_BOX(1, false, true); else RCW_VIEW_BOX(1, false, false); }
-    else if (v.hwc) { if (v.wide) RCW_VIEW_BOX(3, true, true); else RCW_VIEW_BOX(3, true, false); }
-    else { if (v.wide) RCW_VIEW_BOX(3, false, true); else RCW_VIEW_BOX(3, false, false); }
-#undef RCW_VIEW_BOX
+    view_instance(v, [&](auto c, auto hwc) {
+        constexpr int C = decltype(c)::value;
+        constexpr bool HWC = decltype(hwc)::value;
+        if (v.wide) hipLaunchKernelGGL((rcw_view_box_kernel<C, HWC, true>), dim3(grid), dim3(kBlock), 0, s, p, v, col_h, col_c, count, mask_dev, out);
+        else        hipLaunchKernelGGL((rcw_view_box_kernel<C, HWC, false>), dim3(grid), dim3(kBlock), 0, s, p, v, col_h, col_c, count, mask_dev, out);
+    });
     return hipGetLastError();
 }
 
