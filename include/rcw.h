@@ -459,7 +459,8 @@ RCW_API int rcw_update_top_view_form(rcw_handle* h, int32_t* form);
  * the geometry cannot take it (the handle then keeps the automatic choice).  runs = 0: automatic; 1..8: the two-kernel
  * form draws and stores the batch in that many runs of agents.  Waits for the handle's stream; reallocates the form's
  * scratch in HBM.  The library reads no environment variable other than RCW_RCCL_LIBRARY: what used to be development
- * switches (RCW_TOP_SPLIT, RCW_TOP_RUNS, ...) exists only in the development build (make dev -> librcw_hip_dev.so). */
+ * switches (RCW_TOP_SPLIT, RCW_TOP_RUNS, ...) exists only in the development build (make dev -> librcw_hip_dev.so), whose knobs override
+ * what the rules compute and select nothing this library cannot reach. */
 RCW_API int rcw_set_top_view_form(rcw_handle* h, int32_t form, int32_t runs);
 /* How many launches a step — RCW.act!(env, a) SR:333-340 — takes; both forms leave the same state and the same pixels:
  *   RCW_STEP_TWO_LAUNCHES  the cast kernel (dynamics SR:139-191, cast_rays! SR:195-231, the columns of update_camera_view!

@@ -220,7 +220,8 @@ _libs = {}
 def load(library=None) -> C.CDLL:
     """Load librcw_hip.so — the shipped library, which reads no RCW_* environment variable but RCW_RCCL_LIBRARY; loud
     failure when it has not been built.  `library="dev"` (or a path) loads the development build instead
-    (`make dev`: -DRCW_DEV_SWITCHES, the tuning knobs and the measured-and-rejected kernel variants); development
+    (`make dev`: -DRCW_DEV_SWITCHES — the same kernels, plus the RCW_* tuning knobs that override what the rules compute, the
+    rules without a device and the record of error returns taken); development
     tools may also point every default load at another build with RCW_LIBRARY=<path> — an explicit path, never a
     silent switch inside the library."""
     global _lib

@@ -83,10 +83,9 @@ struct rcw_handle {
     RcwBuf d_pos, d_dir, d_goal, d_reward, d_done, d_episode, d_tile_map, d_dir_table, d_ray_table, d_obs, d_col_h, d_col_c, d_err, d_status, d_top_view;
     // two-kernel top view: planes / player pixels / tile codes in HBM, the side stream the draw kernel runs on
     RcwBuf d_top_plane, d_top_hdr, d_top_codes;
-    RcwBuf d_top_flags; uint32_t top_epoch = 0;   // the store kernel follows the draw kernel (dev/top_follow_publish.inc)
     // Several draw workgroups an agent (top_parts > 1) OR their bits into the agent's plane in HBM, and only rcw_top_store_kernel — which reads
     // every plane word exactly once — leaves the zero the next drawing needs: a drawing whose store did not follow (a failed launch in
-    // between, the development build's skip-the-store switch) leaves bits behind that every later frame would carry.  Set in front of such a
+    // between) leaves bits behind that every later frame would carry.  Set in front of such a
     // drawing, cleared behind its store's launch; a drawing that finds it set clears the planes first.
     bool top_plane_dirty = false;
     RcwEvent ev_top_fork, ev_top_join[8];   // (a join event per run of agents)
@@ -95,8 +94,6 @@ struct rcw_handle {
     RcwEvent ev_actions[2];
     int action_slot = 0;
     bool profiling = false;
-    int step_pieces = 1;               // development experiment only (RCW_STEP_PIECES)
-    RcwBuf d_step_flags, d_step_hc; uint32_t step_epoch = 0;   // development experiment only (RCW_STEP_FUSED)
     // the one-launch step (rcw_fill256_cast_kernel): two buffers of [B][5][N] packed column words — d_spec[spec_cur] holds the frames of the
     // CURRENT state (slot 0) and of its four successors (slots 1..4), written by the last casting launch; spec_primed: for every agent
     // (each buffer ends in one byte per agent: which of its slots hold the very frame slot 0 holds — rcw_cast.hip, cast_body).
@@ -105,6 +102,7 @@ struct rcw_handle {
     // only (next to launch_step_camera); false costs nothing but the skip: the next one-launch step writes every pixel and sets it again.
     RcwBuf d_spec[2]; int spec_cur = 0; bool spec_primed = false, obs_current = false;
     int spec_on = 0;                   // a step is ONE launch (rcw_fill256_cast_kernel)
+    bool step_store_all = false;       // development build (RCW_STEP_STORE_ALL=1): the one-launch step stores every frame, changed or not — the A/B of the unchanged-frame skip
     // The (height_line_pu, colour id) descriptors of the current frames (d_col_h / d_col_c) are what the two-launch step hands from its cast
     // kernel to its fill kernel; the one-launch step's fill reads the slots instead, and every store of the casting workgroups costs the
     // launch more than its bytes (profiles/r06_step_forms.txt) — so it writes the descriptors only for a caller that holds their device
@@ -165,7 +163,7 @@ hipError_t launch_top_view(rcw_handle* h, const uint8_t* mask_dev, bool beside, 
     if (d.top_parts > 1) {                                   // (see rcw_handle::top_plane_dirty; every order below forks from the handle's stream behind this)
         if (h->top_plane_dirty && (e = hipMemsetAsync(h->d_top_plane.get(), 0, rcw_top_plane_bytes(d), h->stream)) != hipSuccess) return e;
         h->top_plane_dirty = true;
-        struct Clean { rcw_handle* h; hipError_t* e; ~Clean() { if (*e == hipSuccess && !(h->dev.top_debug & 2)) h->top_plane_dirty = false; } };
+        struct Clean { rcw_handle* h; hipError_t* e; ~Clean() { if (*e == hipSuccess) h->top_plane_dirty = false; } };
         hipError_t result = hipErrorUnknown;
         Clean clean{h, &result};
         result = launch_top_view_ordered(h, mask_dev, beside, between, fused_event);
@@ -180,9 +178,6 @@ hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool 
 {
     const RcwDev& d = h->dev;
     hipError_t e;
-#ifdef RCW_DEV_SWITCHES
-#include "dev/api_top_follow.inc"   // RCW_TOP_FOLLOW, the launch order in which the store kernel follows the draw kernel
-#endif
     if (!beside) {                                           // stand-alone, two kernels back to back on the handle's stream
         if ((e = rcw_launch_top_draw(d, mask_dev, 0, d.B, h->stream, d.top_draw_block_alone)) != hipSuccess) return e;
         if ((e = rcw_launch_top_store(d, mask_dev, 0, d.B, h->stream)) != hipSuccess) return e;
@@ -273,7 +268,7 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
             // casting launch left in `cur`; the casting workgroups commit the actions and cast the new states' successors into the other buffer
             uint16_t* const next = h->d_spec[h->spec_cur ^ 1].get<uint16_t>();
             if (prof && ((e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess || (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess)) return e;
-            if ((e = rcw_launch_step_spec(d, actions_dev, nullptr, cur, next, true, h->cols_live, was_current, h->stream)) != hipSuccess) return e;
+            if ((e = rcw_launch_step_spec(d, actions_dev, nullptr, cur, next, true, h->cols_live, was_current && !h->step_store_all, h->stream)) != hipSuccess) return e;
             h->spec_cur ^= 1;
             obs_is_current(h);                                    // (skipped or not: every agent's frame is the new state's)
             if (!h->cols_live) h->cols_stale = true;
@@ -292,19 +287,6 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
         if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
         return hipSuccess;
     }
-#ifdef RCW_DEV_SWITCHES
-#include "dev/api_step_pieces.inc"   // RCW_STEP_PIECES=2, the batch in two halves with the second cast beside the first fill
-#endif
-#ifdef RCW_DEV_SWITCHES
-    if (d.step_fused && rcw_step_fusable(d)) {
-        // Development experiment (RCW_STEP_FUSED=1, docs/experiments.md): cast and camera fill in ONE launch
-        if (prof && ((e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess || (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess)) return e;
-        h->dev.step_epoch = ++h->step_epoch;
-        if ((e = rcw_launch_step256(d, actions_dev, mask_dev, h->step_epoch, h->stream)) != hipSuccess) return e;
-        if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
-        return hipSuccess;
-    }
-#endif
     if ((e = rcw_launch_cast(d, actions_dev, mask_dev, h->stream)) != hipSuccess) return e;
     if (prof && (e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess) return e;
     auto fill = [&](hipStream_t fs) -> hipError_t {            // (fs: the handle's stream, or its side stream: launch_top_view)
@@ -506,14 +488,14 @@ constexpr TopRule kTopRules[kTopRuleCount] = {
     /* kRuns4Gib              */ {"four_runs_from_gib", 4, "GiB", "profiles/r03_top_view_shapes.txt: 16 GiB of top view 4516 / 4409 / 4332 / 4294 us with 1 / 2 / 4 / 8 runs, 32 GiB 8586 / 8459 / 7658 / 8068"},
     /* kRuns2Gib              */ {"two_runs_from_gib", 2, "GiB", "same table; runs of 256 MiB do not pay (205 vs 181 us at 1 GiB of 512^2 px images)"},
     /* kSideStreamMinBytes    */ {"side_stream_form_from_bytes", 256.0 * 1048576.0, "B", "profiles/r04_top_view_small_batches.txt: the fork / join and the extra launch cost ~13 us a step (39 / 51 / 53 / 60 / 102 / 341 us against the ring's 36 / 38 / 41 / 47 / 103 / 387 at 1 .. 4096 agents)"},
-    /* kPartsMax              */ {"draw_parts_max", 4, "workgroups", "profiles/r05_draw_kernel.txt (tools/r05_draw_parts.sh): 1024^2 px x 64 agents 53.6 / 38.6 / 30.5 us with 1 / 2 / 4 parts"},
+    /* kPartsMax              */ {"draw_parts_max", 4, "workgroups", "profiles/r05_draw_kernel.txt (tools/experiments.md: r05_draw_parts.sh): 1024^2 px x 64 agents 53.6 / 38.6 / 30.5 us with 1 / 2 / 4 parts"},
     /* kPartsMinRays          */ {"draw_part_min_rays", 128, "rays", "same table: a part's fixed costs (plane cleared, every end point, plane scanned) are most of a workgroup's life; x 256 agents 61.4 / 78.7 / 110"},
     /* kFillGBperMs           */ {"camera_fill_rate", 6.5e6, "B/us", "profiles/r05_kernel_stats.csv: rcw_fill256_kernel 156 us a GiB = 6.88 TB/s; 6.5 with its smaller siblings"},
     /* kFillLateStartUs       */ {"side_stream_late_start", 12, "us", "profiles/r05_top_view_shapes.txt / tools/step_timeline.sh: a kernel behind an event of the other stream starts ~13 us later than behind a kernel of its own (19 against 6 us after the cast kernel's end)"},
     /* kDrawUsPerGibFewRays   */ {"draw_floor_few_rays", 34, "us/GiB", "profiles/r05_draw_kernel.txt, r05_top_view_shapes.txt (a): the draw kernel's floor per GiB of top view with up to 256 rays (768^2 px x 455: 37 us)"},
     /* kDrawUsPerGibManyRays  */ {"draw_floor_many_rays", 55, "us/GiB", "same: beyond 256 rays (1024^2 px x 256, 1024 rays: 58-61 us)"},
     /* kDrawManyRays          */ {"draw_many_rays_from", 257, "rays", "the boundary between the two floors above"},
-    /* kDrawPartialRound      */ {"draw_partial_round", 0.7, "", "profiles/r05_draw_kernel.txt (tools/r05_draw_first.sh): a partial round of draw workgroups takes about as long as a full one (768^2 px x 114 / 228 / 341 agents 90 -> 75, 129 -> 115, 169 -> 155 us)"},
+    /* kDrawPartialRound      */ {"draw_partial_round", 0.7, "", "profiles/r05_draw_kernel.txt (tools/experiments.md: r05_draw_first.sh): a partial round of draw workgroups takes about as long as a full one (768^2 px x 114 / 228 / 341 agents 90 -> 75, 129 -> 115, 169 -> 155 us)"},
     /* kDrawLdsCap            */ {"draw_kernel_lds_cap", 159 * 1024, "B", "rcw_top_split_unit / rcw_top_flat_cols: the draw kernel's plane + ray lists within the CU's LDS less 1 KiB"},
     /* kFillWavefrontsPerCu   */ {"fill_wavefronts_per_cu", 4, "wavefronts", "one workgroup of the camera fill (four wavefronts) sits on every CU: what is left of the CU's wavefront slots is the drawing's"},
 };
@@ -525,7 +507,6 @@ constexpr double top_rule(TopRuleId id) { return kTopRules[id].value; }
 int top_view_rule(RcwDev& d, const rcw_config* cfg, size_t B, const RcwHw& hw, int want_form, int want_runs, bool lenient)
 {
     const int H = cfg->height_tile_map_tu, W = cfg->width_tile_map_tu, N = cfg->num_rays, Hc = cfg->height_camera_view_pu;
-    d.top_blk_shift = 0; d.top_epoch = 0; d.top_signal = 0; d.top_follow = 0; d.top_follow_ok = 0;
     d.top_lds = 0; d.top_split = 0; d.top_flat = 0; d.top_plane_words = 0; d.top_unit_px = 256; d.top_runs = 1;
     d.top_alone_split = 0; d.top_fused = 0; d.top_grid = hw.cus; d.top_store_grid = d.fill_grid; d.top_store_plain = 0; d.top_draw_block = 256; d.top_draw_block_alone = 256; d.top_draw_first = 0; d.top_parts = 1;
     if (!cfg->render_top_view) {
@@ -612,7 +593,7 @@ int top_view_rule(RcwDev& d, const rcw_config* cfg, size_t B, const RcwHw& hw, i
     // reads every plane word exactly once and leaves the zero the next drawing needs.
     const int draw_per_cu = rcw_top_draw_per_cu(d, d.top_draw_block, hw.lds_per_cu, hw.waves_per_cu - (int)top_rule(kFillWavefrontsPerCu));
     d.top_parts = 1;
-    if (d.top_split && !d.top_flat && d.top_unit_px == 256 && !d.top_fused && !d.top_draw_r4) {
+    if (d.top_split && !d.top_flat && d.top_unit_px == 256 && !d.top_fused) {
         const long long slots = (long long)hw.cus * draw_per_cu;
         int parts = (int)std::min<long long>((long long)top_rule(kPartsMax), slots / (long long)B);
         while (parts > 1 && N / parts < (int)top_rule(kPartsMinRays)) --parts;
@@ -641,8 +622,8 @@ int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient)
 {
     RcwDev& d = h->dev;
     const size_t B = (size_t)h->B;
-    RCW_HIP(replace_buffers(h, {&h->d_top_plane, &h->d_top_hdr, &h->d_top_codes, &h->d_top_flags}));
-    d.top_plane = nullptr; d.top_hdr = nullptr; d.top_codes = nullptr; d.top_flags = nullptr; h->top_epoch = 0;
+    RCW_HIP(replace_buffers(h, {&h->d_top_plane, &h->d_top_hdr, &h->d_top_codes}));
+    d.top_plane = nullptr; d.top_hdr = nullptr; d.top_codes = nullptr;
     int rc = top_view_rule(d, &h->cfg, B, h->hw, want_form, want_runs, lenient);
     if (rc != RCW_OK || !h->cfg.render_top_view) return rc;
     if (d.top_split) {
@@ -657,18 +638,11 @@ int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient)
         if (e == hipSuccess) e = h->d_top_hdr.hipMalloc((size_t)h->B * sizeof(int2));
         if (e == hipSuccess) e = hipMemsetAsync(h->d_top_hdr.get(), 0, (size_t)h->B * sizeof(int2), h->stream);
         if (e == hipSuccess) e = h->d_top_codes.hipMalloc(rcw_top_codes_bytes(d));
-#ifdef RCW_DEV_SWITCHES
-        if (e == hipSuccess) e = h->d_top_flags.hipMalloc((size_t)h->B * sizeof(uint32_t));                      // (experiment RCW_TOP_FOLLOW)
-        if (e == hipSuccess) e = hipMemsetAsync(h->d_top_flags.get(), 0, (size_t)h->B * sizeof(uint32_t), h->stream);
-#endif
         if (e == hipSuccess && !h->top_stream.get()) e = h->top_stream.hipStreamCreate();
         if (e == hipSuccess && !h->ev_top_fork.get()) e = h->ev_top_fork.hipEventCreate(hipEventDisableTiming);
         for (RcwEvent& q : h->ev_top_join) if (e == hipSuccess && !q.get()) e = q.hipEventCreate(hipEventDisableTiming);
         if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "top view planes: %s", hip_failure(e));
         d.top_plane = h->d_top_plane.get<uint32_t>(); d.top_hdr = h->d_top_hdr.get<int2>(); d.top_codes = h->d_top_codes.get<uint2>();
-#ifdef RCW_DEV_SWITCHES
-#include "dev/api_top_follow_plan.inc"   // RCW_TOP_FOLLOW: the counters' block size and where the store kernel may follow the draw kernel
-#endif
     }
     hipError_t e = rcw_prepare_top_view(d, h->device);
     if (e != hipSuccess) return fail(RCW_ERR_HIP, "top view kernel attribute: %s", hip_failure(e));
@@ -1063,48 +1037,15 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     // with two a lane, 256 columns 12.3 vs 12.7; 1024 columns take 256 lanes either way), two a lane for small batches, where
     // an agent's own latency is what counts
     { const int lanes = h->B >= 1024 ? (N + 3) / 4 : (N + 1) / 2; d.cast_block = lanes >= 256 ? 256 : ((lanes + 63) / 64) * 64; }
-    d.cast_ballot = 0; d.cast_table_lds = 0; d.cast_r3 = 0; d.cast_waves = 0; d.top_debug = 0;
-    // development builds (make dev: -DRCW_DEV_SWITCHES -> librcw_hip_dev.so) read tuning knobs and the measured-and-rejected
-    // kernel variants from the environment; the shipped library reads nothing but RCW_RCCL_LIBRARY
+    // development builds (make dev: -DRCW_DEV_SWITCHES -> librcw_hip_dev.so) read tuning knobs — each overrides a value the rule
+    // computes, and so selects code the shipped library can reach too — from the environment; the shipped library reads nothing but
+    // RCW_RCCL_LIBRARY
     if (const char* v = RCW_DEV_ENV("RCW_CAST_BLOCK")) { const int b = std::atoi(v); if (b == 64 || b == 128 || b == 192 || b == 256) d.cast_block = b; }
-    if (const char* v = RCW_DEV_ENV("RCW_CAST_KERNEL")) d.cast_r3 = std::strcmp(v, "r3") == 0 ? 1 : 0;
-    if (const char* v = RCW_DEV_ENV("RCW_CAST_WAVES")) d.cast_waves = std::atoi(v) ? 1 : 0;
-    if (const char* v = RCW_DEV_ENV("RCW_CAST_MARCH")) d.cast_ballot = std::strcmp(v, "ballot") == 0 ? 1 : 0;
-    if (const char* v = RCW_DEV_ENV("RCW_CAST_TABLE"))   // only where tile bytes + 5 N table values fit the default 64 KiB
-        d.cast_table_lds = std::strcmp(v, "lds") == 0 && rcw_step_lds_bytes(d) + 2 * (size_t)H + (size_t)RCW_TABLE_ROWS * N * h->real_size + 128 <= 64 * 1024 ? 1 : 0;
     if (const char* v = RCW_DEV_ENV("RCW_FILL_GRID")) { const int g = std::atoi(v); if (g >= 1 && g <= 65536) d.fill_grid = g; }
     if (const char* v = RCW_DEV_ENV("RCW_FILL_PLAIN")) d.fill_plain = std::atoi(v) ? 1 : 0;
     if (const char* v = RCW_DEV_ENV("RCW_FILL_FLAT")) d.fill_flat = std::atoi(v) ? 1 : 0;
-    if (const char* v = RCW_DEV_ENV("RCW_TOP_DEBUG")) d.top_debug = std::atoi(v);
-    d.fill_pairs = 0;
-    if (const char* v = RCW_DEV_ENV("RCW_FILL_FLAT_PAIRS")) d.fill_pairs = std::atoi(v);   // 1: two wavefronts a slot; 2: timing only, a prefetch without loads
-    d.top_draw_r4 = 0;
-    d.top_draw_banks = 0;
-    if (const char* v = RCW_DEV_ENV("RCW_TOP_DRAW")) { d.top_draw_r4 = std::strcmp(v, "r4") == 0 ? 1 : 0; d.top_draw_banks = std::strcmp(v, "banks") == 0 ? 1 : (std::strcmp(v, "halfds") == 0 ? 2 : (std::strcmp(v, "nods") == 0 ? 3 : 0)); }
     d.top_rotate = 33;                                                       // (measured: rcw_kernels.hip, rcw_top_store_flat_kernel)
     if (const char* v = RCW_DEV_ENV("RCW_TOP_ROTATE")) { const int r = std::atoi(v); if (r >= 0 && r < 65536) d.top_rotate = r; }
-    d.fill_trips = -1;
-    if (const char* v = RCW_DEV_ENV("RCW_FILL_TRIPS")) d.fill_trips = std::atoi(v);
-    d.step_fused = 0; d.step_flags = nullptr; d.step_hc = nullptr; d.step_epoch = 0;
-    if (const char* v = RCW_DEV_ENV("RCW_STEP_FUSED")) {
-        if (std::atoi(v)) {
-            hipError_t e = h->d_step_flags.hipMalloc(B * sizeof(uint32_t));
-            if (e == hipSuccess) e = h->d_step_hc.hipMalloc(B * (size_t)N * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemset(h->d_step_flags.get(), 0, B * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemset(h->d_step_hc.get(), 0, B * (size_t)N * sizeof(uint32_t));
-            if (e != hipSuccess) return fail(RCW_ERR_OUT_OF_MEMORY, "fused step: %s", hip_failure(e));
-            d.step_flags = h->d_step_flags.get<uint32_t>(); d.step_hc = h->d_step_hc.get<uint32_t>(); d.step_fused = std::atoi(v) == 2 ? 2 : 1; d.step_epoch = 0;
-        }
-    }
-    if (const char* v = RCW_DEV_ENV("RCW_STEP_PIECES")) {
-        h->step_pieces = std::atoi(v) == 2 ? 2 : 1;
-        if (h->step_pieces == 2) {                                                            // the side stream and its two events
-            hipError_t e = h->top_stream.hipStreamCreate();
-            if (e == hipSuccess) e = h->ev_top_fork.hipEventCreate(hipEventDisableTiming);
-            if (e == hipSuccess) e = h->ev_top_join[0].hipEventCreate(hipEventDisableTiming);
-            if (e != hipSuccess) return fail(RCW_ERR_HIP, "side stream: %s", hip_failure(e));
-        }
-    }
     {
         int want_form = 0, want_runs = 0;
         if (const char* v = RCW_DEV_ENV("RCW_TOP_SPLIT")) { const int f = std::atoi(v); if (!f) want_form = RCW_TOP_VIEW_ONE_KERNEL; else if (f == 2) want_form = RCW_TOP_VIEW_TWO_KERNELS; }
@@ -1114,14 +1055,10 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     }
     if (rcw_step_lds_bytes(d) > 64 * 1024)
         return fail(RCW_ERR_UNSUPPORTED, "tile map + column buffer need %zu B of LDS (> 64 KiB)", rcw_step_lds_bytes(d));
-#ifdef RCW_DEV_SWITCHES
-    d.spec_debug = 0;
-    if (const char* v = RCW_DEV_ENV("RCW_SPEC_DEBUG")) d.spec_debug = std::atoi(v);
-#endif
+    if (const char* v = RCW_DEV_ENV("RCW_STEP_STORE_ALL")) h->step_store_all = std::atoi(v) != 0;
     {
         int want = 0;
         if (const char* v = RCW_DEV_ENV("RCW_STEP_FORM")) { const int f = std::atoi(v); if (f == RCW_STEP_TWO_LAUNCHES) want = f; }
-        if (d.step_fused || h->step_pieces == 2) want = RCW_STEP_TWO_LAUNCHES;          // (development experiments on the two-launch step)
         rc = plan_step_form(h.get(), want); if (rc) return rc;
     }
 

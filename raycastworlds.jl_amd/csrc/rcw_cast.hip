@@ -5,10 +5,6 @@
 
 namespace {
 
-#ifdef RCW_DEV_SWITCHES
-#include "dev/cast_kernel_r3.inc"   // RCW_CAST_KERNEL=r3, the round-3 cast kernel and its two rejected variants
-#endif
-
 // ---- kernel 1 of a step: dynamics + ray cast + projection --------------------------------
 // One workgroup per agent.  Output: the agent's new state and one compact descriptor per
 // image column (height_line_pu, colour id) — 5 bytes per column, against the 4·H_cam bytes
@@ -23,8 +19,7 @@ namespace {
 //      nothing else (UT:13-14) —: the old heading's direction vector (move_forward / move_backward, UT:16-17) and the new
 //      heading's ray-table entries of this lane's first kCastCols view columns (20 registers), in flight while the tile
 //      bytes are unpacked into LDS and the dynamics run.
-// (The round-3 kernel asked for the same loads in the same order of SOURCE lines; its ISA waited five times:
-// rcw_cast_kernel_r3 above, kept in the development build for the comparison.)
+// (The round-3 kernel asked for the same loads in the same order of SOURCE lines; its ISA waited five times: docs/experiments.md.)
 
 #ifdef RCW_TRACE_WAVES
 // Measurement build only (make trace, tools/cast_trace.py): the first wavefront of each of the first 4096 workgroups of
@@ -45,6 +40,7 @@ namespace {
 // One view column: march, projection, descriptor.  Returns whether the ray left the map (the caller reports it once per lane:
 // a branch around two stores in every column costs the issue-bound kernel eight instructions a column).  The descriptor arrays
 // are addressed as uniform base (the agent's row) + 32-bit lane offset.
+// (PUBLISH / hc_a, here and in cast_body: what is left of a retired experiment, never set; they leave with RcwDev's dead members: rcw_kernels.h)
 template <typename T, bool TIE_LE, bool DIST_PRE, bool PUBLISH = false>
 __device__ __forceinline__ bool cast_column(const RcwDev& p, const uint8_t* tb, int32_t* col_h_a, uint8_t* col_c_a, int i, T x, T y, T dx, T dy, T ddx, T ddy, T dot,
                                             uint32_t* hc_a = nullptr)
@@ -57,10 +53,6 @@ __device__ __forceinline__ bool cast_column(const RcwDev& p, const uint8_t* tb, 
     const uint32_t k = (uint32_t)(p.N - 1 - i);                             // SR:431 (0-based)
     *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(col_h_a) + k * 4u) = h;
     *(col_c_a + k) = (uint8_t)cid;
-#ifdef RCW_DEV_SWITCHES
-    // (rcw_step256_kernel: the two in one word for the fill workgroups of the SAME launch — a write-through store, agent scope)
-    if (PUBLISH) __hip_atomic_store(hc_a + k, (uint32_t)column_padding(256, h) | ((uint32_t)cid << 9) | (p.step_epoch << 11), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     return r.oob;
 }
 
@@ -133,19 +125,12 @@ __device__ __forceinline__ bool spec_fan(const RcwDev& p, const uint8_t* tb, int
         const int h = r.oob ? p.Hc : hl;
         const int cid = ((r.bits & 1u) ? 0 : 2) + (r.dim == 1 ? 0 : 1);     // SR:417-429
         const uint32_t k = (uint32_t)(N - 1 - i);                           // SR:431 (0-based)
-#ifdef RCW_DEV_SWITCHES
-        if (COLS && col_h_a != nullptr && !(p.spec_debug & 4)) {
-#else
         if (COLS && col_h_a != nullptr) {                                    // (wave-uniform)
-#endif
             *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(col_h_a) + k * 4u) = h;
             *(col_c_a + k) = (uint8_t)cid;
         }
         const uint16_t w = (uint16_t)spec_word(p.Hc, h, cid);
         uint16_t* const q = slot_a + k;
-#ifdef RCW_DEV_SWITCHES
-        if (p.spec_debug & 4) { asm volatile("" :: "v"(w)); left |= r.oob; return w; }   // (timing probe: no slot stores)
-#endif
 #pragma unroll
         for (int s = 0; s < 5; ++s) if (slots & (1u << s)) q[(uint32_t)s * stride] = w;   // (wave-uniform)
         left |= r.oob;
@@ -211,8 +196,8 @@ __device__ __forceinline__ void agent_sync()
     else __syncthreads();
 }
 
-// WAVE = false: the workgroup is one agent (tid = its thread, nthr = blockDim).  WAVE = true (development build only, measured and
-// rejected): 64 lanes are an agent and the workgroup's wavefronts are DIFFERENT agents (rcw_cast_waves_kernel): the same code with
+// WAVE = false: the workgroup is one agent (tid = its thread, nthr = blockDim).  WAVE = true (the one-launch step at up to 256 view
+// columns): 64 lanes are an agent and the workgroup's wavefronts are DIFFERENT agents: the same code with
 // tid = the lane, nthr = 64, the wavefront's own slice of LDS, and no workgroup barrier.
 template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE, bool PUBLISH = false, bool SPEC = false>
 __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask,
@@ -385,9 +370,6 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
         uint16_t w0[kCastCols];                                             // this lane's words of the current frame
         uint32_t differs = 0u;                                              // bit s: a word of slot s differs from slot 0's (this lane's columns)
         left_the_map = spec_fan<T, TIE_LE, DIST_PRE, true>(p, tb, tid, nthr, x, y, r_dx, r_dy, r_ddx, r_ddy, r_dot, tab, dvn.x, dvn.y, ch, col_c_a, slot_a, stride, stay, w0, differs);
-#ifdef RCW_DEV_SWITCHES
-        if (p.spec_debug & 16) return;                                      // (timing probe: the current state's fan only)
-#endif
         if (!reborn) {
             if (f_free) (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, xf, yf, r_dx, r_dy, r_ddx, r_ddy, r_dot, tab, dvn.x, dvn.y, nullptr, nullptr, slot_a, stride, 2u, w0, differs);
             if (b_free) (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, xb, yb, r_dx, r_dy, r_ddx, r_ddy, r_dot, tab, dvn.x, dvn.y, nullptr, nullptr, slot_a, stride, 4u, w0, differs);
@@ -396,9 +378,6 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
                 const int dt = turn == 0 ? (d_new + 1 >= p.nd ? 0 : d_new + 1) : (d_new - 1 < 0 ? p.nd - 1 : d_new - 1);   // UT:13-14
                 const T* const tt = Real<T>::ray_table(p) + (size_t)dt * RCW_TABLE_ROWS * N;
                 const vec2 dvt = Real<T>::dir_table(p)[dt];
-#ifdef RCW_DEV_SWITCHES
-                if (!(p.spec_debug & 8))                                    // (timing probe: the turns with the current heading's rows, no further table loads)
-#endif
                 spec_load_rows<T>(tt, tid, nthr, N, r_dx, r_dy);
                 spec_derive_rows<T>(dvt.x, dvt.y, r_dx, r_dy, r_ddx, r_ddy, r_dot);
                 (void)spec_fan<T, TIE_LE, DIST_PRE, false>(p, tb, tid, nthr, x, y, r_dx, r_dy, r_ddx, r_ddy, r_dot, tt, dvt.x, dvt.y, nullptr, nullptr, slot_a, stride, turn == 0 ? 8u : 16u, w0, differs);
@@ -470,14 +449,6 @@ __global__ __launch_bounds__(kBlock) void rcw_cast_kernel(const RcwDev p,
     cast_body<T, TIE_LE, DIST_PRE, false>(p, actions, mask, first + (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, lds, (int)blockIdx.x);
 }
 
-#ifdef RCW_DEV_SWITCHES
-#include "dev/cast_waves_kernel.inc"   // RCW_CAST_WAVES=1, a wavefront per agent in the two-launch cast kernel (measured, rejected)
-#endif
-
-#ifdef RCW_DEV_SWITCHES
-#include "dev/step256_kernel.inc"   // RCW_STEP_FUSED, cast and fill in one launch WITH a hand-off inside it (measured, rejected)
-#endif
-
 // ---- the WHOLE step in one launch, without a dependency inside it (round 6) ------------------------------------------------
 // act!(env, a) SR:333-340 orders dynamics -> cast_rays! -> update_camera_view!; as two kernels the cast (11 us at 4096 agents x
 // 256 columns, latency / issue bound) and a launch boundary sit in front of every fill.  But the frame of step t + 1 depends only on
@@ -485,8 +456,8 @@ __global__ __launch_bounds__(kBlock) void rcw_cast_kernel(const RcwDev p,
 // also cast the four successors of the new state into five slots of packed column words [B][5][N] (slot 0: the state itself — an
 // invalid action leaves the agent where it is; slots 1..4: the actions), and the fill workgroups of launch t + 1 only read the action
 // and pick the slot: action -> word -> colour, three dependent round trips a group like rcw_fill256_kernel's height -> colour id ->
-// colour (its pace: DESIGN.md §4.2).  Nothing in a launch waits for anything else in it — unlike rcw_step256_kernel above, whose
-// fill workgroups waited for the cast's flags and gained nothing.  Two slot buffers alternate: launch t reads the one launch t - 1
+// colour (its pace: DESIGN.md §4.2).  Nothing in a launch waits for anything else in it (a form whose fill
+// workgroups waited for the cast's flags gained nothing: docs/experiments.md, RCW_STEP_FUSED).  Two slot buffers alternate: launch t reads the one launch t - 1
 // wrote and writes the other.  Workgroups 0 .. fill_blocks - 1 are the fill's (dispatched first, one per CU as in a launch of their
 // own); the casting workgroups — VALU / LDS work — run beside them under the HBM-bound sweep.  rcw_cast_successors_kernel is the
 // casting half alone: it PRIMES the slots behind a reset / set_state (or a first step), the camera fill following as a launch of its own.
@@ -623,9 +594,6 @@ __global__ __launch_bounds__(kBlock) void rcw_fill256_cast_kernel(const RcwDev p
                                                                   const uint16_t* __restrict__ slots_in, uint16_t* __restrict__ slots_out, int lds_words, int n_shift, int cols, int keep)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-#ifdef RCW_DEV_SWITCHES
-    if (p.spec_debug & ((int)blockIdx.x < fill_blocks ? 2 : 1)) return;     // (timing probes: one half of the launch alone)
-#endif
     if ((int)blockIdx.x < fill_blocks) { fill256_spec_body<false>(p, actions, slots_in, out, total_cols, (int)blockIdx.x, fill_blocks, n_shift, (uint32_t)keep); return; }
     cast_successors<T, TIE_LE, DIST_PRE, WAVE>(p, actions, mask, (int)blockIdx.x - fill_blocks, slots_out, lds, lds_words, cols);
 }
@@ -749,13 +717,10 @@ size_t rcw_step_lds_bytes(const RcwDev& p)
 {
     return (((size_t)p.H * p.W + 15) & ~(size_t)15);   // one byte per tile
 }
-// the cast kernel's LDS: the tile bytes (+ the heading's table slice under the RCW_CAST_TABLE=lds development switch)
-static size_t rcw_cast_lds_bytes(const RcwDev& p)                          // guard | tile bytes | guard | re-sampled pose (32 B) [| table slice]
+// the cast kernel's LDS: guard | tile bytes | guard | re-sampled pose (32 B)
+static size_t rcw_cast_lds_bytes(const RcwDev& p)
 {
     const size_t tiles = (((size_t)p.H * p.W + 2 * (size_t)p.H + 15) & ~(size_t)15);
-#ifdef RCW_DEV_SWITCHES
-    if (p.cast_table_lds) return tiles + 32 + (size_t)RCW_TABLE_ROWS * p.N * (p.real64 ? 8 : 4);
-#endif
     return tiles + 32;
 }
 
@@ -763,15 +728,6 @@ hipError_t rcw_launch_cast(const RcwDev& p, const uint8_t* actions_dev, const ui
                            hipStream_t s, int first, int count)
 {
     if (count < 0) count = p.B - first;
-#ifdef RCW_DEV_SWITCHES
-    if (p.cast_ballot || p.cast_table_lds || p.cast_r3) {                  // the round-3 kernel and its two rejected variants
-        RCW_DISPATCH(rcw_cast_kernel_r3, dim3(count), dim3(p.cast_block), rcw_cast_lds_bytes(p), p, actions_dev, mask_dev, first);
-        return hipGetLastError();
-    }
-#endif
-#ifdef RCW_DEV_SWITCHES
-#include "dev/launch_cast_waves.inc"   // RCW_CAST_WAVES=1, the launch of rcw_cast_waves_kernel
-#endif
     RCW_DISPATCH(rcw_cast_kernel, dim3(count), dim3(p.cast_block), rcw_cast_lds_bytes(p), p, actions_dev, mask_dev, first);
     return hipGetLastError();
 }
@@ -794,10 +750,7 @@ hipError_t rcw_launch_step_spec(const RcwDev& p, const uint8_t* actions_dev, con
                                 uint16_t* slots_out, bool with_fill, bool cols, bool keep, hipStream_t s)
 {
     const int icols = cols ? 1 : 0;
-    int ikeep = keep ? 1 : 0;
-#ifdef RCW_DEV_SWITCHES
-    if (p.spec_debug & 32) ikeep = 0;                                       // (A/B measurement: every pixel stored, as before the skip)
-#endif
+    const int ikeep = keep ? 1 : 0;
     const size_t per_agent = (rcw_cast_lds_bytes(p) + 15) & ~(size_t)15;
     const int fill_blocks = with_fill ? p.fill_grid : 0;
     const long long total_cols = (long long)p.B * p.N;
@@ -829,10 +782,6 @@ hipError_t rcw_launch_step_spec(const RcwDev& p, const uint8_t* actions_dev, con
     }
     return hipGetLastError();
 }
-
-#ifdef RCW_DEV_SWITCHES
-#include "dev/launch_step256.inc"   // RCW_STEP_FUSED, eligibility and launch of rcw_step256_kernel
-#endif
 
 hipError_t rcw_launch_reset(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s)
 {

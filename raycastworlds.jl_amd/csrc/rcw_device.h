@@ -318,10 +318,6 @@ __device__ __forceinline__ RayHit<T> cast_ray_guarded(const uint8_t* tiles, int 
     return r;
 }
 
-#ifdef RCW_DEV_SWITCHES
-#include "dev/cast_ray_ballot.inc"   // RCW_CAST_MARCH=ballot, the ballot-bounded march (measured, rejected)
-#endif
-
 // ---- column height  SR:404-411 ------------------------------------------------------------
 template <typename T>
 __device__ __forceinline__ int height_line_pu(const RcwDev& p, T dist, T dot)

@@ -86,10 +86,6 @@ __global__ __launch_bounds__(kBlock) void rcw_fill256_kernel(const RcwDev p,
 #endif
 }
 
-#ifdef RCW_DEV_SWITCHES
-#include "dev/fill256_trips_kernel.inc"   // RCW_FILL_TRIPS, rcw_fill256_kernel's body with more round trips a prefetch
-#endif
-
 // The same moving window for the camera heights that tile a 1 KiB chunk evenly: H_cam = 256·k (a chunk is one of
 // the k row blocks of a column: M = 1) and H_cam = 128 or 64 (a chunk holds M = 2 or 4 whole columns; lane l of a
 // chunk belongs to column l / (64 / M)).  Lane l prefetches the descriptor(s) of the wavefront's l-th next chunk, as
@@ -212,10 +208,8 @@ __device__ __forceinline__ u32x4 flat_fill_pixels(int r, int Hc, uint4 d0, uint4
     return v;
 }
 
-// PAIR (development build, RCW_FILL_FLAT_PAIRS=1: measured, profiles/r05_flat_kernels.txt): workgroups of EIGHT wavefronts, two to a
-// slot of the window — wavefronts w and w + 4 make the same group's descriptors and take its chunks by turns (t even / odd) —: the
-// same compact window, twice the issue slots (a wavefront alone on its SIMD issues a vector instruction every four cycles, two
-// wavefronts one every two).
+// PAIR: what is left of a retired experiment (two wavefronts to a slot of the window, workgroups of eight: docs/experiments.md); no launch
+// sets it.  Taking the parameter out renames the kernel and waits with RcwDev's dead members for a measurement (rcw_kernels.h).
 template <bool ALIGNED, int K, bool PAIR = false>                       // K = the columns a chunk may touch (254 / H_cam + 2)
 __global__ __launch_bounds__(PAIR ? 2 * kBlock : kBlock) void rcw_fill_flat_kernel(const RcwDev p,
                                                                const int32_t* __restrict__ col_h,
@@ -266,9 +260,6 @@ __global__ __launch_bounds__(PAIR ? 2 * kBlock : kBlock) void rcw_fill_flat_kern
 #pragma unroll
         for (int j = 0; j < KS; ++j) {
             const uint32_t c = min(col + (unsigned)j, last_col);
-#ifdef RCW_DEV_SWITCHES
-            if (p.fill_pairs == 2) { hh[j] = (int32_t)(c & 127u); cc[j] = c & 3u; mm[j] = 1u; continue; }   // (timing only, wrong frames: a prefetch without loads — what is the prefetch's latency worth?)
-#endif
             hh[j] = col_h[c];
             cc[j] = (uint32_t)col_c[c];
             mm[j] = mask != nullptr ? (uint32_t)mask[c / (unsigned)p.N] : 1u;   // (wave-uniform branch; the division only with a mask)
@@ -278,9 +269,6 @@ __global__ __launch_bounds__(PAIR ? 2 * kBlock : kBlock) void rcw_fill_flat_kern
             const bool valid = j <= touched && col + (unsigned)j <= last_col && mm[j] != 0u;
             const uint32_t pad = (uint32_t)column_padding(Hc, hh[j]);
             if (j <= touched && !valid) all_valid = false;
-#ifdef RCW_DEV_SWITCHES
-            if (p.fill_pairs == 2) { desc[lane * KS + j] = make_uint4(pad, (uint32_t)Hc - pad, 0x808080u + cc[j], valid ? 1u : 0u); continue; }
-#endif
             desc[lane * KS + j] = make_uint4(pad, (uint32_t)Hc - pad, p.colour[cc[j] & 3], valid ? 1u : 0u);
         }
         const int state_l = (exists ? 1 : 0) | (all_valid ? 2 : 0);
@@ -476,9 +464,6 @@ static FillKernel fill_choice(const RcwDev& p, long long total_cols)
 }
 const char* rcw_fill_kernel_name(const RcwDev& p, long long total_cols)
 {
-#ifdef RCW_DEV_SWITCHES
-    if (p.step_fused && total_cols == (long long)p.B * p.N && rcw_step_fusable(p)) return "rcw_step256_kernel";
-#endif
     // a step that also renders the top view in the fused form: the camera fill of the whole batch and the drawing are ONE launch
     if (p.top_view && p.top_split && p.top_fused && total_cols == (long long)p.B * p.N) return "rcw_fill256_draw_kernel";
     switch (fill_choice(p, total_cols)) {
@@ -499,9 +484,6 @@ hipError_t rcw_launch_fill(const RcwDev& p, const int32_t* col_h, const uint8_t*
     switch (fill_choice(p, total_cols)) {
     case kFill256:
 #ifdef RCW_DEV_SWITCHES
-#include "dev/launch_fill256_trips.inc"   // RCW_FILL_TRIPS, the launch of rcw_fill256_trips_kernel
-#endif
-#ifdef RCW_DEV_SWITCHES
         if (p.fill_plain) { hipLaunchKernelGGL(rcw_fill256_kernel<true>, dim3(grid), dim3(kBlock), 0, s, p, col_h, col_c, frames4, total_cols, mask_dev); break; }
 #endif
         hipLaunchKernelGGL(rcw_fill256_kernel<false>, dim3(grid), dim3(kBlock), 0, s, p, col_h, col_c, frames4, total_cols, mask_dev);
@@ -519,12 +501,7 @@ hipError_t rcw_launch_fill(const RcwDev& p, const int32_t* col_h, const uint8_t*
         // the moving window over 256-pixel chunks of the flat batch
         const int K = rcw_fill_flat_cols(p);
         const size_t lds = (size_t)(kBlock / 64) * 64 * (K + 1) * sizeof(uint4) + 512;   // (+ the fast loop reads a 65th chunk's pairs behind the last wavefront's)
-#ifdef RCW_DEV_SWITCHES
-#define RCW_FILL_FLAT(AL, KK) do { if (p.fill_pairs == 1) hipLaunchKernelGGL((rcw_fill_flat_kernel<AL, KK, true>), dim3(grid), dim3(2 * kBlock), 2 * lds, s, p, col_h, col_c, frames, total_cols, mask_dev); \
-                                   else hipLaunchKernelGGL((rcw_fill_flat_kernel<AL, KK>), dim3(grid), dim3(kBlock), lds, s, p, col_h, col_c, frames, total_cols, mask_dev); } while (0)
-#else
 #define RCW_FILL_FLAT(AL, KK) hipLaunchKernelGGL((rcw_fill_flat_kernel<AL, KK>), dim3(grid), dim3(kBlock), lds, s, p, col_h, col_c, frames, total_cols, mask_dev)
-#endif
 #define RCW_FILL_FLAT_K(KK) case KK: if ((p.Hc & 3) == 0) RCW_FILL_FLAT(true, KK); else RCW_FILL_FLAT(false, KK); break
         switch (K) { RCW_FILL_FLAT_K(2); RCW_FILL_FLAT_K(3); RCW_FILL_FLAT_K(4); RCW_FILL_FLAT_K(5); RCW_FILL_FLAT_K(6); RCW_FILL_FLAT_K(7); RCW_FILL_FLAT_K(8);
                      RCW_FILL_FLAT_K(9); RCW_FILL_FLAT_K(11); RCW_FILL_FLAT_K(12);

@@ -28,9 +28,6 @@ __device__ __forceinline__ void fill256_body(const RcwDev& p, const int32_t* __r
             // instead of 1250 (1 GiB: 158 instead of 156.5).  The empty asm statements pin the order the round-1 kernel had.
             int h = col_h[mine];
             asm volatile("" :: "v"(h) : "memory");
-#ifdef RCW_DEV_SWITCHES
-#include "dev/fill256_extra_trips.inc"   // RCW_FILL_TRIPS: more dependent round trips in front of the prefetch
-#endif
             pad_l = column_padding(256, h);
             const uint32_t cid = col_c[mine];
             asm volatile("" :: "v"(cid) : "memory");

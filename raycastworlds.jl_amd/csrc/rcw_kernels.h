@@ -9,6 +9,10 @@
 // so lane i of the cast phase reads five coalesced floats (SR:214-221, SR:404).
 #define RCW_TABLE_ROWS 5
 
+// (The members marked "development only" below — cast_ballot ... fill_pairs, top_flags ... top_follow_ok, step_*, top_debug, spec_debug — are
+// what is left of retired experiments (docs/experiments.md): no build sets or reads them any more, but for the draw kernel's `!p.top_signal`
+// and cast_body's PUBLISH.  Taking them out moves every kernel's argument offsets, so it waits for a measurement against the parent on the
+// GPU: docs/review_ledger.md §19, profiles/retire_variants_isa.txt.)
 struct RcwDev {
     // geometry / config (all wave-uniform, live in SGPRs)
     int32_t B, H, W, N, nd, Hc;
@@ -134,7 +138,6 @@ size_t rcw_top_plane_bytes(const RcwDev& p);
 size_t rcw_top_codes_bytes(const RcwDev& p);
 struct RcwHw { int cus, lds_per_cu, waves_per_cu; };       // what the top view's rule needs of the device (hipDeviceProp_t: multiProcessorCount, sharedMemPerBlock, maxThreadsPerMultiProcessor / 64)
 int rcw_top_draw_per_cu(const RcwDev& p, int draw_block, int lds_per_cu = 160 * 1024, int waves = 28);   // draw workgroups resident on a CU together: by LDS, by the wavefront slots the camera fill leaves
-int rcw_top_follow_fits(const RcwDev& p, int draw_block, bool beside_fill, int cus);   // draw + store (+ camera fill) workgroups resident on one CU together
 hipError_t rcw_launch_top_draw(const RcwDev& p, const uint8_t* mask_dev, int first, int count, hipStream_t s, int block = 0);    // agents [first, first + count); block: threads a workgroup, 0 = p.top_draw_block
 hipError_t rcw_launch_top_store(const RcwDev& p, const uint8_t* mask_dev, int first, int count, hipStream_t s);
 // the one-launch step (round 6): eligibility of a geometry, the bytes of one of its two slot buffers ([B][5][N] packed column words + [B] bytes), the launch
@@ -142,10 +145,6 @@ int rcw_step_spec_eligible(const RcwDev& p);
 size_t rcw_step_spec_slot_bytes(const RcwDev& p);
 hipError_t rcw_launch_step_spec(const RcwDev& p, const uint8_t* actions_dev, const uint8_t* mask_dev, const uint16_t* slots_in,
                                 uint16_t* slots_out, bool with_fill, bool cols, bool keep, hipStream_t s);   // cols: the step also leaves the current frame's (height, colour id) descriptors; keep: p.obs holds every agent's current frame — unchanged frames are not stored again
-#ifdef RCW_DEV_SWITCHES
-bool rcw_step_fusable(const RcwDev& p);       // development experiment (RCW_STEP_FUSED): cast + camera fill in one launch
-hipError_t rcw_launch_step256(const RcwDev& p, const uint8_t* actions_dev, const uint8_t* mask_dev, uint32_t epoch, hipStream_t s);
-#endif
 int rcw_fill_draw_fusable(const RcwDev& p);   // a step's camera fill + top-view drawing in one launch: this geometry takes it
 hipError_t rcw_launch_fill256_draw(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);   // (fills p.obs from p.col_h / p.col_c, draws every agent)
 hipError_t rcw_prepare_top_view(const RcwDev& p, int device);

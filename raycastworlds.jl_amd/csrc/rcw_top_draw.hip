@@ -397,7 +397,6 @@ __device__ __forceinline__ void top_store(const RcwDev& p, int a, const TopBuf& 
         const int vpc = Ht >> 2;
         const int wpc = top_col_bits(p) >> 5;                               // plane words per (padded) column
         const int step = kTopGroup / 64;                                    // columns between two of this wavefront's
-        [[maybe_unused]] const int ncols = (c_hi - c_lo - wave + step - 1) / step;           // wave-uniform trip count (development path below)
         auto overlay = [](uint32_t bits, int e, uint32_t colour, uint32_t under) {
             const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)bits, e, 1);   // 0 or ~0
             return (m & colour) | (~m & under);                             // v_bfi_b32
@@ -415,12 +414,6 @@ __device__ __forceinline__ void top_store(const RcwDev& p, int a, const TopBuf& 
             int jp0 = wave;                                                  // this wavefront's columns: wave, wave + 4, ...
             const uint32_t* lp = b.line + jp0 * wpc + (ip0 >> 5);
             u32x4* dst = out + (size_t)jp0 * vpc + (ip0 >> 2);
-#ifdef RCW_DEV_SWITCHES
-            if (p.top_debug & 8) {      // development: the bare store stream of this path (no pixel logic, no LDS reads)
-                for (int c = 0; c < ncols; ++c) { const u32x4 o = {grid_c, grid_c, grid_c, grid_c}; if (active) *dst = o; dst += dstep; }
-                continue;
-            }
-#endif
             // Tile columns outermost: step = 4 divides pu, so every tile column holds cpt = pu / 4 of this wavefront's
             // columns, the tile's colour is read once (the next tile's byte is already on its way), and a frame
             // column (SR:366-367) can only be the first one (wavefront 0) or the last one (wavefront 3) of a tile.
@@ -563,9 +556,6 @@ __global__ __launch_bounds__(kTopBlock, 6) void rcw_top_view_kernel(const RcwDev
                 top_prepare(p, a, b, tid);
                 prepared += 1;
                 lds_signal(c_prepared); lds_wait(c_prepared, 4 * prepared);  // planes cleared by all four wavefronts
-#ifdef RCW_DEV_SWITCHES
-                if (!(p.top_debug & 1))
-#endif
                 top_draw<T, TIE_LE, DIST_PRE>(p, a, b, tid);
             }
             lds_signal(c_drawn);
@@ -575,9 +565,6 @@ __global__ __launch_bounds__(kTopBlock, 6) void rcw_top_view_kernel(const RcwDev
             const int a = blockIdx.x + q * G;
             const bool on = mask == nullptr || mask[a] != 0;
             lds_wait(c_drawn, 4 * (q + 1));
-#ifdef RCW_DEV_SWITCHES
-            if (p.top_debug & 2) { lds_signal(c_stored); continue; }
-#endif
             if (on) top_store(p, a, top_buf(p, bufs + (size_t)(q % K) * bw), tid);
             lds_signal(c_stored);
         }
@@ -595,24 +582,6 @@ __global__ __launch_bounds__(kTopBlock, 6) void rcw_top_view_kernel(const RcwDev
 // Taken when a 1 KiB chunk (256 pixels of one image column) holds whole tiles and a lane's four pixels whole
 // quarters of one: pu in {8, 16, 32, 64, 128, 256}, H·pu a multiple of 256; and the player's circle fits one
 // 32-bit mask per image column (2·rp + 1 <= 32).  Other geometries keep the ring kernel.
-//
-// ---- EXPERIMENT, development build only (RCW_TOP_FOLLOW, docs/experiments.md): the store kernel FOLLOWS the draw kernel.  Launched
-// on two streams with no event between them, the two run at once: the draw workgroup of agent a, when its plane, header and codes
-// are in memory, adds one to the counter of the agent's BLOCK (2^p.top_blk_shift consecutive agents; the counters are never reset:
-// after the call numbered p.top_epoch a complete block stands at epoch x its agents); a storing wavefront, before it loads anything
-// of a group of 64 chunks, waits until every block up to the group's last agent is complete — 64 counters a look, one per lane.
-// What the draw kernel publishes goes out as write-through stores (sc0 sc1: through the XCD's L2 to memory) — a release fence in
-// front of the counter writes the WHOLE L2 back instead, the store kernel's gigabyte of pixels included, once per agent (100 us an
-// agent); the counters are relaxed agent-scope atomics; a wavefront that has seen its blocks complete invalidates its caches once
-// (acquire) and reads on with ordinary loads.  Bit-exact — and SLOWER than draw -> store back to back at every shape (a wavefront's
-// look drains its stores, every advance invalidates an L2 under the window): rejected, not in the shipped library.
-#ifdef RCW_DEV_SWITCHES
-#include "dev/top_follow_publish.inc"   // RCW_TOP_FOLLOW, the draw kernel publishes its agents for a store kernel that follows it (measured, rejected)
-#endif
-
-#ifdef RCW_DEV_SWITCHES
-#include "dev/top_draw_body_r4.inc"   // RCW_TOP_DRAW=r4, the round-4 body of the draw kernel
-#endif
 
 // ---- the draw kernel's body (round 5) ------------------------------------------------------------------------------
 // One workgroup per agent: rays -> lines in an LDS bit plane -> the plane (1/32 of the image) to HBM, with the player's pixel
@@ -621,11 +590,6 @@ __global__ __launch_bounds__(kTopBlock, 6) void rcw_top_view_kernel(const RcwDev
 // cfg-2), so this body (a) asks for everything it needs from HBM in two batches, as rcw_cast_kernel does; (b) does not walk what
 // another lane walks anyway — see top_covered_prefix: exact, the planes are bit for bit those of the round-4 body —; (c) has no
 // integer or Float64 division in its set-up; (d) walks with a hand-scheduled loop of 8 vector instructions a pixel.
-#ifdef RCW_DEV_SWITCHES
-#define RCW_PLANE_STORE(q, v) do { if (p.top_signal) store_through((q), (v)); else *(q) = (v); } while (0)   // (the experiment above: write-through where the draw kernel publishes)
-#else
-#define RCW_PLANE_STORE(q, v) (*(q) = (v))
-#endif
 constexpr int kDrawRays = 2;                // rays a lane holds from the early table loads (more rays a lane take a loop)
 constexpr uint32_t kNoLine = 0xFFFFFFFFu;   // the ray's line is not in the list: off-image end points (walked at once, clipped), or no such ray
 // words of the draw kernel's LDS: header, tile bytes, line plane | the rays' end pixels [N] | what is left of each ray's line [N] | the lines to walk,
@@ -634,9 +598,6 @@ constexpr uint32_t kNoLine = 0xFFFFFFFFu;   // the ray's line is not in the list
 // counters, which are dead by then.  At 768 x 768 px this is what lets TWO draw workgroups share a CU's 160 KiB: 79.8 KiB each.)
 __host__ __device__ __forceinline__ size_t top_draw_lds_words(const RcwDev& p)
 {
-#ifdef RCW_DEV_SWITCHES
-    if (p.top_draw_r4) return top_buf_words(p) + 4 * (size_t)((p.N + 3) & ~3) + 64;      // (the round-4 body: the one-kernel form's whole buffer in front)
-#endif
     return 4 + top_tile_words(p) + top_line_words(p) + 4 * (size_t)((p.N + 3) & ~3) + 64;
 }
 
@@ -734,10 +695,6 @@ __device__ __forceinline__ uint32_t lds_address(const void* q) { return (uint32_
                  "1:"                                                                                                        \
                  : "+v"(A), "+v"(f), "+v"(rem), "=&v"(t), "=&v"(m), "=&v"(dd)                                                \
                  : "v"(slope), "v"(smaj), "v"(sboth), "v"(rem0), "v"(f0), "v"(A_0) : "vcc", "memory")
-
-#ifdef RCW_DEV_SWITCHES
-#include "dev/top_draw_step_no_lds.inc"   // RCW_TOP_DRAW=halfds / nods, the walk's step without its LDS atomic (timing probes)
-#endif
 
 // LDS atomic add that returns the old value, by name: through __hip_atomic_fetch_add the compiler wraps every such add in a
 // wavefront-wide reduction loop (its atomic optimizer), two dozen instructions where one is meant
@@ -863,13 +820,7 @@ __device__ __forceinline__ void top_draw_body(const RcwDev& p, const uint8_t* __
         const int n = g.a + 1 - skip;                                        // pixels skip .. a to walk
         uint32_t m = 0x7FFFu;                                                // (nothing of this line is walked)
         if (n > 0) {
-            int cls = kDrawBuckets - 1 - min(kDrawBuckets - 1, (n - 1) >> len_shift);
-#ifdef RCW_DEV_SWITCHES
-            if (p.top_draw_banks == 1) {                                     // (experiment) four kinds of line x eight classes of length: a wavefront's lanes then move through the banks alike
-                const int kind = (g.oct & 1) | ((((g.oct & 1) ? (g.oct >> 1) : (g.oct >> 2)) & 1) << 1);
-                cls = kind * 8 + 7 - min(7, (n - 1) >> (len_shift + 2));
-            }
-#endif
+            const int cls = kDrawBuckets - 1 - min(kDrawBuckets - 1, (n - 1) >> len_shift);
             m = (uint32_t)skip | ((uint32_t)cls << 15) | (lds_add_return(bcount + cls, 1u) << 20);
         }
         meta[i] = m;
@@ -934,10 +885,7 @@ __device__ __forceinline__ void top_draw_body(const RcwDev& p, const uint8_t* __
                 if (len == 0) { A0 = dummy_A; smaj = sboth = 0; slope = 0u; }
             }
             const int ke = ks + len;
-            int k0 = len > 1 ? ks + (int)((((unsigned)(tid * 37) & 63u) * (unsigned)len) >> 6) : ks;   // neighbouring lanes start 37/64 of a segment apart
-#ifdef RCW_DEV_SWITCHES
-#include "dev/top_draw_banks_start.inc"   // RCW_TOP_DRAW=banks, every lane starts its walk on its own LDS bank (measured, rejected)
-#endif
+            const int k0 = len > 1 ? ks + (int)((((unsigned)(tid * 37) & 63u) * (unsigned)len) >> 6) : ks;   // neighbouring lanes start 37/64 of a segment apart
             const unsigned long long at_ks = (unsigned long long)(unsigned)ks * slope + frac0;     // v_mad_u64_u32
             const unsigned long long at_k0 = (unsigned long long)(unsigned)k0 * slope + frac0;
             const uint32_t frac_s = (uint32_t)at_ks;
@@ -952,9 +900,6 @@ __device__ __forceinline__ void top_draw_body(const RcwDev& p, const uint8_t* __
 #endif
             uint32_t t_, m_, d_;
             // four steps a trip (up to three more than the longest segment needs: lanes go round their own segments, harmless)
-#ifdef RCW_DEV_SWITCHES
-#include "dev/top_draw_probe_loops.inc"   // RCW_TOP_DRAW=halfds / nods, the walk loops of the two timing probes
-#endif
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
             for (int trips = (nmax + 3) >> 2; trips > 0; --trips) {
                 RCW_DRAW_STEP(A, frac, rem, slope, smaj, sboth, t_, m_, d_, len_m1, frac_s, A_s);
@@ -969,7 +914,7 @@ __device__ __forceinline__ void top_draw_body(const RcwDev& p, const uint8_t* __
     // lgkmcnt(0) a wavefront could pass the barrier with plane ORs still in flight while others read b.line[] below)
     lds_barrier();
     RCW_DRAW_STAMP(4);
-    if (tid == 0 && part == 0) RCW_PLANE_STORE(reinterpret_cast<uint2*>(p.top_hdr + a), make_uint2((uint32_t)ip, (uint32_t)jp));
+    if (tid == 0 && part == 0) *reinterpret_cast<uint2*>(p.top_hdr + a) = make_uint2((uint32_t)ip, (uint32_t)jp);
     if (p.top_flat) {
         // rcw_top_store_flat_kernel's plane: the bit of agent pixel q = (j-1)·Ht + (i-1) sits at bit s + q of the agent's
         // region of p.top_plane_words words, s = (a · Ht·Wt) mod 256 — where the agent's image starts inside its first
@@ -1002,14 +947,11 @@ __device__ __forceinline__ void top_draw_body(const RcwDev& p, const uint8_t* __
                 }
                 word = bits << lead;
             }
-            RCW_PLANE_STORE(out + w, word);
+            out[w] = word;
         }
 #ifdef RCW_TRACE_WAVES
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         RCW_DRAW_STAMP(5);
-#endif
-#ifdef RCW_DEV_SWITCHES
-    if (p.top_signal) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); if (tid == 0) top_publish(p, a); }   // (the write-through stores above: written by name, awaited by name)
 #endif
         return;
     }
@@ -1043,7 +985,7 @@ __device__ __forceinline__ void top_draw_body(const RcwDev& p, const uint8_t* __
     } else
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
     for (int idx = tid; idx < total; idx += group) {
-        RCW_PLANE_STORE(out + idx, b.line[j * wpc + w]);
+        out[idx] = b.line[j * wpc + w];
         j += qstep; w += rstep;
         if (w >= wpu) { w -= wpu; j += 1; }
     }
@@ -1055,14 +997,11 @@ __device__ __forceinline__ void top_draw_body(const RcwDev& p, const uint8_t* __
             const uint32_t code = (tiles[t] & 1u) ? 1u : (tiles[t] & 2u);          // wall (white) before goal (red)  SR:355-360
             if (t < 16) lo |= code << (2 * t); else hi |= code << (2 * (t - 16));
         }
-        RCW_PLANE_STORE(p.top_codes + ((size_t)a * p.W + tj) * k + rb, make_uint2(lo, hi));
+        *(p.top_codes + ((size_t)a * p.W + tj) * k + rb) = make_uint2(lo, hi);
     }
 #ifdef RCW_TRACE_WAVES
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     RCW_DRAW_STAMP(5);
-#endif
-#ifdef RCW_DEV_SWITCHES
-    if (p.top_signal) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); if (tid == 0) top_publish(p, a); }   // (the write-through stores above: written by name, awaited by name)
 #endif
 }
 
@@ -1070,9 +1009,6 @@ template <typename T, bool TIE_LE, bool DIST_PRE>
 __global__ __launch_bounds__(1024) void rcw_top_draw_kernel(const RcwDev p, const uint8_t* __restrict__ mask, int first)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-#ifdef RCW_DEV_SWITCHES
-    if (p.top_draw_r4) { top_draw_body_r4<T, TIE_LE, DIST_PRE>(p, mask, first + (int)blockIdx.x, lds); return; }
-#endif
     // p.top_parts workgroups an agent (1, or 2 .. 4 where a batch of big images leaves CUs without a workgroup, or one agent has a CU to
     // itself and the slowest agent is the kernel): workgroup q draws part q mod parts of agent q / parts — neighbours in the dispatch
     // order, i.e. on different XCDs
@@ -1095,9 +1031,6 @@ __global__ __launch_bounds__(kBlock) void rcw_fill256_draw_kernel(const RcwDev p
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     if ((int)blockIdx.x < fill_blocks) { fill256_body<false>(p, col_h, col_c, out, total_cols, mask, (int)blockIdx.x, fill_blocks); return; }
-#ifdef RCW_DEV_SWITCHES
-    if (p.top_draw_r4) { top_draw_body_r4<T, TIE_LE, DIST_PRE>(p, mask, first + (int)blockIdx.x - fill_blocks, lds); return; }
-#endif
     top_draw_body<T, TIE_LE, DIST_PRE>(p, mask, first + (int)blockIdx.x - fill_blocks, lds);
 }
 
@@ -1129,9 +1062,6 @@ int rcw_top_split_unit(const RcwDev& p)
     if (p.pu < 8 || 2 * p.top_rp > 31 || p.N > 4096) return 0;                                   // (the draw kernel ranks a line within its length class in 12 bits)
     int unit = 0;
     if (256 % p.pu == 0 && Ht % 256 == 0) unit = 256;
-#ifdef RCW_DEV_SWITCHES
-    else if (128 % p.pu == 0 && Ht % 128 == 0 && 128 / p.pu <= 14) unit = 128;   // (every such geometry takes the flat kernel: RCW_TOP_FLAT=0 only)
-#endif
     else if (64 % p.pu == 0 && Ht % 64 == 0) unit = 64;
     else if (32 % p.pu == 0 && Ht % 32 == 0) unit = 32;
     if (!unit) return 0;
@@ -1187,9 +1117,6 @@ hipError_t rcw_launch_fill256_draw(const RcwDev& p, const uint8_t* mask_dev, hip
                  (long long)p.B * p.N, mask_dev, p.fill_grid, 0);
     return hipGetLastError();
 }
-// The store kernel may FOLLOW the draw kernel (top_follow_wait) only where a draw workgroup still finds room on a CU whose store
-// workgroups — resident for the whole launch, and waiting — are already there (and, inside a step, the camera fill's): wavefronts
-// (32 a CU; 28 counted, what the draw kernel was seen to reach) and LDS (160 KiB).
 // draw workgroups that fit on a CU together (LDS, wavefronts): what one "round" of the draw kernel is
 int rcw_top_draw_per_cu(const RcwDev& p, int draw_block, int lds_per_cu, int waves)
 {
@@ -1198,18 +1125,6 @@ int rcw_top_draw_per_cu(const RcwDev& p, int draw_block, int lds_per_cu, int wav
     const int by_waves = waves / (draw_block / 64 > 0 ? draw_block / 64 : 1);
     if (n > by_waves) n = by_waves;
     return n < 1 ? 1 : n;
-}
-int rcw_top_follow_fits(const RcwDev& p, int draw_block, bool beside_fill, int cus)
-{
-    if (!p.top_split || cus <= 0) return 0;
-    const int store_wgs = (p.top_store_grid + cus - 1) / cus;               // per CU
-    size_t store_lds = (kBlock / 64) * 512 * 4;                              // rcw_top_store_kernel's plane words
-    if (p.top_flat) store_lds = top_store_flat_lds_bytes(p, p.top_flat);
-    else if (p.top_unit_px != 256) store_lds = (size_t)(kBlock / 64) * (512 + 3 * 64 * (256 / p.top_unit_px)) * 4;
-    const int fill_wgs = beside_fill ? (p.fill_grid + cus - 1) / cus : 0;
-    const int waves = draw_block / 64 + (store_wgs + fill_wgs) * (kBlock / 64);
-    const size_t lds = 4 * top_draw_lds_words(p) + store_wgs * (store_lds + 512) + fill_wgs * (size_t)(8 * 1024);
-    return waves <= 28 && lds <= 156 * 1024 ? 1 : 0;
 }
 // Above 64 KiB of dynamic LDS a kernel has to be told so once (the CU has 160 KiB).  The attribute belongs to the
 // FUNCTION, i.e. to every handle on the device: it is set once per device, to the fixed cap the geometry selection

@@ -107,10 +107,6 @@ __device__ __forceinline__ u32x4 top_chunk_pixels(const TopLane& L, uint32_t wor
     return o;
 }
 
-#ifdef RCW_DEV_SWITCHES
-#include "dev/top_follow_wait.inc"   // RCW_TOP_FOLLOW, the store kernels wait for the draw kernel agent by agent (measured, rejected)
-#endif
-
 // A group = the next 64 chunks of a wavefront; lane l holds the descriptor of the l-th.
 struct TopGroup {
     int flags, r0, woff;         // bit 0 valid, bit 1 frame column | chunk row of the circle mask's bit 0 | plane word offset
@@ -194,15 +190,9 @@ __global__ __launch_bounds__(kBlock) void rcw_top_store_kernel(const RcwDev p, c
     uint32_t* const lw_write = plane_words + (threadIdx.x >> 6) * 512 + lane;
     const uint32_t* const lw_read = plane_words + (threadIdx.x >> 6) * 512 + (lane >> 3);
     uint32_t base = chunk_begin + g;
-    [[maybe_unused]] uint32_t have = 0u;                                     // (development experiment RCW_TOP_FOLLOW: blocks of agents known to be drawn)
+    [[maybe_unused]] uint32_t have = 0u;                                     // (unused: what is left of a retired experiment; removing it renames registers in the flat kernel, see profiles/retire_variants_isa.txt)
     for (; base < total; base += G * 64) {
         TopGroup cur;
-#ifdef RCW_DEV_SWITCHES
-        if (p.top_follow) {                                                  // the agent of the group's last chunk
-            const uint32_t id_last = min(base + 63u * G, total - 1u);
-            top_follow_wait(p, id_last / (((uint32_t)(p.H * p.pu) >> 8) * (uint32_t)(p.W * p.pu)), have);
-        }
-#endif
         top_group_issue(p, mask, base, G, total, lane, cur);
         top_group_finish(p, L, cur);
         // the plane words go through a wave-private 2 KiB of LDS (index 8 t + word: lane l's register m is entry
@@ -231,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void rcw_top_store_kernel(const RcwDev p, c
 }
 
 // The same sweep for image heights that are a multiple of 128, 64 or 32 rows but not of 256 (and tiles that divide that
-// number): a 1 KiB chunk then holds U = 2, 4 or 8 UNITS — runs of 128 / 64 / 32 rows of one image column — which may
+// number; 128-row units, U = 2, are not instantiated: the flat kernel takes every such geometry): a 1 KiB chunk then holds U = 2, 4 or 8 UNITS — runs of 128 / 64 / 32 rows of one image column — which may
 // belong to different columns, so the descriptor is per unit: lane l of the prefetch computes the U descriptors of its
 // chunk and parks them, like the plane words, in wave-private LDS; in the chunk loop a lane reads its unit's
 // (lane / (64 / U)) back with one ds_read (broadcast with v_readlane and picked with selects instead: the same at
@@ -267,15 +257,8 @@ __global__ __launch_bounds__(kBlock) void rcw_top_store_units_kernel(const RcwDe
     uint32_t* const desc = ws + 512;                                         // [64 chunks][U]
     uint32_t* const circ = desc + 64 * U;
     uint32_t* const crow = circ + 64 * U;
-    [[maybe_unused]] uint32_t have = 0u;                                     // (development experiment RCW_TOP_FOLLOW: blocks of agents known to be drawn)
+    [[maybe_unused]] uint32_t have = 0u;                                     // (unused: what is left of a retired experiment; removing it renames registers in the flat kernel, see profiles/retire_variants_isa.txt)
     for (uint32_t base = chunk_begin + g; base < total; base += G * 64) {
-#ifdef RCW_DEV_SWITCHES
-        if (p.top_follow) {                                                  // the agent of the last unit of the group's last chunk
-            const uint32_t id_last = min(base + 63u * G, total - 1u);
-            const uint32_t un_last = min(id_last * U + (U - 1), total_units - 1u);
-            top_follow_wait(p, un_last / (k * (uint32_t)Wt), have);
-        }
-#endif
         const uint32_t id = base + (uint32_t)lane * G;
         uint32_t packed[U], cmask[U];
         int r0[U];
@@ -557,14 +540,10 @@ __global__ __launch_bounds__(kBlock) void rcw_top_store_flat_kernel(const RcwDev
     uint32_t a_cur = col / (unsigned)Wt, j_cur = col - a_cur * (unsigned)Wt;      // (agent, image column) of this lane's next chunk
     const uint32_t dqa = dq / (unsigned)Wt, dqj = dq - dqa * (unsigned)Wt;        // ... move by this much a group (+ 1 column on a row wrap)
     const uint32_t dqa_w = dq_w / (unsigned)Wt, dqj_w = dq_w - dqa_w * (unsigned)Wt;
-    [[maybe_unused]] uint32_t have = 0u;                                     // (development experiment RCW_TOP_FOLLOW: blocks of agents known to be drawn)
+    [[maybe_unused]] uint32_t have = 0u;                                     // (unused: what is left of a retired experiment; removing it renames registers in the flat kernel, see profiles/retire_variants_isa.txt)
     auto issue = [&](uint32_t base, TopFlatPre<K>& P) {
         const uint32_t id = base + (uint32_t)lane * G;
         const bool exists = id < chunk_end;
-#ifdef RCW_DEV_SWITCHES
-        if (p.top_follow)                                                    // the last agent any of the group's chunks touches (the assignment turns: no lane order)
-            top_follow_wait(p, (uint32_t)__builtin_amdgcn_readlane(wave_max_in_lane63(exists ? (int)min(a_cur + 1u, last_agent) : 0), 63), have);
-#endif
         P.rem = rem; P.a0 = a_cur; P.j0 = j_cur;
         int touched = 0;
 #pragma unroll
@@ -783,21 +762,15 @@ hipError_t rcw_launch_top_store(const RcwDev& p, const uint8_t* mask_dev, int fi
     }
     const uint32_t per_agent = (uint32_t)(((long long)p.H * p.pu * p.W * p.pu) >> 8);
     const uint32_t c0 = (uint32_t)first * per_agent, c1 = (uint32_t)(first + count) * per_agent;
-    // (plain instead of non-temporal stores — p.top_store_plain — and units of 128 rows, which the flat kernel has taken over, are
-    // choices of the development build only: the shipped library carries no instantiation it cannot reach)
+    // (plain instead of non-temporal stores — p.top_store_plain — is a choice of the development build only: the shipped library
+    // carries no instantiation it cannot reach)
 #ifdef RCW_DEV_SWITCHES
 #define RCW_STORE(KERNEL, ...) do { if (p.top_store_plain) hipLaunchKernelGGL((KERNEL<true, __VA_ARGS__>), grid, block, 0, s, p, mask_dev, c0, c1); \
                                     else hipLaunchKernelGGL((KERNEL<false, __VA_ARGS__>), grid, block, 0, s, p, mask_dev, c0, c1); } while (0)
 #else
 #define RCW_STORE(KERNEL, ...) hipLaunchKernelGGL((KERNEL<false, __VA_ARGS__>), grid, block, 0, s, p, mask_dev, c0, c1)
 #endif
-    if (p.top_unit_px == 128) {
-#ifdef RCW_DEV_SWITCHES
-        RCW_STORE(rcw_top_store_units_kernel, 2);
-#else
-        return hipErrorInvalidValue;
-#endif
-    }
+    if (p.top_unit_px == 128) return hipErrorInvalidValue;                  // (every such geometry takes the flat kernel: rcw_top_split_unit never answers 128)
     else if (p.top_unit_px == 64) RCW_STORE(rcw_top_store_units_kernel, 4);
     else if (p.top_unit_px == 32) RCW_STORE(rcw_top_store_units_kernel, 8);
     else if (p.pu < 16) RCW_STORE(rcw_top_store_kernel, true);               // 32 tiles in a chunk

@@ -371,7 +371,7 @@ class SingleRoom:
         self.T = np.float64 if str(T) in f64_names else np.float32
         self.R, reward_type = r_names[str(R)]
         # `library`: None = the shipped librcw_hip.so; "dev" (or a path) = the development build, which also reads the
-        # RCW_* tuning knobs and carries the measured-and-rejected kernel variants (csrc/Makefile `dev`)
+        # RCW_* tuning knobs (overrides of what the rules compute; the kernels are the shipped ones: csrc/Makefile `dev`)
         self._lib = _capi.load(library)
         cfg = _capi.RcwConfig()
         _capi.check(self._lib.rcw_config_default(C.byref(cfg)), self._lib)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Test infrastructure (GPU box, from the repository root: tests/kernel_census.sh; tools/gpu_round.sh runs it at the end of a round).
+# Test infrastructure (GPU box, from the repository root: tests/kernel_census.sh, at the end of a round).
 # Which kernel instantiations of the shipped library does the GPU suite launch?  rocprofv3 --kernel-trace over the in-process GPU test
 # files and the fuzzers (each program directly after `--`; the tests that start child processes are left out: rank scripts, bench.py,
 # the examples and the plain-C harness use the same kernels), kernel names against the .amdhsa_kernel list of `make asm`

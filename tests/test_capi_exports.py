@@ -78,27 +78,33 @@ def test_product_never_imports_the_oracle():
 
 def test_shipped_library_reads_no_development_switch(rcw):
     """The shipped librcw_hip.so names exactly one environment variable, RCW_RCCL_LIBRARY (where to find RCCL): the
-    tuning knobs and measured-and-rejected kernel variants of development live in librcw_hip_dev.so only, so a stray
-    RCW_* variable in a user's shell cannot change results or performance."""
+    tuning knobs of development live in librcw_hip_dev.so only, so a stray RCW_* variable in a user's shell cannot change
+    results or performance.  Neither library carries a measured-and-rejected kernel variant or a switch that selected one
+    (docs/experiments.md keeps their numbers, the history their source)."""
     from raycastworlds_jl_amd import _capi
 
     def env_names(path):
         data = open(path, "rb").read()
         return sorted(set(m.decode() for m in re.findall(rb"(?<![A-Z_0-9])RCW_[A-Z0-9_]{3,}(?=\x00)", data)))
 
+    retired_switches = {"RCW_CAST_KERNEL", "RCW_CAST_MARCH", "RCW_CAST_TABLE", "RCW_CAST_WAVES", "RCW_STEP_FUSED", "RCW_STEP_PIECES",
+                        "RCW_FILL_TRIPS", "RCW_FILL_FLAT_PAIRS", "RCW_TOP_DRAW", "RCW_TOP_FOLLOW", "RCW_TOP_DEBUG", "RCW_SPEC_DEBUG"}
+    retired_kernels = (b"rcw_cast_kernel_r3", b"rcw_step256_kernel", b"rcw_cast_waves_kernel")
+
     assert env_names(_capi.LIB_PATH) == ["RCW_RCCL_LIBRARY"]
-    # ... nor does it carry the development-only kernels (the round-3 cast kernel and its variants, the wavefront-per-agent form)
     shipped = open(_capi.LIB_PATH, "rb").read()
-    assert b"rcw_cast_kernel_r3" not in shipped and b"rcw_cast_waves_kernel" not in shipped and b"rcw_step256_kernel" not in shipped
+    assert not [k for k in retired_kernels if k in shipped]
     assert b"rcw_cast_kernel" in shipped and b"rcw_fill256_draw_kernel" in shipped
     if os.path.exists(_capi.DEV_LIB_PATH):
         dev = env_names(_capi.DEV_LIB_PATH)
-        assert "RCW_CAST_MARCH" in dev and "RCW_TOP_DEBUG" in dev and "RCW_RCCL_LIBRARY" in dev
-        assert "RCW_CAST_KERNEL" in dev and "RCW_TOP_FUSED" in dev and "RCW_STEP_FUSED" in dev
-        assert b"rcw_cast_kernel_r3" in open(_capi.DEV_LIB_PATH, "rb").read() and b"rcw_step256_kernel" in open(_capi.DEV_LIB_PATH, "rb").read()
-        # the development build exports the same ABI
+        assert "RCW_TOP_PARTS" in dev and "RCW_TOP_DRAW_FIRST" in dev and "RCW_RCCL_LIBRARY" in dev
+        assert not retired_switches & set(dev)
+        dev_bytes = open(_capi.DEV_LIB_PATH, "rb").read()
+        assert not [k for k in retired_kernels if k in dev_bytes]
+        # the development build exports the same ABI, and the rules without a device (tests/test_top_view_plan.py)
         lib = C.CDLL(_capi.DEV_LIB_PATH)
         assert not [n for n in _declared() if not hasattr(lib, n)]
+        assert hasattr(lib, "rcw_dev_plan_top_view")
 
 
 def test_every_entry_point_refuses_a_null_handle(rcw):

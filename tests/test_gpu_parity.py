@@ -1316,60 +1316,6 @@ def test_several_draw_workgroups_an_agent(rcw, oracle, monkeypatch, parts):
         env.close()
 
 
-def test_ballot_bounded_march_gives_the_same_rays(rcw, oracle, monkeypatch):
-    """The ballot-bounded march (the form north_star words; development switch RCW_CAST_MARCH=ballot of the development
-    build librcw_hip_dev.so, measured against the shipped exec-masked march in profiles/) is the same function: bit-exact
-    at the deep-march config and under every unpinned switch."""
-    monkeypatch.setenv("RCW_CAST_MARCH", "ballot")
-    rng = np.random.default_rng(12)
-    env, orc = _make(rcw, oracle, 16, seed=9, library="dev", **CFG5)
-    _rollout(rcw, env, orc, 30, rng, check_every=10, rays_every=10)
-    env.close()
-    for tie in (0, 1):
-        for dist in (0, 1):
-            env, orc = _make(rcw, oracle, 16, seed=5, dda_tie_break=tie, dda_distance=dist, library="dev", **CFG1)
-            _rollout(rcw, env, orc, 30, rng, check_every=10, rays_every=10)
-            env.close()
-    env, orc = _make(rcw, oracle, 8, seed=3, T="Float64", library="dev", **CFG2)
-    _rollout(rcw, env, orc, 20, rng, check_every=10, rays_every=10)
-    env.close()
-
-
-def test_lds_staged_ray_table_gives_the_same_rays(rcw, oracle, monkeypatch):
-    """Development switch RCW_CAST_TABLE=lds of the development build (the heading's ray-table slice copied to LDS before
-    use, as north_star words it; measured against the shipped direct L2 read in profiles/): same results."""
-    monkeypatch.setenv("RCW_CAST_TABLE", "lds")
-    rng = np.random.default_rng(14)
-    for kw in (CFG2, CFG5, dict(T="Float64", **CFG1), dict(num_rays=100, height_tile_map_tu=9, width_tile_map_tu=7)):
-        env, orc = _make(rcw, oracle, 12, seed=4, auto_reset=True, library="dev", **kw)
-        _rollout(rcw, env, orc, 25, rng, check_every=5, rays_every=5)
-        env.close()
-
-
-@pytest.mark.parametrize("form", ["1", "2"])
-def test_whole_step_in_one_launch_gives_the_same_frames(rcw, oracle, monkeypatch, form):
-    """Development switch RCW_STEP_FUSED of the development build (measured and rejected, docs/experiments.md): cast and camera fill
-    in ONE launch, the column descriptors handed from the casting wavefronts to the fill workgroups inside it — through a
-    per-agent flag (1) or through words that carry the step's epoch (2).  Same frames, same state, with masked resets and
-    auto-reset; also in Float64 and with a batch that is not a multiple of a workgroup's four agents."""
-    monkeypatch.setenv("RCW_STEP_FUSED", form)
-    rng = np.random.default_rng(21)
-    for batch, kw in ((203, dict(num_rays=100, height_tile_map_tu=9, width_tile_map_tu=7)), (64, dict(T="Float64", **CFG1)),
-                      (1030, dict(num_rays=256, height_tile_map_tu=8, width_tile_map_tu=8))):
-        env, orc = _make(rcw, oracle, batch, seed=6, auto_reset=True, out_of_bounds=1, library="dev", **kw)
-        assert env.fill_kernel_name() == "rcw_step256_kernel"
-        for s in range(12):
-            if s % 5 == 2:
-                mask = (rng.random(batch) < 0.4).astype(np.uint8)
-                rcw.reset_(env, mask=mask, seed=40 + s); orc.reset(mask=mask, seed=40 + s)
-            a = rng.integers(1, 5, batch).astype(np.uint8)
-            rcw.act_(env, a)
-            assert orc.step(a) == 0
-            if s % 4 == 3 or s == 11:
-                assert_state_equal(env, orc, frames=True, where=f"fused form {form}, {kw}, step {s}")
-        env.close()
-
-
 def test_create_destroy_cycles_leave_device_memory_unchanged(rcw):
     """Handles with every optional buffer (top view, Float64 tables, typed rewards, rays scratch, a bound observation
     buffer, the gather scratch is covered by the RCCL test) are created, used and destroyed 25 times: free device

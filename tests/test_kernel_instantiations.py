@@ -3,7 +3,7 @@
 The library picks a template instantiation from the geometry (camera height -> rcw_fill_flat_kernel<ALIGNED, K>; top-view image
 height and pixel scale -> rcw_top_store_flat_kernel<STRADDLE, NARROW, K>; world-unit type and the two unpinned cast_ray switches ->
 <T, TIE, DIST> of the casting / drawing kernels).  The rules are restated here, the case lists below are checked against the
-kernels of the shipped build's ISA (CPU), and each case runs against the oracle (GPU).  tools/gpu_round.sh then counts, under
+kernels of the shipped build's ISA (CPU), and each case runs against the oracle (GPU).  tests/kernel_census.sh then counts, under
 rocprofv3, which instantiations the suite really launched (profiles/r04_kernel_census.txt)."""
 import os
 import re
@@ -28,7 +28,7 @@ def _b(x):
 
 
 def fill_flat_label(hc):
-    return f"rcw_fill_flat_kernel<{_b(hc % 4 == 0)}, {254 // hc + 2}, false>"      # (the third parameter: two wavefronts to a slot — the development build's only)
+    return f"rcw_fill_flat_kernel<{_b(hc % 4 == 0)}, {254 // hc + 2}, false>"      # (the third parameter: two wavefronts to a slot — a retired experiment's, never true)
 
 
 def top_flat_label(H, W, pu):
@@ -59,7 +59,7 @@ def test_the_case_lists_cover_every_shipped_instantiation_of_the_flat_kernels():
     assert fill == {fill_flat_label(hc) for hc in FILL_HEIGHTS}, fill ^ {fill_flat_label(hc) for hc in FILL_HEIGHTS}
     assert top == {top_flat_label(*g) for g in TOP_FLAT}, top ^ {top_flat_label(*g) for g in TOP_FLAT}
     assert len(FILL_HEIGHTS) == len(fill) and len(TOP_FLAT) == len(top)
-    # no plain-store variant, no 128-row units kernel: the development build's only
+    # no plain-store variant (the development build's only), no 128-row units kernel (the flat kernel takes every such geometry)
     assert not [n for n in names if re.match(r"rcw_(fill256|top_store|top_store_units)_kernel<true", n)], names
     assert "rcw_top_store_units_kernel<false, 2>" not in names
     assert not [n for n in names if re.match(r"rcw_fill_flat_kernel<\w+, \d+, true>", n)], names

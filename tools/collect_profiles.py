@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""After `gpurun -- tools/gpu_round.sh <tag>`: copy the judged summaries from gpurun_out/ into profiles/.
+"""After a round's closing GPU call (tools/experiments.md, "the rounds' closing calls": the commands and the names of what
+they leave in the tools' output directory): copy the judged summaries from there into profiles/.
 
     python tools/collect_profiles.py r02
 """
@@ -88,32 +89,6 @@ if os.path.exists(f"gpurun_out/{tag}_top_kernel_stats.csv"):
         + side + ring + "\n" + tw + fr + "\n" + sq)
     if bench_top:
         shutil.copy(f"gpurun_out/{tag}_top_bench.json", f"profiles/{tag}_bench_reference_default_act.json")
-# ---- cast kernel at cfg-5: exec-masked march (shipped) vs ballot-bounded march (RCW_CAST_MARCH=ballot)
-if os.path.exists(f"gpurun_out/{tag}_cfg5_exec_sq.txt"):
-    out = ["rcw_cast_kernel_r3 (the round-3 kernel, which carries both marches; development build, RCW_CAST_KERNEL=r3; the shipped round-4 kernel runs the\n"
-           "exec-masked march: profiles/r04_cast_kernel.txt) at cfg-5 (SingleRoom 32x32, 1024 columns, 8192 agents: rays up to 60 tile steps), 1 MI355X\n"
-           "exec-masked march (shipped: per-lane `break`, the hardware exec mask retires finished lanes) vs ballot-bounded march\n"
-           "(RCW_CAST_MARCH=ballot: wave-uniform loop bound via __ballot, finished lanes carried through selects)\n"
-           "commands: rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --workload cfg5 --steps 30 --warmup 3\n"
-           "          rocprofv3 --pmc <SQ counters> --kernel-trace -- python3 bench.py --no-cpu-baseline --workload cfg5 --steps 10 --warmup 2\n"
-           "per dispatch, summed over the 8 XCDs; SQ_*_CYCLES count quad-cycles\n"]
-    for march in ("exec", "ballot"):
-        rows = list(csv.reader(open(f"gpurun_out/{tag}_cfg5_{march}_kernel_stats.csv")))
-        cast = [r for r in rows[1:] if "rcw_cast_kernel" in r[0]][0]
-        sq = open(f"gpurun_out/{tag}_cfg5_{march}_sq.txt").read()
-        v = {m.group(1): float(m.group(2)) for m in re.finditer(r"rcw_cast_kernel\w*\s+(\w+)\s+dispatches=.*?mean=\s*([\d.]+)", sq)}
-        lane = v.get("SQ_THREAD_CYCLES_VALU", 0) / max(v.get("SQ_ACTIVE_INST_VALU", 1) * 64, 1)
-        out.append(f"\n== {march}: kernel avg {float(cast[3]) / 1e3:.1f} us (min {float(cast[5]) / 1e3:.1f}, max {float(cast[6]) / 1e3:.1f}), "
-                   f"{v.get('SQ_INSTS_VALU', 0) / v.get('SQ_WAVES', 1):.0f} VALU instructions per wavefront, "
-                   f"waiting {v.get('SQ_WAIT_ANY', 0) / max(v.get('SQ_WAVE_CYCLES', 1), 1) * 100:.0f} % of wave cycles, "
-                   f"active lanes per VALU instruction {lane * 100:.1f} %\n" + sq)
-    open(f"profiles/{tag}_cast_march_cfg5.txt", "w").write("".join(out))
-if os.path.exists(f"gpurun_out/{tag}_cast_table.txt"):
-    open(f"profiles/{tag}_cast_table.txt", "w").write(
-        "rcw_cast_kernel_r3 (the round-3 kernel, development build, RCW_CAST_KERNEL=r3), the heading's ray-table slice (5 N values): read directly from the L2-resident table by the lane\n"
-        "that uses it (shipped, \"tablel2\") vs copied to LDS first and read back (RCW_CAST_TABLE=lds, \"tablelds\", the form\n"
-        "north_star words).  rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --workload <cfg> --steps 30 --warmup 3\n\n"
-        + open(f"gpurun_out/{tag}_cast_table.txt").read())
 if os.path.exists("gpurun_out/rccl_world1.json"):
     shutil.copy("gpurun_out/rccl_world1.json", f"profiles/{tag}_rccl_world1.json")
 b = json.load(open(f"profiles/{tag}_bench.json"))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Assemble profiles/<tag>_top_view_shapes.txt from what tools/gpu_round.sh left under gpurun_out/ (<tag>_top_shapes_kernels.txt:
+"""Assemble profiles/<tag>_top_view_shapes.txt from what a round's closing call (tools/experiments.md) left in the tools' output directory (<tag>_top_shapes_kernels.txt:
 rocprofv3 kernel averages per shape; <tag>_top_shapes_steps.txt: the HIP-event lines of tools/top_view_shapes.py).
 usage: python tools/top_shapes_profile.py r03"""
 import re
