@@ -9,7 +9,7 @@ __attribute__((visibility("default"))) int rcw_dev_plan_top_view(const rcw_confi
                                                                 int32_t want_form, int32_t want_runs, int32_t* out)
 {
     if (!cfg || !out || batch < 1 || cus < 1) return RCW_ERR_INVALID_ARGUMENT;
-    RcwDev d{};
+    RcwPlan d{};
     set_geometry(d, cfg, batch);
     d.fill_grid = cus;
     d.top_view = cfg->render_top_view ? reinterpret_cast<uint32_t*>(16) : nullptr;      // (a marker: the rule only asks whether the handle renders one)
@@ -39,7 +39,7 @@ __attribute__((visibility("default"))) int rcw_dev_top_view_rules(char* buf, int
 __attribute__((visibility("default"))) int rcw_dev_step_rule(const rcw_config* cfg, int32_t batch, int32_t cus)
 {
     if (!cfg || batch < 1 || cus < 1) return RCW_ERR_INVALID_ARGUMENT;
-    RcwDev d{};
+    RcwPlan d{};
     set_geometry(d, cfg, batch);
     d.fill_grid = cus;
     d.top_view = cfg->render_top_view ? reinterpret_cast<uint32_t*>(16) : nullptr;

@@ -75,7 +75,7 @@ struct rcw_handle {
     rcw_config cfg{};
     int32_t B = 0, device = 0, nchunks = 0;
     RcwHw hw{256, 160 * 1024, 32};     // the device's CUs, LDS bytes and wavefront slots a CU (hipDeviceProp_t: rcw_create)
-    RcwDev dev{};
+    RcwPlan dev{};
     RcwStream own_stream, top_stream;  // (top_stream: the side stream of the two-kernel top view)
     hipStream_t stream = nullptr;      // the caller's (rcw_set_stream) or own_stream: not owned
     RcwEvent ev_start, ev_stop;
@@ -154,7 +154,7 @@ hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool 
 template <typename Between>
 hipError_t launch_top_view(rcw_handle* h, const uint8_t* mask_dev, bool beside, Between between, hipEvent_t fused_event = nullptr)   // between(stream): the caller's camera fill
 {
-    const RcwDev& d = h->dev;
+    const RcwPlan& d = h->dev;
     hipError_t e;
     if (!d.top_split || (!beside && !d.top_alone_split)) {   // (nothing to hide the draw kernel behind: the one-kernel form is the faster one)
         if ((e = rcw_launch_top_view(d, mask_dev, h->stream)) != hipSuccess) return e;
@@ -176,7 +176,7 @@ hipError_t launch_top_view(rcw_handle* h, const uint8_t* mask_dev, bool beside, 
 template <typename Between>
 hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool beside, Between between, hipEvent_t fused_event)
 {
-    const RcwDev& d = h->dev;
+    const RcwPlan& d = h->dev;
     hipError_t e;
     if (!beside) {                                           // stand-alone, two kernels back to back on the handle's stream
         if ((e = rcw_launch_top_draw(d, mask_dev, 0, d.B, h->stream, d.top_draw_block_alone)) != hipSuccess) return e;
@@ -246,7 +246,7 @@ void spec_forget(rcw_handle* h) { h->spec_primed = false; h->obs_current = false
 // duration from): start | after cast | after the top view (one-kernel form) or the fill (two-kernel form) | end.
 hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev)
 {
-    const RcwDev& d = h->dev;
+    const RcwPlan& d = h->dev;
     // Whatever fails below, and every form but the one-launch step and what primes it, leaves the fact cleared.
     const bool was_current = h->obs_current && h->spec_primed;
     obs_unknown(h);
@@ -447,7 +447,7 @@ int upload_tables(rcw_handle* h)
 
 // The geometry of a batch as the kernels' argument block holds it: what the launchers' and the top view's rules read (rcw_create; the
 // development build's rcw_dev_plan_top_view, which runs the rule without a device).
-void set_geometry(RcwDev& d, const rcw_config* cfg, int32_t batch)
+void set_geometry(RcwPlan& d, const rcw_config* cfg, int32_t batch)
 {
     d.B = batch; d.H = cfg->height_tile_map_tu; d.W = cfg->width_tile_map_tu; d.N = cfg->num_rays; d.nd = cfg->num_directions; d.Hc = cfg->height_camera_view_pu;
     d.real64 = cfg->world_unit_bits == 64 ? 1 : 0;
@@ -501,10 +501,10 @@ constexpr TopRule kTopRules[kTopRuleCount] = {
 };
 constexpr double top_rule(TopRuleId id) { return kTopRules[id].value; }
 
-// what the rule decides (fields of RcwDev), from the configuration, the batch, the device's numbers and the caller's wishes; no HIP call.
+// what the rule decides (fields of RcwPlan), from the configuration, the batch, the device's numbers and the caller's wishes; no HIP call.
 // want_form: 0 = the rule, or one of RCW_TOP_VIEW_IN_PLACE / ONE_KERNEL / TWO_KERNELS (rcw_set_top_view_form); want_runs: 0 = the rule, or 1..8.
 // `lenient`: a form the geometry cannot take falls back to the rule (development switches) instead of failing.
-int top_view_rule(RcwDev& d, const rcw_config* cfg, size_t B, const RcwHw& hw, int want_form, int want_runs, bool lenient)
+int top_view_rule(RcwPlan& d, const rcw_config* cfg, size_t B, const RcwHw& hw, int want_form, int want_runs, bool lenient)
 {
     const int H = cfg->height_tile_map_tu, W = cfg->width_tile_map_tu, N = cfg->num_rays, Hc = cfg->height_camera_view_pu;
     d.top_lds = 0; d.top_split = 0; d.top_flat = 0; d.top_plane_words = 0; d.top_unit_px = 256; d.top_runs = 1;
@@ -620,7 +620,7 @@ int top_view_rule(RcwDev& d, const rcw_config* cfg, size_t B, const RcwHw& hw, i
 // Which form update_top_view! (SR:446-483) takes for this handle (top_view_rule), and its scratch in HBM.
 int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient)
 {
-    RcwDev& d = h->dev;
+    RcwPlan& d = h->dev;
     const size_t B = (size_t)h->B;
     RCW_HIP(replace_buffers(h, {&h->d_top_plane, &h->d_top_hdr, &h->d_top_codes}));
     d.top_plane = nullptr; d.top_hdr = nullptr; d.top_codes = nullptr;
@@ -669,7 +669,7 @@ bool step_one_launch_pays(const RcwDev& d)
 // form is taken; the caller primes them (launch_step without an action).
 int plan_step_form(rcw_handle* h, int want)
 {
-    RcwDev& d = h->dev;
+    RcwPlan& d = h->dev;
     const bool eligible = rcw_step_spec_eligible(d) != 0;
     if (h->learner.only()) {                           // (the cast kernel followed by the view kernel: no camera fill to fuse)
         if (want == RCW_STEP_ONE_LAUNCH) return fail(RCW_ERR_UNSUPPORTED, "the handle's learner view is set with RCW_VIEW_ONLY: a step is the cast kernel and the view kernel");
@@ -992,7 +992,7 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     RCW_HIP(hipMemsetAsync(h->d_err.get(), 0, sizeof(int32_t), h->stream));
     RCW_HIP(hipMemsetAsync(h->d_status.get(), 0, B * sizeof(int32_t), h->stream));
 
-    RcwDev& d = h->dev;
+    RcwPlan& d = h->dev;
     set_geometry(d, cfg, batch);
     d.nwords = h->nchunks * 2;
     d.radius = cfg->player_radius_wu;
@@ -1789,7 +1789,7 @@ int rcw_profile_read(rcw_handle* h, float* cast_ms, float* top_view_ms, float* f
 int rcw_top_view_form(rcw_handle* h, int32_t* form)
 {
     if (!h || !form) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    const RcwDev& d = h->dev;
+    const RcwPlan& d = h->dev;
     *form = !d.top_view ? RCW_TOP_VIEW_NONE : d.top_split ? RCW_TOP_VIEW_TWO_KERNELS : d.top_lds ? RCW_TOP_VIEW_ONE_KERNEL : RCW_TOP_VIEW_IN_PLACE;
     return RCW_OK;
 }
@@ -1797,7 +1797,7 @@ int rcw_top_view_form(rcw_handle* h, int32_t* form)
 int rcw_update_top_view_form(rcw_handle* h, int32_t* form)
 {
     if (!h || !form) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    const RcwDev& d = h->dev;
+    const RcwPlan& d = h->dev;
     *form = !d.top_view ? RCW_TOP_VIEW_NONE : (d.top_split && d.top_alone_split) ? RCW_TOP_VIEW_TWO_KERNELS : d.top_lds ? RCW_TOP_VIEW_ONE_KERNEL : RCW_TOP_VIEW_IN_PLACE;
     return RCW_OK;
 }

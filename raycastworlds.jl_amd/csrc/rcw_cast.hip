@@ -40,10 +40,8 @@ namespace {
 // One view column: march, projection, descriptor.  Returns whether the ray left the map (the caller reports it once per lane:
 // a branch around two stores in every column costs the issue-bound kernel eight instructions a column).  The descriptor arrays
 // are addressed as uniform base (the agent's row) + 32-bit lane offset.
-// (PUBLISH / hc_a, here and in cast_body: what is left of a retired experiment, never set; they leave with RcwDev's dead members: rcw_kernels.h)
-template <typename T, bool TIE_LE, bool DIST_PRE, bool PUBLISH = false>
-__device__ __forceinline__ bool cast_column(const RcwDev& p, const uint8_t* tb, int32_t* col_h_a, uint8_t* col_c_a, int i, T x, T y, T dx, T dy, T ddx, T ddy, T dot,
-                                            uint32_t* hc_a = nullptr)
+template <typename T, bool TIE_LE, bool DIST_PRE>
+__device__ __forceinline__ bool cast_column(const RcwDev& p, const uint8_t* tb, int32_t* col_h_a, uint8_t* col_c_a, int i, T x, T y, T dx, T dy, T ddx, T ddy, T dot)
 {
     const RayHit<T> r = cast_ray_guarded<T, TIE_LE, DIST_PRE>(tb, p.H, p.W, x, y, dx, dy, ddx, ddy);
     const int hl = height_line_pu<T>(p, r.dist, dot);
@@ -199,7 +197,7 @@ __device__ __forceinline__ void agent_sync()
 // WAVE = false: the workgroup is one agent (tid = its thread, nthr = blockDim).  WAVE = true (the one-launch step at up to 256 view
 // columns): 64 lanes are an agent and the workgroup's wavefronts are DIFFERENT agents: the same code with
 // tid = the lane, nthr = 64, the wavefront's own slice of LDS, and no workgroup barrier.
-template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE, bool PUBLISH = false, bool SPEC = false>
+template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE, bool SPEC = false>
 __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask,
                                           const int a, const int tid, const int nthr, uint32_t* const lds, const int trace_slot,
                                           uint16_t* __restrict__ spec_out = nullptr, const int spec_cols = 1)
@@ -343,7 +341,6 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
 #endif
     int32_t* const col_h_a = p.col_h + (size_t)a * N;
     uint8_t* const col_c_a = p.col_c + (size_t)a * N;
-    uint32_t* const hc_a = PUBLISH ? p.step_hc + (size_t)a * N : nullptr;
     bool left_the_map = false;
     if (SPEC) {
         // The one-launch step (rcw_fill256_cast_kernel): besides the frame of the state just committed — descriptors as below, and the
@@ -415,7 +412,7 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
 #pragma unroll
     for (int k = 0; k < kCastCols; ++k) {
         const int i = tid + k * nthr;
-        if (i < N) left_the_map |= cast_column<T, TIE_LE, DIST_PRE, PUBLISH>(p, tb, col_h_a, col_c_a, i, x, y, r_dx[k], r_dy[k], r_ddx[k], r_ddy[k], r_dot[k], hc_a);
+        if (i < N) left_the_map |= cast_column<T, TIE_LE, DIST_PRE>(p, tb, col_h_a, col_c_a, i, x, y, r_dx[k], r_dy[k], r_ddx[k], r_ddy[k], r_dot[k]);
 #ifdef RCW_TRACE_WAVES
         if (k == 0) RCW_CAST_STAMP(5);
 #endif
@@ -434,7 +431,7 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
         const T* tab = Real<T>::ray_table(p) + (size_t)d_new * RCW_TABLE_ROWS * N;
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
         for (int i = tid + kCastCols * nthr; i < N; i += nthr)
-            left_the_map |= cast_column<T, TIE_LE, DIST_PRE, PUBLISH>(p, tb, col_h_a, col_c_a, i, x, y, tab[i], tab[N + i], tab[2 * N + i], tab[3 * N + i], tab[4 * N + i], hc_a);
+            left_the_map |= cast_column<T, TIE_LE, DIST_PRE>(p, tb, col_h_a, col_c_a, i, x, y, tab[i], tab[N + i], tab[2 * N + i], tab[3 * N + i], tab[4 * N + i]);
     }
     if (left_the_map) { p.err[0] = RCW_ERR_OUT_OF_BOUNDS; p.status[a] = RCW_ERR_OUT_OF_BOUNDS; }   // (Julia: BoundsError in cast_ray)
 }
@@ -582,9 +579,9 @@ __device__ __forceinline__ void cast_successors(const RcwDev& p, const uint8_t* 
         const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         const int a = block * (kBlock / 64) + wave;
         if (a >= p.B) return;                                               // (wave-uniform: the batch's last workgroup may be short)
-        cast_body<T, TIE_LE, DIST_PRE, true, false, true>(p, actions, mask, a, (int)(threadIdx.x & 63u), 64, lds + (size_t)wave * lds_words, a, slots_out, cols);
+        cast_body<T, TIE_LE, DIST_PRE, true, true>(p, actions, mask, a, (int)(threadIdx.x & 63u), 64, lds + (size_t)wave * lds_words, a, slots_out, cols);
     } else {
-        cast_body<T, TIE_LE, DIST_PRE, false, false, true>(p, actions, mask, block, (int)threadIdx.x, kBlock, lds, block, slots_out, cols);
+        cast_body<T, TIE_LE, DIST_PRE, false, true>(p, actions, mask, block, (int)threadIdx.x, kBlock, lds, block, slots_out, cols);
     }
 }
 
@@ -724,7 +721,7 @@ static size_t rcw_cast_lds_bytes(const RcwDev& p)
     return tiles + 32;
 }
 
-hipError_t rcw_launch_cast(const RcwDev& p, const uint8_t* actions_dev, const uint8_t* mask_dev,
+hipError_t rcw_launch_cast(const RcwPlan& p, const uint8_t* actions_dev, const uint8_t* mask_dev,
                            hipStream_t s, int first, int count)
 {
     if (count < 0) count = p.B - first;
@@ -737,7 +734,7 @@ hipError_t rcw_launch_cast(const RcwDev& p, const uint8_t* actions_dev, const ui
 // batch of fewer than 2^29 view columns and 2^31 chunks — the bytes of ONE
 // of its two slot buffers, and the launch: with_fill = the fill workgroups in front (a step); without, the casting workgroups alone
 // (they prime the slots behind a reset / set_state, or for a first step: the camera fill then follows as a launch of its own).
-int rcw_step_spec_eligible(const RcwDev& p)
+int rcw_step_spec_eligible(const RcwPlan& p)
 {
     const long long cols = (long long)p.B * p.N;
     if (p.top_view != nullptr || p.fill_plain || cols >= (1ll << 29) || p.Hc > 8191) return 0;                  // (the slot word holds a padding of 13 bits)
@@ -746,7 +743,7 @@ int rcw_step_spec_eligible(const RcwDev& p)
 }
 // ([B][5][N] words, then one byte per agent: which of its slots hold the frame slot 0 holds)
 size_t rcw_step_spec_slot_bytes(const RcwDev& p) { return (size_t)5 * (size_t)p.B * (size_t)p.N * sizeof(uint16_t) + (((size_t)p.B + 15) & ~(size_t)15); }
-hipError_t rcw_launch_step_spec(const RcwDev& p, const uint8_t* actions_dev, const uint8_t* mask_dev, const uint16_t* slots_in,
+hipError_t rcw_launch_step_spec(const RcwPlan& p, const uint8_t* actions_dev, const uint8_t* mask_dev, const uint16_t* slots_in,
                                 uint16_t* slots_out, bool with_fill, bool cols, bool keep, hipStream_t s)
 {
     const int icols = cols ? 1 : 0;

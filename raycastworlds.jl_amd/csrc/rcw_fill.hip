@@ -208,10 +208,8 @@ __device__ __forceinline__ u32x4 flat_fill_pixels(int r, int Hc, uint4 d0, uint4
     return v;
 }
 
-// PAIR: what is left of a retired experiment (two wavefronts to a slot of the window, workgroups of eight: docs/experiments.md); no launch
-// sets it.  Taking the parameter out renames the kernel and waits with RcwDev's dead members for a measurement (rcw_kernels.h).
-template <bool ALIGNED, int K, bool PAIR = false>                       // K = the columns a chunk may touch (254 / H_cam + 2)
-__global__ __launch_bounds__(PAIR ? 2 * kBlock : kBlock) void rcw_fill_flat_kernel(const RcwDev p,
+template <bool ALIGNED, int K>                                         // K = the columns a chunk may touch (254 / H_cam + 2)
+__global__ __launch_bounds__(kBlock) void rcw_fill_flat_kernel(const RcwDev p,
                                                                const int32_t* __restrict__ col_h,
                                                                const uint8_t* __restrict__ col_c,
                                                                uint32_t* __restrict__ out, long long total_cols,
@@ -219,8 +217,6 @@ __global__ __launch_bounds__(PAIR ? 2 * kBlock : kBlock) void rcw_fill_flat_kern
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int lane = threadIdx.x & 63;
-    constexpr int STEP = PAIR ? 2 : 1;                                    // chunks of a group between two of this wavefront's
-    const int half = PAIR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;   // which of a slot's two wavefronts
     const uint32_t G = gridDim.x * (kBlock / 64);
     const uint32_t g = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 3u);
     uint32_t ceil_c = p.ceiling_color, floor_c = p.floor_color;
@@ -283,20 +279,20 @@ __global__ __launch_bounds__(PAIR ? 2 * kBlock : kBlock) void rcw_fill_flat_kern
             grp += 1;
         }
 #endif
-        u32x4* dst = out4 + base * 64 + (unsigned long long)half * dstep;    // wave-uniform
+        u32x4* dst = out4 + base * 64;                                        // wave-uniform
         if (__ballot(state_l == 3) == ~0ull) {
             // every chunk of the group is whole and unmasked: no branch in the loop, the next chunk's pair(s) on their way
             int rel, r, rel_n, r_n;
-            flat_locate(L, __builtin_amdgcn_readlane(rem_l, half), Hc, rel, r);
-            uint4 d0 = desc[half * KS + rel], d1 = ALIGNED ? d0 : desc[half * KS + rel + 1];
+            flat_locate(L, __builtin_amdgcn_readlane(rem_l, 0), Hc, rel, r);
+            uint4 d0 = desc[rel], d1 = ALIGNED ? d0 : desc[rel + 1];
             // (measured, µs per GiB: four-pixel groups inside one column 162 / 163 / 173 / 182 unrolled by 1 / 2 / 4 / 8 — unrolled, the
             // compiler bunches the stores of several chunks together, and the memory system takes evenly spaced stores best —;
             // groups that straddle columns, with their longer arithmetic, 182 / 177 / 171 / 171)
 #pragma unroll (ALIGNED ? 1 : 4)
-            for (int t = half; t < 64; t += STEP, dst += STEP * dstep) {
+            for (int t = 0; t < 64; ++t, dst += dstep) {
                 // (the last trip fetches a 65th chunk's pair: lane 0's row again, and whatever lies behind in LDS; unused)
-                flat_locate(L, __builtin_amdgcn_readlane(rem_l, t + STEP), Hc, rel_n, r_n);
-                const uint4 n0 = desc[(t + STEP) * KS + rel_n], n1 = ALIGNED ? n0 : desc[(t + STEP) * KS + rel_n + 1];
+                flat_locate(L, __builtin_amdgcn_readlane(rem_l, t + 1), Hc, rel_n, r_n);
+                const uint4 n0 = desc[(t + 1) * KS + rel_n], n1 = ALIGNED ? n0 : desc[(t + 1) * KS + rel_n + 1];
                 bool ok[4];
                 const u32x4 v = flat_fill_pixels<ALIGNED>(r, Hc, d0, d1, ceil_c, floor_c, ok);
                 __builtin_nontemporal_store(v, dst + lane);
@@ -310,22 +306,21 @@ __global__ __launch_bounds__(PAIR ? 2 * kBlock : kBlock) void rcw_fill_flat_kern
             const int n_fast = (int)__builtin_ctzll(~whole);                 // (not all ones here)
             if (n_fast >= 4) {
                 int rel, r, rel_n, r_n;
-                flat_locate(L, __builtin_amdgcn_readlane(rem_l, half), Hc, rel, r);
-                uint4 d0 = desc[half * KS + rel], d1 = ALIGNED ? d0 : desc[half * KS + rel + 1];
+                flat_locate(L, __builtin_amdgcn_readlane(rem_l, 0), Hc, rel, r);
+                uint4 d0 = desc[rel], d1 = ALIGNED ? d0 : desc[rel + 1];
 #pragma unroll 1
-                for (int t = half; t < n_fast; t += STEP, dst += STEP * dstep) {
-                    flat_locate(L, __builtin_amdgcn_readlane(rem_l, t + STEP), Hc, rel_n, r_n);
-                    const uint4 n0 = desc[(t + STEP) * KS + rel_n], n1 = ALIGNED ? n0 : desc[(t + STEP) * KS + rel_n + 1];
+                for (int t = 0; t < n_fast; ++t, dst += dstep) {
+                    flat_locate(L, __builtin_amdgcn_readlane(rem_l, t + 1), Hc, rel_n, r_n);
+                    const uint4 n0 = desc[(t + 1) * KS + rel_n], n1 = ALIGNED ? n0 : desc[(t + 1) * KS + rel_n + 1];
                     bool ok[4];
                     const u32x4 v = flat_fill_pixels<ALIGNED>(r, Hc, d0, d1, ceil_c, floor_c, ok);
                     __builtin_nontemporal_store(v, dst + lane);
                     d0 = n0; d1 = n1; r = r_n;
                 }
             }
-            int t_first = n_fast >= 4 ? n_fast : 0;
-            if (PAIR) { t_first += ((t_first ^ half) & 1); dst = out4 + base * 64 + (unsigned long long)t_first * dstep; }   // this wavefront's next chunk of the group
+            const int t_first = n_fast >= 4 ? n_fast : 0;
 #pragma unroll 2
-            for (int t = t_first; t < 64; t += STEP, dst += STEP * dstep) {
+            for (int t = t_first; t < 64; ++t, dst += dstep) {
                 const int s_state = __builtin_amdgcn_readlane(state_l, t);
                 if (!(s_state & 1)) continue;                                // wave-uniform: past the end
                 int rel, r;
@@ -453,7 +448,7 @@ int rcw_fill_flat_cols(const RcwDev& p)
 
 // which kernel fills the frames of this geometry
 enum FillKernel { kFill256, kFillWindow1, kFillWindow2, kFillWindow4, kFillFlat, kFillFrame, kFillAny };
-static FillKernel fill_choice(const RcwDev& p, long long total_cols)
+static FillKernel fill_choice(const RcwPlan& p, long long total_cols)
 {
     if (p.Hc == 256) return kFill256;
     if ((p.Hc & 255) == 0) return kFillWindow1;                             // a 1 KiB chunk is a row block of one column
@@ -462,7 +457,7 @@ static FillKernel fill_choice(const RcwDev& p, long long total_cols)
     if (p.N <= 8192 && (long long)p.N * p.Hc < (1ll << 25)) return kFillFrame;
     return kFillAny;
 }
-const char* rcw_fill_kernel_name(const RcwDev& p, long long total_cols)
+const char* rcw_fill_kernel_name(const RcwPlan& p, long long total_cols)
 {
     // a step that also renders the top view in the fused form: the camera fill of the whole batch and the drawing are ONE launch
     if (p.top_view && p.top_split && p.top_fused && total_cols == (long long)p.B * p.N) return "rcw_fill256_draw_kernel";
@@ -475,7 +470,7 @@ const char* rcw_fill_kernel_name(const RcwDev& p, long long total_cols)
     }
 }
 
-hipError_t rcw_launch_fill(const RcwDev& p, const int32_t* col_h, const uint8_t* col_c, uint32_t* frames,
+hipError_t rcw_launch_fill(const RcwPlan& p, const int32_t* col_h, const uint8_t* col_c, uint32_t* frames,
                            long long total_cols, const uint8_t* mask_dev, hipStream_t s)
 {
     const int grid = p.fill_grid;
@@ -527,9 +522,9 @@ hipError_t rcw_launch_fill(const RcwDev& p, const int32_t* col_h, const uint8_t*
 }
 
 // (for the other translation units: does this geometry take rcw_fill256_kernel's window?)
-int rcw_fill_takes_256(const RcwDev& p, long long total_cols) { return fill_choice(p, total_cols) == kFill256 ? 1 : 0; }
+int rcw_fill_takes_256(const RcwPlan& p, long long total_cols) { return fill_choice(p, total_cols) == kFill256 ? 1 : 0; }
 // ... or the window of rcw_fill_window_kernel<M>: 0 for the 256-row kernel, M = 1 / 2 / 4 for the window kernel's forms, -1 for the other fill kernels
-int rcw_fill_window_columns(const RcwDev& p, long long total_cols)
+int rcw_fill_window_columns(const RcwPlan& p, long long total_cols)
 {
     switch (fill_choice(p, total_cols)) {
     case kFill256: return 0;
@@ -540,7 +535,7 @@ int rcw_fill_window_columns(const RcwDev& p, long long total_cols)
     }
 }
 
-hipError_t rcw_launch_expand(const RcwDev& p, const int32_t* col_h, const uint8_t* col_c,
+hipError_t rcw_launch_expand(const RcwPlan& p, const int32_t* col_h, const uint8_t* col_c,
                              int32_t count, uint32_t* frames, hipStream_t s)
 {
     return rcw_launch_fill(p, col_h, col_c, frames, (long long)count * p.N, nullptr, s);

@@ -5,7 +5,7 @@ namespace {
 
 // rcw_fill256_kernel's body as a function — workgroup `block` of `blocks` — for rcw_fill256_draw_kernel, which runs it in the
 // first `blocks` workgroups of a larger launch (the kernel proper follows, with its body verbatim)
-template <bool PLAIN, int EXTRA = 0>
+template <bool PLAIN>
 __device__ __forceinline__ void fill256_body(const RcwDev& p, const int32_t* __restrict__ col_h, const uint8_t* __restrict__ col_c,
                                              u32x4* __restrict__ out, long long total_cols, const uint8_t* __restrict__ mask,
                                              int block, int blocks)

@@ -9,10 +9,8 @@
 // so lane i of the cast phase reads five coalesced floats (SR:214-221, SR:404).
 #define RCW_TABLE_ROWS 5
 
-// (The members marked "development only" below — cast_ballot ... fill_pairs, top_flags ... top_follow_ok, step_*, top_debug, spec_debug — are
-// what is left of retired experiments (docs/experiments.md): no build sets or reads them any more, but for the draw kernel's `!p.top_signal`
-// and cast_body's PUBLISH.  Taking them out moves every kernel's argument offsets, so it waits for a measurement against the parent on the
-// GPU: docs/review_ledger.md §19, profiles/retire_variants_isa.txt.)
+// The kernels' argument block, passed by value to every kernel: only what device code reads goes in here.  A choice the host makes
+// about a launch (a grid, a block size, which kernel) belongs to RcwPlan below, where no kernel can see it.
 struct RcwDev {
     // geometry / config (all wave-uniform, live in SGPRs)
     int32_t B, H, W, N, nd, Hc;
@@ -32,14 +30,6 @@ struct RcwDev {
     int32_t dist_pre;        // RCW_DDA_DIST_PRE_INCREMENT
     int32_t auto_reset;
     int32_t oob_empty;       // RCW_OOB_TREAT_EMPTY
-    int32_t fill_grid;       // workgroups of the fill kernel (the moving window = fill_grid KiB x 4)
-    int32_t fill_plain;      // 1: plain stores, 0: non-temporal
-    int32_t fill_flat;       // development only (RCW_FILL_FLAT): rcw_fill_flat_kernel also where rcw_fill_window_kernel<2 / 4> applies
-    int32_t cast_block;      // threads per agent in the cast kernel (multiple of 64, <= 256)
-    int32_t cast_ballot;     // development only (RCW_CAST_MARCH=ballot): the ballot-bounded march instead of the exec-masked one
-    int32_t cast_table_lds;  // development only (RCW_CAST_TABLE=lds): stage the heading's ray-table slice in LDS first
-    int32_t cast_waves;      // development only (RCW_CAST_WAVES=1): the cast kernel with a wavefront per agent, four agents a workgroup — measured, rejected
-    int32_t cast_r3;         // development only (RCW_CAST_KERNEL=r3): the round-3 cast kernel (five dependent round trips), for the comparison
     int64_t agent_id_offset;
     uint64_t seed;
     // state (SR:21-40), one entry per agent
@@ -64,45 +54,35 @@ struct RcwDev {
     int32_t pu;              // pu_per_tu
     int32_t top_rp;          // player_radius_pu = wu_to_pu(player_radius_wu, pu)  SR:469 (host-computed in T)
     int32_t top_lds;         // write-once LDS bit-plane kernel: the number of buffers in its ring (1..3); 0: in-place fallback
-    int32_t top_grid;        // workgroups of the (persistent) write-once top view kernel
-    int32_t top_unit_px;     // ... its store kernel's unit: 256 rows of an image column (a whole 1 KiB chunk), 128 or 64
-    int32_t top_split;       // 1: the two-kernel top view (draw kernel -> planes in HBM -> moving-window store kernel)
+    int32_t top_unit_px;     // the two-kernel top view's store kernel's unit: 256 rows of an image column (a whole 1 KiB chunk), 128 or 64
     int32_t top_flat;        // ... with rcw_top_store_flat_kernel (any pixel scale >= 9): the image columns a 256-pixel chunk may touch; 0: the unit kernels
     int32_t top_plane_words; // ... and the words of one agent's region of top_plane in that form
-    int32_t top_alone_split; // rcw_update_top_view alone (no camera fill beside it) also takes the two-kernel form, back to back
-    int32_t top_runs;        // the batch is drawn and stored in this many runs of agents (store of run r beside the drawing of run r + 1)
     int32_t top_parts;       // draw workgroups an agent (two-kernel form on the side-stream / stand-alone path with rcw_top_store_kernel): 1, or 2..4 for few big images
-    int32_t top_draw_first;  // (host) inside a step the drawing stays on the handle's stream and the camera fill goes to the side stream
-    int32_t top_fused;       // a step's camera fill and top-view drawing go in ONE launch (rcw_fill256_draw_kernel) instead of two streams
-    int32_t top_draw_block;  // threads of a draw-kernel workgroup: 256; a lane per ray (up to 1024) when the plane leaves room for few workgroups on a CU
-    int32_t top_draw_block_alone;   // ... in rcw_update_top_view alone: 64 / 128 for batches of tens of thousands of small images
-    int32_t top_store_plain; // its store kernel: 1 plain stores, 0 non-temporal
-    int32_t top_store_grid;  // ... and its workgroups (the moving window = top_store_grid KiB x 4)
+    int32_t top_rotate;      // rcw_top_store_flat_kernel's wavefront -> chunk assignment turns by this many slots from group to group (33; development: RCW_TOP_ROTATE)
     uint32_t* top_plane;     // [B][W*pu][H*pu/32] ray-line bit plane of every agent (two-kernel top view)
     int2* top_hdr;           // [B] the player's pixel (ip, jp), 1-based  SR:468
     uint2* top_codes;        // [B][W][H*pu/256] 2-bit fill codes of a chunk's tiles
-    // the store kernel FOLLOWS the draw kernel (round 5): both run at once on two streams, ordered through memory instead of an event
-    uint32_t* top_flags;     // [blocks of 2^top_blk_shift agents] how many of the block's agents' planes, headers and codes were written, over all calls
-    int32_t top_blk_shift;
-    uint32_t top_epoch;      // this call's number among the calls that count: a complete block stands at top_epoch x its agents
-    int32_t top_signal;      // draw kernel: publish each agent as it is done
-    int32_t top_follow;      // store kernels: wait for the agents of a group of chunks before loading anything of theirs
-    int32_t top_follow_ok;   // (host) the geometry's draw and store workgroups fit on a CU together, in a step (bit 0) / alone (bit 1)
-    int32_t top_rotate;      // rcw_top_store_flat_kernel's wavefront -> chunk assignment turns by this many slots from group to group (33; development: RCW_TOP_ROTATE)
-    int32_t fill_trips;      // development only (RCW_FILL_TRIPS=0..3): rcw_fill256_kernel's body with that many more dependent round trips a prefetch; -1: the kernel proper
-    int32_t step_fused;      // development only (RCW_STEP_FUSED=1): cast and camera fill in ONE launch (rcw_step256_kernel), handed off through the two arrays below
-    uint32_t* step_flags;    // ... [B] the epoch of the last step whose descriptors of this agent are complete
-    uint32_t* step_hc;       // ... (N, B) the column's padding (SR:436, 0..256) | colour id << 9 | the step's epoch << 11 by image column
-    uint32_t step_epoch;     // ... this launch's epoch (the handle counts its fused steps)
-    int32_t top_debug;       // development only (RCW_TOP_DEBUG): bit 0 skip drawing, bit 1 skip storing — for timing the halves
-    int32_t top_draw_banks;  // development only (RCW_TOP_DRAW=banks): wavefronts of one kind of line (axis, direction), every lane starting on its own LDS bank
-    int32_t top_draw_r4;     // development only (RCW_TOP_DRAW=r4): the round-4 body of the draw kernel, for the comparison
-    int32_t fill_pairs;      // development only (RCW_FILL_FLAT_PAIRS=1): rcw_fill_flat_kernel with two wavefronts to a slot of the window
     int32_t* err;            // sticky error word of the handle (0 = ok); never blocks a step
     int32_t* status;         // per-agent sticky status
-#ifdef RCW_DEV_SWITCHES
-    int32_t spec_debug;      // development only (RCW_SPEC_DEBUG): timing probes of the one-launch step — bit 0 the casting workgroups return at once, bit 1 the fill's (wrong frames), ..., bit 5 (32) the fill stores every frame, changed or not (the A/B of the unchanged-frame skip)
-#endif
+};
+
+// The host's launch plan: the argument block plus the decisions of set_geometry and top_view_rule that only launchers read.  A kernel
+// launch takes its RcwDev part (the conversion to the base); a value a kernel needs does not go here but in RcwDev.
+struct RcwPlan : RcwDev {
+    int32_t fill_grid;       // workgroups of the fill kernel (the moving window = fill_grid KiB x 4)
+    int32_t fill_plain;      // 1: plain stores, 0: non-temporal
+    int32_t fill_flat;       // development build only (RCW_FILL_FLAT): rcw_fill_flat_kernel also where rcw_fill_window_kernel<2 / 4> applies
+    int32_t cast_block;      // threads per agent in the cast kernel (multiple of 64, <= 256)
+    int32_t top_grid;        // workgroups of the (persistent) write-once top view kernel
+    int32_t top_split;       // 1: the two-kernel top view (draw kernel -> planes in HBM -> moving-window store kernel)
+    int32_t top_alone_split; // rcw_update_top_view alone (no camera fill beside it) also takes the two-kernel form, back to back
+    int32_t top_runs;        // the batch is drawn and stored in this many runs of agents (store of run r beside the drawing of run r + 1)
+    int32_t top_draw_first;  // inside a step the drawing stays on the handle's stream and the camera fill goes to the side stream
+    int32_t top_fused;       // a step's camera fill and top-view drawing go in ONE launch (rcw_fill256_draw_kernel) instead of two streams
+    int32_t top_draw_block;  // threads of a draw-kernel workgroup: 256; a lane per ray (up to 1024) when the plane leaves room for few workgroups on a CU
+    int32_t top_draw_block_alone;   // ... in rcw_update_top_view alone: 64 / 128 for batches of tens of thousands of small images
+    int32_t top_store_plain; // the two-kernel form's store kernel: 1 plain stores, 0 non-temporal
+    int32_t top_store_grid;  // ... and its workgroups (the moving window = top_store_grid KiB x 4)
 };
 
 struct RcwRayOut {           // rcw_rays(): SR:29-31,39 for agents [first, first+count)
@@ -112,41 +92,42 @@ struct RcwRayOut {           // rcw_rays(): SR:29-31,39 for agents [first, first
     void* dirs;              // (2, N, count) in T
 };
 
+// Host entry points: const RcwPlan& where the function (or one it calls) reads a launch decision, const RcwDev& where the geometry is enough.
 size_t rcw_step_lds_bytes(const RcwDev& p);
 
 // act!(env, a) = cast kernel (dynamics + rays + projection -> column descriptors) followed by
 // the fill kernel (descriptors -> pixels).  actions == nullptr: render only (after reset /
 // set_state); mask == nullptr: all agents.
-hipError_t rcw_launch_cast(const RcwDev& p, const uint8_t* actions_dev, const uint8_t* mask_dev,
+hipError_t rcw_launch_cast(const RcwPlan& p, const uint8_t* actions_dev, const uint8_t* mask_dev,
                            hipStream_t s, int first = 0, int count = -1);   // agents [first, first + count); -1: to the end
-hipError_t rcw_launch_fill(const RcwDev& p, const int32_t* col_h, const uint8_t* col_c, uint32_t* frames,
+hipError_t rcw_launch_fill(const RcwPlan& p, const int32_t* col_h, const uint8_t* col_c, uint32_t* frames,
                            long long total_cols, const uint8_t* mask_dev, hipStream_t s);
 // update_top_view!(env) SR:446-483 for every (unmasked) agent; needs p.top_view
-hipError_t rcw_launch_top_view(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);
+hipError_t rcw_launch_top_view(const RcwPlan& p, const uint8_t* mask_dev, hipStream_t s);
 // LDS bytes of the write-once top view kernel for this geometry, and the one-off preparation (raises the
 // kernel's dynamic LDS limit when the bit planes need more than 64 KiB); sets nothing on the device.
 size_t rcw_top_view_lds_bytes(const RcwDev& p);
 // the two-kernel top view: eligibility of a geometry, its HBM scratch sizes, and the two launches
-int rcw_top_split_unit(const RcwDev& p);   // rows of a store-kernel unit (256 / 128 / 64), 0: geometry not taken
-int rcw_top_flat_cols(const RcwDev& p);    // rcw_top_store_flat_kernel: columns a chunk may touch, 0: geometry not taken
+int rcw_top_split_unit(const RcwPlan& p);   // rows of a store-kernel unit (256 / 128 / 64), 0: geometry not taken
+int rcw_top_flat_cols(const RcwPlan& p);    // rcw_top_store_flat_kernel: columns a chunk may touch, 0: geometry not taken
 int32_t rcw_top_plane_words(const RcwDev& p);
 int rcw_fill_flat_cols(const RcwDev& p);   // rcw_fill_flat_kernel: columns a chunk may touch at this camera height, 0: not taken
-const char* rcw_fill_kernel_name(const RcwDev& p, long long total_cols);   // the kernel rcw_launch_fill takes
-int rcw_fill_takes_256(const RcwDev& p, long long total_cols);              // ... is rcw_fill256_kernel (what the fused launches build on)
-int rcw_fill_window_columns(const RcwDev& p, long long total_cols);         // ... 0: rcw_fill256_kernel, 1 / 2 / 4: rcw_fill_window_kernel<M>, -1: another one (the one-launch step takes the first four)
+const char* rcw_fill_kernel_name(const RcwPlan& p, long long total_cols);   // the kernel rcw_launch_fill takes
+int rcw_fill_takes_256(const RcwPlan& p, long long total_cols);              // ... is rcw_fill256_kernel (what the fused launches build on)
+int rcw_fill_window_columns(const RcwPlan& p, long long total_cols);         // ... 0: rcw_fill256_kernel, 1 / 2 / 4: rcw_fill_window_kernel<M>, -1: another one (the one-launch step takes the first four)
 size_t rcw_top_plane_bytes(const RcwDev& p);
 size_t rcw_top_codes_bytes(const RcwDev& p);
 struct RcwHw { int cus, lds_per_cu, waves_per_cu; };       // what the top view's rule needs of the device (hipDeviceProp_t: multiProcessorCount, sharedMemPerBlock, maxThreadsPerMultiProcessor / 64)
 int rcw_top_draw_per_cu(const RcwDev& p, int draw_block, int lds_per_cu = 160 * 1024, int waves = 28);   // draw workgroups resident on a CU together: by LDS, by the wavefront slots the camera fill leaves
-hipError_t rcw_launch_top_draw(const RcwDev& p, const uint8_t* mask_dev, int first, int count, hipStream_t s, int block = 0);    // agents [first, first + count); block: threads a workgroup, 0 = p.top_draw_block
-hipError_t rcw_launch_top_store(const RcwDev& p, const uint8_t* mask_dev, int first, int count, hipStream_t s);
+hipError_t rcw_launch_top_draw(const RcwPlan& p, const uint8_t* mask_dev, int first, int count, hipStream_t s, int block = 0);    // agents [first, first + count); block: threads a workgroup, 0 = p.top_draw_block
+hipError_t rcw_launch_top_store(const RcwPlan& p, const uint8_t* mask_dev, int first, int count, hipStream_t s);
 // the one-launch step (round 6): eligibility of a geometry, the bytes of one of its two slot buffers ([B][5][N] packed column words + [B] bytes), the launch
-int rcw_step_spec_eligible(const RcwDev& p);
+int rcw_step_spec_eligible(const RcwPlan& p);
 size_t rcw_step_spec_slot_bytes(const RcwDev& p);
-hipError_t rcw_launch_step_spec(const RcwDev& p, const uint8_t* actions_dev, const uint8_t* mask_dev, const uint16_t* slots_in,
+hipError_t rcw_launch_step_spec(const RcwPlan& p, const uint8_t* actions_dev, const uint8_t* mask_dev, const uint16_t* slots_in,
                                 uint16_t* slots_out, bool with_fill, bool cols, bool keep, hipStream_t s);   // cols: the step also leaves the current frame's (height, colour id) descriptors; keep: p.obs holds every agent's current frame — unchanged frames are not stored again
-int rcw_fill_draw_fusable(const RcwDev& p);   // a step's camera fill + top-view drawing in one launch: this geometry takes it
-hipError_t rcw_launch_fill256_draw(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);   // (fills p.obs from p.col_h / p.col_c, draws every agent)
+int rcw_fill_draw_fusable(const RcwPlan& p);   // a step's camera fill + top-view drawing in one launch: this geometry takes it
+hipError_t rcw_launch_fill256_draw(const RcwPlan& p, const uint8_t* mask_dev, hipStream_t s);   // (fills p.obs from p.col_h / p.col_c, draws every agent)
 hipError_t rcw_prepare_top_view(const RcwDev& p, int device);
 hipError_t rcw_launch_reset(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);
 hipError_t rcw_launch_set_state(const RcwDev& p, const int2* goal, const void* pos /* float2* or double2* */,
@@ -154,7 +135,7 @@ hipError_t rcw_launch_set_state(const RcwDev& p, const int2* goal, const void* p
 hipError_t rcw_launch_init_tile_map(const RcwDev& p, hipStream_t s);
 hipError_t rcw_launch_rays(const RcwDev& p, int32_t first, int32_t count, RcwRayOut out,
                            hipStream_t s);
-hipError_t rcw_launch_expand(const RcwDev& p, const int32_t* col_h, const uint8_t* col_c,
+hipError_t rcw_launch_expand(const RcwPlan& p, const int32_t* col_h, const uint8_t* col_c,
                              int32_t count, uint32_t* frames, hipStream_t s);
 
 // The learner view (rcw_set_learner_view, rcw_view.hip): uint8 RGB or gray, area-averaged to (h, w), computed from the column
@@ -169,13 +150,13 @@ struct RcwView {
     int32_t full_ok;         // (h, w) = (Hc, N) and the geometry rcw_view_full_kernel takes
 };
 // the view of agents [0, count) of the descriptors col_h / col_c (N a agent) into out (count * C * h * w bytes); mask: NULL = all
-hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,
+hipError_t rcw_launch_view(const RcwPlan& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,
                            const uint8_t* mask_dev, uint8_t* out, hipStream_t s);
 // The view with a k-frame stack (frames = k > 1, layout CHW): the frame of agents [0, count) pushed into (refill: written to all of) their
 // `frames` slots of stack; episode / last_episode: the agents' counters now / as of their previous push (updated); mask: NULL = all.
 // At the sizes rcw_view_agent_kernel takes: rcw_view_agent_push_kernel, the one kernel that does both and leaves `staged` alone; otherwise
 // rcw_launch_view into `staged` (count * C * h * w bytes) and rcw_view_push_kernel behind it.
-hipError_t rcw_launch_view_stack(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count, int frames,
+hipError_t rcw_launch_view_stack(const RcwPlan& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count, int frames,
                                  const uint8_t* mask_dev, uint8_t* staged, uint8_t* stack, const uint32_t* episode, uint32_t* last_episode,
                                  bool refill, hipStream_t s);
 int rcw_view_full_eligible(const RcwDev& p, int C, int hwc);   // the full-resolution kernel takes this geometry and layout

@@ -970,7 +970,7 @@ __device__ __forceinline__ void top_draw_body(const RcwDev& p, const uint8_t* __
             if (w >= wpu) { w -= wpu; j += 1; }
         }
         if (part != 0) return;                                               // (the tile codes: the first part's)
-    } else if ((wpu & 3) == 0 && !p.top_signal) {
+    } else if ((wpu & 3) == 0) {
         // four words of a column a thread, one 16-byte store (a column is a multiple of 8 words here; in LDS its stride is odd: four 4-byte reads)
         const int qpc = wpu >> 2, quads = Wt * qpc, qs = group / qpc, rs = group - qs * qpc;
         int jq = tid / qpc, wq = tid - jq * qpc;
@@ -1042,7 +1042,7 @@ size_t rcw_top_view_lds_bytes(const RcwDev& p)
     return 16 + (size_t)(p.top_lds > 0 ? p.top_lds : 1) * 4 * top_buf_words(p);      // counters + the ring of p.top_lds buffers
 }
 
-hipError_t rcw_launch_top_view(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s)
+hipError_t rcw_launch_top_view(const RcwPlan& p, const uint8_t* mask_dev, hipStream_t s)
 {
     if (p.top_lds) {
         const int grid = p.B < p.top_grid ? p.B : p.top_grid;              // persistent: 4 workgroups of 8 wavefronts per CU
@@ -1056,7 +1056,7 @@ hipError_t rcw_launch_top_view(const RcwDev& p, const uint8_t* mask_dev, hipStre
 // The two-kernel top view (see rcw_top_draw_kernel): whether this geometry takes it
 // ... as the number of rows of a unit (256: rcw_top_store_kernel; 128, 64 or 32: rcw_top_store_units_kernel), 0: not taken.
 // A unit is a run of rows of ONE image column that holds whole tiles, a lane's four pixels a whole quarter of one.
-int rcw_top_split_unit(const RcwDev& p)
+int rcw_top_split_unit(const RcwPlan& p)
 {
     const long long Ht = (long long)p.H * p.pu, Wt = (long long)p.W * p.pu;
     if (p.pu < 8 || 2 * p.top_rp > 31 || p.N > 4096) return 0;                                   // (the draw kernel ranks a line within its length class in 12 bits)
@@ -1069,7 +1069,7 @@ int rcw_top_split_unit(const RcwDev& p)
     if ((long long)p.B * Wt * (Ht >> 5) >= (1ll << 31) - 64) return 0;                                               // plane word offsets
     return 4 * top_draw_lds_words(p) <= 159 * 1024 ? unit : 0;                                       // the draw kernel's LDS: plane + ray lists
 }
-int rcw_top_flat_cols(const RcwDev& p)
+int rcw_top_flat_cols(const RcwPlan& p)
 {
     const long long Ht = (long long)p.H * p.pu, Wt = (long long)p.W * p.pu;
     if (p.pu < 9 || (Ht & 3) != 0 || Ht > 16384 || Wt > 16384 || p.H > 65535 || p.top_rp > 8191 || p.N > 4096) return 0;
@@ -1098,19 +1098,19 @@ size_t rcw_top_codes_bytes(const RcwDev& p)
 
 // agents [first, first + count): the draw kernel's workgroups / the store kernel's chunks of that run (an image is a
 // whole number of 1 KiB chunks in every geometry rcw_top_split_unit takes)
-hipError_t rcw_launch_top_draw(const RcwDev& p, const uint8_t* mask_dev, int first, int count, hipStream_t s, int block)
+hipError_t rcw_launch_top_draw(const RcwPlan& p, const uint8_t* mask_dev, int first, int count, hipStream_t s, int block)
 {
     RCW_DISPATCH(rcw_top_draw_kernel, dim3(count * (p.top_parts > 1 ? p.top_parts : 1)), dim3(block > 0 ? block : p.top_draw_block), 4 * top_draw_lds_words(p), p, mask_dev, first);
     return hipGetLastError();
 }
 // the camera fill of the whole batch + the drawing of every agent in one launch (rcw_fill256_draw_kernel): whether this handle's
 // geometry takes it, and the launch
-int rcw_fill_draw_fusable(const RcwDev& p)
+int rcw_fill_draw_fusable(const RcwPlan& p)
 {
     return p.top_split && p.top_runs <= 1 && p.top_draw_block == kBlock && !p.fill_plain && 4 * top_draw_lds_words(p) <= 64 * 1024 &&
            rcw_fill_takes_256(p, (long long)p.B * p.N) && (long long)p.fill_grid + p.B < (1ll << 31);
 }
-hipError_t rcw_launch_fill256_draw(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s)
+hipError_t rcw_launch_fill256_draw(const RcwPlan& p, const uint8_t* mask_dev, hipStream_t s)
 {
     u32x4* const frames4 = reinterpret_cast<u32x4*>(p.obs);
     RCW_DISPATCH(rcw_fill256_draw_kernel, dim3(p.fill_grid + p.B), dim3(kBlock), 4 * top_draw_lds_words(p), p, p.col_h, p.col_c, frames4,

@@ -190,7 +190,6 @@ __global__ __launch_bounds__(kBlock) void rcw_top_store_kernel(const RcwDev p, c
     uint32_t* const lw_write = plane_words + (threadIdx.x >> 6) * 512 + lane;
     const uint32_t* const lw_read = plane_words + (threadIdx.x >> 6) * 512 + (lane >> 3);
     uint32_t base = chunk_begin + g;
-    [[maybe_unused]] uint32_t have = 0u;                                     // (unused: what is left of a retired experiment; removing it renames registers in the flat kernel, see profiles/retire_variants_isa.txt)
     for (; base < total; base += G * 64) {
         TopGroup cur;
         top_group_issue(p, mask, base, G, total, lane, cur);
@@ -257,7 +256,6 @@ __global__ __launch_bounds__(kBlock) void rcw_top_store_units_kernel(const RcwDe
     uint32_t* const desc = ws + 512;                                         // [64 chunks][U]
     uint32_t* const circ = desc + 64 * U;
     uint32_t* const crow = circ + 64 * U;
-    [[maybe_unused]] uint32_t have = 0u;                                     // (unused: what is left of a retired experiment; removing it renames registers in the flat kernel, see profiles/retire_variants_isa.txt)
     for (uint32_t base = chunk_begin + g; base < total; base += G * 64) {
         const uint32_t id = base + (uint32_t)lane * G;
         uint32_t packed[U], cmask[U];
@@ -540,7 +538,6 @@ __global__ __launch_bounds__(kBlock) void rcw_top_store_flat_kernel(const RcwDev
     uint32_t a_cur = col / (unsigned)Wt, j_cur = col - a_cur * (unsigned)Wt;      // (agent, image column) of this lane's next chunk
     const uint32_t dqa = dq / (unsigned)Wt, dqj = dq - dqa * (unsigned)Wt;        // ... move by this much a group (+ 1 column on a row wrap)
     const uint32_t dqa_w = dq_w / (unsigned)Wt, dqj_w = dq_w - dqa_w * (unsigned)Wt;
-    [[maybe_unused]] uint32_t have = 0u;                                     // (unused: what is left of a retired experiment; removing it renames registers in the flat kernel, see profiles/retire_variants_isa.txt)
     auto issue = [&](uint32_t base, TopFlatPre<K>& P) {
         const uint32_t id = base + (uint32_t)lane * G;
         const bool exists = id < chunk_end;
@@ -736,7 +733,7 @@ __global__ __launch_bounds__(kBlock) void rcw_top_store_flat_kernel(const RcwDev
 }  // namespace
 
 // ---- launcher -----------------------------------------------------------------------------------
-hipError_t rcw_launch_top_store(const RcwDev& p, const uint8_t* mask_dev, int first, int count, hipStream_t s)
+hipError_t rcw_launch_top_store(const RcwPlan& p, const uint8_t* mask_dev, int first, int count, hipStream_t s)
 {
     const dim3 grid(p.top_store_grid), block(kBlock);
     if (p.top_flat) {

@@ -430,7 +430,7 @@ static void view_instance(const RcwView& v, Launch launch)
     else launch(std::integral_constant<int, 3>{}, std::false_type{});
 }
 
-hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,
+hipError_t rcw_launch_view(const RcwPlan& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,
                            const uint8_t* mask_dev, uint8_t* out, hipStream_t s)
 {
     if (count < 1) return hipSuccess;
@@ -464,7 +464,7 @@ hipError_t rcw_launch_view(const RcwDev& p, const RcwView& v, const int32_t* col
     return hipGetLastError();
 }
 
-hipError_t rcw_launch_view_stack(const RcwDev& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count, int frames,
+hipError_t rcw_launch_view_stack(const RcwPlan& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count, int frames,
                                  const uint8_t* mask_dev, uint8_t* staged, uint8_t* stack, const uint32_t* episode, uint32_t* last_episode,
                                  bool refill, hipStream_t s)
 {

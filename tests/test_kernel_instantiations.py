@@ -28,7 +28,7 @@ def _b(x):
 
 
 def fill_flat_label(hc):
-    return f"rcw_fill_flat_kernel<{_b(hc % 4 == 0)}, {254 // hc + 2}, false>"      # (the third parameter: two wavefronts to a slot — a retired experiment's, never true)
+    return f"rcw_fill_flat_kernel<{_b(hc % 4 == 0)}, {254 // hc + 2}>"
 
 
 def top_flat_label(H, W, pu):
@@ -62,7 +62,8 @@ def test_the_case_lists_cover_every_shipped_instantiation_of_the_flat_kernels():
     # no plain-store variant (the development build's only), no 128-row units kernel (the flat kernel takes every such geometry)
     assert not [n for n in names if re.match(r"rcw_(fill256|top_store|top_store_units)_kernel<true", n)], names
     assert "rcw_top_store_units_kernel<false, 2>" not in names
-    assert not [n for n in names if re.match(r"rcw_fill_flat_kernel<\w+, \d+, true>", n)], names
+    # the flat fill kernel is <ALIGNED, K> and nothing more: no name of the family carries a third template argument
+    assert not [n for n in names if re.match(r"rcw_fill_flat_kernel<[^,>]*,[^,>]*,", n)], names
     # the step's kernels: <T, TIE, DIST> of the cast kernel, <T, TIE, DIST, WAVE> of the one-launch step and of what primes its slots
     for family, count in (("rcw_cast_kernel<", 8), ("rcw_fill256_cast_kernel<", 16), ("rcw_fill_window_cast_kernel<", 16), ("rcw_cast_successors_kernel<", 16)):
         assert len([n for n in names if n.startswith(family)]) == count, (family, sorted(n for n in names if n.startswith(family)))
