@@ -1,6 +1,6 @@
 // Development build only (-DRCW_DEV_SWITCHES): the top view's rule and its table of thresholds WITHOUT a device — what
 // tests/test_top_view_plan.py runs on the CPU.  A fragment of rcw_api.hip, included behind plan_top_view (inside the anonymous namespace: the
-// two exports leave it and come back).
+// exports leave it and come back).
 }  // namespace
 extern "C" {
 // out[16]: form in a step (RCW_TOP_VIEW_*), form of rcw_update_top_view alone, then top_lds, top_split, top_flat, top_unit_px, top_fused,
@@ -15,9 +15,7 @@ __attribute__((visibility("default"))) int rcw_dev_plan_top_view(const rcw_confi
     d.top_view = cfg->render_top_view ? reinterpret_cast<uint32_t*>(16) : nullptr;      // (a marker: the rule only asks whether the handle renders one)
     const RcwHw hw{cus, lds_per_cu, waves_per_cu};
     const int rc = top_view_rule(d, cfg, (size_t)batch, hw, want_form, want_runs, /*lenient=*/want_form == 0);
-    const int form = !d.top_view ? RCW_TOP_VIEW_NONE : d.top_split ? RCW_TOP_VIEW_TWO_KERNELS : d.top_lds ? RCW_TOP_VIEW_ONE_KERNEL : RCW_TOP_VIEW_IN_PLACE;
-    const int alone = !d.top_view ? RCW_TOP_VIEW_NONE : (d.top_split && d.top_alone_split) ? RCW_TOP_VIEW_TWO_KERNELS : d.top_lds ? RCW_TOP_VIEW_ONE_KERNEL : RCW_TOP_VIEW_IN_PLACE;
-    const int32_t v[16] = {form, alone, d.top_lds, d.top_split, d.top_flat, d.top_unit_px, d.top_fused, d.top_draw_first, d.top_parts, d.top_runs,
+    const int32_t v[16] = {top_form_in_step(d), top_form_alone(d), d.top_lds, d.top_split, d.top_flat, d.top_unit_px, d.top_fused, d.top_draw_first, d.top_parts, d.top_runs,
                            d.top_draw_block, d.top_draw_block_alone, d.top_alone_split, d.top_grid, d.top_store_grid, rc};
     std::memcpy(out, v, sizeof v);
     return rc;
@@ -44,6 +42,45 @@ __attribute__((visibility("default"))) int rcw_dev_step_rule(const rcw_config* c
     d.fill_grid = cus;
     d.top_view = cfg->render_top_view ? reinterpret_cast<uint32_t*>(16) : nullptr;
     return rcw_step_spec_eligible(d) && step_one_launch_pays(d) ? 1 : 0;
+}
+// A StepFacts driven through a list of events without a device (tests/test_step_state.py).  `eligible`, `pays`: what rcw_step_spec_eligible and
+// step_one_launch_pays would say of the handle.  events [n][3] = kind, a, b; out [n][12] = the nine facts behind each event (StepFacts::read),
+// then, for a camera step, the path it took (StepFacts::Path; else -1) and the `keep` it passes, then 1 where the event was refused.
+//   0  plan_step_form(want = a), the learner view with RCW_VIEW_ONLY: b
+//   1  launch_step_camera; a: bit 0 actions, bit 1 a mask, bit 2 the stream is capturing, bit 3 the first launch fails, bit 4 the priming path's fill fails
+//   2  a RCW_VIEW_ONLY step (launch_step); a: bit 1 a mask             3  rcw_bind_obs
+//   4  rcw_reset in front of its render; a: bit 0 a mask, bit 1 a seed that is not the handle's, bit 2 cfg.auto_reset
+//   5  rcw_cast_rays, or ensure_columns in front of a reader           6  rcw_columns_device_ptr / a learner view switched on
+//   7  rcw_update_camera_view
+__attribute__((visibility("default"))) int rcw_dev_step_facts(int32_t eligible, int32_t pays, int32_t store_all, const int32_t* events, int32_t n, int32_t* out)
+{
+    if (!events || !out || n < 0) return RCW_ERR_INVALID_ARGUMENT;
+    StepFacts f;
+    f.set_store_all(store_all != 0);
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t kind = events[3 * i], a = events[3 * i + 1], b = events[3 * i + 2];
+        const bool masked = (a & 2) != 0;
+        int32_t* const o = out + 12 * (size_t)i;
+        o[9] = -1; o[10] = 0; o[11] = 0;
+        if (kind == 0) {
+            const StepFacts::Plan p = f.plan(a, b != 0, eligible != 0, pays != 0);
+            if (p.refused) o[11] = 1; else f.take(p);
+        } else if (kind == 1) {
+            const StepFacts::Camera c = f.camera_step((a & 1) != 0, masked, [a] { return (a & 4) != 0; });
+            o[9] = c.path; o[10] = c.keep;
+            if (c.path == StepFacts::kOneLaunch && !(a & 8)) f.one_launch_queued();
+            if (c.path == StepFacts::kPrime && !(a & 8)) { f.prime_cast_queued(masked); if (!(a & 16)) f.prime_fill_queued(c, masked); }
+        }
+        else if (kind == 2) { f.obs_unknown(); f.columns_cast(masked); }
+        else if (kind == 3) f.obs_unknown();
+        else if (kind == 4) f.reset((a & 1) != 0, (a & 2) != 0, (a & 4) != 0);
+        else if (kind == 5) f.columns_cast();
+        else if (kind == 6) { f.columns_wanted(); f.columns_cast(); }
+        else if (kind == 7) { f.obs_unknown(); f.columns_cast(); f.camera_repainted(); }
+        else return RCW_ERR_INVALID_ARGUMENT;
+        f.read(o);
+    }
+    return n;
 }
 }  // extern "C"
 namespace {

@@ -48,13 +48,13 @@ int fail_at(int line, int code, const char* fmt, A... args)
 // The text of a failed runtime call, which is thereby REPORTED: the runtime also keeps the code as the thread's last error, and the launchers'
 // hipGetLastError() would hand it out as their own (a create that ran out of memory made the next rcw_create fail in its first launch).
 const char* hip_failure(hipError_t e) { (void)hipGetLastError(); return hipGetErrorString(e); }
+int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP; }   // the RCW_ERR_* of a failed runtime call
 
 #define RCW_HIP(expr)                                                                   \
     do {                                                                                \
         hipError_t e_ = (expr);                                                         \
         if (e_ != hipSuccess)                                                           \
-            return fail(e_ == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, \
-                        "%s failed: %s", #expr, hip_failure(e_));                 \
+            return fail(hip_code(e_), "%s failed: %s", #expr, hip_failure(e_));         \
     } while (0)
 
 }  // namespace
@@ -67,6 +67,85 @@ extern "C" __attribute__((visibility("default"))) int rcw_dev_fail_sites(unsigne
     return n;
 }
 #endif
+
+// THE FACTS OF A STEP: what decides which launches a step of a handle makes, and whether the one-launch step (rcw_fill256_cast_kernel) may
+// leave the frame of an agent whose view it does not change as it is (`keep`).  No HIP call — the development build drives it without a
+// device (rcw_dev_step_facts, tests/test_step_state.py) —, and private: only the events below, what happens to a handle, change a fact.
+//   on, want, captured     a step is ONE launch; what rcw_set_step_form asked for (0 = the rule); a step of the handle was captured into a graph
+//   cur, primed            of the one-launch step's two buffers of [B][5][N] packed column words (rcw_handle::Step), `cur` holds the frames of
+//                          the CURRENT state (slot 0) and of its four successors (slots 1..4), written by the last casting launch — primed: for
+//                          every agent (each buffer ends in one byte per agent: which of its slots hold the very frame slot 0 holds — cast_body)
+//   obs_current            dev.obs holds, for EVERY agent, the frame of the state the primed slots were cast from: the one-launch step may then
+//                          skip the unchanged frames.  False costs nothing but the skip: the next one-launch step writes every pixel and sets it.
+//   cols_live, cols_stale  The (height_line_pu, colour id) descriptors of the current frames (d_col_h / d_col_c) are what the two-launch step
+//                          hands from its cast kernel to its fill kernel; the one-launch step's fill reads the slots instead, and every store of
+//                          the casting workgroups costs the launch more than its bytes (profiles/r06_step_forms.txt) — so it writes them only
+//                          for a caller that holds their device pointers (cols_live), and otherwise leaves them stale: ensure_columns recasts
+//                          the current state in front of whatever reads them (rcw_columns, the gathers, rcw_update_camera_view).
+//   store_all              development build (RCW_STEP_STORE_ALL=1): every frame is stored, changed or not — the A/B of the unchanged-frame skip
+class StepFacts {
+    bool on_ = false, captured_ = false, primed_ = false, obs_current_ = false, cols_live_ = false, cols_stale_ = false, store_all_ = false;
+    int want_ = 0, cur_ = 0;
+    void forget() { primed_ = false; obs_current_ = false; }     // the slots describe nothing any more: so do their bytes
+public:
+    bool on() const { return on_; }
+    bool cols_live() const { return cols_live_; }
+    bool cols_stale() const { return cols_stale_; }
+    int want() const { return want_; }
+    int cur() const { return cur_; }
+    void read(int32_t out[9]) const { const int32_t v[9] = {on_, want_, captured_, primed_, obs_current_, cur_, cols_live_, cols_stale_, store_all_}; std::memcpy(out, v, sizeof v); }
+    void set_store_all(bool v) { store_all_ = v; }               // rcw_create
+
+    // Which form a step takes (plan_step_form), in two halves with the slot buffers' allocation between them: plan() changes nothing, so a
+    // refused or failed request leaves every fact as it was.  view_only: the cast kernel followed by the view kernel, no camera fill to fuse.
+    struct Plan { const char* refused; int want; bool on, view_only; };
+    Plan plan(int want, bool view_only, bool eligible, bool pays) const
+    {
+        const bool one = want == RCW_STEP_ONE_LAUNCH;
+        if (view_only) return {one ? "the handle's learner view is set with RCW_VIEW_ONLY: a step is the cast kernel and the view kernel" : nullptr, want, false, true};
+        if (one && !eligible) return {"this handle does not take the one-launch step (a camera view of 256 k, 128 or 64 rows — up to 8191 — without a top view, fewer than 2^29 view columns)", want, false, false};
+        return {nullptr, want, want == RCW_STEP_TWO_LAUNCHES ? false : (one ? true : eligible && !captured_ && pays), false};
+    }
+    void take(const Plan& p)
+    {
+        if (p.on && p.want == RCW_STEP_ONE_LAUNCH) captured_ = false;
+        if (p.view_only || p.on != on_) forget();                 // (a change of form, either way)
+        on_ = p.on; want_ = p.want;
+    }
+
+    // A step, reset! or set_state's camera view begins: what it launches, and whether one launch may skip the unchanged frames.  Whatever
+    // fails from here on leaves obs_current cleared.  capturing(), asked only where the one-launch form is on: that form keeps its place in
+    // the slot buffers on the HOST, and a graph would replay one launch's pointers for ever.  A handle whose step is captured keeps the
+    // two-launch form from then on (replays advance the state behind the library's back: its slots can never be trusted again).
+    enum Path { kTwoLaunches, kOneLaunch, kPrime };
+    struct Camera { Path path; bool was_current, keep; };
+    template <typename Capturing>
+    Camera camera_step(bool actions, bool masked, Capturing capturing)
+    {
+        const bool was_current = obs_current_ && primed_;
+        obs_current_ = false;
+        if (on_ && capturing()) { on_ = false; captured_ = true; forget(); }
+        const Path path = !on_ ? kTwoLaunches : (actions && !masked && primed_ ? kOneLaunch : kPrime);
+        return {path, was_current, path == kOneLaunch && was_current && !store_all_};
+    }
+    // ... and what it has launched (kTwoLaunches: nothing comes back).  One launch, skipped or not: every agent's frame is the new state's.
+    void one_launch_queued() { cur_ ^= 1; obs_current_ = true; if (!cols_live_) cols_stale_ = true; }
+    // (with a mask: the masked agents' descriptors are fresh — the fill behind it reads only those —, the others' as stale as before)
+    void prime_cast_queued(bool masked) { if (!masked) { cols_stale_ = false; primed_ = true; } }
+    // every agent painted and every slot primed — or, with a mask, exactly the agents repainted whose slots were rewritten: as it was
+    void prime_fill_queued(const Camera& c, bool masked) { obs_current_ = primed_ && (!masked || c.was_current); }
+
+    // rcw_bind_obs (also with the pointer it had: the caller may have written into the buffer), a RCW_VIEW_ONLY step (which does not paint
+    // the camera view), rcw_update_camera_view before it paints — and behind its fill: every agent's current frame, which slot 0 holds
+    void obs_unknown() { obs_current_ = false; }
+    void camera_repainted() { if (on_ && primed_) obs_current_ = true; }
+    // rcw_reset.  The seed is the HANDLE's: an agent that is done under auto_reset and NOT in the mask is re-sampled by its next action with
+    // the new seed — but the one-launch step has already cast that agent's successors from a preview drawn with the old one: every agent's
+    // slots are cast again by the next step, as a launch of its own.
+    void reset(bool masked, bool new_seed, bool auto_reset) { if (masked && new_seed && auto_reset) forget(); }
+    void columns_cast(bool masked = false) { if (!masked) cols_stale_ = false; }   // the cast kernel was queued: rcw_cast_rays, ensure_columns, a RCW_VIEW_ONLY step
+    void columns_wanted() { cols_live_ = true; }                 // rcw_columns_device_ptr, a learner view switched on: every step refreshes the descriptors
+};
 
 // OWNERSHIP: every device buffer, pinned buffer, stream and event of a handle is a member of one of rcw_owned.h's types; nothing else frees
 // them.  ~rcw_handle waits for all the handle's streams and then lets the members go in reverse order of declaration: the two STREAMS ARE
@@ -93,26 +172,15 @@ struct rcw_handle {
     RcwPinned h_err, h_actions[2];     // the error word (int32_t); the staging ring of rcw_step (uint8_t)
     RcwEvent ev_actions[2];
     int action_slot = 0;
-    bool profiling = false;
-    // the one-launch step (rcw_fill256_cast_kernel): two buffers of [B][5][N] packed column words — d_spec[spec_cur] holds the frames of the
-    // CURRENT state (slot 0) and of its four successors (slots 1..4), written by the last casting launch; spec_primed: for every agent
-    // (each buffer ends in one byte per agent: which of its slots hold the very frame slot 0 holds — rcw_cast.hip, cast_body).
-    // obs_current: dev.obs holds, for EVERY agent, the frame of the state the primed slots were cast from — the one-launch step may then leave
-    // the frames of agents whose view it does not change as they are.  Set by obs_is_current() only, cleared by obs_unknown() / spec_forget()
-    // only (next to launch_step_camera); false costs nothing but the skip: the next one-launch step writes every pixel and sets it again.
-    RcwBuf d_spec[2]; int spec_cur = 0; bool spec_primed = false, obs_current = false;
-    int spec_on = 0;                   // a step is ONE launch (rcw_fill256_cast_kernel)
-    bool step_store_all = false;       // development build (RCW_STEP_STORE_ALL=1): the one-launch step stores every frame, changed or not — the A/B of the unchanged-frame skip
-    // The (height_line_pu, colour id) descriptors of the current frames (d_col_h / d_col_c) are what the two-launch step hands from its cast
-    // kernel to its fill kernel; the one-launch step's fill reads the slots instead, and every store of the casting workgroups costs the
-    // launch more than its bytes (profiles/r06_step_forms.txt) — so it writes the descriptors only for a caller that holds their device
-    // pointers (cols_live: rcw_columns_device_ptr was called), and otherwise leaves them stale: ensure_columns recasts the current state
-    // (the cast kernel, no action) in front of whatever reads them (rcw_columns, the gathers, rcw_update_camera_view).
-    bool cols_live = false, cols_stale = false;
-    int step_form_want = 0;            // rcw_set_step_form: 0 = the rule, or RCW_STEP_TWO_LAUNCHES / RCW_STEP_ONE_LAUNCH
-    bool step_captured = false;        // a step of this handle was captured into a graph: it keeps the two-launch form from then on
-    int prof_count = 0;
-    std::vector<RcwEvent> prof_ev;     // 4 per recorded step: start | after cast | after top view | after fill
+    struct Step : StepFacts { RcwBuf slot[2]; } step;   // (the one-launch step's two slot buffers: slot[cur()] is the one the next launch reads)
+    // rcw_profile: HIP events around each kernel of a step (what bench.py's roofline block reads the fill kernel's duration from), four a
+    // recorded step — start | after cast | after top view | after fill —, for the first kSlots steps since it was switched on
+    struct Profile {
+        static constexpr int kSlots = 256;
+        bool on = false;
+        int count = 0;
+        std::vector<RcwEvent> ev;
+    } prof;
     RcwBuf d_rays[4];                  // rcw_rays scratch (grow-only)
     size_t rays_cap[4] = {0, 0, 0, 0};
     size_t reward_size = sizeof(float);
@@ -143,16 +211,24 @@ struct rcw_handle {
 
 namespace {
 
-constexpr int kProfileSlots = 256;
+// The four profiling events of ONE step, or none (profiling off, slots used up): mark(k) records event k on a stream, done() the last one on
+// the handle's stream — and, recorded, counts the step: one that failed on the way is not counted.
+class Bracket {
+    rcw_handle::Profile* p_;
+public:
+    explicit Bracket(rcw_handle::Profile* p = nullptr) : p_(p && p->on && p->count < p->kSlots ? p : nullptr) {}
+    hipError_t mark(int k, hipStream_t s) const { return p_ ? hipEventRecord(p_->ev[4 * p_->count + k].get(), s) : hipSuccess; }
+    hipError_t done(hipStream_t s) const { const hipError_t e = mark(3, s); if (p_ && e == hipSuccess) p_->count++; return e; }
+};
 
 // update_top_view!(env) SR:446-483.  Two-kernel form: the draw kernel (VALU/LDS work, planes -> HBM) and the
 // moving-window store kernel.  `between` (the camera fill, inside a step) is launched on the handle's stream while
 // the draw kernel runs on the side stream: fork after what is already queued (the cast kernel), join before the store.
 // The stand-alone call (`beside` = false) has no camera fill to run beside and takes the one-kernel form.
 template <typename Between>
-hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool beside, Between between, hipEvent_t fused_event);
+hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool beside, Between between, const Bracket& prof);
 template <typename Between>
-hipError_t launch_top_view(rcw_handle* h, const uint8_t* mask_dev, bool beside, Between between, hipEvent_t fused_event = nullptr)   // between(stream): the caller's camera fill
+hipError_t launch_top_view(rcw_handle* h, const uint8_t* mask_dev, bool beside, Between between, const Bracket& prof = Bracket())   // between(stream): the caller's camera fill
 {
     const RcwPlan& d = h->dev;
     hipError_t e;
@@ -166,15 +242,15 @@ hipError_t launch_top_view(rcw_handle* h, const uint8_t* mask_dev, bool beside, 
         struct Clean { rcw_handle* h; hipError_t* e; ~Clean() { if (*e == hipSuccess) h->top_plane_dirty = false; } };
         hipError_t result = hipErrorUnknown;
         Clean clean{h, &result};
-        result = launch_top_view_ordered(h, mask_dev, beside, between, fused_event);
+        result = launch_top_view_ordered(h, mask_dev, beside, between, prof);
         return result;
     }
-    return launch_top_view_ordered(h, mask_dev, beside, between, fused_event);
+    return launch_top_view_ordered(h, mask_dev, beside, between, prof);
 }
 
 // (the launch orders of the two-kernel form; launch_top_view above decides whether it is taken)
 template <typename Between>
-hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool beside, Between between, hipEvent_t fused_event)
+hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool beside, Between between, const Bracket& prof)
 {
     const RcwPlan& d = h->dev;
     hipError_t e;
@@ -188,7 +264,7 @@ hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool 
         // stream, no fork / join.  `between` — the camera fill of the caller — is replaced by that launch; its profiling
         // event (behind the fill, in front of the store kernel) is recorded here.
         if ((e = rcw_launch_fill256_draw(d, mask_dev, h->stream)) != hipSuccess) return e;
-        if (fused_event && (e = hipEventRecord(fused_event, h->stream)) != hipSuccess) return e;
+        if ((e = prof.mark(2, h->stream)) != hipSuccess) return e;
         return rcw_launch_top_store(d, mask_dev, 0, d.B, h->stream);
     }
     if (d.top_draw_first && d.top_runs <= 1) {
@@ -235,77 +311,70 @@ hipError_t launch_top_view_ordered(rcw_handle* h, const uint8_t* mask_dev, bool 
     return e;
 }
 
-// rcw_handle::obs_current and spec_primed: the only places that write them, besides the priming path of launch_step_camera (spec_primed = true)
-void obs_is_current(rcw_handle* h) { h->obs_current = true; }
-void obs_unknown(rcw_handle* h) { h->obs_current = false; }
-void spec_forget(rcw_handle* h) { h->spec_primed = false; h->obs_current = false; }   // the slots describe nothing any more: so do their bytes
+// the camera fill of the handle's own descriptors into dev.obs (the unmasked agents' frames only)
+hipError_t paint_camera(rcw_handle* h, const uint8_t* mask_dev, hipStream_t stream)
+{
+    return rcw_launch_fill(h->dev, h->dev.col_h, h->dev.col_c, h->dev.obs, (long long)h->dev.B * h->dev.N, mask_dev, stream);
+}
 
-// One step = cast kernel + fill kernel, back to back on the handle's stream (+ the top view when the handle renders
-// it: before the fill with the one-kernel form, around it with the two-kernel form).  With profiling on,
-// HIP events bracket each kernel (what bench.py's roofline block reads the fill kernel's
-// duration from): start | after cast | after the top view (one-kernel form) or the fill (two-kernel form) | end.
-hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev)
+// A step's camera view is one of three sequences of launches (launch_step_camera chooses: StepFacts::camera_step).  With profiling on, HIP
+// events bracket each kernel (Bracket): start (launch_step_camera's) | after cast | after the top view or the fill | end.
+// act!(env, a) SR:333-340 in ONE launch: the fill workgroups write the frames the actions select among the successors the last casting
+// launch left in the current slot buffer; the casting workgroups commit the actions and cast the new states' successors into the other one
+hipError_t launch_step_one(rcw_handle* h, const uint8_t* actions_dev, bool keep, const Bracket& prof)
+{
+    rcw_handle::Step& st = h->step;
+    hipError_t e;
+    if ((e = prof.mark(1, h->stream)) != hipSuccess || (e = prof.mark(2, h->stream)) != hipSuccess) return e;
+    if ((e = rcw_launch_step_spec(h->dev, actions_dev, nullptr, st.slot[st.cur()].get<uint16_t>(), st.slot[st.cur() ^ 1].get<uint16_t>(), true, st.cols_live(), keep, h->stream)) != hipSuccess) return e;
+    st.one_launch_queued();
+    return prof.done(h->stream);
+}
+
+// reset! / set_state (no action, maybe a mask) or a first step of the one-launch form: the casting workgroups alone — dynamics if any, the
+// current frame's descriptors, and the (masked) agents' slots in place —, then the camera fill as a launch of its own
+hipError_t launch_step_prime(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, const StepFacts::Camera& c, const Bracket& prof)
+{
+    rcw_handle::Step& st = h->step;
+    hipError_t e;
+    if ((e = rcw_launch_step_spec(h->dev, actions_dev, mask_dev, nullptr, st.slot[st.cur()].get<uint16_t>(), false, true, false, h->stream)) != hipSuccess) return e;
+    st.prime_cast_queued(mask_dev != nullptr);
+    if ((e = prof.mark(1, h->stream)) != hipSuccess || (e = prof.mark(2, h->stream)) != hipSuccess) return e;
+    if ((e = paint_camera(h, mask_dev, h->stream)) != hipSuccess) return e;
+    st.prime_fill_queued(c, mask_dev != nullptr);
+    return prof.done(h->stream);
+}
+
+// cast kernel + fill kernel, back to back on the handle's stream (+ the top view when the handle renders it: before the fill with the
+// one-kernel form, around it with the two-kernel form, whose event 2 is behind the fill)
+hipError_t launch_step_two(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, const Bracket& prof)
 {
     const RcwPlan& d = h->dev;
-    // Whatever fails below, and every form but the one-launch step and what primes it, leaves the fact cleared.
-    const bool was_current = h->obs_current && h->spec_primed;
-    obs_unknown(h);
-    const bool prof = h->profiling && h->prof_count < kProfileSlots;
-    const RcwEvent* ev = prof ? &h->prof_ev[4 * h->prof_count] : nullptr;
     hipError_t e;
-    if (h->spec_on) {
-        // The one-launch step keeps its place in the slot buffers on the HOST (which of the two the next launch reads): a graph would replay
-        // one launch's pointers for ever.  A handle whose step is captured keeps the two-launch form from then on (replays advance the
-        // state behind the library's back, so its slots can never be trusted again): rcw_step_form says so.
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { h->spec_on = 0; h->step_captured = true; spec_forget(h); }
-    }
-    if (prof && (e = hipEventRecord(ev[0].get(), h->stream)) != hipSuccess) return e;
-    if (h->spec_on) {
-        uint16_t* const cur = h->d_spec[h->spec_cur].get<uint16_t>();
-        if (actions_dev && !mask_dev && h->spec_primed) {
-            // act!(env, a) SR:333-340 in ONE launch: the fill workgroups write the frames the actions select among the successors the last
-            // casting launch left in `cur`; the casting workgroups commit the actions and cast the new states' successors into the other buffer
-            uint16_t* const next = h->d_spec[h->spec_cur ^ 1].get<uint16_t>();
-            if (prof && ((e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess || (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess)) return e;
-            if ((e = rcw_launch_step_spec(d, actions_dev, nullptr, cur, next, true, h->cols_live, was_current && !h->step_store_all, h->stream)) != hipSuccess) return e;
-            h->spec_cur ^= 1;
-            obs_is_current(h);                                    // (skipped or not: every agent's frame is the new state's)
-            if (!h->cols_live) h->cols_stale = true;
-            if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
-            return hipSuccess;
-        }
-        // reset! / set_state (no action, maybe a mask) or a first step: the casting workgroups alone — dynamics if any, the current frame's
-        // descriptors, and the (masked) agents' slots in place —, then the camera fill as a launch of its own
-        if ((e = rcw_launch_step_spec(d, actions_dev, mask_dev, nullptr, cur, false, true, false, h->stream)) != hipSuccess) return e;
-        if (!mask_dev) h->cols_stale = false;                 // (with a mask: the masked agents' descriptors are fresh — the fill below reads only those —, the others' as stale as before)
-        if (!mask_dev) h->spec_primed = true;
-        if (prof && ((e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess || (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess)) return e;
-        if ((e = rcw_launch_fill(d, d.col_h, d.col_c, d.obs, (long long)d.B * d.N, mask_dev, h->stream)) != hipSuccess) return e;
-        // every agent painted and every slot primed — or, with a mask, exactly the agents repainted whose slots were rewritten: as it was
-        if (h->spec_primed && (!mask_dev || was_current)) obs_is_current(h);
-        if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
-        return hipSuccess;
-    }
     if ((e = rcw_launch_cast(d, actions_dev, mask_dev, h->stream)) != hipSuccess) return e;
-    if (prof && (e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess) return e;
+    if ((e = prof.mark(1, h->stream)) != hipSuccess) return e;
     auto fill = [&](hipStream_t fs) -> hipError_t {            // (fs: the handle's stream, or its side stream: launch_top_view)
         hipError_t f;
-        if (prof && !d.top_split && (f = hipEventRecord(ev[2].get(), fs)) != hipSuccess) return f;
-        if ((f = rcw_launch_fill(d, d.col_h, d.col_c, d.obs, (long long)d.B * d.N, mask_dev, fs)) != hipSuccess) return f;
-        if (prof && d.top_split && (f = hipEventRecord(ev[2].get(), fs)) != hipSuccess) return f;
-        return hipSuccess;
+        if (!d.top_split && (f = prof.mark(2, fs)) != hipSuccess) return f;
+        if ((f = paint_camera(h, mask_dev, fs)) != hipSuccess) return f;
+        return d.top_split ? prof.mark(2, fs) : hipSuccess;
     };
-    if (d.top_view) { if ((e = launch_top_view(h, mask_dev, true, fill, prof ? ev[2].get() : nullptr)) != hipSuccess) return e; }   // SR:337
-    else {
-        if (prof && (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess) return e;
-        if ((e = rcw_launch_fill(d, d.col_h, d.col_c, d.obs, (long long)d.B * d.N, mask_dev, h->stream)) != hipSuccess) return e;
-    }
-    if (prof) {
-        if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e;
-        h->prof_count++;
-    }
-    return hipSuccess;
+    if ((e = d.top_view ? launch_top_view(h, mask_dev, true, fill, prof) : fill(h->stream)) != hipSuccess) return e;   // SR:337
+    return prof.done(h->stream);
+}
+
+hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev)
+{
+    const StepFacts::Camera c = h->step.camera_step(actions_dev != nullptr, mask_dev != nullptr, [h] {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        return hipStreamIsCapturing(h->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    });
+    const Bracket prof(&h->prof);
+    const hipError_t e = prof.mark(0, h->stream);
+    if (e != hipSuccess) return e;
+    if (c.path == StepFacts::kOneLaunch) return launch_step_one(h, actions_dev, c.keep, prof);
+    if (c.path == StepFacts::kPrime) return launch_step_prime(h, actions_dev, mask_dev, c, prof);
+    return launch_step_two(h, actions_dev, mask_dev, prof);
 }
 
 // What a render does to the k-frame stack (include/rcw.h, "the frame stack"): a step pushes, reset! / set_state / a new view or direction
@@ -332,19 +401,17 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
         const hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
         return e == hipSuccess && h->learner.on() ? launch_view(h, mask_dev, op) : e;
     }
-    obs_unknown(h);                                               // (RCW_VIEW_ONLY: the camera view is not painted)
-    const bool prof = h->profiling && h->prof_count < kProfileSlots;
-    const RcwEvent* ev = prof ? &h->prof_ev[4 * h->prof_count] : nullptr;
+    h->step.obs_unknown();                                        // (the camera view is not painted)
+    const Bracket prof(&h->prof);
     hipError_t e;
-    if (prof && (e = hipEventRecord(ev[0].get(), h->stream)) != hipSuccess) return e;
+    if ((e = prof.mark(0, h->stream)) != hipSuccess) return e;
     if ((e = rcw_launch_cast(h->dev, actions_dev, mask_dev, h->stream)) != hipSuccess) return e;
-    if (!mask_dev) h->cols_stale = false;
-    if (prof && (e = hipEventRecord(ev[1].get(), h->stream)) != hipSuccess) return e;
+    h->step.columns_cast(mask_dev != nullptr);
+    if ((e = prof.mark(1, h->stream)) != hipSuccess) return e;
     if (h->dev.top_view && (e = launch_top_view(h, mask_dev, false, [](hipStream_t) { return hipSuccess; })) != hipSuccess) return e;
-    if (prof && (e = hipEventRecord(ev[2].get(), h->stream)) != hipSuccess) return e;
+    if ((e = prof.mark(2, h->stream)) != hipSuccess) return e;
     if ((e = launch_view(h, mask_dev, op)) != hipSuccess) return e;
-    if (prof) { if ((e = hipEventRecord(ev[3].get(), h->stream)) != hipSuccess) return e; h->prof_count++; }
-    return hipSuccess;
+    return prof.done(h->stream);
 }
 
 // Every stream that may hold work of the handle — the side stream, its own, the caller's current one — is waited for; the first failure comes back.
@@ -617,6 +684,11 @@ int top_view_rule(RcwPlan& d, const rcw_config* cfg, size_t B, const RcwHw& hw, 
     return RCW_OK;
 }
 
+// the RCW_TOP_VIEW_* name of the form a plan takes inside a step, and of rcw_update_top_view alone
+int top_form_alone(const RcwPlan& d, bool split) { return !d.top_view ? RCW_TOP_VIEW_NONE : split ? RCW_TOP_VIEW_TWO_KERNELS : d.top_lds ? RCW_TOP_VIEW_ONE_KERNEL : RCW_TOP_VIEW_IN_PLACE; }
+int top_form_alone(const RcwPlan& d) { return top_form_alone(d, d.top_split && d.top_alone_split); }
+int top_form_in_step(const RcwPlan& d) { return top_form_alone(d, d.top_split != 0); }
+
 // Which form update_top_view! (SR:446-483) takes for this handle (top_view_rule), and its scratch in HBM.
 int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient)
 {
@@ -641,7 +713,7 @@ int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient)
         if (e == hipSuccess && !h->top_stream.get()) e = h->top_stream.hipStreamCreate();
         if (e == hipSuccess && !h->ev_top_fork.get()) e = h->ev_top_fork.hipEventCreate(hipEventDisableTiming);
         for (RcwEvent& q : h->ev_top_join) if (e == hipSuccess && !q.get()) e = q.hipEventCreate(hipEventDisableTiming);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "top view planes: %s", hip_failure(e));
+        if (e != hipSuccess) return fail(hip_code(e), "top view planes: %s", hip_failure(e));
         d.top_plane = h->d_top_plane.get<uint32_t>(); d.top_hdr = h->d_top_hdr.get<int2>(); d.top_codes = h->d_top_codes.get<uint2>();
     }
     hipError_t e = rcw_prepare_top_view(d, h->device);
@@ -669,32 +741,21 @@ bool step_one_launch_pays(const RcwDev& d)
 // form is taken; the caller primes them (launch_step without an action).
 int plan_step_form(rcw_handle* h, int want)
 {
-    RcwPlan& d = h->dev;
-    const bool eligible = rcw_step_spec_eligible(d) != 0;
-    if (h->learner.only()) {                           // (the cast kernel followed by the view kernel: no camera fill to fuse)
-        if (want == RCW_STEP_ONE_LAUNCH) return fail(RCW_ERR_UNSUPPORTED, "the handle's learner view is set with RCW_VIEW_ONLY: a step is the cast kernel and the view kernel");
-        h->spec_on = 0; spec_forget(h); h->step_form_want = want;
-        return RCW_OK;
+    const RcwPlan& d = h->dev;
+    rcw_handle::Step& st = h->step;
+    const StepFacts::Plan p = st.plan(want, h->learner.only(), rcw_step_spec_eligible(d) != 0, step_one_launch_pays(d));
+    if (p.refused) return fail(RCW_ERR_UNSUPPORTED, "%s", p.refused);
+    for (RcwBuf& q : st.slot) {
+        if (!p.on || q.get()) continue;
+        const hipError_t e = q.hipMalloc(rcw_step_spec_slot_bytes(d));
+        if (e != hipSuccess) return fail(hip_code(e), "one-launch step, slot buffers: %s", hip_failure(e));
     }
-    if (want == RCW_STEP_ONE_LAUNCH && !eligible)
-        return fail(RCW_ERR_UNSUPPORTED, "this handle does not take the one-launch step (a camera view of 256 k, 128 or 64 rows — up to 8191 — without a top view, fewer than 2^29 view columns)");
-    const bool on = want == RCW_STEP_TWO_LAUNCHES ? false : (want == RCW_STEP_ONE_LAUNCH ? true : eligible && !h->step_captured && step_one_launch_pays(d));
-    if (on) {
-        for (int k = 0; k < 2; ++k) {
-            if (h->d_spec[k].get()) continue;
-            const hipError_t e = h->d_spec[k].hipMalloc(rcw_step_spec_slot_bytes(d));
-            if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "one-launch step, slot buffers: %s", hip_failure(e));
-        }
-        if (want == RCW_STEP_ONE_LAUNCH) h->step_captured = false;
-    }
-    if (on != (h->spec_on != 0)) spec_forget(h);                    // (a change of form, either way)
-    h->spec_on = on ? 1 : 0;
-    h->step_form_want = want;
+    st.take(p);
     return RCW_OK;
 }
 
 #ifdef RCW_DEV_SWITCHES
-#include "dev/api_plan_export.inc"   // rcw_dev_plan_top_view / rcw_dev_top_view_rules / rcw_dev_step_rule: the rules without a device (tests/test_top_view_plan.py)
+#include "dev/api_plan_export.inc"   // the rules and the step's facts without a device (tests/test_top_view_plan.py, tests/test_step_state.py)
 #endif
 
 int validate_config(const rcw_config* c, int32_t batch)
@@ -749,13 +810,13 @@ int validate_config(const rcw_config* c, int32_t batch)
     return RCW_OK;
 }
 
-// The descriptors of the current frames, where the one-launch step left them stale (rcw_handle::cols_live): cast_rays! SR:195-231 on the
+// The descriptors of the current frames, where the one-launch step left them stale (StepFacts::cols_live): cast_rays! SR:195-231 on the
 // current state, no action — the cast kernel, stream-ordered in front of the reader.
 int ensure_columns(rcw_handle* h)
 {
-    if (!h->cols_stale) return RCW_OK;
+    if (!h->step.cols_stale()) return RCW_OK;
     RCW_HIP(rcw_launch_cast(h->dev, nullptr, nullptr, h->stream));
-    h->cols_stale = false;
+    h->step.columns_cast();
     return RCW_OK;
 }
 
@@ -778,6 +839,23 @@ int check_real(rcw_handle* h, bool want64, const char* fn)
     if (h->real64 == want64) return RCW_OK;
     return fail(RCW_ERR_UNSUPPORTED, "%s: the handle's world-unit type is %s; use the %s entry point", fn,
                 h->real64 ? "Float64" : "Float32", h->real64 ? "*64" : "Float32");
+}
+
+// agents [first, first + count) of the handle, count >= min_count (`ok`: what else the caller refuses with the same words — a NULL output pointer)
+int check_range(rcw_handle* h, bool ok, int32_t first, int32_t count, int32_t min_count = 0)
+{
+    if (ok && first >= 0 && count >= min_count && first + (int64_t)count <= h->B) return RCW_OK;
+    return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
+}
+
+// rcw_ray_table / rcw_direction_table and their *64 twins: the host's copy of a table, as uploaded
+template <typename T>
+int table_out(rcw_handle* h, T* out, std::vector<T> rcw_handle::*table, const char* fn)
+{
+    if (!h || !out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = check_real(h, sizeof(T) == sizeof(double), fn); if (rc) return rc;
+    std::memcpy(out, (h->*table).data(), (h->*table).size() * sizeof(T));
+    return RCW_OK;
 }
 
 int check_handle(rcw_handle* h)
@@ -1055,7 +1133,7 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     }
     if (rcw_step_lds_bytes(d) > 64 * 1024)
         return fail(RCW_ERR_UNSUPPORTED, "tile map + column buffer need %zu B of LDS (> 64 KiB)", rcw_step_lds_bytes(d));
-    if (const char* v = RCW_DEV_ENV("RCW_STEP_STORE_ALL")) h->step_store_all = std::atoi(v) != 0;
+    if (const char* v = RCW_DEV_ENV("RCW_STEP_STORE_ALL")) h->step.set_store_all(std::atoi(v) != 0);
     {
         int want = 0;
         if (const char* v = RCW_DEV_ENV("RCW_STEP_FORM")) { const int f = std::atoi(v); if (f == RCW_STEP_TWO_LAUNCHES) want = f; }
@@ -1137,7 +1215,7 @@ int rcw_bind_obs(rcw_handle* h, void* device_ptr)
     // No synchronisation: the pointer travels in the kernel arguments of the launches that follow,
     // work already enqueued keeps the buffer it was launched with (double-buffered observations).
     h->dev.obs = device_ptr ? (uint32_t*)device_ptr : h->d_obs.get<uint32_t>();
-    obs_unknown(h);      // (also with the pointer it had: the caller may have written into the buffer — the next step stores every frame)
+    h->step.obs_unknown();      // (also with the pointer it had: the caller may have written into the buffer — the next step stores every frame)
     return RCW_OK;
 }
 
@@ -1146,10 +1224,7 @@ int rcw_reset(rcw_handle* h, const uint8_t* mask_host, uint64_t seed)
     int rc = check_handle(h); if (rc) return rc;
     const uint8_t* mask_dev = nullptr;
     rc = upload_mask(h, mask_host, &mask_dev); if (rc) return rc;
-    // (the seed is the HANDLE's: an agent that is done under auto_reset and NOT in the mask is re-sampled by its next action with the new
-    // seed — but the one-launch step has already cast that agent's successors from a preview drawn with the old one: every agent's slots are
-    // cast again by the next step, as a launch of its own)
-    if (seed != h->dev.seed && h->dev.auto_reset && mask_dev) spec_forget(h);
+    h->step.reset(mask_dev != nullptr, seed != h->dev.seed, h->dev.auto_reset != 0);
     h->dev.seed = seed;
     RCW_HIP(rcw_launch_reset(h->dev, mask_dev, h->stream));            // SR:110-132
     RCW_HIP(launch_step(h, nullptr, mask_dev, kStackRefill));    // SR:134, SR:329
@@ -1235,17 +1310,17 @@ int rcw_cast_rays(rcw_handle* h)
 {
     int rc = check_handle(h); if (rc) return rc;
     RCW_HIP(rcw_launch_cast(h->dev, nullptr, nullptr, h->stream));   // no action: rays + descriptors only
-    h->cols_stale = false;
+    h->step.columns_cast();
     return RCW_OK;
 }
 
 int rcw_update_camera_view(rcw_handle* h)
 {
     int rc = check_handle(h); if (rc) return rc;
-    obs_unknown(h);
+    h->step.obs_unknown();
     rc = ensure_columns(h); if (rc) return rc;
-    RCW_HIP(rcw_launch_fill(h->dev, h->dev.col_h, h->dev.col_c, h->dev.obs, (long long)h->dev.B * h->dev.N, nullptr, h->stream));
-    if (h->spec_on && h->spec_primed) obs_is_current(h);            // every agent's current frame, which is what slot 0 of the primed slots holds
+    RCW_HIP(paint_camera(h, nullptr, h->stream));
+    h->step.camera_repainted();
     return RCW_OK;
 }
 
@@ -1282,8 +1357,7 @@ int rcw_obs_device_ptr(rcw_handle* h, void** device_ptr)
 int rcw_obs_copy(rcw_handle* h, uint32_t* out_host, int32_t first, int32_t count)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (!out_host || first < 0 || count < 0 || first + (int64_t)count > h->B)
-        return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
+    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
     rc = sync_and_check(h);
     const size_t frame = (size_t)h->cfg.num_rays * h->cfg.height_camera_view_pu;
     RCW_HIP(hipMemcpy(out_host, h->dev.obs + (size_t)first * frame, (size_t)count * frame * sizeof(uint32_t),
@@ -1303,8 +1377,7 @@ int rcw_top_view_copy(rcw_handle* h, uint32_t* out_host, int32_t first, int32_t 
 {
     int rc = check_handle(h); if (rc) return rc;
     if (!h->d_top_view.get()) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
-    if (!out_host || first < 0 || count < 0 || first + (int64_t)count > h->B)
-        return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
+    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
     rc = sync_and_check(h);
     const size_t frame = (size_t)h->cfg.height_tile_map_tu * h->cfg.width_tile_map_tu * h->cfg.pu_per_tu * h->cfg.pu_per_tu;
     RCW_HIP(hipMemcpy(out_host, h->d_top_view.get<uint32_t>() + (size_t)first * frame, (size_t)count * frame * sizeof(uint32_t),
@@ -1377,8 +1450,7 @@ template <typename T>
 int rays_impl(rcw_handle* h, int32_t first, int32_t count, int64_t* stop_ij, int64_t* hit_dimension,
               T* distance_wu, T* directions_wu)
 {
-    if (first < 0 || count < 1 || first + (int64_t)count > h->B)
-        return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
+    int rc = check_range(h, true, first, count, 1); if (rc) return rc;
     const size_t n = (size_t)count * h->cfg.num_rays;
     RcwRayOut out{};
     // device scratch lives in the handle and only ever grows: no hipMalloc/hipFree per call
@@ -1422,8 +1494,7 @@ int rcw_rays64(rcw_handle* h, int32_t first, int32_t count, int64_t* stop_ij, in
 int rcw_columns(rcw_handle* h, int32_t first, int32_t count, int32_t* height_line_pu, uint8_t* colour_id)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (first < 0 || count < 0 || first + (int64_t)count > h->B)
-        return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
+    rc = check_range(h, true, first, count); if (rc) return rc;
     rc = ensure_columns(h); if (rc) return rc;
     rc = sync_and_check(h);
     const size_t N = (size_t)h->cfg.num_rays;
@@ -1439,7 +1510,7 @@ int rcw_columns_device_ptr(rcw_handle* h, void** height_line_pu, void** colour_i
     if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL handle");
     {   // from now on every step refreshes the descriptors (the caller reads them through the pointers, behind the library's back)
         int rc = check_handle(h); if (rc) return rc;
-        h->cols_live = true;
+        h->step.columns_wanted();
         rc = ensure_columns(h); if (rc) return rc;
     }
     if (height_line_pu) *height_line_pu = h->d_col_h.get();
@@ -1529,7 +1600,7 @@ int rcw_set_learner_view_stack(rcw_handle* h, int32_t format, int32_t layout, in
         if (e == hipSuccess && frames > 1) e = fresh.stack.hipMalloc(bytes * (size_t)frames);
         if (e == hipSuccess && frames > 1) e = fresh.last_episode.hipMalloc((size_t)h->B * sizeof(uint32_t));
         if (e != hipSuccess)                                       // the handle keeps its previous view
-            return fail(e == hipErrorOutOfMemory ? RCW_ERR_OUT_OF_MEMORY : RCW_ERR_HIP, "learner view buffer of %zu bytes: %s", bytes * (size_t)frames, hip_failure(e));
+            return fail(hip_code(e), "learner view buffer of %zu bytes: %s", bytes * (size_t)frames, hip_failure(e));
         fresh.view.rows = fresh.tab.get<int32_t>();
         fresh.view.cols = fresh.tab.get<int32_t>() + height + 1;
     }
@@ -1538,16 +1609,15 @@ int rcw_set_learner_view_stack(rcw_handle* h, int32_t format, int32_t layout, in
     lv.view = fresh.view;
     if (lv.on()) {
         // the view kernel reads the descriptors: every step of the handle refreshes them from now on (as for rcw_columns_device_ptr)
-        h->cols_live = true;
+        h->step.columns_wanted();
         rc = ensure_columns(h); if (rc) return rc;
     }
     if (lv.only()) {                                              // (a caller's one-launch request gives way: the step has no camera fill)
-        if (h->step_form_want == RCW_STEP_ONE_LAUNCH) h->step_form_want = 0;
-        rc = plan_step_form(h, h->step_form_want); if (rc) return rc;
+        rc = plan_step_form(h, h->step.want() == RCW_STEP_ONE_LAUNCH ? 0 : h->step.want()); if (rc) return rc;
     }
     else if (was_only) {                                          // back to the camera view in the step: its form by the rule, its frames now
-        rc = plan_step_form(h, h->step_form_want); if (rc) return rc;
-        RCW_HIP(rcw_launch_fill(h->dev, h->dev.col_h, h->dev.col_c, h->dev.obs, (long long)h->dev.B * h->dev.N, nullptr, h->stream));
+        rc = plan_step_form(h, h->step.want()); if (rc) return rc;
+        RCW_HIP(paint_camera(h, nullptr, h->stream));
     }
     if (lv.on()) RCW_HIP(launch_view(h, nullptr, kStackRefill));
     return RCW_OK;
@@ -1580,8 +1650,7 @@ int rcw_learner_view_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32
 {
     int rc = check_handle(h); if (rc) return rc;
     if (!h->learner.on()) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
-    if (!out_host || first < 0 || count < 0 || first + (int64_t)count > h->B)
-        return fail(RCW_ERR_INVALID_ARGUMENT, "bad agent range [%d, %d)", first, first + count);
+    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
     rc = sync_and_check(h);
     const size_t per = h->learner.agent_bytes();
     RCW_HIP(hipMemcpy(out_host, h->learner.batch() + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
@@ -1707,34 +1776,10 @@ int rcw_memcpy_to_host(rcw_handle* h, void* dst_host, const void* src_device, ui
     return rc;
 }
 
-int rcw_ray_table(rcw_handle* h, float* out)
-{
-    if (!h || !out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = check_real(h, false, "rcw_ray_table"); if (rc) return rc;
-    std::memcpy(out, h->ray_table.data(), h->ray_table.size() * sizeof(float));
-    return RCW_OK;
-}
-int rcw_direction_table(rcw_handle* h, float* out)
-{
-    if (!h || !out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = check_real(h, false, "rcw_direction_table"); if (rc) return rc;
-    std::memcpy(out, h->dir_table.data(), h->dir_table.size() * sizeof(float));
-    return RCW_OK;
-}
-int rcw_ray_table64(rcw_handle* h, double* out)
-{
-    if (!h || !out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = check_real(h, true, "rcw_ray_table64"); if (rc) return rc;
-    std::memcpy(out, h->ray_table64.data(), h->ray_table64.size() * sizeof(double));
-    return RCW_OK;
-}
-int rcw_direction_table64(rcw_handle* h, double* out)
-{
-    if (!h || !out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = check_real(h, true, "rcw_direction_table64"); if (rc) return rc;
-    std::memcpy(out, h->dir_table64.data(), h->dir_table64.size() * sizeof(double));
-    return RCW_OK;
-}
+int rcw_ray_table(rcw_handle* h, float* out) { return table_out(h, out, &rcw_handle::ray_table, "rcw_ray_table"); }
+int rcw_direction_table(rcw_handle* h, float* out) { return table_out(h, out, &rcw_handle::dir_table, "rcw_direction_table"); }
+int rcw_ray_table64(rcw_handle* h, double* out) { return table_out(h, out, &rcw_handle::ray_table64, "rcw_ray_table64"); }
+int rcw_direction_table64(rcw_handle* h, double* out) { return table_out(h, out, &rcw_handle::dir_table64, "rcw_direction_table64"); }
 
 int rcw_timer_start(rcw_handle* h)
 {
@@ -1756,12 +1801,13 @@ int rcw_profile(rcw_handle* h, int32_t enable)
 {
     int rc = check_handle(h); if (rc) return rc;
     RCW_HIP(hipStreamSynchronize(h->stream));
-    if (enable && h->prof_ev.empty()) {
-        h->prof_ev.resize(4 * kProfileSlots);
-        for (RcwEvent& ev : h->prof_ev) RCW_HIP(ev.hipEventCreate());
+    rcw_handle::Profile& p = h->prof;
+    if (enable && p.ev.empty()) {
+        p.ev.resize(4 * p.kSlots);
+        for (RcwEvent& ev : p.ev) RCW_HIP(ev.hipEventCreate());
     }
-    h->profiling = enable != 0;
-    h->prof_count = 0;
+    p.on = enable != 0;
+    p.count = 0;
     return RCW_OK;
 }
 
@@ -1771,34 +1817,33 @@ int rcw_profile_read(rcw_handle* h, float* cast_ms, float* top_view_ms, float* f
     if (!cast_ms || !top_view_ms || !fill_ms || !steps) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
     RCW_HIP(hipStreamSynchronize(h->stream));
     double c = 0.0, t = 0.0, f = 0.0;
-    for (int k = 0; k < h->prof_count; ++k) {
+    const rcw_handle::Profile& p = h->prof;
+    for (int k = 0; k < p.count; ++k) {
         float a = 0.0f, b = 0.0f, d = 0.0f;
-        RCW_HIP(hipEventElapsedTime(&a, h->prof_ev[4 * k].get(), h->prof_ev[4 * k + 1].get()));
-        RCW_HIP(hipEventElapsedTime(&b, h->prof_ev[4 * k + 1].get(), h->prof_ev[4 * k + 2].get()));
-        RCW_HIP(hipEventElapsedTime(&d, h->prof_ev[4 * k + 2].get(), h->prof_ev[4 * k + 3].get()));
+        RCW_HIP(hipEventElapsedTime(&a, p.ev[4 * k].get(), p.ev[4 * k + 1].get()));
+        RCW_HIP(hipEventElapsedTime(&b, p.ev[4 * k + 1].get(), p.ev[4 * k + 2].get()));
+        RCW_HIP(hipEventElapsedTime(&d, p.ev[4 * k + 2].get(), p.ev[4 * k + 3].get()));
         c += a;
         if (h->dev.top_split) { f += b; t += d; } else { t += b; f += d; }      // two-kernel top view: cast | fill (+ draw beside it) | store
     }
-    *steps = h->prof_count;
-    *cast_ms = h->prof_count ? (float)(c / h->prof_count) : 0.0f;
-    *top_view_ms = h->prof_count && h->dev.top_view ? (float)(t / h->prof_count) : 0.0f;
-    *fill_ms = h->prof_count ? (float)(f / h->prof_count) : 0.0f;
+    *steps = p.count;
+    *cast_ms = p.count ? (float)(c / p.count) : 0.0f;
+    *top_view_ms = p.count && h->dev.top_view ? (float)(t / p.count) : 0.0f;
+    *fill_ms = p.count ? (float)(f / p.count) : 0.0f;
     return RCW_OK;
 }
 
 int rcw_top_view_form(rcw_handle* h, int32_t* form)
 {
     if (!h || !form) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    const RcwPlan& d = h->dev;
-    *form = !d.top_view ? RCW_TOP_VIEW_NONE : d.top_split ? RCW_TOP_VIEW_TWO_KERNELS : d.top_lds ? RCW_TOP_VIEW_ONE_KERNEL : RCW_TOP_VIEW_IN_PLACE;
+    *form = top_form_in_step(h->dev);
     return RCW_OK;
 }
 
 int rcw_update_top_view_form(rcw_handle* h, int32_t* form)
 {
     if (!h || !form) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    const RcwPlan& d = h->dev;
-    *form = !d.top_view ? RCW_TOP_VIEW_NONE : (d.top_split && d.top_alone_split) ? RCW_TOP_VIEW_TWO_KERNELS : d.top_lds ? RCW_TOP_VIEW_ONE_KERNEL : RCW_TOP_VIEW_IN_PLACE;
+    *form = top_form_alone(h->dev);
     return RCW_OK;
 }
 
@@ -1820,7 +1865,7 @@ int rcw_set_top_view_form(rcw_handle* h, int32_t form, int32_t runs)
 int rcw_step_form(rcw_handle* h, int32_t* form)
 {
     if (!h || !form) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    *form = h->spec_on ? RCW_STEP_ONE_LAUNCH : RCW_STEP_TWO_LAUNCHES;
+    *form = h->step.on() ? RCW_STEP_ONE_LAUNCH : RCW_STEP_TWO_LAUNCHES;
     return RCW_OK;
 }
 
@@ -1829,16 +1874,16 @@ int rcw_set_step_form(rcw_handle* h, int32_t form)
     int rc = check_handle(h); if (rc) return rc;
     if (form != 0 && form != RCW_STEP_TWO_LAUNCHES && form != RCW_STEP_ONE_LAUNCH)
         return fail(RCW_ERR_INVALID_ARGUMENT, "form must be 0 (automatic) or RCW_STEP_TWO_LAUNCHES / RCW_STEP_ONE_LAUNCH (got %d)", form);
-    const bool was_on = h->spec_on != 0;
+    const bool was_on = h->step.on();
     rc = plan_step_form(h, form); if (rc) return rc;
-    if (h->spec_on && !was_on) RCW_HIP(launch_step(h, nullptr, nullptr, kStackKeep));   // prime the slots (re-renders the current frames: the same pixels)
+    if (h->step.on() && !was_on) RCW_HIP(launch_step(h, nullptr, nullptr, kStackKeep));   // prime the slots (re-renders the current frames: the same pixels)
     return RCW_OK;
 }
 
 int rcw_fill_kernel_name(rcw_handle* h, char* buf, int32_t buflen)
 {
     if (!h || !buf || buflen < 1) return fail(RCW_ERR_INVALID_ARGUMENT, "bad argument");
-    std::snprintf(buf, (size_t)buflen, "%s", h->spec_on ? (h->dev.Hc == 256 ? "rcw_fill256_cast_kernel" : "rcw_fill_window_cast_kernel") : rcw_fill_kernel_name(h->dev, (long long)h->dev.B * h->dev.N));
+    std::snprintf(buf, (size_t)buflen, "%s", h->step.on() ? (h->dev.Hc == 256 ? "rcw_fill256_cast_kernel" : "rcw_fill_window_cast_kernel") : rcw_fill_kernel_name(h->dev, (long long)h->dev.B * h->dev.N));
     return RCW_OK;
 }
 

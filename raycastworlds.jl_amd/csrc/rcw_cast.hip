@@ -462,7 +462,7 @@ template <bool PLAIN>
 __device__ __forceinline__ void fill256_spec_body(const RcwDev& p, const uint8_t* __restrict__ actions, const uint16_t* __restrict__ slots,
                                                   u32x4* __restrict__ out, long long total_cols, int block, int blocks, int n_shift, uint32_t keep)
 {
-    // keep = 1: the observation buffer holds every agent's CURRENT frame (the handle says so: rcw_api.hip, obs_current) — the chunks of an
+    // keep = 1: the observation buffer holds every agent's CURRENT frame (the handle says so: rcw_api.hip, StepFacts::obs_current) — the chunks of an
     // agent whose selected successor frame equals it (the casting half's byte behind the slots) are not stored again; 0: every pixel is written.
     const uint8_t* const same = reinterpret_cast<const uint8_t*>(slots + (size_t)5 * (size_t)p.B * (size_t)p.N);
     // (Raising the fill wavefronts' priority over the casting ones — s_setprio 3 — changes nothing: what the casting half costs this

@@ -101,10 +101,10 @@ def test_shipped_library_reads_no_development_switch(rcw):
         assert not retired_switches & set(dev)
         dev_bytes = open(_capi.DEV_LIB_PATH, "rb").read()
         assert not [k for k in retired_kernels if k in dev_bytes]
-        # the development build exports the same ABI, and the rules without a device (tests/test_top_view_plan.py)
+        # the development build exports the same ABI, and the rules and the step's facts without a device (tests/test_top_view_plan.py, tests/test_step_state.py)
         lib = C.CDLL(_capi.DEV_LIB_PATH)
         assert not [n for n in _declared() if not hasattr(lib, n)]
-        assert hasattr(lib, "rcw_dev_plan_top_view")
+        assert hasattr(lib, "rcw_dev_plan_top_view") and hasattr(lib, "rcw_dev_step_facts")
 
 
 def test_every_entry_point_refuses_a_null_handle(rcw):
