@@ -278,6 +278,44 @@ RCW_API int rcw_reward_typed(rcw_handle* h, void* out_host /* (B) of R */);
 RCW_API int rcw_done(rcw_handle* h, uint8_t* out_host /* (B) */);
 RCW_API int rcw_reward_device_ptr(rcw_handle* h, void** device_ptr);
 RCW_API int rcw_done_device_ptr(rcw_handle* h, void** device_ptr);
+/* ---- the episode time limit (this build's addition: the reference has none) ----------------------------------------------
+ * SingleRoom ends an episode at the goal only.  rcw_set_time_limit puts the limit almost every RL loop wants around it where `done` is
+ * decided, on the device, at no host synchronisation.  State: episode_steps (UInt32 (B)) and truncated (UInt8 (B), 0/1), allocated by
+ * rcw_create and zero there; their device pointers are stable for the handle's lifetime.  The ABI is additive: RCW_ABI_VERSION and
+ * rcw_config are what they were.
+ *   rcw_set_time_limit(h, L)   L = 0: no limit (the default, the reference's behaviour); L > 0: the limit; L < 0:
+ *                              RCW_ERR_INVALID_ARGUMENT.  Every call — stream-ordered — zeroes every agent's episode_steps and truncated
+ *                              (the limit counts from the call) and makes the one-launch step cast every agent's successors again, as a
+ *                              change of the step's form does (they were cast under the old limit).  The step's form, the observation
+ *                              and every other state stay as they are.
+ *   rcw_time_limit             the current L.
+ *   rcw_episode_steps / rcw_truncated                 host copies; they wait for the stream, like rcw_done.
+ *   rcw_episode_steps_device_ptr / rcw_truncated_device_ptr   the arrays where they live, rewritten by steps in stream order.
+ * While L > 0, rcw_step / rcw_step_device do for each agent, in this order:
+ *   1  invalid device action   the agent is not stepped (rcw_step_device): episode_steps and truncated keep their values, and the
+ *                              agent is not restarted even if it is done or truncated.
+ *   2  restart                 under cfg.auto_reset an agent whose `done` OR `truncated` is set is re-sampled by this call exactly as a
+ *                              done agent is: the action is ignored, reset!(world) runs with the handle's seed, the episode counter
+ *                              (rcw_episode) goes up by one, reward 0, done false — and episode_steps = 0, truncated = 0.
+ *   3  ordinary step           act! as ever.  If it raised (RCW_OOB_ERROR: the agent is left exactly as it was) the two words stay too.
+ *                              Otherwise episode_steps += 1 — a blocked move and the step that reaches the goal count —, then
+ *                              truncated = (episode_steps >= L && !done): termination wins on the step where both happen.
+ *                              Without cfg.auto_reset nothing restarts: the counter keeps counting and the flag is recomputed by every
+ *                              step, as the reference's `done` is.
+ * So truncated == (episode_steps >= L && !done) after every call while L > 0; episode_steps at the done / truncated step is the
+ * episode's length.  rcw_reset and rcw_set_state / rcw_set_state64 zero both words of the agents in their mask and leave the others';
+ * rcw_cast_rays, rcw_update_camera_view, rcw_update_top_view, rcw_set_direction_table*, rcw_set_step_form, the learner-view calls and
+ * every getter do not touch them.  With L = 0 steps neither read nor write the two arrays (they run the kernels they ran before the
+ * limit existed): both stay zero.  What follows without more: the learner view's frame stack refills on a truncation restart (the
+ * episode counter moved); a replayed HIP graph of a step counts and truncates like any step (nothing about the limit lives on the
+ * host but L, which the kernels read as an argument) — and therefore keeps the L it was CAPTURED with: capture again after
+ * rcw_set_time_limit. */
+RCW_API int rcw_set_time_limit(rcw_handle* h, int32_t max_episode_steps);
+RCW_API int rcw_time_limit(rcw_handle* h, int32_t* out);
+RCW_API int rcw_episode_steps(rcw_handle* h, uint32_t* out_host /* (B) */);
+RCW_API int rcw_truncated(rcw_handle* h, uint8_t* out_host /* (B) */);
+RCW_API int rcw_episode_steps_device_ptr(rcw_handle* h, void** device_ptr);
+RCW_API int rcw_truncated_device_ptr(rcw_handle* h, void** device_ptr);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

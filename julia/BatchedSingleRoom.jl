@@ -319,6 +319,42 @@ function episode(env::BatchedSingleRoom)
     out = Vector{UInt32}(undef, env.batch)
     check(ccall((:rcw_episode, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt32}), env.handle, out)); out
 end
+# ---- the episode time limit (this build's addition; include/rcw.h, rcw_set_time_limit) ----------------------------------------
+"""
+    set_time_limit!(env, max_episode_steps)
+
+An episode ends after `max_episode_steps` calls of `act!` without the goal: that step sets `truncated`, and with `auto_reset`
+the next action restarts the agent as it restarts a done one.  `0` switches the limit off (the default, the reference's
+behaviour).  Decided on the device; every call zeroes `episode_steps` and `truncated` of every agent.
+"""
+function set_time_limit!(env::BatchedSingleRoom, max_episode_steps::Integer)
+    check(ccall((:rcw_set_time_limit, librcw), Cint, (Ptr{Cvoid}, Int32), env.handle, max_episode_steps))
+    return nothing
+end
+function time_limit(env::BatchedSingleRoom)
+    n = Ref{Int32}(0)
+    check(ccall((:rcw_time_limit, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}), env.handle, n)); Int(n[])
+end
+function episode_steps(env::BatchedSingleRoom)
+    out = Vector{UInt32}(undef, env.batch)
+    check(ccall((:rcw_episode_steps, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt32}), env.handle, out)); out
+end
+function truncated(env::BatchedSingleRoom)
+    out = Vector{UInt8}(undef, env.batch)
+    check(ccall((:rcw_truncated, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}), env.handle, out)); out .!= 0
+end
+function episode_steps_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_episode_steps_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
+function truncated_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_truncated_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
+# (no RLBase verb in the reference; the device form mirrors is_terminated_device)
+is_truncated(env::RCW.RLBaseEnv{E}) where {E <: BatchedSingleRoom} = truncated(env.env)
+is_truncated_device(env::BatchedSingleRoom) = (ptr = truncated_device_ptr(env), eltype = UInt8, dims = (env.batch,))
+
 # per-agent sticky status: 0, -5 where the reference would have raised BoundsError, -2 for an invalid device action,
 # 1 (a warning) where sample_empty_position gave up after max_tries and returned an occupied tile (utils.jl:34 @warns there)
 function status(env::BatchedSingleRoom)

@@ -121,6 +121,12 @@ SIGNATURES = {
     "rcw_done": [_vp, _vp],
     "rcw_reward_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_done_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_set_time_limit": [_vp, _i32],
+    "rcw_time_limit": [_vp, C.POINTER(_i32)],
+    "rcw_episode_steps": [_vp, _vp],
+    "rcw_truncated": [_vp, _vp],
+    "rcw_episode_steps_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_truncated_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_position": [_vp, _vp],
     "rcw_direction": [_vp, _vp],
     "rcw_goal": [_vp, _vp],

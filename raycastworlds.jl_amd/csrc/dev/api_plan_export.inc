@@ -51,7 +51,7 @@ __attribute__((visibility("default"))) int rcw_dev_step_rule(const rcw_config* c
 //   2  a RCW_VIEW_ONLY step (launch_step); a: bit 1 a mask             3  rcw_bind_obs
 //   4  rcw_reset in front of its render; a: bit 0 a mask, bit 1 a seed that is not the handle's, bit 2 cfg.auto_reset
 //   5  rcw_cast_rays, or ensure_columns in front of a reader           6  rcw_columns_device_ptr / a learner view switched on
-//   7  rcw_update_camera_view
+//   7  rcw_update_camera_view                                         8  rcw_set_time_limit
 __attribute__((visibility("default"))) int rcw_dev_step_facts(int32_t eligible, int32_t pays, int32_t store_all, const int32_t* events, int32_t n, int32_t* out)
 {
     if (!events || !out || n < 0) return RCW_ERR_INVALID_ARGUMENT;
@@ -77,6 +77,7 @@ __attribute__((visibility("default"))) int rcw_dev_step_facts(int32_t eligible, 
         else if (kind == 5) f.columns_cast();
         else if (kind == 6) { f.columns_wanted(); f.columns_cast(); }
         else if (kind == 7) { f.obs_unknown(); f.columns_cast(); f.camera_repainted(); }
+        else if (kind == 8) f.time_limit_set();
         else return RCW_ERR_INVALID_ARGUMENT;
         f.read(o);
     }

@@ -145,6 +145,9 @@ public:
     void reset(bool masked, bool new_seed, bool auto_reset) { if (masked && new_seed && auto_reset) forget(); }
     void columns_cast(bool masked = false) { if (!masked) cols_stale_ = false; }   // the cast kernel was queued: rcw_cast_rays, ensure_columns, a RCW_VIEW_ONLY step
     void columns_wanted() { cols_live_ = true; }                 // rcw_columns_device_ptr, a learner view switched on: every step refreshes the descriptors
+    // rcw_set_time_limit: the slots were cast under the old limit (which agents the next action re-samples, whose successors are therefore a
+    // preview's) — every agent's are cast again by the next step, as a launch of its own
+    void time_limit_set() { forget(); }
 };
 
 // OWNERSHIP: every device buffer, pinned buffer, stream and event of a handle is a member of one of rcw_owned.h's types; nothing else frees
@@ -159,7 +162,7 @@ struct rcw_handle {
     hipStream_t stream = nullptr;      // the caller's (rcw_set_stream) or own_stream: not owned
     RcwEvent ev_start, ev_stop;
     // device allocations
-    RcwBuf d_pos, d_dir, d_goal, d_reward, d_done, d_episode, d_tile_map, d_dir_table, d_ray_table, d_obs, d_col_h, d_col_c, d_err, d_status, d_top_view;
+    RcwBuf d_pos, d_dir, d_goal, d_reward, d_done, d_episode, d_episode_steps, d_truncated, d_tile_map, d_dir_table, d_ray_table, d_obs, d_col_h, d_col_c, d_err, d_status, d_top_view;
     // two-kernel top view: planes / player pixels / tile codes in HBM, the side stream the draw kernel runs on
     RcwBuf d_top_plane, d_top_hdr, d_top_codes;
     // Several draw workgroups an agent (top_parts > 1) OR their bits into the agent's plane in HBM, and only rcw_top_store_kernel — which reads
@@ -1047,6 +1050,8 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     RCW_HIP(h->d_reward.hipMalloc(B * h->reward_size));
     RCW_HIP(h->d_done.hipMalloc(B));
     RCW_HIP(h->d_episode.hipMalloc(B * sizeof(uint32_t)));
+    RCW_HIP(h->d_episode_steps.hipMalloc(B * sizeof(uint32_t)));
+    RCW_HIP(h->d_truncated.hipMalloc(B));
     RCW_HIP(h->d_tile_map.hipMalloc(B * (size_t)h->nchunks * sizeof(uint64_t) + 16));   // (+ 2 words: the flat top store kernel reads three words from any word of a map)
     RCW_HIP(h->d_dir_table.hipMalloc((size_t)nd * 2 * h->real_size));
     RCW_HIP(h->d_ray_table.hipMalloc((size_t)nd * RCW_TABLE_ROWS * N * h->real_size));
@@ -1069,6 +1074,8 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     }
     RCW_HIP(hipMemsetAsync(h->d_err.get(), 0, sizeof(int32_t), h->stream));
     RCW_HIP(hipMemsetAsync(h->d_status.get(), 0, B * sizeof(int32_t), h->stream));
+    RCW_HIP(hipMemsetAsync(h->d_episode_steps.get(), 0, B * sizeof(uint32_t), h->stream));
+    RCW_HIP(hipMemsetAsync(h->d_truncated.get(), 0, B, h->stream));
 
     RcwPlan& d = h->dev;
     set_geometry(d, cfg, batch);
@@ -1105,6 +1112,7 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     d.err = h->d_err.get<int32_t>();
     d.top_view = h->d_top_view.get<uint32_t>();
     d.status = h->d_status.get<int32_t>();
+    d.limit = RcwLimit{h->d_episode_steps.get<uint32_t>(), h->d_truncated.get<uint8_t>(), 0};
     d.oob_empty = cfg->out_of_bounds == RCW_OOB_TREAT_EMPTY;
     h->hw.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (prop.sharedMemPerBlock >= 64 * 1024) h->hw.lds_per_cu = (int)prop.sharedMemPerBlock;           // (gfx950: 160 KiB, the whole CU's)
@@ -1306,6 +1314,25 @@ int rcw_step_device(rcw_handle* h, const uint8_t* actions_device)
     return RCW_OK;
 }
 
+// The episode time limit (include/rcw.h).  The limit itself is a kernel argument (dev.limit.max_steps): a step takes the *_limit_kernel
+// instantiations while it is > 0 and the plain kernels otherwise; the counters count from this call.
+int rcw_set_time_limit(rcw_handle* h, int32_t max_episode_steps)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    if (max_episode_steps < 0) return fail(RCW_ERR_INVALID_ARGUMENT, "max_episode_steps must be >= 0 (0: no limit; got %d)", max_episode_steps);
+    RCW_HIP(hipMemsetAsync(h->d_episode_steps.get(), 0, (size_t)h->B * sizeof(uint32_t), h->stream));
+    RCW_HIP(hipMemsetAsync(h->d_truncated.get(), 0, (size_t)h->B, h->stream));
+    h->dev.limit.max_steps = max_episode_steps;
+    h->step.time_limit_set();
+    return RCW_OK;
+}
+
+int rcw_time_limit(rcw_handle* h, int32_t* out)
+{
+    if (!h || !out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = h->dev.limit.max_steps; return RCW_OK;
+}
+
 int rcw_cast_rays(rcw_handle* h)
 {
     int rc = check_handle(h); if (rc) return rc;
@@ -1413,6 +1440,8 @@ int rcw_position64(rcw_handle* h, double* out)
 int rcw_direction(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_dir.get(), (size_t)h->B); }
 int rcw_goal(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_goal.get(), (size_t)2 * h->B); }
 int rcw_episode(rcw_handle* h, uint32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_episode.get(), (size_t)h->B); }
+int rcw_episode_steps(rcw_handle* h, uint32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_episode_steps.get(), (size_t)h->B); }
+int rcw_truncated(rcw_handle* h, uint8_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_truncated.get(), (size_t)h->B); }
 
 int rcw_status(rcw_handle* h, int32_t* out)
 {
@@ -1432,6 +1461,17 @@ int rcw_done_device_ptr(rcw_handle* h, void** p)
 {
     if (!h || !p) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
     *p = h->d_done.get(); return RCW_OK;
+}
+
+int rcw_episode_steps_device_ptr(rcw_handle* h, void** p)
+{
+    if (!h || !p) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    *p = h->d_episode_steps.get(); return RCW_OK;
+}
+int rcw_truncated_device_ptr(rcw_handle* h, void** p)
+{
+    if (!h || !p) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    *p = h->d_truncated.get(); return RCW_OK;
 }
 
 int rcw_tile_map_num_chunks(rcw_handle* h, int32_t* out)

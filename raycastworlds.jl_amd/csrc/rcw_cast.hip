@@ -197,10 +197,13 @@ __device__ __forceinline__ void agent_sync()
 // WAVE = false: the workgroup is one agent (tid = its thread, nthr = blockDim).  WAVE = true (the one-launch step at up to 256 view
 // columns): 64 lanes are an agent and the workgroup's wavefronts are DIFFERENT agents: the same code with
 // tid = the lane, nthr = 64, the wavefront's own slice of LDS, and no workgroup barrier.
-template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE, bool SPEC = false>
+// LIMIT: the episode time limit (include/rcw.h, rcw_set_time_limit; lim.max_steps > 0) — the *_limit_kernel instantiations, which a step takes only
+// while a limit is set: the agent's episode_steps word comes with batch 1, `truncated` is not loaded but derived (every writer keeps
+// truncated == (episode_steps >= time_limit && !done)), a truncated agent restarts like a done one, and lane 0 stores the two words beside `done`.
+template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE, bool SPEC = false, bool LIMIT = false>
 __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask,
                                           const int a, const int tid, const int nthr, uint32_t* const lds, const int trace_slot,
-                                          uint16_t* __restrict__ spec_out = nullptr, const int spec_cols = 1)
+                                          uint16_t* __restrict__ spec_out = nullptr, const int spec_cols = 1, const RcwLimit& lim = RcwLimit{})
 {
     typedef typename Real<T>::vec2 vec2;
     const int H = p.H, HW = p.H * p.W, N = p.N;
@@ -220,7 +223,10 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
     const uint8_t* const mask_q = mask != nullptr ? mask + a : p.done + a;
     const uint8_t* const act_q = actions != nullptr ? actions + a : p.done + a;
     vec2 pos;
-    const CastState st = load_cast_state(mask_q, act_q, p.done + a, p.dir + a, Real<T>::pos(p) + a, pos);
+    uint32_t steps = 0u;                                                    // episode_steps (LIMIT)
+    CastState st;
+    if (LIMIT) st = load_cast_state_limit(mask_q, act_q, p.done + a, p.dir + a, Real<T>::pos(p) + a, lim.episode_steps + a, pos, steps);
+    else st = load_cast_state(mask_q, act_q, p.done + a, p.dir + a, Real<T>::pos(p) + a, pos);
     const int m = byte_of_word(st.mask_w, mask_q), was_done = byte_of_word(st.done_w, p.done + a), d = st.d;
     int act = byte_of_word(st.act_w, act_q);
     // the tile words too (and every wavefront of the workgroup has READ the state before lane 0 overwrites it below)
@@ -231,7 +237,10 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
 
     const bool invalid = actions != nullptr && (act < 1 || act > RCW_NUM_ACTIONS);   // @assert SR:140
     if (invalid) act = 0;                                                   // this agent is not stepped
-    const bool resample = act != 0 && p.auto_reset != 0 && was_done != 0;
+    // (LIMIT is a constant: each of these ternaries compiles its live arm alone — the plain instantiations keep the code they had)
+    const bool was_truncated = LIMIT ? was_done == 0 && steps >= (uint32_t)lim.max_steps : false;
+    const bool resample = LIMIT ? act != 0 && p.auto_reset != 0 && (was_done != 0 || was_truncated)
+                                : act != 0 && p.auto_reset != 0 && was_done != 0;
     int d_new = d;
     if (!resample && act == 3) d_new = d + 1 >= p.nd ? 0 : d + 1;          // turn_left  UT:13
     if (!resample && act == 4) d_new = d - 1 < 0 ? p.nd - 1 : d - 1;       // turn_right UT:14
@@ -283,11 +292,14 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
     // ---- phase 0: dynamics, computed redundantly by every lane (no broadcast needed) --------
     T x = pos.x, y = pos.y;
     int done_now = was_done;                                                // world.done once this call's dynamics are through (SPEC)
+    bool truncated_now = was_truncated;                                     // ... and `truncated` (an agent that is not stepped keeps both words)
     if (resample) {                                                         // wave-uniform, rare
         done_now = 0;
+        if (LIMIT) truncated_now = false;
         if (tid == 0) {
             const Pose<T> np = reset_agent<T>(p, a, tm_hbm, nullptr);
             s_pose[0] = np.x; s_pose[1] = np.y; s_pose_d = np.d;
+            if (LIMIT) { lim.episode_steps[a] = 0u; lim.truncated[a] = 0; }
         }
         agent_sync<WAVE>();
         stage_tile_bytes(tb, tm_hbm, HW, tid, nthr);                        // the goal moved
@@ -320,6 +332,7 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
             else { x = nx; y = ny; }                                        // SR:174
         }
         if (!oob) done_now = done;
+        if (LIMIT && !oob) { steps += 1u; truncated_now = done == 0 && steps >= (uint32_t)lim.max_steps; }   // (a blocked move and the goal's step count; termination wins)
         if (tid == 0) {
             if (oob) {
                 p.err[0] = RCW_ERR_OUT_OF_BOUNDS;
@@ -328,6 +341,7 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
                 Real<T>::pos(p)[a] = Real<T>::make(x, y);                   // SR:174
                 p.dir[a] = d_new;                                           // SR:185
                 store_reward(p, a, done != 0); p.done[a] = (uint8_t)done;   // SR:167-176, SR:186-187
+                if (LIMIT) { lim.episode_steps[a] = steps; lim.truncated[a] = truncated_now ? 1 : 0; }
             }
         }
     }
@@ -347,13 +361,13 @@ __device__ __forceinline__ void cast_body(const RcwDev& p, const uint8_t* __rest
         // fill's packed word in slot 0 — the frames of its FOUR SUCCESSORS, one per action of the next act!(world, a) SR:139-191, so
         // that the next launch's fill workgroups only pick the slot the action names.  A move that would be blocked, reach the goal or
         // raise (SR:162-176: the pose stays) has the current frame: its slot gets the current fan's words.  An agent that is done
-        // under auto_reset is re-sampled by ANY next action: reset_preview draws the pose the next launch's commit will draw.
+        // (LIMIT: or truncated) under auto_reset is re-sampled by ANY next action: reset_preview draws the pose the next launch's commit will draw.
         const T* const tab = Real<T>::ray_table(p) + (size_t)d_new * RCW_TABLE_ROWS * N;
         uint16_t* const slot_a = spec_out + (size_t)a * 5u * (size_t)N;     // [B][5][N]
         const uint32_t stride = (uint32_t)N;
         int32_t* const ch = spec_cols ? col_h_a : nullptr;                  // the descriptors of the current frame: only where somebody reads them (rcw_api.hip, ensure_columns)
         spec_derive_rows<T>(dvn.x, dvn.y, r_dx, r_dy, r_ddx, r_ddy, r_dot);
-        const bool reborn = p.auto_reset != 0 && done_now != 0;
+        const bool reborn = LIMIT ? p.auto_reset != 0 && (done_now != 0 || truncated_now) : p.auto_reset != 0 && done_now != 0;
         bool f_free = false, b_free = false;
         const T ix = Real<T>::inc(p) * dvn.x, iy = Real<T>::inc(p) * dvn.y;
         const T xf = x + ix, yf = y + iy, xb = x - ix, yb = y - iy;        // UT:16-17
@@ -571,17 +585,17 @@ __device__ __forceinline__ void fill_window_spec_body(const RcwDev& p, const uin
 
 // casting workgroup `block` of the launch.  WAVE: a wavefront per agent, four agents a casting workgroup (at most 256 view columns:
 // four a lane); else a workgroup per agent.
-template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE>
+template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE, bool LIMIT = false>
 __device__ __forceinline__ void cast_successors(const RcwDev& p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask, int block,
-                                                uint16_t* __restrict__ slots_out, uint32_t* lds, int lds_words, int cols)
+                                                uint16_t* __restrict__ slots_out, uint32_t* lds, int lds_words, int cols, const RcwLimit& lim = RcwLimit{})
 {
     if (WAVE) {
         const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         const int a = block * (kBlock / 64) + wave;
         if (a >= p.B) return;                                               // (wave-uniform: the batch's last workgroup may be short)
-        cast_body<T, TIE_LE, DIST_PRE, true, true>(p, actions, mask, a, (int)(threadIdx.x & 63u), 64, lds + (size_t)wave * lds_words, a, slots_out, cols);
+        cast_body<T, TIE_LE, DIST_PRE, true, true, LIMIT>(p, actions, mask, a, (int)(threadIdx.x & 63u), 64, lds + (size_t)wave * lds_words, a, slots_out, cols, lim);
     } else {
-        cast_body<T, TIE_LE, DIST_PRE, false, true>(p, actions, mask, block, (int)threadIdx.x, kBlock, lds, block, slots_out, cols);
+        cast_body<T, TIE_LE, DIST_PRE, false, true, LIMIT>(p, actions, mask, block, (int)threadIdx.x, kBlock, lds, block, slots_out, cols, lim);
     }
 }
 
@@ -627,6 +641,51 @@ __global__ __launch_bounds__(kBlock) void rcw_cast_successors_kernel(const RcwDe
     cast_successors<T, TIE_LE, DIST_PRE, WAVE>(p, actions, mask, (int)blockIdx.x, slots_out, lds, lds_words, 1);
 }
 
+// ---- the same four kernels with the episode time limit (cast_body<..., LIMIT = true>) --------------------------------------------------
+// Instantiations only, under names of their own: a step takes them while the handle has a limit (RcwPlan::limit.max_steps > 0) and the kernels above
+// otherwise, whose code therefore stays what it was.  The fill halves are the same bodies: the limit lives in the casting half alone.
+template <typename T, bool TIE_LE, bool DIST_PRE>
+__global__ __launch_bounds__(kBlock) void rcw_cast_limit_kernel(const RcwDev p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask, int first, const RcwLimit lim)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    cast_body<T, TIE_LE, DIST_PRE, false, false, true>(p, actions, mask, first + (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, lds, (int)blockIdx.x, nullptr, 1, lim);
+}
+
+template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE>
+__global__ __launch_bounds__(kBlock) void rcw_fill256_cast_limit_kernel(const RcwDev p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask,
+                                                                        u32x4* __restrict__ out, long long total_cols, int fill_blocks,
+                                                                        const uint16_t* __restrict__ slots_in, uint16_t* __restrict__ slots_out, int lds_words, int n_shift, int cols, int keep,
+                                                                        const RcwLimit lim)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    if ((int)blockIdx.x < fill_blocks) { fill256_spec_body<false>(p, actions, slots_in, out, total_cols, (int)blockIdx.x, fill_blocks, n_shift, (uint32_t)keep); return; }
+    cast_successors<T, TIE_LE, DIST_PRE, WAVE, true>(p, actions, mask, (int)blockIdx.x - fill_blocks, slots_out, lds, lds_words, cols, lim);
+}
+
+template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE>
+__global__ __launch_bounds__(kBlock) void rcw_fill_window_cast_limit_kernel(const RcwDev p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask,
+                                                                            u32x4* __restrict__ out, long long total_chunks, int fill_blocks,
+                                                                            const uint16_t* __restrict__ slots_in, uint16_t* __restrict__ slots_out, int lds_words, int n_shift, int cols,
+                                                                            int window, int keep, const RcwLimit lim)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    if ((int)blockIdx.x < fill_blocks) {
+        if (window == 1) fill_window_spec_body<1>(p, actions, slots_in, out, total_chunks, (int)blockIdx.x, fill_blocks, n_shift, (uint32_t)keep);
+        else if (window == 2) fill_window_spec_body<2>(p, actions, slots_in, out, total_chunks, (int)blockIdx.x, fill_blocks, n_shift, (uint32_t)keep);
+        else fill_window_spec_body<4>(p, actions, slots_in, out, total_chunks, (int)blockIdx.x, fill_blocks, n_shift, (uint32_t)keep);
+        return;
+    }
+    cast_successors<T, TIE_LE, DIST_PRE, WAVE, true>(p, actions, mask, (int)blockIdx.x - fill_blocks, slots_out, lds, lds_words, cols, lim);
+}
+
+template <typename T, bool TIE_LE, bool DIST_PRE, bool WAVE>
+__global__ __launch_bounds__(kBlock) void rcw_cast_successors_limit_kernel(const RcwDev p, const uint8_t* __restrict__ actions, const uint8_t* __restrict__ mask,
+                                                                           uint16_t* __restrict__ slots_out, int lds_words, const RcwLimit lim)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    cast_successors<T, TIE_LE, DIST_PRE, WAVE, true>(p, actions, mask, (int)blockIdx.x, slots_out, lds, lds_words, 1, lim);
+}
+
 // ---- small kernels ---------------------------------------------------------------------------
 // wall ring SR:57-60 and a placeholder goal at (2,2) (cleared by the first reset)
 __global__ void rcw_init_tile_map_kernel(const RcwDev p)
@@ -648,20 +707,24 @@ __global__ void rcw_init_tile_map_kernel(const RcwDev p)
     p.status[a] = 0;
 }
 
+// reset! / set_state begin an episode: the time limit's two words of the agent (include/rcw.h, rcw_set_time_limit)
+__device__ __forceinline__ void clear_time_limit_words(const RcwLimit& lim, int a) { lim.episode_steps[a] = 0u; lim.truncated[a] = 0; }
+
 template <typename T>
-__global__ void rcw_reset_kernel(const RcwDev p, const uint8_t* __restrict__ mask)
+__global__ void rcw_reset_kernel(const RcwDev p, const uint8_t* __restrict__ mask, const RcwLimit lim)
 {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= p.B) return;
     if (mask != nullptr && mask[a] == 0) return;
     reset_agent<T>(p, a, p.tile_map + (size_t)a * p.nwords, nullptr);
+    clear_time_limit_words(lim, a);
 }
 
 // inject post-reset state: SR:118-132 with caller-chosen draws
 template <typename T>
 __global__ void rcw_set_state_kernel(const RcwDev p, const int2* __restrict__ goal,
                                      const typename Real<T>::vec2* __restrict__ pos, const int32_t* __restrict__ dir,
-                                     const uint8_t* __restrict__ mask)
+                                     const uint8_t* __restrict__ mask, const RcwLimit lim)
 {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= p.B) return;
@@ -676,6 +739,7 @@ __global__ void rcw_set_state_kernel(const RcwDev p, const int2* __restrict__ go
     p.dir[a] = dir[a];                            // SR:129
     store_reward(p, a, false);                    // SR:131
     p.done[a] = 0;                                // SR:132
+    clear_time_limit_words(lim, a);
 }
 
 // cast_rays!(world) SR:195-231 with the ray buffers materialised (rcw_rays)
@@ -725,7 +789,9 @@ hipError_t rcw_launch_cast(const RcwPlan& p, const uint8_t* actions_dev, const u
                            hipStream_t s, int first, int count)
 {
     if (count < 0) count = p.B - first;
-    RCW_DISPATCH(rcw_cast_kernel, dim3(count), dim3(p.cast_block), rcw_cast_lds_bytes(p), p, actions_dev, mask_dev, first);
+    // (without an action nobody is stepped and nothing here reads the limit's words: the plain kernel)
+    if (p.limit.max_steps > 0 && actions_dev != nullptr) RCW_DISPATCH(rcw_cast_limit_kernel, dim3(count), dim3(p.cast_block), rcw_cast_lds_bytes(p), p, actions_dev, mask_dev, first, p.limit);
+    else RCW_DISPATCH(rcw_cast_kernel, dim3(count), dim3(p.cast_block), rcw_cast_lds_bytes(p), p, actions_dev, mask_dev, first);
     return hipGetLastError();
 }
 
@@ -758,45 +824,45 @@ hipError_t rcw_launch_step_spec(const RcwPlan& p, const uint8_t* actions_dev, co
     const int cast_blocks = wave ? (p.B + kBlock / 64 - 1) / (kBlock / 64) : p.B;
     const size_t lds = wave ? (kBlock / 64) * per_agent : per_agent;
     const int lds_words = (int)(per_agent / 4);
+    // WAVE by the geometry; the *_limit_kernel twin while the handle has a time limit — also where the casting workgroups run without an action
+    // (they prime the slots of the CURRENT state, and a truncated agent's successors are the re-sampled world's)
+#define RCW_DISPATCH_STEP(KERNEL, ...)                                                                              \
+    do {                                                                                                            \
+        if (p.limit.max_steps > 0) { if (wave) RCW_DISPATCH_W(KERNEL##_limit_kernel, true, __VA_ARGS__, p.limit); else RCW_DISPATCH_W(KERNEL##_limit_kernel, false, __VA_ARGS__, p.limit); } \
+        else { if (wave) RCW_DISPATCH_W(KERNEL##_kernel, true, __VA_ARGS__); else RCW_DISPATCH_W(KERNEL##_kernel, false, __VA_ARGS__); }                              \
+    } while (0)
     if (with_fill) {
         const int window = rcw_fill_window_columns(p, total_cols);          // 0: the 256-row window; 1, 2, 4: rcw_fill_window_kernel<M>'s
         const long long units = window == 0 ? total_cols : total_cols * p.Hc / 256;   // view columns / 1 KiB chunks of the batch
         if (window < 0) return hipErrorInvalidValue;
-        if (window == 0) {
-            if (wave) RCW_DISPATCH_W(rcw_fill256_cast_kernel, true, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
-                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, ikeep);
-            else      RCW_DISPATCH_W(rcw_fill256_cast_kernel, false, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
-                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, ikeep);
-        } else {
-            if (wave) RCW_DISPATCH_W(rcw_fill_window_cast_kernel, true, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
-                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, window, ikeep);
-            else      RCW_DISPATCH_W(rcw_fill_window_cast_kernel, false, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
-                                     out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, window, ikeep);
-        }
+        if (window == 0) RCW_DISPATCH_STEP(rcw_fill256_cast, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
+                                           out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, ikeep);
+        else             RCW_DISPATCH_STEP(rcw_fill_window_cast, dim3(fill_blocks + cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev,
+                                           out, units, fill_blocks, slots_in, slots_out, lds_words, n_shift, icols, window, ikeep);
     } else {
-        if (wave) RCW_DISPATCH_W(rcw_cast_successors_kernel, true, dim3(cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev, slots_out, lds_words);
-        else      RCW_DISPATCH_W(rcw_cast_successors_kernel, false, dim3(cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev, slots_out, lds_words);
+        RCW_DISPATCH_STEP(rcw_cast_successors, dim3(cast_blocks), dim3(kBlock), lds, p, actions_dev, mask_dev, slots_out, lds_words);
     }
+#undef RCW_DISPATCH_STEP
     return hipGetLastError();
 }
 
-hipError_t rcw_launch_reset(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s)
+hipError_t rcw_launch_reset(const RcwPlan& p, const uint8_t* mask_dev, hipStream_t s)
 {
-    if (p.real64) hipLaunchKernelGGL(rcw_reset_kernel<double>, dim3((p.B + 63) / 64), dim3(64), 0, s, p, mask_dev);
-    else          hipLaunchKernelGGL(rcw_reset_kernel<float>, dim3((p.B + 63) / 64), dim3(64), 0, s, p, mask_dev);
+    if (p.real64) hipLaunchKernelGGL(rcw_reset_kernel<double>, dim3((p.B + 63) / 64), dim3(64), 0, s, p, mask_dev, p.limit);
+    else          hipLaunchKernelGGL(rcw_reset_kernel<float>, dim3((p.B + 63) / 64), dim3(64), 0, s, p, mask_dev, p.limit);
     return hipGetLastError();
 }
 
 // pos: float2* for a Float32 world, double2* for a Float64 world
-hipError_t rcw_launch_set_state(const RcwDev& p, const int2* goal, const void* pos,
+hipError_t rcw_launch_set_state(const RcwPlan& p, const int2* goal, const void* pos,
                                 const int32_t* dir, const uint8_t* mask_dev, hipStream_t s)
 {
     if (p.real64)
         hipLaunchKernelGGL(rcw_set_state_kernel<double>, dim3((p.B + 63) / 64), dim3(64), 0, s, p, goal,
-                           static_cast<const double2*>(pos), dir, mask_dev);
+                           static_cast<const double2*>(pos), dir, mask_dev, p.limit);
     else
         hipLaunchKernelGGL(rcw_set_state_kernel<float>, dim3((p.B + 63) / 64), dim3(64), 0, s, p, goal,
-                           static_cast<const float2*>(pos), dir, mask_dev);
+                           static_cast<const float2*>(pos), dir, mask_dev, p.limit);
     return hipGetLastError();
 }
 

@@ -389,6 +389,29 @@ __device__ __forceinline__ CastState load_cast_state(const uint8_t* mask_q, cons
     pos.x = __longlong_as_double((long long)(((uint64_t)pw.y << 32) | pw.x)); pos.y = __longlong_as_double((long long)(((uint64_t)pw.w << 32) | pw.z));
     return c;
 }
+// The same with the agent's episode_steps word as a sixth load (the *_limit_kernel instantiations of cast_body; the drawing kernels keep the five).
+__device__ __forceinline__ CastState load_cast_state_limit(const uint8_t* mask_q, const uint8_t* act_q, const uint8_t* done_q, const int32_t* dir_q,
+                                                           const float2* pos_q, const uint32_t* steps_q, float2& pos, uint32_t& steps)
+{
+    CastState c; uint64_t pw;
+    asm volatile("s_load_dword %0, %6, 0x0\n\ts_load_dword %1, %7, 0x0\n\ts_load_dword %2, %8, 0x0\n\ts_load_dword %3, %9, 0x0\n\t"
+                 "s_load_dwordx2 %4, %10, 0x0\n\ts_load_dword %5, %11, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(c.mask_w), "=&s"(c.act_w), "=&s"(c.done_w), "=&s"(c.d), "=&s"(pw), "=&s"(steps)
+                 : "s"(mask_q), "s"(act_q), "s"(done_q), "s"(dir_q), "s"(pos_q), "s"(steps_q) : "memory");
+    pos.x = __uint_as_float((uint32_t)pw); pos.y = __uint_as_float((uint32_t)(pw >> 32));
+    return c;
+}
+__device__ __forceinline__ CastState load_cast_state_limit(const uint8_t* mask_q, const uint8_t* act_q, const uint8_t* done_q, const int32_t* dir_q,
+                                                           const double2* pos_q, const uint32_t* steps_q, double2& pos, uint32_t& steps)
+{
+    CastState c; su32x4 pw;
+    asm volatile("s_load_dword %0, %6, 0x0\n\ts_load_dword %1, %7, 0x0\n\ts_load_dword %2, %8, 0x0\n\ts_load_dword %3, %9, 0x0\n\t"
+                 "s_load_dwordx4 %4, %10, 0x0\n\ts_load_dword %5, %11, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(c.mask_w), "=&s"(c.act_w), "=&s"(c.done_w), "=&s"(c.d), "=&s"(pw), "=&s"(steps)
+                 : "s"(mask_q), "s"(act_q), "s"(done_q), "s"(dir_q), "s"(pos_q), "s"(steps_q) : "memory");
+    pos.x = __longlong_as_double((long long)(((uint64_t)pw.y << 32) | pw.x)); pos.y = __longlong_as_double((long long)(((uint64_t)pw.w << 32) | pw.z));
+    return c;
+}
 __device__ __forceinline__ int byte_of_word(uint32_t w, const uint8_t* q) { return (int)((w >> (8u * (uint32_t)(reinterpret_cast<uintptr_t>(q) & 3u))) & 0xffu); }
 // base[byte_offset] with a 32-bit byte offset: the uniform base stays in scalar registers and the lane's part of the address
 // is one register (global_load ... v_off, s[base]); indexed in C the offset is sign-extended and the address built per lane in

@@ -66,6 +66,17 @@ struct RcwDev {
     int32_t* status;         // per-agent sticky status
 };
 
+// The episode time limit (include/rcw.h, rcw_set_time_limit): what its kernels read.  An argument of its OWN, behind RcwDev, of the kernels
+// that need it — the *_limit_kernel instantiations of the step (taken only while max_steps > 0) and the reset / set_state kernels — and not
+// three more members of RcwDev: a larger RcwDev moves the arguments of every kernel of the library, and the compiler then allocates their
+// scalar registers differently (tools/isa_diff.py against the build before: 168 of 170 kernels changed, some in length).  This way every
+// kernel a limit-less handle runs keeps its code to the byte.
+struct RcwLimit {
+    uint32_t* episode_steps; // [B] act! calls the agent's episode has taken
+    uint8_t* truncated;      // [B] 0/1: episode_steps >= max_steps && !done, as of the agent's last step
+    int32_t max_steps;       // max_episode_steps; 0: no limit — steps neither read nor write the two arrays
+};
+
 // The host's launch plan: the argument block plus the decisions of set_geometry and top_view_rule that only launchers read.  A kernel
 // launch takes its RcwDev part (the conversion to the base); a value a kernel needs does not go here but in RcwDev.
 struct RcwPlan : RcwDev {
@@ -83,6 +94,7 @@ struct RcwPlan : RcwDev {
     int32_t top_draw_block_alone;   // ... in rcw_update_top_view alone: 64 / 128 for batches of tens of thousands of small images
     int32_t top_store_plain; // the two-kernel form's store kernel: 1 plain stores, 0 non-temporal
     int32_t top_store_grid;  // ... and its workgroups (the moving window = top_store_grid KiB x 4)
+    RcwLimit limit;          // the time limit's argument block: launchers pick the *_limit_kernel twins by it and hand it to them
 };
 
 struct RcwRayOut {           // rcw_rays(): SR:29-31,39 for agents [first, first+count)
@@ -129,8 +141,8 @@ hipError_t rcw_launch_step_spec(const RcwPlan& p, const uint8_t* actions_dev, co
 int rcw_fill_draw_fusable(const RcwPlan& p);   // a step's camera fill + top-view drawing in one launch: this geometry takes it
 hipError_t rcw_launch_fill256_draw(const RcwPlan& p, const uint8_t* mask_dev, hipStream_t s);   // (fills p.obs from p.col_h / p.col_c, draws every agent)
 hipError_t rcw_prepare_top_view(const RcwDev& p, int device);
-hipError_t rcw_launch_reset(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);
-hipError_t rcw_launch_set_state(const RcwDev& p, const int2* goal, const void* pos /* float2* or double2* */,
+hipError_t rcw_launch_reset(const RcwPlan& p, const uint8_t* mask_dev, hipStream_t s);   // (both also zero the masked agents' RcwLimit words)
+hipError_t rcw_launch_set_state(const RcwPlan& p, const int2* goal, const void* pos /* float2* or double2* */,
                                 const int32_t* dir, const uint8_t* mask_dev, hipStream_t s);
 hipError_t rcw_launch_init_tile_map(const RcwDev& p, hipStream_t s);
 hipError_t rcw_launch_rays(const RcwDev& p, int32_t first, int32_t count, RcwRayOut out,

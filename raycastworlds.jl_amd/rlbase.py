@@ -71,3 +71,10 @@ def reward(env: RLBaseEnv):
 def is_terminated(env: RLBaseEnv):
     """`RLBase.is_terminated(env) = env.env.world.done` SR:584: Bool (B,), device-resident like `reward`."""
     return env.env.done_device(as_bool=True)
+
+
+def is_truncated(env: RLBaseEnv):
+    """This build's addition (the reference has no such verb: SingleRoom ends at the goal only): Bool (B,), device-resident like
+    `is_terminated` — the agents whose episode the time limit (`env.env.set_time_limit`, `SingleRoom(max_episode_steps=...)`) has
+    cut.  All False while no limit is set.  An episode is over where `is_terminated(env) | is_truncated(env)`."""
+    return env.env.truncated_device(as_bool=True)

@@ -284,6 +284,16 @@ class SingleRoomWorld:
         return self._get(self._env._lib.rcw_episode, np.uint32, (self._env.batch,))
 
     @property
+    def episode_steps(self) -> np.ndarray:
+        """Steps each agent's episode has taken since `set_time_limit` / its last reset (uint32; zero while there is no limit)."""
+        return self._get(self._env._lib.rcw_episode_steps, np.uint32, (self._env.batch,))
+
+    @property
+    def truncated(self) -> np.ndarray:
+        """Which agents' episodes the time limit has cut (bool; `episode_steps >= time_limit and not done`)."""
+        return self._get(self._env._lib.rcw_truncated, np.uint8, (self._env.batch,)).astype(bool)
+
+    @property
     def directions_wu(self) -> np.ndarray:             # SR:28, (nd, 2)
         out = np.empty((self.num_directions, 2), dtype=self._env.T)
         fn = self._env._lib.rcw_direction_table64 if self._env.T is np.float64 else self._env._lib.rcw_direction_table
@@ -327,6 +337,8 @@ class SingleRoom:
     distribution).  `rng` (SR:49,265) gives the reference's keyword back: a `numpy.random.Generator` — or one per agent —
     from which construction and every `reset_(env, rng=...)` draw goal, player tile and heading on the HOST in exactly
     the reference's order (`reference_reset_draws`), injected with `rcw_set_state`.  `device` is the HIP device index.
+    `max_episode_steps` (this build's addition; 0 = none, the reference's behaviour) is the episode time limit of
+    `set_time_limit`.
     """
 
     def __init__(
@@ -356,6 +368,7 @@ class SingleRoom:
         out_of_bounds: int = 0,
         render_top_view: bool = False,
         library: Optional[str] = None,
+        max_episode_steps: int = 0,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -431,6 +444,12 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        if max_episode_steps:
+            try:
+                self.set_time_limit(max_episode_steps)
+            except BaseException:
+                self._handle.close()
+                raise
         # colour fields of the reference struct SR:241-256
         self.floor_color = cfg.floor_color
         self.ceiling_color = cfg.ceiling_color
@@ -457,7 +476,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -735,6 +754,41 @@ class SingleRoom:
             setattr(self, name, DeviceArray(p.value, (self.batch,), np.bool_ if as_bool else np.uint8, self, self._sync,
                                             host_getter=getter))
         return getattr(self, name)
+
+    # ---- the episode time limit (include/rcw.h, rcw_set_time_limit) -------------------
+    def set_time_limit(self, max_episode_steps: int) -> None:
+        """An episode ends after `max_episode_steps` steps without the goal: the step that reaches the limit sets `truncated`, and under
+        `auto_reset` the next action restarts the agent as it restarts a done one (the action is ignored, the episode counter moves, the
+        frame stack refills).  0 switches the limit off (the default).  Decided on the device by the step's own kernels: no host
+        synchronisation.  Every call zeroes `episode_steps` and `truncated` of every agent — the limit counts from the call."""
+        self._check(self._lib.rcw_set_time_limit(self._h, int(max_episode_steps)))
+
+    @property
+    def time_limit(self) -> int:
+        n = C.c_int32()
+        self._check(self._lib.rcw_time_limit(self._h, C.byref(n)))
+        return int(n.value)
+
+    def truncated_device(self, as_bool: bool = False) -> DeviceArray:
+        """`truncated` in device memory: one byte per agent (`as_bool`: the same bytes viewed as Bool), rewritten by every step in
+        stream order while a time limit is set.  The same object on every call, like `done_device`."""
+        name = "_truncated_dev_bool" if as_bool else "_truncated_dev"
+        if getattr(self, name, None) is None:
+            p = C.c_void_p()
+            self._check(self._lib.rcw_truncated_device_ptr(self._h, C.byref(p)))
+            getter = (lambda: self.world.truncated) if as_bool else (lambda: self.world.truncated.astype(np.uint8))
+            setattr(self, name, DeviceArray(p.value, (self.batch,), np.bool_ if as_bool else np.uint8, self, self._sync,
+                                            host_getter=getter))
+        return getattr(self, name)
+
+    def episode_steps_device(self) -> DeviceArray:
+        """`episode_steps` in device memory: uint32 (B,); at the step that sets `done` or `truncated` it is the episode's length."""
+        if getattr(self, "_episode_steps_dev", None) is None:
+            p = C.c_void_p()
+            self._check(self._lib.rcw_episode_steps_device_ptr(self._h, C.byref(p)))
+            self._episode_steps_dev = DeviceArray(p.value, (self.batch,), np.uint32, self, self._sync,
+                                                  host_getter=lambda: self.world.episode_steps)
+        return self._episode_steps_dev
 
     def ray_table(self) -> np.ndarray:
         """(nd, 5, N) float32: per heading [dx | dy | |1/dx| | |1/dy| | dir·ray]."""
