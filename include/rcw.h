@@ -316,6 +316,34 @@ RCW_API int rcw_episode_steps(rcw_handle* h, uint32_t* out_host /* (B) */);
 RCW_API int rcw_truncated(rcw_handle* h, uint8_t* out_host /* (B) */);
 RCW_API int rcw_episode_steps_device_ptr(rcw_handle* h, void** device_ptr);
 RCW_API int rcw_truncated_device_ptr(rcw_handle* h, void** device_ptr);
+/* ---- wall layouts (this build's addition: the reference builds the wall ring SR:57-60 and nothing else) ------------------------
+ * The WALL layer of world.tile_map is per agent, and everything that reads it — cast_ray, is_player_colliding, the top view, the
+ * sampler — takes whatever it holds.  rcw_set_walls writes it: corridors, rooms, mazes, a different layout per agent.  The ABI is
+ * additive: RCW_ABI_VERSION and rcw_config are what they were.
+ *   walls_host          UInt8 (H*W, layouts): tile (i, j), 1-based, of layout m at m*H*W + (i-1) + H*(j-1) — the tile map's own linear
+ *                       order; non-zero = WALL.
+ *   layout_index_host   Int32 (B): agent a takes layout index[a].  NULL only with layouts == 1 (every agent takes it) or layouts == B
+ *                       (agent a takes layout a).
+ *   mask_host           as in rcw_reset: the agents the call touches (NULL: all).
+ * Validated on the host before anything is queued; a refusal — RCW_ERR_INVALID_ARGUMENT, the message names the layout and the tile —
+ * leaves the handle untouched: a NULL walls_host or layouts < 1; a NULL index with another number of layouts; an index outside
+ * 0..layouts-1 (of an agent in the mask); a layout whose ring tile (i or j on the border, SR:57-60) is not a wall — the ring is what
+ * ends every ray's march —; a layout with fewer than two free interior tiles (a goal and a player must fit).  Layouts are NOT checked
+ * for reachability: a goal the agent cannot reach is what the time limit is for.
+ * Effect, stream-ordered, for the agents in the mask: the WALL layer becomes the layout and the GOAL layer is cleared; then the agents
+ * are reset exactly as rcw_reset(h, mask, <the handle's current seed>) resets them — goal and pose drawn against the new walls, episode
+ * counter + 1, reward 0, done false, the time limit's two words zeroed, rays cast, camera view / top view / learner view rendered, the
+ * frame stack refilled.  After the call every agent is in a valid post-reset world; a caller who wants a chosen state follows with
+ * rcw_set_state, whose host validation (interior tile, inside the room) does NOT know the walls: a goal or a pose it puts into a wall is
+ * the caller's.  The walls persist through every later rcw_reset, rcw_set_state and device-side restart (done or truncated under
+ * cfg.auto_reset) until the next rcw_set_walls.
+ * reset!(world) with walls — the one change of rule, and none on a ring-only map: after the old goal bit is cleared (SR:118) the goal
+ * pair is drawn (two draws, SR:120) and drawn AGAIN (two more draws) while the drawn tile's WALL bit is set, at most 1024*H*W redraws
+ * (the sampler's own max_tries, utils.jl:23); after that it keeps the last pair and sets RCW_WARN_SAMPLER_GAVE_UP.  Then the player's
+ * tile (rejection on any bit, as ever) and the heading.  No interior tile of a ring-only map is a wall: no redraw, the same draw
+ * indices, every sequence what it was. */
+RCW_API int rcw_set_walls(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
+                          const int32_t* layout_index_host, const uint8_t* mask_host);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

@@ -208,6 +208,34 @@ function RCW.reset!(env::BatchedSingleRoom; mask::Union{Nothing, Vector{UInt8}} 
     return nothing
 end
 
+# ---- wall layouts (this build's addition; include/rcw.h, rcw_set_walls) ------------------------------------------------------
+"""
+    set_walls!(env, walls; index = nothing, mask = nothing)
+
+Interior walls.  `walls` is `Bool` / `UInt8` `(H, W)` — one layout for every agent — or `(H, W, M)`, `walls[i, j, m]` = tile `(i, j)`
+of layout `m` is a wall, the index order of `world.tile_map[WALL, i, j]`.  `index` (`Vector{<:Integer}`, 1-based, one entry an agent)
+names each agent's layout; `nothing` needs `M == 1` or `M == batch` (agent `a` takes layout `a`).  `mask`: the agents the call touches.
+The wall ring must be there and two interior tiles free.  The touched agents are reset against the new walls with the environment's
+seed (an environment built with `rng` follows with `reset!(env; mask)` itself, whose host draws do not know the walls), and the walls
+stay through every later `reset!`, `set_state!` and `auto_reset` restart until the next call.
+"""
+function set_walls!(env::BatchedSingleRoom, walls::AbstractArray; index::Union{Nothing, AbstractVector{<:Integer}} = nothing,
+                    mask::Union{Nothing, Vector{UInt8}} = nothing)
+    H, W = Int(env.config.height_tile_map_tu), Int(env.config.width_tile_map_tu)
+    (ndims(walls) in (2, 3) && size(walls, 1) == H && size(walls, 2) == W) || throw(DimensionMismatch("walls must be ($H, $W) or ($H, $W, M)"))
+    flat = Vector{UInt8}(vec(walls .!= 0))                                       # column-major: m H W + (i - 1) + H (j - 1)
+    layouts = ndims(walls) == 2 ? 1 : size(walls, 3)
+    index0 = index === nothing ? nothing : Vector{Int32}(index .- 1)
+    index0 === nothing || length(index0) == env.batch || throw(DimensionMismatch("expected $(env.batch) layout indices"))
+    mask === nothing || length(mask) == env.batch || throw(DimensionMismatch("expected $(env.batch) mask bytes"))
+    GC.@preserve flat index0 mask check(ccall((:rcw_set_walls, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int32, Ptr{Int32}, Ptr{UInt8}),
+                                              env.handle, pointer(flat), layouts,
+                                              index0 === nothing ? Ptr{Int32}(C_NULL) : pointer(index0),
+                                              mask === nothing ? Ptr{UInt8}(C_NULL) : pointer(mask)))
+    env.stale = true
+    return nothing
+end
+
 # RCW.act!(env, action)  — single_room.jl:333-340; one action per agent (or one for all)
 function RCW.act!(env::BatchedSingleRoom, actions::Vector{UInt8})
     length(actions) == env.batch || throw(DimensionMismatch("expected $(env.batch) actions"))

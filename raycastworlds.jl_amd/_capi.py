@@ -99,6 +99,7 @@ SIGNATURES = {
     "rcw_bind_obs": [_vp, _vp],
     "rcw_reset": [_vp, _vp, _u64],
     "rcw_set_state": [_vp, _vp, _vp, _vp, _vp],
+    "rcw_set_walls": [_vp, _vp, _i32, _vp, _vp],
     "rcw_set_state64": [_vp, _vp, _vp, _vp, _vp],
     "rcw_position64": [_vp, _vp],
     "rcw_rays64": [_vp, _i32, _i32, _vp, _vp, _vp, _vp],

@@ -83,5 +83,13 @@ __attribute__((visibility("default"))) int rcw_dev_step_facts(int32_t eligible, 
     }
     return n;
 }
+// rcw_set_walls' host validation without a handle (tests/test_walls_spec.py): the return code of validate_walls, its reason in msg
+__attribute__((visibility("default"))) int rcw_dev_validate_walls(int32_t H, int32_t W, int32_t batch, const uint8_t* walls, int32_t layouts,
+                                                                 const int32_t* index, const uint8_t* mask, char* msg, int32_t cap)
+{
+    if (!msg || cap < 1 || H < 3 || W < 3 || batch < 1) return RCW_ERR_INVALID_ARGUMENT;
+    msg[0] = 0;
+    return validate_walls(H, W, batch, walls, layouts, index, mask, msg, (size_t)cap);
+}
 }  // extern "C"
 namespace {

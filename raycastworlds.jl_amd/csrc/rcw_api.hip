@@ -172,6 +172,8 @@ struct rcw_handle {
     bool top_plane_dirty = false;
     RcwEvent ev_top_fork, ev_top_join[8];   // (a join event per run of agents)
     RcwBuf d_actions, d_mask, d_in_goal, d_in_pos, d_in_dir;
+    RcwBuf d_in_walls, d_in_wall_index;   // rcw_set_walls' staging: the layouts (in_walls_cap bytes, grow-only) and the agents' layout index (int32 [B])
+    size_t in_walls_cap = 0;
     RcwPinned h_err, h_actions[2];     // the error word (int32_t); the staging ring of rcw_step (uint8_t)
     RcwEvent ev_actions[2];
     int action_slot = 0;
@@ -757,6 +759,46 @@ int plan_step_form(rcw_handle* h, int want)
     return RCW_OK;
 }
 
+// rcw_set_walls' refusals (include/rcw.h, "wall layouts") as a pure host function — no handle, no device: the development build exports it
+// (rcw_dev_validate_walls).  0, or RCW_ERR_INVALID_ARGUMENT with the reason, naming the layout and the tile, in msg.  EVERY layout handed
+// over is checked, also one no agent of the mask takes: a ring tile that is no wall lets a march leave the map (stage_tile_bytes, the guard
+// bands of cast_ray_guarded), and a later call may well index it.
+int validate_walls(int H, int W, int B, const uint8_t* walls, int layouts, const int32_t* index, const uint8_t* mask, char* msg, size_t cap)
+{
+    if (!walls) { std::snprintf(msg, cap, "NULL walls"); return RCW_ERR_INVALID_ARGUMENT; }
+    if (layouts < 1) { std::snprintf(msg, cap, "layouts must be >= 1 (got %d)", layouts); return RCW_ERR_INVALID_ARGUMENT; }
+    if (!index && layouts != 1 && layouts != B) {
+        std::snprintf(msg, cap, "a NULL layout index needs 1 layout or one per agent (%d); got %d layouts", B, layouts);
+        return RCW_ERR_INVALID_ARGUMENT;
+    }
+    for (int a = 0; index && a < B; ++a) {
+        if (mask && !mask[a]) continue;
+        if (index[a] < 0 || index[a] >= layouts) {
+            std::snprintf(msg, cap, "agent %d: layout index %d not in 0..%d", a, index[a], layouts - 1);
+            return RCW_ERR_INVALID_ARGUMENT;
+        }
+    }
+    for (int m = 0; m < layouts; ++m) {
+        const uint8_t* const q = walls + (size_t)m * (size_t)H * (size_t)W;
+        int free_tiles = 0;
+        for (int j = 1; j <= W; ++j)
+            for (int i = 1; i <= H; ++i) {
+                const bool wall = q[(i - 1) + (size_t)H * (j - 1)] != 0;
+                const bool ring = i == 1 || i == H || j == 1 || j == W;                   // SR:57-60
+                if (ring && !wall) {
+                    std::snprintf(msg, cap, "layout %d: ring tile (%d,%d) is not a wall (the ring ends every ray)", m, i, j);
+                    return RCW_ERR_INVALID_ARGUMENT;
+                }
+                if (!ring && !wall) ++free_tiles;
+            }
+        if (free_tiles < 2) {
+            std::snprintf(msg, cap, "layout %d: %d free interior tile(s), a goal and a player need two", m, free_tiles);
+            return RCW_ERR_INVALID_ARGUMENT;
+        }
+    }
+    return RCW_OK;
+}
+
 #ifdef RCW_DEV_SWITCHES
 #include "dev/api_plan_export.inc"   // the rules and the step's facts without a device (tests/test_top_view_plan.py, tests/test_step_state.py)
 #endif
@@ -1236,6 +1278,45 @@ int rcw_reset(rcw_handle* h, const uint8_t* mask_host, uint64_t seed)
     h->dev.seed = seed;
     RCW_HIP(rcw_launch_reset(h->dev, mask_dev, h->stream));            // SR:110-132
     RCW_HIP(launch_step(h, nullptr, mask_dev, kStackRefill));    // SR:134, SR:329
+    return RCW_OK;
+}
+
+// Wall layouts (include/rcw.h): validate on the host, stage layouts and index, write the (masked) agents' WALL layer — and from there on the
+// body of rcw_reset with the handle's own seed: no step fact moves that a reset with the same seed would not move.
+int rcw_set_walls(rcw_handle* h, const uint8_t* walls_host, int32_t layouts, const int32_t* layout_index_host, const uint8_t* mask_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
+    char why[256];
+    if (validate_walls(H, W, h->B, walls_host, layouts, layout_index_host, mask_host, why, sizeof why) != RCW_OK)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_set_walls: %s", why);
+    const size_t B = (size_t)h->B, bytes = (size_t)layouts * (size_t)H * (size_t)W;
+    std::vector<int32_t> index;
+    try {
+        index.resize(B);
+    } catch (const std::bad_alloc&) {
+        return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the layout index failed");
+    }
+    // (an agent outside the mask takes no layout: its entry is never read, and a stray value of the caller's must not reach the device)
+    for (size_t a = 0; a < B; ++a) {
+        const bool in = !mask_host || mask_host[a];
+        index[a] = !in ? 0 : (layout_index_host ? layout_index_host[a] : (layouts == 1 ? 0 : (int32_t)a));
+    }
+    if (bytes > h->in_walls_cap) {
+        RcwBuf larger; RCW_HIP(larger.hipMalloc(bytes));
+        RCW_HIP(replace_buffers(h, {&h->d_in_walls}, {&larger}));
+        h->in_walls_cap = bytes;
+    }
+    if (!h->d_in_wall_index.get()) RCW_HIP(h->d_in_wall_index.hipMalloc(B * sizeof(int32_t)));
+    const uint8_t* mask_dev = nullptr;
+    rc = upload_mask(h, mask_host, &mask_dev); if (rc) return rc;
+    RCW_HIP(hipMemcpyAsync(h->d_in_walls.get(), walls_host, bytes, hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipMemcpyAsync(h->d_in_wall_index.get(), index.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipStreamSynchronize(h->stream));                          // (pageable host memory, the caller's and ours)
+    h->step.reset(mask_dev != nullptr, false, h->dev.auto_reset != 0);
+    RCW_HIP(rcw_launch_set_walls(h->dev, h->d_in_walls.get<uint8_t>(), h->d_in_wall_index.get<int32_t>(), mask_dev, h->stream));
+    RCW_HIP(rcw_launch_reset(h->dev, mask_dev, h->stream));            // SR:110-132 against the new walls
+    RCW_HIP(launch_step(h, nullptr, mask_dev, kStackRefill));          // SR:134, SR:329
     return RCW_OK;
 }
 

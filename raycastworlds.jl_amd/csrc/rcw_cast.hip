@@ -167,11 +167,15 @@ __device__ __forceinline__ Pose<T> reset_preview(const RcwDev& p, int a, uint8_t
     uint64_t n = 0;
     const int2 old = p.goal[a];
     tb[(old.x - 1) + H * (old.y - 1)] &= (uint8_t)~2u;                      // SR:118
-    const int gi = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(H - 2));  // SR:120
-    const int gj = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(W - 2));
-    tb[(gi - 1) + H * (gj - 1)] |= 2u;                                      // SR:122
+    int gi = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(H - 2));      // SR:120
+    int gj = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(W - 2));
     const uint64_t HW = (uint64_t)H * (uint64_t)W;
     const uint64_t max_tries = 1024ull * HW;
+    for (uint64_t t = 0; (tb[(gi - 1) + H * (gj - 1)] & 1u) != 0u && t < max_tries; ++t) {   // (reset_agent's redraws: a goal is not drawn into a wall)
+        gi = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(H - 2));
+        gj = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(W - 2));
+    }
+    tb[(gi - 1) + H * (gj - 1)] |= 2u;                                      // SR:122
     uint64_t lin = rcw_below(rcw_draw(key, n++), HW);                        // UT:24
     for (uint64_t t = 0; t < max_tries; ++t) {                               // UT:26 (tile (i, j) is byte (i-1) + H (j-1) = lin)
         if (tb[lin]) lin = rcw_below(rcw_draw(key, n++), HW);                // UT:27-28
@@ -707,6 +711,25 @@ __global__ void rcw_init_tile_map_kernel(const RcwDev p)
     p.status[a] = 0;
 }
 
+// rcw_set_walls: the WALL layer of the (masked) agents' tile maps from their layouts, the GOAL layer cleared.  One thread per (agent, tile-map
+// word): the 16 tiles of the word are 16 bytes of the layout (tile t of layout m at walls[m H W + t], the tile map's own linear order, non-zero
+// = WALL) -> bit 0 of each 2-bit field; tiles past H W — the padding of the last chunk, which the flat top-view store reads — are 0.
+__global__ void rcw_set_walls_kernel(const RcwDev p, const uint8_t* __restrict__ walls, const int32_t* __restrict__ index, const uint8_t* __restrict__ mask)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long long)p.B * p.nwords) return;
+    const int a = (int)(g / p.nwords), w = (int)(g - (long long)a * p.nwords);
+    if (mask != nullptr && mask[a] == 0) return;
+    const int HW = p.H * p.W;
+    const uint8_t* const layout = walls + (size_t)index[a] * (size_t)HW;
+    uint32_t word = 0u;
+    for (int k = 0; k < 16; ++k) {
+        const int t = 16 * w + k;
+        if (t < HW && layout[t] != 0) word |= 1u << (2 * k);
+    }
+    p.tile_map[(size_t)a * p.nwords + w] = word;
+}
+
 // reset! / set_state begin an episode: the time limit's two words of the agent (include/rcw.h, rcw_set_time_limit)
 __device__ __forceinline__ void clear_time_limit_words(const RcwLimit& lim, int a) { lim.episode_steps[a] = 0u; lim.truncated[a] = 0; }
 
@@ -850,6 +873,14 @@ hipError_t rcw_launch_reset(const RcwPlan& p, const uint8_t* mask_dev, hipStream
 {
     if (p.real64) hipLaunchKernelGGL(rcw_reset_kernel<double>, dim3((p.B + 63) / 64), dim3(64), 0, s, p, mask_dev, p.limit);
     else          hipLaunchKernelGGL(rcw_reset_kernel<float>, dim3((p.B + 63) / 64), dim3(64), 0, s, p, mask_dev, p.limit);
+    return hipGetLastError();
+}
+
+// (index: a layout per agent, 0 <= index[a] < layouts — validated on the host, rcw_api.hip)
+hipError_t rcw_launch_set_walls(const RcwDev& p, const uint8_t* walls_dev, const int32_t* index_dev, const uint8_t* mask_dev, hipStream_t s)
+{
+    const long long words = (long long)p.B * p.nwords;
+    hipLaunchKernelGGL(rcw_set_walls_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, p, walls_dev, index_dev, mask_dev);
     return hipGetLastError();
 }
 

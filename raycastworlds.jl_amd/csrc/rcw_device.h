@@ -188,21 +188,30 @@ __device__ __forceinline__ Pose<T> reset_agent(const RcwDev& p, int a, uint32_t*
     const int2 old = p.goal[a];
     set_goal_bit(tm_a, H, old.x, old.y, false);                               // SR:118
     if (tm_b) set_goal_bit(tm_b, H, old.x, old.y, false);
-    const int gi = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(H - 2));  // SR:120
-    const int gj = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(W - 2));
+    int gi = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(H - 2));        // SR:120
+    int gj = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(W - 2));
+    // Interior walls (rcw_set_walls): the pair is drawn again while its tile is a wall, at most max_tries times — then the last pair stays,
+    // with the sampler's warning.  No interior tile of a ring-only map is a wall: no redraw, and the draw indices below are what they were.
+    const uint64_t HW = (uint64_t)H * (uint64_t)W;
+    const uint64_t max_tries = 1024ull * HW;
+    bool gave_up = false;
+    for (uint64_t t = 0; (tile_bits(tm_a, H, gi, gj) & 1u) != 0u; ++t) {
+        if (t == max_tries) { gave_up = true; break; }
+        gi = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(H - 2));
+        gj = 2 + (int)rcw_below(rcw_draw(key, n++), (uint64_t)(W - 2));
+    }
     p.goal[a] = make_int2(gi, gj);                                            // SR:121
     set_goal_bit(tm_a, H, gi, gj, true);                                      // SR:122
     if (tm_b) set_goal_bit(tm_b, H, gi, gj, true);
     // sample_empty_position UT:52-58 -> UT:23-37: rejection over all H*W tiles
-    const uint64_t HW = (uint64_t)H * (uint64_t)W;
-    const uint64_t max_tries = 1024ull * HW;
     uint64_t lin = rcw_below(rcw_draw(key, n++), HW);                          // UT:24
-    bool gave_up = true;
+    bool placed = false;
     for (uint64_t t = 0; t < max_tries; ++t) {                                 // UT:26
         const int ti = (int)(lin % (uint64_t)H) + 1, tj = (int)(lin / (uint64_t)H) + 1;
         if (tile_bits(tm_a, H, ti, tj)) lin = rcw_below(rcw_draw(key, n++), HW);   // UT:27-28
-        else { gave_up = false; break; }
+        else { placed = true; break; }
     }
+    gave_up |= !placed;
     // UT:34: "@warn Could not sample an empty position in max_tries ... Returning non-empty position" — the reference goes on
     // with the occupied tile; so does the engine, and says so in the agent's status word (a warning: no error word, no call fails)
     if (gave_up && p.status[a] == 0) p.status[a] = RCW_WARN_SAMPLER_GAVE_UP;

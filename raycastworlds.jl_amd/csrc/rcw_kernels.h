@@ -145,6 +145,8 @@ hipError_t rcw_launch_reset(const RcwPlan& p, const uint8_t* mask_dev, hipStream
 hipError_t rcw_launch_set_state(const RcwPlan& p, const int2* goal, const void* pos /* float2* or double2* */,
                                 const int32_t* dir, const uint8_t* mask_dev, hipStream_t s);
 hipError_t rcw_launch_init_tile_map(const RcwDev& p, hipStream_t s);
+// rcw_set_walls: walls UInt8 (H*W, layouts) and index Int32 (B) in DEVICE memory; the (masked) agents' WALL layer := their layout, GOAL layer := 0
+hipError_t rcw_launch_set_walls(const RcwDev& p, const uint8_t* walls_dev, const int32_t* index_dev, const uint8_t* mask_dev, hipStream_t s);
 hipError_t rcw_launch_rays(const RcwDev& p, int32_t first, int32_t count, RcwRayOut out,
                            hipStream_t s);
 hipError_t rcw_launch_expand(const RcwPlan& p, const int32_t* col_h, const uint8_t* col_c,

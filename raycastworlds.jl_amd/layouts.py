@@ -1,0 +1,92 @@
+"""Wall layouts for `SingleRoom.set_walls`: host-side numpy, nothing here touches the device.
+
+A layout is bool (H, W) with `walls[i-1, j-1]` = tile (i, j) is a WALL — the index order of `env.world.tile_map[b, 0]`.
+Every generator returns the wall ring (SR:57-60) closed, as `rcw_set_walls` requires, and at least two free interior
+tiles.  `is_connected` is the host-side answer to reachability, which the engine does not check.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+def _check_size(H: int, W: int, least: int) -> None:
+    if H < least or W < least:
+        raise ValueError(f"a {H} x {W} tile map is too small for this layout (at least {least} x {least})")
+
+
+def ring(H: int, W: int) -> np.ndarray:
+    """The reference's map: the wall ring around an empty room (SR:57-60)."""
+    _check_size(H, W, 3)
+    w = np.zeros((H, W), dtype=bool)
+    w[[0, -1], :] = True
+    w[:, [0, -1]] = True
+    return w
+
+
+def four_rooms(H: int, W: int) -> np.ndarray:
+    """A wall along the middle row and one along the middle column, each with one door in either half: four rooms, every
+    one joined to its two neighbours.  Any H, W >= 5."""
+    _check_size(H, W, 5)
+    w = ring(H, W)
+    ci, cj = H // 2, W // 2                       # the dividing row and column (0-based; interior since H, W >= 5)
+    w[ci, :] = True
+    w[:, cj] = True
+    # doors: the middle of each of the four wall segments (segments are 1 .. c-1 and c+1 .. n-2, never empty)
+    w[ci, (1 + cj - 1) // 2] = False
+    w[ci, (cj + 1 + W - 2) // 2] = False
+    w[(1 + ci - 1) // 2, cj] = False
+    w[(ci + 1 + H - 2) // 2, cj] = False
+    return w
+
+
+def maze(H: int, W: int, rng) -> np.ndarray:
+    """A perfect maze by the recursive backtracker (depth-first, an explicit stack) on the odd sub-grid: cells are the
+    tiles with odd 0-based (i, j) inside the ring, a passage is the tile between two cells.  Connected by construction;
+    a pure function of `rng` (a `numpy.random.Generator`).  Any H, W >= 5; with an even H or W the last interior row or
+    column stays wall."""
+    _check_size(H, W, 5)
+    w = np.ones((H, W), dtype=bool)
+    ni, nj = (H - 1) // 2, (W - 1) // 2           # cells along each axis: 0-based tiles 1, 3, ..., 2 n - 1 <= size - 2
+    seen = np.zeros((ni, nj), dtype=bool)
+    ci, cj = int(rng.integers(0, ni)), int(rng.integers(0, nj))
+    seen[ci, cj] = True
+    w[2 * ci + 1, 2 * cj + 1] = False
+    stack = [(ci, cj)]
+    steps = ((1, 0), (-1, 0), (0, 1), (0, -1))
+    while stack:
+        ci, cj = stack[-1]
+        free = [(di, dj) for di, dj in steps
+                if 0 <= ci + di < ni and 0 <= cj + dj < nj and not seen[ci + di, cj + dj]]
+        if not free:
+            stack.pop()
+            continue
+        di, dj = free[int(rng.integers(0, len(free)))]
+        w[2 * ci + 1 + di, 2 * cj + 1 + dj] = False           # the passage
+        ci, cj = ci + di, cj + dj
+        w[2 * ci + 1, 2 * cj + 1] = False
+        seen[ci, cj] = True
+        stack.append((ci, cj))
+    return w
+
+
+def is_connected(walls) -> bool:
+    """True where every free tile of the layout (bool (H, W)) can be reached from every other through free tiles that
+    share an edge — the moves `act!` can make between tile centres.  A layout without a free tile is not connected."""
+    w = np.asarray(walls) != 0
+    if w.ndim != 2:
+        raise ValueError(f"one layout (H, W) at a time, got {w.shape}")
+    free = np.argwhere(~w)
+    if len(free) == 0:
+        return False
+    H, W = w.shape
+    seen = np.zeros_like(w)
+    start = tuple(free[0])
+    seen[start] = True
+    todo = [start]
+    while todo:
+        i, j = todo.pop()
+        for a, b in ((i + 1, j), (i - 1, j), (i, j + 1), (i, j - 1)):
+            if 0 <= a < H and 0 <= b < W and not w[a, b] and not seen[a, b]:
+                seen[a, b] = True
+                todo.append((a, b))
+    return bool(seen.sum() == len(free))

@@ -139,6 +139,42 @@ class ShardedSingleRoom:
             return
         reset_(self.env, local_mask, seed)
 
+    def set_walls(self, walls, index=None, mask=None) -> None:
+        """`SingleRoom.set_walls` for the sharded batch: `index` and `mask` are GLOBAL (one entry per global agent) and every
+        rank passes the same arguments; each rank hands its engine its slice.  `walls` (H, W) or (M, H, W) is replicated —
+        or, with M == the global batch and no index (agent a takes layout a), sliced.  A batch built with `rng` resets the
+        touched agents from the global generator(s), as `reset_(global_mask=...)` does."""
+        G, lo, hi = self.global_batch, self.first, self.first + self.count
+        w = np.asarray(walls) != 0
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3:
+            raise ValueError(f"walls must be (H, W) or (M, H, W), got {w.shape}")
+        M = w.shape[0]
+        if index is None and M not in (1, G):
+            raise ValueError(f"without an index, walls holds 1 layout or one per global agent ({G}); got {M}")
+        gi = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(G)
+        gm = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(G)
+        if gi is None and M == G and M != 1:
+            local_walls, local_index = w[lo:hi], None                 # agent a takes layout a: this shard's rows
+        else:
+            local_walls, local_index = w, (None if gi is None else gi[lo:hi])
+        if gi is not None and ((gi < 0) | (gi >= M))[np.ones(G, bool) if gm is None else gm != 0].any():
+            raise ValueError(f"layout index not in 0..{M - 1}")     # (also another rank's: every rank refuses alike)
+        self.env.set_walls(local_walls, local_index, None if gm is None else gm[lo:hi])
+        if self.rng is not None:
+            from .single_room import _reset_from_rng
+
+            took = gi if gi is not None else (np.zeros(G, dtype=np.int32) if M == 1 else np.arange(G, dtype=np.int32))
+            if getattr(self.env, "_rng_walls_global", None) is None:
+                ring = np.zeros((G,) + w.shape[1:], dtype=bool)
+                ring[:, [0, -1], :] = True
+                ring[:, :, [0, -1]] = True
+                self.env._rng_walls_global = ring
+            touched = np.ones(G, dtype=bool) if gm is None else gm != 0
+            self.env._rng_walls_global[touched] = w[took[touched]]
+            _reset_from_rng(self.env, self.rng, gm, first=self.first, global_batch=self.global_batch)
+
     # ---- the observation gather over torch.distributed -------------------------------------
     def _as_tensor(self, x):
         import torch

@@ -313,6 +313,11 @@ class SingleRoomWorld:
         env = self._env
         return unpack_tile_map(self.tile_map_chunks, env.cfg.height_tile_map_tu, env.cfg.width_tile_map_tu)
 
+    @property
+    def walls(self) -> np.ndarray:
+        """bool (B, H, W): the WALL layer, `tile_map[:, 0]` — the ring (SR:57-60) and what `set_walls` put inside it."""
+        return self.tile_map[:, WALL - 1]
+
     def rays(self, first: int = 0, count: Optional[int] = None):
         """(ray_stop_position_tu (n, N, 2) int64, ray_hit_dimension (n, N) int64,
         ray_distance_wu (n, N) float32, ray_directions_wu (n, N, 2) float32)  SR:29-31,39."""
@@ -338,7 +343,8 @@ class SingleRoom:
     from which construction and every `reset_(env, rng=...)` draw goal, player tile and heading on the HOST in exactly
     the reference's order (`reference_reset_draws`), injected with `rcw_set_state`.  `device` is the HIP device index.
     `max_episode_steps` (this build's addition; 0 = none, the reference's behaviour) is the episode time limit of
-    `set_time_limit`.
+    `set_time_limit`.  `walls` / `wall_index` (this build's addition; None = the reference's empty room) are `set_walls`'
+    arguments, applied right after construction.
     """
 
     def __init__(
@@ -369,6 +375,8 @@ class SingleRoom:
         render_top_view: bool = False,
         library: Optional[str] = None,
         max_episode_steps: int = 0,
+        walls=None,
+        wall_index=None,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -444,6 +452,16 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        self._rng_walls = None   # bool (B, H, W): each agent's layout, kept for the host-drawn resets of an `rng` environment only
+        if walls is not None:
+            try:
+                self.set_walls(walls, wall_index)
+            except BaseException:
+                self._handle.close()
+                raise
+        elif wall_index is not None:
+            self._handle.close()
+            raise ValueError("wall_index needs walls")
         if max_episode_steps:
             try:
                 self.set_time_limit(max_episode_steps)
@@ -790,6 +808,39 @@ class SingleRoom:
                                                   host_getter=lambda: self.world.episode_steps)
         return self._episode_steps_dev
 
+    # ---- wall layouts (include/rcw.h, rcw_set_walls) ----------------------------------
+    def set_walls(self, walls, index=None, mask=None) -> None:
+        """Interior walls: `walls` is bool / uint8 (H, W) — one layout for every agent — or (M, H, W) with `index` int (B,)
+        naming each agent's layout (None: M == 1, or M == B and agent a takes layout a); `walls[m, i-1, j-1]` is tile (i, j),
+        the index order of `env.world.tile_map[b, 0]`.  `mask`: the agents the call touches (None: all).  The wall ring must
+        be there and two interior tiles free (ValueError otherwise, the environment untouched); `layouts` has generators.
+        The touched agents are reset against the new walls — on the device with the environment's seed, or, for an
+        environment built with `rng`, from that generator on the host (`reference_reset_draws(..., walls=...)`) —, and
+        the walls stay through every later reset, set_state and auto_reset restart until the next call.  Reachability is
+        not checked (`layouts.is_connected`); `set_state` does not know the walls."""
+        H, W, B = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu, self.batch
+        w = np.asarray(walls)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1:] != (H, W):
+            raise ValueError(f"walls must be (H, W) = ({H}, {W}) or (M, {H}, {W}), got {np.asarray(walls).shape}")
+        w = w != 0
+        M = w.shape[0]
+        # tile (i, j) of layout m at m H W + (i - 1) + H (j - 1): (M, W, H) in C order
+        flat = np.ascontiguousarray(w.transpose(0, 2, 1), dtype=np.uint8)
+        ix = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(B)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(B)
+        self._check(self._lib.rcw_set_walls(self._h, _as_ptr(flat), M, _as_ptr(ix), _as_ptr(m)))
+        if self.rng is not None:
+            took = ix if ix is not None else (np.zeros(B, dtype=np.int32) if M == 1 else np.arange(B, dtype=np.int32))
+            if self._rng_walls is None:
+                self._rng_walls = np.zeros((B, H, W), dtype=bool)
+                self._rng_walls[:, [0, -1], :] = True
+                self._rng_walls[:, :, [0, -1]] = True
+            touched = np.ones(B, dtype=bool) if m is None else m != 0
+            self._rng_walls[touched] = w[took[touched]]
+            _reset_from_rng(self, self.rng, m)
+
     def ray_table(self) -> np.ndarray:
         """(nd, 5, N) float32: per heading [dx | dy | |1/dx| | |1/dy| | dir·ray]."""
         out = np.empty((self.cfg.num_directions, 5, self.cfg.num_rays), dtype=self.T)
@@ -924,7 +975,7 @@ class SingleRoom:
 
 
 # ---- the generic functions of RayCastWorlds.jl:7-14 that are on the path ------------------
-def reference_reset_draws(rng, H: int, W: int, nd: int, old_goal=None):
+def reference_reset_draws(rng, H: int, W: int, nd: int, old_goal=None, walls=None):
     """The random draws of ONE `reset!(world)` (SR:110-137) from `rng` (a `numpy.random.Generator`: `integers(lo, hi)`,
     `hi` exclusive), in the reference's order and number:
 
@@ -935,12 +986,28 @@ def reference_reset_draws(rng, H: int, W: int, nd: int, old_goal=None):
 
     A position is ONE draw of a linear index into the column-major region (i = lin mod H + 1, j = lin div H + 1), as
     `rand(rng, ::AbstractArray)` indexes its argument with one `rand(rng, 1:length)`.  Returns (goal_i, goal_j, tile_i,
-    tile_j, heading), tiles 1-based.  `old_goal` is not needed: reset! clears the old goal bit before it draws (SR:118)."""
+    tile_j, heading), tiles 1-based.  `old_goal` is not needed: reset! clears the old goal bit before it draws (SR:118).
+
+    `walls` (bool (H, W), `walls[i-1, j-1]`; None: the wall ring alone, the reference's map) — this build's interior walls
+    (`SingleRoom.set_walls`): the goal pair is drawn AGAIN while its tile is a wall, at most 1024 H W times (then the last pair
+    stays), and the player's tile is occupied where `walls` says so.  On the ring alone no interior tile is a wall: the same
+    draws, in number and value."""
     gi = int(rng.integers(2, H))                     # 2 : H - 1
     gj = int(rng.integers(2, W))
+    if walls is not None:
+        walls = np.asarray(walls) != 0
+        if walls.shape != (H, W):
+            raise ValueError(f"walls must be (H, W) = ({H}, {W}), got {walls.shape}")
+        for _ in range(1024 * H * W):
+            if not walls[gi - 1, gj - 1]:
+                break
+            gi = int(rng.integers(2, H))
+            gj = int(rng.integers(2, W))
 
     def occupied(lin):
         i, j = lin % H + 1, lin // H + 1
+        if walls is not None:
+            return bool(walls[i - 1, j - 1]) or (i == gi and j == gj)
         return i == 1 or i == H or j == 1 or j == W or (i == gi and j == gj)      # any(@view tile_map[:, position]) UT:27
 
     lin = int(rng.integers(0, H * W))                # UT:24
@@ -980,10 +1047,13 @@ def _reset_from_rng(env: "SingleRoom", rng, mask, construction: bool = False, fi
         if gm is not None and not gm[ga]:
             continue
         g = rng[ga] if per_agent else rng
+        a = ga - first
+        layouts = getattr(env, "_rng_walls", None)   # (set_walls on an rng environment: each LOCAL agent's layout; the other shards' agents draw as the caller's global layouts say)
+        gw = getattr(env, "_rng_walls_global", None)
+        w = gw[ga] if gw is not None else (layouts[a] if layouts is not None and 0 <= a < B else None)
         if construction:
             reference_reset_draws(g, H, W, nd)       # SR:62-74: drawn, then overwritten by reset!(world) SR:105
-        gi, gj, ti, tj, d = reference_reset_draws(g, H, W, nd)
-        a = ga - first
+        gi, gj, ti, tj, d = reference_reset_draws(g, H, W, nd, walls=w)
         if 0 <= a < B:
             goal[a] = (gi, gj)
             pos[a] = (env.T(ti - 0.5), env.T(tj - 0.5))  # convert(T, tile - 0.5) SR:125
