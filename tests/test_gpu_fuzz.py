@@ -2,6 +2,7 @@
 fixed seed (map size, columns, headings, field of view, radius, step, camera/image heights, Float32
 and Float64 world units, the unpinned switches, both BoundsError policies, auto-reset, top view)."""
 import os
+import re
 import subprocess
 import sys
 
@@ -25,6 +26,20 @@ def test_random_flat_kernel_geometries_stay_in_parity():
                          capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
     assert "80 random configurations" in res.stdout and ", 0 mismatches" in res.stdout
+
+
+def test_random_time_limits_stay_in_parity():
+    """tools/fuzz_parity.py limit: the geometries of the one-launch step (asked for in every case; maps of 3 x 3 to 40 x 40 tiles, 1 to 1,500
+    view columns, 64 to 512 rows, 1 to 17 agents) with a time limit of 1, 2, 3, 7 or 20 steps, with and without auto_reset, under both
+    BoundsError policies: the *_limit_kernel twins against tests/time_limit_ref.py over the oracle, episode_steps and truncated included.
+    (Seed 31: 21 of the 24 take the one-launch step; 1660 truncations, 358 restarts after a truncation, 3 moves that raised with a counter.)"""
+    res = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "tools", "fuzz_parity.py"), "24", "31", "limit"],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
+    assert "24 random configurations" in res.stdout and ", 0 mismatches" in res.stdout
+    closing = res.stdout.strip().splitlines()[-1]
+    events = {k: int(v) for v, k in re.findall(r"(\d+) (truncations|restarts_after_truncation)\b", closing)}
+    assert events["truncations"] > 0 and events["restarts_after_truncation"] > 0, closing
 
 
 def test_random_sequences_of_api_calls_stay_in_parity():

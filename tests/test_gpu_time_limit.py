@@ -4,7 +4,16 @@ and the limit's own two words — in every form a step takes.
 
 The scenarios (4 x 4 / 4 x 5 rooms, 8 headings, a quarter tile a move, forward-heavy actions, limits of 3 and 4 steps) were rehearsed on
 the oracle alone: each truncates hundreds of times, reaches the goal dozens of times — some of them on the very step the limit is
-reached —, and restarts after either.  Each test asserts from the helper's own event counts that its run did exercise what it claims."""
+reached —, and restarts after either.  Each test asserts from the helper's own event counts that its run did exercise what it claims.
+
+Under RCW_OOB_ERROR (out_of_bounds = 0) the same rooms raise: a quarter-tile move next to the ring tests a neighbourhood that leaves the map.
+The rehearsal of the raising rollouts (24 steps, 64 agents, no invalid actions; the same counts in Float32 and Float64):
+
+    rollout   raised_with_words_kept   steps of the 24 that raise   truncations   terminations   on_the_limit_step   restarts after truncation / done
+    A          84                       19                           258           27             6                   240 / 25
+    WIDE       34                       20                           357           18             8                   350 / 18
+    F64        79                       23                           255           34             7                   234 / 31
+"""
 import numpy as np
 import pytest
 
@@ -25,13 +34,15 @@ ALL = ("truncations", "terminations", "on_the_limit_step", "restarts_after_trunc
 class Limited:
     """engine, oracle and the helper side by side"""
 
-    def __init__(self, rcw, oracle, H, W, N, Hc, L, seed, steps=0, bad_every=0, T="Float32", auto_reset=True, form=None, limit_by="call", **kw):
-        geometry = dict(height_tile_map_tu=H, width_tile_map_tu=W, num_rays=N, height_camera_view_pu=Hc, num_directions=8, out_of_bounds=1, **kw)
+    def __init__(self, rcw, oracle, H, W, N, Hc, L, seed, steps=0, bad_every=0, T="Float32", auto_reset=True, form=None, limit_by="call", batch=B,
+                 out_of_bounds=1, **kw):
+        geometry = dict(height_tile_map_tu=H, width_tile_map_tu=W, num_rays=N, height_camera_view_pu=Hc, num_directions=8, out_of_bounds=out_of_bounds, **kw)
         ctor = dict(max_episode_steps=L) if limit_by == "constructor" else {}
-        self.env = rcw.SingleRoomModule.SingleRoom(batch=B, seed=seed, T=T, auto_reset=auto_reset, position_increment_wu=0.25, **geometry, **ctor)
-        self.orc = oracle.OracleBatch(B, seed=seed, auto_reset=1 if auto_reset else 0, position_increment_wu=0.25, position_increment_wu_f64=0.25,
+        self.env = rcw.SingleRoomModule.SingleRoom(batch=batch, seed=seed, T=T, auto_reset=auto_reset, position_increment_wu=0.25, **geometry, **ctor)
+        self.orc = oracle.OracleBatch(batch, seed=seed, auto_reset=1 if auto_reset else 0, position_increment_wu=0.25, position_increment_wu_f64=0.25,
                                       world_unit_bits=64 if T == "Float64" else 32, **geometry)
         self.rcw, self.steps_planned, self.bad_every, self.top = rcw, steps, bad_every, bool(kw.get("render_top_view"))
+        self.B, self.may_raise, self.steps_that_raised = batch, out_of_bounds == 0, 0
         self.rng = np.random.default_rng(seed + 1)
         self.t = 0
         if form is not None:
@@ -52,7 +63,7 @@ class Limited:
             np.testing.assert_array_equal(env.top_view_host(), orc.top_view, err_msg=f"top view {where}")
 
     def step(self, where, device=None, a=None, check=True):
-        a = TL.draw_actions(self.rng, B, self.t, self.bad_every) if a is None else a
+        a = TL.draw_actions(self.rng, self.B, self.t, self.bad_every) if a is None else a
         valid = bool(((a >= 1) & (a <= 4)).all())
         if device is None:
             device = not valid or self.t % 2 == 1                          # (rcw_step refuses the whole batch: the invalid rows take the device path)
@@ -68,6 +79,17 @@ class Limited:
             with pytest.raises(AssertionError, match="invalid action"):
                 self.env.sync()
             self.env.clear_error()
+        elif self.may_raise:
+            # RCW_OOB_ERROR: a move that tested a tile outside the map raised in the reference.  The engine says so at the next sync, once for
+            # the batch (IndexError), and per agent in the sticky status words: the oracle's, agent for agent.
+            try:
+                self.env.sync()
+            except IndexError:
+                np.testing.assert_array_equal(self.env.world.status, self.orc.status, err_msg=f"status {where}")
+                self.env.clear_error(); self.orc.clear_status()
+                self.steps_that_raised += 1
+            else:
+                assert not (self.orc.status == TL.RCW_ERR_OUT_OF_BOUNDS).any(), f"the oracle raised and the engine did not, {where}: {self.orc.status}"
         if check:
             self.check(where)
 
@@ -100,6 +122,30 @@ def test_step_by_step_against_the_composed_oracle(rcw, oracle, name, case, form,
     s.check(f"{name}: before the first step")
     covered(s.run(name), columns)
     assert s.orc.episode.max() >= 5
+    s.close()
+
+
+RAISED = {"A": (84, 19), "WIDE": (34, 20), "Float64": (79, 23)}             # (raised_with_words_kept, steps of the 24 that raise)
+RAISING = [("A, two launches", A, "two-launches"), ("A, one launch", A, "one-launch"), ("WIDE, two launches", WIDE, "two-launches"),
+           ("WIDE, one launch", WIDE, "one-launch"), ("Float64, the flat fill", F64, None)]
+
+
+@pytest.mark.parametrize("name,case,form", RAISING, ids=[r[0] for r in RAISING])
+def test_a_raising_move_leaves_the_agent_and_keeps_both_words(rcw, oracle, name, case, form):
+    """The "raised in act!" row of DESIGN 4.7 under RCW_OOB_ERROR: the agent is left as it was and episode_steps / truncated are kept (the
+    `LIMIT && !oob` arm of cast_body).  Every step syncs: an IndexError there must come with the oracle's status words, no IndexError with
+    none.  In the one-launch form the forward (or backward) slot of a move that would raise is the current frame: the frames are compared
+    behind every step, the raising ones included.  (The two-launch kernels store the words only where the move did not raise, so the guard
+    decides nothing there that reaches memory: a build without it fails the two one-launch cases alone, through `reborn` and the frames.)"""
+    pytest.importorskip("torch")
+    s = Limited(rcw, oracle, form=form, out_of_bounds=0, **dict(case, steps=24, bad_every=0))
+    if form is None:
+        assert s.env.step_form() == "two-launches" and s.env.fill_kernel_name() == "rcw_fill_flat_kernel"
+    ev = s.run(name)
+    covered(ev, ALL + ("raised_with_words_kept",))
+    assert (ev["raised_with_words_kept"], s.steps_that_raised) == RAISED[name.split(",")[0]]          # (the rehearsal's)
+    if form is not None:
+        assert s.env.step_form() == form
     s.close()
 
 

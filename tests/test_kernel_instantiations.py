@@ -2,7 +2,7 @@
 
 The library picks a template instantiation from the geometry (camera height -> rcw_fill_flat_kernel<ALIGNED, K>; top-view image
 height and pixel scale -> rcw_top_store_flat_kernel<STRADDLE, NARROW, K>; world-unit type and the two unpinned cast_ray switches ->
-<T, TIE, DIST> of the casting / drawing kernels).  The rules are restated here, the case lists below are checked against the
+<T, TIE, DIST> of the casting / drawing kernels; a time limit -> the *_limit_kernel twins of the step's kernels).  The rules are restated here, the case lists below are checked against the
 kernels of the shipped build's ISA (CPU), and each case runs against the oracle (GPU).  tests/kernel_census.sh then counts, under
 rocprofv3, which instantiations the suite really launched (profiles/r04_kernel_census.txt)."""
 import os
@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import time_limit_ref as TL
 from helpers import CFG1, CFG2, assert_state_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,6 +67,9 @@ def test_the_case_lists_cover_every_shipped_instantiation_of_the_flat_kernels():
     assert not [n for n in names if re.match(r"rcw_fill_flat_kernel<[^,>]*,[^,>]*,", n)], names
     # the step's kernels: <T, TIE, DIST> of the cast kernel, <T, TIE, DIST, WAVE> of the one-launch step and of what primes its slots
     for family, count in (("rcw_cast_kernel<", 8), ("rcw_fill256_cast_kernel<", 16), ("rcw_fill_window_cast_kernel<", 16), ("rcw_cast_successors_kernel<", 16)):
+        assert len([n for n in names if n.startswith(family)]) == count, (family, sorted(n for n in names if n.startswith(family)))
+    # ... and their twins with the episode time limit (cast_body<..., LIMIT>), which a step takes while the handle has a limit: 56 kernels
+    for family, count in (("rcw_cast_limit_kernel<", 8), ("rcw_fill256_cast_limit_kernel<", 16), ("rcw_fill_window_cast_limit_kernel<", 16), ("rcw_cast_successors_limit_kernel<", 16)):
         assert len([n for n in names if n.startswith(family)]) == count, (family, sorted(n for n in names if n.startswith(family)))
 
 
@@ -175,6 +179,95 @@ def test_step_kernels_under_every_unpinned_switch(rcw, oracle, T):
                     rcw.reset_(env, mask=mask, seed=8); orc.reset(mask=mask, seed=8)
                     _steps(rcw, env, orc, rng, 4, False)
                     env.close()
+
+
+# ---- the step's kernels with the episode time limit ------------------------------------------------------------------------------
+# 16 agents of a 4 x 4 (96 view columns: a wavefront per agent) or 4 x 5 room (300: a workgroup per agent), 8 headings, a quarter tile a
+# move, a limit of 3 steps, 24 steps of forward-heavy actions with invalid ones every fifth step, a masked reset behind step 12.
+LIMIT_EVENTS = ("truncations", "terminations", "on_the_limit_step", "restarts_after_truncation", "restarts_after_done", "invalid_while_truncated")
+LIMIT_MASK = np.array([1, 0, 1, 1, 0, 0, 1, 0, 1, 0, 1, 1, 0, 0, 1, 0], dtype=np.uint8)
+REHEARSED = {96: (92, 4, 3, 84, 3, 2), 300: (92, 4, 2, 83, 4, 2)}        # LIMIT_EVENTS of the 4 x 4 and of the 4 x 5 room
+
+
+def limit_scenario(N):
+    return dict(H=4, W=4 if N == 96 else 5, N=N, L=3, seed=18, steps=24, bad_every=5, batch=16)
+
+
+def limit_rollout(ref, step, reset):
+    """24 steps of `step(actions)`, `reset(mask, seed)` behind the twelfth; -> the helper's event counts"""
+    rng = np.random.default_rng(18 + 1)
+    for t in range(24):
+        step(TL.draw_actions(rng, 16, t, bad_every=5))
+        if t == 11:
+            assert ref.episode_steps[LIMIT_MASK != 0].any() and (ref.truncated[LIMIT_MASK == 0] != 0).any()   # (the reset has words to zero and words to keep)
+            reset(LIMIT_MASK, 8)
+            ref.clear(LIMIT_MASK); ref.seed = 8                             # (the handle's seed from here on)
+    return ref.events
+
+
+@pytest.mark.parametrize("N", [96, 300])
+def test_the_limit_scenario_reaches_every_event_on_the_oracle_alone(oracle, N):
+    """(CPU) the rehearsal of test_limit_step_kernels_under_every_unpinned_switch, from the helper's own counts.  The dynamics do not read
+    the rays: the counts are the same for Float32 and Float64 and under all four settings of the two switches.
+
+        room    truncations   terminations   on_the_limit_step   restarts after truncation / done   invalid_while_truncated
+        4 x 4   92            4              3                   84 / 3                             2
+        4 x 5   92            4              2                   83 / 4                             2
+    """
+    c = limit_scenario(N)
+    seen = set()
+    for T, tie, dist in (("Float32", 0, 0), ("Float32", 1, 1), ("Float64", 0, 0), ("Float64", 1, 0)):
+        orc = oracle.OracleBatch(16, seed=c["seed"], render=False, auto_reset=1, out_of_bounds=1, num_directions=8, position_increment_wu=0.25,
+                                 position_increment_wu_f64=0.25, world_unit_bits=64 if T == "Float64" else 32, dda_tie_break=tie, dda_distance=dist,
+                                 height_tile_map_tu=c["H"], width_tile_map_tu=c["W"], num_rays=8, height_camera_view_pu=8)
+        ref = TL.TimeLimitRef(orc, c["L"], c["seed"], True)
+        ev = limit_rollout(ref, ref.step, lambda mask, seed: orc.reset(mask=mask, seed=seed))
+        assert all(ev[k] > 0 for k in LIMIT_EVENTS), ev
+        seen.add(tuple(ev[k] for k in LIMIT_EVENTS))
+        orc.close()
+    assert seen == {REHEARSED[N]}, seen
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", ["Float32", "Float64"])
+def test_limit_step_kernels_under_every_unpinned_switch(rcw, oracle, T):
+    """The twin of test_step_kernels_under_every_unpinned_switch with a time limit set: <T, TIE, DIST> of rcw_cast_limit_kernel (the two-launch
+    step) and <T, TIE, DIST, WAVE> of rcw_fill256_cast_limit_kernel / rcw_fill_window_cast_limit_kernel / rcw_cast_successors_limit_kernel (the
+    one-launch step at 256 rows, at the window's other heights — 128 rows, and 512 once — and what primes its slots), under all four settings
+    of the two unpinned cast_ray switches and in both casting shapes.  Every step of the scenario above against tests/time_limit_ref.py over
+    the oracle with the same switches: state, frames, descriptors, episode counter and the limit's two words; each environment must have seen
+    all six kinds of event (rehearsed: test_the_limit_scenario_reaches_every_event_on_the_oracle_alone).
+
+    rcw_fill_kernel_name cannot tell a limit twin from its plain twin — it names the family: the launcher's rule (limit.max_steps > 0) is
+    the selector, and `time_limit == 3` is what this test can assert of it."""
+    pytest.importorskip("torch")
+    from test_gpu_time_limit import Limited
+
+    cases = [(tie, dist, N, form, hc) for tie in (0, 1) for dist in (0, 1) for N in (96, 300)
+             for form, hc in (("one-launch", 256), ("one-launch", 128), ("two-launches", 256))]   # (128 rows: rcw_fill_window_cast_limit_kernel)
+    cases.append((0, 0, 96, "one-launch", 512))                                                 # (512 rows: the window kernel, one window a column)
+    for tie, dist, N, form, hc in cases:
+        c = limit_scenario(N)
+        s = Limited(rcw, oracle, T=T, form=form, Hc=hc, dda_tie_break=tie, dda_distance=dist, **c)
+        where = f"{T} tie {tie} dist {dist} N {N} {form} {hc} rows"
+        assert s.env.step_form() == form and s.env.time_limit == c["L"], where
+        if form == "one-launch":
+            assert s.env.fill_kernel_name() == ("rcw_fill256_cast_kernel" if hc == 256 else "rcw_fill_window_cast_kernel"), where
+        s.check(f"{where}: before the first step")
+
+        def reset(mask, seed, s=s):
+            rcw.reset_(s.env, mask=mask, seed=seed); s.orc.reset(mask=mask, seed=seed)
+
+        def step(a, s=s, where=where):
+            if s.t == 12:
+                s.check(f"{where}: behind the masked reset")
+            s.step(f"{where}, step {s.t}", a=a)
+
+        ev = limit_rollout(s.ref, step, reset)
+        s.check(f"{where}: behind the rollout")
+        assert tuple(ev[k] for k in LIMIT_EVENTS) == REHEARSED[N] and all(ev[k] > 0 for k in LIMIT_EVENTS), (where, ev)
+        assert s.env.step_form() == form, where
+        s.close()
 
 
 @pytest.mark.gpu

@@ -86,9 +86,9 @@ def test_a_raising_move_leaves_the_words(oracle):
     assert words(ref) == ([2], [0], [0])
     ref.step([FORWARD])
     assert orc.status.tolist() == [TL.RCW_ERR_OUT_OF_BOUNDS] and orc.position[0].tolist() == [2.875, 1.5]
-    assert words(ref) == ([2], [0], [0])
+    assert words(ref) == ([2], [0], [0]) and ref.events["raised_with_words_kept"] == 1
     ref.step([LEFT])
-    assert words(ref) == ([3], [1], [0])
+    assert words(ref) == ([3], [1], [0]) and ref.events["raised_with_words_kept"] == 1
 
 
 def test_a_masked_reset_zeroes_the_masked_agents_words(oracle):

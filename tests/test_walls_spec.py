@@ -1,5 +1,5 @@
 """Interior walls on the CPU (include/rcw.h, rcw_set_walls): the export in the header, the bindings and the library; the generator of
-tests/walls_ref.py against the unchanged C oracle on ring-only maps; the development build's device-less validation; the host-rng
+tests/walls_ref.py against the unchanged C oracle on ring-only maps, alone and under the time limit's composition; the development build's device-less validation; the host-rng
 draws with and without walls; the layout generators."""
 import ctypes as C
 import os
@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import time_limit_ref as TL
 import walls_ref as WR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,6 +48,45 @@ def test_the_restated_generator_is_the_oracles_on_a_ring_only_map(rcw, oracle, H
             assert gave_up == (orc.status[a] == WR.RCW_WARN_SAMPLER_GAVE_UP) == ((H, W) == (3, 3))
     assert counts["goal_redraws"] == 0                                       # no interior tile of a ring is a wall: the draw indices did not move
     orc.close()
+
+
+def test_the_time_limit_over_the_reference_worlds_is_the_time_limit_over_the_oracle_on_a_ring_only_map(oracle):
+    """TimeLimitRef(WallsRef) — what tests/test_gpu_walls_time_limit.py compares the engine with — beside TimeLimitRef(OracleBatch), the
+    composition tests/test_gpu_time_limit.py uses, on a 6 x 6 map without interior walls: 16 agents, a limit of 5, 30 steps.  Position bits,
+    heading, goal, done, reward, episode counter and the limit's two words after every step; the restarts after a truncation go through
+    WallsRef.reset(mask, seed) and the generator restated in Python, those after `done` through step_lenient."""
+    B, L, seed = 16, 5, 7
+    walled = WR.WallsRef(B, seed, 6, 6, 8, 8, nd=8, inc=0.25, radius=0.3, render=False)
+    orc = oracle.OracleBatch(B, seed=seed, render=False, height_tile_map_tu=6, width_tile_map_tu=6, num_rays=8, height_camera_view_pu=8, num_directions=8,
+                             auto_reset=1, position_increment_wu=0.25, player_radius_wu=0.3)
+    a, b = TL.TimeLimitRef(walled, L, seed, True), TL.TimeLimitRef(orc, L, seed, True)
+    rng = np.random.default_rng(seed + 1)
+    for t in range(30):
+        actions = TL.draw_actions(rng, B, t)
+        a.step(actions); b.step(actions)
+        np.testing.assert_array_equal(walled.position.view(np.uint32), orc.position.view(np.uint32), err_msg=f"position, step {t}")
+        np.testing.assert_array_equal(walled.direction, orc.direction, err_msg=f"heading, step {t}")
+        np.testing.assert_array_equal(walled.goal, orc.goal, err_msg=f"goal, step {t}")
+        np.testing.assert_array_equal(walled.done, orc.done, err_msg=f"done, step {t}")
+        np.testing.assert_array_equal(walled.reward, orc.reward, err_msg=f"reward, step {t}")
+        np.testing.assert_array_equal(walled.episode, orc.episode, err_msg=f"episode, step {t}")
+        np.testing.assert_array_equal(a.episode_steps, b.episode_steps, err_msg=f"episode_steps, step {t}")
+        np.testing.assert_array_equal(a.truncated, b.truncated, err_msg=f"truncated, step {t}")
+    assert a.events == b.events and all(a.events[k] > 0 for k in ("truncations", "terminations", "restarts_after_truncation", "restarts_after_done")), a.events
+    assert walled.events["restarts_after_done"] == a.events["restarts_after_done"] and walled.events["goal_redraws"] == 0
+    assert not walled.status.any() and not orc.status.any()
+    orc.close()
+
+
+@pytest.mark.parametrize("name", ["ROOMS", "WIDE", "MAZE", "F64"])
+def test_the_limited_rollouts_on_walled_maps_reach_what_they_claim(rcw, name):
+    """the rehearsal of tests/test_gpu_walls_time_limit.py without the frames: the dynamics alone give the counts its docstring quotes"""
+    import test_gpu_walls_time_limit as G
+
+    events = G.rollout(name, render=False)[2]
+    assert tuple(events[k] for k in G.COLUMNS) == G.REHEARSED[name], events
+    assert events["goal_redraws_on_truncation_restarts"] > 0 and events["restarts_after_truncation"] == events["truncations"] > 0
+    assert (events["restarts_after_done"] > 0) == (name != "MAZE")
 
 
 def test_the_numpy_blocks_of_the_generator_are_its_python_integers(rcw):

@@ -11,8 +11,12 @@ each agent in the header's order:
                                     two words; every other one counts — blocked or not, goal or not — and
                                     truncated = (episode_steps >= L and not done).
 With L = 0 the helper is step_lenient and two arrays of zeros.  The status words step_lenient leaves on the agents of rule 2 (their action
-0 is "invalid" to the oracle) are the helper's business: `status` is not part of what is compared.  `events` counts what a rollout
-exercised, so that a test can insist that its scenario reaches the restart and the coincidence step."""
+0 is "invalid" to the oracle) are the helper's business: it takes them back, so that `orc.status` stays the sticky word the engine keeps
+(rcw_status) and a test of RCW_OOB_ERROR can compare the two.  `events` counts what a rollout exercised, so that a test can insist that
+its scenario reaches the restart and the coincidence step; raised_with_words_kept: agents whose step raised while episode_steps > 0.
+
+The oracle may be oracle.OracleBatch or anything with its B, done, status, reset(mask, seed), step_lenient and clear_status
+(tests/walls_ref.py's WallsRef: the limit on a walled map)."""
 import numpy as np
 
 RCW_ERR_OUT_OF_BOUNDS = -5
@@ -22,7 +26,7 @@ class TimeLimitRef:
     def __init__(self, orc, limit, seed, auto_reset):
         self.orc, self.seed, self.auto_reset = orc, int(seed), bool(auto_reset)
         self.events = dict(truncations=0, terminations=0, on_the_limit_step=0, restarts_after_truncation=0, restarts_after_done=0,
-                           invalid_while_truncated=0)
+                           invalid_while_truncated=0, raised_with_words_kept=0)
         self.set_time_limit(limit)
 
     def set_time_limit(self, limit):
@@ -56,6 +60,7 @@ class TimeLimitRef:
         sent = a.copy()
         sent[re_t] = 0
         orc.step_lenient(sent)
+        orc.status[re_t] = 0                                                   # (the helper's action 0, not the caller's: nothing was invalid)
         raised = orc.status == RCW_ERR_OUT_OF_BOUNDS                           # (act! raised: "the agent is left exactly as it was")
         orc.status[...] = np.where(orc.status != 0, orc.status, status0)       # (sticky, as the oracle keeps it)
         stepped = valid & ~re_t & ~re_d & ~raised
@@ -70,6 +75,7 @@ class TimeLimitRef:
         ev["terminations"] += int((stepped & done).sum())
         ev["restarts_after_truncation"] += int(re_t.sum())
         ev["restarts_after_done"] += int(re_d.sum())
+        ev["raised_with_words_kept"] += int((valid & ~re_t & ~re_d & raised & (self.episode_steps > 0)).sum())
 
 
 def draw_actions(rng, batch, step, bad_every=0):

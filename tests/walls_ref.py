@@ -14,6 +14,8 @@ Two pieces, both independent of the engine's code:
                     blocked_next_to_interior_wall   moves the reference refused because the player would touch a wall tile inside the ring
                     goal_redraws                    goal pairs drawn again because the pair before fell on a wall
                     restarts_after_done             agents re-sampled by a step because they were done
+                  step_lenient and clear_status are the two further calls tests/time_limit_ref.py makes of an oracle:
+                  TimeLimitRef(WallsRef(...), L, seed, True) is the time limit on a walled map, without a second reference.
 """
 import numpy as np
 
@@ -22,6 +24,7 @@ from oracle import pyref
 M64 = (1 << 64) - 1
 GOLDEN = 0x9E3779B97F4A7C15
 RCW_WARN_SAMPLER_GAVE_UP = 1
+RCW_ERR_INVALID_ACTION = -2
 
 
 # ---- csrc/rcw_rng.h ------------------------------------------------------------------------------------------------------------
@@ -217,23 +220,39 @@ class WallsRef:
             self.worlds[b].set_state(goal[b], pos[b], heading[b])
             self._account_rays(b)
 
+    def _step_agent(self, b, act):
+        w = self.worlds[b]
+        if self.auto_reset and w.done:
+            self.events["restarts_after_done"] += 1
+            self._reset_agent(b)
+            return
+        if act in (1, 2):                                                       # the move act! is about to test (UT:16-17), against the interior walls alone
+            d = w.directions[w.dir]
+            s = 1 if act == 1 else -1
+            new = (w.pos[0] + w.inc * d[0], w.pos[1] + w.inc * d[1]) if s == 1 else (w.pos[0] - w.inc * d[0], w.pos[1] - w.inc * d[1])
+            inner = [[1 < i < self.H and 1 < j < self.W and bool(w.tile_map[pyref.WALL][i][j]) for j in range(self.W + 1)] for i in range(self.H + 1)]
+            if not pyref.is_player_colliding(w.tile_map[pyref.GOAL], new, w.radius, self.T) and pyref.is_player_colliding(inner, new, w.radius, self.T):
+                self.events["blocked_next_to_interior_wall"] += 1
+        w.step(act)
+        self._account_rays(b)
+
     def step(self, actions):
         a = np.asarray(actions).reshape(self.B)
-        for b, w in enumerate(self.worlds):
-            if self.auto_reset and w.done:
-                self.events["restarts_after_done"] += 1
-                self._reset_agent(b)
-                continue
-            act = int(a[b])
-            if act in (1, 2):                                                   # the move act! is about to test (UT:16-17), against the interior walls alone
-                d = w.directions[w.dir]
-                s = 1 if act == 1 else -1
-                new = (w.pos[0] + w.inc * d[0], w.pos[1] + w.inc * d[1]) if s == 1 else (w.pos[0] - w.inc * d[0], w.pos[1] - w.inc * d[1])
-                inner = [[1 < i < self.H and 1 < j < self.W and bool(w.tile_map[pyref.WALL][i][j]) for j in range(self.W + 1)] for i in range(self.H + 1)]
-                if not pyref.is_player_colliding(w.tile_map[pyref.GOAL], new, w.radius, self.T) and pyref.is_player_colliding(inner, new, w.radius, self.T):
-                    self.events["blocked_next_to_interior_wall"] += 1
-            w.step(act)
-            self._account_rays(b)
+        for b in range(self.B):
+            self._step_agent(b, int(a[b]))
+
+    def step_lenient(self, actions):
+        """rcw_step_device's rule, as the oracle's step_lenient has it: an agent whose action is outside 1..4 is not stepped — not restarted
+        either — and its status word says so; every other agent steps as in `step`."""
+        a = np.asarray(actions).reshape(self.B)
+        for b in range(self.B):
+            if 1 <= int(a[b]) <= 4:
+                self._step_agent(b, int(a[b]))
+            else:
+                self.status[b] = RCW_ERR_INVALID_ACTION
+
+    def clear_status(self):
+        self.status[...] = 0
 
     # ---- the batched arrays, in the engine's shapes and types ---------------------------------------------------------------------
     @property

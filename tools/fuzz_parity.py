@@ -3,10 +3,15 @@
 configurations (map size, columns, headings, field of view, radius, step, camera height, image
 height, world-unit type, the three unpinned switches, both BoundsError policies, auto-reset).
 
-    python tools/fuzz_parity.py [configs] [seed] [top|split|flat]   # "top": every configuration renders the top view;
+    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit]
+                                                                   # "top": every configuration renders the top view;
                                                                    # "split": ... with a geometry of the unit store kernels;
                                                                    # "flat": ... of the flat store kernel (any pu >= 9), and any
                                                                    #         camera height from 24 rows (the flat fill kernel)
+                                                                   # "step": the geometries of the one-launch step, asked for in every case
+                                                                   # "limit": ... of at most 17 agents and 512 rows, with an episode time limit of
+                                                                   #         1, 2, 3, 7 or 20 steps: the rollout against tests/time_limit_ref.py over
+                                                                   #         the oracle, episode_steps and truncated compared with the rest
 """
 import os
 import sys
@@ -16,6 +21,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import numpy as np
 
 import raycastworlds_jl_amd as RCW
+import time_limit_ref as TL
 from helpers import assert_state_equal
 from oracle import oracle as O
 
@@ -26,6 +32,8 @@ split_geometry = len(sys.argv) > 3 and sys.argv[3] == "split"   # geometries of 
 flat_geometry = len(sys.argv) > 3 and sys.argv[3] == "flat"     # geometries of the flat store kernel; the two-kernel form is asked for
 step_geometry = len(sys.argv) > 3 and sys.argv[3] == "step"     # what the one-launch step takes (a camera view of 256 k / 128 / 64 rows, no top view), asked for in every case:
                                                                 # 1 .. 1,500 view columns (a wavefront per agent, a workgroup per agent, the table's tail), maps of up to 40 x 40 tiles
+limit_geometry = len(sys.argv) > 3 and sys.argv[3] == "limit"   # "step"'s draw with a time limit (rcw_set_time_limit): the *_limit_kernel twins of the step's kernels
+limit_events = {}
 one_launch_steps = 0
 two_kernel_forms = 0                                            # (rcw_set_top_view_form: by default it is taken only from 256 MiB a step)
 fails = 0
@@ -48,6 +56,11 @@ for c in range(n_cfg):
               pu_per_tu=int(rng.choice([4, 8, 13, 32, 40, 52] if always_top else [4, 8, 13, 32])))
     R = str(rng.choice(["Float32", "Float64", "Int32", "Int64"]))
     B = int(rng.integers(1, 40))
+    if limit_geometry:                                      # (draws of its own: the other modes' stay what they were for a given seed)
+        kw.update(height_camera_view_pu=int(rng.choice([256, 256, 256, 64, 128, 512])), render_top_view=False, num_rays=int(rng.choice([1, 7, 64, 100, 255, 256, 257, 333, 512, 700, 1024, 1100, 1500])),
+                  height_tile_map_tu=int(rng.integers(3, 41)), width_tile_map_tu=int(rng.integers(3, 41)))
+        B = int(rng.choice([1, 3, 4, 5, 17]))
+        L = int(rng.choice([1, 2, 3, 7, 20]))
     if step_geometry:
         kw.update(height_camera_view_pu=int(rng.choice([256, 256, 256, 64, 128, 512, 768, 1024, 2048])), render_top_view=False, num_rays=int(rng.choice([1, 7, 64, 100, 255, 256, 257, 333, 512, 700, 1024, 1100, 1500])),
                   height_tile_map_tu=int(rng.integers(3, 41)), width_tile_map_tu=int(rng.integers(3, 41)))
@@ -83,13 +96,21 @@ for c in range(n_cfg):
         env = RCW.SingleRoomModule.SingleRoom(batch=B, seed=seed, T="Float64" if T64 else "Float32", R=R, **kw)
         orc = O.OracleBatch(B, seed=seed, **okw)
         assert_state_equal(env, orc, rays=True, where="create")
+        ref = None
+        if limit_geometry:
+            env.set_time_limit(L)
+            ref = TL.TimeLimitRef(orc, L, seed, kw["auto_reset"])
+
+        def words(where):
+            np.testing.assert_array_equal(env.world.episode_steps, ref.episode_steps, err_msg=f"episode_steps {where}")
+            np.testing.assert_array_equal(env.world.truncated.astype(np.uint8), ref.truncated, err_msg=f"truncated {where}")
         if kw["render_top_view"] and (split_geometry or flat_geometry or rng.integers(0, 2)):
             try:
                 env.set_top_view_form("two-kernels", runs=int(rng.integers(0, 4)))
                 two_kernel_forms += 1
             except Exception:                                  # the geometry does not take it: the automatic form stays
                 pass
-        if step_geometry or rng.integers(0, 2):               # the one-launch step (these batches are below where the rule takes it by itself)
+        if step_geometry or limit_geometry or rng.integers(0, 2):               # the one-launch step (these batches are below where the rule takes it by itself)
             try:
                 env.set_step_form("one-launch")
                 one_launch_steps += 1
@@ -113,6 +134,8 @@ for c in range(n_cfg):
             d = rng.integers(0, kw["num_directions"], B).astype(np.int32)
             env.set_state(goal, pos, d)
             orc.set_state(goal, pos, d)
+            if ref is not None:
+                ref.clear()
             assert_state_equal(env, orc, rays=True, where="set_state with arbitrary poses")
         for s in range(int(rng.integers(5, 60))):
             if rng.integers(0, 12) == 0:                       # a masked reset with a fresh seed now and then
@@ -120,9 +143,17 @@ for c in range(n_cfg):
                 sd = int(rng.integers(0, 2**31))
                 RCW.reset_(env, mask=mask, seed=sd)
                 orc.reset(mask=mask, seed=sd)
+                if ref is not None:
+                    ref.clear(mask); ref.seed = sd
+                    assert_state_equal(env, orc, rays=True, where=f"masked reset in front of step {s}")
+                    np.testing.assert_array_equal(env.world.episode, orc.episode)
+                    words(f"masked reset in front of step {s}")
             a = rng.integers(1, 5, B).astype(np.uint8)
             RCW.act_(env, a)
-            assert orc.step(a) == 0
+            if ref is not None:
+                ref.step(a)                                    # (both BoundsError policies: the helper reads who raised from the status words)
+            else:
+                assert orc.step(a) == 0
             try:
                 env.sync()
             except IndexError:
@@ -130,13 +161,18 @@ for c in range(n_cfg):
                 env.clear_error(); orc.clear_status()
         assert_state_equal(env, orc, rays=True, where="rollout")
         np.testing.assert_array_equal(env.world.episode, orc.episode)
+        if ref is not None:
+            words("rollout")
+            for k, v in ref.events.items():
+                limit_events[k] = limit_events.get(k, 0) + v
         if kw["render_top_view"]:
             np.testing.assert_array_equal(env.top_view_host(), orc.top_view)
         env.close(); orc.close()
     except Exception as e:   # noqa: BLE001
         fails += 1
-        print(f"config {c} FAILED: T64={T64} R={R} B={B} seed={seed} {kw}\n   {type(e).__name__}: {str(e)[:300]}")
+        print(f"config {c} FAILED: T64={T64} R={R} B={B} seed={seed}{f' L={L}' if limit_geometry else ''} {kw}\n   {type(e).__name__}: {str(e)[:300]}")
         if fails >= 5:
             break
-print(f"{n_cfg} random configurations ({two_kernel_forms} with the two-kernel top view asked for and taken, {one_launch_steps} with the one-launch step), {fails} mismatches")
+limit_words = "; time limit: " + ", ".join(f"{v} {k}" for k, v in limit_events.items()) if limit_geometry else ""
+print(f"{n_cfg} random configurations ({two_kernel_forms} with the two-kernel top view asked for and taken, {one_launch_steps} with the one-launch step{limit_words}), {fails} mismatches")
 sys.exit(1 if fails else 0)
