@@ -344,6 +344,54 @@ RCW_API int rcw_truncated_device_ptr(rcw_handle* h, void** device_ptr);
  * indices, every sequence what it was. */
 RCW_API int rcw_set_walls(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
                           const int32_t* layout_index_host, const uint8_t* mask_host);
+/* ---- the goal distance (this build's addition: the reference's only signal is the reward of 1 at the goal) ------------------------
+ * Opt-in per handle: the shortest-path distance to the goal through the walls, kept on the device for every agent behind every call
+ * that moves an agent, a goal or a wall — what potential-based shaping, SPL and a distance-map target need, at no host
+ * synchronisation.  A handle that never enables it runs exactly the kernels it ran before.  The ABI is additive: RCW_ABI_VERSION and
+ * rcw_config are what they were.
+ * For agent a, with `walls` the WALL layer of its tile map, g its goal tile (rcw_goal) and t the player's tile — wu_to_tu of its
+ * position (utils.jl:5): floor(x) + 1, floor(y) + 1, the same in Float64 worlds —:
+ *   field            UInt16 (H*W, B), tile (i, j), 1-based, of agent a at a*H*W + (i-1) + H*(j-1) — the tile map's own linear order, the
+ *                    one rcw_set_walls takes.  The breadth-first distance in tiles from g, moving between tiles that share an edge and
+ *                    whose WALL bit is clear; the GOAL bit plays no part.  field[g] = 0; walls and tiles that cannot be reached hold
+ *                    0xFFFF; if g itself is a wall (rcw_set_state put it there, or the sampler gave up) every entry is 0xFFFF.
+ *                    rcw_create bounds H*W + 2H <= 65280, so every real distance is below 0xFFFF.
+ *   distance         Int32 (B): field[t], or -1 where that is 0xFFFF or t is off the map (the kernel checks and never reads outside
+ *                    the field).
+ *   start_distance   Int32 (B): distance as of the start of the agent's current episode — SPL is success * l / max(p, l) with l this
+ *                    word and p the path taken.
+ *   progress         Int32 (B): what the last call brought the agent closer by, in tiles; positive means closer.
+ * What each call does to them — stream-ordered on the handle's stream, behind everything the call already queues:
+ *   rcw_set_goal_distance(h, 1)   allocates, computes the field of every agent, distance from it, start_distance = distance,
+ *                                 progress = 0; on a handle that has it, the same again.  An allocation failure leaves what was there.
+ *   rcw_set_goal_distance(h, 0)   frees it (RCW_OK also where there was none).
+ *   rcw_reset, rcw_set_state, rcw_set_state64, rcw_set_walls
+ *                                 for the agents in the call's mask: field recomputed, distance new, start_distance = distance,
+ *                                 progress = 0; an agent outside the mask keeps every byte of its field and its three words.
+ *                                 rcw_set_state does not move the episode counter: the mask decides here, not the counter.
+ *   rcw_step, rcw_step_device     an agent the call restarted (its episode counter, rcw_episode, differs from the one recorded at its
+ *                                 last flood: done or truncated under cfg.auto_reset): field recomputed against the new goal, distance
+ *                                 new, start_distance = distance, progress = 0.  Every other agent: progress = old - new if both
+ *                                 distances are >= 0, else 0; distance = new; start_distance kept.  The rule needs no knowledge of the
+ *                                 action: an invalid device action, a raising move under RCW_OOB_ERROR, a turn and a blocked move
+ *                                 leave the tile — progress 0.
+ *   rcw_cast_rays, rcw_update_camera_view, rcw_update_top_view, rcw_set_direction_table*, rcw_set_step_form, rcw_set_time_limit, the
+ *   learner-view calls and every getter   nothing.
+ * A replayed HIP graph of a step works like any step: nothing about this alternates on the host, the recorded episode counter lives on the
+ * device.  The device pointers are stable until the next rcw_set_goal_distance.  The kernel (one launch, rcw_goal_distance_kernel) runs
+ * behind the step's own and OUTSIDE rcw_profile's events: cast_ms + top_view_ms + fill_ms is what it was.
+ *   rcw_goal_distance_enabled            0 / 1.
+ *   rcw_goal_distance                    host copies of the three words (any pointer may be NULL); waits for the stream as rcw_done does.
+ *   rcw_goal_distance_device_ptr         the three arrays where they live (any pointer may be NULL).
+ *   rcw_goal_distance_field              the fields of agents [first, first+count) to host memory, H*W UInt16 each (waits for the stream).
+ *   rcw_goal_distance_field_device_ptr   the field batch in DEVICE memory.
+ * The last four return RCW_ERR_UNSUPPORTED on a handle that has not enabled it. */
+RCW_API int rcw_set_goal_distance(rcw_handle* h, int32_t enable);
+RCW_API int rcw_goal_distance_enabled(rcw_handle* h, int32_t* out);
+RCW_API int rcw_goal_distance(rcw_handle* h, int32_t* distance /* (B) */, int32_t* start_distance /* (B) */, int32_t* progress /* (B) */);
+RCW_API int rcw_goal_distance_device_ptr(rcw_handle* h, void** distance, void** start_distance, void** progress);
+RCW_API int rcw_goal_distance_field(rcw_handle* h, int32_t first, int32_t count, void* out_host /* UInt16 (H*W, count) */);
+RCW_API int rcw_goal_distance_field_device_ptr(rcw_handle* h, void** ptr);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

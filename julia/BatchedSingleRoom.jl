@@ -382,6 +382,42 @@ end
 # (no RLBase verb in the reference; the device form mirrors is_terminated_device)
 is_truncated(env::RCW.RLBaseEnv{E}) where {E <: BatchedSingleRoom} = truncated(env.env)
 is_truncated_device(env::BatchedSingleRoom) = (ptr = truncated_device_ptr(env), eltype = UInt8, dims = (env.batch,))
+# ---- the goal distance (this build's addition; include/rcw.h, rcw_set_goal_distance) -------------------------------------------
+"""
+    set_goal_distance!(env, on = true)
+
+Keep every agent's shortest-path distance to its goal (breadth-first through its walls, in tiles) on the device, behind every
+`act!`, `reset!`, `set_state!` and `set_walls!`: `goal_distance(env)` returns `(distance, start_distance, progress)`, each
+`Vector{Int32}` of `batch` (`-1`: no path); `goal_distance_field(env)` the `UInt16` fields as `(H, W, batch)`, `0xFFFF` for
+walls and tiles without a path.  Shaping is `reward .+ c .* progress`.
+"""
+function set_goal_distance!(env::BatchedSingleRoom, on::Bool = true)
+    check(ccall((:rcw_set_goal_distance, librcw), Cint, (Ptr{Cvoid}, Int32), env.handle, on ? 1 : 0))
+    return nothing
+end
+function goal_distance_enabled(env::BatchedSingleRoom)
+    n = Ref{Int32}(0)
+    check(ccall((:rcw_goal_distance_enabled, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}), env.handle, n)); n[] != 0
+end
+function goal_distance(env::BatchedSingleRoom)
+    d, s, p = (Vector{Int32}(undef, env.batch) for _ in 1:3)
+    check(ccall((:rcw_goal_distance, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), env.handle, d, s, p))
+    return (distance = d, start_distance = s, progress = p)
+end
+function goal_distance_device_ptr(env::BatchedSingleRoom)
+    d, s, p = (Ref{Ptr{Cvoid}}(C_NULL) for _ in 1:3)
+    check(ccall((:rcw_goal_distance_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                env.handle, d, s, p))
+    return (distance = d[], start_distance = s[], progress = p[])
+end
+function goal_distance_field(env::BatchedSingleRoom, first::Integer = 0, count::Integer = env.batch - first)
+    out = Array{UInt16, 3}(undef, env.config.height_tile_map_tu, env.config.width_tile_map_tu, count)
+    check(ccall((:rcw_goal_distance_field, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}), env.handle, first, count, out)); out
+end
+function goal_distance_field_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_goal_distance_field_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
 
 # per-agent sticky status: 0, -5 where the reference would have raised BoundsError, -2 for an invalid device action,
 # 1 (a warning) where sample_empty_position gave up after max_tries and returned an occupied tile (utils.jl:34 @warns there)

@@ -146,6 +146,12 @@ SIGNATURES = {
     "rcw_learner_view_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_learner_view_copy": [_vp, _vp, _i32, _i32],
     "rcw_expand_columns_view": [_vp, _vp, _vp, _i32, _vp],
+    "rcw_set_goal_distance": [_vp, _i32],
+    "rcw_goal_distance_enabled": [_vp, C.POINTER(_i32)],
+    "rcw_goal_distance": [_vp, _vp, _vp, _vp],
+    "rcw_goal_distance_device_ptr": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+    "rcw_goal_distance_field": [_vp, _i32, _i32, _vp],
+    "rcw_goal_distance_field_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_ray_table": [_vp, _vp],
     "rcw_direction_table": [_vp, _vp],
     "rcw_timer_start": [_vp],

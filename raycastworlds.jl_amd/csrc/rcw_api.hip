@@ -211,6 +211,13 @@ struct rcw_handle {
         size_t agent_bytes() const { return (size_t)set.frames * view.C * set.h * set.w; }   // one agent's whole output: its k frames
         uint8_t* batch() const { return set.frames > 1 ? stack.get<uint8_t>() : frame.get<uint8_t>(); }   // what the caller sees
     } learner;
+    // The goal distance (rcw_set_goal_distance): the UInt16 (H*W, B) field, the three Int32 (B) words — one allocation, `words` points into
+    // it — and each agent's episode counter as of the flood its field holds (uint32 [B]).  Empty while the feature is off.
+    struct GoalDistance {
+        RcwBuf field, word_buf, last_episode;
+        RcwGoalWords words{};
+        bool on() const { return field.get() != nullptr; }
+    } goal;
     ~rcw_handle();
 };
 
@@ -384,7 +391,8 @@ hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const u
 
 // What a render does to the k-frame stack (include/rcw.h, "the frame stack"): a step pushes, reset! / set_state / a new view or direction
 // table refill the (masked) agents' slots, a re-render of the very same frames (rcw_set_step_form) leaves it alone.
-enum StackOp { kStackPush, kStackRefill, kStackKeep };
+// kStackRefillSameWorld: a refill behind which no agent's world differs (a new direction table): the frames are new, goal and walls are not.
+enum StackOp { kStackPush, kStackRefill, kStackRefillSameWorld, kStackKeep };
 
 // the learner view of the handle's current descriptors (the unmasked agents' only), on the handle's stream; with a frame stack the view
 // kernel's frame is the staging batch and the push kernel follows it
@@ -394,17 +402,27 @@ hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
     if (lv.set.frames < 2 || op == kStackKeep)
         return rcw_launch_view(h->dev, lv.view, h->dev.col_h, h->dev.col_c, h->B, mask_dev, lv.frame.get<uint8_t>(), h->stream);
     return rcw_launch_view_stack(h->dev, lv.view, h->dev.col_h, h->dev.col_c, h->B, lv.set.frames, mask_dev, lv.frame.get<uint8_t>(),
-                                 lv.stack.get<uint8_t>(), h->dev.episode, lv.last_episode.get<uint32_t>(), op == kStackRefill, h->stream);
+                                 lv.stack.get<uint8_t>(), h->dev.episode, lv.last_episode.get<uint32_t>(), op != kStackPush, h->stream);
 }
 
 // A step, reset! or set_state's render: the camera view (launch_step_camera), then the learner view where the handle has one.  With
 // RCW_VIEW_ONLY the cast kernel is followed by the view kernel alone (the top view, if any, in its stand-alone form between them);
 // profiling events: start | after cast | after the top view | after the view kernel.
+// Last of all, and OUTSIDE the profiling bracket (cast_ms + top_view_ms + fill_ms is what it was), the goal distance where the handle has
+// enabled it: behind a step (the episode counter decides who floods) or a reset / set_state / set_walls (the mask decides).
+hipError_t launch_goal_distance(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
+{
+    if (!h->goal.on() || op == kStackKeep || op == kStackRefillSameWorld) return hipSuccess;
+    return rcw_launch_goal_distance(h->dev, h->B, mask_dev, op == kStackRefill, h->goal.field.get<uint16_t>(), h->goal.words,
+                                    h->goal.last_episode.get<uint32_t>(), h->stream);
+}
+
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op)
 {
     if (!h->learner.only()) {
-        const hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
-        return e == hipSuccess && h->learner.on() ? launch_view(h, mask_dev, op) : e;
+        hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
+        if (e == hipSuccess && h->learner.on()) e = launch_view(h, mask_dev, op);
+        return e == hipSuccess ? launch_goal_distance(h, mask_dev, op) : e;
     }
     h->step.obs_unknown();                                        // (the camera view is not painted)
     const Bracket prof(&h->prof);
@@ -416,7 +434,8 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if (h->dev.top_view && (e = launch_top_view(h, mask_dev, false, [](hipStream_t) { return hipSuccess; })) != hipSuccess) return e;
     if ((e = prof.mark(2, h->stream)) != hipSuccess) return e;
     if ((e = launch_view(h, mask_dev, op)) != hipSuccess) return e;
-    return prof.done(h->stream);
+    if ((e = prof.done(h->stream)) != hipSuccess) return e;
+    return launch_goal_distance(h, mask_dev, op);
 }
 
 // Every stream that may hold work of the handle — the side stream, its own, the caller's current one — is waited for; the first failure comes back.
@@ -1224,7 +1243,7 @@ int set_direction_table_impl(rcw_handle* h, const T* directions_wu, std::vector<
         return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the (direction, ray) table failed");
     }
     int rc = upload_tables(h); if (rc) return rc;
-    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));   // re-render
+    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefillSameWorld));   // re-render
     return RCW_OK;
 }
 }  // extern "C++"
@@ -1776,6 +1795,84 @@ int rcw_learner_view_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32
     const size_t per = h->learner.agent_bytes();
     RCW_HIP(hipMemcpy(out_host, h->learner.batch() + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
     return rc;
+}
+
+// The goal distance (include/rcw.h).  Enabling allocates and floods every agent at once, stream-ordered behind what is queued; enabling
+// again does the same again; an allocation failure leaves what was there.
+int rcw_set_goal_distance(rcw_handle* h, int32_t enable)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::GoalDistance& gd = h->goal;
+    if (!enable && !gd.on()) return RCW_OK;
+    rcw_handle::GoalDistance fresh;
+    if (enable) {
+        const size_t B = (size_t)h->B, bytes = B * (size_t)h->dev.H * (size_t)h->dev.W * sizeof(uint16_t);
+        hipError_t e = fresh.field.hipMalloc(bytes);
+        if (e == hipSuccess) e = fresh.word_buf.hipMalloc(3 * B * sizeof(int32_t));
+        if (e == hipSuccess) e = fresh.last_episode.hipMalloc(B * sizeof(uint32_t));
+        if (e != hipSuccess) return fail(hip_code(e), "goal distance field of %zu bytes: %s", bytes, hip_failure(e));
+        int32_t* const w = fresh.word_buf.get<int32_t>();
+        fresh.words = RcwGoalWords{w, w + B, w + 2 * B};
+    }
+    RCW_HIP(replace_buffers(h, {&gd.field, &gd.word_buf, &gd.last_episode}, {&fresh.field, &fresh.word_buf, &fresh.last_episode}));
+    gd.words = fresh.words;
+    if (gd.on()) RCW_HIP(launch_goal_distance(h, nullptr, kStackRefill));
+    return RCW_OK;
+}
+
+int rcw_goal_distance_enabled(rcw_handle* h, int32_t* out)
+{
+    if (!h || !out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = h->goal.on() ? 1 : 0;
+    return RCW_OK;
+}
+
+extern "C++" {
+namespace {
+int need_goal_distance(rcw_handle* h) { return h->goal.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no goal distance (rcw_set_goal_distance)"); }
+}  // namespace
+}  // extern "C++"
+
+int rcw_goal_distance(rcw_handle* h, int32_t* distance, int32_t* start_distance, int32_t* progress)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_goal_distance(h); if (rc) return rc;
+    rc = sync_and_check(h);
+    const size_t bytes = (size_t)h->B * sizeof(int32_t);
+    const RcwGoalWords& w = h->goal.words;
+    if (distance) RCW_HIP(hipMemcpy(distance, w.distance, bytes, hipMemcpyDeviceToHost));
+    if (start_distance) RCW_HIP(hipMemcpy(start_distance, w.start_distance, bytes, hipMemcpyDeviceToHost));
+    if (progress) RCW_HIP(hipMemcpy(progress, w.progress, bytes, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int rcw_goal_distance_device_ptr(rcw_handle* h, void** distance, void** start_distance, void** progress)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = need_goal_distance(h); if (rc) return rc;
+    if (distance) *distance = h->goal.words.distance;
+    if (start_distance) *start_distance = h->goal.words.start_distance;
+    if (progress) *progress = h->goal.words.progress;
+    return RCW_OK;
+}
+
+int rcw_goal_distance_field(rcw_handle* h, int32_t first, int32_t count, void* out_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_goal_distance(h); if (rc) return rc;
+    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
+    rc = sync_and_check(h);
+    const size_t per = (size_t)h->dev.H * (size_t)h->dev.W;
+    RCW_HIP(hipMemcpy(out_host, h->goal.field.get<uint16_t>() + (size_t)first * per, (size_t)count * per * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int rcw_goal_distance_field_device_ptr(rcw_handle* h, void** ptr)
+{
+    if (!h || !ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = need_goal_distance(h); if (rc) return rc;
+    *ptr = h->goal.field.get();
+    return RCW_OK;
 }
 
 int rcw_expand_columns_view(rcw_handle* h, const int32_t* height_line_pu_device, const uint8_t* colour_id_device,

@@ -174,3 +174,16 @@ hipError_t rcw_launch_view_stack(const RcwPlan& p, const RcwView& v, const int32
                                  const uint8_t* mask_dev, uint8_t* staged, uint8_t* stack, const uint32_t* episode, uint32_t* last_episode,
                                  bool refill, hipStream_t s);
 int rcw_view_full_eligible(const RcwDev& p, int C, int hwc);   // the full-resolution kernel takes this geometry and layout
+
+// The goal distance (rcw_set_goal_distance, rcw_goal_distance.hip): the three Int32 (B) words beside the UInt16 (H*W, B) field.
+struct RcwGoalWords {
+    int32_t* distance;       // field[player's tile], -1: unreachable or off the map
+    int32_t* start_distance; // ... as of the start of the agent's episode
+    int32_t* progress;       // what the last call brought the agent closer by
+};
+// One launch behind a step (refill = false: an agent whose episode counter differs from last_episode floods, every other one looks its tile
+// up and takes progress = old - new) or behind reset / set_state / set_walls / enabling (refill = true: the agents of the mask — NULL: all —
+// flood and take start_distance = distance, progress = 0; the others are left alone).  Reads p's state arrays, writes only its own buffers.
+size_t rcw_goal_distance_lds_bytes(const RcwDev& p);
+hipError_t rcw_launch_goal_distance(const RcwDev& p, int32_t B, const uint8_t* mask_dev, bool refill, uint16_t* field, const RcwGoalWords& words,
+                                    uint32_t* last_episode, hipStream_t s);

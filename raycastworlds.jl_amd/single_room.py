@@ -344,7 +344,7 @@ class SingleRoom:
     the reference's order (`reference_reset_draws`), injected with `rcw_set_state`.  `device` is the HIP device index.
     `max_episode_steps` (this build's addition; 0 = none, the reference's behaviour) is the episode time limit of
     `set_time_limit`.  `walls` / `wall_index` (this build's addition; None = the reference's empty room) are `set_walls`'
-    arguments, applied right after construction.
+    arguments, applied right after construction.  `goal_distance` (this build's addition) is `set_goal_distance(True)` after them.
     """
 
     def __init__(
@@ -377,6 +377,7 @@ class SingleRoom:
         max_episode_steps: int = 0,
         walls=None,
         wall_index=None,
+        goal_distance: bool = False,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -468,6 +469,12 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        if goal_distance:
+            try:
+                self.set_goal_distance(True)
+            except BaseException:
+                self._handle.close()
+                raise
         # colour fields of the reference struct SR:241-256
         self.floor_color = cfg.floor_color
         self.ceiling_color = cfg.ceiling_color
@@ -494,7 +501,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -807,6 +814,75 @@ class SingleRoom:
             self._episode_steps_dev = DeviceArray(p.value, (self.batch,), np.uint32, self, self._sync,
                                                   host_getter=lambda: self.world.episode_steps)
         return self._episode_steps_dev
+
+    # ---- the goal distance (include/rcw.h, rcw_set_goal_distance) ----------------------
+    def set_goal_distance(self, on: bool = True) -> None:
+        """Keep each agent's shortest-path distance to its goal on the device: the breadth-first distance in tiles through the agent's
+        walls (`goal_distance_field`), looked up at the player's tile after every call (`goal_distance`, -1: unreachable), its value at
+        the start of the episode (`goal_start_distance`: SPL's path length) and what the last step gained (`goal_progress`: potential-
+        based shaping is `r + c * env.goal_progress.torch(sync=False)`).  Follows resets, `set_state`, `set_walls` and `auto_reset`
+        restarts with no host synchronisation.  Switching it on (again) recomputes everything and makes the current state the
+        episode's start; the device arrays handed out before are invalid after every call."""
+        self.__dict__.pop("_goal_distance_dev", None)
+        self._check(self._lib.rcw_set_goal_distance(self._h, 1 if on else 0))
+
+    @property
+    def goal_distance_enabled(self) -> bool:
+        n = C.c_int32()
+        self._check(self._lib.rcw_goal_distance_enabled(self._h, C.byref(n)))
+        return bool(n.value)
+
+    def _goal_distance_host(self, which: int) -> np.ndarray:
+        out = np.empty(self.batch, dtype=np.int32)
+        args = [None, None, None]
+        args[which] = _as_ptr(out)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_goal_distance(self._h, *args))
+        return out
+
+    def _goal_distance_arrays(self):
+        if getattr(self, "_goal_distance_dev", None) is None:
+            p = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+            self._check(self._lib.rcw_goal_distance_device_ptr(self._h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])))
+            self._goal_distance_dev = tuple(
+                DeviceArray(p[k].value, (self.batch,), np.int32, self, self._sync, host_getter=lambda k=k: self._goal_distance_host(k))
+                for k in range(3))
+        return self._goal_distance_dev
+
+    @property
+    def goal_distance(self) -> DeviceArray:
+        """int32 (B,) in device memory: tiles from the player's tile to the goal through the walls; -1 where there is no path (or the
+        player is off the map).  Rewritten behind every step, reset, `set_state` and `set_walls` in stream order."""
+        return self._goal_distance_arrays()[0]
+
+    @property
+    def goal_start_distance(self) -> DeviceArray:
+        """int32 (B,): `goal_distance` as of the start of each agent's current episode."""
+        return self._goal_distance_arrays()[1]
+
+    @property
+    def goal_progress(self) -> DeviceArray:
+        """int32 (B,): tiles the last step brought each agent closer to its goal (negative: farther); 0 for an agent the call restarted
+        or reset, and where either distance is -1."""
+        return self._goal_distance_arrays()[2]
+
+    @property
+    def goal_distance_field(self) -> np.ndarray:
+        """uint16 (B, H, W), a host copy: `field[b, i-1, j-1]` is the distance of tile (i, j) from agent b's goal, 0xFFFF for walls and
+        tiles without a path — indexed like `env.world.walls`."""
+        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
+        out = np.empty((self.batch, W, H), dtype=np.uint16)                # tile (i, j) at (i - 1) + H (j - 1)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_goal_distance_field(self._h, 0, self.batch, _as_ptr(out)))
+        return np.ascontiguousarray(out.transpose(0, 2, 1))
+
+    def goal_distance_field_device(self) -> DeviceArray:
+        """The field where it lives: uint16 (B, W, H) in device memory — the tile map's own order, `[b, j-1, i-1]`."""
+        p = C.c_void_p()
+        self._check(self._lib.rcw_goal_distance_field_device_ptr(self._h, C.byref(p)))
+        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
+        return DeviceArray(p.value, (self.batch, W, H), np.uint16, self, self._sync,
+                           host_getter=lambda: np.ascontiguousarray(self.goal_distance_field.transpose(0, 2, 1)))
 
     # ---- wall layouts (include/rcw.h, rcw_set_walls) ----------------------------------
     def set_walls(self, walls, index=None, mask=None) -> None:
