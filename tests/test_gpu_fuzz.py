@@ -42,6 +42,27 @@ def test_random_time_limits_stay_in_parity():
     assert events["truncations"] > 0 and events["restarts_after_truncation"] > 0, closing
 
 
+def test_random_goal_distances_stay_in_parity():
+    """tools/fuzz_parity.py goal: maps of 3 x 4 to 48 x 48 tiles and one in six of 64 to 140 on a side, the ring / four rooms / a maze /
+    pillars / the serpentine per agent or shared, 1 to 17 agents (1 to 4 on the maps of 64 and more on a side: the reference's Python floods
+    are the cost, and agents are cut before the map size), Float32 and Float64, both forms of the step, auto_reset on and off, a
+    time limit of 0, 2, 5 or 20; 30 random calls each (steps, masked and full resets, masked set_state and set_walls, the feature off and
+    on), the three words and every agent's field against tests/goal_distance_ref.py after every call.
+    (Seed 54: 88 floods behind a step, 63 agent-steps at distance -1, 336 steps, 70 full and 86 masked resets, 72 set_state, 81 set_walls, 75 times off
+    and on, the widest level 177 tiles, 4 of the 24 maps with H W a multiple of 32, 8 configurations with the one-launch step.)"""
+    res = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "tools", "fuzz_parity.py"), "24", "54", "goal"],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
+    assert "24 random configurations" in res.stdout and ", 0 mismatches" in res.stdout
+    closing = res.stdout.strip().splitlines()[-1]
+    print(closing)
+    totals = {k: int(v) for v, k in re.findall(r"(\d+) ([a-z_0-9]+)\b", closing[closing.index("goal distance:"):closing.rindex(")")])}
+    assert set(totals) == {"floods_behind_a_step", "agent_steps_at_distance_minus_1", "step", "reset", "masked_reset", "set_state", "set_walls", "off_and_on",
+                           "widest_level", "tiles_multiple_of_32", "tiles_not_multiple_of_32", "one_launch_steps", "two_launch_steps"}, closing
+    assert all(v > 0 for v in totals.values()), closing
+    assert totals["widest_level"] > 64, closing
+
+
 def test_random_sequences_of_api_calls_stay_in_parity():
     """tools/api_fuzz.py: 12 handles x 50 random calls — steps with host / device / scalar actions, masked and full resets,
     injected states, rejected actions, another stream, another output buffer, another top-view form, another form of the step (one launch / two), stand-alone

@@ -3,7 +3,7 @@
 configurations (map size, columns, headings, field of view, radius, step, camera height, image
 height, world-unit type, the three unpinned switches, both BoundsError policies, auto-reset).
 
-    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit]
+    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit|goal]
                                                                    # "top": every configuration renders the top view;
                                                                    # "split": ... with a geometry of the unit store kernels;
                                                                    # "flat": ... of the flat store kernel (any pu >= 9), and any
@@ -12,6 +12,9 @@ height, world-unit type, the three unpinned switches, both BoundsError policies,
                                                                    # "limit": ... of at most 17 agents and 512 rows, with an episode time limit of
                                                                    #         1, 2, 3, 7 or 20 steps: the rollout against tests/time_limit_ref.py over
                                                                    #         the oracle, episode_steps and truncated compared with the rest
+                                                                   # "goal": the goal distance (rcw_set_goal_distance) — random maps, layouts and
+                                                                   #         sequences of calls against tests/goal_distance_ref.py, the three words and
+                                                                   #         every agent's whole field compared after every call (goal_mode below)
 """
 import os
 import sys
@@ -20,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
 
+import goal_distance_ref as GD
 import raycastworlds_jl_amd as RCW
 import time_limit_ref as TL
 from helpers import assert_state_equal
@@ -33,6 +37,107 @@ flat_geometry = len(sys.argv) > 3 and sys.argv[3] == "flat"     # geometries of 
 step_geometry = len(sys.argv) > 3 and sys.argv[3] == "step"     # what the one-launch step takes (a camera view of 256 k / 128 / 64 rows, no top view), asked for in every case:
                                                                 # 1 .. 1,500 view columns (a wavefront per agent, a workgroup per agent, the table's tail), maps of up to 40 x 40 tiles
 limit_geometry = len(sys.argv) > 3 and sys.argv[3] == "limit"   # "step"'s draw with a time limit (rcw_set_time_limit): the *_limit_kernel twins of the step's kernels
+
+
+def goal_mode(n_cfg, seed):
+    """Maps of 3 x 4 to 48 x 48 tiles, one in six 64 to 140 on a side (levels wider than a wavefront; at most 4 agents there: the Python
+    floods of the reference are the cost); the ring, four rooms, a maze, pillars at 0.05 to 0.35 or the serpentine, one layout per agent
+    or one for all; 1 to 17 agents, Float32 and Float64, both forms of the step asked for, auto_reset on and off, a time limit of 0, 2, 5
+    or 20.  Then 30 random calls — a step, a masked or full reset_, a masked set_state to random free tiles, a masked set_walls, the
+    feature off and on again —, everything compared by GD.Tracked after each.  Every configuration draws from a generator of its own,
+    default_rng([seed, c]): what it is does not depend on the ones before it."""
+    from raycastworlds_jl_amd import _capi, layouts
+
+    rng = None
+
+    def layout(H, W):
+        kind = str(rng.choice(["ring", "four_rooms", "maze", "pillars", "serpentine"]))
+        if kind in ("four_rooms", "maze") and min(H, W) < 5:
+            kind = "ring"
+        w = {"ring": lambda: layouts.ring(H, W), "four_rooms": lambda: layouts.four_rooms(H, W), "maze": lambda: layouts.maze(H, W, rng),
+             "pillars": lambda: GD.pillars(H, W, float(rng.uniform(0.05, 0.35)), rng), "serpentine": lambda: GD.serpentine(H, W)}[kind]()
+        return w if (~w).sum() >= 2 else layouts.ring(H, W)                  # (rcw_set_walls wants two free tiles)
+
+    def world(B, H, W):
+        return np.stack([layout(H, W) for _ in range(B)]) if rng.integers(0, 2) else layout(H, W)
+
+    def some(B):
+        mask = (rng.random(B) < 0.5).astype(np.uint8)
+        mask[int(rng.integers(0, B))] = 1
+        return mask
+
+    totals = dict(floods_behind_a_step=0, agent_steps_at_distance_minus_1=0, step=0, reset=0, masked_reset=0, set_state=0, set_walls=0, off_and_on=0,
+                  widest_level=0, tiles_multiple_of_32=0, tiles_not_multiple_of_32=0, one_launch_steps=0, two_launch_steps=0)
+    fails = 0
+    for c in range(n_cfg):
+        rng = np.random.default_rng([seed, c])
+        big = rng.integers(0, 6) == 0
+        H, W = (int(rng.integers(64, 141)), int(rng.integers(64, 141))) if big else (int(rng.integers(3, 49)), int(rng.integers(4, 49)))
+        B = int(rng.integers(1, 5 if big else 18))
+        T64, auto_reset, L = bool(rng.integers(0, 2)), bool(rng.integers(0, 2)), int(rng.choice([0, 2, 5, 20]))
+        N, Hc = [(8, 24), (16, 64), (64, 256), (7, 128)][int(rng.integers(0, 4))]
+        form = str(rng.choice(["one-launch", "two-launches"]))
+        engine_seed = int(rng.integers(0, 2**31))
+        where = f"config {c}: {H} x {W}, B={B} T64={T64} auto_reset={auto_reset} L={L} N={N} Hc={Hc} {form} seed={engine_seed}"
+        try:
+            env = RCW.SingleRoomModule.SingleRoom(batch=B, seed=engine_seed, T="Float64" if T64 else "Float32", auto_reset=auto_reset, height_tile_map_tu=H,
+                                                  width_tile_map_tu=W, num_rays=N, height_camera_view_pu=Hc, num_directions=8, position_increment_wu=0.25,
+                                                  player_radius_wu=0.3)
+            try:
+                env.set_step_form(form)
+            except _capi.RcwError as e:                        # the one refusal there is: this geometry does not take the one-launch step
+                assert form == "one-launch" and e.code == _capi.RCW_ERR_UNSUPPORTED and "does not take the one-launch step" in e.message, e
+                form = "two-launches"
+            assert env.step_form() == form
+            totals["one_launch_steps" if form == "one-launch" else "two_launch_steps"] += 1
+            totals["tiles_multiple_of_32" if H * W % 32 == 0 else "tiles_not_multiple_of_32"] += 1
+            env.set_walls(world(B, H, W))
+            env.set_time_limit(L)
+            t = GD.Tracked(RCW, env)
+            for k in range(30):
+                call = str(rng.choice(["step", "step", "step", "step", "reset", "masked_reset", "set_state", "set_walls", "off_and_on"]))
+                at = f"{where}, call {k} ({call})"
+                totals[call] += 1
+                if call == "step":
+                    t.step(rng.integers(1, 5, B).astype(np.uint8), at)
+                elif call in ("reset", "masked_reset"):
+                    mask = some(B) if call == "masked_reset" else None
+                    RCW.reset_(env, mask=mask, seed=int(rng.integers(0, 2**31)))
+                    t.masked(mask, at)
+                elif call == "set_state":
+                    mask, w = some(B), env.world
+                    goal, pos, heading = w.goal_position, w.player_position_wu, w.player_direction_au
+                    for b in np.flatnonzero(mask):
+                        free = np.argwhere(~t._walls[b])
+                        goal[b] = free[int(rng.integers(0, len(free)))] + 1
+                        pos[b] = free[int(rng.integers(0, len(free)))] + 0.5
+                        heading[b] = int(rng.integers(0, 8))
+                    env.set_state(goal, pos, heading, mask=mask)
+                    t.masked(mask, at)
+                elif call == "set_walls":
+                    mask = some(B)
+                    env.set_walls(world(B, H, W), mask=mask)
+                    t.masked(mask, at)
+                else:
+                    env.set_goal_distance(False)
+                    assert not env.goal_distance_enabled
+                    env.set_goal_distance(True)
+                    t.masked(None, at)
+            totals["floods_behind_a_step"] += t.floods["step"]
+            totals["agent_steps_at_distance_minus_1"] += t.events["unreachable"]
+            totals["widest_level"] = max(totals["widest_level"], t.widest["step"], t.widest["refill"])
+            env.close()
+        except Exception as e:   # noqa: BLE001
+            fails += 1
+            print(f"{where} FAILED\n   {type(e).__name__}: {str(e)[:400]}")
+            if fails >= 5:
+                break
+    print(f"{n_cfg} random configurations (goal distance: " + ", ".join(f"{v} {k}" for k, v in totals.items()) + f"), {fails} mismatches")
+    return 1 if fails else 0
+
+
+if len(sys.argv) > 3 and sys.argv[3] == "goal":
+    sys.exit(goal_mode(n_cfg, int(sys.argv[2])))
 limit_events = {}
 one_launch_steps = 0
 two_kernel_forms = 0                                            # (rcw_set_top_view_form: by default it is taken only from 256 MiB a step)
