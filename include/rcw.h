@@ -441,8 +441,25 @@ RCW_API int rcw_expand_columns(rcw_handle* h, const int32_t* height_line_pu_devi
  *   RCW_VIEW_GRAY8: Y = (77 R + 150 G + 29 B + 128) >> 8 of each pixel, averaged the same way (reference colours: ceiling 255,
  *                  floor 64, walls 128 / 192, goal 39 / 58);
  *   at (h, w) = (H, N) the RGB view is the camera view's bytes, transposed to rows first.  The handle's configured colours apply.
- * Layouts: RCW_VIEW_CHW (B, C, h, w) or RCW_VIEW_HWC (B, h, w, C), C order (Julia sees (w, h, C, B) / (C, w, h, B)); gray has
- * C = 1 and both layouts are the same bytes.
+ * The depth plane (bit 2 of the format: "a depth plane D follows the colour planes").  RCW_VIEW_DEPTH8: C = 1, D alone; RCW_VIEW_RGBD8
+ * (= RCW_VIEW_RGB8 | 4): C = 4, R, G, B, D; RCW_VIEW_GRAYD8 (= RCW_VIEW_GRAY8 | 4): C = 2, Y, D.  Format 3 and every value from 7 up:
+ * RCW_ERR_INVALID_ARGUMENT.  D is inverse depth, exact in integers.  For image column k of an agent let hl be its height_line_pu (the
+ * descriptor rcw_columns hands out) and pad its column padding (hl >= H - 1: 0; otherwise min((H - hl) / 2, H), rounded down): rows
+ * [0, pad) show the ceiling, [pad, H - pad) the column's colour, the rows from max(pad, H - pad) on the floor — the rule the colour
+ * planes follow.  Pixel (y, k) has an inverse depth of u pixels,
+ *   u = min(max(hl, 0), H)           where pad <= y < H - pad (the colour's rows: the height of the column's line, clipped),
+ *   u = H - 2 min(y, H - 1 - y)      on the ceiling and floor rows: the height a line would need for y to be its first or last row,
+ *                                    i.e. the inverse depth of the ceiling or floor point seen through that pixel,
+ * and the full-size byte is D(y, k) = (255 u + floor(H / 2)) / H, rounded down: 255 = at or nearer than the distance at which a wall
+ * fills the column, 0 = infinitely far.  At reduced sizes D is averaged over the same boxes with the same rounding as the colour
+ * channels, (S + floor(n/2)) / n.  What follows: D(y, k) = D(H - 1 - y, k) wherever pad <= H / 2; a column with pad = 0 is one value;
+ * the colour planes of RCW_VIEW_RGBD8 / RCW_VIEW_GRAYD8 are byte for byte the RCW_VIEW_RGB8 / RCW_VIEW_GRAY8 view.  Approximately (the
+ * integer rule above is the contract) D / 255 = d0 / perpendicular distance, clipped at 1, with d0 = camera_height_tile_wu * num_rays
+ * / (2 semi_field_of_view_wu * H) — camera_height_tile_wu / (2 semi_field_of_view_wu) where the view is as high as it is wide, as
+ * height_line_pu counts square pixels of a view num_rays wide.  Layouts, sizes, flags, the frame stack and every rule below about when
+ * the view is written are those of the colour formats with this C.
+ * Layouts: RCW_VIEW_CHW (B, C, h, w) or RCW_VIEW_HWC (B, h, w, C), C order (Julia sees (w, h, C, B) / (C, w, h, B)); gray and depth
+ * have C = 1 and both layouts are the same bytes.
  * RCW_VIEW_ONLY: a step is the cast kernel followed by the view kernel — the UInt32 camera view is NOT written by steps (see
  * rcw_obs_device_ptr; rcw_update_camera_view renders it on demand), the step takes two launches (rcw_step_form) and
  * rcw_set_step_form(h, RCW_STEP_ONE_LAUNCH) returns RCW_ERR_UNSUPPORTED.  The top view, if enabled, is rendered as before.
@@ -477,6 +494,9 @@ RCW_API int rcw_expand_columns(rcw_handle* h, const int32_t* height_line_pu_devi
 #define RCW_VIEW_OFF   0
 #define RCW_VIEW_RGB8  1
 #define RCW_VIEW_GRAY8 2
+#define RCW_VIEW_DEPTH8 4  /* bit 2: a depth plane follows the colour planes */
+#define RCW_VIEW_RGBD8  5  /* RCW_VIEW_RGB8 | RCW_VIEW_DEPTH8 */
+#define RCW_VIEW_GRAYD8 6  /* RCW_VIEW_GRAY8 | RCW_VIEW_DEPTH8 */
 #define RCW_VIEW_CHW   0
 #define RCW_VIEW_HWC   1
 #define RCW_VIEW_ONLY  1   /* flag: no camera view in the step */

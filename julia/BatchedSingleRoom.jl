@@ -44,6 +44,9 @@ const RCW_GATHER_FRAMES = Int32(1)
 const RCW_VIEW_OFF = Int32(0)      # rcw_set_learner_view: format
 const RCW_VIEW_RGB8 = Int32(1)
 const RCW_VIEW_GRAY8 = Int32(2)
+const RCW_VIEW_DEPTH8 = Int32(4)   # bit 2: a depth plane follows the colour planes
+const RCW_VIEW_RGBD8 = Int32(5)
+const RCW_VIEW_GRAYD8 = Int32(6)
 const RCW_VIEW_CHW = Int32(0)      # ... layout (C order; Julia sees the axes reversed)
 const RCW_VIEW_HWC = Int32(1)
 const RCW_VIEW_ONLY = Int32(1)     # ... flag: steps skip the UInt32 camera view
@@ -554,18 +557,19 @@ expand_columns!(env::BatchedSingleRoom, height_line_pu_device::Ptr{Int32}, colou
                 env.handle, height_line_pu_device, colour_id_device, count, frames_device))
 
 #####
-##### the learner view: UInt8 RGB / gray, area-averaged to (h, w), rendered by every reset / step (include/rcw.h)
+##### the learner view: UInt8 RGB / gray / inverse depth, area-averaged to (h, w), rendered by every reset / step (include/rcw.h)
 #####
 
-# format = :gray | :rgb | :off; size = (h, w) with h <= height_camera_view_pu, w <= num_rays; layout = :chw | :hwc;
+# format = :gray | :rgb | :depth (inverse depth, one plane) | :rgbd (R, G, B, D) | :grayd (Y, D) | :off; size = (h, w) with h <= height_camera_view_pu, w <= num_rays; layout = :chw | :hwc;
 # camera_view = false: steps skip the UInt32 camera view (RCW_VIEW_ONLY).  Renders the current state at once.
 # stack = k (1 .. 16, :chw only): the view holds each agent's last k frames, slot 1 the oldest (Julia sees (w, h, k C, B)); the engine
 # shifts it at every step and fills all k slots with the new frame at reset!, set_state! and when auto_reset restarts the agent.
 function set_learner_view!(env::BatchedSingleRoom; format::Symbol = :gray,
                            size::Tuple{Integer, Integer} = (env.config.height_camera_view_pu, env.config.num_rays),
                            layout::Symbol = :chw, camera_view::Bool = true, stack::Integer = 1)
-    fmt = format === :gray ? RCW_VIEW_GRAY8 : format === :rgb ? RCW_VIEW_RGB8 : format === :off ? RCW_VIEW_OFF :
-          throw(ArgumentError("format must be :gray, :rgb or :off"))
+    fmt = format === :gray ? RCW_VIEW_GRAY8 : format === :rgb ? RCW_VIEW_RGB8 : format === :depth ? RCW_VIEW_DEPTH8 :
+          format === :rgbd ? RCW_VIEW_RGBD8 : format === :grayd ? RCW_VIEW_GRAYD8 : format === :off ? RCW_VIEW_OFF :
+          throw(ArgumentError("format must be :gray, :rgb, :depth, :rgbd, :grayd or :off"))
     lay = layout === :chw ? RCW_VIEW_CHW : layout === :hwc ? RCW_VIEW_HWC : throw(ArgumentError("layout must be :chw or :hwc"))
     flags = camera_view ? Int32(0) : RCW_VIEW_ONLY
     stack == 1 && return check(ccall((:rcw_set_learner_view, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32),
@@ -589,7 +593,7 @@ end
 function learner_view_dims(env::BatchedSingleRoom)
     v = learner_view_info(env)
     v.format == RCW_VIEW_OFF && error("no learner view: call set_learner_view! first")
-    C = v.format == RCW_VIEW_RGB8 ? 3 : 1
+    C = ((v.format & Int32(3)) == RCW_VIEW_RGB8 ? 3 : (v.format & Int32(3)) == RCW_VIEW_GRAY8 ? 1 : 0) + ((v.format & RCW_VIEW_DEPTH8) != 0 ? 1 : 0)
     return v.layout == RCW_VIEW_CHW ? (Int(v.width), Int(v.height), learner_view_stack(env) * C, env.batch) : (C, Int(v.width), Int(v.height), env.batch)
 end
 function learner_view_device_ptr(env::BatchedSingleRoom)

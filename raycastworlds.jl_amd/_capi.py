@@ -30,6 +30,7 @@ RCW_UNIQUE_ID_BYTES = 128
 RCW_TOP_VIEW_NONE, RCW_TOP_VIEW_IN_PLACE, RCW_TOP_VIEW_ONE_KERNEL, RCW_TOP_VIEW_TWO_KERNELS = 0, 1, 2, 3
 RCW_STEP_TWO_LAUNCHES, RCW_STEP_ONE_LAUNCH = 1, 2   # rcw_step_form / rcw_set_step_form
 RCW_VIEW_OFF, RCW_VIEW_RGB8, RCW_VIEW_GRAY8 = 0, 1, 2   # rcw_set_learner_view: format
+RCW_VIEW_DEPTH8, RCW_VIEW_RGBD8, RCW_VIEW_GRAYD8 = 4, 5, 6   # ... bit 2: a depth plane follows the colour planes
 RCW_VIEW_CHW, RCW_VIEW_HWC = 0, 1                      # ... layout
 RCW_VIEW_ONLY = 1                                      # ... flag: no camera view in the step
 RCW_VIEW_MAX_FRAMES = 16                               # rcw_set_learner_view_stack: frames

@@ -1681,15 +1681,18 @@ namespace {
 // device) and the box tables — or the refusal.  Host arithmetic only: no HIP call, and nothing of a handle changes.
 struct ViewPlan {
     RcwView v{};
-    std::vector<int32_t> tab;      // rows [h + 1], then columns [w + 1]; empty: RCW_VIEW_OFF
+    std::vector<int32_t> tab;      // rows [h + 1], then columns [w + 1], then (depth formats) RcwView::dsum [Hc + 1]; empty: RCW_VIEW_OFF
 };
+
+// the channels of a format: its colour's, then the depth plane's
+int view_channels(int32_t format) { return ((format & 3) == RCW_VIEW_RGB8 ? 3 : (format & 3) == RCW_VIEW_GRAY8 ? 1 : 0) + (format & RCW_VIEW_DEPTH8 ? 1 : 0); }
 
 int plan_learner_view(const rcw_config& cfg, const RcwDev& dev, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags,
                       int32_t frames, ViewPlan* plan)
 {
     const int Hc = cfg.height_camera_view_pu, N = cfg.num_rays;
-    if (format != RCW_VIEW_OFF && format != RCW_VIEW_RGB8 && format != RCW_VIEW_GRAY8)
-        return fail(RCW_ERR_INVALID_ARGUMENT, "format must be RCW_VIEW_OFF / RCW_VIEW_RGB8 / RCW_VIEW_GRAY8 (got %d)", format);
+    if (format < RCW_VIEW_OFF || format > RCW_VIEW_GRAYD8 || format == (RCW_VIEW_RGB8 | RCW_VIEW_GRAY8))
+        return fail(RCW_ERR_INVALID_ARGUMENT, "format must be RCW_VIEW_OFF / RCW_VIEW_RGB8 / RCW_VIEW_GRAY8 / RCW_VIEW_DEPTH8 / RCW_VIEW_RGBD8 / RCW_VIEW_GRAYD8 (got %d)", format);
     if (flags & ~RCW_VIEW_ONLY) return fail(RCW_ERR_INVALID_ARGUMENT, "unknown learner view flags 0x%x", (unsigned)flags);
     if (format == RCW_VIEW_OFF && flags) return fail(RCW_ERR_INVALID_ARGUMENT, "RCW_VIEW_ONLY needs a format");
     if (frames < 1 || frames > RCW_VIEW_MAX_FRAMES)
@@ -1699,16 +1702,17 @@ int plan_learner_view(const rcw_config& cfg, const RcwDev& dev, int32_t format, 
         return fail(RCW_ERR_INVALID_ARGUMENT, "layout must be RCW_VIEW_CHW or RCW_VIEW_HWC (got %d)", layout);
     if (height < 1 || height > Hc || width < 1 || width > N)
         return fail(RCW_ERR_INVALID_ARGUMENT, "learner view size %d x %d outside 1..%d x 1..%d (no up-sampling)", height, width, Hc, N);
-    if (frames > 1 && (long long)(format == RCW_VIEW_RGB8 ? 3 : 1) * height * width >= (1ll << 31))
+    if (frames > 1 && (long long)view_channels(format) * height * width >= (1ll << 31))
         return fail(RCW_ERR_UNSUPPORTED, "a stack of frames of 2 GiB or more");
     if (frames > 1 && layout != RCW_VIEW_CHW)
         return fail(RCW_ERR_UNSUPPORTED, "a stack of %d frames needs RCW_VIEW_CHW (slot s is channels [s C, (s + 1) C))", frames);
     RcwView& v = plan->v;
-    v.C = format == RCW_VIEW_RGB8 ? 3 : 1;
+    v.C = view_channels(format);
+    v.depth = format & RCW_VIEW_DEPTH8 ? 1 : 0;
     v.hwc = layout == RCW_VIEW_HWC ? 1 : 0;
     v.h = height; v.w = width;
     std::vector<int32_t>& t = plan->tab;
-    try { t.resize((size_t)height + width + 2); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    try { t.resize((size_t)height + width + 2 + (v.depth ? (size_t)Hc + 1 : 0)); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation failed"); }
     long long max_rows = 0, max_cols = 0;
     for (int r = 0; r <= height; ++r) t[r] = (int32_t)((long long)r * Hc / height);
     for (int c = 0; c <= width; ++c) t[(size_t)height + 1 + c] = (int32_t)((long long)c * N / width);
@@ -1717,6 +1721,13 @@ int plan_learner_view(const rcw_config& cfg, const RcwDev& dev, int32_t format, 
     const long long n = max_rows * max_cols;
     v.wide = n * 256 + n >= (1ll << 31) ? 1 : 0;          // (a box's channel sum + n/2 must stay below 2^31 for 32-bit sums)
     v.full_ok = height == Hc && width == N && rcw_view_full_eligible(dev, v.C, v.hwc) ? 1 : 0;
+    if (v.depth) {
+        // the ceiling / floor depth byte De(y) = (255 u + Hc/2) / Hc, u = Hc - 2 min(y, Hc - 1 - y) (include/rcw.h), summed over rows [0, y):
+        // at most 255 * 2^20
+        int32_t* const ds = t.data() + (size_t)height + width + 2;
+        ds[0] = 0;
+        for (int y = 0; y < Hc; ++y) ds[y + 1] = ds[y] + (int32_t)((255ll * (Hc - 2 * std::min(y, Hc - 1 - y)) + Hc / 2) / Hc);
+    }
     return RCW_OK;
 }
 }  // namespace
@@ -1743,6 +1754,7 @@ int rcw_set_learner_view_stack(rcw_handle* h, int32_t format, int32_t layout, in
             return fail(hip_code(e), "learner view buffer of %zu bytes: %s", bytes * (size_t)frames, hip_failure(e));
         fresh.view.rows = fresh.tab.get<int32_t>();
         fresh.view.cols = fresh.tab.get<int32_t>() + height + 1;
+        fresh.view.dsum = plan.v.depth ? fresh.tab.get<int32_t>() + height + width + 2 : nullptr;
     }
     RCW_HIP(replace_buffers(h, {&lv.frame, &lv.tab, &lv.stack, &lv.last_episode}, {&fresh.frame, &fresh.tab, &fresh.stack, &fresh.last_episode}));   // (the new ones, or none: the view switched off)
     lv.set = fresh.set;

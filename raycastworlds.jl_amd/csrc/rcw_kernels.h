@@ -152,16 +152,18 @@ hipError_t rcw_launch_rays(const RcwDev& p, int32_t first, int32_t count, RcwRay
 hipError_t rcw_launch_expand(const RcwPlan& p, const int32_t* col_h, const uint8_t* col_c,
                              int32_t count, uint32_t* frames, hipStream_t s);
 
-// The learner view (rcw_set_learner_view, rcw_view.hip): uint8 RGB or gray, area-averaged to (h, w), computed from the column
-// descriptors.  Output row r averages camera rows [rows[r], rows[r+1]), column c image columns [cols[c], cols[c+1]).
+// The learner view (rcw_set_learner_view, rcw_view.hip): uint8 RGB or gray and / or inverse depth, area-averaged to (h, w), computed from
+// the column descriptors.  Output row r averages camera rows [rows[r], rows[r+1]), column c image columns [cols[c], cols[c+1]).
 struct RcwView {
-    int32_t C;               // channels: 1 (gray) or 3 (RGB)
+    int32_t C;               // channels: 1 (gray, depth), 3 (RGB), 2 (gray + depth), 4 (RGB + depth)
     int32_t hwc;             // layout: 0 = (B, C, h, w), 1 = (B, h, w, C)
     int32_t h, w;            // output size, 1 <= h <= Hc, 1 <= w <= N
     const int32_t* rows;     // [h + 1] floor(r * Hc / h)
     const int32_t* cols;     // [w + 1] floor(c * N / w)
     int32_t wide;            // a box's channel sums may pass 2^31: 64-bit sums and divisions
     int32_t full_ok;         // (h, w) = (Hc, N) and the geometry rcw_view_full_kernel takes
+    int32_t depth;           // 1: the last of the C channels is the depth plane (C - 1 colour channels in front of it)
+    const int32_t* dsum;     // depth: [Hc + 1] prefix sums of the ceiling / floor depth byte De(y) over camera rows, dsum[0] = 0
 };
 // the view of agents [0, count) of the descriptors col_h / col_c (N a agent) into out (count * C * h * w bytes); mask: NULL = all
 hipError_t rcw_launch_view(const RcwPlan& p, const RcwView& v, const int32_t* col_h, const uint8_t* col_c, int32_t count,

@@ -604,10 +604,15 @@ class SingleRoom:
         return out
 
     # ---- the learner view (rcw_set_learner_view) ------------------------------------------------------------------
+    _VIEW_FORMATS = {None: _capi.RCW_VIEW_OFF, "rgb": _capi.RCW_VIEW_RGB8, "gray": _capi.RCW_VIEW_GRAY8,
+                     "depth": _capi.RCW_VIEW_DEPTH8, "rgbd": _capi.RCW_VIEW_RGBD8, "grayd": _capi.RCW_VIEW_GRAYD8}
+    _VIEW_CHANNELS = {"rgb": 3, "gray": 1, "depth": 1, "rgbd": 4, "grayd": 2}
+
     def set_learner_view(self, format: Optional[str] = "gray", size=None, layout: str = "chw", camera_view: bool = True,
                          stack: int = 1) -> None:
-        """Also render a uint8 observation a learner consumes at every reset / set_state / step: `format` "gray" or "rgb"
-        (None: off), `size` (h, w) with h <= height_camera_view_pu and w <= num_rays (None: full size; each output pixel is
+        """Also render a uint8 observation a learner consumes at every reset / set_state / step: `format` "gray" or "rgb",
+        "depth" (one plane of inverse depth: 255 at or nearer than the distance at which a wall fills the column, 0 infinitely
+        far — include/rcw.h), "rgbd" (R, G, B, D) or "grayd" (Y, D) (None: off), `size` (h, w) with h <= height_camera_view_pu and w <= num_rays (None: full size; each output pixel is
         the rounded mean of its box of camera pixels), `layout` "chw" (B, C, h, w) or "hwc" (B, h, w, C).
         `camera_view=False` (RCW_VIEW_ONLY): steps skip the uint32 camera view — `camera_view` then holds the last frames
         rendered until `update_camera_view_(env)`.  Renders the current state at once.
@@ -615,10 +620,10 @@ class SingleRoom:
         [0, C)) the oldest and slot k - 1 the newest.  The engine keeps it per episode on the device: a step shifts the slots
         and appends the new frame; reset_, set_state and the step in which auto_reset restarts an agent fill all k slots of
         that agent with its new frame, so no frame of a finished episode shows in the next one (include/rcw.h)."""
-        formats = {None: _capi.RCW_VIEW_OFF, "rgb": _capi.RCW_VIEW_RGB8, "gray": _capi.RCW_VIEW_GRAY8}
+        formats = self._VIEW_FORMATS
         layouts = {"chw": _capi.RCW_VIEW_CHW, "hwc": _capi.RCW_VIEW_HWC}
         if format not in formats:
-            raise ValueError(f"unknown learner view format {format!r} (\"gray\", \"rgb\" or None)")
+            raise ValueError(f"unknown learner view format {format!r} (\"gray\", \"rgb\", \"depth\", \"rgbd\", \"grayd\" or None)")
         if layout not in layouts:
             raise ValueError(f"unknown learner view layout {layout!r} (\"chw\" or \"hwc\")")
         if format is None and not camera_view:
@@ -638,7 +643,7 @@ class SingleRoom:
         v = [C.c_int32() for _ in range(5)]
         self._check(self._lib.rcw_learner_view_info(self._h, *[C.byref(x) for x in v]))
         fmt, lay, h, w, flags = (x.value for x in v)
-        return {"format": {_capi.RCW_VIEW_OFF: None, _capi.RCW_VIEW_RGB8: "rgb", _capi.RCW_VIEW_GRAY8: "gray"}[fmt],
+        return {"format": {value: name for name, value in self._VIEW_FORMATS.items()}[fmt],
                 "layout": "hwc" if lay == _capi.RCW_VIEW_HWC else "chw", "size": (h, w),
                 "camera_view": not (flags & _capi.RCW_VIEW_ONLY)}
 
@@ -653,7 +658,7 @@ class SingleRoom:
         info = info or self.learner_view_info()
         if info["format"] is None:
             raise RuntimeError("this environment has no learner view: call set_learner_view first")
-        c = 3 if info["format"] == "rgb" else 1
+        c = self._VIEW_CHANNELS[info["format"]]
         h, w = info["size"]
         k = self.learner_view_stack if stack is None else stack
         return (n, k * c, h, w) if info["layout"] == "chw" else (n, h, w, c)

@@ -4,6 +4,12 @@
 
     python tools/isa_diff.py OLD.s NEW.s [--only SUBSTR] [--show]
     python tools/isa_diff.py OLD.s NEW_DIR        (a directory: every *.s in it, concatenated)
+    python tools/isa_diff.py OLD.s NEW.s --rename PATTERN REPL [--figures]
+                                                  (NEW's text through re.sub first: a kernel that gained a template
+                                                  parameter is compared with the one it was; --figures: each compared
+                                                  kernel's VGPRs / SGPRs / static LDS / scratch on both sides)
+    ... --ignore-kernarg                          (a by-value argument struct grew: the offsets of the scalar loads and
+                                                  the kernarg size are left out of the comparison)
 
 A kernel's body is the text between its `<symbol>:` label and its `.Lfunc_end`; comments, debug directives and
 local label NUMBERS (which shift when a translation unit is cut differently) are normalised away.  Exit code 1 when
@@ -43,6 +49,15 @@ def kernels(text: str) -> dict[str, list[str]]:
     return out
 
 
+def figures(text: str) -> dict[str, tuple]:
+    """(next free VGPR, next free SGPR, static LDS bytes, scratch bytes a lane) of every kernel descriptor."""
+    out = {}
+    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S+)\n(.*?)\.end_amdhsa_kernel", text, flags=re.M | re.S):
+        f = lambda key: int(re.search(r"\.amdhsa_" + key + r"\s+(\d+)", m.group(2)).group(1))
+        out[m.group(1)] = (f("next_free_vgpr"), f("next_free_sgpr"), f("group_segment_fixed_size"), f("private_segment_fixed_size"))
+    return out
+
+
 def normalise(body: list[str]) -> list[str]:
     labels: dict[str, str] = {}
     res = []
@@ -66,17 +81,30 @@ def main() -> int:
     ap.add_argument("old"); ap.add_argument("new")
     ap.add_argument("--only", default="")
     ap.add_argument("--show", action="store_true")
+    ap.add_argument("--rename", nargs=2, metavar=("PATTERN", "REPL"))
+    ap.add_argument("--figures", action="store_true")
+    ap.add_argument("--ignore-kernarg", action="store_true")
     a = ap.parse_args()
-    ko, kn = kernels(read(a.old)), kernels(read(a.new))
+    told, tnew = read(a.old), read(a.new)
+    if a.rename:
+        tnew = re.sub(a.rename[0], a.rename[1], tnew)
+    ko, kn = kernels(told), kernels(tnew)
+    fo, fn = figures(told), figures(tnew)
     names = sorted(set(ko) | set(kn))
     same = diff = 0
     for n in names:
         if a.only and a.only not in n:
             continue
         if n not in ko:
-            print(f"only in NEW: {n}"); continue
+            print(f"only in NEW: {n}" + (f"  vgpr/sgpr/lds/scratch {'/'.join(map(str, fn[n]))}" if a.figures else "")); continue
         if n not in kn:
             print(f"only in OLD: {n}"); continue
+        if a.figures:
+            print(f"vgpr/sgpr/lds/scratch {'/'.join(map(str, fo[n]))} -> {'/'.join(map(str, fn[n]))}  {n}")
+        if a.ignore_kernarg:
+            karg = lambda body: [re.sub(r"^(s_load_dword\w*\s+\S+,\s+s\[\d+:\d+\]),\s+0x[0-9a-f]+$", r"\1, KERNARG", l) for l in body
+                                 if not l.startswith(".amdhsa_kernarg_size")]
+            ko[n], kn[n] = karg(ko[n]), karg(kn[n])
         if ko[n] == kn[n]:
             same += 1
         else:

@@ -9,10 +9,13 @@ Cases: plain (the camera view only), plus_gray84 (camera view + gray 84x84), onl
 set_learner_view(stack=4)) against plus_gray84_torch_stack4 / only_gray84_torch_stack4: the single-frame view plus a stack kept by torch
 ops on the same stream with the same semantics — the done flags of before the step copied, the slots shifted by a cat, all four taken
 from the new frame by a where on the agents that were done (those auto_reset re-samples in the step): three launches and two fresh
-tensors a step, no host synchronisation.  The view kernel's own duration comes from a separate rocprofv3 run
+tensors a step, no host synchronisation.  The depth plane (include/rcw.h): only_depth84 beside only_gray84, only_grayd84_stack4 beside
+only_gray84_stack4, and plus_rgbd_full — camera view + RGB-D at full size, CHW —, reported as the bytes of the view over the TIME IT ADDS TO
+THE PLAIN STEP (`us_over_plain_step`: the view kernel runs alone on the stream, behind the step's; not the kernel's duration).  The view kernel's own duration comes from a separate rocprofv3 run
 (--case NAME runs one case alone, for `rocprofv3 --kernel-trace --stats -- python tools/learner_view_bench.py --case ...`)."""
 import argparse
 import json
+import math
 import os
 import sys
 
@@ -29,7 +32,11 @@ CASES = {
     "only_gray84_stack4": dict(format="gray", size=(84, 84), layout="chw", camera_view=False, stack=4),
     "plus_gray84_torch_stack4": dict(format="gray", size=(84, 84), layout="chw", camera_view=True, torch_stack=4),
     "only_gray84_torch_stack4": dict(format="gray", size=(84, 84), layout="chw", camera_view=False, torch_stack=4),
+    "only_depth84": dict(format="depth", size=(84, 84), layout="chw", camera_view=False),
+    "only_grayd84_stack4": dict(format="grayd", size=(84, 84), layout="chw", camera_view=False, stack=4),
+    "plus_rgbd_full": dict(format="rgbd", size=None, layout="chw", camera_view=True),
 }
+DEPTH_TWINS = {"only_depth84": "only_gray84", "only_grayd84_stack4": "only_gray84_stack4"}
 
 
 def run_case(RCW, torch, name, batch, steps, warmup, actions):
@@ -63,12 +70,13 @@ def run_case(RCW, torch, name, batch, steps, warmup, actions):
         ms = env.timer_stop()
         stream.synchronize()
     form = env.step_form()
+    view_bytes = math.prod(env.learner_view.shape) if kw else 0   # the bytes of the view batch (all its frame slots)
     try:
         env.sync()
     except IndexError:
         env.clear_error()
     env.close()
-    return ms, form
+    return ms, form, view_bytes
 
 
 def main():
@@ -88,23 +96,32 @@ def main():
     actions = [torch.randint(1, 5, (args.batch,), dtype=torch.uint8, generator=g).cuda() for _ in range(64)]
     names = [args.case] if args.case else list(CASES)
     runs = {n: [] for n in names}
-    forms = {}
+    forms, view_bytes = {}, {}
     for _ in range(args.repeats):
         for n in names:
-            ms, forms[n] = run_case(RCW, torch, n, args.batch, args.steps, args.warmup, actions)
+            ms, forms[n], view_bytes[n] = run_case(RCW, torch, n, args.batch, args.steps, args.warmup, actions)
             runs[n].append(args.batch * args.steps / (ms / 1000.0))
     out = {"metric": "env-steps/s", "config": "cfg-2: 8x8 map, 256 view columns, 256 rows", "batch": args.batch,
            "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats, "cases": {}}
     for n in names:
         r = np.array(runs[n])
         out["cases"][n] = {"median": float(np.median(r)), "min": float(r.min()), "max": float(r.max()),
-                           "us_per_step_median": float(args.batch / np.median(r) * 1e6), "step_form": forms[n],
+                           "us_per_step_median": float(args.batch / np.median(r) * 1e6), "step_form": forms[n], "view_bytes": view_bytes[n],
                            "runs": [float(x) for x in r]}
     for n in names:                                                # the engine's stack against the torch one: faster, and the ranges apart?
         t = n.replace("_stack4", "_torch_stack4")
         if n.endswith("_stack4") and t != n and t in runs:
             e, b = out["cases"][n], out["cases"][t]
             out[n + "_over_torch"] = {"median_ratio": e["median"] / b["median"], "ranges_apart": bool(e["min"] > b["max"])}
+    for n, t in DEPTH_TWINS.items():                               # the depth cases beside their colour twins
+        if n in runs and t in runs:
+            e, b = out["cases"][n], out["cases"][t]
+            out[n + "_over_" + t] = {"median_ratio": e["median"] / b["median"],
+                                     "us_per_step_more": e["us_per_step_median"] - b["us_per_step_median"]}
+    if "plus_rgbd_full" in runs and "plain" in runs:
+        us = out["cases"]["plus_rgbd_full"]["us_per_step_median"] - out["cases"]["plain"]["us_per_step_median"]
+        nbytes = view_bytes["plus_rgbd_full"]
+        out["plus_rgbd_full_view"] = {"bytes": nbytes, "us_over_plain_step": us, "GB_per_s_over_plain_step": nbytes / us / 1e3}
     if "plain" in runs and "only_gray84" in runs:
         out["only_gray84_over_plain"] = out["cases"]["only_gray84"]["median"] / out["cases"]["plain"]["median"]
     print(json.dumps(out))
