@@ -11,7 +11,8 @@ Two independent readings of it:
                       which box-averages such an image with prefix sums;
   from_descriptors    counts, per image column and box, the ceiling / colour / floor rows and takes the ceiling and floor sums from a
                       prefix table of the edge value.
-view() puts the colour planes of learner_view_ref.from_descriptors and the depth plane together for a format and a layout."""
+view() puts the colour planes of learner_view_ref.from_descriptors and the depth plane together for a format and a layout; full_size() is
+the whole view at (Hc, N) alone, selected pixel by pixel in bytes."""
 import numpy as np
 
 import learner_view_ref as LV
@@ -95,3 +96,29 @@ def view(col_h, col_c, cfg, Hc, fmt, size, layout="chw", depth=from_descriptors)
 
 def by_frames(col_h, Hc, size):
     return from_depth_frames(depth_frames(col_h, Hc), size)
+
+
+def full_size(col_h, col_c, cfg, Hc, fmt, layout="chw"):
+    """view() at size (Hc, N), where a box is one pixel and nothing is averaged: every plane selected per pixel from the column rule, in
+    bytes — for batches at which view()'s int64 box sums take seconds (a thousand agents).  tests/test_learner_view_depth_spec.py holds it
+    against view() byte for byte."""
+    col_h = np.asarray(col_h, dtype=np.int64)
+    B, N = col_h.shape
+    pad = LV.padding(Hc, col_h)
+    fs = np.maximum(pad, Hc - pad).astype(np.int32)[:, None, :]
+    y = np.arange(Hc, dtype=np.int32)[None, :, None]
+    ceiling, floor = y < pad.astype(np.int32)[:, None, :], y >= fs
+    planes = []
+    if COLOUR_OF[fmt] is not None:
+        ceil_c, floor_c, ids = LV.colours(cfg)
+        vc, vf = LV.channels_of(ceil_c, COLOUR_OF[fmt]), LV.channels_of(floor_c, COLOUR_OF[fmt])
+        vm = LV.channels_of(np.array(ids, dtype=np.int64), COLOUR_OF[fmt])[np.asarray(col_c, dtype=np.int64) & 3].astype(np.uint8)   # (B, N, C)
+        for k in range(len(vc)):
+            planes.append(np.where(ceiling, np.uint8(vc[k]), np.where(floor, np.uint8(vf[k]), vm[:, None, :, k])))
+    if HAS_DEPTH[fmt]:
+        rows = np.arange(Hc, dtype=np.int64)
+        edge = depth_byte(Hc - 2 * np.minimum(rows, Hc - 1 - rows), Hc).astype(np.uint8)[None, :, None]
+        wall = depth_byte(np.clip(col_h, 0, Hc), Hc).astype(np.uint8)[:, None, :]
+        planes.append(np.where(ceiling | floor, edge, wall))
+    chw = np.stack(planes, axis=1)
+    return np.ascontiguousarray(chw if layout == "chw" else chw.transpose(0, 2, 3, 1))

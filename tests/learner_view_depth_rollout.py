@@ -23,7 +23,11 @@ AGENT_LDS = lambda cfg, size: (3 * cfg["num_rays"] + size[0] + size[1] + 2) * 4 
 ROLLOUTS = {"cfg1": (CFG1, 5, 5, 8, False), "odd": (ODD, 5, 1, 8, False), "many rays": (MANY_RAYS, 3, 1, 8, False),
             "depth table": (DEPTH_TABLE, 2, 1, 8, False), "huge box": (HUGE_BOX, 2, 1, 8, False),
             "cfg2 near the goal": (CFG2, 7, 1, 8, True), "cfg1 near the goal": (CFG1, 5, 1, 8, True),
-            "many rays near the goal": (MANY_RAYS, 3, 1, 8, True), "cfg2": (CFG2, 6, 1, 8, False), "cfg2 x 64": (CFG2, 64, 1, 8, False)}
+            "many rays near the goal": (MANY_RAYS, 3, 1, 8, True), "cfg2": (CFG2, 6, 1, 8, False), "cfg2 x 64": (CFG2, 64, 1, 8, False),
+            # more (agent, plane) items than the full kernel's grid of 4 workgroups a CU: its sweep's second trip, the masked reset's
+            # `continue` behind the prefetch included
+            "cfg1 x 1100": (CFG1, 1100, 5, 8, False)}
+FULL_SIZE_PIXELS = 1 << 22                                   # frames of more pixels than this, at full size: LD.full_size for LD.view
 
 
 class DepthRollout:
@@ -55,6 +59,9 @@ class DepthRollout:
 
     def single(self, layout=None):
         o = self.orc
+        if tuple(self.size) == (o.Hc, o.N) and self.B * o.Hc * o.N > FULL_SIZE_PIXELS:
+            # a thousand agents at full size: the same bytes (tests/test_learner_view_depth_spec.py) without view()'s int64 box sums
+            return LD.full_size(o.col_height, o.col_colour, o.cfg, o.Hc, self.fmt, layout or self.layout)
         return LD.view(o.col_height, o.col_colour, o.cfg, o.Hc, self.fmt, self.size, layout or self.layout)
 
     def check(self, where):

@@ -67,14 +67,15 @@ def test_sums_of_64_bits(rcw, oracle):
 STACK = [("the fused kernel, frames of 2 x 84 x 84", "cfg2 near the goal", "grayd", (84, 84), 3),
          ("the fused kernel, frames of 7844 bytes", "cfg2 near the goal", "rgbd", (37, 53), 3),
          ("the full kernel, then the push", "cfg1 near the goal", "rgbd", None, 2),
-         ("the box kernel, then the push", "many rays near the goal", "depth", (8, 700), 3)]
+         ("the box kernel, then the push", "many rays near the goal", "depth", (8, 700), 3),
+         ("the fused kernel, six slots", "cfg2 near the goal", "grayd", (20, 30), 6)]
 
 
 @pytest.mark.parametrize("what,name,fmt,size,k", STACK, ids=[s[0] for s in STACK])
 def test_the_stack(rcw, oracle, what, name, fmt, size, k):
     """the k-frame stack with C = 2 and C = 4: rcw_view_agent_push_kernel (per = 14112: 16-byte chunks; 7844: bytes) and the staged frame
     with rcw_view_push_kernel behind the full and the box kernel; the slot rule (tests/learner_view_stack_ref.py) across an auto_reset
-    restart and the masked reset"""
+    restart and the masked reset; six slots: shift_chunk moves four a trip, its second trip inside a depth instantiation of the fused kernel"""
     assert (4 * 37 * 53) % 16 != 0 and (2 * 84 * 84) % 16 == 0
     rollout(rcw, oracle, name, fmt=fmt, size=size, layout="chw", k=k)
 
