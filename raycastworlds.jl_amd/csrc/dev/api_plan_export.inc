@@ -1,7 +1,5 @@
 // Development build only (-DRCW_DEV_SWITCHES): the top view's rule and its table of thresholds WITHOUT a device — what
-// tests/test_top_view_plan.py runs on the CPU.  A fragment of rcw_api.hip, included behind plan_top_view (inside the anonymous namespace: the
-// exports leave it and come back).
-}  // namespace
+// tests/test_top_view_plan.py runs on the CPU.  The tail of rcw_rules.hip, at file scope.
 extern "C" {
 // out[16]: form in a step (RCW_TOP_VIEW_*), form of rcw_update_top_view alone, then top_lds, top_split, top_flat, top_unit_px, top_fused,
 // top_draw_first, top_parts, top_runs, top_draw_block, top_draw_block_alone, top_alone_split, top_grid, top_store_grid, return code
@@ -92,4 +90,3 @@ __attribute__((visibility("default"))) int rcw_dev_validate_walls(int32_t H, int
     return validate_walls(H, W, batch, walls, layouts, index, mask, msg, (size_t)cap);
 }
 }  // extern "C"
-namespace {

@@ -1,0 +1,411 @@
+// The host-built tables, and every rule and validation of librcw_hip: no HIP call, and nothing of a handle changes.
+// Host code in this file that does floating point follows the reference operation for
+// operation and must be compiled with -ffp-contract=off (see Makefile).
+#include "rcw_handle.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+// directions_wu  SR:65-69: theta = (i-1)*2*pi/nd in Float64, components converted to T
+template <typename T>
+void build_direction_table(int nd, std::vector<T>& out)
+{
+    out.resize((size_t)2 * nd);
+    for (int i = 1; i <= nd; ++i) {
+        const double theta = (double)((long long)(i - 1) * 2) * 3.141592653589793 / (double)nd;
+        out[2 * (size_t)(i - 1)] = (T)std::cos(theta);
+        out[2 * (size_t)(i - 1) + 1] = (T)std::sin(theta);
+    }
+}
+
+// Per heading d and ray i (SR:214-221, SR:404): the fan end points dir ± fov·rot₋₉₀(dir),
+// the LinRange element (Float64 lerp converted to T), its normalisation, and the derived
+// |1/dx|, |1/dy| (cast_ray's delta distances) and dir·ray (SR:404).
+// Layout [nd][5][N]: see RCW_TABLE_ROWS.  T is the world-unit type; fov = convert(T, .) SR:267.
+template <typename T>
+void build_ray_table(const rcw_config& c, T fov, const std::vector<T>& dirs, std::vector<T>& out)
+{
+    const int N = c.num_rays, nd = c.num_directions;
+    out.assign((size_t)nd * RCW_TABLE_ROWS * N, (T)0);
+    const int lendiv = N - 1 > 1 ? N - 1 : 1;   // LinRange lendiv = max(len - 1, 1)
+    for (int d = 0; d < nd; ++d) {
+        const T d1 = dirs[2 * (size_t)d], d2 = dirs[2 * (size_t)d + 1];
+        const T cam1 = d2, cam2 = -d1;                        // rotate_minus_90 SR:193
+        const T fc1 = fov * cam1, fc2 = fov * cam2;
+        const T first1 = d1 + fc1, first2 = d2 + fc2;         // SR:216
+        const T last1 = d1 - fc1, last2 = d2 - fc2;           // SR:217
+        T* row = out.data() + (size_t)d * RCW_TABLE_ROWS * N;
+        for (int i = 0; i < N; ++i) {
+            const double t = (double)i / (double)lendiv;      // lerpi: t = j/d in Float64
+            const double omt = 1.0 - t;
+            const double a1 = omt * (double)first1, b1 = t * (double)last1;
+            const double a2 = omt * (double)first2, b2 = t * (double)last2;
+            const T u1 = (T)(a1 + b1);
+            const T u2 = (T)(a2 + b2);
+            const T s1 = u1 * u1, s2 = u2 * u2;
+            const T nrm = std::sqrt(s1 + s2);                 // norm(SVector) = sqrt(sum abs2)
+            T r1, r2;
+            if (c.normalize_mode == RCW_NORMALIZE_DIVIDE) {
+                r1 = u1 / nrm; r2 = u2 / nrm;
+            } else {
+                const T inv = (T)1 / nrm;                     // inv(norm(a)) * a
+                r1 = inv * u1; r2 = inv * u2;
+            }
+            const T m1 = d1 * r1, m2 = d2 * r2;               // sum(dir .* ray) SR:404
+            row[i] = r1;
+            row[(size_t)N + i] = r2;
+            row[2 * (size_t)N + i] = std::fabs((T)1 / r1);
+            row[3 * (size_t)N + i] = std::fabs((T)1 / r2);
+            row[4 * (size_t)N + i] = m1 + m2;
+        }
+    }
+}
+template void build_direction_table<float>(int, std::vector<float>&);
+template void build_direction_table<double>(int, std::vector<double>&);
+template void build_ray_table<float>(const rcw_config&, float, const std::vector<float>&, std::vector<float>&);
+template void build_ray_table<double>(const rcw_config&, double, const std::vector<double>&, std::vector<double>&);
+
+// The geometry of a batch as the kernels' argument block holds it: what the launchers' and the top view's rules read (rcw_create; the
+// development build's rcw_dev_plan_top_view, which runs the rule without a device).
+void set_geometry(RcwPlan& d, const rcw_config* cfg, int32_t batch)
+{
+    d.B = batch; d.H = cfg->height_tile_map_tu; d.W = cfg->width_tile_map_tu; d.N = cfg->num_rays; d.nd = cfg->num_directions; d.Hc = cfg->height_camera_view_pu;
+    d.real64 = cfg->world_unit_bits == 64 ? 1 : 0;
+    d.pu = cfg->pu_per_tu;
+    // player_radius_pu = wu_to_pu(player_radius_wu, pu_per_tu) SR:469 = floor(Int, r * pu) + 1 in T (UT:6)
+    d.top_rp = d.real64 ? (int32_t)std::floor(cfg->player_radius_wu_f64 * (double)cfg->pu_per_tu) + 1
+                        : (int32_t)std::floor(cfg->player_radius_wu * (float)cfg->pu_per_tu) + 1;
+}
+
+// ---- update_top_view! (SR:446-483): which form a handle takes — the RULES AS DATA ------------------------------------------------------
+// Every threshold the choice of a form rests on, with the measurement that put it there.  The rule itself (top_view_rule below) is a pure
+// function of the configuration, the batch and three numbers of the device (CUs, LDS and wavefronts a CU: rcw_create reads them from
+// hipDeviceProp_t); tests/test_top_view_plan.py runs it on the CPU (development build: rcw_dev_plan_top_view) for every shape of the
+// committed profile table and compares with tests/golden/top_view_plan_cases.json — the forms those profiles were taken with.  A retune
+// on another box is an edit of this table, a re-run of tools/top_view_shapes.py and of tools/make_top_view_plan_cases.py; a change of a
+// rule by accident is a red test.
+namespace {
+struct TopRule { const char* name; double value; const char* unit; const char* evidence; };
+enum TopRuleId {
+    kRingThreeBuffersLds, kRingLdsCap, kRingWorkgroupsPerCu, kLineWalkMaxPixels, kAloneTwoKernelsPixels, kAloneTwoKernelsBelowPu,
+    kDrawWideBlockLds, kDrawBlockMin, kDrawBlockMax, kAloneBlock64Agents, kAloneBlock128Agents, kRunsLineToCameraNum, kRunsLineToCameraDen,
+    kRuns4Gib, kRuns2Gib, kSideStreamMinBytes, kPartsMax, kPartsMinRays, kFillGBperMs, kFillLateStartUs, kDrawUsPerGibFewRays,
+    kDrawUsPerGibManyRays, kDrawManyRays, kDrawPartialRound, kDrawLdsCap, kFillWavefrontsPerCu, kTopRuleCount
+};
+constexpr TopRule kTopRules[kTopRuleCount] = {
+    /* kRingThreeBuffersLds   */ {"ring_three_buffers_max_lds", 52 * 1024, "B", "profiles/r02_top_view_summary.txt: three workgroups of 8 wavefronts a CU still fit beside each other up to 52 KiB of ring each"},
+    /* kRingLdsCap            */ {"ring_lds_cap", 156 * 1024, "B", "the CU's 160 KiB less what the kernel's static words and the runtime keep: beyond it the in-place form (profiles/r02_top_draw_lds.txt)"},
+    /* kRingWorkgroupsPerCu   */ {"ring_workgroups_per_cu_max", 3, "", "profiles/r02_top_view_summary.txt: 3 x 8 wavefronts is what the ring kernel's register use admits; 4 measured no faster"},
+    /* kLineWalkMaxPixels     */ {"line_walk_max_pixels", 16384, "px", "exactness, not tuning: the bit-plane kernels step a line on the carry of a 32-bit fraction, exact for lines of up to 2^14 pixels (tests/test_host_logic.py)"},
+    /* kAloneTwoKernelsPixels */ {"stand_alone_two_kernels_from_pixels", 65536, "px", "profiles/r05_top_view_shapes.txt (b): draw -> store back to back 217 / 224 / 198 / 210 / 218 us/GiB against 214 / 231 / 228 / 253 / 360 for the ring from 256^2 px up"},
+    /* kAloneTwoKernelsBelowPu*/ {"stand_alone_two_kernels_below_pu", 16, "px/tile", "profiles/r05_top_view_shapes.txt (b): 10 / 13 px a tile 360 / 302 against 507 / 450, 12 px 310 against 347; the ring keeps 16, 20, 24 ... px below 256^2 (264 / 228 / 229 against 268 / 246 / 233)"},
+    /* kDrawWideBlockLds      */ {"draw_wide_block_from_plane_lds", 64 * 1024, "B", "profiles/r04_top_view_small_batches.txt, r03_top_view_shapes.txt: planes beyond 64 KiB leave one or two workgroups a CU: 512^2 px 180 / 182 / 200, 768^2 212 / 200 / 203, 1024^2 357 / 265 / 216 us with 256 / 512 / 1024 threads"},
+    /* kDrawBlockMin          */ {"draw_wide_block_min_threads", 512, "threads", "same measurement"},
+    /* kDrawBlockMax          */ {"draw_wide_block_max_threads", 1024, "threads", "same measurement (a lane per ray up to 1024 rays)"},
+    /* kAloneBlock64Agents    */ {"stand_alone_64_threads_from_agents", 24576, "agents", "profiles/r05_draw_kernel.txt: 41,943 images of 80^2 px 175 us with 64 threads against 193 with 256"},
+    /* kAloneBlock128Agents   */ {"stand_alone_128_threads_from_agents", 12288, "agents", "profiles/r05_draw_kernel.txt: 16,384 images of 128^2 px 103 us with 128 threads against 109"},
+    /* kRunsLineToCameraNum   */ {"runs_when_lines_to_camera_num", 7, "", "profiles/r03_top_view_shapes.txt: (H + W) pu / 2 >= 1.75 H_cam, i.e. 2 (H + W) pu >= 7 H_cam: the drawing no longer fits beside the camera fill"},
+    /* kRunsLineToCameraDen   */ {"runs_when_lines_to_camera_den", 2, "", "same rule's left-hand factor"},
+    /* kRuns4Gib              */ {"four_runs_from_gib", 4, "GiB", "profiles/r03_top_view_shapes.txt: 16 GiB of top view 4516 / 4409 / 4332 / 4294 us with 1 / 2 / 4 / 8 runs, 32 GiB 8586 / 8459 / 7658 / 8068"},
+    /* kRuns2Gib              */ {"two_runs_from_gib", 2, "GiB", "same table; runs of 256 MiB do not pay (205 vs 181 us at 1 GiB of 512^2 px images)"},
+    /* kSideStreamMinBytes    */ {"side_stream_form_from_bytes", 256.0 * 1048576.0, "B", "profiles/r04_top_view_small_batches.txt: the fork / join and the extra launch cost ~13 us a step (39 / 51 / 53 / 60 / 102 / 341 us against the ring's 36 / 38 / 41 / 47 / 103 / 387 at 1 .. 4096 agents)"},
+    /* kPartsMax              */ {"draw_parts_max", 4, "workgroups", "profiles/r05_draw_kernel.txt (tools/experiments.md: r05_draw_parts.sh): 1024^2 px x 64 agents 53.6 / 38.6 / 30.5 us with 1 / 2 / 4 parts"},
+    /* kPartsMinRays          */ {"draw_part_min_rays", 128, "rays", "same table: a part's fixed costs (plane cleared, every end point, plane scanned) are most of a workgroup's life; x 256 agents 61.4 / 78.7 / 110"},
+    /* kFillGBperMs           */ {"camera_fill_rate", 6.5e6, "B/us", "profiles/r05_kernel_stats.csv: rcw_fill256_kernel 156 us a GiB = 6.88 TB/s; 6.5 with its smaller siblings"},
+    /* kFillLateStartUs       */ {"side_stream_late_start", 12, "us", "profiles/r05_top_view_shapes.txt / tools/step_timeline.sh: a kernel behind an event of the other stream starts ~13 us later than behind a kernel of its own (19 against 6 us after the cast kernel's end)"},
+    /* kDrawUsPerGibFewRays   */ {"draw_floor_few_rays", 34, "us/GiB", "profiles/r05_draw_kernel.txt, r05_top_view_shapes.txt (a): the draw kernel's floor per GiB of top view with up to 256 rays (768^2 px x 455: 37 us)"},
+    /* kDrawUsPerGibManyRays  */ {"draw_floor_many_rays", 55, "us/GiB", "same: beyond 256 rays (1024^2 px x 256, 1024 rays: 58-61 us)"},
+    /* kDrawManyRays          */ {"draw_many_rays_from", 257, "rays", "the boundary between the two floors above"},
+    /* kDrawPartialRound      */ {"draw_partial_round", 0.7, "", "profiles/r05_draw_kernel.txt (tools/experiments.md: r05_draw_first.sh): a partial round of draw workgroups takes about as long as a full one (768^2 px x 114 / 228 / 341 agents 90 -> 75, 129 -> 115, 169 -> 155 us)"},
+    /* kDrawLdsCap            */ {"draw_kernel_lds_cap", 159 * 1024, "B", "rcw_top_split_unit / rcw_top_flat_cols: the draw kernel's plane + ray lists within the CU's LDS less 1 KiB"},
+    /* kFillWavefrontsPerCu   */ {"fill_wavefronts_per_cu", 4, "wavefronts", "one workgroup of the camera fill (four wavefronts) sits on every CU: what is left of the CU's wavefront slots is the drawing's"},
+};
+constexpr double top_rule(TopRuleId id) { return kTopRules[id].value; }
+}  // namespace
+
+// what the rule decides (fields of RcwPlan), from the configuration, the batch, the device's numbers and the caller's wishes; no HIP call.
+// want_form: 0 = the rule, or one of RCW_TOP_VIEW_IN_PLACE / ONE_KERNEL / TWO_KERNELS (rcw_set_top_view_form); want_runs: 0 = the rule, or 1..8.
+// `lenient`: a form the geometry cannot take falls back to the rule (development switches) instead of failing.
+int top_view_rule(RcwPlan& d, const rcw_config* cfg, size_t B, const RcwHw& hw, int want_form, int want_runs, bool lenient)
+{
+    const int H = cfg->height_tile_map_tu, W = cfg->width_tile_map_tu, N = cfg->num_rays, Hc = cfg->height_camera_view_pu;
+    d.top_lds = 0; d.top_split = 0; d.top_flat = 0; d.top_plane_words = 0; d.top_unit_px = 256; d.top_runs = 1;
+    d.top_alone_split = 0; d.top_fused = 0; d.top_grid = hw.cus; d.top_store_grid = d.fill_grid; d.top_store_plain = 0; d.top_draw_block = 256; d.top_draw_block_alone = 256; d.top_draw_first = 0; d.top_parts = 1;
+    if (!cfg->render_top_view) {
+        if (want_form != 0 && !lenient) return fail(RCW_ERR_UNSUPPORTED, "handle was created with render_top_view = 0");
+        return RCW_OK;
+    }
+    const size_t ring_cap = (size_t)top_rule(kRingLdsCap);
+    // the write-once kernel keeps a ring of 1..3 agents' bit planes in LDS: three where three workgroups per CU still fit beside
+    // each other, else two, else one; larger images take the in-place kernel
+    d.top_lds = 3;
+    if (rcw_top_view_lds_bytes(d) > (size_t)top_rule(kRingThreeBuffersLds)) d.top_lds = 2;
+    if (rcw_top_view_lds_bytes(d) > ring_cap) d.top_lds = 1;
+    if (rcw_top_view_lds_bytes(d) > ring_cap) d.top_lds = 0;             // (the size depends on top_lds)
+    if ((long long)H * cfg->pu_per_tu > (long long)top_rule(kLineWalkMaxPixels) || (long long)W * cfg->pu_per_tu > (long long)top_rule(kLineWalkMaxPixels)) d.top_lds = 0;
+    if (const char* v = RCW_DEV_ENV("RCW_TOP_RING")) { const int k = std::atoi(v); if (k >= 1 && k <= 3 && d.top_lds > 0) { d.top_lds = k; if (rcw_top_view_lds_bytes(d) > ring_cap) d.top_lds = 1; } }
+    if (want_form == RCW_TOP_VIEW_IN_PLACE) d.top_lds = 0;
+    if (want_form == RCW_TOP_VIEW_ONE_KERNEL && !d.top_lds && !lenient)
+        return fail(RCW_ERR_UNSUPPORTED, "the image's bit planes do not fit in LDS: this geometry takes the in-place form only");
+    {   // persistent grid: as many 8-wavefront workgroups per CU as registers and LDS allow
+        const size_t lds = rcw_top_view_lds_bytes(d);
+        int per_cu = lds ? (int)((size_t)hw.lds_per_cu / lds) : 4;
+        per_cu = per_cu < 1 ? 1 : (per_cu > (int)top_rule(kRingWorkgroupsPerCu) ? (int)top_rule(kRingWorkgroupsPerCu) : per_cu);
+        d.top_grid = per_cu * hw.cus;
+    }
+    if (const char* v = RCW_DEV_ENV("RCW_TOP_GRID")) { const int g = std::atoi(v); if (g >= 1 && g <= 65536) d.top_grid = g; }
+    if (const char* v = RCW_DEV_ENV("RCW_TOP_STORE_GRID")) { const int g = std::atoi(v); if (g >= 1 && g <= 65536) d.top_store_grid = g; }
+    // The two-kernel form where the geometry allows it: the unit kernels (whole tiles in runs of 256 / 128 / 64 / 32 rows)
+    // or the flat kernel (any pixel scale from 9, any image height that is a multiple of 4 from 42 rows)
+    int unit = d.top_lds > 0 ? rcw_top_split_unit(d) : 0;
+    const int flat = d.top_lds > 0 ? rcw_top_flat_cols(d) : 0;
+    // (several units a chunk: the flat kernel is the faster one — 384² / 320² / 288² px images, µs per GiB: 181 / 194 / 207 with
+    // 2 / 4 / 8 units against 176 / 175 / 173; whole 256-row chunks keep rcw_top_store_kernel: 159 against 179)
+    if (flat && unit && unit < 256) unit = 0;
+    if (const char* v = RCW_DEV_ENV("RCW_TOP_FLAT")) { const int f = std::atoi(v); if (f == 1 && flat) unit = 0; if (f == 0 && rcw_top_split_unit(d) && d.top_lds > 0) unit = rcw_top_split_unit(d); }
+    const bool eligible = unit || flat;
+    d.top_unit_px = unit ? unit : 256;
+    d.top_flat = unit ? 0 : flat;
+    d.top_plane_words = d.top_flat ? rcw_top_plane_words(d) : 0;
+    // ... at every batch size where a step's camera fill and the drawing go in ONE launch (rcw_fill256_draw_kernel); where the drawing
+    // needs the side stream (another camera height, planes beyond 64 KiB, runs of agents), only where the batch is big enough to pay for
+    // the fork / join and the extra launch (kSideStreamMinBytes).  (Decided below, when the draw kernel's block and the runs are known.)
+    d.top_split = eligible ? 1 : 0;
+    if (want_form == RCW_TOP_VIEW_ONE_KERNEL || want_form == RCW_TOP_VIEW_IN_PLACE) d.top_split = 0;
+    if (want_form == RCW_TOP_VIEW_TWO_KERNELS) {
+        if (eligible) d.top_split = 1;
+        else if (!lenient) return fail(RCW_ERR_UNSUPPORTED, "this geometry does not take the two-kernel form (pu_per_tu >= 8, image height a multiple of 4 and of at least 42 rows, bit plane within LDS)");
+    }
+    if (!d.top_split) { d.top_unit_px = 256; d.top_flat = 0; d.top_plane_words = 0; }
+    // rcw_update_top_view alone has no camera fill to hide the drawing behind (kAloneTwoKernelsPixels, kAloneTwoKernelsBelowPu): draw ->
+    // store back to back for images from 256 x 256 px, pixel scales that are no multiple of 4 and tiles below 16 px; the one-kernel form
+    // keeps what is left of the two-kernel form's geometries — and every geometry the two-kernel form cannot take.
+    {
+        const long long px = (long long)H * cfg->pu_per_tu * W * cfg->pu_per_tu;
+        d.top_alone_split = d.top_split && (px >= (long long)top_rule(kAloneTwoKernelsPixels) || (cfg->pu_per_tu & 3) != 0 || cfg->pu_per_tu < (int)top_rule(kAloneTwoKernelsBelowPu)) ? 1 : 0;
+    }
+    if (const char* v = RCW_DEV_ENV("RCW_TOP_ALONE_SPLIT")) d.top_alone_split = d.top_split && std::atoi(v) ? 1 : 0;
+    // draw kernel: one workgroup of 4 wavefronts per agent; where the bit plane leaves room for one or two workgroups on a CU
+    // (kDrawWideBlockLds), 8 to 16 wavefronts: a lane per ray for N > 256, two lanes a ray for fewer
+    if (rcw_top_view_lds_bytes(d) / (d.top_lds > 0 ? d.top_lds : 1) > (size_t)top_rule(kDrawWideBlockLds)) {
+        const int b = ((N + 255) / 256) * 256;
+        d.top_draw_block = b < (int)top_rule(kDrawBlockMin) ? (int)top_rule(kDrawBlockMin) : (b > (int)top_rule(kDrawBlockMax) ? (int)top_rule(kDrawBlockMax) : b);
+    }
+    // ... and alone, with tens of thousands of small images, one or two wavefronts an agent (the set-up per wavefront is what such a batch costs)
+    d.top_draw_block_alone = d.top_draw_block;
+    if (d.top_draw_block == 256) d.top_draw_block_alone = B >= (size_t)top_rule(kAloneBlock64Agents) ? 64 : (B >= (size_t)top_rule(kAloneBlock128Agents) ? 128 : 256);
+    if (const char* v = RCW_DEV_ENV("RCW_TOP_DRAW_BLOCK")) { const int b = std::atoi(v); if (b == 64 || b == 128 || b == 256 || b == 512 || b == 768 || b == 1024) d.top_draw_block = d.top_draw_block_alone = b; }
+    // runs of agents: where the lines are long against the camera image's columns the drawing does not fit beside the camera fill; with
+    // several GiB of top view a step, runs of >= 1 GiB let the rest of it hide beside the storing of earlier runs
+    if ((long long)top_rule(kRunsLineToCameraDen) * ((long long)H + W) * cfg->pu_per_tu >= (long long)top_rule(kRunsLineToCameraNum) * Hc) {
+        const size_t gib = (B * (size_t)H * W * cfg->pu_per_tu * cfg->pu_per_tu * sizeof(uint32_t)) >> 30;
+        d.top_runs = gib >= (size_t)top_rule(kRuns4Gib) ? 4 : (gib >= (size_t)top_rule(kRuns2Gib) ? 2 : 1);
+    }
+    if (want_runs >= 1) d.top_runs = want_runs <= 8 ? (want_runs <= (int)B ? want_runs : (int)B) : 8;
+    // a step's camera fill and the drawing in one launch where the geometry allows (256-row camera view, one run, planes of a
+    // 256-thread draw workgroup): no side stream in the step
+    d.top_fused = rcw_fill_draw_fusable(d) ? 1 : 0;
+    if (const char* v = RCW_DEV_ENV("RCW_TOP_FUSED")) d.top_fused = d.top_fused && std::atoi(v) ? 1 : 0;
+    if (d.top_split && !d.top_fused && want_form != RCW_TOP_VIEW_TWO_KERNELS &&
+        (double)(B * (size_t)H * W * cfg->pu_per_tu * cfg->pu_per_tu * sizeof(uint32_t)) < top_rule(kSideStreamMinBytes)) {
+        d.top_split = 0; d.top_unit_px = 256; d.top_flat = 0; d.top_plane_words = 0; d.top_alone_split = 0;
+    }
+    // Several draw workgroups an agent (rcw_top_draw_kernel: each walks a part of the fan and ORs its plane into the agent's) where a batch
+    // of big images leaves draw slots empty: as many parts as fill them (kPartsMax, kPartsMinRays).  Only with rcw_top_store_kernel, which
+    // reads every plane word exactly once and leaves the zero the next drawing needs.
+    const int draw_per_cu = rcw_top_draw_per_cu(d, d.top_draw_block, hw.lds_per_cu, hw.waves_per_cu - (int)top_rule(kFillWavefrontsPerCu));
+    d.top_parts = 1;
+    if (d.top_split && !d.top_flat && d.top_unit_px == 256 && !d.top_fused) {
+        const long long slots = (long long)hw.cus * draw_per_cu;
+        int parts = (int)std::min<long long>((long long)top_rule(kPartsMax), slots / (long long)B);
+        while (parts > 1 && N / parts < (int)top_rule(kPartsMinRays)) --parts;
+        d.top_parts = parts < 1 ? 1 : parts;
+        if (const char* v = RCW_DEV_ENV("RCW_TOP_PARTS")) { const int q = std::atoi(v); if (q >= 1 && q <= 4 && N / q >= 16) d.top_parts = q; }
+    }
+    // The drawing first on the handle's stream and the camera fill on the side stream (launch_top_view) where the fill is the SHORTER of the
+    // two: it then ends before the store kernel starts (where it is the longer one it runs into the store kernel — two moving windows on one
+    // HBM — and the step takes up to 60 % longer).  Both are estimated from the sizes: the fill at kFillGBperMs plus its late start, the
+    // drawing at its measured floor per GiB of top view — of the batch or, for a small one, of most of one round of workgroups.
+    {
+        const double fill_us = (double)B * N * Hc * 4.0 / top_rule(kFillGBperMs) + top_rule(kFillLateStartUs);
+        const double image_gib = (double)H * W * cfg->pu_per_tu * cfg->pu_per_tu * 4.0 / (double)(1u << 30);
+        const double round_gib = (double)hw.cus * draw_per_cu * image_gib;
+        const double top_gib = std::max((double)B * image_gib, top_rule(kDrawPartialRound) * round_gib);
+        const double draw_us = top_gib * (N >= (int)top_rule(kDrawManyRays) ? top_rule(kDrawUsPerGibManyRays) : top_rule(kDrawUsPerGibFewRays));
+        d.top_draw_first = d.top_split && !d.top_fused && d.top_runs <= 1 && fill_us <= draw_us ? 1 : 0;
+    }
+    if (const char* v = RCW_DEV_ENV("RCW_TOP_DRAW_FIRST")) d.top_draw_first = d.top_split && !d.top_fused && std::atoi(v) ? 1 : 0;
+    if (const char* v = RCW_DEV_ENV("RCW_TOP_STORE_PLAIN")) d.top_store_plain = std::atoi(v) ? 1 : 0;
+    return RCW_OK;
+}
+
+// the RCW_TOP_VIEW_* name of the form a plan takes inside a step, and of rcw_update_top_view alone
+int top_form_alone(const RcwPlan& d, bool split) { return !d.top_view ? RCW_TOP_VIEW_NONE : split ? RCW_TOP_VIEW_TWO_KERNELS : d.top_lds ? RCW_TOP_VIEW_ONE_KERNEL : RCW_TOP_VIEW_IN_PLACE; }
+int top_form_alone(const RcwPlan& d) { return top_form_alone(d, d.top_split && d.top_alone_split); }
+int top_form_in_step(const RcwPlan& d) { return top_form_alone(d, d.top_split != 0); }
+
+// The one-launch step pays where the fill outlasts the casting half's own life: one casting workgroup marches FIVE fans one after the
+// other, so a small batch waits for it (4096 x 256 columns: 17 us of casting life under a 154 us fill; 64 agents: 22 us a step against
+// 12 for cast kernel + fill).  Measured crossovers (profiles/r06_small_batches.txt, frames of a step): 8x8 map, 256 columns ~128 MiB;
+// 16x16, 512 columns ~100 MiB; 32x32, 1024 columns ~350 MiB; 8x8, 64 columns below 64 MiB — the casting life fits
+// kStepCastBaseUs + kStepCastUsPerUnit x (view columns a lane x 5 fans x (H + W) tiles a ray may cross), the fill kFillGBperMs.
+constexpr double kStepCastBaseUs = 4.5, kStepCastUsPerUnit = 0.045;
+bool step_one_launch_pays(const RcwDev& d)
+{
+    const int lanes = d.N <= 256 ? 64 : 256;                                // a wavefront per agent up to 256 view columns, a workgroup beyond
+    const double units = (double)((d.N + lanes - 1) / lanes) * 5.0 * (double)(d.H + d.W);
+    const double cast_us = kStepCastBaseUs + kStepCastUsPerUnit * units;
+    const double fill_us = (double)d.B * d.N * d.Hc * 4.0 / top_rule(kFillGBperMs);
+    return fill_us >= cast_us;
+}
+
+// rcw_set_walls' refusals (include/rcw.h, "wall layouts") as a pure host function — no handle, no device: the development build exports it
+// (rcw_dev_validate_walls).  0, or RCW_ERR_INVALID_ARGUMENT with the reason, naming the layout and the tile, in msg.  EVERY layout handed
+// over is checked, also one no agent of the mask takes: a ring tile that is no wall lets a march leave the map (stage_tile_bytes, the guard
+// bands of cast_ray_guarded), and a later call may well index it.
+int validate_walls(int H, int W, int B, const uint8_t* walls, int layouts, const int32_t* index, const uint8_t* mask, char* msg, size_t cap)
+{
+    if (!walls) { std::snprintf(msg, cap, "NULL walls"); return RCW_ERR_INVALID_ARGUMENT; }
+    if (layouts < 1) { std::snprintf(msg, cap, "layouts must be >= 1 (got %d)", layouts); return RCW_ERR_INVALID_ARGUMENT; }
+    if (!index && layouts != 1 && layouts != B) {
+        std::snprintf(msg, cap, "a NULL layout index needs 1 layout or one per agent (%d); got %d layouts", B, layouts);
+        return RCW_ERR_INVALID_ARGUMENT;
+    }
+    for (int a = 0; index && a < B; ++a) {
+        if (mask && !mask[a]) continue;
+        if (index[a] < 0 || index[a] >= layouts) {
+            std::snprintf(msg, cap, "agent %d: layout index %d not in 0..%d", a, index[a], layouts - 1);
+            return RCW_ERR_INVALID_ARGUMENT;
+        }
+    }
+    for (int m = 0; m < layouts; ++m) {
+        const uint8_t* const q = walls + (size_t)m * (size_t)H * (size_t)W;
+        int free_tiles = 0;
+        for (int j = 1; j <= W; ++j)
+            for (int i = 1; i <= H; ++i) {
+                const bool wall = q[(i - 1) + (size_t)H * (j - 1)] != 0;
+                const bool ring = i == 1 || i == H || j == 1 || j == W;                   // SR:57-60
+                if (ring && !wall) {
+                    std::snprintf(msg, cap, "layout %d: ring tile (%d,%d) is not a wall (the ring ends every ray)", m, i, j);
+                    return RCW_ERR_INVALID_ARGUMENT;
+                }
+                if (!ring && !wall) ++free_tiles;
+            }
+        if (free_tiles < 2) {
+            std::snprintf(msg, cap, "layout %d: %d free interior tile(s), a goal and a player need two", m, free_tiles);
+            return RCW_ERR_INVALID_ARGUMENT;
+        }
+    }
+    return RCW_OK;
+}
+
+int validate_config(const rcw_config* c, int32_t batch)
+{
+    if (c->abi_version != RCW_ABI_VERSION)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_config.abi_version %d != %d", c->abi_version, RCW_ABI_VERSION);
+    if (batch < 1) return fail(RCW_ERR_INVALID_ARGUMENT, "batch must be >= 1 (got %d)", batch);
+    if (c->height_tile_map_tu < 3 || c->width_tile_map_tu < 3)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "tile map must be at least 3x3 (got %dx%d)",
+                    c->height_tile_map_tu, c->width_tile_map_tu);
+    // the cast kernel stages a byte per tile in dynamic LDS next to a few static words: 64 KiB per workgroup in all
+    if ((long long)c->height_tile_map_tu * c->width_tile_map_tu + 2ll * c->height_tile_map_tu > 65536 - 256)   // (+ the cast kernel's two guard bands of H bytes)
+        return fail(RCW_ERR_UNSUPPORTED, "tile map larger than 65280 tiles does not fit the LDS staging");
+    if (c->num_directions < 1 || c->num_rays < 1 || c->height_camera_view_pu < 1)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "num_directions, num_rays, height_camera_view_pu must be >= 1");
+    if (c->num_rays > (1 << 24)) return fail(RCW_ERR_INVALID_ARGUMENT, "num_rays not exactly representable in Float32");
+    if (c->num_directions > (1 << 20) || (long long)c->num_directions * c->num_rays > (1ll << 24))
+        return fail(RCW_ERR_UNSUPPORTED, "num_directions * num_rays = %lld: the (direction, ray) table is limited to 2^24 entries",
+                    (long long)c->num_directions * c->num_rays);
+    if (c->height_camera_view_pu > (1 << 20))
+        return fail(RCW_ERR_UNSUPPORTED, "height_camera_view_pu larger than 2^20");
+    if (c->reward_type < RCW_REWARD_FLOAT32 || c->reward_type > RCW_REWARD_INT64)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "reward_type must be one of RCW_REWARD_* (got %d)", c->reward_type);
+    if (!std::isfinite(c->goal_reward) || !std::isfinite(c->goal_reward_f64))
+        return fail(RCW_ERR_INVALID_ARGUMENT, "goal_reward must be finite");
+    if ((c->reward_type == RCW_REWARD_INT32 || c->reward_type == RCW_REWARD_INT64) &&
+        (c->goal_reward_f64 != std::floor(c->goal_reward_f64) || std::fabs(c->goal_reward_f64) > 2147483647.0))
+        return fail(RCW_ERR_INVALID_ARGUMENT, "goal_reward_f64 = %g is not an integer the reward type holds", c->goal_reward_f64);
+    if (c->world_unit_bits != 32 && c->world_unit_bits != 64)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "world_unit_bits must be 32 or 64 (got %d)", c->world_unit_bits);
+    if (c->world_unit_bits == 64) {
+        if (!(c->player_radius_wu_f64 > 0.0 && c->player_radius_wu_f64 < 0.5))
+            return fail(RCW_ERR_INVALID_ARGUMENT, "player_radius_wu_f64 must be in (0, 0.5)");
+        if (!(c->position_increment_wu_f64 > 0.0) || !std::isfinite(c->position_increment_wu_f64) ||
+            !(c->semi_field_of_view_wu_f64 > 0.0) || !std::isfinite(c->semi_field_of_view_wu_f64) ||
+            !(c->camera_height_tile_wu_f64 > 0.0) || !std::isfinite(c->camera_height_tile_wu_f64))
+            return fail(RCW_ERR_INVALID_ARGUMENT, "the *_f64 world-unit parameters must be positive and finite");
+    }
+    if (!(c->player_radius_wu > 0.0f && c->player_radius_wu < 0.5f))   // "should be less than 0.5" SR:47
+        return fail(RCW_ERR_INVALID_ARGUMENT, "player_radius_wu must be in (0, 0.5)");
+    if (!(c->position_increment_wu > 0.0f) || !std::isfinite(c->position_increment_wu))
+        return fail(RCW_ERR_INVALID_ARGUMENT, "position_increment_wu must be positive and finite");
+    if (!(c->semi_field_of_view_wu > 0.0f) || !std::isfinite(c->semi_field_of_view_wu))
+        return fail(RCW_ERR_INVALID_ARGUMENT, "semi_field_of_view_wu must be positive and finite");
+    if (c->render_top_view && (c->pu_per_tu < 1 || c->pu_per_tu > 4096))
+        return fail(RCW_ERR_INVALID_ARGUMENT, "pu_per_tu must be in 1..4096 for the top view");
+    if (!(c->camera_height_tile_wu > 0.0f) || !std::isfinite(c->camera_height_tile_wu))
+        return fail(RCW_ERR_INVALID_ARGUMENT, "camera_height_tile_wu must be positive and finite");
+    if (c->dda_tie_break < 0 || c->dda_tie_break > 1 || c->dda_distance < 0 || c->dda_distance > 1 ||
+        c->normalize_mode < 0 || c->normalize_mode > 1 || c->out_of_bounds < 0 || c->out_of_bounds > 1)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "dda_tie_break / dda_distance / normalize_mode / out_of_bounds out of range");
+    return RCW_OK;
+}
+
+namespace {
+// the channels of a format: its colour's, then the depth plane's
+int view_channels(int32_t format) { return ((format & 3) == RCW_VIEW_RGB8 ? 3 : (format & 3) == RCW_VIEW_GRAY8 ? 1 : 0) + (format & RCW_VIEW_DEPTH8 ? 1 : 0); }
+}  // namespace
+
+// What rcw_set_learner_view_stack's arguments ask of this geometry (ViewPlan, rcw_handle.h), or the refusal
+int plan_learner_view(const rcw_config& cfg, const RcwDev& dev, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags,
+                      int32_t frames, ViewPlan* plan)
+{
+    const int Hc = cfg.height_camera_view_pu, N = cfg.num_rays;
+    if (format < RCW_VIEW_OFF || format > RCW_VIEW_GRAYD8 || format == (RCW_VIEW_RGB8 | RCW_VIEW_GRAY8))
+        return fail(RCW_ERR_INVALID_ARGUMENT, "format must be RCW_VIEW_OFF / RCW_VIEW_RGB8 / RCW_VIEW_GRAY8 / RCW_VIEW_DEPTH8 / RCW_VIEW_RGBD8 / RCW_VIEW_GRAYD8 (got %d)", format);
+    if (flags & ~RCW_VIEW_ONLY) return fail(RCW_ERR_INVALID_ARGUMENT, "unknown learner view flags 0x%x", (unsigned)flags);
+    if (format == RCW_VIEW_OFF && flags) return fail(RCW_ERR_INVALID_ARGUMENT, "RCW_VIEW_ONLY needs a format");
+    if (frames < 1 || frames > RCW_VIEW_MAX_FRAMES)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "frames must be in 1..%d (got %d)", RCW_VIEW_MAX_FRAMES, frames);
+    if (format == RCW_VIEW_OFF) return RCW_OK;
+    if (layout != RCW_VIEW_CHW && layout != RCW_VIEW_HWC)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "layout must be RCW_VIEW_CHW or RCW_VIEW_HWC (got %d)", layout);
+    if (height < 1 || height > Hc || width < 1 || width > N)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "learner view size %d x %d outside 1..%d x 1..%d (no up-sampling)", height, width, Hc, N);
+    if (frames > 1 && (long long)view_channels(format) * height * width >= (1ll << 31))
+        return fail(RCW_ERR_UNSUPPORTED, "a stack of frames of 2 GiB or more");
+    if (frames > 1 && layout != RCW_VIEW_CHW)
+        return fail(RCW_ERR_UNSUPPORTED, "a stack of %d frames needs RCW_VIEW_CHW (slot s is channels [s C, (s + 1) C))", frames);
+    RcwView& v = plan->v;
+    v.C = view_channels(format);
+    v.depth = format & RCW_VIEW_DEPTH8 ? 1 : 0;
+    v.hwc = layout == RCW_VIEW_HWC ? 1 : 0;
+    v.h = height; v.w = width;
+    std::vector<int32_t>& t = plan->tab;
+    try { t.resize((size_t)height + width + 2 + (v.depth ? (size_t)Hc + 1 : 0)); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    long long max_rows = 0, max_cols = 0;
+    for (int r = 0; r <= height; ++r) t[r] = (int32_t)((long long)r * Hc / height);
+    for (int c = 0; c <= width; ++c) t[(size_t)height + 1 + c] = (int32_t)((long long)c * N / width);
+    for (int r = 0; r < height; ++r) max_rows = std::max<long long>(max_rows, t[r + 1] - t[r]);
+    for (int c = 0; c < width; ++c) max_cols = std::max<long long>(max_cols, t[(size_t)height + 2 + c] - t[(size_t)height + 1 + c]);
+    const long long n = max_rows * max_cols;
+    v.wide = n * 256 + n >= (1ll << 31) ? 1 : 0;          // (a box's channel sum + n/2 must stay below 2^31 for 32-bit sums)
+    v.full_ok = height == Hc && width == N && rcw_view_full_eligible(dev, v.C, v.hwc) ? 1 : 0;
+    if (v.depth) {
+        // the ceiling / floor depth byte De(y) = (255 u + Hc/2) / Hc, u = Hc - 2 min(y, Hc - 1 - y) (include/rcw.h), summed over rows [0, y):
+        // at most 255 * 2^20
+        int32_t* const ds = t.data() + (size_t)height + width + 2;
+        ds[0] = 0;
+        for (int y = 0; y < Hc; ++y) ds[y + 1] = ds[y] + (int32_t)((255ll * (Hc - 2 * std::min(y, Hc - 1 - y)) + Hc / 2) / Hc);
+    }
+    return RCW_OK;
+}
+
+#ifdef RCW_DEV_SWITCHES
+#include "dev/api_plan_export.inc"   // the rules and the step's facts without a device (tests/test_top_view_plan.py, tests/test_step_state.py)
+#endif

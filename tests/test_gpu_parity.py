@@ -1241,7 +1241,7 @@ def test_captured_step_with_top_view_replays(rcw, oracle, shape):
 
 def test_drawing_first_and_camera_fill_on_the_side_stream(rcw, oracle, monkeypatch):
     """Round 5: where the camera fill is the shorter of the two, a step keeps the top view's DRAWING on the handle's stream (cast -> draw ->
-    store, no event between them) and sends the camera fill to the side stream (rcw_api.hip, launch_top_view).  The rule takes it for big
+    store, no event between them) and sends the camera fill to the side stream (rcw_step.hip, launch_top_view).  The rule takes it for big
     batches only (768^2 x 455 and 1024^2 x 256 in test_full_size_top_view run through it); here it is forced on small ones through the
     development build (RCW_TOP_DRAW_FIRST=1): plain steps, a masked reset, a change of stream, and a step captured into a HIP graph
     and replayed — both images and the state against the oracle every time."""

@@ -3,7 +3,7 @@
 The casting half of a launch leaves one byte per agent beside the slots it writes: bit s set when the frame the action s selects is the
 very frame of the current state (a blocked / goal / raising move SR:162-176, an invalid action SR:140, or a move or turn so close to a wall
 that every column stays saturated SR:433).  The fill half of the NEXT launch does not store the chunks of such an agent — if the handle
-knows that the bound observation buffer holds the current frames (rcw_api.hip, StepFacts::obs_current).  What must hold whatever was skipped: after
+knows that the bound observation buffer holds the current frames (rcw_handle.h, StepFacts::obs_current).  What must hold whatever was skipped: after
 every step the buffer equals the reference's camera_view for EVERY agent.
 
 Every rollout here compares every pixel of every agent with the CPU oracle after every step, and does between steps whatever may make

@@ -145,7 +145,7 @@ def test_line_carry_walk_equals_the_closed_form():
     """What top_draw actually carries: the 32-bit FRACTION of k * slope / 2^32 + 1/2 + 2^-18 with
     slope = floor(2^32 b / a) (computed in Float64 as the kernel does), the minor axis stepping on the carry, started
     at an arbitrary pixel k0 with one 64-bit multiply-add.  Against floor((2 b k + a) / (2 a)) for every (a, b) up to
-    96, for the extreme slopes, and for random lines up to the 16,384 pixels the kernels accept (rcw_api.hip)."""
+    96, for the extreme slopes, and for random lines up to the 16,384 pixels the kernels accept (rcw_rules.hip)."""
     frac0 = 0x80000000 + (1 << 14)
 
     def check(a, b, ks):
@@ -251,7 +251,7 @@ def test_flat_store_kernel_reads_stay_inside_their_allocations():
     """rcw_top_store_flat_kernel's loads are CLAMPED into their arrays, not predicated (rcw_top_store.hip, `issue`), and two of
     them reach past the element they name: three tile_map words from any word of a map (12-byte load), eight plane words
     from a chunk's first word (two 16-byte loads).  Restated here with the allocation sizes of rcw_api.hip /
-    rcw_api.hip — tile_map: B * nwords words + 16 bytes; top_plane: B * PW words + 64 bytes, PW = ((Ht Wt + 510) div
+    rcw_step.hip — tile_map: B * nwords words + 16 bytes; top_plane: B * PW words + 64 bytes, PW = ((Ht Wt + 510) div
     256) * 8 — and checked for the EXTREME addresses over geometries whose images are not a whole number of chunks
     (profiles/r04_exp5_fault.txt: one of the three candidate causes of round 3's unexplained memory access fault)."""
     rng = np.random.default_rng(4)

@@ -1,4 +1,4 @@
-"""The facts of a step (csrc/rcw_api.hip, StepFacts): which launches a step of a handle makes, and whether the one-launch step may leave
+"""The facts of a step (csrc/rcw_handle.h, StepFacts): which launches a step of a handle makes, and whether the one-launch step may leave
 the frame of an agent whose view it does not change as it is (`keep`).  A wrong fact does not crash: it leaves stale frames in the
 observation batch, so the transitions are pinned here, on the CPU.  The development build drives a StepFacts through a list of events
 without a device (rcw_dev_step_facts); the helpers below put the events together as the entry points of include/rcw.h do, and every

@@ -1,4 +1,4 @@
-"""The top view's rule as data: rcw_api.hip keeps every threshold of update_top_view!'s choice of a form in ONE
+"""The top view's rule as data: rcw_rules.hip keeps every threshold of update_top_view!'s choice of a form in ONE
 table (kTopRules: name, value, unit, the profile line that put it there) and decides with a pure function of the configuration, the
 batch and three numbers of the device (top_view_rule).  The development build exports both without needing a device:
 
@@ -78,8 +78,8 @@ def test_every_rule_names_its_evidence(devlib):
             assert os.path.exists(os.path.join(ROOT, f)), (name, f)
     assert sum(1 for r in rows if "profiles/" in r[3]) >= 16               # (the others: an exactness limit, a rule's second factor, "same measurement")
     # the source holds no second copy of a threshold: the rule's function reads the table
-    src = open(os.path.join(ROOT, "raycastworlds.jl_amd", "csrc", "rcw_api.hip")).read()
-    body = src[src.index("int top_view_rule("):src.index("// Which form update_top_view! (SR:446-483) takes for this handle (top_view_rule)")]
+    src = open(os.path.join(ROOT, "raycastworlds.jl_amd", "csrc", "rcw_rules.hip")).read()
+    body = src[src.index("int top_view_rule("):src.index("// The one-launch step pays where")]                # (the rule and the names of its forms)
     for literal in ("52 * 1024", "156 * 1024", ">= 65536", "24576", "12288", "6.5e6", "55.0", "34.0", "0.7 *", "160 * 1024", "<< 20"):
         assert literal not in body, literal
 
@@ -104,7 +104,7 @@ def test_the_devices_numbers_are_arguments(devlib):
 
 
 def test_the_steps_rule_agrees_with_the_measured_crossovers(devlib):
-    """rcw_api.hip, step_one_launch_pays: the one-launch step where the fill outlasts the casting half's five serial fans.  For every line of
+    """rcw_rules.hip, step_one_launch_pays: the one-launch step where the fill outlasts the casting half's five serial fans.  For every line of
     profiles/r06_small_batches.txt (us per step of both forms, four geometries, 1 .. 8192 agents) the rule picks the form that was measured
     faster — ties within 6 % (one box's run-to-run spread at these sizes) may go either way."""
     from raycastworlds_jl_amd import _capi

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tests/golden/top_view_plan_cases.json: what the top view's rule (rcw_api.hip: kTopRules, top_view_rule) decides for every shape the
+"""tests/golden/top_view_plan_cases.json: what the top view's rule (rcw_rules.hip: kTopRules, top_view_rule) decides for every shape the
 committed profiles were taken with — the table of profiles/*_top_view_shapes.txt (~1 GiB of top view a launch) and the batches the rule's
 thresholds were measured at (kTopRules' evidence: small batches, big images in few / many agents, another camera height).
 
