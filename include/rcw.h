@@ -392,6 +392,57 @@ RCW_API int rcw_goal_distance(rcw_handle* h, int32_t* distance /* (B) */, int32_
 RCW_API int rcw_goal_distance_device_ptr(rcw_handle* h, void** distance, void** start_distance, void** progress);
 RCW_API int rcw_goal_distance_field(rcw_handle* h, int32_t first, int32_t count, void* out_host /* UInt16 (H*W, count) */);
 RCW_API int rcw_goal_distance_field_device_ptr(rcw_handle* h, void** ptr);
+/* ---- the seen map (this build's addition: the tiles each agent's view rays have crossed since its episode began) -----------------------
+ * Opt-in per handle: what a coverage / exploration bonus, a "goal in sight" signal and a fog-of-war observation need, kept on the device
+ * at no host synchronisation.  A handle that never enables it runs exactly the kernels it ran before.  The ABI is additive:
+ * RCW_ABI_VERSION and rcw_config are what they were.
+ * For agent a, bits(t) of tile t is what its tile map holds NOW: the WALL bit | the GOAL bit << 1.
+ *   map          UInt8 (H*W, B), tile (i, j), 1-based, of agent a at a*H*W + (i-1) + H*(j-1) — the tile map's own linear order, the one
+ *                rcw_set_walls and the goal-distance field use.  0 = not seen in the agent's current episode; otherwise 1 + bits(t) as of
+ *                the call that first saw it: 1 free, 2 wall, 3 goal; 4 appears only where rcw_set_state put a goal into a wall.
+ *   seen_count   Int32 (B): the number of non-zero entries of the agent's map.
+ *   newly_seen   Int32 (B): the number of entries the last call turned from 0 to non-zero; 0 after any call that started the agent's
+ *                map afresh.
+ *   goal_seen    Int32 (B): 1 if map[goal tile] is non-zero, else 0; 0 when the goal is off the map.
+ * "Seen" is exactly what the camera saw.  For the agent's current pose a call takes each of the handle's N rays — the rows of the ray
+ * table for its heading, as cast_rays! does (SR:195-231) — and marks every tile RayCaster.cast_ray's march visits with the handle's
+ * dda_tie_break, from the player's tile (wu_to_tu of its position) through the stop tile, both included; dda_distance plays no part in
+ * which tiles are visited.  A player whose tile is off the map, or whose position is NaN, marks nothing; a player standing on an obstacle
+ * tile marks that tile alone.  Every map the library accepts has the wall ring, so every ray stops on the map; the kernel nonetheless
+ * never reads or writes outside the agent's H*W entries, and what it marks for a ray that left the map is unspecified.  Float64 worlds
+ * march in Float64.
+ * What each call does — stream-ordered on the handle's stream, behind everything the call already queues:
+ *   rcw_set_seen_map(h, 1)        allocates; every agent's map is cleared and marked from its current pose: seen_count is the result,
+ *                                 newly_seen = 0, goal_seen is set.  On a handle that has it, the same again.  An allocation failure
+ *                                 leaves what was there.
+ *   rcw_set_seen_map(h, 0)        frees it (RCW_OK also where there was none).
+ *   rcw_reset, rcw_set_state, rcw_set_state64, rcw_set_walls
+ *                                 the agents in the call's mask are cleared and marked from the new pose against the new world,
+ *                                 newly_seen = 0, and the episode counter is recorded; an agent outside the mask keeps every byte and
+ *                                 its three words.  The mask decides, not the episode counter.
+ *   rcw_step, rcw_step_device     an agent the call restarted (its episode counter, rcw_episode, differs from the one recorded at its
+ *                                 last clear: done or truncated under cfg.auto_reset) is cleared and marked from the new pose,
+ *                                 newly_seen = 0, and the counter is recorded.  Every other agent is marked from its pose after the step:
+ *                                 newly_seen = the tiles that were 0 before, seen_count += newly_seen, goal_seen may go 0 -> 1 and never
+ *                                 back within an episode.  The rule needs no knowledge of the action: an invalid device action, a raising
+ *                                 move under RCW_OOB_ERROR and a blocked move leave the pose — newly_seen 0; a turn can see new tiles.
+ *   rcw_cast_rays, rcw_update_camera_view, rcw_update_top_view, rcw_set_direction_table*, rcw_set_step_form, rcw_set_time_limit, the
+ *   learner-view and goal-distance calls and every getter   nothing.  A new direction table takes effect at the next marking.
+ * A replayed HIP graph of a step marks like any step: nothing about this alternates on the host, the recorded episode counter lives on
+ * the device.  The device pointers are stable until the next rcw_set_seen_map.  The kernel (one launch, rcw_seen_map_kernel) runs behind
+ * the step's own and OUTSIDE rcw_profile's events: cast_ms + top_view_ms + fill_ms is what it was.
+ *   rcw_seen_map_enabled            0 / 1.
+ *   rcw_seen_words                  host copies of the three words (any pointer may be NULL); waits for the stream as rcw_done does.
+ *   rcw_seen_words_device_ptr       the three arrays where they live (any pointer may be NULL).
+ *   rcw_seen_map                    the maps of agents [first, first+count) to host memory, H*W UInt8 each (waits for the stream).
+ *   rcw_seen_map_device_ptr         the map batch in DEVICE memory.
+ * The last four return RCW_ERR_UNSUPPORTED on a handle that has not enabled it. */
+RCW_API int rcw_set_seen_map(rcw_handle* h, int32_t enable);
+RCW_API int rcw_seen_map_enabled(rcw_handle* h, int32_t* out);
+RCW_API int rcw_seen_words(rcw_handle* h, int32_t* seen_count /* (B) */, int32_t* newly_seen /* (B) */, int32_t* goal_seen /* (B) */);
+RCW_API int rcw_seen_words_device_ptr(rcw_handle* h, void** seen_count, void** newly_seen, void** goal_seen);
+RCW_API int rcw_seen_map(rcw_handle* h, int32_t first, int32_t count, void* out_host /* UInt8 (H*W, count) */);
+RCW_API int rcw_seen_map_device_ptr(rcw_handle* h, void** ptr);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

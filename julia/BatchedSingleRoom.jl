@@ -422,6 +422,43 @@ function goal_distance_field_device_ptr(env::BatchedSingleRoom)
     check(ccall((:rcw_goal_distance_field_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
 end
 
+# ---- the seen map (this build's addition; include/rcw.h, rcw_set_seen_map) ------------------------------------------------------
+"""
+    set_seen_map!(env, on = true)
+
+Keep, on the device, the tiles each agent's view rays have crossed since its episode began, behind every `act!`, `reset!`,
+`set_state!` and `set_walls!`: `seen_words(env)` returns `(seen_count, newly_seen, goal_seen)`, each `Vector{Int32}` of `batch`;
+`seen_map(env)` the `UInt8` maps as `(H, W, batch)`: `0` not seen, else `1` free, `2` wall, `3` goal.  A coverage bonus is
+`c .* newly_seen`.
+"""
+function set_seen_map!(env::BatchedSingleRoom, on::Bool = true)
+    check(ccall((:rcw_set_seen_map, librcw), Cint, (Ptr{Cvoid}, Int32), env.handle, on ? 1 : 0))
+    return nothing
+end
+function seen_map_enabled(env::BatchedSingleRoom)
+    n = Ref{Int32}(0)
+    check(ccall((:rcw_seen_map_enabled, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}), env.handle, n)); n[] != 0
+end
+function seen_words(env::BatchedSingleRoom)
+    c, n, g = (Vector{Int32}(undef, env.batch) for _ in 1:3)
+    check(ccall((:rcw_seen_words, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), env.handle, c, n, g))
+    return (seen_count = c, newly_seen = n, goal_seen = g)
+end
+function seen_words_device_ptr(env::BatchedSingleRoom)
+    c, n, g = (Ref{Ptr{Cvoid}}(C_NULL) for _ in 1:3)
+    check(ccall((:rcw_seen_words_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                env.handle, c, n, g))
+    return (seen_count = c[], newly_seen = n[], goal_seen = g[])
+end
+function seen_map(env::BatchedSingleRoom, first::Integer = 0, count::Integer = env.batch - first)
+    out = Array{UInt8, 3}(undef, env.config.height_tile_map_tu, env.config.width_tile_map_tu, count)
+    check(ccall((:rcw_seen_map, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}), env.handle, first, count, out)); out
+end
+function seen_map_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_seen_map_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
+
 # per-agent sticky status: 0, -5 where the reference would have raised BoundsError, -2 for an invalid device action,
 # 1 (a warning) where sample_empty_position gave up after max_tries and returned an occupied tile (utils.jl:34 @warns there)
 function status(env::BatchedSingleRoom)

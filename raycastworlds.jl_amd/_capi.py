@@ -153,6 +153,12 @@ SIGNATURES = {
     "rcw_goal_distance_device_ptr": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
     "rcw_goal_distance_field": [_vp, _i32, _i32, _vp],
     "rcw_goal_distance_field_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_set_seen_map": [_vp, _i32],
+    "rcw_seen_map_enabled": [_vp, C.POINTER(_i32)],
+    "rcw_seen_words": [_vp, _vp, _vp, _vp],
+    "rcw_seen_words_device_ptr": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+    "rcw_seen_map": [_vp, _i32, _i32, _vp],
+    "rcw_seen_map_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_ray_table": [_vp, _vp],
     "rcw_direction_table": [_vp, _vp],
     "rcw_timer_start": [_vp],

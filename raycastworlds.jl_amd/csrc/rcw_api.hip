@@ -952,6 +952,87 @@ int rcw_goal_distance_field_device_ptr(rcw_handle* h, void** ptr)
     return RCW_OK;
 }
 
+// The seen map (include/rcw.h).  Enabling allocates and marks every agent afresh at once, stream-ordered behind what is queued; enabling
+// again does the same again; an allocation failure leaves what was there.
+int rcw_set_seen_map(rcw_handle* h, int32_t enable)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::SeenMap& sm = h->seen;
+    if (!enable && !sm.on()) return RCW_OK;
+    rcw_handle::SeenMap fresh;
+    if (enable) {
+        // words and counter | packed bits | map: every part starts on a multiple of four bytes
+        const size_t B = (size_t)h->B, HW = (size_t)h->dev.H * (size_t)h->dev.W, bwords = (HW + 31) / 32;
+        const size_t bytes = 4 * B * sizeof(int32_t) + B * bwords * sizeof(uint32_t) + B * HW;
+        const hipError_t e = fresh.buf.hipMalloc(bytes);
+        if (e != hipSuccess) return fail(hip_code(e), "seen map of %zu bytes: %s", bytes, hip_failure(e));
+        int32_t* const w = fresh.buf.get<int32_t>();
+        fresh.words = RcwSeenWords{w, w + B, w + 2 * B};
+        fresh.last_episode = reinterpret_cast<uint32_t*>(w + 3 * B);
+        fresh.bits = fresh.last_episode + B;
+        fresh.map = reinterpret_cast<uint8_t*>(fresh.bits + B * bwords);
+    }
+    RCW_HIP(replace_buffers(h, {&sm.buf}, {&fresh.buf}));
+    sm.words = fresh.words; sm.last_episode = fresh.last_episode; sm.bits = fresh.bits; sm.map = fresh.map;
+    if (sm.on()) RCW_HIP(launch_seen_map(h, nullptr, kStackRefill));
+    return RCW_OK;
+}
+
+int rcw_seen_map_enabled(rcw_handle* h, int32_t* out)
+{
+    if (!h || !out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = h->seen.on() ? 1 : 0;
+    return RCW_OK;
+}
+
+extern "C++" {
+namespace {
+int need_seen_map(rcw_handle* h) { return h->seen.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no seen map (rcw_set_seen_map)"); }
+}  // namespace
+}  // extern "C++"
+
+int rcw_seen_words(rcw_handle* h, int32_t* seen_count, int32_t* newly_seen, int32_t* goal_seen)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_seen_map(h); if (rc) return rc;
+    rc = sync_and_check(h);
+    const size_t bytes = (size_t)h->B * sizeof(int32_t);
+    const RcwSeenWords& w = h->seen.words;
+    if (seen_count) RCW_HIP(hipMemcpy(seen_count, w.seen_count, bytes, hipMemcpyDeviceToHost));
+    if (newly_seen) RCW_HIP(hipMemcpy(newly_seen, w.newly_seen, bytes, hipMemcpyDeviceToHost));
+    if (goal_seen) RCW_HIP(hipMemcpy(goal_seen, w.goal_seen, bytes, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int rcw_seen_words_device_ptr(rcw_handle* h, void** seen_count, void** newly_seen, void** goal_seen)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = need_seen_map(h); if (rc) return rc;
+    if (seen_count) *seen_count = h->seen.words.seen_count;
+    if (newly_seen) *newly_seen = h->seen.words.newly_seen;
+    if (goal_seen) *goal_seen = h->seen.words.goal_seen;
+    return RCW_OK;
+}
+
+int rcw_seen_map(rcw_handle* h, int32_t first, int32_t count, void* out_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_seen_map(h); if (rc) return rc;
+    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
+    rc = sync_and_check(h);
+    const size_t per = (size_t)h->dev.H * (size_t)h->dev.W;
+    RCW_HIP(hipMemcpy(out_host, h->seen.map + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int rcw_seen_map_device_ptr(rcw_handle* h, void** ptr)
+{
+    if (!h || !ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = need_seen_map(h); if (rc) return rc;
+    *ptr = h->seen.map;
+    return RCW_OK;
+}
+
 int rcw_expand_columns_view(rcw_handle* h, const int32_t* height_line_pu_device, const uint8_t* colour_id_device,
                             int32_t count, void* view_device)
 {

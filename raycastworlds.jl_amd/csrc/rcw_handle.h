@@ -163,6 +163,17 @@ struct rcw_handle {
         RcwGoalWords words{};
         bool on() const { return field.get() != nullptr; }
     } goal;
+    // The seen map (rcw_set_seen_map): ONE allocation — the three Int32 (B) words and each agent's episode counter as of its last clear
+    // (uint32 [B]), then the packed seen bits (uint32 [B][(H*W + 31) / 32], internal), then the UInt8 (H*W, B) map; the pointers point
+    // into it.  Empty while the feature is off.
+    struct SeenMap {
+        RcwBuf buf;
+        RcwSeenWords words{};
+        uint32_t* last_episode = nullptr;
+        uint32_t* bits = nullptr;
+        uint8_t* map = nullptr;
+        bool on() const { return buf.get() != nullptr; }
+    } seen;
     ~rcw_handle();
 };
 
@@ -206,6 +217,7 @@ hipError_t launch_top_view_alone(rcw_handle* h, const uint8_t* mask_dev);
 hipError_t paint_camera(rcw_handle* h, const uint8_t* mask_dev, hipStream_t stream);
 hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_goal_distance(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
+hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
 hipError_t replace_buffers(rcw_handle* h, std::initializer_list<RcwBuf*> old, std::initializer_list<RcwBuf*> fresh = {});
 int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient);

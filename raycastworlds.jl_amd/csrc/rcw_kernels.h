@@ -189,3 +189,17 @@ struct RcwGoalWords {
 size_t rcw_goal_distance_lds_bytes(const RcwDev& p);
 hipError_t rcw_launch_goal_distance(const RcwDev& p, int32_t B, const uint8_t* mask_dev, bool refill, uint16_t* field, const RcwGoalWords& words,
                                     uint32_t* last_episode, hipStream_t s);
+
+// The seen map (rcw_set_seen_map, rcw_seen_map.hip): the three Int32 (B) words beside the UInt8 (H*W, B) map.
+struct RcwSeenWords {
+    int32_t* seen_count;     // non-zero entries of the agent's map
+    int32_t* newly_seen;     // entries the last call turned from 0 to non-zero; 0 behind a clear
+    int32_t* goal_seen;      // map[goal tile] != 0
+};
+// One launch behind a step (refill = false: an agent whose episode counter differs from last_episode is cleared and marked afresh, every
+// other one is marked on top of what it has) or behind reset / set_state / set_walls / enabling (refill = true: the agents of the mask —
+// NULL: all — are cleared and marked; the others are left alone).  seen_bits: the packed map, (H*W + 31) / 32 words an agent.  Reads p's
+// state arrays and ray table, writes only its own buffers.
+size_t rcw_seen_map_lds_bytes(const RcwDev& p);
+hipError_t rcw_launch_seen_map(const RcwDev& p, int32_t B, const uint8_t* mask_dev, bool refill, uint8_t* map, uint32_t* seen_bits,
+                               const RcwSeenWords& words, uint32_t* last_episode, hipStream_t s);

@@ -218,12 +218,20 @@ hipError_t launch_goal_distance(rcw_handle* h, const uint8_t* mask_dev, StackOp 
                                     h->goal.last_episode.get<uint32_t>(), h->stream);
 }
 
+// ... and behind it, on the same terms, the seen map: behind a step the counter decides who is cleared, behind a refill the mask
+hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
+{
+    if (!h->seen.on() || op == kStackKeep || op == kStackRefillSameWorld) return hipSuccess;
+    return rcw_launch_seen_map(h->dev, h->B, mask_dev, op == kStackRefill, h->seen.map, h->seen.bits, h->seen.words, h->seen.last_episode, h->stream);
+}
+
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op)
 {
     if (!h->learner.only()) {
         hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
         if (e == hipSuccess && h->learner.on()) e = launch_view(h, mask_dev, op);
-        return e == hipSuccess ? launch_goal_distance(h, mask_dev, op) : e;
+        if (e == hipSuccess) e = launch_goal_distance(h, mask_dev, op);
+        return e == hipSuccess ? launch_seen_map(h, mask_dev, op) : e;
     }
     h->step.obs_unknown();                                        // (the camera view is not painted)
     const Bracket prof(&h->prof);
@@ -236,7 +244,8 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if ((e = prof.mark(2, h->stream)) != hipSuccess) return e;
     if ((e = launch_view(h, mask_dev, op)) != hipSuccess) return e;
     if ((e = prof.done(h->stream)) != hipSuccess) return e;
-    return launch_goal_distance(h, mask_dev, op);
+    if ((e = launch_goal_distance(h, mask_dev, op)) != hipSuccess) return e;
+    return launch_seen_map(h, mask_dev, op);
 }
 
 // THE way a buffer of a live handle is given up: wait_all_streams (queued work may still use the old ones), then each of `old` takes

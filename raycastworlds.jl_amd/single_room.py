@@ -344,7 +344,8 @@ class SingleRoom:
     the reference's order (`reference_reset_draws`), injected with `rcw_set_state`.  `device` is the HIP device index.
     `max_episode_steps` (this build's addition; 0 = none, the reference's behaviour) is the episode time limit of
     `set_time_limit`.  `walls` / `wall_index` (this build's addition; None = the reference's empty room) are `set_walls`'
-    arguments, applied right after construction.  `goal_distance` (this build's addition) is `set_goal_distance(True)` after them.
+    arguments, applied right after construction.  `goal_distance` (this build's addition) is `set_goal_distance(True)` after them,
+    `seen_map` (this build's addition) `set_seen_map(True)` after that.
     """
 
     def __init__(
@@ -378,6 +379,7 @@ class SingleRoom:
         walls=None,
         wall_index=None,
         goal_distance: bool = False,
+        seen_map: bool = False,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -475,6 +477,12 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        if seen_map:
+            try:
+                self.set_seen_map(True)
+            except BaseException:
+                self._handle.close()
+                raise
         # colour fields of the reference struct SR:241-256
         self.floor_color = cfg.floor_color
         self.ceiling_color = cfg.ceiling_color
@@ -501,7 +509,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_seen_map_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -888,6 +896,75 @@ class SingleRoom:
         H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
         return DeviceArray(p.value, (self.batch, W, H), np.uint16, self, self._sync,
                            host_getter=lambda: np.ascontiguousarray(self.goal_distance_field.transpose(0, 2, 1)))
+
+    # ---- the seen map (include/rcw.h, rcw_set_seen_map) ---------------------------------
+    def set_seen_map(self, on: bool = True) -> None:
+        """Keep, on the device, the tiles each agent's view rays have crossed since its episode began — exactly what the camera saw:
+        every tile the march of each of the `num_rays` rays visits, from the player's tile through the stop tile.  `seen_map` holds 0 for
+        an unseen tile and otherwise 1 free, 2 wall, 3 goal; `seen_count` counts the seen tiles, `seen_new` those the last step saw for
+        the first time (a coverage bonus is `c * env.seen_new.torch(sync=False)`), `goal_seen` says whether the goal tile is among them.
+        Follows resets, `set_state`, `set_walls` and `auto_reset` restarts with no host synchronisation.  Switching it on (again) starts
+        every agent's map afresh from its current pose; the device arrays handed out before are invalid after every call."""
+        self.__dict__.pop("_seen_map_dev", None)
+        self._check(self._lib.rcw_set_seen_map(self._h, 1 if on else 0))
+
+    @property
+    def seen_map_enabled(self) -> bool:
+        n = C.c_int32()
+        self._check(self._lib.rcw_seen_map_enabled(self._h, C.byref(n)))
+        return bool(n.value)
+
+    def _seen_words_host(self, which: int) -> np.ndarray:
+        out = np.empty(self.batch, dtype=np.int32)
+        args = [None, None, None]
+        args[which] = _as_ptr(out)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_seen_words(self._h, *args))
+        return out
+
+    def _seen_map_arrays(self):
+        if getattr(self, "_seen_map_dev", None) is None:
+            p = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+            self._check(self._lib.rcw_seen_words_device_ptr(self._h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])))
+            self._seen_map_dev = tuple(
+                DeviceArray(p[k].value, (self.batch,), np.int32, self, self._sync, host_getter=lambda k=k: self._seen_words_host(k))
+                for k in range(3))
+        return self._seen_map_dev
+
+    @property
+    def seen_count(self) -> DeviceArray:
+        """int32 (B,) in device memory: the tiles of each agent's map seen so far in its episode.  Rewritten behind every step, reset,
+        `set_state` and `set_walls` in stream order."""
+        return self._seen_map_arrays()[0]
+
+    @property
+    def seen_new(self) -> DeviceArray:
+        """int32 (B,): the tiles the last step saw for the first time; 0 for an agent the call restarted or reset."""
+        return self._seen_map_arrays()[1]
+
+    @property
+    def goal_seen(self) -> DeviceArray:
+        """int32 (B,): 1 once the goal tile is among the seen tiles of the agent's episode, else 0."""
+        return self._seen_map_arrays()[2]
+
+    @property
+    def seen_map(self) -> np.ndarray:
+        """uint8 (B, H, W), a host copy: `seen_map[b, i-1, j-1]` is 0 while agent b has not seen tile (i, j) in its episode, else 1 free,
+        2 wall, 3 goal (4: a goal `set_state` put into a wall) — indexed like `env.world.walls`."""
+        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
+        out = np.empty((self.batch, W, H), dtype=np.uint8)                 # tile (i, j) at (i - 1) + H (j - 1)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_seen_map(self._h, 0, self.batch, _as_ptr(out)))
+        return np.ascontiguousarray(out.transpose(0, 2, 1))
+
+    @property
+    def seen_map_device(self) -> DeviceArray:
+        """The map where it lives: uint8 (B, W, H) in device memory — the tile map's own order, `[b, j-1, i-1]`."""
+        p = C.c_void_p()
+        self._check(self._lib.rcw_seen_map_device_ptr(self._h, C.byref(p)))
+        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
+        return DeviceArray(p.value, (self.batch, W, H), np.uint8, self, self._sync,
+                           host_getter=lambda: np.ascontiguousarray(self.seen_map.transpose(0, 2, 1)))
 
     # ---- wall layouts (include/rcw.h, rcw_set_walls) ----------------------------------
     def set_walls(self, walls, index=None, mask=None) -> None:
