@@ -443,6 +443,53 @@ RCW_API int rcw_seen_words(rcw_handle* h, int32_t* seen_count /* (B) */, int32_t
 RCW_API int rcw_seen_words_device_ptr(rcw_handle* h, void** seen_count, void** newly_seen, void** goal_seen);
 RCW_API int rcw_seen_map(rcw_handle* h, int32_t first, int32_t count, void* out_host /* UInt8 (H*W, count) */);
 RCW_API int rcw_seen_map_device_ptr(rcw_handle* h, void** ptr);
+/* ---- the local map (this build's addition: an agent-centred, heading-up crop of the map) ---------------------------------------------
+ * Opt-in per handle: the "egocentric map" input of a mapping-based navigation agent, computed on the device from the engine's own
+ * position, heading, direction table and tiles, at no host synchronisation.  A handle that never enables it runs exactly the kernels it
+ * ran before.  The ABI is additive: RCW_ABI_VERSION and rcw_config are what they were.
+ * Per agent one UInt8 (S, S) image, row-major: cell (row q, column c) of agent a at a*S*S + q*S + c; the batch is (B, S, S), the agent
+ * stride S*S bytes, unpadded.  size S in 1..RCW_LOCAL_MAX_SIZE, cells_per_tile r in 1..RCW_LOCAL_MAX_CELLS_PER_TILE (a cell is 1/r of a
+ * tile wide), and the source:
+ *   RCW_LOCAL_WORLD   the agent's tile map as it is NOW;
+ *   RCW_LOCAL_SEEN    its seen map; the handle must have enabled the seen map first, else RCW_ERR_UNSUPPORTED.
+ * A cell holds the seen map's alphabet, for both sources: 0 = outside the map (RCW_LOCAL_SEEN: or not seen), otherwise 1 + bits(t):
+ * 1 free, 2 wall, 3 goal, 4 a goal in a wall.
+ * The geometry is exact, in the handle's world-unit type T, every operation rounded once:
+ *   off[k] = (T)(2k + 1 - S) / (T)(2r), k = 0..S-1   the cell centres' offsets from the agent, in tiles;
+ *   (px, py) the agent's position, (d1, d2) entry player_direction_au of the direction table the handle holds — whatever
+ *   rcw_set_direction_table or its 64 twin last put there, unit or not; the lateral axis is rotate_minus_90 of it, (d2, -d1), as in the
+ *   ray table (SR:193);
+ *   cell (q, c): ahead = off[S-1-q] — row 0 is the farthest ahead —, lateral = off[S-1-c] — column 0 is on the +lateral side, the side
+ *   of ray 0 = dir + fov * lateral axis (which fills the camera view's LAST image column: SR:431 mirrors) —,
+ *       wx = (px + ahead*d1) + lateral*d2        wy = (py + ahead*d2) - lateral*d1          (in exactly this association)
+ *   fx = floor(wx), fy = floor(wy), compared in T: if 0 <= fx < H and 0 <= fy < W the cell shows tile t = (int)fx + H*(int)fy, that is
+ *   tile (i, j) = (fx+1, fy+1) in the order rcw_set_walls and the seen map use: RCW_LOCAL_WORLD 1 + its two bits, RCW_LOCAL_SEEN map[t].
+ *   Otherwise, and for any NaN, 0.  Nothing outside the agent's H*W entries is read for any position, NaN, +-Inf and far off the map
+ *   included.
+ * What each call does — stream-ordered on the handle's stream, behind everything the call already queues (the seen map's launch too):
+ *   rcw_set_local_map(h, source, size, cells_per_tile)
+ *                                 source = 0 frees it (RCW_OK also where there was none).  Otherwise allocates and computes every agent's
+ *                                 image at once; on a handle that has one, the new parameters replace the old (and the device pointer).  A
+ *                                 bad value: RCW_ERR_INVALID_ARGUMENT, the handle as it was.  An allocation failure leaves what was there.
+ *   rcw_step, rcw_step_device, rcw_reset, rcw_set_state, rcw_set_state64, rcw_set_walls, rcw_set_direction_table, rcw_set_direction_table64,
+ *   rcw_set_seen_map(h, 1)        every agent's image is computed again from the state behind the call.  The function is stateless: an agent
+ *                                 outside a mask gets the same bytes again; there is no mask and no episode logic.
+ *   rcw_set_seen_map(h, 0)        while the source is RCW_LOCAL_SEEN: RCW_ERR_UNSUPPORTED (switch the local map off first), nothing changes.
+ *   every other call              nothing.
+ * A replayed HIP graph of a step computes the images like any step.  The device pointer is stable until the next rcw_set_local_map.  The
+ * kernel (one launch, rcw_local_map_kernel) runs last and OUTSIDE rcw_profile's events.
+ *   rcw_local_map_info            the three parameters (any pointer may be NULL); zeros while it is off.
+ *   rcw_local_map_device_ptr      the image batch in DEVICE memory.
+ *   rcw_local_map_copy            the images of agents [first, first+count) to host memory, S*S bytes each (waits for the stream).
+ * The last two return RCW_ERR_UNSUPPORTED on a handle that has not enabled it. */
+#define RCW_LOCAL_WORLD 1
+#define RCW_LOCAL_SEEN 2
+#define RCW_LOCAL_MAX_SIZE 128
+#define RCW_LOCAL_MAX_CELLS_PER_TILE 16
+RCW_API int rcw_set_local_map(rcw_handle* h, int32_t source, int32_t size, int32_t cells_per_tile);
+RCW_API int rcw_local_map_info(rcw_handle* h, int32_t* source, int32_t* size, int32_t* cells_per_tile);
+RCW_API int rcw_local_map_device_ptr(rcw_handle* h, void** device_ptr);
+RCW_API int rcw_local_map_copy(rcw_handle* h, uint8_t* out_host /* (S*S, count) */, int32_t first, int32_t count);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

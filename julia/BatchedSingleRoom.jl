@@ -459,6 +459,36 @@ function seen_map_device_ptr(env::BatchedSingleRoom)
     check(ccall((:rcw_seen_map_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
 end
 
+# ---- the local map (this build's addition; include/rcw.h, rcw_set_local_map) ----------------------------------------------------
+const LOCAL_MAP_SOURCES = (off = Int32(0), world = Int32(1), seen = Int32(2))
+"""
+    set_local_map!(env, size; cells_per_tile = 1, source = :world)
+
+Keep, on the device, an agent-centred, heading-up crop of each agent's map, behind every `act!`, `reset!`, `set_state!`, `set_walls!`
+and `set_direction_table!`: `local_map(env)` is `UInt8`, C row-major `(batch, size, size)` — in Julia's order `(size, size, batch)` with
+the image's COLUMN first —, row 1 the farthest ahead, `cells_per_tile` cells to a tile; `0` outside the map (`:seen`: or not seen), else
+`1` free, `2` wall, `3` goal.  `source = :seen` crops the seen map (`set_seen_map!` first).  `size = 0` switches it off.
+"""
+function set_local_map!(env::BatchedSingleRoom, size::Integer; cells_per_tile::Integer = 1, source::Symbol = :world)
+    src = size == 0 ? LOCAL_MAP_SOURCES.off : getfield(LOCAL_MAP_SOURCES, source)
+    check(ccall((:rcw_set_local_map, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Int32), env.handle, src, size, size == 0 ? 0 : cells_per_tile))
+    return nothing
+end
+function local_map_info(env::BatchedSingleRoom)
+    s = Ref{Int32}(0); n = Ref{Int32}(0); r = Ref{Int32}(0)
+    check(ccall((:rcw_local_map_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}), env.handle, s, n, r))
+    return (source = s[], size = n[], cells_per_tile = r[])
+end
+function local_map_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_local_map_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
+function local_map(env::BatchedSingleRoom; first::Integer = 0, count::Integer = env.batch - first)
+    n = Int(local_map_info(env).size)
+    out = Array{UInt8, 3}(undef, n, n, count)
+    check(ccall((:rcw_local_map_copy, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int32, Int32), env.handle, out, first, count)); out
+end
+
 # per-agent sticky status: 0, -5 where the reference would have raised BoundsError, -2 for an invalid device action,
 # 1 (a warning) where sample_empty_position gave up after max_tries and returned an occupied tile (utils.jl:34 @warns there)
 function status(env::BatchedSingleRoom)

@@ -34,6 +34,8 @@ RCW_VIEW_DEPTH8, RCW_VIEW_RGBD8, RCW_VIEW_GRAYD8 = 4, 5, 6   # ... bit 2: a dept
 RCW_VIEW_CHW, RCW_VIEW_HWC = 0, 1                      # ... layout
 RCW_VIEW_ONLY = 1                                      # ... flag: no camera view in the step
 RCW_VIEW_MAX_FRAMES = 16                               # rcw_set_learner_view_stack: frames
+RCW_LOCAL_WORLD, RCW_LOCAL_SEEN = 1, 2                 # rcw_set_local_map: source (0 = off)
+RCW_LOCAL_MAX_SIZE, RCW_LOCAL_MAX_CELLS_PER_TILE = 128, 16
 
 
 class RcwConfig(C.Structure):
@@ -159,6 +161,10 @@ SIGNATURES = {
     "rcw_seen_words_device_ptr": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
     "rcw_seen_map": [_vp, _i32, _i32, _vp],
     "rcw_seen_map_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_set_local_map": [_vp, _i32, _i32, _i32],
+    "rcw_local_map_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
+    "rcw_local_map_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_local_map_copy": [_vp, _vp, _i32, _i32],
     "rcw_ray_table": [_vp, _vp],
     "rcw_direction_table": [_vp, _vp],
     "rcw_timer_start": [_vp],

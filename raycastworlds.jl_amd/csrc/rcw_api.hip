@@ -959,6 +959,8 @@ int rcw_set_seen_map(rcw_handle* h, int32_t enable)
     int rc = check_handle(h); if (rc) return rc;
     rcw_handle::SeenMap& sm = h->seen;
     if (!enable && !sm.on()) return RCW_OK;
+    if (!enable && h->local.source == RCW_LOCAL_SEEN)
+        return fail(RCW_ERR_UNSUPPORTED, "the handle's local map reads the seen map: switch the local map off first (rcw_set_local_map)");
     rcw_handle::SeenMap fresh;
     if (enable) {
         // words and counter | packed bits | map: every part starts on a multiple of four bytes
@@ -975,6 +977,7 @@ int rcw_set_seen_map(rcw_handle* h, int32_t enable)
     RCW_HIP(replace_buffers(h, {&sm.buf}, {&fresh.buf}));
     sm.words = fresh.words; sm.last_episode = fresh.last_episode; sm.bits = fresh.bits; sm.map = fresh.map;
     if (sm.on()) RCW_HIP(launch_seen_map(h, nullptr, kStackRefill));
+    if (sm.on()) RCW_HIP(launch_local_map(h, kStackRefill));
     return RCW_OK;
 }
 
@@ -1031,6 +1034,68 @@ int rcw_seen_map_device_ptr(rcw_handle* h, void** ptr)
     int rc = need_seen_map(h); if (rc) return rc;
     *ptr = h->seen.map;
     return RCW_OK;
+}
+
+// The local map (include/rcw.h).  Enabling allocates and computes every agent's image at once, stream-ordered behind what is queued; new
+// parameters replace the old; an allocation failure leaves what was there.
+int rcw_set_local_map(rcw_handle* h, int32_t source, int32_t size, int32_t cells_per_tile)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::LocalMap& lm = h->local;
+    std::vector<unsigned char> table;
+    rc = plan_local_map(source, size, cells_per_tile, h->real64, &table); if (rc) return rc;
+    if (source == RCW_LOCAL_SEEN && !h->seen.on())
+        return fail(RCW_ERR_UNSUPPORTED, "RCW_LOCAL_SEEN needs the handle's seen map (rcw_set_seen_map)");
+    if (source == 0 && !lm.on()) return RCW_OK;
+    rcw_handle::LocalMap fresh;
+    if (source != 0) {
+        // offset table | images: the images start on a multiple of 16 bytes
+        const size_t tbytes = (table.size() + 15) & ~(size_t)15, bytes = tbytes + (size_t)h->B * (size_t)size * (size_t)size;
+        hipError_t e = fresh.buf.hipMalloc(bytes);
+        if (e == hipSuccess) e = hipMemcpy(fresh.buf.get(), table.data(), table.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(hip_code(e), "local map of %zu bytes: %s", bytes, hip_failure(e));
+        fresh.source = source; fresh.size = size; fresh.cells_per_tile = cells_per_tile;
+        fresh.off = fresh.buf.get();
+        fresh.img = fresh.buf.get<uint8_t>() + tbytes;
+    }
+    RCW_HIP(replace_buffers(h, {&lm.buf}, {&fresh.buf}));
+    lm.source = fresh.source; lm.size = fresh.size; lm.cells_per_tile = fresh.cells_per_tile; lm.off = fresh.off; lm.img = fresh.img;
+    RCW_HIP(launch_local_map(h, kStackRefill));
+    return RCW_OK;
+}
+
+int rcw_local_map_info(rcw_handle* h, int32_t* source, int32_t* size, int32_t* cells_per_tile)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (source) *source = h->local.source;
+    if (size) *size = h->local.size;
+    if (cells_per_tile) *cells_per_tile = h->local.cells_per_tile;
+    return RCW_OK;
+}
+
+extern "C++" {
+namespace {
+int need_local_map(rcw_handle* h) { return h->local.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no local map (rcw_set_local_map)"); }
+}  // namespace
+}  // extern "C++"
+
+int rcw_local_map_device_ptr(rcw_handle* h, void** device_ptr)
+{
+    if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = need_local_map(h); if (rc) return rc;
+    *device_ptr = h->local.img;
+    return RCW_OK;
+}
+
+int rcw_local_map_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32_t count)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_local_map(h); if (rc) return rc;
+    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
+    rc = sync_and_check(h);
+    const size_t per = (size_t)h->local.size * (size_t)h->local.size;
+    RCW_HIP(hipMemcpy(out_host, h->local.img + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
+    return rc;
 }
 
 int rcw_expand_columns_view(rcw_handle* h, const int32_t* height_line_pu_device, const uint8_t* colour_id_device,

@@ -174,6 +174,16 @@ struct rcw_handle {
         uint8_t* map = nullptr;
         bool on() const { return buf.get() != nullptr; }
     } seen;
+    // The local map (rcw_set_local_map): ONE allocation — the offset table (S entries of the world-unit type, padded to 16 bytes), then the
+    // UInt8 (S, S, B) images; the pointers point into it.  source = 0 and empty while the feature is off.  With RCW_LOCAL_SEEN the launch
+    // reads seen.map as it is THEN: rcw_set_seen_map may have replaced it.
+    struct LocalMap {
+        RcwBuf buf;
+        int32_t source = 0, size = 0, cells_per_tile = 0;
+        const void* off = nullptr;
+        uint8_t* img = nullptr;
+        bool on() const { return buf.get() != nullptr; }
+    } local;
     ~rcw_handle();
 };
 
@@ -211,6 +221,7 @@ int validate_walls(int H, int W, int B, const uint8_t* walls, int layouts, const
 int validate_config(const rcw_config* c, int32_t batch);
 int plan_learner_view(const rcw_config& cfg, const RcwDev& dev, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags,
                       int32_t frames, ViewPlan* plan);
+int plan_local_map(int32_t source, int32_t size, int32_t cells_per_tile, bool real64, std::vector<unsigned char>* table);
 
 // ---- rcw_step.hip: what a step, a reset or a re-render launches, and the resources those launches need ---------------------------------
 hipError_t launch_top_view_alone(rcw_handle* h, const uint8_t* mask_dev);
@@ -218,6 +229,7 @@ hipError_t paint_camera(rcw_handle* h, const uint8_t* mask_dev, hipStream_t stre
 hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_goal_distance(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
+hipError_t launch_local_map(rcw_handle* h, StackOp op);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
 hipError_t replace_buffers(rcw_handle* h, std::initializer_list<RcwBuf*> old, std::initializer_list<RcwBuf*> fresh = {});
 int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient);

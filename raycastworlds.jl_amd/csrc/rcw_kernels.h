@@ -203,3 +203,9 @@ struct RcwSeenWords {
 size_t rcw_seen_map_lds_bytes(const RcwDev& p);
 hipError_t rcw_launch_seen_map(const RcwDev& p, int32_t B, const uint8_t* mask_dev, bool refill, uint8_t* map, uint32_t* seen_bits,
                                const RcwSeenWords& words, uint32_t* last_episode, hipStream_t s);
+
+// The local map (rcw_set_local_map, rcw_local_map.hip): per agent an UInt8 (size, size) crop of its tile map — or, seen_map != NULL, of its
+// seen map ([B][H*W]) — around its position, its heading up.  off: the offset table, `size` entries of the world-unit type in DEVICE memory
+// (plan_local_map); out: [B][size*size], 4-byte aligned.  One launch, every agent; reads p's state arrays and direction table, writes only out.
+size_t rcw_local_map_lds_bytes(const RcwDev& p, int32_t size, bool seen);
+hipError_t rcw_launch_local_map(const RcwDev& p, int32_t B, const uint8_t* seen_map, const void* off, int32_t size, uint8_t* out, hipStream_t s);

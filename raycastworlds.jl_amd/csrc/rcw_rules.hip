@@ -406,6 +406,26 @@ int plan_learner_view(const rcw_config& cfg, const RcwDev& dev, int32_t format, 
     return RCW_OK;
 }
 
+// What rcw_set_local_map's arguments ask for, or the refusal; source != 0: the offset table off[k] = (T)(2k + 1 - S) / (T)(2r), k = 0..S-1, in
+// the handle's world-unit type T — one correctly rounded division of two exactly representable integers (|2k + 1 - S| < 128, 2r <= 32) —
+// as the bytes to upload.
+int plan_local_map(int32_t source, int32_t size, int32_t cells_per_tile, bool real64, std::vector<unsigned char>* table)
+{
+    if (source != 0 && source != RCW_LOCAL_WORLD && source != RCW_LOCAL_SEEN)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "source must be 0 (off), RCW_LOCAL_WORLD or RCW_LOCAL_SEEN (got %d)", source);
+    if (source == 0) return RCW_OK;
+    if (size < 1 || size > RCW_LOCAL_MAX_SIZE)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "local map size must be in 1..%d (got %d)", RCW_LOCAL_MAX_SIZE, size);
+    if (cells_per_tile < 1 || cells_per_tile > RCW_LOCAL_MAX_CELLS_PER_TILE)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "cells_per_tile must be in 1..%d (got %d)", RCW_LOCAL_MAX_CELLS_PER_TILE, cells_per_tile);
+    try { table->resize((size_t)size * (real64 ? sizeof(double) : sizeof(float))); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    for (int k = 0; k < size; ++k) {
+        if (real64) { const double v = (double)(2 * k + 1 - size) / (double)(2 * cells_per_tile); std::memcpy(table->data() + (size_t)k * sizeof v, &v, sizeof v); }
+        else { const float v = (float)(2 * k + 1 - size) / (float)(2 * cells_per_tile); std::memcpy(table->data() + (size_t)k * sizeof v, &v, sizeof v); }
+    }
+    return RCW_OK;
+}
+
 #ifdef RCW_DEV_SWITCHES
 #include "dev/api_plan_export.inc"   // the rules and the step's facts without a device (tests/test_top_view_plan.py, tests/test_step_state.py)
 #endif

@@ -225,13 +225,23 @@ hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
     return rcw_launch_seen_map(h->dev, h->B, mask_dev, op == kStackRefill, h->seen.map, h->seen.bits, h->seen.words, h->seen.last_episode, h->stream);
 }
 
+// ... and last, behind the seen map it may read, the local map: a pure function of the state, so every agent's image at every render but
+// the one that re-renders the very same frames
+hipError_t launch_local_map(rcw_handle* h, StackOp op)
+{
+    const rcw_handle::LocalMap& lm = h->local;
+    if (!lm.on() || op == kStackKeep) return hipSuccess;
+    return rcw_launch_local_map(h->dev, h->B, lm.source == RCW_LOCAL_SEEN ? h->seen.map : nullptr, lm.off, lm.size, lm.img, h->stream);
+}
+
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op)
 {
     if (!h->learner.only()) {
         hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
         if (e == hipSuccess && h->learner.on()) e = launch_view(h, mask_dev, op);
         if (e == hipSuccess) e = launch_goal_distance(h, mask_dev, op);
-        return e == hipSuccess ? launch_seen_map(h, mask_dev, op) : e;
+        if (e == hipSuccess) e = launch_seen_map(h, mask_dev, op);
+        return e == hipSuccess ? launch_local_map(h, op) : e;
     }
     h->step.obs_unknown();                                        // (the camera view is not painted)
     const Bracket prof(&h->prof);
@@ -245,7 +255,8 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if ((e = launch_view(h, mask_dev, op)) != hipSuccess) return e;
     if ((e = prof.done(h->stream)) != hipSuccess) return e;
     if ((e = launch_goal_distance(h, mask_dev, op)) != hipSuccess) return e;
-    return launch_seen_map(h, mask_dev, op);
+    if ((e = launch_seen_map(h, mask_dev, op)) != hipSuccess) return e;
+    return launch_local_map(h, op);
 }
 
 // THE way a buffer of a live handle is given up: wait_all_streams (queued work may still use the old ones), then each of `old` takes

@@ -345,7 +345,8 @@ class SingleRoom:
     `max_episode_steps` (this build's addition; 0 = none, the reference's behaviour) is the episode time limit of
     `set_time_limit`.  `walls` / `wall_index` (this build's addition; None = the reference's empty room) are `set_walls`'
     arguments, applied right after construction.  `goal_distance` (this build's addition) is `set_goal_distance(True)` after them,
-    `seen_map` (this build's addition) `set_seen_map(True)` after that.
+    `seen_map` (this build's addition) `set_seen_map(True)` after that, `local_map` (this build's addition; an int — the size — or a dict
+    of `set_local_map`'s keywords) `set_local_map` last.
     """
 
     def __init__(
@@ -380,6 +381,7 @@ class SingleRoom:
         wall_index=None,
         goal_distance: bool = False,
         seen_map: bool = False,
+        local_map=None,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -483,6 +485,12 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        if local_map is not None:
+            try:
+                self.set_local_map(**local_map) if isinstance(local_map, dict) else self.set_local_map(local_map)
+            except BaseException:
+                self._handle.close()
+                raise
         # colour fields of the reference struct SR:241-256
         self.floor_color = cfg.floor_color
         self.ceiling_color = cfg.ceiling_color
@@ -509,7 +517,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_seen_map_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_seen_map_dev", "_local_map_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -906,6 +914,7 @@ class SingleRoom:
         Follows resets, `set_state`, `set_walls` and `auto_reset` restarts with no host synchronisation.  Switching it on (again) starts
         every agent's map afresh from its current pose; the device arrays handed out before are invalid after every call."""
         self.__dict__.pop("_seen_map_dev", None)
+        self.__dict__.pop("_local_map_dev", None)
         self._check(self._lib.rcw_set_seen_map(self._h, 1 if on else 0))
 
     @property
@@ -965,6 +974,52 @@ class SingleRoom:
         H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
         return DeviceArray(p.value, (self.batch, W, H), np.uint8, self, self._sync,
                            host_getter=lambda: np.ascontiguousarray(self.seen_map.transpose(0, 2, 1)))
+
+    # ---- the local map (include/rcw.h, rcw_set_local_map) -------------------------------
+    _LOCAL_SOURCES = {"world": _capi.RCW_LOCAL_WORLD, "seen": _capi.RCW_LOCAL_SEEN}
+
+    def set_local_map(self, size, cells_per_tile: int = 1, source: str = "world") -> None:
+        """Keep, on the device, an agent-centred, heading-up crop of each agent's map: `local_map` is uint8 (B, size, size), the agent
+        at the centre, row 0 the farthest ahead, column 0 on the side of ray 0 (rotate_minus_90 of the heading), `cells_per_tile` cells to a tile.
+        `source="world"` shows the tile map as it is now, `source="seen"` the agent's seen map (`set_seen_map()` first): 0 outside the
+        map (or not seen), 1 free, 2 wall, 3 goal.  Computed from the engine's own position, heading and direction table behind every
+        step, reset, `set_state`, `set_walls` and `set_direction_table`, with no host synchronisation.  `size=0` or `None` switches it
+        off; the device array handed out before is invalid after every call."""
+        self.__dict__.pop("_local_map_dev", None)
+        if not size:
+            self._check(self._lib.rcw_set_local_map(self._h, 0, 0, 0))
+            return
+        if source not in self._LOCAL_SOURCES:
+            raise ValueError(f"source must be one of {sorted(self._LOCAL_SOURCES)} (got {source!r})")
+        self._check(self._lib.rcw_set_local_map(self._h, self._LOCAL_SOURCES[source], int(size), int(cells_per_tile)))
+
+    @property
+    def local_map_info(self) -> dict:
+        """The local map's settings (rcw_local_map_info): `source` (None while it is off), `size`, `cells_per_tile`."""
+        v = [C.c_int32() for _ in range(3)]
+        self._check(self._lib.rcw_local_map_info(self._h, *[C.byref(x) for x in v]))
+        src, size, cpt = (x.value for x in v)
+        return {"source": {value: name for name, value in self._LOCAL_SOURCES.items()}.get(src), "size": size, "cells_per_tile": cpt}
+
+    def local_map_host(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Agents [first, first + count) of the local map, uint8 (count, size, size), copied to the host (waits for the engine's stream)."""
+        n = self.batch - first if count is None else count
+        S = self.local_map_info["size"]
+        out = np.empty((max(n, 0), S, S), dtype=np.uint8)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_local_map_copy(self._h, _as_ptr(out), first, n))
+        return out
+
+    @property
+    def local_map(self) -> DeviceArray:
+        """The local map batch, aliased device memory: uint8 (B, size, size), rewritten in place behind every step in stream order
+        (`.torch(sync=False)` for a policy on the GPU; `np.asarray(env.local_map)` copies it to the host)."""
+        if getattr(self, "_local_map_dev", None) is None:
+            p = C.c_void_p()
+            self._check(self._lib.rcw_local_map_device_ptr(self._h, C.byref(p)))
+            S = self.local_map_info["size"]
+            self._local_map_dev = DeviceArray(p.value, (self.batch, S, S), np.uint8, self, self._sync, host_getter=lambda: self.local_map_host())
+        return self._local_map_dev
 
     # ---- wall layouts (include/rcw.h, rcw_set_walls) ----------------------------------
     def set_walls(self, walls, index=None, mask=None) -> None:
