@@ -490,6 +490,54 @@ RCW_API int rcw_set_local_map(rcw_handle* h, int32_t source, int32_t size, int32
 RCW_API int rcw_local_map_info(rcw_handle* h, int32_t* source, int32_t* size, int32_t* cells_per_tile);
 RCW_API int rcw_local_map_device_ptr(rcw_handle* h, void** device_ptr);
 RCW_API int rcw_local_map_copy(rcw_handle* h, uint8_t* out_host /* (S*S, count) */, int32_t first, int32_t count);
+/* ---- the wall bank (this build's addition: a wall layout drawn on the device at every start of an episode) ---------------------------
+ * Opt-in per handle.  rcw_set_walls gives an agent one layout, which then stays through every later reset and device-side restart: under
+ * cfg.auto_reset the agent replays one maze for the whole run.  A handle with a bank holds L layouts on the device, each checked as
+ * rcw_set_walls checks one (ring present, at least two free interior tiles), and UInt32 weights w[0..L-1] (NULL: all 1) whose sum lies in
+ * 1 .. 2^32 - 1; cum[k] = w[0] + ... + w[k].  An agent BEGINS AN EPISODE whenever its episode counter moves: rcw_reset, a done or
+ * truncated restart under cfg.auto_reset, and the call that installs the bank.  With g = agent_id_offset + a the agent's global id and e
+ * its counter before the increment:
+ *   key = the episode key of (seed, g, e)             csrc/rcw_rng.h: the key the reset of that episode already uses
+ *   u   = draw number 2^63 of that key                (the reset's own draw indices count from 0 and stay below 4 + 3*1024*H*W)
+ *   k   = the smallest index with cum[k] > floor(u * cum[L-1] / 2^64)
+ *   WALL layer := layout k, GOAL layer cleared, wall_layout[a] := k; then reset!(world) exactly as under "wall layouts" above against the
+ *   new walls — the same key, draw indices from 0 —: goal (redrawn while on a wall), player tile, heading, reward 0, done false, the
+ *   time limit's two words zeroed; counter = e + 1 (once).
+ * The result is a pure function of (seed, global id, episode, bank): not of the sharding, the step form, or the walls the agent had.  A
+ * layout of weight 0 is never drawn.  Every draw index a handle without a bank uses is untouched: such a handle draws what it drew before
+ * and launches exactly the kernels it launched before.  The ABI is additive: RCW_ABI_VERSION and rcw_config are what they were.
+ * What each call does — stream-ordered on the handle's stream:
+ *   rcw_set_wall_bank             walls_host UInt8 (H*W, L) in rcw_set_walls' order (non-zero = wall), L = layouts, weights_host UInt32 (L)
+ *                                 or NULL.  Validated on the host before anything is queued: a refusal (RCW_ERR_INVALID_ARGUMENT: a bad
+ *                                 layout — the message names the layout and the tile —, layouts < 0, weights whose sum is 0 or above
+ *                                 2^32 - 1) leaves the handle untouched, an allocation failure leaves what was there.  Installs the bank
+ *                                 (replacing one that was there) and restarts EVERY agent under the rule with the handle's current seed, as
+ *                                 rcw_reset(h, NULL, seed) would: the counters go up by one, everything is rendered, the features refilled.
+ *                                 layouts == 0 or walls_host == NULL switches the bank off (RCW_OK also where there was none): the agents
+ *                                 keep the walls they have, and the handle is an ordinary walled handle again.
+ *   rcw_set_wall_bank_weights     new weights for the installed bank (NULL: all 1), stream-ordered WITHOUT waiting for the stream: they
+ *                                 hold from each agent's next episode start, no agent is touched — the call a prioritised-replay caller
+ *                                 makes every few updates.  A sum of 0 or above 2^32 - 1: RCW_ERR_INVALID_ARGUMENT, the old weights stay.
+ *   rcw_reset                     the agents of the mask begin an episode: a layout each, by the rule, with the seed the call gives.
+ *   rcw_step, rcw_step_device     an agent the step restarted (done or truncated under cfg.auto_reset) takes a layout by the rule: the
+ *                                 reset the step made against the old walls is discarded without a trace, the agent's rays are cast and
+ *                                 its views rendered again, and goal distance, seen map, local map, learner view and frame stack follow
+ *                                 the new maze.  No host synchronisation; a replayed HIP graph of a step draws layouts like any step.
+ *   rcw_set_state, rcw_set_state64   do not move the counter: the layout stays.
+ *   rcw_set_walls                 RCW_ERR_UNSUPPORTED while the handle has a bank, nothing changes: switch the bank off first.
+ *   rcw_set_direction_table*, rcw_set_time_limit, rcw_set_step_form, the feature switches, the getters   nothing.
+ * The bank's kernel (one launch, rcw_wall_bank_kernel) and the re-render of the agents it restarted (the masked cast, then their camera
+ * view by rcw_wall_bank_paint_kernel — or, with a top view, the masked fill) run behind the step's own launches and
+ * OUTSIDE rcw_profile's events (with RCW_VIEW_ONLY: in front of the view kernel, inside cast_ms).  Of the bank the host keeps its sizes only.
+ *   rcw_wall_bank_info            L and the weights' sum (either pointer may be NULL); zeros while the bank is off.
+ *   rcw_wall_layout               host copy of each agent's current layout index, Int32 (B); waits for the stream as rcw_done does.
+ *   rcw_wall_layout_device_ptr    the same array in DEVICE memory, stable until the next rcw_set_wall_bank.
+ * The last two, and rcw_set_wall_bank_weights, return RCW_ERR_UNSUPPORTED on a handle without a bank. */
+RCW_API int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host /* (H*W, L) */, int32_t layouts, const uint32_t* weights_host /* (L) or NULL */);
+RCW_API int rcw_set_wall_bank_weights(rcw_handle* h, const uint32_t* weights_host /* (L) or NULL */);
+RCW_API int rcw_wall_bank_info(rcw_handle* h, int32_t* layouts, uint64_t* total_weight);
+RCW_API int rcw_wall_layout(rcw_handle* h, int32_t* out_host /* (B) */);
+RCW_API int rcw_wall_layout_device_ptr(rcw_handle* h, void** device_ptr);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

@@ -489,6 +489,62 @@ function local_map(env::BatchedSingleRoom; first::Integer = 0, count::Integer = 
     check(ccall((:rcw_local_map_copy, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int32, Int32), env.handle, out, first, count)); out
 end
 
+# ---- the wall bank (this build's addition; include/rcw.h, rcw_set_wall_bank) ----------------------------------------------------
+"""
+    set_wall_bank!(env, walls; weights = nothing)
+
+A bank of wall layouts on the device, one drawn for an agent at every start of an episode: `reset!`, a done or truncated restart under
+`auto_reset`, and this call, which restarts every agent with the environment's seed (episode counters + 1).  `walls` is `Bool` / `UInt8`
+`(H, W, M)` (or `(H, W)`: a bank of one), each layout checked as `set_walls!` checks one; `weights` is `M` integers in `0 : 2^32 - 1`
+whose sum lies in `1 : 2^32 - 1` (`nothing`: uniform).  Layout `k` (0-based in `wall_layout(env)`) is drawn with probability
+`weights[k + 1] / sum`, a pure function of (seed, global agent id, episode, bank).  `set_walls!` is refused while the bank is on;
+`set_wall_bank!(env, nothing)` switches it off, the agents keep the walls they have.  An environment built with `rng` draws its resets
+on the host and takes no bank.
+"""
+function set_wall_bank!(env::BatchedSingleRoom, walls::Union{Nothing, AbstractArray}; weights::Union{Nothing, AbstractVector{<:Integer}} = nothing)
+    if walls === nothing
+        check(ccall((:rcw_set_wall_bank, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int32, Ptr{UInt32}), env.handle, C_NULL, 0, C_NULL))
+        return nothing
+    end
+    env.rng === nothing || throw(ArgumentError("an environment built with rng draws its resets on the host: it takes no wall bank"))
+    H, W = Int(env.config.height_tile_map_tu), Int(env.config.width_tile_map_tu)
+    (ndims(walls) in (2, 3) && size(walls, 1) == H && size(walls, 2) == W) || throw(DimensionMismatch("walls must be ($H, $W) or ($H, $W, M)"))
+    flat = Vector{UInt8}(vec(walls .!= 0))                                       # column-major: m H W + (i - 1) + H (j - 1)
+    layouts = ndims(walls) == 2 ? 1 : size(walls, 3)
+    w = weights === nothing ? nothing : Vector{UInt32}(weights)
+    w === nothing || length(w) == layouts || throw(DimensionMismatch("expected $(layouts) weights"))
+    GC.@preserve flat w check(ccall((:rcw_set_wall_bank, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int32, Ptr{UInt32}),
+                                    env.handle, pointer(flat), layouts, w === nothing ? Ptr{UInt32}(C_NULL) : pointer(w)))
+    env.stale = true
+    return nothing
+end
+"""
+    set_wall_bank_weights!(env, weights)
+
+New weights for the installed bank (`nothing`: uniform), in stream order and without waiting for the device: they hold from each agent's
+next episode start, no agent is touched.
+"""
+function set_wall_bank_weights!(env::BatchedSingleRoom, weights::Union{Nothing, AbstractVector{<:Integer}})
+    w = weights === nothing ? nothing : Vector{UInt32}(weights)
+    w === nothing || length(w) == wall_bank_info(env).layouts || throw(DimensionMismatch("expected $(wall_bank_info(env).layouts) weights"))
+    GC.@preserve w check(ccall((:rcw_set_wall_bank_weights, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt32}), env.handle,
+                               w === nothing ? Ptr{UInt32}(C_NULL) : pointer(w)))
+    return nothing
+end
+function wall_bank_info(env::BatchedSingleRoom)
+    n = Ref{Int32}(0); t = Ref{UInt64}(0)
+    check(ccall((:rcw_wall_bank_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{UInt64}), env.handle, n, t))
+    return (layouts = n[], total_weight = t[])
+end
+function wall_layout(env::BatchedSingleRoom)
+    out = Vector{Int32}(undef, env.batch)
+    check(ccall((:rcw_wall_layout, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}), env.handle, out)); out
+end
+function wall_layout_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_wall_layout_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
+
 # per-agent sticky status: 0, -5 where the reference would have raised BoundsError, -2 for an invalid device action,
 # 1 (a warning) where sample_empty_position gave up after max_tries and returned an occupied tile (utils.jl:34 @warns there)
 function status(env::BatchedSingleRoom)

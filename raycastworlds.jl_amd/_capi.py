@@ -165,6 +165,11 @@ SIGNATURES = {
     "rcw_local_map_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
     "rcw_local_map_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_local_map_copy": [_vp, _vp, _i32, _i32],
+    "rcw_set_wall_bank": [_vp, _vp, _i32, _vp],
+    "rcw_set_wall_bank_weights": [_vp, _vp],
+    "rcw_wall_bank_info": [_vp, C.POINTER(_i32), C.POINTER(_u64)],
+    "rcw_wall_layout": [_vp, _vp],
+    "rcw_wall_layout_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_ray_table": [_vp, _vp],
     "rcw_direction_table": [_vp, _vp],
     "rcw_timer_start": [_vp],

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -419,6 +420,7 @@ int rcw_reset(rcw_handle* h, const uint8_t* mask_host, uint64_t seed)
     h->step.reset(mask_dev != nullptr, seed != h->dev.seed, h->dev.auto_reset != 0);
     h->dev.seed = seed;
     RCW_HIP(rcw_launch_reset(h->dev, mask_dev, h->stream));            // SR:110-132
+    RCW_HIP(launch_wall_bank(h, false));                               // (a handle with a wall bank: the agents of the mask take a layout each)
     RCW_HIP(launch_step(h, nullptr, mask_dev, kStackRefill));    // SR:134, SR:329
     return RCW_OK;
 }
@@ -428,6 +430,7 @@ int rcw_reset(rcw_handle* h, const uint8_t* mask_host, uint64_t seed)
 int rcw_set_walls(rcw_handle* h, const uint8_t* walls_host, int32_t layouts, const int32_t* layout_index_host, const uint8_t* mask_host)
 {
     int rc = check_handle(h); if (rc) return rc;
+    if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     char why[256];
     if (validate_walls(H, W, h->B, walls_host, layouts, layout_index_host, mask_host, why, sizeof why) != RCW_OK)
@@ -593,6 +596,7 @@ int rcw_clear_error(rcw_handle* h)
     int rc = check_handle(h); if (rc) return rc;
     RCW_HIP(hipMemsetAsync(h->d_err.get(), 0, sizeof(int32_t), h->stream));
     RCW_HIP(hipMemsetAsync(h->d_status.get(), 0, (size_t)h->B * sizeof(int32_t), h->stream));
+    if (h->bank.on()) RCW_HIP(hipMemsetAsync(h->bank.dev.status_seen, 0, (size_t)h->B * sizeof(int32_t), h->stream));   // (the bank's record of them)
     RCW_HIP(hipStreamSynchronize(h->stream));
     return RCW_OK;
 }
@@ -1096,6 +1100,114 @@ int rcw_local_map_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32_t 
     const size_t per = (size_t)h->local.size * (size_t)h->local.size;
     RCW_HIP(hipMemcpy(out_host, h->local.img + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
     return rc;
+}
+
+// The wall bank (include/rcw.h).  Validated and allocated before anything of the handle changes; then the layouts are staged, packed on the
+// device, and every agent is restarted under the bank's rule: the body of rcw_reset(h, NULL, <the handle's seed>) with the bank's kernel
+// forced for every agent.
+int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts, const uint32_t* weights_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::WallBank& wb = h->bank;
+    if (layouts == 0 || !walls_host) {                                 // off: the agents keep the walls they have
+        if (!wb.on()) return RCW_OK;
+        RCW_HIP(replace_buffers(h, {&wb.words, &wb.cum, &wb.agents}));
+        wb.h_cum.reset(); wb.ev_cum.reset();
+        wb.dev = RcwWallBank{}; wb.total_weight = 0;
+        return RCW_OK;
+    }
+    const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
+    char why[256];
+    if (layouts < 0) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_set_wall_bank: layouts must be >= 0 (got %d)", layouts);
+    if (validate_walls(H, W, layouts, walls_host, layouts, nullptr, nullptr, why, sizeof why) != RCW_OK)   // (a layout each of `layouts` agents: every one is checked)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_set_wall_bank: %s", why);
+    const size_t B = (size_t)h->B, L = (size_t)layouts, bytes = L * (size_t)H * (size_t)W, nwords = (size_t)h->dev.nwords;
+    std::vector<uint32_t> cum;
+    try { cum.resize(L); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the cumulative weights failed"); }
+    uint64_t total = 0;
+    rc = plan_wall_bank_weights(weights_host, layouts, cum.data(), &total); if (rc) return rc;
+    rcw_handle::WallBank fresh;
+    {
+        hipError_t e = fresh.words.hipMalloc(L * nwords * sizeof(uint32_t));
+        if (e == hipSuccess) e = fresh.cum.hipMalloc(L * sizeof(uint32_t));
+        if (e == hipSuccess) e = fresh.agents.hipMalloc(3 * B * sizeof(uint32_t) + B);
+        if (e == hipSuccess) e = fresh.h_cum.hipHostMalloc(L * sizeof(uint32_t));
+        if (e == hipSuccess) e = fresh.ev_cum.hipEventCreate(hipEventDisableTiming);
+        if (e != hipSuccess) return fail(hip_code(e), "wall bank of %d layouts: %s", layouts, hip_failure(e));
+    }
+    if (bytes > h->in_walls_cap) {
+        RcwBuf larger; RCW_HIP(larger.hipMalloc(bytes));
+        RCW_HIP(replace_buffers(h, {&h->d_in_walls}, {&larger}));
+        h->in_walls_cap = bytes;
+    }
+    RCW_HIP(hipMemcpyAsync(h->d_in_walls.get(), walls_host, bytes, hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipStreamSynchronize(h->stream));                          // (pageable host memory of the caller's)
+    RCW_HIP(replace_buffers(h, {&wb.words, &wb.cum, &wb.agents}, {&fresh.words, &fresh.cum, &fresh.agents}));
+    wb.h_cum = std::move(fresh.h_cum); wb.ev_cum = std::move(fresh.ev_cum);
+    uint32_t* const q = wb.agents.get<uint32_t>();
+    wb.dev = RcwWallBank{layouts, wb.words.get<uint32_t>(), wb.cum.get<uint32_t>(), q, reinterpret_cast<int32_t*>(q + B),
+                         reinterpret_cast<int32_t*>(q + 2 * B), reinterpret_cast<uint8_t*>(q + 3 * B)};
+    wb.total_weight = total;
+    std::memcpy(wb.h_cum.get(), cum.data(), L * sizeof(uint32_t));
+    RCW_HIP(hipMemcpyAsync(wb.cum.get(), wb.h_cum.get(), L * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipEventRecord(wb.ev_cum.get(), h->stream));
+    RCW_HIP(rcw_launch_wall_bank_pack(h->dev, h->d_in_walls.get<uint8_t>(), wb.words.get<uint32_t>(), layouts, h->stream));
+    RCW_HIP(hipMemsetAsync(wb.agents.get(), 0, 3 * B * sizeof(uint32_t) + B, h->stream));
+    RCW_HIP(hipMemcpyAsync(wb.dev.status_seen, h->d_status.get(), B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    h->step.reset(false, false, h->dev.auto_reset != 0);
+    RCW_HIP(rcw_launch_reset(h->dev, nullptr, h->stream));             // the counters move by one ...
+    RCW_HIP(launch_wall_bank(h, true));                                // ... and every agent starts that episode on a layout of the bank
+    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));
+    return RCW_OK;
+}
+
+extern "C++" {
+namespace {
+int need_wall_bank(rcw_handle* h) { return h->bank.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no wall bank (rcw_set_wall_bank)"); }
+}  // namespace
+}  // extern "C++"
+
+// New weights for the installed bank, stream-ordered behind what is queued and without waiting for it: the cumulative weights travel through the
+// bank's pinned buffer, whose previous copy the event guards.
+int rcw_set_wall_bank_weights(rcw_handle* h, const uint32_t* weights_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_wall_bank(h); if (rc) return rc;
+    rcw_handle::WallBank& wb = h->bank;
+    const size_t L = (size_t)wb.dev.layouts;
+    std::vector<uint32_t> cum;
+    try { cum.resize(L); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the cumulative weights failed"); }
+    uint64_t total = 0;
+    rc = plan_wall_bank_weights(weights_host, wb.dev.layouts, cum.data(), &total); if (rc) return rc;
+    RCW_HIP(hipEventSynchronize(wb.ev_cum.get()));
+    std::memcpy(wb.h_cum.get(), cum.data(), L * sizeof(uint32_t));
+    RCW_HIP(hipMemcpyAsync(wb.cum.get(), wb.h_cum.get(), L * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    RCW_HIP(hipEventRecord(wb.ev_cum.get(), h->stream));
+    wb.total_weight = total;
+    return RCW_OK;
+}
+
+int rcw_wall_bank_info(rcw_handle* h, int32_t* layouts, uint64_t* total_weight)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (layouts) *layouts = h->bank.on() ? h->bank.dev.layouts : 0;
+    if (total_weight) *total_weight = h->bank.total_weight;
+    return RCW_OK;
+}
+
+int rcw_wall_layout(rcw_handle* h, int32_t* out_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_wall_bank(h); if (rc) return rc;
+    return copy_out<int32_t>(h, out_host, h->bank.dev.layout, (size_t)h->B);
+}
+
+int rcw_wall_layout_device_ptr(rcw_handle* h, void** device_ptr)
+{
+    if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = need_wall_bank(h); if (rc) return rc;
+    *device_ptr = h->bank.dev.layout;
+    return RCW_OK;
 }
 
 int rcw_expand_columns_view(rcw_handle* h, const int32_t* height_line_pu_device, const uint8_t* colour_id_device,

@@ -184,6 +184,18 @@ struct rcw_handle {
         uint8_t* img = nullptr;
         bool on() const { return buf.get() != nullptr; }
     } local;
+    // The wall bank (rcw_set_wall_bank): the packed layouts, the cumulative weights, and ONE allocation of the per-agent arrays — recorded
+    // counter, recorded status, layout index (the three 4-byte arrays), then the mask; `dev` points into them.  The weights reach `cum`
+    // through a pinned staging buffer and an event (rcw_set_wall_bank_weights does not wait for the stream).  Of the bank the host keeps
+    // only its sizes: layouts and the weights' sum.  Empty while the bank is off.
+    struct WallBank {
+        RcwBuf words, cum, agents;
+        RcwPinned h_cum;
+        RcwEvent ev_cum;
+        RcwWallBank dev{};
+        uint64_t total_weight = 0;
+        bool on() const { return words.get() != nullptr; }
+    } bank;
     ~rcw_handle();
 };
 
@@ -222,6 +234,7 @@ int validate_config(const rcw_config* c, int32_t batch);
 int plan_learner_view(const rcw_config& cfg, const RcwDev& dev, int32_t format, int32_t layout, int32_t height, int32_t width, int32_t flags,
                       int32_t frames, ViewPlan* plan);
 int plan_local_map(int32_t source, int32_t size, int32_t cells_per_tile, bool real64, std::vector<unsigned char>* table);
+int plan_wall_bank_weights(const uint32_t* weights, int32_t layouts, uint32_t* cum, uint64_t* total);
 
 // ---- rcw_step.hip: what a step, a reset or a re-render launches, and the resources those launches need ---------------------------------
 hipError_t launch_top_view_alone(rcw_handle* h, const uint8_t* mask_dev);
@@ -230,6 +243,7 @@ hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_goal_distance(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_local_map(rcw_handle* h, StackOp op);
+hipError_t launch_wall_bank(rcw_handle* h, bool force);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
 hipError_t replace_buffers(rcw_handle* h, std::initializer_list<RcwBuf*> old, std::initializer_list<RcwBuf*> fresh = {});
 int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient);

@@ -209,3 +209,22 @@ hipError_t rcw_launch_seen_map(const RcwDev& p, int32_t B, const uint8_t* mask_d
 // (plan_local_map); out: [B][size*size], 4-byte aligned.  One launch, every agent; reads p's state arrays and direction table, writes only out.
 size_t rcw_local_map_lds_bytes(const RcwDev& p, int32_t size, bool seen);
 hipError_t rcw_launch_local_map(const RcwDev& p, int32_t B, const uint8_t* seen_map, const void* off, int32_t size, uint8_t* out, hipStream_t s);
+
+// The wall bank (rcw_set_wall_bank, rcw_wall_bank.hip): what its kernel reads and writes, all in DEVICE memory.
+struct RcwWallBank {
+    int32_t layouts;             // L >= 1
+    const uint32_t* words;       // [L][nwords] the layouts in the tile map's word format: WALL bits set, GOAL bits and the padding clear
+    const uint32_t* cum;         // [L] cumulative weights, cum[L - 1] = the sum (1 .. 2^32 - 1)
+    uint32_t* last_episode;      // [B] each agent's episode counter as of its last start under the bank
+    int32_t* status_seen;        // [B] ... and its status word as of then
+    int32_t* layout;             // [B] the layout the agent's episode was given (rcw_wall_layout)
+    uint8_t* mask;               // [B] 1: the launch gave the agent a layout and a fresh state — the host re-renders these
+};
+// The layouts UInt8 (H*W, layouts) in device memory -> words; one launch, once per rcw_set_wall_bank.
+hipError_t rcw_launch_wall_bank_pack(const RcwDev& p, const uint8_t* walls_dev, uint32_t* words_dev, int32_t layouts, hipStream_t s);
+// One launch behind the core launches of a call that can move an episode counter: an agent whose counter differs from last_episode (force:
+// every agent) takes a layout and is reset against it under its episode's own key (counter: what the launch in front left); mask[a] says who.
+hipError_t rcw_launch_wall_bank(const RcwPlan& p, const RcwWallBank& bank, bool force, hipStream_t s);
+// The camera view (p.obs) of the agents with mask[a] != 0 from p.col_h / p.col_c, a workgroup an agent: the repaint behind rcw_launch_wall_bank,
+// whose mask is sparse — the camera fill's pixels, without its sweep over the whole batch.
+hipError_t rcw_launch_wall_bank_paint(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);

@@ -18,6 +18,7 @@ class RcwPinned {   // hipHostMalloc / hipHostFree
     void* p_ = nullptr;
 public:
     RcwPinned() = default;  RcwPinned(RcwPinned&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    RcwPinned& operator=(RcwPinned&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
     ~RcwPinned() { reset(); }
     void reset() { if (p_) (void)hipHostFree(p_); p_ = nullptr; }
     hipError_t hipHostMalloc(size_t bytes) { reset(); const hipError_t e = ::hipHostMalloc(&p_, bytes, hipHostMallocDefault); if (e != hipSuccess) p_ = nullptr; return e; }
@@ -38,6 +39,7 @@ class RcwEvent {   // hipEventCreateWithFlags / hipEventDestroy
     hipEvent_t e_ = nullptr;
 public:
     RcwEvent() = default;  RcwEvent(RcwEvent&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    RcwEvent& operator=(RcwEvent&& o) noexcept { if (this != &o) { reset(); e_ = o.e_; o.e_ = nullptr; } return *this; }
     ~RcwEvent() { reset(); }
     void reset() { if (e_) (void)hipEventDestroy(e_); e_ = nullptr; }
     hipError_t hipEventCreate(unsigned flags = hipEventDefault) { reset(); const hipError_t e = ::hipEventCreateWithFlags(&e_, flags); if (e != hipSuccess) e_ = nullptr; return e; }

@@ -426,6 +426,21 @@ int plan_local_map(int32_t source, int32_t size, int32_t cells_per_tile, bool re
     return RCW_OK;
 }
 
+// The wall bank's weights (include/rcw.h, "the wall bank") as the kernel reads them: cum[k] = w[0] + ... + w[k] (NULL: every weight 1), and
+// their sum, which must lie in 1 .. 2^32 - 1 — or the refusal.
+int plan_wall_bank_weights(const uint32_t* weights, int32_t layouts, uint32_t* cum, uint64_t* total)
+{
+    uint64_t sum = 0;
+    for (int32_t k = 0; k < layouts; ++k) {
+        sum += weights ? (uint64_t)weights[k] : 1u;
+        if (sum > 0xFFFFFFFFull) return fail(RCW_ERR_INVALID_ARGUMENT, "the wall bank's weights sum to more than 2^32 - 1 (at layout %d)", k);
+        cum[k] = (uint32_t)sum;
+    }
+    if (sum == 0) return fail(RCW_ERR_INVALID_ARGUMENT, "the wall bank's weights sum to zero: no layout could be drawn");
+    *total = sum;
+    return RCW_OK;
+}
+
 #ifdef RCW_DEV_SWITCHES
 #include "dev/api_plan_export.inc"   // the rules and the step's facts without a device (tests/test_top_view_plan.py, tests/test_step_state.py)
 #endif

@@ -131,6 +131,12 @@ hipError_t paint_camera(rcw_handle* h, const uint8_t* mask_dev, hipStream_t stre
     return rcw_launch_fill(h->dev, h->dev.col_h, h->dev.col_c, h->dev.obs, (long long)h->dev.B * h->dev.N, mask_dev, stream);
 }
 
+// ... or, behind the wall bank's kernel (sparse: the mask is the bank's, nearly always empty), a workgroup an agent instead of the window's sweep
+hipError_t paint_camera(rcw_handle* h, const uint8_t* mask_dev, hipStream_t stream, bool sparse)
+{
+    return sparse ? rcw_launch_wall_bank_paint(h->dev, mask_dev, stream) : paint_camera(h, mask_dev, stream);
+}
+
 // A step's camera view is one of three sequences of launches (launch_step_camera chooses: StepFacts::camera_step).  With profiling on, HIP
 // events bracket each kernel (Bracket): start (launch_step_camera's) | after cast | after the top view or the fill | end.
 namespace {
@@ -149,21 +155,21 @@ hipError_t launch_step_one(rcw_handle* h, const uint8_t* actions_dev, bool keep,
 
 // reset! / set_state (no action, maybe a mask) or a first step of the one-launch form: the casting workgroups alone — dynamics if any, the
 // current frame's descriptors, and the (masked) agents' slots in place —, then the camera fill as a launch of its own
-hipError_t launch_step_prime(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, const StepFacts::Camera& c, const Bracket& prof)
+hipError_t launch_step_prime(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, const StepFacts::Camera& c, const Bracket& prof, bool sparse)
 {
     rcw_handle::Step& st = h->step;
     hipError_t e;
     if ((e = rcw_launch_step_spec(h->dev, actions_dev, mask_dev, nullptr, st.slot[st.cur()].get<uint16_t>(), false, true, false, h->stream)) != hipSuccess) return e;
     st.prime_cast_queued(mask_dev != nullptr);
     if ((e = prof.mark(1, h->stream)) != hipSuccess || (e = prof.mark(2, h->stream)) != hipSuccess) return e;
-    if ((e = paint_camera(h, mask_dev, h->stream)) != hipSuccess) return e;
+    if ((e = paint_camera(h, mask_dev, h->stream, sparse)) != hipSuccess) return e;
     st.prime_fill_queued(c, mask_dev != nullptr);
     return prof.done(h->stream);
 }
 
 // cast kernel + fill kernel, back to back on the handle's stream (+ the top view when the handle renders it: before the fill with the
 // one-kernel form, around it with the two-kernel form, whose event 2 is behind the fill)
-hipError_t launch_step_two(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, const Bracket& prof)
+hipError_t launch_step_two(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, const Bracket& prof, bool sparse)
 {
     const RcwPlan& d = h->dev;
     hipError_t e;
@@ -172,25 +178,26 @@ hipError_t launch_step_two(rcw_handle* h, const uint8_t* actions_dev, const uint
     auto fill = [&](hipStream_t fs) -> hipError_t {            // (fs: the handle's stream, or its side stream: launch_top_view)
         hipError_t f;
         if (!d.top_split && (f = prof.mark(2, fs)) != hipSuccess) return f;
-        if ((f = paint_camera(h, mask_dev, fs)) != hipSuccess) return f;
+        if ((f = paint_camera(h, mask_dev, fs, sparse && !d.top_view)) != hipSuccess) return f;   // (with a top view the fill may be the launch that draws)
         return d.top_split ? prof.mark(2, fs) : hipSuccess;
     };
     if ((e = d.top_view ? launch_top_view(h, mask_dev, true, fill, prof) : fill(h->stream)) != hipSuccess) return e;   // SR:337
     return prof.done(h->stream);
 }
 
-hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev)
+// (bank = true: the wall bank's re-render of the agents it restarted — behind the step proper, outside its bracket, the mask sparse)
+hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, bool bank = false)
 {
     const StepFacts::Camera c = h->step.camera_step(actions_dev != nullptr, mask_dev != nullptr, [h] {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         return hipStreamIsCapturing(h->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
     });
-    const Bracket prof(&h->prof);
+    const Bracket prof(bank ? nullptr : &h->prof);
     const hipError_t e = prof.mark(0, h->stream);
     if (e != hipSuccess) return e;
     if (c.path == StepFacts::kOneLaunch) return launch_step_one(h, actions_dev, c.keep, prof);
-    if (c.path == StepFacts::kPrime) return launch_step_prime(h, actions_dev, mask_dev, c, prof);
-    return launch_step_two(h, actions_dev, mask_dev, prof);
+    if (c.path == StepFacts::kPrime) return launch_step_prime(h, actions_dev, mask_dev, c, prof, bank);
+    return launch_step_two(h, actions_dev, mask_dev, prof, bank);
 }
 
 }  // namespace
@@ -234,10 +241,25 @@ hipError_t launch_local_map(rcw_handle* h, StackOp op)
     return rcw_launch_local_map(h->dev, h->B, lm.source == RCW_LOCAL_SEEN ? h->seen.map : nullptr, lm.off, lm.size, lm.img, h->stream);
 }
 
+// The wall bank (rcw_set_wall_bank), behind the core launches of a call that can move an episode counter: its kernel gives every agent that
+// began an episode a layout and a fresh state against it, and leaves in the bank's own mask who that was.  force: every agent (the call
+// that installs the bank).  Behind rcw_reset the caller's re-render covers exactly those agents; behind a step, launch_step re-renders them.
+hipError_t launch_wall_bank(rcw_handle* h, bool force)
+{
+    return h->bank.on() ? rcw_launch_wall_bank(h->dev, h->bank.dev, force, h->stream) : hipSuccess;
+}
+
+// A step of a handle with a wall bank: the step proper, the bank's kernel, the camera view of the agents it restarted once more through the
+// masked path (valid in both step forms: a masked prime behind a one-launch step is what rcw_set_walls(mask) queues) — all OUTSIDE
+// rcw_profile's bracket —, and then every feature ONCE: they key on the episode counter and find the restarted agents stale against the
+// final world.  A handle without a bank launches what it launched before.
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op)
 {
+    const bool bank = h->bank.on() && actions_dev != nullptr;
     if (!h->learner.only()) {
         hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
+        if (e == hipSuccess && bank) e = launch_wall_bank(h, false);
+        if (e == hipSuccess && bank) e = launch_step_camera(h, nullptr, h->bank.dev.mask, true);
         if (e == hipSuccess && h->learner.on()) e = launch_view(h, mask_dev, op);
         if (e == hipSuccess) e = launch_goal_distance(h, mask_dev, op);
         if (e == hipSuccess) e = launch_seen_map(h, mask_dev, op);
@@ -249,6 +271,9 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if ((e = prof.mark(0, h->stream)) != hipSuccess) return e;
     if ((e = rcw_launch_cast(h->dev, actions_dev, mask_dev, h->stream)) != hipSuccess) return e;
     h->step.columns_cast(mask_dev != nullptr);
+    // (RCW_VIEW_ONLY: nothing is rendered yet — the bank's kernel and the restarted agents' cast go right here, and the top view and the
+    // view kernel below render every agent once; the two launches count into cast_ms of a handle that has a bank)
+    if (bank && ((e = launch_wall_bank(h, false)) != hipSuccess || (e = rcw_launch_cast(h->dev, nullptr, h->bank.dev.mask, h->stream)) != hipSuccess)) return e;
     if ((e = prof.mark(1, h->stream)) != hipSuccess) return e;
     if (h->dev.top_view && (e = launch_top_view_alone(h, mask_dev)) != hipSuccess) return e;
     if ((e = prof.mark(2, h->stream)) != hipSuccess) return e;

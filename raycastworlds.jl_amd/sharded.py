@@ -97,6 +97,8 @@ class ShardedSingleRoom:
         # for all, which every rank advances through all global agents' draws (in the same initial state on every rank) —
         # so that the states do not depend on the sharding, as with the device generator (agent_id_offset)
         self.rng = kwargs.pop("rng", None)
+        if self.rng is not None and kwargs.get("wall_bank") is not None:
+            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall bank")
         self.env = env_factory(batch=self.count, agent_id_offset=self.first,
                                device=default_device() if device is None else device, **kwargs)
         self._abi_comm = False
@@ -174,6 +176,18 @@ class ShardedSingleRoom:
             touched = np.ones(G, dtype=bool) if gm is None else gm != 0
             self.env._rng_walls_global[touched] = w[took[touched]]
             _reset_from_rng(self.env, self.rng, gm, first=self.first, global_batch=self.global_batch)
+
+    def set_wall_bank(self, walls, weights=None) -> None:
+        """`SingleRoom.set_wall_bank` for the sharded batch: the bank and its weights are REPLICATED — every rank passes the same
+        arguments — and nothing else is needed: the layout an agent draws is keyed by its global id (`agent_id_offset`), so a shard
+        equals its slice of the whole batch."""
+        if self.rng is not None and walls is not None:
+            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall bank")
+        self.env.set_wall_bank(walls, weights)
+
+    def set_wall_bank_weights(self, weights) -> None:
+        """`SingleRoom.set_wall_bank_weights`, the same weights on every rank."""
+        self.env.set_wall_bank_weights(weights)
 
     # ---- the observation gather over torch.distributed -------------------------------------
     def _as_tensor(self, x):

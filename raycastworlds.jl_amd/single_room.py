@@ -346,7 +346,8 @@ class SingleRoom:
     `set_time_limit`.  `walls` / `wall_index` (this build's addition; None = the reference's empty room) are `set_walls`'
     arguments, applied right after construction.  `goal_distance` (this build's addition) is `set_goal_distance(True)` after them,
     `seen_map` (this build's addition) `set_seen_map(True)` after that, `local_map` (this build's addition; an int — the size — or a dict
-    of `set_local_map`'s keywords) `set_local_map` last.
+    of `set_local_map`'s keywords) `set_local_map` last.  `wall_bank` / `wall_bank_weights` (this build's addition) are `set_wall_bank`'s
+    arguments, applied after `walls` and the time limit and before the features: a layout drawn on the device at every episode start.
     """
 
     def __init__(
@@ -382,6 +383,8 @@ class SingleRoom:
         goal_distance: bool = False,
         seen_map: bool = False,
         local_map=None,
+        wall_bank=None,
+        wall_bank_weights=None,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -473,6 +476,15 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        if wall_bank is not None:
+            try:
+                self.set_wall_bank(wall_bank, wall_bank_weights)
+            except BaseException:
+                self._handle.close()
+                raise
+        elif wall_bank_weights is not None:
+            self._handle.close()
+            raise ValueError("wall_bank_weights needs wall_bank")
         if goal_distance:
             try:
                 self.set_goal_distance(True)
@@ -517,7 +529,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_seen_map_dev", "_local_map_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_seen_map_dev", "_local_map_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -1054,6 +1066,71 @@ class SingleRoom:
             self._rng_walls[touched] = w[took[touched]]
             _reset_from_rng(self, self.rng, m)
 
+    # ---- the wall bank (include/rcw.h, rcw_set_wall_bank) -------------------------------
+    def set_wall_bank(self, walls, weights=None) -> None:
+        """A bank of wall layouts on the device, one drawn for an agent at every start of an episode — `reset_`, a done or truncated
+        restart under `auto_reset`, and this call, which restarts every agent (episode counters + 1).  `walls` is bool / uint8
+        (M, H, W) (or (H, W): a bank of one), each layout checked as `set_walls` checks one (ValueError otherwise, the environment
+        untouched); `weights` is M non-negative integers whose sum lies in 1 .. 2^32 - 1 (None: uniform): layout k is drawn with
+        probability weights[k] / sum, as a pure function of (seed, global agent id, episode, bank) — sharding, the step form and the
+        agent's previous walls play no part.  No host synchronisation per step; `wall_layout` says which layout each agent has,
+        `env.world.walls` reads the walls back.  `walls=None` switches the bank off: the agents keep the walls they have and
+        `set_walls` works again.  An environment built with `rng` draws its resets on the host and takes no bank."""
+        if walls is None:
+            self.__dict__.pop("_wall_layout_dev", None)
+            self._check(self._lib.rcw_set_wall_bank(self._h, None, 0, None))
+            return
+        if self.rng is not None:
+            raise ValueError("an environment built with rng draws its resets on the host: it takes no wall bank")
+        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
+        w = np.asarray(walls)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1:] != (H, W) or w.shape[0] < 1:
+            raise ValueError(f"wall bank must be (M, H, W) = (M, {H}, {W}) with M >= 1, got {np.asarray(walls).shape}")
+        flat = np.ascontiguousarray((w != 0).transpose(0, 2, 1), dtype=np.uint8)   # tile (i, j) of layout m at m H W + (i - 1) + H (j - 1)
+        wt = self._wall_bank_weights(weights, w.shape[0])
+        self.__dict__.pop("_wall_layout_dev", None)
+        self._check(self._lib.rcw_set_wall_bank(self._h, _as_ptr(flat), w.shape[0], _as_ptr(wt)))
+
+    @staticmethod
+    def _wall_bank_weights(weights, layouts: int):
+        if weights is None:
+            return None
+        wt = np.asarray(weights)
+        if wt.shape != (layouts,) or not np.issubdtype(wt.dtype, np.integer) or (wt < 0).any() or (wt > 0xFFFFFFFF).any():
+            raise ValueError(f"wall bank weights must be {layouts} integers in 0 .. 2^32 - 1")
+        return np.ascontiguousarray(wt, dtype=np.uint32)
+
+    def set_wall_bank_weights(self, weights) -> None:
+        """New weights for the installed bank (None: uniform), in stream order and without waiting for the device: they hold from each
+        agent's next episode start, no agent is touched — what a prioritised-replay caller calls every few updates."""
+        wt = self._wall_bank_weights(weights, self.wall_bank_info["layouts"])
+        self._check(self._lib.rcw_set_wall_bank_weights(self._h, _as_ptr(wt)))
+
+    @property
+    def wall_bank_info(self) -> dict:
+        """`layouts` and `total_weight` of the bank (rcw_wall_bank_info); zeros while it is off."""
+        n, t = C.c_int32(), C.c_uint64()
+        self._check(self._lib.rcw_wall_bank_info(self._h, C.byref(n), C.byref(t)))
+        return {"layouts": n.value, "total_weight": t.value}
+
+    def _wall_layout_host(self) -> np.ndarray:
+        out = np.empty(self.batch, dtype=np.int32)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_wall_layout(self._h, _as_ptr(out)))
+        return out
+
+    @property
+    def wall_layout(self) -> DeviceArray:
+        """int32 (B,) in device memory: the bank layout each agent's current episode was given (`.torch(sync=False)` on the GPU,
+        `np.asarray(env.wall_layout)` for a host copy).  Valid until the next `set_wall_bank`."""
+        if getattr(self, "_wall_layout_dev", None) is None:
+            p = C.c_void_p()
+            self._check(self._lib.rcw_wall_layout_device_ptr(self._h, C.byref(p)))
+            self._wall_layout_dev = DeviceArray(p.value, (self.batch,), np.int32, self, self._sync, host_getter=self._wall_layout_host)
+        return self._wall_layout_dev
+
     def ray_table(self) -> np.ndarray:
         """(nd, 5, N) float32: per heading [dx | dy | |1/dx| | |1/dy| | dir·ray]."""
         out = np.empty((self.cfg.num_directions, 5, self.cfg.num_rays), dtype=self.T)
@@ -1284,6 +1361,8 @@ def reset_(env: SingleRoom, mask=None, seed: Optional[int] = None, rng=None) -> 
     if rng is None and seed is None:
         rng = getattr(env, "rng", None)
     if rng is not None:
+        if env.wall_bank_info["layouts"]:
+            raise ValueError("the environment draws its walls from a wall bank on the device: reset it with a seed, not an rng")
         _reset_from_rng(env, rng, mask)
         return None
     if seed is not None:

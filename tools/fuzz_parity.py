@@ -3,7 +3,7 @@
 configurations (map size, columns, headings, field of view, radius, step, camera height, image
 height, world-unit type, the three unpinned switches, both BoundsError policies, auto-reset).
 
-    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit|goal]
+    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit|goal|bank]
                                                                    # "top": every configuration renders the top view;
                                                                    # "split": ... with a geometry of the unit store kernels;
                                                                    # "flat": ... of the flat store kernel (any pu >= 9), and any
@@ -15,6 +15,9 @@ height, world-unit type, the three unpinned switches, both BoundsError policies,
                                                                    # "goal": the goal distance (rcw_set_goal_distance) — random maps, layouts and
                                                                    #         sequences of calls against tests/goal_distance_ref.py, the three words and
                                                                    #         every agent's whole field compared after every call (goal_mode below)
+                                                                   # "bank": the wall bank (rcw_set_wall_bank) — random maps, banks, weights and
+                                                                   #         sequences of calls against tests/wall_bank_ref.py, the whole state, the
+                                                                   #         frames and wall_layout compared after every call (bank_mode below)
 """
 import os
 import sys
@@ -136,8 +139,116 @@ def goal_mode(n_cfg, seed):
     return 1 if fails else 0
 
 
+def bank_mode(n_cfg, seed):
+    """Maps of 3 x 4 to 40 x 40 tiles; a bank of 1, 2, 3, 7 or 70 layouts — the ring, four rooms, a maze or pillars at 0.05 to 0.35 —,
+    uniform or with random weights of 0 to 5; 1 to 9 agents with 8 or 16 view columns (the reference renders in Python), Float32 and
+    Float64, both forms of the step asked for, a time limit of 0, 2 or 5, auto_reset.  Then 30 random calls — a step, a masked or full
+    reset_ with a new seed, a masked set_state onto free tiles of each agent's current layout, new weights, the bank off and another one
+    on —, each made on the reference (tests/wall_bank_cases.py's Recorder) and on the engine (its Player), which compares the whole state,
+    the frames, the time limit's words and wall_layout after every call.  Every configuration draws from default_rng([seed, c])."""
+    import wall_bank_cases as BC
+    from raycastworlds_jl_amd import _capi, layouts
+
+    rng = None
+
+    def layout(H, W):
+        kind = str(rng.choice(["ring", "four_rooms", "maze", "pillars"]))
+        if kind in ("four_rooms", "maze") and min(H, W) < 5:
+            kind = "ring"
+        w = {"ring": lambda: layouts.ring(H, W), "four_rooms": lambda: layouts.four_rooms(H, W), "maze": lambda: layouts.maze(H, W, rng),
+             "pillars": lambda: GD.pillars(H, W, float(rng.uniform(0.05, 0.35)), rng)}[kind]()
+        return w if (~w).sum() >= 2 else layouts.ring(H, W)
+
+    def bank(H, W):
+        M = int(rng.choice([1, 2, 3, 7, 70]))
+        walls = np.stack([layout(H, W) for _ in range(M)])
+        weights = None
+        if rng.integers(0, 2):
+            weights = rng.integers(0, 6, M).astype(np.uint32)
+            weights[int(rng.integers(0, M))] += 1                            # (a sum of zero is refused)
+        return walls, weights
+
+    def some(B):
+        mask = (rng.random(B) < 0.5).astype(np.uint8)
+        mask[int(rng.integers(0, B))] = 1
+        return mask
+
+    totals = dict(step=0, reset=0, masked_reset=0, set_state=0, weights=0, off_and_on=0, episode_starts=0, layout_changed=0, layout_kept=0, goal_redraws=0,
+                  restarts_after_done=0, restarts_after_truncation=0, one_launch_steps=0, two_launch_steps=0, words_not_multiple_of_4=0, banks_past_64=0)
+    fails = 0
+    for c in range(n_cfg):
+        rng = np.random.default_rng([seed, c])
+        H, W = int(rng.integers(3, 41)), int(rng.integers(4, 41))
+        B = int(rng.integers(1, 10))
+        T64, L = bool(rng.integers(0, 2)), int(rng.choice([0, 2, 5]))
+        N, Hc = [(8, 64), (16, 64), (8, 24), (16, 128)][int(rng.integers(0, 4))]
+        form = str(rng.choice(["one-launch", "two-launches"]))
+        engine_seed = int(rng.integers(0, 2**31))
+        shape = dict(H=H, W=W, N=N, Hc=Hc, B=B, seed=engine_seed, T="Float64" if T64 else "Float32")
+        where = f"config {c}: {H} x {W}, B={B} T64={T64} L={L} N={N} Hc={Hc} {form} seed={engine_seed}"
+        try:
+            env = BC.make_env(RCW, shape)
+            try:
+                env.set_step_form(form)
+            except _capi.RcwError as e:
+                assert form == "one-launch" and e.code == _capi.RCW_ERR_UNSUPPORTED and "does not take the one-launch step" in e.message, e
+                form = "two-launches"
+            totals["one_launch_steps" if form == "one-launch" else "two_launch_steps"] += 1
+            totals["words_not_multiple_of_4"] += int(((2 * H * W + 63) // 64 * 2) % 4 != 0)
+            rec = BC.Recorder(shape)
+            play = BC.Player(RCW, env, rec.snaps, where)
+            both = lambda call, *a, **k: (getattr(rec, call)(*a, **k), getattr(play, call)(*a, **k))
+            if L:
+                both("set_time_limit", L)
+            walls, weights = bank(H, W)
+            totals["banks_past_64"] += int(len(walls) > 64)
+            both("set_wall_bank", walls, weights)
+            for k in range(30):
+                call = str(rng.choice(["step", "step", "step", "step", "step", "reset", "masked_reset", "set_state", "weights", "off_and_on"]))
+                play.name = f"{where}, call {k} ({call})"
+                totals[call] += 1
+                if call == "step":
+                    both("step", rng.integers(1, 5, B).astype(np.uint8))
+                elif call in ("reset", "masked_reset"):
+                    both("reset", some(B) if call == "masked_reset" else None, int(rng.integers(0, 2**31)))
+                elif call == "set_state":
+                    mask, s = some(B), rec.snaps[-1]
+                    goal, pos, heading = s["goal"].copy(), s["position"].copy(), s["direction"].copy()
+                    for b in np.flatnonzero(mask):
+                        free = np.argwhere(~rec.ref.walls_of(b))
+                        goal[b] = free[int(rng.integers(0, len(free)))] + 1
+                        pos[b] = free[int(rng.integers(0, len(free)))] + 0.5
+                        heading[b] = int(rng.integers(0, 8))
+                    both("set_state", goal, pos, heading, mask)
+                elif call == "weights":
+                    M = len(rec.ref.bank)
+                    weights = rng.integers(0, 6, M).astype(np.uint32)
+                    weights[int(rng.integers(0, M))] += 1
+                    both("set_weights", weights if rng.integers(0, 4) else None)
+                else:
+                    both("set_wall_bank", None)
+                    both("step", rng.integers(1, 5, B).astype(np.uint8))
+                    walls, weights = bank(H, W)
+                    totals["banks_past_64"] += int(len(walls) > 64)
+                    both("set_wall_bank", walls, weights)
+            play.finished()
+            for k, v in rec.events.items():
+                if k in totals:
+                    totals[k] += v
+            env.close()
+        except Exception as e:   # noqa: BLE001
+            fails += 1
+            print(f"{where} FAILED\n   {type(e).__name__}: {str(e)[:400]}")
+            if fails >= 5:
+                break
+    print(f"{n_cfg} random configurations (wall bank: " + ", ".join(f"{v} {k}" for k, v in totals.items()) + f"), {fails} mismatches")
+    return 1 if fails else 0
+
+
 if len(sys.argv) > 3 and sys.argv[3] == "goal":
     sys.exit(goal_mode(n_cfg, int(sys.argv[2])))
+if len(sys.argv) > 3 and sys.argv[3] == "bank":
+    sys.exit(bank_mode(n_cfg, int(sys.argv[2])))
 limit_events = {}
 one_launch_steps = 0
 two_kernel_forms = 0                                            # (rcw_set_top_view_form: by default it is taken only from 256 MiB a step)
