@@ -532,12 +532,58 @@ RCW_API int rcw_local_map_copy(rcw_handle* h, uint8_t* out_host /* (S*S, count) 
  *   rcw_wall_bank_info            L and the weights' sum (either pointer may be NULL); zeros while the bank is off.
  *   rcw_wall_layout               host copy of each agent's current layout index, Int32 (B); waits for the stream as rcw_done does.
  *   rcw_wall_layout_device_ptr    the same array in DEVICE memory, stable until the next rcw_set_wall_bank.
- * The last two, and rcw_set_wall_bank_weights, return RCW_ERR_UNSUPPORTED on a handle without a bank. */
+ * rcw_set_wall_bank_weights returns RCW_ERR_UNSUPPORTED on a handle without a bank, the two getters on a handle with neither a bank nor
+ * a wall generator (below).  rcw_set_wall_bank is refused (RCW_ERR_UNSUPPORTED) while the handle has a wall generator. */
 RCW_API int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host /* (H*W, L) */, int32_t layouts, const uint32_t* weights_host /* (L) or NULL */);
 RCW_API int rcw_set_wall_bank_weights(rcw_handle* h, const uint32_t* weights_host /* (L) or NULL */);
 RCW_API int rcw_wall_bank_info(rcw_handle* h, int32_t* layouts, uint64_t* total_weight);
 RCW_API int rcw_wall_layout(rcw_handle* h, int32_t* out_host /* (B) */);
 RCW_API int rcw_wall_layout_device_ptr(rcw_handle* h, void** device_ptr);
+/* ---- the wall generator (this build's addition: a new maze made on the device at every start of an episode) ---------------------------
+ * Opt-in per handle.  The bank above draws from a finite set the host built; a handle with a generator makes the layout itself, in the
+ * kernel that gives it out, from one 64-bit key — a fresh maze every episode, or a seeded range of levels to train or evaluate on.
+ * A MAZE FROM ONE KEY  maze(m, H, W, loops), H, W >= 5, with draw(m, n) the counter-based draw number n of key m (csrc/rcw_rng.h):
+ *   cells   the tiles with odd 0-based (i, j) inside the ring: ni = (H-1)/2, nj = (W-1)/2 (integer division), C = ni nj, cell c = ci nj + cj
+ *           on tile (2ci+1, 2cj+1).  With an even H or W the last interior row or column stays wall.
+ *   edges   the east edge of cell c has id 2c, exists where cj+1 < nj, and its passage tile is (2ci+1, 2cj+2); the south edge has id 2c+1,
+ *           exists where ci+1 < ni, passage tile (2ci+2, 2cj+1).
+ *   order   every edge has the order word w(id) = (draw(m, id) & 0xFFFFFFFFFFF00000) | id.  Ids stay below 2^20: the words are distinct.
+ *   tree    the minimum spanning tree of the cell grid under w.  It is unique, so it does not depend on the algorithm that finds it
+ *           (the device runs Boruvka rounds in LDS, rcw_wall_generator_layout below sorts the edges and runs Kruskal).
+ *   loops   a non-tree edge is opened too where (draw(m, 2C + id) >> 32) < loops; loops is UInt32, 0 gives a perfect maze.
+ *   Every tile is WALL except the cells and the passage tiles of tree edges and opened edges.  The layout is connected and ring-closed by
+ *   construction and has at least 7 free interior tiles: always valid as rcw_set_walls wants one.
+ * THE KEY OF AN EPISODE  With g = agent_id_offset + a the agent's global id and e its episode counter before the increment:
+ *   key = the episode key of (seed, g, e), u = draw number 2^63 of that key (the bank's draw index: generator and bank exclude each other).
+ *   levels == 0   m = u, wall_layout[a] = -1: every episode gets a maze of its own.
+ *   levels >= 1   l = first_level + floor(u * levels / 2^64), m = the episode key of (level_seed, l, 0), wall_layout[a] = l: the maze is a
+ *                 function of (level_seed, l, H, W, loops) alone.  Requires first_level >= 0 and first_level + levels <= 2^31 - 1.
+ * After that the rule is exactly the bank's: the WALL layer becomes the maze, the GOAL layer is cleared, reset!(world) runs against the new
+ * walls under `key` from draw 0, the time limit's words are zeroed, the counter ends at e + 1 (once).  The result is a pure function of
+ * (seed, g, e, parameters): not of the sharding, the step form, or the walls the agent had.  A handle without a generator draws and
+ * launches exactly what it did before.  The ABI is additive: RCW_ABI_VERSION and rcw_config are what they were.
+ *   rcw_set_wall_generator        enable != 0: installs the generator and restarts EVERY agent under the rule with the handle's current seed,
+ *                                 as rcw_set_wall_bank does (counters + 1, everything rendered, the features refilled).  Validated on the
+ *                                 host before anything is queued, a refusal leaves the handle untouched: RCW_ERR_INVALID_ARGUMENT for H or
+ *                                 W below 5 or a bad level range; RCW_ERR_UNSUPPORTED for C > 4096 (maps beyond 129 x 129: the message names
+ *                                 the bound) and while a bank is on — rcw_set_wall_bank is likewise refused while the generator is on:
+ *                                 switch one off first.  enable == 0 switches it off (RCW_OK also where there was none): the walls stay.
+ *                                 The parameters are kernel arguments fixed at install: a captured step replays correctly.
+ *   rcw_reset, rcw_step, rcw_step_device, rcw_set_state*, the feature switches   as with a bank: an agent that begins an episode takes a
+ *                                 maze by the rule, goal distance, seen map, local map, learner view and frame stack follow it;
+ *                                 rcw_set_state* keeps the maze.  rcw_set_walls: RCW_ERR_UNSUPPORTED while the generator is on.
+ *   rcw_wall_generator_info       the parameters (any pointer may be NULL); zeros while the generator is off.
+ *   rcw_wall_layout, rcw_wall_layout_device_ptr   also serve a handle with a generator: l, or -1.
+ *   rcw_wall_generator_key        handle-less, pure host arithmetic: the maze key m and the level (-1 with levels == 0) of episode `episode`
+ *                                 (the counter before the increment) of global agent `global_agent` under `seed`.
+ *   rcw_wall_generator_layout     handle-less, pure host arithmetic: maze(maze_key, H, W, loops) as UInt8 (H*W) in rcw_set_walls' order
+ *                                 (1 = wall) — what the agent's WALL layer holds; the replay and evaluation tool of a caller.
+ *                                 RCW_ERR_INVALID_ARGUMENT for H or W below 5, or edge ids of 2^20 and more. */
+RCW_API int rcw_set_wall_generator(rcw_handle* h, int32_t enable, uint32_t loops, int32_t levels, int32_t first_level, uint64_t level_seed);
+RCW_API int rcw_wall_generator_info(rcw_handle* h, int32_t* enabled, uint32_t* loops, int32_t* levels, int32_t* first_level, uint64_t* level_seed);
+RCW_API int rcw_wall_generator_key(uint64_t seed, int32_t global_agent, uint32_t episode, int32_t levels, int32_t first_level, uint64_t level_seed,
+                                   uint64_t* maze_key, int32_t* level);
+RCW_API int rcw_wall_generator_layout(int32_t H, int32_t W, uint64_t maze_key, uint32_t loops, uint8_t* out_host /* (H*W), rcw_set_walls' order */);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

@@ -545,6 +545,64 @@ function wall_layout_device_ptr(env::BatchedSingleRoom)
     check(ccall((:rcw_wall_layout_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
 end
 
+# ---- the wall generator (this build's addition; include/rcw.h, rcw_set_wall_generator) --------------------------------------------
+"""
+    set_wall_generator!(env; loops = 0.0, levels = 0, first_level = 0, level_seed = 0)
+    set_wall_generator!(env, nothing)
+
+A new maze made on the device at every start of an episode: `reset!`, a done or truncated restart under `auto_reset`, and this call,
+which restarts every agent with the environment's seed (episode counters + 1).  The maze is the minimum spanning tree of the odd
+sub-grid of tiles under an order drawn from one 64-bit key, plus the non-tree edges `loops` opens — a probability in `[0, 1]`, scaled
+to `UInt32` with `min(floor(p * 2^32), 2^32 - 1)`.  `levels == 0`: every episode a maze of its own, `wall_layout(env)` reads `-1`.
+`levels >= 1`: the episode picks level `first_level + (0 : levels - 1)` and the maze is a function of (level_seed, level, H, W, loops)
+alone; `wall_layout(env)` says which.  Maps of 5 x 5 to 129 x 129.  `set_walls!` and `set_wall_bank!` are refused while the generator
+is on; `set_wall_generator!(env, nothing)` switches it off, the agents keep their walls.  An environment built with `rng` draws its
+resets on the host and takes no generator.
+"""
+function set_wall_generator!(env::BatchedSingleRoom; loops::Real = 0.0, levels::Integer = 0, first_level::Integer = 0, level_seed::Integer = 0)
+    env.rng === nothing || throw(ArgumentError("an environment built with rng draws its resets on the host: it takes no wall generator"))
+    0 <= loops <= 1 || throw(ArgumentError("loops is a probability in [0, 1]"))
+    word = UInt32(min(floor(UInt64, Float64(loops) * 2.0^32), UInt64(0xFFFFFFFF)))
+    check(ccall((:rcw_set_wall_generator, librcw), Cint, (Ptr{Cvoid}, Int32, UInt32, Int32, Int32, UInt64),
+                env.handle, 1, word, levels, first_level, level_seed))
+    env.stale = true
+    return nothing
+end
+function set_wall_generator!(env::BatchedSingleRoom, ::Nothing)
+    check(ccall((:rcw_set_wall_generator, librcw), Cint, (Ptr{Cvoid}, Int32, UInt32, Int32, Int32, UInt64), env.handle, 0, 0, 0, 0, 0))
+    return nothing
+end
+function wall_generator_info(env::BatchedSingleRoom)
+    on = Ref{Int32}(0); loops = Ref{UInt32}(0); levels = Ref{Int32}(0); first = Ref{Int32}(0); seed = Ref{UInt64}(0)
+    check(ccall((:rcw_wall_generator_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{UInt32}, Ref{Int32}, Ref{Int32}, Ref{UInt64}),
+                env.handle, on, loops, levels, first, seed))
+    return (enabled = on[] != 0, loops = loops[], levels = levels[], first_level = first[], level_seed = seed[])
+end
+"""
+    generated_maze_key(seed, global_agent, episode; levels = 0, first_level = 0, level_seed = 0) -> (maze_key, level)
+
+The wall generator's maze key and level (`-1` with `levels == 0`) of episode `episode` (the counter before the increment) of a global
+agent: host arithmetic, no device.
+"""
+function generated_maze_key(seed::Integer, global_agent::Integer, episode::Integer; levels::Integer = 0, first_level::Integer = 0, level_seed::Integer = 0)
+    key = Ref{UInt64}(0); level = Ref{Int32}(0)
+    check(ccall((:rcw_wall_generator_key, librcw), Cint, (UInt64, Int32, UInt32, Int32, Int32, UInt64, Ref{UInt64}, Ref{Int32}),
+                seed, global_agent, episode, levels, first_level, level_seed, key, level))
+    return (key[], level[])
+end
+"""
+    generated_maze(maze_key, H, W; loops = 0.0) -> BitMatrix (H, W)
+
+The wall generator's maze of one key (`true` = wall), as an agent's WALL layer holds it: host arithmetic (Kruskal), no device.
+"""
+function generated_maze(maze_key::Integer, H::Integer, W::Integer; loops::Real = 0.0)
+    0 <= loops <= 1 || throw(ArgumentError("loops is a probability in [0, 1]"))
+    word = UInt32(min(floor(UInt64, Float64(loops) * 2.0^32), UInt64(0xFFFFFFFF)))
+    out = Matrix{UInt8}(undef, max(H, 0), max(W, 0))                             # column-major: tile (i, j) at (i - 1) + H (j - 1)
+    check(ccall((:rcw_wall_generator_layout, librcw), Cint, (Int32, Int32, UInt64, UInt32, Ptr{UInt8}), H, W, maze_key, word, out))
+    return out .!= 0
+end
+
 # per-agent sticky status: 0, -5 where the reference would have raised BoundsError, -2 for an invalid device action,
 # 1 (a warning) where sample_empty_position gave up after max_tries and returned an occupied tile (utils.jl:34 @warns there)
 function status(env::BatchedSingleRoom)

@@ -431,6 +431,7 @@ int rcw_set_walls(rcw_handle* h, const uint8_t* walls_host, int32_t layouts, con
 {
     int rc = check_handle(h); if (rc) return rc;
     if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
+    if (h->gen.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle makes its walls with the wall generator; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     char why[256];
     if (validate_walls(H, W, h->B, walls_host, layouts, layout_index_host, mask_host, why, sizeof why) != RCW_OK)
@@ -596,7 +597,7 @@ int rcw_clear_error(rcw_handle* h)
     int rc = check_handle(h); if (rc) return rc;
     RCW_HIP(hipMemsetAsync(h->d_err.get(), 0, sizeof(int32_t), h->stream));
     RCW_HIP(hipMemsetAsync(h->d_status.get(), 0, (size_t)h->B * sizeof(int32_t), h->stream));
-    if (h->bank.on()) RCW_HIP(hipMemsetAsync(h->bank.dev.status_seen, 0, (size_t)h->B * sizeof(int32_t), h->stream));   // (the bank's record of them)
+    if (h->drawn()) RCW_HIP(hipMemsetAsync(h->drawn()->status_seen, 0, (size_t)h->B * sizeof(int32_t), h->stream));   // (the bank's or the generator's record of them)
     RCW_HIP(hipStreamSynchronize(h->stream));
     return RCW_OK;
 }
@@ -1116,6 +1117,7 @@ int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
         wb.dev = RcwWallBank{}; wb.total_weight = 0;
         return RCW_OK;
     }
+    if (h->gen.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_bank: the handle makes its walls with the wall generator; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     char why[256];
     if (layouts < 0) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_set_wall_bank: layouts must be >= 0 (got %d)", layouts);
@@ -1164,6 +1166,7 @@ int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
 extern "C++" {
 namespace {
 int need_wall_bank(rcw_handle* h) { return h->bank.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no wall bank (rcw_set_wall_bank)"); }
+int need_drawn_walls(rcw_handle* h) { return h->drawn() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator)"); }
 }  // namespace
 }  // extern "C++"
 
@@ -1198,15 +1201,62 @@ int rcw_wall_bank_info(rcw_handle* h, int32_t* layouts, uint64_t* total_weight)
 int rcw_wall_layout(rcw_handle* h, int32_t* out_host)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_wall_bank(h); if (rc) return rc;
-    return copy_out<int32_t>(h, out_host, h->bank.dev.layout, (size_t)h->B);
+    rc = need_drawn_walls(h); if (rc) return rc;
+    return copy_out<int32_t>(h, out_host, h->drawn()->layout, (size_t)h->B);
 }
 
 int rcw_wall_layout_device_ptr(rcw_handle* h, void** device_ptr)
 {
     if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = need_wall_bank(h); if (rc) return rc;
-    *device_ptr = h->bank.dev.layout;
+    int rc = need_drawn_walls(h); if (rc) return rc;
+    *device_ptr = h->drawn()->layout;
+    return RCW_OK;
+}
+
+// The wall generator (include/rcw.h).  Validated and allocated before anything of the handle changes; then every agent is restarted under
+// the rule: the body of rcw_reset(h, NULL, <the handle's seed>) with the generator's kernel forced for every agent — rcw_set_wall_bank's
+// sequence without a bank to stage.
+int rcw_set_wall_generator(rcw_handle* h, int32_t enable, uint32_t loops, int32_t levels, int32_t first_level, uint64_t level_seed)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::WallGen& wg = h->gen;
+    if (!enable) {                                                     // off: the agents keep the walls they have
+        if (!wg.on()) return RCW_OK;
+        RCW_HIP(replace_buffers(h, {&wg.agents}));
+        wg.dev = RcwWallBank{}; wg.par = RcwWallGen{};
+        return RCW_OK;
+    }
+    const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
+    rc = plan_wall_generator(H, W, levels, first_level); if (rc) return rc;
+    if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_generator: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
+    const size_t B = (size_t)h->B;
+    RcwBuf fresh;
+    {
+        const hipError_t e = fresh.hipMalloc(3 * B * sizeof(uint32_t) + B);
+        if (e != hipSuccess) return fail(hip_code(e), "wall generator: %s", hip_failure(e));
+    }
+    RCW_HIP(replace_buffers(h, {&wg.agents}, {&fresh}));
+    uint32_t* const q = wg.agents.get<uint32_t>();
+    wg.dev = RcwWallBank{0, nullptr, nullptr, q, reinterpret_cast<int32_t*>(q + B), reinterpret_cast<int32_t*>(q + 2 * B), reinterpret_cast<uint8_t*>(q + 3 * B)};
+    wg.par = RcwWallGen{loops, levels, first_level, level_seed, (H - 1) / 2, (W - 1) / 2};
+    RCW_HIP(hipMemsetAsync(wg.agents.get(), 0, 3 * B * sizeof(uint32_t) + B, h->stream));
+    RCW_HIP(hipMemcpyAsync(wg.dev.status_seen, h->d_status.get(), B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    h->step.reset(false, false, h->dev.auto_reset != 0);
+    RCW_HIP(rcw_launch_reset(h->dev, nullptr, h->stream));             // the counters move by one ...
+    RCW_HIP(launch_wall_bank(h, true));                                // ... and every agent starts that episode in a maze of its own making
+    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));
+    return RCW_OK;
+}
+
+int rcw_wall_generator_info(rcw_handle* h, int32_t* enabled, uint32_t* loops, int32_t* levels, int32_t* first_level, uint64_t* level_seed)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    const RcwWallGen& g = h->gen.par;                                  // (zeros while the generator is off)
+    if (enabled) *enabled = h->gen.on() ? 1 : 0;
+    if (loops) *loops = g.loops;
+    if (levels) *levels = g.levels;
+    if (first_level) *first_level = g.first_level;
+    if (level_seed) *level_seed = g.level_seed;
     return RCW_OK;
 }
 

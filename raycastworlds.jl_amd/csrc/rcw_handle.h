@@ -196,6 +196,15 @@ struct rcw_handle {
         uint64_t total_weight = 0;
         bool on() const { return words.get() != nullptr; }
     } bank;
+    // The wall generator (rcw_set_wall_generator): the bank's per-agent arrays (one allocation, the same order) and the parameters, which
+    // travel as kernel arguments.  It and the bank exclude each other; `drawn()` is whichever is on.
+    struct WallGen {
+        RcwBuf agents;
+        RcwWallBank dev{};
+        RcwWallGen par{};
+        bool on() const { return agents.get() != nullptr; }
+    } gen;
+    const RcwWallBank* drawn() const { return bank.on() ? &bank.dev : gen.on() ? &gen.dev : nullptr; }
     ~rcw_handle();
 };
 
@@ -235,6 +244,7 @@ int plan_learner_view(const rcw_config& cfg, const RcwDev& dev, int32_t format, 
                       int32_t frames, ViewPlan* plan);
 int plan_local_map(int32_t source, int32_t size, int32_t cells_per_tile, bool real64, std::vector<unsigned char>* table);
 int plan_wall_bank_weights(const uint32_t* weights, int32_t layouts, uint32_t* cum, uint64_t* total);
+int plan_wall_generator(int32_t H, int32_t W, int32_t levels, int32_t first_level);
 
 // ---- rcw_step.hip: what a step, a reset or a re-render launches, and the resources those launches need ---------------------------------
 hipError_t launch_top_view_alone(rcw_handle* h, const uint8_t* mask_dev);

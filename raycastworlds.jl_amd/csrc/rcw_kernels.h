@@ -228,3 +228,15 @@ hipError_t rcw_launch_wall_bank(const RcwPlan& p, const RcwWallBank& bank, bool 
 // The camera view (p.obs) of the agents with mask[a] != 0 from p.col_h / p.col_c, a workgroup an agent: the repaint behind rcw_launch_wall_bank,
 // whose mask is sparse — the camera fill's pixels, without its sweep over the whole batch.
 hipError_t rcw_launch_wall_bank_paint(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);
+
+// The wall generator (rcw_set_wall_generator, rcw_wall_bank.hip): a maze made in LDS where the bank copies one.  The per-agent arrays are an
+// RcwWallBank's (layouts 0, words and cum NULL); the parameters are kernel arguments, fixed at install.
+struct RcwWallGen {
+    uint32_t loops;              // a non-tree edge is opened where the high word of its draw is below this
+    int32_t levels, first_level; // levels == 0: a maze of its own every episode; else level first_level + below(u, levels)
+    uint64_t level_seed;
+    int32_t ni, nj;              // the cell grid: (H - 1) / 2 by (W - 1) / 2, ni * nj <= kWallGenMaxCells
+};
+constexpr int kWallGenMaxCells = 4096;
+// Where rcw_launch_wall_bank goes on a handle with a generator: the same contract (counter moved or force -> a maze and a fresh state, mask[a]).
+hipError_t rcw_launch_wall_generator(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, bool force, hipStream_t s);

@@ -2,6 +2,7 @@
 // Host code in this file that does floating point follows the reference operation for
 // operation and must be compiled with -ffp-contract=off (see Makefile).
 #include "rcw_handle.h"
+#include "rcw_rng.h"
 
 #include <algorithm>
 #include <cmath>
@@ -438,6 +439,76 @@ int plan_wall_bank_weights(const uint32_t* weights, int32_t layouts, uint32_t* c
     }
     if (sum == 0) return fail(RCW_ERR_INVALID_ARGUMENT, "the wall bank's weights sum to zero: no layout could be drawn");
     *total = sum;
+    return RCW_OK;
+}
+
+// ---- the wall generator (include/rcw.h, "the wall generator") ---------------------------------------------------------------------------
+// What rcw_set_wall_generator checks of a geometry and a level range before anything is queued — or the refusal.
+int plan_wall_generator(int32_t H, int32_t W, int32_t levels, int32_t first_level)
+{
+    if (H < 5 || W < 5) return fail(RCW_ERR_INVALID_ARGUMENT, "the wall generator needs a map of at least 5 x 5 tiles (this one is %d x %d)", H, W);
+    if (levels < 0 || first_level < 0 || (int64_t)first_level + (int64_t)levels > 2147483647ll)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "the wall generator's level range must satisfy levels >= 0, first_level >= 0 and first_level + levels <= 2^31 - 1 (got first_level %d, levels %d)", first_level, levels);
+    const int64_t cells = (int64_t)((H - 1) / 2) * (int64_t)((W - 1) / 2);
+    if (cells > kWallGenMaxCells)
+        return fail(RCW_ERR_UNSUPPORTED, "the wall generator makes mazes of at most %d cells (maps up to 129 x 129); %d x %d has %lld", kWallGenMaxCells, H, W, (long long)cells);
+    return RCW_OK;
+}
+
+// The two handle-less exports: the rule once more on the host, for replay and evaluation — and, inside the library, a second implementation
+// beside the device's Boruvka: plain Kruskal, the edges sorted by their order words, union-find with path halving.
+extern "C" int rcw_wall_generator_key(uint64_t seed, int32_t global_agent, uint32_t episode, int32_t levels, int32_t first_level, uint64_t level_seed,
+                                      uint64_t* maze_key, int32_t* level)
+{
+    if (global_agent < 0 || levels < 0 || first_level < 0 || (int64_t)first_level + (int64_t)levels > 2147483647ll)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_wall_generator_key: global_agent >= 0, levels >= 0, first_level >= 0 and first_level + levels <= 2^31 - 1 are required");
+    const uint64_t u = rcw_draw(rcw_episode_key(seed, (uint64_t)global_agent, (uint64_t)episode), 0x8000000000000000ull);
+    int32_t l = -1;
+    uint64_t m = u;
+    if (levels > 0) {
+        l = first_level + (int32_t)rcw_below(u, (uint64_t)levels);
+        m = rcw_episode_key(level_seed, (uint64_t)l, 0ull);
+    }
+    if (maze_key) *maze_key = m;
+    if (level) *level = l;
+    return RCW_OK;
+}
+
+extern "C" int rcw_wall_generator_layout(int32_t H, int32_t W, uint64_t maze_key, uint32_t loops, uint8_t* out_host)
+{
+    if (!out_host) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (H < 5 || W < 5) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_wall_generator_layout: a maze needs at least 5 x 5 tiles (got %d x %d)", H, W);
+    const int64_t ni = (H - 1) / 2, nj = (W - 1) / 2, C = ni * nj;
+    if (2 * C >= (1ll << 20)) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_wall_generator_layout: edge ids must stay below 2^20 (%d x %d has %lld cells)", H, W, (long long)C);
+    std::vector<uint64_t> order;
+    std::vector<uint32_t> parent;
+    try { order.reserve((size_t)(2 * C)); parent.resize((size_t)C); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the maze's edges failed"); }
+    std::memset(out_host, 1, (size_t)H * (size_t)W);
+    auto open = [&](int64_t i, int64_t j) { out_host[(size_t)(i + (int64_t)H * j)] = 0; };   // tile (i, j), 0-based, in rcw_set_walls' order
+    auto passage = [&](uint64_t id) {
+        const int64_t c = (int64_t)(id >> 1), ci = c / nj, cj = c % nj;
+        if (id & 1) open(2 * ci + 2, 2 * cj + 1); else open(2 * ci + 1, 2 * cj + 2);
+    };
+    for (int64_t c = 0; c < C; ++c) {
+        const int64_t ci = c / nj, cj = c % nj;
+        parent[(size_t)c] = (uint32_t)c;
+        open(2 * ci + 1, 2 * cj + 1);
+        for (uint64_t id = 2 * (uint64_t)c; id < 2 * (uint64_t)c + 2; ++id) {
+            if ((id & 1) ? ci + 1 >= ni : cj + 1 >= nj) continue;
+            order.push_back((rcw_draw(maze_key, id) & 0xFFFFFFFFFFF00000ull) | id);
+            if ((uint32_t)(rcw_draw(maze_key, 2 * (uint64_t)C + id) >> 32) < loops) passage(id);   // (a tree edge too: it is opened either way)
+        }
+    }
+    std::sort(order.begin(), order.end());
+    auto find = [&](uint32_t x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
+    for (const uint64_t w : order) {
+        const uint64_t id = w & 0xFFFFFull;
+        const uint32_t c = (uint32_t)(id >> 1), d = c + ((id & 1) ? (uint32_t)nj : 1u);
+        const uint32_t rc = find(c), rd = find(d);
+        if (rc == rd) continue;
+        parent[rc] = rd;
+        passage(id);
+    }
     return RCW_OK;
 }
 

@@ -246,6 +246,7 @@ hipError_t launch_local_map(rcw_handle* h, StackOp op)
 // that installs the bank).  Behind rcw_reset the caller's re-render covers exactly those agents; behind a step, launch_step re-renders them.
 hipError_t launch_wall_bank(rcw_handle* h, bool force)
 {
+    if (h->gen.on()) return rcw_launch_wall_generator(h->dev, h->gen.dev, h->gen.par, force, h->stream);   // (the generator: a maze made where the bank copies one)
     return h->bank.on() ? rcw_launch_wall_bank(h->dev, h->bank.dev, force, h->stream) : hipSuccess;
 }
 
@@ -255,11 +256,12 @@ hipError_t launch_wall_bank(rcw_handle* h, bool force)
 // final world.  A handle without a bank launches what it launched before.
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op)
 {
-    const bool bank = h->bank.on() && actions_dev != nullptr;
+    const RcwWallBank* const drawn = h->drawn();                           // (the bank's per-agent arrays, or the generator's)
+    const bool bank = drawn != nullptr && actions_dev != nullptr;
     if (!h->learner.only()) {
         hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
         if (e == hipSuccess && bank) e = launch_wall_bank(h, false);
-        if (e == hipSuccess && bank) e = launch_step_camera(h, nullptr, h->bank.dev.mask, true);
+        if (e == hipSuccess && bank) e = launch_step_camera(h, nullptr, drawn->mask, true);
         if (e == hipSuccess && h->learner.on()) e = launch_view(h, mask_dev, op);
         if (e == hipSuccess) e = launch_goal_distance(h, mask_dev, op);
         if (e == hipSuccess) e = launch_seen_map(h, mask_dev, op);
@@ -273,7 +275,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     h->step.columns_cast(mask_dev != nullptr);
     // (RCW_VIEW_ONLY: nothing is rendered yet — the bank's kernel and the restarted agents' cast go right here, and the top view and the
     // view kernel below render every agent once; the two launches count into cast_ms of a handle that has a bank)
-    if (bank && ((e = launch_wall_bank(h, false)) != hipSuccess || (e = rcw_launch_cast(h->dev, nullptr, h->bank.dev.mask, h->stream)) != hipSuccess)) return e;
+    if (bank && ((e = launch_wall_bank(h, false)) != hipSuccess || (e = rcw_launch_cast(h->dev, nullptr, drawn->mask, h->stream)) != hipSuccess)) return e;
     if ((e = prof.mark(1, h->stream)) != hipSuccess) return e;
     if (h->dev.top_view && (e = launch_top_view_alone(h, mask_dev)) != hipSuccess) return e;
     if ((e = prof.mark(2, h->stream)) != hipSuccess) return e;

@@ -1,5 +1,6 @@
 // The wall bank (include/rcw.h, rcw_set_wall_bank): L wall layouts resident on the device, one of them drawn for an agent at every start of
-// an episode.  Three kernels; nothing else of the library knows about the bank.
+// an episode.  Three kernels; nothing else of the library knows about the bank.  The wall generator's kernel (further down) lives here too:
+// it shares the bank's tail.
 //
 // rcw_wall_bank_pack_kernel   once per rcw_set_wall_bank: the layouts, UInt8 (H*W, L) as rcw_set_walls takes them, into the tile map's own
 //          word format — nwords uint32 a layout, 16 tiles a word, bit 0 of each 2-bit field = WALL, the GOAL bits and the padding past H*W
@@ -45,6 +46,29 @@ __global__ void rcw_wall_bank_pack_kernel(const uint8_t* __restrict__ walls, uin
     words[g] = word;
 }
 
+// The tail the bank's kernel and the generator's share, behind a barrier: the episode's layout (WALL bits, nothing else) lies in lds_w.
+// Lane 0 takes back the discarded reset's status, puts the counter back to e = ep - 1 and runs reset_agent against the LDS words; then the
+// wave copies them over the agent's tile map.  k: what wall_layout[a] says.
+template <typename T>
+__device__ __forceinline__ void restart_on_lds_words(const RcwDev& p, const RcwLimit& lim, const RcwWallBank& b, int a, int lane, uint32_t* lds_w,
+                                                     uint32_t ep, int k)
+{
+    if (lane == 0) {
+        if (p.status[a] == RCW_WARN_SAMPLER_GAVE_UP && b.status_seen[a] != RCW_WARN_SAMPLER_GAVE_UP) p.status[a] = 0;
+        p.episode[a] = ep - 1u;
+        reset_agent<T>(p, a, lds_w, nullptr);                              // (reads the counter back: e; leaves e + 1)
+        lim.episode_steps[a] = 0u;
+        lim.truncated[a] = 0;
+        b.status_seen[a] = p.status[a];
+        b.layout[a] = k;
+        b.last_episode[a] = ep;
+        b.mask[a] = 1;
+    }
+    __syncthreads();
+    uint32_t* const tm = p.tile_map + (size_t)a * (size_t)p.nwords;
+    for (int w = lane; w < p.nwords; w += kBankBlock) tm[w] = lds_w[w];
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBankBlock) void rcw_wall_bank_kernel(const RcwDev p, const RcwLimit lim, const RcwWallBank b, const int force)
 {
@@ -70,20 +94,129 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_bank_kernel(const RcwDev 
     const uint32_t* const src = b.words + (size_t)k * (size_t)p.nwords;
     for (int w = lane; w < p.nwords; w += kBankBlock) lds_b[w] = src[w];
     __syncthreads();
-    if (lane == 0) {
-        if (p.status[a] == RCW_WARN_SAMPLER_GAVE_UP && b.status_seen[a] != RCW_WARN_SAMPLER_GAVE_UP) p.status[a] = 0;
-        p.episode[a] = e;
-        reset_agent<T>(p, a, lds_b, nullptr);                              // (reads the counter back: e; leaves e + 1)
-        lim.episode_steps[a] = 0u;
-        lim.truncated[a] = 0;
-        b.status_seen[a] = p.status[a];
-        b.layout[a] = k;
-        b.last_episode[a] = ep;
-        b.mask[a] = 1;
+    restart_on_lds_words<T>(p, lim, b, a, lane, lds_b, ep, k);
+}
+
+// ---- the wall generator (include/rcw.h, "the wall generator") ---------------------------------------------------------------------------
+// rcw_wall_generator_kernel<T>   the bank's kernel with another layout source: the same launch point, the same common path (two loads, one
+//          byte, exit), the same tail.  An agent that began an episode gets the maze of one 64-bit key m, made by the whole wave in LDS:
+//            words   [nwords]  the tile map's words: every tile WALL, then the cells' bits cleared (ds_and);
+//            slot    [C]       per label the smallest order word of an edge leaving it this round (ds_min_u64), then its hook;
+//            label   [C]       per cell the cell that names its component (label[root] == root);
+//          C = ni * nj cells, cell c = ci * nj + cj on tile (2 ci + 1, 2 cj + 1) (0-based), lane takes cells lane + 64 i.
+//          The tree is the minimum spanning tree under the order words w(id) = (draw(m, id) & ~0xFFFFF) | id — distinct, so the tree is
+//          unique and Boruvka finds the one Kruskal finds.  A round:
+//            offer   every cell offers the order words of its east (id 2c) and south (id 2c + 1) edge, where the edge joins two labels, to
+//                    both labels' slots;
+//            pick    every root with an offer opens the winning edge's passage tile and leaves in its slot the label across it;
+//            hook    ... and hangs itself under that label — of two roots that picked each other (the same edge: the only cycle distinct
+//                    words allow) the smaller stays a root;
+//            jump    label[c] = label[label[c]] until nothing moves; one label left: done.  Every round at least halves the labels:
+//                    at most ceil(log2 C) rounds.
+//          Then one pass over the edges opens those whose loop draw (index 2C + id, high word) is below `loops` (tree edges are open
+//          already: clearing a clear bit changes nothing).  Every barrier is the wave's own (a 64-thread workgroup), every condition around
+//          one is uniform: the agent, the round's counts (__syncthreads_or / _count) and kernel arguments.
+__device__ __forceinline__ void open_tile(uint32_t* words, int t) { atomicAnd(&words[t >> 4], ~(1u << ((t & 15) * 2))); }
+
+template <typename T>
+__global__ __launch_bounds__(kBankBlock) void rcw_wall_generator_kernel(const RcwDev p, const RcwLimit lim, const RcwWallBank b, const RcwWallGen g, const int force)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_g[];
+    const int a = blockIdx.x, lane = threadIdx.x;
+    if (a >= p.B) return;
+    const uint32_t ep = p.episode[a];
+    if (!force && b.last_episode[a] == ep) {
+        if (lane == 0) b.mask[a] = 0;
+        return;
+    }
+    const int H = p.H, nwords = p.nwords, HW = p.H * p.W, ni = g.ni, nj = g.nj, C = ni * nj;
+    uint32_t* const words = lds_g;
+    unsigned long long* const slot = reinterpret_cast<unsigned long long*>(lds_g + ((nwords + 1) & ~1));   // (8-byte aligned)
+    uint32_t* const label = reinterpret_cast<uint32_t*>(slot + C);
+    // the maze's key: the episode's own draw 2^63 (the bank's index), or the key of the level it picks
+    const uint64_t key = rcw_episode_key(p.seed, (uint64_t)(p.agent_id_offset + a), (uint64_t)(ep - 1u));
+    const uint64_t u = rcw_draw(key, kLayoutDraw);
+    int level = -1;
+    uint64_t m = u;
+    if (g.levels > 0) {
+        level = g.first_level + (int)rcw_below(u, (uint64_t)g.levels);
+        m = rcw_episode_key(g.level_seed, (uint64_t)level, 0ull);
+    }
+    for (int w = lane; w < nwords; w += kBankBlock) {
+        const int left = HW - 16 * w;                                      // tiles of this word inside the map (the padding stays clear)
+        words[w] = left >= 16 ? 0x55555555u : left <= 0 ? 0u : (0x55555555u & ((1u << (2 * left)) - 1u));   // (nwords is even: a whole word may be padding)
+    }
+    for (int c = lane; c < C; c += kBankBlock) label[c] = (uint32_t)c;
+    __syncthreads();
+    for (int c = lane; c < C; c += kBankBlock) {
+        const int ci = c / nj, cj = c - ci * nj;
+        open_tile(words, (2 * ci + 1) + H * (2 * cj + 1));
+    }
+    constexpr unsigned long long kNone = ~0ull;
+    for (int round = 0; round < 13 && C > 1; ++round) {                    // (C <= 4096: 12 rounds at most; the count below ends it sooner)
+        for (int c = lane; c < C; c += kBankBlock) slot[c] = kNone;
+        __syncthreads();
+        for (int c = lane; c < C; c += kBankBlock) {                       // offer
+            const int ci = c / nj, cj = c - ci * nj;
+            const uint32_t la = label[c];
+            if (cj + 1 < nj) {
+                const uint32_t lb = label[c + 1];
+                if (la != lb) {
+                    const unsigned long long id = 2ull * (unsigned)c;
+                    const unsigned long long w = (rcw_draw(m, id) & 0xFFFFFFFFFFF00000ull) | id;
+                    atomicMin(&slot[la], w); atomicMin(&slot[lb], w);
+                }
+            }
+            if (ci + 1 < ni) {
+                const uint32_t lb = label[c + nj];
+                if (la != lb) {
+                    const unsigned long long id = 2ull * (unsigned)c + 1ull;
+                    const unsigned long long w = (rcw_draw(m, id) & 0xFFFFFFFFFFF00000ull) | id;
+                    atomicMin(&slot[la], w); atomicMin(&slot[lb], w);
+                }
+            }
+        }
+        __syncthreads();
+        for (int c = lane; c < C; c += kBankBlock) {                       // pick: the roots' winning edges are opened, the slot takes the label across
+            if (label[c] != (uint32_t)c) continue;
+            const unsigned long long w = slot[c];
+            if (w == kNone) { slot[c] = (unsigned long long)c; continue; }
+            const int id = (int)(w & 0xFFFFFull), ec = id >> 1, ed = ec + ((id & 1) ? nj : 1);
+            const int ci = ec / nj, cj = ec - ci * nj;
+            open_tile(words, (id & 1) ? (2 * ci + 2) + H * (2 * cj + 1) : (2 * ci + 1) + H * (2 * cj + 2));
+            const uint32_t la = label[ec], lb = label[ed];
+            slot[c] = (unsigned long long)(la == (uint32_t)c ? lb : la);
+        }
+        __syncthreads();
+        for (int c = lane; c < C; c += kBankBlock) {                       // hook (only roots' labels are written, only slots are read)
+            if (label[c] != (uint32_t)c) continue;
+            const uint32_t o = (uint32_t)slot[c];
+            if (o != (uint32_t)c && !((uint32_t)slot[o] == (uint32_t)c && (uint32_t)c < o)) label[c] = o;
+        }
+        __syncthreads();
+        for (;;) {                                                         // jump: any value read is an ancestor, so the race within the wave is benign
+            int moved = 0;
+            for (int c = lane; c < C; c += kBankBlock) {
+                const uint32_t q = label[c], qq = label[q];
+                if (qq != q) { label[c] = qq; moved = 1; }
+            }
+            if (!__syncthreads_or(moved)) break;
+        }
+        int apart = 0;
+        const uint32_t l0 = label[0];
+        for (int c = lane; c < C; c += kBankBlock) apart |= (label[c] != l0) ? 1 : 0;
+        if (!__syncthreads_or(apart)) break;
+    }
+    if (g.loops != 0u) {
+        for (int c = lane; c < C; c += kBankBlock) {
+            const int ci = c / nj, cj = c - ci * nj;
+            const unsigned long long id = 2ull * (unsigned)c, base = 2ull * (unsigned)C;
+            if (cj + 1 < nj && (uint32_t)(rcw_draw(m, base + id) >> 32) < g.loops) open_tile(words, (2 * ci + 1) + H * (2 * cj + 2));
+            if (ci + 1 < ni && (uint32_t)(rcw_draw(m, base + id + 1ull) >> 32) < g.loops) open_tile(words, (2 * ci + 2) + H * (2 * cj + 1));
+        }
     }
     __syncthreads();
-    uint32_t* const tm = p.tile_map + (size_t)a * (size_t)p.nwords;
-    for (int w = lane; w < p.nwords; w += kBankBlock) tm[w] = lds_b[w];
+    restart_on_lds_words<T>(p, lim, b, a, lane, words, ep, level);
 }
 
 // The camera view of the agents the bank restarted (mask[a] != 0), from their fresh column descriptors: update_camera_view!'s column fill
@@ -132,5 +265,16 @@ hipError_t rcw_launch_wall_bank(const RcwPlan& p, const RcwWallBank& bank, bool 
     const size_t lds = (size_t)p.nwords * sizeof(uint32_t);                 // at most 16 KiB: the largest map rcw_create accepts has 4080 words
     if (p.real64) hipLaunchKernelGGL(rcw_wall_bank_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, bank, force ? 1 : 0);
     else          hipLaunchKernelGGL(rcw_wall_bank_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, bank, force ? 1 : 0);
+    return hipGetLastError();
+}
+
+// LDS: the words (rounded to an even count), 8 bytes a slot and 4 a label: at the 4096-cell bound 48 KiB + at most 4.1 KiB of words (129 x 129).
+hipError_t rcw_launch_wall_generator(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, bool force, hipStream_t s)
+{
+    const int cells = gen.ni * gen.nj;
+    if (p.B < 1 || cells < 1 || cells > kWallGenMaxCells) return cells > kWallGenMaxCells ? hipErrorInvalidValue : hipSuccess;
+    const size_t lds = (size_t)((p.nwords + 1) & ~1) * sizeof(uint32_t) + (size_t)cells * 12u;
+    if (p.real64) hipLaunchKernelGGL(rcw_wall_generator_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, force ? 1 : 0);
+    else          hipLaunchKernelGGL(rcw_wall_generator_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, force ? 1 : 0);
     return hipGetLastError();
 }

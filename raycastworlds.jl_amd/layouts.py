@@ -1,4 +1,5 @@
-"""Wall layouts for `SingleRoom.set_walls`: host-side numpy, nothing here touches the device.
+"""Wall layouts for `SingleRoom.set_walls`: host-side numpy, nothing here touches the device (`generated_maze` and
+`generated_maze_key` call the library's two handle-less host functions: no device either).
 
 A layout is bool (H, W) with `walls[i-1, j-1]` = tile (i, j) is a WALL — the index order of `env.world.tile_map[b, 0]`.
 Every generator returns the wall ring (SR:57-60) closed, as `rcw_set_walls` requires, and at least two free interior
@@ -67,6 +68,51 @@ def maze(H: int, W: int, rng) -> np.ndarray:
         seen[ci, cj] = True
         stack.append((ci, cj))
     return w
+
+
+def loops_word(loops) -> int:
+    """The wall generator's `loops` as the UInt32 the rule compares with: a probability in [0, 1] scaled with
+    min(int(p * 2^32), 2^32 - 1) (an int is taken as the word itself)."""
+    if isinstance(loops, (int, np.integer)) and not isinstance(loops, bool):
+        word = int(loops)
+        if not 0 <= word <= 0xFFFFFFFF:
+            raise ValueError(f"loops as an integer is the UInt32 word itself: 0 .. 2^32 - 1, got {loops}")
+        return word
+    p = float(loops)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"loops is a probability in [0, 1], got {loops}")
+    return min(int(p * 2.0 ** 32), 0xFFFFFFFF)
+
+
+def generated_maze_key(seed: int, global_agent: int, episode: int, levels: int = 0, first_level: int = 0, level_seed: int = 0):
+    """(maze_key, level) of the wall generator (include/rcw.h, "the wall generator") for episode `episode` — the counter before
+    the increment, `env.world.episode - 1` of a running episode — of global agent `global_agent` under `seed`; level is -1
+    with `levels == 0`.  rcw_wall_generator_key: host arithmetic, no device."""
+    import ctypes as C
+
+    from . import _capi
+
+    lib = _capi.load()
+    key, level = C.c_uint64(), C.c_int32()
+    rc = lib.rcw_wall_generator_key(int(seed), int(global_agent), int(episode), int(levels), int(first_level), int(level_seed),
+                                    C.byref(key), C.byref(level))
+    if rc != _capi.RCW_OK:
+        raise ValueError(_capi.last_error(lib))
+    return key.value, level.value
+
+
+def generated_maze(maze_key: int, H: int, W: int, loops=0.0) -> np.ndarray:
+    """The wall generator's maze of one 64-bit key, bool (H, W): the minimum spanning tree of the cell grid under the key's
+    order words, plus the non-tree edges `loops` opens (a probability in [0, 1]; an int: the UInt32 word itself).
+    rcw_wall_generator_layout: host arithmetic (Kruskal), no device — what an agent's `env.world.walls[a]` holds."""
+    from . import _capi
+
+    lib = _capi.load()
+    out = np.empty((max(int(W), 0), max(int(H), 0)), dtype=np.uint8)   # tile (i, j), 0-based, at i + H j
+    rc = lib.rcw_wall_generator_layout(int(H), int(W), int(maze_key), loops_word(loops), out.ctypes.data)
+    if rc != _capi.RCW_OK:
+        raise ValueError(_capi.last_error(lib))
+    return np.ascontiguousarray(out.T != 0)
 
 
 def is_connected(walls) -> bool:

@@ -348,6 +348,8 @@ class SingleRoom:
     `seen_map` (this build's addition) `set_seen_map(True)` after that, `local_map` (this build's addition; an int — the size — or a dict
     of `set_local_map`'s keywords) `set_local_map` last.  `wall_bank` / `wall_bank_weights` (this build's addition) are `set_wall_bank`'s
     arguments, applied after `walls` and the time limit and before the features: a layout drawn on the device at every episode start.
+    `wall_generator` (this build's addition; a dict of `set_wall_generator`'s keywords, `{}` for the defaults) is applied in the same
+    place: a new maze made on the device at every episode start.  It and `wall_bank` exclude each other.
     """
 
     def __init__(
@@ -385,6 +387,7 @@ class SingleRoom:
         local_map=None,
         wall_bank=None,
         wall_bank_weights=None,
+        wall_generator=None,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -485,6 +488,12 @@ class SingleRoom:
         elif wall_bank_weights is not None:
             self._handle.close()
             raise ValueError("wall_bank_weights needs wall_bank")
+        if wall_generator is not None:
+            try:
+                self.set_wall_generator(**dict(wall_generator))
+            except BaseException:
+                self._handle.close()
+                raise
         if goal_distance:
             try:
                 self.set_goal_distance(True)
@@ -1115,6 +1124,40 @@ class SingleRoom:
         self._check(self._lib.rcw_wall_bank_info(self._h, C.byref(n), C.byref(t)))
         return {"layouts": n.value, "total_weight": t.value}
 
+    # ---- the wall generator (include/rcw.h, rcw_set_wall_generator) ---------------------
+    def set_wall_generator(self, loops=0.0, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
+        """A new maze made on the device at every start of an episode — `reset_`, a done or truncated restart under `auto_reset`, and
+        this call, which restarts every agent (episode counters + 1).  The maze is the minimum spanning tree of the odd sub-grid
+        (`layouts.maze`'s cells) under an order drawn from one 64-bit key, plus the non-tree edges `loops` opens — a probability in
+        [0, 1], scaled to UInt32 with min(int(p * 2^32), 2^32 - 1); 0 is a perfect maze.  `levels == 0`: the key is the episode's own,
+        every episode a maze of its own, `wall_layout` reads -1.  `levels >= 1`: the episode picks level
+        first_level + (0 .. levels - 1) and the maze is a function of (level_seed, level, H, W, loops) alone — a seeded range to train
+        on and a held-out one to evaluate on; `wall_layout` says which.  `layouts.generated_maze(*layouts.generated_maze_key(...))`
+        replays any of them on the host.  Maps of 5 x 5 to 129 x 129 (4096 cells).  `set_walls` and `set_wall_bank` are refused while
+        the generator is on; `set_wall_generator(None)` switches it off, the agents keep their walls.  An environment built with
+        `rng` draws its resets on the host and takes no generator."""
+        self.__dict__.pop("_wall_layout_dev", None)
+        if loops is None:
+            self._check(self._lib.rcw_set_wall_generator(self._h, 0, 0, 0, 0, 0))
+            return
+        if self.rng is not None:
+            raise ValueError("an environment built with rng draws its resets on the host: it takes no wall generator")
+        from . import layouts as _layouts
+
+        word = _layouts.loops_word(loops)
+        for name, v, top in (("levels", levels, 2 ** 31 - 1), ("first_level", first_level, 2 ** 31 - 1), ("level_seed", level_seed, 2 ** 64 - 1)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= top:
+                raise ValueError(f"{name} must be an integer in 0 .. {top}, got {v!r}")
+        self._check(self._lib.rcw_set_wall_generator(self._h, 1, word, int(levels), int(first_level), int(level_seed)))
+
+    @property
+    def wall_generator_info(self) -> dict:
+        """`enabled`, `loops` (the UInt32 word), `levels`, `first_level` and `level_seed` of the generator (rcw_wall_generator_info);
+        zeros while it is off."""
+        on, loops, levels, first, seed = C.c_int32(), C.c_uint32(), C.c_int32(), C.c_int32(), C.c_uint64()
+        self._check(self._lib.rcw_wall_generator_info(self._h, C.byref(on), C.byref(loops), C.byref(levels), C.byref(first), C.byref(seed)))
+        return {"enabled": bool(on.value), "loops": loops.value, "levels": levels.value, "first_level": first.value, "level_seed": seed.value}
+
     def _wall_layout_host(self) -> np.ndarray:
         out = np.empty(self.batch, dtype=np.int32)
         self.host_syncs += 1
@@ -1123,8 +1166,9 @@ class SingleRoom:
 
     @property
     def wall_layout(self) -> DeviceArray:
-        """int32 (B,) in device memory: the bank layout each agent's current episode was given (`.torch(sync=False)` on the GPU,
-        `np.asarray(env.wall_layout)` for a host copy).  Valid until the next `set_wall_bank`."""
+        """int32 (B,) in device memory: the bank layout each agent's current episode was given — with the wall generator its level, or
+        -1 — (`.torch(sync=False)` on the GPU, `np.asarray(env.wall_layout)` for a host copy).  Valid until the next `set_wall_bank`
+        or `set_wall_generator`."""
         if getattr(self, "_wall_layout_dev", None) is None:
             p = C.c_void_p()
             self._check(self._lib.rcw_wall_layout_device_ptr(self._h, C.byref(p)))
@@ -1363,6 +1407,8 @@ def reset_(env: SingleRoom, mask=None, seed: Optional[int] = None, rng=None) -> 
     if rng is not None:
         if env.wall_bank_info["layouts"]:
             raise ValueError("the environment draws its walls from a wall bank on the device: reset it with a seed, not an rng")
+        if env.wall_generator_info["enabled"]:
+            raise ValueError("the environment makes its walls with the wall generator on the device: reset it with a seed, not an rng")
         _reset_from_rng(env, rng, mask)
         return None
     if seed is not None:

@@ -1,0 +1,165 @@
+"""The wall generator (include/rcw.h, rcw_set_wall_generator) restated on the CPU — the specification, test infrastructure, not a test.
+
+A MAZE FROM ONE 64-BIT KEY, maze(m, H, W, loops) for H, W >= 5, with draw(m, n) of walls_ref.py (csrc/rcw_rng.h):
+
+    cells   the tiles with odd 0-based (i, j) inside the ring: ni = (H-1)//2, nj = (W-1)//2, C = ni nj, cell c = ci nj + cj on tile
+            (2ci+1, 2cj+1) — layouts.maze's grid; with an even H or W the last interior row or column stays wall
+    edges   east of c: id 2c, where cj+1 < nj, passage tile (2ci+1, 2cj+2); south of c: id 2c+1, where ci+1 < ni, passage (2ci+2, 2cj+1)
+    order   w(id) = (draw(m, id) & 0xFFFFFFFFFFF00000) | id — ids stay below 2^20, so the words are distinct
+    tree    the minimum spanning tree of the cell grid under w (unique); here: Kruskal by sorting w
+    loops   a non-tree edge is opened too where (draw(m, 2C + id) >> 32) < loops (UInt32; 0: a perfect maze)
+    every tile is WALL except the cells and the passage tiles of tree edges and opened edges
+
+THE KEY OF AN EPISODE, with g the global agent id and e the counter before the increment: key = episode_key(seed, g, e),
+u = draw(key, 2^63) — the bank's draw index.  levels == 0: m = u, wall_layout = -1.  levels >= 1: l = first_level + below(u, levels),
+m = episode_key(level_seed, l, 0), wall_layout = l.  After that the rule is the bank's: WALL := the maze, GOAL cleared, the reset of
+walls_ref.py against the new walls under `key` from draw 0, counter = e + 1 (once).
+
+WallGeneratorRef is WallsRef with that one override of _reset_agent, as WallBankRef is.  `events` also counts episode_starts, and
+`mazes_made` is the set of maze keys used so far.
+"""
+import numpy as np
+
+import walls_ref as WR
+from oracle import pyref
+
+LAYOUT_DRAW = 1 << 63
+ORDER_MASK = 0xFFFFFFFFFFF00000
+MAX_CELLS = 4096
+
+
+def loops_word(p):
+    """a probability in [0, 1] as the UInt32 the rule compares with"""
+    return min(int(float(p) * 2.0 ** 32), 0xFFFFFFFF)
+
+
+def grid(H, W):
+    ni, nj = (H - 1) // 2, (W - 1) // 2
+    return ni, nj, ni * nj
+
+
+def edges(H, W):
+    """every edge of the cell grid: (id, cell, other cell, passage tile (i, j) 0-based)"""
+    ni, nj, _ = grid(H, W)
+    out = []
+    for ci in range(ni):
+        for cj in range(nj):
+            c = ci * nj + cj
+            if cj + 1 < nj:
+                out.append((2 * c, c, c + 1, (2 * ci + 1, 2 * cj + 2)))
+            if ci + 1 < ni:
+                out.append((2 * c + 1, c, c + nj, (2 * ci + 2, 2 * cj + 1)))
+    return out
+
+
+def order_word(m, eid):
+    return (WR.draw(m, eid) & ORDER_MASK) | eid
+
+
+def tree_edges(m, H, W):
+    """the ids of the minimum spanning tree's edges: Kruskal, the edges sorted by their order words, a plain union-find"""
+    _, _, C = grid(H, W)
+    parent = list(range(C))
+
+    def find(x):
+        while parent[x] != x:
+            x = parent[x]
+        return x
+
+    took = []
+    for _, eid, a, b in sorted((order_word(m, e[0]), e[0], e[1], e[2]) for e in edges(H, W)):
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[ra] = rb
+            took.append(eid)
+    return took
+
+
+def maze(m, H, W, loops=0):
+    """bool (H, W), walls[i, j] 0-based = tile (i + 1, j + 1) is a WALL; loops is the UInt32 word"""
+    assert H >= 5 and W >= 5 and 0 <= loops <= 0xFFFFFFFF
+    ni, nj, C = grid(H, W)
+    assert 2 * C < (1 << 20)
+    w = np.ones((H, W), bool)
+    w[1:2 * ni:2, 1:2 * nj:2] = False
+    tree = set(tree_edges(m, H, W))
+    for eid, _, _, (i, j) in edges(H, W):
+        if eid in tree or (WR.draw(m, 2 * C + eid) >> 32) < loops:
+            w[i, j] = False
+    return w
+
+
+def maze_key(seed, global_agent, episode, levels=0, first_level=0, level_seed=0):
+    """(m, wall_layout) of the episode `episode` (the counter before the increment) of a global agent"""
+    assert levels >= 0 and first_level >= 0 and first_level + levels <= 2 ** 31 - 1
+    u = WR.draw(WR.episode_key(seed, global_agent, episode), LAYOUT_DRAW)
+    if levels == 0:
+        return u, -1
+    level = first_level + WR.below(u, levels)
+    return WR.episode_key(level_seed, level, 0), level
+
+
+def install_refusal(H, W, levels, first_level):
+    """what rcw_set_wall_generator says of a geometry and a level range: None, "invalid" or "unsupported" """
+    if H < 5 or W < 5 or levels < 0 or first_level < 0 or first_level + levels > 2 ** 31 - 1:
+        return "invalid"
+    return "unsupported" if grid(H, W)[2] > MAX_CELLS else None
+
+
+class WallGeneratorRef(WR.WallsRef):
+    def __init__(self, *args, **kw):
+        self.gen = None
+        super().__init__(*args, **kw)
+        self.wall_layout = np.zeros(self.B, np.int32)
+        self.events.update(episode_starts=0)
+        self.mazes_made = set()
+        self._cache = {}
+
+    # ---- the rule ------------------------------------------------------------------------------------------------------------------
+    def _reset_agent(self, b):
+        if self.gen is not None:
+            loops, levels, first_level, level_seed = self.gen
+            m, level = maze_key(self.seed, self.offset + b, int(self.episode[b]), levels, first_level, level_seed)
+            if m not in self._cache:
+                self._cache[m] = maze(m, self.H, self.W, loops)
+            walls = self._cache[m]
+            tm = self.worlds[b].tile_map
+            for i in range(1, self.H + 1):
+                for j in range(1, self.W + 1):
+                    tm[pyref.WALL][i][j] = bool(walls[i - 1, j - 1])
+                    tm[pyref.GOAL][i][j] = False
+            self.events["episode_starts"] += 1
+            self.mazes_made.add(m)
+            self.wall_layout[b] = level
+        super()._reset_agent(b)
+
+    # ---- the calls -----------------------------------------------------------------------------------------------------------------
+    def set_wall_generator(self, loops=0.0, levels=0, first_level=0, level_seed=0):
+        """rcw_set_wall_generator: install (every agent restarts under the rule with the current seed) or, loops None, switch off (walls
+        kept).  loops: a probability (float) or the UInt32 word (int)."""
+        if loops is None:
+            self.gen = None
+            return
+        assert install_refusal(self.H, self.W, levels, first_level) is None
+        word = int(loops) if isinstance(loops, (int, np.integer)) else loops_word(loops)
+        self.gen = (word, int(levels), int(first_level), int(level_seed))
+        self._cache = {}
+        self.reset()
+
+    def set_walls(self, walls, index=None, mask=None):
+        if self.gen is not None:
+            raise RuntimeError("rcw_set_walls is refused while the handle has a generator")
+        super().set_walls(walls, index, mask)
+
+    def snapshot(self):
+        return dict(super().snapshot(), wall_layout=self.wall_layout.copy())
+
+
+def assert_equal(env, ref, where=""):
+    """walls_ref.assert_equal plus wall_layout (while the reference has a generator: without one the engine refuses the getter)"""
+    r = ref if isinstance(ref, dict) else ref.snapshot()
+    WR.assert_equal(env, r, where)
+    if env.wall_generator_info["enabled"]:
+        got = env.wall_layout.numpy()
+        assert got.dtype == np.int32
+        np.testing.assert_array_equal(got, r["wall_layout"], err_msg=f"wall_layout {where}")

@@ -3,7 +3,7 @@
 configurations (map size, columns, headings, field of view, radius, step, camera height, image
 height, world-unit type, the three unpinned switches, both BoundsError policies, auto-reset).
 
-    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit|goal|bank]
+    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit|goal|bank|gen]
                                                                    # "top": every configuration renders the top view;
                                                                    # "split": ... with a geometry of the unit store kernels;
                                                                    # "flat": ... of the flat store kernel (any pu >= 9), and any
@@ -18,6 +18,9 @@ height, world-unit type, the three unpinned switches, both BoundsError policies,
                                                                    # "bank": the wall bank (rcw_set_wall_bank) — random maps, banks, weights and
                                                                    #         sequences of calls against tests/wall_bank_ref.py, the whole state, the
                                                                    #         frames and wall_layout compared after every call (bank_mode below)
+                                                                   # "gen": the wall generator (rcw_set_wall_generator) — random maps, loops, level
+                                                                   #         ranges and sequences of calls against tests/wall_generator_ref.py, compared
+                                                                   #         the same way (gen_mode below)
 """
 import os
 import sys
@@ -245,10 +248,107 @@ def bank_mode(n_cfg, seed):
     return 1 if fails else 0
 
 
+def gen_mode(n_cfg, seed):
+    """Maps of 5 x 5 to 40 x 40 tiles (up to 19 x 19 = 361 cells); loops 0, 0.1, 0.5 or 1; no levels, or 1, 2 or 5 levels from a random first
+    level under a random level seed; 1 to 9 agents with 8 or 16 view columns (the reference renders in Python), Float32 and Float64, both
+    forms of the step asked for, a time limit of 0, 2 or 5, auto_reset.  Then 30 random calls — a step, a masked or full reset_ with a new
+    seed, a masked set_state onto free tiles of each agent's current maze, the generator off and another one on —, each made on the
+    reference (tests/wall_generator_cases.py's Recorder) and on the engine (its Player), which compares the whole state, the frames, the
+    time limit's words and wall_layout after every call.  Every configuration draws from default_rng([seed, c])."""
+    import wall_generator_cases as GC
+    from raycastworlds_jl_amd import _capi
+
+    rng = None
+
+    def generator():
+        levels = int(rng.choice([0, 0, 1, 2, 5]))
+        return dict(loops=float(rng.choice([0.0, 0.0, 0.1, 0.5, 1.0])), levels=levels, first_level=int(rng.integers(0, 2**31 - 1 - levels)) if levels else 0,
+                    level_seed=int(rng.integers(0, 2**63)) if levels else 0)
+
+    def some(B):
+        mask = (rng.random(B) < 0.5).astype(np.uint8)
+        mask[int(rng.integers(0, B))] = 1
+        return mask
+
+    totals = dict(step=0, reset=0, masked_reset=0, set_state=0, off_and_on=0, episode_starts=0, goal_redraws=0, restarts_after_done=0,
+                  restarts_after_truncation=0, one_launch_steps=0, two_launch_steps=0, even_sizes=0, with_levels=0, with_loops=0, cells_past_64=0)
+    fails = 0
+    for c in range(n_cfg):
+        rng = np.random.default_rng([seed, c])
+        H, W = int(rng.integers(5, 41)), int(rng.integers(5, 41))
+        if c % 4 == 0:
+            H, W = int(rng.integers(5, 9)), int(rng.integers(5, 9))          # (a quarter small: agents arrive, restarts after done)
+        B = int(rng.integers(1, 10))
+        T64, L = bool(rng.integers(0, 2)), int(rng.choice([0, 2, 5]))
+        N, Hc = [(8, 64), (16, 64), (8, 24), (16, 128)][int(rng.integers(0, 4))]
+        form = str(rng.choice(["one-launch", "two-launches"]))
+        engine_seed = int(rng.integers(0, 2**31))
+        shape = dict(H=H, W=W, N=N, Hc=Hc, B=B, seed=engine_seed, T="Float64" if T64 else "Float32")
+        where = f"config {c}: {H} x {W}, B={B} T64={T64} L={L} N={N} Hc={Hc} {form} seed={engine_seed}"
+        try:
+            env = GC.make_env(RCW, shape)
+            try:
+                env.set_step_form(form)
+            except _capi.RcwError as e:
+                assert form == "one-launch" and e.code == _capi.RCW_ERR_UNSUPPORTED and "does not take the one-launch step" in e.message, e
+                form = "two-launches"
+            totals["one_launch_steps" if form == "one-launch" else "two_launch_steps"] += 1
+            totals["even_sizes"] += int(H % 2 == 0 or W % 2 == 0)
+            totals["cells_past_64"] += int(((H - 1) // 2) * ((W - 1) // 2) > 64)
+            rec = GC.Recorder(shape)
+            play = GC.Player(RCW, env, rec.snaps, where)
+            both = lambda call, *a, **k: (getattr(rec, call)(*a, **k), getattr(play, call)(*a, **k))
+            if L:
+                both("set_time_limit", L)
+
+            def install():
+                g = generator()
+                totals["with_levels"] += int(g["levels"] > 0)
+                totals["with_loops"] += int(g["loops"] > 0)
+                both("set_wall_generator", **g)
+
+            install()
+            for k in range(30):
+                call = str(rng.choice(["step", "step", "step", "step", "step", "step", "reset", "masked_reset", "set_state", "off_and_on"]))
+                play.name = f"{where}, call {k} ({call})"
+                totals[call] += 1
+                if call == "step":
+                    both("step", rng.integers(1, 5, B).astype(np.uint8))
+                elif call in ("reset", "masked_reset"):
+                    both("reset", some(B) if call == "masked_reset" else None, int(rng.integers(0, 2**31)))
+                elif call == "set_state":
+                    mask, s = some(B), rec.snaps[-1]
+                    goal, pos, heading = s["goal"].copy(), s["position"].copy(), s["direction"].copy()
+                    for b in np.flatnonzero(mask):
+                        free = np.argwhere(~rec.ref.walls_of(b))
+                        goal[b] = free[int(rng.integers(0, len(free)))] + 1
+                        pos[b] = free[int(rng.integers(0, len(free)))] + 0.5
+                        heading[b] = int(rng.integers(0, 8))
+                    both("set_state", goal, pos, heading, mask)
+                else:
+                    both("set_wall_generator", None)
+                    both("step", rng.integers(1, 5, B).astype(np.uint8))
+                    install()
+            play.finished()
+            for k, v in rec.events.items():
+                if k in totals:
+                    totals[k] += v
+            env.close()
+        except Exception as e:   # noqa: BLE001
+            fails += 1
+            print(f"{where} FAILED\n   {type(e).__name__}: {str(e)[:400]}")
+            if fails >= 5:
+                break
+    print(f"{n_cfg} random configurations (wall generator: " + ", ".join(f"{v} {k}" for k, v in totals.items()) + f"), {fails} mismatches")
+    return 1 if fails else 0
+
+
 if len(sys.argv) > 3 and sys.argv[3] == "goal":
     sys.exit(goal_mode(n_cfg, int(sys.argv[2])))
 if len(sys.argv) > 3 and sys.argv[3] == "bank":
     sys.exit(bank_mode(n_cfg, int(sys.argv[2])))
+if len(sys.argv) > 3 and sys.argv[3] == "gen":
+    sys.exit(gen_mode(n_cfg, int(sys.argv[2])))
 limit_events = {}
 one_launch_steps = 0
 two_kernel_forms = 0                                            # (rcw_set_top_view_form: by default it is taken only from 256 MiB a step)
