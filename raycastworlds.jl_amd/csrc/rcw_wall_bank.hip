@@ -268,7 +268,9 @@ hipError_t rcw_launch_wall_bank(const RcwPlan& p, const RcwWallBank& bank, bool 
     return hipGetLastError();
 }
 
-// LDS: the words (rounded to an even count), 8 bytes a slot and 4 a label: at the 4096-cell bound 48 KiB + at most 4.1 KiB of words (129 x 129).
+// LDS: the words (rounded to an even count), 8 bytes a slot and 4 a label: at the 4096-cell bound 48 KiB + the map's words.  A square map has
+// the fewest (129 x 129: 1042, 4.1 KiB), a thin one the most: 2 x 2048 cells lie on 5 x 4097 (1282 words) and, with the last interior row
+// and column left wall, on 6 x 4098 — 1538 words, 6.0 KiB, the largest request: 55,304 bytes, under the 64 KiB default.
 hipError_t rcw_launch_wall_generator(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, bool force, hipStream_t s)
 {
     const int cells = gen.ni * gen.nj;

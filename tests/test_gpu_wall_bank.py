@@ -31,7 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # ---- the rollouts -----------------------------------------------------------------------------------------------------------------
 ROLLOUTS = [("small", "two-launches"), ("small", "one-launch"), ("square_one", None), ("square_zero_weight", None), ("big", "two-launches"),
-            ("big", "one-launch"), ("f64", None), ("calls", "two-launches"), ("calls", "one-launch")]
+            ("big", "one-launch"), ("f64", None), ("calls", "two-launches"), ("calls", "one-launch"), ("edge", None)]
 
 
 @pytest.mark.parametrize("name,form", ROLLOUTS, ids=[f"{n}-{f or 'auto'}" for n, f in ROLLOUTS])
@@ -46,6 +46,9 @@ def test_a_scenario_against_the_reference_after_every_call(rcw, name, form):
     if name == "big":
         assert env.world.tile_map_chunks.shape[1] * 2 > 64                    # more tile-map words than a wavefront has lanes
         assert max(events["layouts_drawn"]) >= 64
+    if name == "edge":                                                        # the largest map a handle takes: 64 passes of the copy loops, 15.8 KiB of LDS
+        assert env.world.tile_map_chunks.shape[1] * 2 == 4050 == 64 * 64 - 46
+        assert events["layouts_drawn"] == {0, 2} and events["restarts_after_done"] > 0 and events["restarts_after_truncation"] > 0
     env.close()
 
 

@@ -5,6 +5,12 @@ them: the goal distance's words and fields (which never read -1: every maze is c
 from the seen map and the 4-frame stack in the `features` scenario.  tests/test_wall_generator_spec.py rehearses every scenario on the CPU
 and asserts from the reference's counts that it reaches restarts of both kinds and goal redraws.
 
+AT THE SIZE BOUND (4096 cells: 64 cells a lane, 48 KiB of slots and labels beside the words): the `huge` script at 129 x 129, 130 x 130,
+5 x 4097, 4097 x 5 and 6 x 4098 — all recorded WITH frames, the reference takes a second or two each; 129 x 129 in both step forms, the
+one-launch step with 64 camera rows (`edge_rows64`: it does not take the 24 of the others) —; the hardest mazes a search with
+the model of the kernel's rounds finds (wall_generator_ref.boruvka), installed through levels=1; and 1031 agents, more workgroups than the
+device holds at once.
+
 The `small` scenario is the issue's own (67 agents x 320 rays, 30 steps): its reference takes some ten seconds of Python ray casting, once,
 shared by the two step forms.  Every export is missing from the build before this feature: each test here fails there.
 """
@@ -50,7 +56,8 @@ class NeverLost:
 
 # ---- the rollouts -----------------------------------------------------------------------------------------------------------------
 ROLLOUTS = [("small", "two-launches"), ("small", "one-launch"), ("square", None), ("big", "two-launches"), ("big", "one-launch"), ("wide", None),
-            ("huge", None), ("f64", None), ("levels", None), ("calls", "two-launches"), ("calls", "one-launch")]
+            ("huge", None), ("f64", None), ("levels", None), ("calls", "two-launches"), ("calls", "one-launch"),
+            ("edge", "two-launches"), ("edge_rows64", "one-launch"), ("edge_even", None), ("thin", None), ("tall", None), ("thin_even", None)]
 
 
 @pytest.mark.parametrize("name,form", ROLLOUTS, ids=[f"{n}-{f or 'auto'}" for n, f in ROLLOUTS])
@@ -70,6 +77,9 @@ def test_a_scenario_against_the_reference_after_every_call(rcw, name, form):
         assert env.world.tile_map_chunks.shape[1] * 2 > 64                    # more tile-map words than a wavefront has lanes
     if name == "huge":
         assert WG.grid(c["H"], c["W"])[2] == 1024
+    if name in GC.AT_THE_BOUND:
+        assert WG.grid(c["H"], c["W"])[2] == 4096 == WG.MAX_CELLS            # the bound itself, not 4095
+        assert env.world.tile_map_chunks.shape[1] * 2 == GC.WORDS[name]       # (a chunk is two words)
     if name == "levels":
         layout, walls = env.wall_layout.numpy(), env.world.walls
         assert set(layout.tolist()) == {40, 41, 42} and min(np.bincount(layout - 40)) > 5
@@ -79,6 +89,103 @@ def test_a_scenario_against_the_reference_after_every_call(rcw, name, form):
             np.testing.assert_array_equal(held[0], rcw.layouts.generated_maze(rcw.layouts.generated_maze_key(0, 0, 0, 1, level, 9)[0], c["H"], c["W"]))
     else:
         assert (env.wall_layout.numpy() == -1).all()
+    env.close()
+
+
+# ---- mazes chosen for the rounds they take ------------------------------------------------------------------------------------------------
+def assert_a_maze_of_the_rule(L, walls, H, W, m, word, where):
+    """one agent's walls against both CPU makers of the maze of key m, and what holds of every maze"""
+    assert walls.tobytes() == WG.maze(m, H, W, word).tobytes(), f"the reference's maze, {where}"
+    assert walls.tobytes() == L.generated_maze(m, H, W, word).tobytes(), f"the host export's maze, {where}"
+    assert L.is_connected(walls), where
+    assert walls[0].all() and walls[-1].all() and walls[:, 0].all() and walls[:, -1].all(), f"the ring, {where}"
+
+
+@pytest.mark.parametrize("T", ["Float32", "Float64"])
+@pytest.mark.parametrize("H,W", sorted(GC.HARD_LEVELS))
+def test_the_maze_that_takes_the_most_rounds(rcw, H, W, T):
+    """levels=1: every agent's maze key is episode_key(level_seed, first_level, 0), so the test chooses its maze — the level of 0 .. 149
+    under level seed 9 that takes the model of the kernel's rounds the most rounds, then the deepest hook chain (the search and its
+    distribution: tests/test_wall_generator_spec.py).  Seven rounds at 129 x 129 and eight on the thin maps are the most that search
+    shows; random keys come nowhere near the kernel's cap of 13, and nothing here claims to.  The rounds are asserted from the model,
+    never from the engine.  Three agents, a perfect maze and loops 0.25: the walls byte for byte against the Python reference and the
+    host export, after the install and after a step that restarts everybody under limit 1."""
+    L, level = rcw.layouts, GC.HARD_LEVELS[(H, W)]
+    m = WR.episode_key(GC.HARD_LEVEL_SEED, level, 0)
+    tree, rounds, chain = WG.boruvka(m, H, W)
+    assert tree == sorted(WG.tree_edges(m, H, W))
+    assert rounds >= {(129, 129): 7, (5, 4097): 8, (4097, 5): 8, (33, 33): 5}[(H, W)] == GC.HARD_ROUNDS[(H, W)] and chain >= 6
+    assert L.generated_maze_key(0, 0, 0, 1, level, GC.HARD_LEVEL_SEED) == (m, level)
+    env = GC.make_env(rcw, dict(H=H, W=W, N=8, Hc=16, B=3, seed=3, T=T))
+    for loops in (0.0, 0.25):
+        word = WG.loops_word(loops)
+        env.set_time_limit(0)
+        env.set_wall_generator(loops, levels=1, first_level=level, level_seed=GC.HARD_LEVEL_SEED)
+        for when in ("installed", "restarted"):
+            walls = env.world.walls
+            assert (env.wall_layout.numpy() == level).all()
+            for a in range(3):
+                assert_a_maze_of_the_rule(L, walls[a], H, W, m, word, f"agent {a}, loops {loops}, {when}")
+            if loops == 0.0:
+                assert int((~walls[0]).sum()) == 2 * WG.grid(H, W)[2] - 1    # a perfect maze: the cells and a passage a tree edge
+            if when == "installed":
+                episode = env.world.episode.copy()
+                env.set_time_limit(1)
+                for _ in range(2):                                           # the first step ends every episode (done or truncated), the second restarts it
+                    rcw.act_(env, np.ones(3, np.uint8))
+                np.testing.assert_array_equal(env.world.episode, episode + 1)
+    assert env.world.player_position_wu.dtype == (np.float64 if T == "Float64" else np.float32)
+    env.close()
+
+
+# ---- more agents than the device holds workgroups ----------------------------------------------------------------------------------------------
+def test_1031_mazes_of_4096_cells_and_a_masked_reset_beside_them(rcw):
+    """129 x 129 asks for 1042 words + 48 KiB = 52.1 KiB of LDS a workgroup: with 160 KiB a compute unit three workgroups fit, 768 on 256
+    compute units (from the documented LDS size; the residency itself has not been measured).  1031 agents — a prime past that — make a
+    later workgroup reuse the LDS of an earlier one uncleared, where a slot, a label or a word left uninitialised would first show.  No
+    levels: 1031 distinct mazes, each against the host export (tests/test_wall_generator_spec.py pins the export to the Python reference
+    at this shape; 1031 Python mazes would take a minute).  Then a masked reset_ of every other agent under a new seed — the masked agents
+    hold the mazes of their new keys, the others are byte-identical: the two-loads-and-out path beside workgroups that rebuilt their
+    LDS — and five levels shared by all."""
+    L = rcw.layouts
+    H = W = 129
+    B, seed, loops = 1031, 17, 0.1
+    env = GC.make_env(rcw, dict(H=H, W=W, N=8, Hc=16, B=B, seed=seed))
+    env.set_wall_generator(loops)
+
+    def check(seeds, where):
+        walls, episode = env.world.walls, env.world.episode
+        assert (env.wall_layout.numpy() == -1).all(), where
+        for a in range(B):
+            key, level = L.generated_maze_key(int(seeds[a]), a, int(episode[a]) - 1)
+            assert level == -1
+            assert walls[a].tobytes() == L.generated_maze(key, H, W, loops).tobytes(), f"agent {a} {where}"
+        return walls
+
+    walls = check(np.full(B, seed), "installed")
+    assert len({w.tobytes() for w in walls}) == B                             # 1031 distinct mazes
+    w = env.world
+    before = dict(tile_map=w.tile_map_chunks.copy(), goal=w.goal_position.copy(), position=w.player_position_wu.copy(),
+                  heading=w.player_direction_au.copy(), episode=w.episode.copy())
+    mask = (np.arange(B) % 2).astype(np.uint8)
+    rcw.reset_(env, mask, 18)
+    check(np.where(mask != 0, 18, seed), "behind the masked reset")
+    w, kept = env.world, mask == 0
+    after = dict(tile_map=w.tile_map_chunks, goal=w.goal_position, position=w.player_position_wu, heading=w.player_direction_au, episode=w.episode)
+    for k in before:
+        np.testing.assert_array_equal(after[k][kept], before[k][kept], err_msg=f"{k} of the agents outside the mask")
+    np.testing.assert_array_equal(after["episode"][~kept], before["episode"][~kept] + 1)
+    assert (after["tile_map"][~kept] != before["tile_map"][~kept]).any(axis=1).all()    # a new maze for every masked agent
+    # five levels: five mazes shared by 1031 agents
+    env.set_wall_generator(loops, levels=5, first_level=60, level_seed=4)
+    layout, walls = env.wall_layout.numpy(), env.world.walls
+    assert set(layout.tolist()) == {60, 61, 62, 63, 64}
+    for level in range(60, 65):
+        held = walls[layout == level]
+        assert len(held) > 100 and (held == held[0]).all()
+        assert held[0].tobytes() == L.generated_maze(L.generated_maze_key(0, 0, 0, 1, level, 4)[0], H, W, loops).tobytes()
+    for a in range(B):
+        assert L.generated_maze_key(18, a, int(env.world.episode[a]) - 1, 5, 60, 4)[1] == layout[a]
     env.close()
 
 

@@ -10,6 +10,8 @@ tests play (tests/wall_bank_cases.py), asserting from the reference's own counts
     f64                   30              18               2          18             1                    19
     features              50              18              16          10             2                    32
     calls                 81              29              20          26             5                    52
+    edge                   9               3               3           6             2                     4     (255 x 254, the largest map: two agents are
+                                                                                                                  walked into their goals)
 """
 import numpy as np
 import pytest
@@ -21,8 +23,9 @@ import walls_ref as WR
 
 COLUMNS = ("episode_starts", "layout_changed", "layout_kept", "goal_redraws", "restarts_after_done", "restarts_after_truncation")
 REHEARSED = dict(small=(472, 265, 140, 64, 31, 374), square_one=(27, 0, 18, 3, 0, 18), square_zero_weight=(27, 0, 18, 3, 0, 18),
-                 big=(64, 40, 8, 43, 0, 48), f64=(30, 18, 2, 18, 1, 19), features=(50, 18, 16, 10, 2, 32), calls=(81, 29, 20, 26, 5, 52))
-ALL_FOUR = ("small", "f64", "features", "calls")       # at least one layout_changed, layout_kept, goal_redraws, and restarts of both kinds
+                 big=(64, 40, 8, 43, 0, 48), f64=(30, 18, 2, 18, 1, 19), features=(50, 18, 16, 10, 2, 32), calls=(81, 29, 20, 26, 5, 52),
+                 edge=(9, 3, 3, 6, 2, 4))
+ALL_FOUR = ("small", "f64", "features", "calls", "edge")    # at least one layout_changed, layout_kept, goal_redraws, and restarts of both kinds
 
 
 def test_the_index_rule_by_hand():
@@ -145,6 +148,10 @@ def test_every_gpu_scenario_reaches_what_it_claims(name):
         assert ev["layouts_drawn"] == {1}                                    # (layout 0 has weight 0)
     if name == "big":
         assert max(ev["layouts_drawn"]) >= 64 and len(ev["layouts_drawn"]) >= 10 and ev["layout_kept"] > 0
+    if name == "edge":
+        c = C.EDGE
+        assert c["H"] * c["W"] + 2 * c["H"] == 65280 and snaps[0]["tile_map_chunks"].shape[1] * 2 == 4050     # no larger map is accepted
+        assert ev["layouts_drawn"] == {0, 2}                                 # (layout 1 has weight 0)
     if name == "calls":
         assert [s["bank"] for s in snaps].count(False) > 5 and snaps[-1]["bank"]
     ep = np.stack([s["episode"] for s in snaps]).astype(np.int64)

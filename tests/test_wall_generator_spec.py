@@ -14,6 +14,26 @@ that each reaches restarts of both kinds and goal redraws:
     levels     201             121            6                   128                          3   (three levels: three mazes)
     features    51              66            5                    30                         51
     calls       97             123           17                    34                         80
+    edge        12              16            2                     2                         12   (`huge`'s script at 4096 cells: 129 x 129)
+    edge_rows64 12              16            2                     2                         12   (the same with 64 camera rows, for the one-launch step)
+    edge_even   12               4            2                     2                         12   (130 x 130)
+    thin        12               6            2                     2                         12   (5 x 4097)
+    tall        12               8            2                     2                         12   (4097 x 5)
+    thin_even   12               9            2                     2                         12   (6 x 4098)
+
+THE KERNEL'S ALGORITHM, wall_generator_ref.boruvka: the rounds of offer, pick, hook and jump as the kernel's header describes them, in plain
+Python, against Kruskal — the same tree at every shape of the suite (200 keys a shape up to 9 x 9, 36 at the larger ones: some 14 s on
+this CPU, both trees of every key).  It also counts the rounds and the longest hook chain, which lets the GPU tests choose their mazes: with levels=1 every agent's
+maze key is episode_key(level_seed, first_level, 0).  Levels 0 .. 149 under level seed 9 (33 x 33: 0 .. 299), some 13 s on this CPU, 4 to 5 s a large shape:
+
+    shape        rounds: levels           hook chain: levels                       the hardest (most rounds, then the deepest chain)
+    129 x 129    6: 99, 7: 51             5: 10, 6: 96, 7: 38, 8: 6                level 32 (7 rounds, chain 8)
+    5 x 4097     7: 78, 8: 72             5: 39, 6: 94, 7: 16, 8: 1                level 31 (8, 7)
+    4097 x 5     7: 78, 8: 72             5: 30, 6: 96, 7: 23, 8: 1                level 141 (8, 8)
+    33 x 33      4: 209, 5: 91            3: 6, 4: 101, 5: 152, 6: 39, 7: 2        level 1 (5, 6; the first of its kind)
+
+Random keys come nowhere near the kernel's cap of 13 rounds (ceil(log2 4096) = 12 is the worst case of any order): eight is what a search
+of this size finds, and the GPU tests claim no more.
 
 The exports are missing from the build before this feature: the tests that call them fail there.
 """
@@ -26,8 +46,10 @@ import walls_ref as WR
 
 COLUMNS = ("episode_starts", "goal_redraws", "restarts_after_done", "restarts_after_truncation")
 REHEARSED = dict(small=(470, 167, 22, 381), square=(36, 45, 3, 24), big=(48, 25, 8, 24), wide=(24, 13, 3, 13), huge=(12, 9, 2, 2),
-                 f64=(31, 11, 2, 19), levels=(201, 121, 6, 128), features=(51, 66, 5, 30), calls=(97, 123, 17, 34))
-SHAPES = [(5, 7), (6, 6), (8, 8), (9, 9), (21, 45), (33, 33), (65, 65)]
+                 f64=(31, 11, 2, 19), levels=(201, 121, 6, 128), features=(51, 66, 5, 30), calls=(97, 123, 17, 34),
+                 edge=(12, 16, 2, 2), edge_rows64=(12, 16, 2, 2), edge_even=(12, 4, 2, 2), thin=(12, 6, 2, 2), tall=(12, 8, 2, 2), thin_even=(12, 9, 2, 2))
+AT_THE_BOUND = [(129, 129), (130, 130), (5, 4097), (4097, 5), (6, 4098)]     # 4096 cells each
+SHAPES = [(5, 7), (6, 6), (8, 8), (9, 9), (21, 45), (33, 33), (65, 65)] + AT_THE_BOUND
 LOOPS = [0, 1, 1 << 30, (1 << 32) - 1]
 KEYS = [0, 1, 0x0123456789ABCDEF, (1 << 64) - 1]
 
@@ -107,6 +129,42 @@ def test_loops_only_open_walls_of_the_perfect_maze(H, W):
         assert 0.15 < opened / (edges - (C_ - 1)) < 0.35                      # about a quarter of the 225 non-tree edges
 
 
+# ---- the kernel's algorithm against Kruskal -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("H,W", [(5, 5)] + SHAPES)
+def test_the_rounds_of_the_kernel_find_kruskals_tree(H, W):
+    """offer, pick, hook, jump until one label is left: the tree Kruskal finds, C - 1 edges, in at most ceil(log2 C) rounds, no chain longer
+    than the roots a round can have"""
+    _, _, C_ = WG.grid(H, W)
+    for k in range(200 if H * W <= 81 else 36):
+        m = WR.draw(79, k)
+        tree, rounds, chain = WG.boruvka(m, H, W)
+        assert tree == sorted(WG.tree_edges(m, H, W)), f"{H} x {W}, key {m:#x}"
+        assert len(tree) == C_ - 1 and 1 <= rounds <= (C_ - 1).bit_length() and 1 <= chain < C_
+
+
+def test_two_roots_that_picked_each_other_keep_the_smaller():
+    """5 x 5: four cells, every round-one root picks its smaller edge.  Over 40 keys some pair always picks each other (the smallest edge of
+    all is the pick of both its ends), the model ends on one label — a cycle would trip its assertion — and both one round and two occur"""
+    rounds = {WG.boruvka(m, 5, 5)[1] for m in range(40)}
+    assert rounds == {1, 2}
+
+
+SEARCHED = {(129, 129): ({6: 99, 7: 51}, (7, 8)), (5, 4097): ({7: 78, 8: 72}, (8, 7)), (4097, 5): ({7: 78, 8: 72}, (8, 8)),
+            (33, 33): ({4: 209, 5: 91}, (5, 6))}
+
+
+@pytest.mark.parametrize("H,W", sorted(SEARCHED))
+def test_the_hard_levels_are_the_hardest_of_their_search(H, W):
+    """wall_generator_cases.HARD_LEVELS, which the GPU tests install, from the model alone: the level of 0 .. 149 under level seed 9 with the
+    most rounds, then the deepest chain, then the smallest number; and the distribution of the docstring"""
+    found = [WG.boruvka(WR.episode_key(C.HARD_LEVEL_SEED, level, 0), H, W)[1:] for level in range(300 if H == 33 else 150)]
+    counts, hardest = SEARCHED[(H, W)]
+    assert {r: [f[0] for f in found].count(r) for r in {f[0] for f in found}} == counts
+    level = max(range(150), key=lambda l: (found[l], -l))
+    assert level == C.HARD_LEVELS[(H, W)] and found[level] == hardest
+    assert hardest[0] >= C.HARD_ROUNDS[(H, W)] == max(counts)                # the most rounds the search shows
+
+
 # ---- the level rule -----------------------------------------------------------------------------------------------------------------------
 def test_levels_stay_in_their_range_and_all_are_reached():
     seen = set()
@@ -145,7 +203,7 @@ def test_what_an_install_is_refused_for():
 
 
 # ---- the library's host exports -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("H,W", [(5, 5)] + SHAPES + [(129, 129)])
+@pytest.mark.parametrize("H,W", [(5, 5)] + SHAPES)
 def test_the_host_export_equals_the_reference_byte_for_byte(H, W):
     L = layouts()
     for m in KEYS[:2] if H >= 65 else KEYS:

@@ -65,7 +65,9 @@ SQUARE = dict(H=8, W=8, N=33, Hc=24, B=9, seed=11)                  # 64 tiles: 
 BIG = dict(H=33, W=33, N=64, Hc=64, B=16, seed=21)                  # 1089 tiles: 69 words, more than a wavefront
 F64 = dict(H=9, W=9, N=96, Hc=40, B=10, seed=5, T="Float64")
 CALLS = dict(H=6, W=6, N=64, Hc=64, B=16, seed=7)
-SHAPES = dict(SMALL=SMALL, SQUARE=SQUARE, BIG=BIG, F64=F64, CALLS=CALLS)
+EDGE = dict(H=255, W=254, N=8, Hc=16, B=3, seed=51)                 # 64770 tiles, the most rcw_create takes (H W + 2 H = 65280): 4050 words,
+                                                                    # 64 passes of the lane + 64 i loops, 15.8 KiB of LDS under reset_agent
+SHAPES = dict(SMALL=SMALL, SQUARE=SQUARE, BIG=BIG, F64=F64, CALLS=CALLS, EDGE=EDGE)
 
 
 def make_ref(c, render=True, **kw):
@@ -138,6 +140,11 @@ class Recorder:
             self.lim.clear(mask)
         self._snap()
 
+    def state(self):
+        """(walls (B, H, W), goal, position, heading) as they stand: what a scenario builds a set_state from"""
+        s = self.snaps[-1]
+        return np.stack([self.ref.walls_of(b) for b in range(self.B)]), s["goal"].copy(), s["position"].copy(), s["direction"].copy()
+
 
 class Player:
     """the same calls on an engine, each compared with the recorded snapshot; trackers: objects with stepped(actions, where) and
@@ -200,6 +207,11 @@ class Player:
         self.env.set_state(goal, pos, heading, mask)
         self._masked(mask, "set_state")
 
+    def state(self):
+        """the engine's own state, which the call before found equal to the reference's"""
+        w = self.env.world
+        return w.walls, w.goal_position.copy(), w.player_position_wu.copy(), w.player_direction_au.copy()
+
 
 # ---- the scenarios ----------------------------------------------------------------------------------------------------------------
 def rollout(d, bank, weights, limit, steps, seed):
@@ -209,6 +221,20 @@ def rollout(d, bank, weights, limit, steps, seed):
     rng = np.random.default_rng(seed)
     for _ in range(steps):
         d.step(WR.draw_actions(rng, d.B))
+
+
+def walk_into_the_goal(d, mask):
+    """the masked agents are put on the first free tile of their map whose neighbour one row down is free too, facing it (heading 0 is
+    +i), the goal on that neighbour; then everybody steps forward once: a quarter tile brings the player's radius of 0.3 over the goal
+    tile's edge, the masked agents are done, and the next step restarts them.  On a large map under a short limit nobody arrives
+    otherwise."""
+    walls, goal, pos, heading = d.state()
+    for b in np.flatnonzero(mask):
+        free = ~walls[b]
+        i, j = np.argwhere(free[:-1] & free[1:])[0]                          # 0-based; the goal on (i + 1, j)
+        goal[b], pos[b], heading[b] = (i + 2, j + 1), (i + 0.5, j + 0.5), 0
+    d.set_state(goal, pos, heading, mask)
+    d.step(np.ones(d.B, np.uint8))
 
 
 def small(d):
@@ -234,6 +260,14 @@ def big(d):
     rng = np.random.default_rng(23)
     for _ in range(7):
         d.step(WR.draw_actions(rng, d.B))
+
+
+def edge(d):
+    """255 x 254, the largest map a handle takes: three layouts (pillars, a maze, pillars), weights (1, 0, 3), limit 2, five steps — two
+    agents walk into their goals — and a step that restarts them"""
+    rollout(d, pillars_and_mazes(255, 254, 3, 500), np.array([1, 0, 3], np.uint32), 2, 5, 52)
+    walk_into_the_goal(d, np.array([1, 0, 1], np.uint8))
+    d.step(np.array([1, 2, 3], np.uint8))
 
 
 def f64(d):
@@ -281,7 +315,7 @@ def calls(d):
 
 
 SCENARIOS = dict(small=(small, SMALL), square_one=(square_one, SQUARE), square_zero_weight=(square_zero_weight, SQUARE), big=(big, BIG),
-                 f64=(f64, F64), features=(features, CALLS), calls=(calls, CALLS))
+                 f64=(f64, F64), features=(features, CALLS), calls=(calls, CALLS), edge=(edge, EDGE))
 
 
 @functools.lru_cache(maxsize=None)

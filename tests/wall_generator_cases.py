@@ -21,7 +21,20 @@ SMALL, SQUARE, BIG, F64, CALLS = BC.SMALL, BC.SQUARE, BC.BIG, BC.F64, BC.CALLS
 WIDE = dict(H=21, W=45, N=32, Hc=24, B=8, seed=31)                  # non-square: 10 x 22 = 220 cells, four cells a lane (the last: 28 lanes)
 HUGE = dict(H=65, W=65, N=16, Hc=24, B=4, seed=41)                  # 1024 cells: 16 a lane, 265 words
 LEVELS = dict(H=7, W=9, N=32, Hc=24, B=67, seed=13)                 # 3 x 4 cells; 67 agents on three levels
-SHAPES = dict(BC.SHAPES, WIDE=WIDE, HUGE=HUGE, LEVELS=LEVELS)
+# the size bound, 4096 cells (64 a lane, 48 KiB of slots and labels), on every kind of map that reaches it
+EDGE = dict(HUGE, H=129, W=129)                                     # 64 x 64 cells, 1042 words
+EDGE_ROWS64 = dict(EDGE, Hc=64)                                     # ... with the fewest camera rows the one-launch step takes (24 rows: refused)
+EDGE_EVEN = dict(HUGE, H=130, W=130)                                # 64 x 64 still: the last interior row and column stay wall; 1058 words
+THIN = dict(HUGE, H=5, W=4097)                                      # 2 x 2048 cells, 1282 words
+TALL = dict(HUGE, H=4097, W=5)                                      # 2048 x 2 cells: nj == 2
+THIN_EVEN = dict(HUGE, H=6, W=4098)                                 # 2 x 2048 still; 1538 words: the largest LDS request the launch makes
+SHAPES = dict(BC.SHAPES, WIDE=WIDE, HUGE=HUGE, LEVELS=LEVELS, EDGE=EDGE, EDGE_ROWS64=EDGE_ROWS64, EDGE_EVEN=EDGE_EVEN, THIN=THIN, TALL=TALL, THIN_EVEN=THIN_EVEN)
+# the level of 0 .. 149 under HARD_LEVEL_SEED whose maze takes the kernel's algorithm the most rounds, then the deepest hook chain
+# (wall_generator_ref.boruvka; tests/test_wall_generator_spec.py makes the search), and the rounds the GPU test demands of it from the model
+HARD_LEVEL_SEED = 9
+HARD_LEVELS = {(129, 129): 32, (5, 4097): 31, (4097, 5): 141, (33, 33): 1}
+HARD_ROUNDS = {(129, 129): 7, (5, 4097): 8, (4097, 5): 8, (33, 33): 5}
+WORDS = dict(edge=1042, edge_rows64=1042, edge_even=1058, thin=1282, tall=1282, thin_even=1538)      # 2 (ceil(H W / 16) rounded up to even)
 
 
 def make_ref(c, render=True, **kw):
@@ -114,18 +127,7 @@ def rollout(d, gen, limit, steps, seed):
         d.step(WR.draw_actions(rng, d.B))
 
 
-def walk_into_the_goal(d, mask):
-    """the masked agents are put on the first free tile of their maze whose neighbour one row down is free too, facing it (heading 0 is
-    +i), the goal on that neighbour; then everybody steps forward once: a quarter tile brings the player's radius of 0.3 over the goal
-    tile's edge, the masked agents are done, and the next step restarts them.  In a large maze under a short limit nobody arrives
-    otherwise."""
-    walls, goal, pos, heading = d.state()
-    for b in np.flatnonzero(mask):
-        free = ~walls[b]
-        i, j = np.argwhere(free[:-1] & free[1:])[0]                          # 0-based; the goal on (i + 1, j)
-        goal[b], pos[b], heading[b] = (i + 2, j + 1), (i + 0.5, j + 0.5), 0
-    d.set_state(goal, pos, heading, mask)
-    d.step(np.ones(d.B, np.uint8))
+walk_into_the_goal = BC.walk_into_the_goal
 
 
 def small(d):
@@ -213,7 +215,9 @@ def calls(d):
 
 
 SCENARIOS = dict(small=(small, SMALL), square=(square, SQUARE), big=(big, BIG), wide=(wide, WIDE), huge=(huge, HUGE), f64=(f64, F64),
-                 levels=(levels, LEVELS), features=(features, CALLS), calls=(calls, CALLS))
+                 levels=(levels, LEVELS), features=(features, CALLS), calls=(calls, CALLS),
+                 edge=(huge, EDGE), edge_rows64=(huge, EDGE_ROWS64), edge_even=(huge, EDGE_EVEN), thin=(huge, THIN), tall=(huge, TALL), thin_even=(huge, THIN_EVEN))
+AT_THE_BOUND = ("edge", "edge_rows64", "edge_even", "thin", "tall", "thin_even")            # `huge`'s script at 4096 cells
 UNRENDERED = ("huge",)
 
 

@@ -75,6 +75,57 @@ def tree_edges(m, H, W):
     return took
 
 
+def boruvka(m, H, W):
+    """the kernel's rounds (csrc/rcw_wall_bank.hip, rcw_wall_generator_kernel's header) restated: (the tree's edge ids sorted, the rounds, the
+    longest hook chain).  A round — offer: every edge that joins two labels offers its order word to both labels' slots, the smallest stays;
+    pick: every root with an offer takes the winning edge into the tree and notes the label across it; hook: the root hangs itself under
+    that label, but of two roots that picked each other the smaller stays a root; jump: every cell takes its root's root until nothing
+    moves.  The chain of a round is the largest number of hooks between a root of the round and the root it ends under — what the
+    pointer jumping has to shorten; the third value is the largest chain of any round.  Rounds run until one label is left: the model has
+    no cap (the kernel's is 13)."""
+    _, nj, C = grid(H, W)
+    offers = [(order_word(m, e[0]), e[1], e[2]) for e in edges(H, W)]
+    label = list(range(C))
+    tree, rounds, deepest = set(), 0, 0
+    while any(l != label[0] for l in label):
+        rounds += 1
+        slot = {}                                                              # offer
+        for w, a, b in offers:
+            la, lb = label[a], label[b]
+            if la != lb:
+                if w < slot.get(la, 1 << 64):
+                    slot[la] = w
+                if w < slot.get(lb, 1 << 64):
+                    slot[lb] = w
+        across = {}                                                            # pick
+        for root, w in slot.items():
+            eid = w & 0xFFFFF
+            a = eid >> 1
+            b = a + (nj if eid & 1 else 1)
+            tree.add(eid)
+            la, lb = label[a], label[b]
+            assert root in (la, lb) and la != lb
+            across[root] = lb if la == root else la
+        up = {}                                                                # hook
+        for root, other in across.items():
+            if not (across.get(other) == root and root < other):
+                up[root] = other
+        top, depth = {}, {}                                                    # jump
+        for r in up:
+            path = []
+            while r in up and r not in top:
+                path.append(r)
+                r = up[r]
+                assert len(path) <= C                                          # (a cycle: the words were not distinct)
+            end, d = (top[r], depth[r]) if r in top else (r, 0)
+            for q in reversed(path):
+                d += 1
+                top[q], depth[q] = end, d
+        deepest = max(deepest, max(depth.values()))
+        label = [top.get(l, l) for l in label]
+    return sorted(tree), rounds, deepest
+
+
 def maze(m, H, W, loops=0):
     """bool (H, W), walls[i, j] 0-based = tile (i + 1, j + 1) is a WALL; loops is the UInt32 word"""
     assert H >= 5 and W >= 5 and 0 <= loops <= 0xFFFFFFFF
