@@ -584,6 +584,46 @@ RCW_API int rcw_wall_generator_info(rcw_handle* h, int32_t* enabled, uint32_t* l
 RCW_API int rcw_wall_generator_key(uint64_t seed, int32_t global_agent, uint32_t episode, int32_t levels, int32_t first_level, uint64_t level_seed,
                                    uint64_t* maze_key, int32_t* level);
 RCW_API int rcw_wall_generator_layout(int32_t H, int32_t W, uint64_t maze_key, uint32_t loops, uint8_t* out_host /* (H*W), rcw_set_walls' order */);
+/* ---- the wall generator: caves (this build's addition: a second family of layouts behind the generator's launch point) -------------------
+ * Opt-in per handle.  The generator above makes one kind of world: one-tile corridors on the odd sub-grid.  Caves are open space with
+ * irregular walls and pockets: a seeded random fill, smoothed by a cellular automaton, pruned to one connected region.
+ * A CAVE FROM ONE KEY  cave(m, H, W, fill, smooth), H, W >= 5, with draw(m, n) of csrc/rcw_rng.h; tiles are 0-based (i, j) with index
+ * t = i + H j, the tile map's own order.  The rule does not depend on the algorithm (the device propagates labels in LDS,
+ * rcw_wall_caves_layout below flood-fills with a queue).
+ *   ring     every tile with i in {0, H-1} or j in {0, W-1} is WALL, at every stage.
+ *   gen 0    an interior tile t is WALL where (draw(m, 2^62 + t) >> 32) < fill.  fill is UInt32 as loops is: 0 gives an empty room,
+ *            2^32 - 1 all wall.  Indices from 2^62 cannot meet the maze's, which stay below 2^21: the fallback uses the same m.
+ *   smooth   `smooth` times, 0 <= smooth <= 8, synchronously (every interior tile reads generation g and writes g + 1): a tile is WALL in
+ *            g + 1 where at least 5 of the 9 tiles of its 3 x 3 neighbourhood, itself included, are WALL in g; the ring counts as WALL.
+ *   regions  the 4-connected components of free tiles.  The one with the most tiles is kept; of several largest, the one that holds the
+ *            smallest tile index t.  Every other free tile becomes WALL.
+ *   fallback need = max(7, ((H-2)(W-2)) / 4) (integer division).  Where the kept region has fewer than `need` tiles, or there is none,
+ *            the layout is maze(m, H, W, 0) instead, exactly as the generator's rule defines it.
+ *   So a layout is always connected and ring-closed with at least 7 free interior tiles: valid as rcw_set_walls wants one.  Small maps
+ *   mostly fall back: at fill 0.40, smooth 2 nearly every 5 x 7 level is a maze, about a quarter of the 8 x 8 ones, none at 32 x 32.
+ * THE KEY OF AN EPISODE is the generator's, unchanged (key, u, levels == 0: m = u and wall_layout -1; levels >= 1: l, m = the episode key of
+ * (level_seed, l, 0), wall_layout l): rcw_wall_generator_key serves both families.  After that the rule is the bank's, word for word.
+ * The ABI is additive: RCW_ABI_VERSION, rcw_config and every existing export are what they were; a handle without caves launches what
+ * it launched.
+ *   rcw_set_wall_caves            enable != 0: installs the caves and restarts EVERY agent under the rule with the handle's current seed, as
+ *                                 rcw_set_wall_generator does.  Validated on the host before anything is queued, a refusal leaves the
+ *                                 handle untouched: RCW_ERR_INVALID_ARGUMENT for H or W below 5, smooth outside 0 .. 8 or a bad level
+ *                                 range; RCW_ERR_UNSUPPORTED for more than 4096 interior tiles ((H-2)(W-2): maps beyond 66 x 66; the message
+ *                                 names the bound) and while a bank or the maze generator is on.  enable == 0 switches them off (RCW_OK
+ *                                 also where there were none): the walls stay.  The parameters are kernel arguments fixed at install: a
+ *                                 captured step replays correctly.
+ *   while caves are on            rcw_set_wall_bank, rcw_set_wall_generator(enable != 0) and rcw_set_walls: RCW_ERR_UNSUPPORTED, nothing
+ *                                 changes (rcw_set_wall_generator(h, 0, ...) is RCW_OK and changes nothing either).  rcw_set_state* keeps
+ *                                 the layout.  rcw_wall_layout* serve l, or -1.  rcw_wall_generator_info reports enabled = 1, loops = 0
+ *                                 and the level parameters.
+ *   rcw_wall_caves_info           enabled, fill, smooth (any pointer may be NULL); zeros while caves are off.
+ *   rcw_wall_caves_layout         handle-less, pure host arithmetic: cave(key, H, W, fill, smooth) as UInt8 (H*W) in rcw_set_walls' order
+ *                                 (1 = wall); *fell_back (may be NULL) = 1 where the layout is the maze.  The refusals of a geometry
+ *                                 and of smooth are rcw_set_wall_caves'. */
+RCW_API int rcw_set_wall_caves(rcw_handle* h, int32_t enable, uint32_t fill, int32_t smooth, int32_t levels, int32_t first_level, uint64_t level_seed);
+RCW_API int rcw_wall_caves_info(rcw_handle* h, int32_t* enabled, uint32_t* fill, int32_t* smooth);
+RCW_API int rcw_wall_caves_layout(int32_t H, int32_t W, uint64_t key, uint32_t fill, int32_t smooth, uint8_t* out_host /* (H*W), rcw_set_walls' order */,
+                                  int32_t* fell_back);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

@@ -603,6 +603,51 @@ function generated_maze(maze_key::Integer, H::Integer, W::Integer; loops::Real =
     return out .!= 0
 end
 
+# ---- the wall generator: caves (this build's addition; include/rcw.h, rcw_set_wall_caves) -----------------------------------------
+"""
+    set_wall_caves!(env; fill = 0.40, smooth = 2, levels = 0, first_level = 0, level_seed = 0)
+    set_wall_caves!(env, nothing)
+
+A new cave made on the device at every start of an episode, where `set_wall_generator!` makes a maze: the interior filled with
+probability `fill` (scaled to `UInt32` as `loops` is), smoothed `smooth` times (0 to 8) by the 5-of-9 automaton and pruned to its
+largest 4-connected region; a cave whose region has fewer than `max(7, (H-2)(W-2) ÷ 4)` tiles is replaced by the perfect maze of the
+same key (on small maps that is most of them).  The level parameters and `wall_layout(env)` are the generator's.  Maps of 5 x 5 up to
+4096 interior tiles (66 x 66).  `set_walls!`, `set_wall_bank!` and `set_wall_generator!` are refused while caves are on;
+`set_wall_caves!(env, nothing)` switches them off, the agents keep their walls.  An environment built with `rng` takes no caves.
+"""
+function set_wall_caves!(env::BatchedSingleRoom; fill::Real = 0.40, smooth::Integer = 2, levels::Integer = 0, first_level::Integer = 0, level_seed::Integer = 0)
+    env.rng === nothing || throw(ArgumentError("an environment built with rng draws its resets on the host: it takes no wall caves"))
+    0 <= fill <= 1 || throw(ArgumentError("fill is a probability in [0, 1]"))
+    word = UInt32(min(floor(UInt64, Float64(fill) * 2.0^32), UInt64(0xFFFFFFFF)))
+    check(ccall((:rcw_set_wall_caves, librcw), Cint, (Ptr{Cvoid}, Int32, UInt32, Int32, Int32, Int32, UInt64),
+                env.handle, 1, word, smooth, levels, first_level, level_seed))
+    env.stale = true
+    return nothing
+end
+function set_wall_caves!(env::BatchedSingleRoom, ::Nothing)
+    check(ccall((:rcw_set_wall_caves, librcw), Cint, (Ptr{Cvoid}, Int32, UInt32, Int32, Int32, Int32, UInt64), env.handle, 0, 0, 0, 0, 0, 0))
+    return nothing
+end
+function wall_caves_info(env::BatchedSingleRoom)
+    on = Ref{Int32}(0); fill = Ref{UInt32}(0); smooth = Ref{Int32}(0)
+    check(ccall((:rcw_wall_caves_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{UInt32}, Ref{Int32}), env.handle, on, fill, smooth))
+    return (enabled = on[] != 0, fill = fill[], smooth = smooth[])
+end
+"""
+    generated_cave(key, H, W; fill = 0.40, smooth = 2) -> (BitMatrix (H, W), fell_back)
+
+The wall generator's cave of one key (`generated_maze_key` serves both families; `true` = wall), as an agent's WALL layer holds it, and
+whether it is the fallback maze: host arithmetic (a queue flood fill), no device.
+"""
+function generated_cave(key::Integer, H::Integer, W::Integer; fill::Real = 0.40, smooth::Integer = 2)
+    0 <= fill <= 1 || throw(ArgumentError("fill is a probability in [0, 1]"))
+    word = UInt32(min(floor(UInt64, Float64(fill) * 2.0^32), UInt64(0xFFFFFFFF)))
+    out = Matrix{UInt8}(undef, max(H, 0), max(W, 0))                             # column-major: tile (i, j) at (i - 1) + H (j - 1)
+    fell = Ref{Int32}(0)
+    check(ccall((:rcw_wall_caves_layout, librcw), Cint, (Int32, Int32, UInt64, UInt32, Int32, Ptr{UInt8}, Ref{Int32}), H, W, key, word, smooth, out, fell))
+    return (out .!= 0, fell[] != 0)
+end
+
 # per-agent sticky status: 0, -5 where the reference would have raised BoundsError, -2 for an invalid device action,
 # 1 (a warning) where sample_empty_position gave up after max_tries and returned an occupied tile (utils.jl:34 @warns there)
 function status(env::BatchedSingleRoom)

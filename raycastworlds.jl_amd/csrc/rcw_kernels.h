@@ -240,3 +240,14 @@ struct RcwWallGen {
 constexpr int kWallGenMaxCells = 4096;
 // Where rcw_launch_wall_bank goes on a handle with a generator: the same contract (counter moved or force -> a maze and a fresh state, mask[a]).
 hipError_t rcw_launch_wall_generator(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, bool force, hipStream_t s);
+
+// The caves (rcw_set_wall_caves, rcw_wall_bank.hip): the generator's slot with another family.  `gen` carries the level rule and the fallback
+// maze's grid (loops 0); these two are the family's own kernel arguments.
+struct RcwWallCaves {
+    uint32_t fill;               // an interior tile is WALL in generation 0 where the high word of its draw is below this
+    int32_t smooth;              // smoothing steps, 0 .. kWallCavesMaxSmooth
+};
+constexpr int kWallCavesMaxTiles = 4096;   // (H - 2)(W - 2): maps up to 66 x 66
+constexpr int kWallCavesMaxSmooth = 8;
+size_t rcw_wall_caves_lds_bytes(int H, int W, int nwords);
+hipError_t rcw_launch_wall_caves(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, const RcwWallCaves& caves, bool force, hipStream_t s);

@@ -512,6 +512,66 @@ extern "C" int rcw_wall_generator_layout(int32_t H, int32_t W, uint64_t maze_key
     return RCW_OK;
 }
 
+// ---- the wall generator: caves (include/rcw.h, "the wall generator: caves") ------------------------------------------------------------
+// What rcw_set_wall_caves checks of a geometry, the smoothing count and a level range before anything is queued — or the refusal.
+int plan_wall_caves(int32_t H, int32_t W, int32_t smooth, int32_t levels, int32_t first_level)
+{
+    if (H < 5 || W < 5) return fail(RCW_ERR_INVALID_ARGUMENT, "caves need a map of at least 5 x 5 tiles (this one is %d x %d)", H, W);
+    if (smooth < 0 || smooth > kWallCavesMaxSmooth) return fail(RCW_ERR_INVALID_ARGUMENT, "caves are smoothed 0 .. %d times (got %d)", kWallCavesMaxSmooth, smooth);
+    if (levels < 0 || first_level < 0 || (int64_t)first_level + (int64_t)levels > 2147483647ll)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "the caves' level range must satisfy levels >= 0, first_level >= 0 and first_level + levels <= 2^31 - 1 (got first_level %d, levels %d)", first_level, levels);
+    const int64_t tiles = (int64_t)(H - 2) * (int64_t)(W - 2);
+    if (tiles > kWallCavesMaxTiles)
+        return fail(RCW_ERR_UNSUPPORTED, "caves are made on at most %d interior tiles (maps up to 66 x 66); %d x %d has %lld", kWallCavesMaxTiles, H, W, (long long)tiles);
+    return RCW_OK;
+}
+
+// The handle-less export: the rule once more on the host, by other algorithms than the device's — a queue flood fill a region where the kernel
+// propagates labels, and rcw_wall_generator_layout's Kruskal for the fallback.
+extern "C" int rcw_wall_caves_layout(int32_t H, int32_t W, uint64_t key, uint32_t fill, int32_t smooth, uint8_t* out_host, int32_t* fell_back)
+{
+    if (!out_host) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    const int rc = plan_wall_caves(H, W, smooth, 0, 0); if (rc) return rc;
+    const size_t HW = (size_t)H * (size_t)W;
+    std::vector<uint8_t> gen, nxt;
+    std::vector<int32_t> region, queue;
+    try { gen.assign(HW, 1); nxt.assign(HW, 1); region.assign(HW, -1); queue.reserve(HW); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the cave failed"); }
+    for (int j = 1; j + 1 < W; ++j)
+        for (int i = 1; i + 1 < H; ++i) {
+            const size_t t = (size_t)i + (size_t)H * (size_t)j;
+            gen[t] = (uint32_t)(rcw_draw(key, 0x4000000000000000ull + (uint64_t)t) >> 32) < fill ? 1 : 0;
+        }
+    for (int s = 0; s < smooth; ++s) {
+        for (int j = 1; j + 1 < W; ++j)
+            for (int i = 1; i + 1 < H; ++i) {
+                int walls = 0;
+                for (int dj = -1; dj <= 1; ++dj)
+                    for (int di = -1; di <= 1; ++di) walls += gen[(size_t)(i + di) + (size_t)H * (size_t)(j + dj)];
+                nxt[(size_t)i + (size_t)H * (size_t)j] = walls >= 5 ? 1 : 0;
+            }
+        gen.swap(nxt);
+    }
+    // regions in the order of their smallest tile: a later one replaces the kept one only where it is strictly larger
+    int32_t kept = -1, kept_size = 0, regions = 0;
+    for (size_t t0 = 0; t0 < HW; ++t0) {
+        if (gen[t0] || region[t0] >= 0) continue;
+        const int32_t id = regions++;
+        queue.clear(); queue.push_back((int32_t)t0); region[t0] = id;
+        for (size_t head = 0; head < queue.size(); ++head) {
+            const int32_t t = queue[head];
+            const int32_t nb[4] = {t - 1, t + 1, t - H, t + H};            // (a free tile is interior: all four exist)
+            for (const int32_t u : nb)
+                if (!gen[(size_t)u] && region[(size_t)u] < 0) { region[(size_t)u] = id; queue.push_back(u); }
+        }
+        if ((int32_t)queue.size() > kept_size) { kept = id; kept_size = (int32_t)queue.size(); }
+    }
+    const int32_t need = std::max<int32_t>(7, (H - 2) * (W - 2) / 4);
+    if (fell_back) *fell_back = kept_size < need ? 1 : 0;
+    if (kept_size < need) return rcw_wall_generator_layout(H, W, key, 0u, out_host);
+    for (size_t t = 0; t < HW; ++t) out_host[t] = region[t] == kept ? 0 : 1;
+    return RCW_OK;
+}
+
 #ifdef RCW_DEV_SWITCHES
 #include "dev/api_plan_export.inc"   // the rules and the step's facts without a device (tests/test_top_view_plan.py, tests/test_step_state.py)
 #endif

@@ -1,6 +1,6 @@
 // The wall bank (include/rcw.h, rcw_set_wall_bank): L wall layouts resident on the device, one of them drawn for an agent at every start of
 // an episode.  Three kernels; nothing else of the library knows about the bank.  The wall generator's kernel (further down) lives here too:
-// it shares the bank's tail.
+// it shares the bank's tail; so does the caves' kernel behind it, which also shares the maze.
 //
 // rcw_wall_bank_pack_kernel   once per rcw_set_wall_bank: the layouts, UInt8 (H*W, L) as rcw_set_walls takes them, into the tile map's own
 //          word format — nwords uint32 a layout, 16 tiles a word, bit 0 of each 2-bit field = WALL, the GOAL bits and the padding past H*W
@@ -118,30 +118,14 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_bank_kernel(const RcwDev 
 //          one is uniform: the agent, the round's counts (__syncthreads_or / _count) and kernel arguments.
 __device__ __forceinline__ void open_tile(uint32_t* words, int t) { atomicAnd(&words[t >> 4], ~(1u << ((t & 15) * 2))); }
 
-template <typename T>
-__global__ __launch_bounds__(kBankBlock) void rcw_wall_generator_kernel(const RcwDev p, const RcwLimit lim, const RcwWallBank b, const RcwWallGen g, const int force)
+// The maze of key m in LDS, by the whole wave: `words` (nwords) and, 8-byte aligned, `scratch` (12 bytes a cell: slots, then labels).  Ends
+// on a barrier: the words are complete.  The generator's kernel and the caves' fallback call it.
+__device__ __forceinline__ void maze_in_lds(uint32_t* const words, void* const scratch, const int H, const int HW, const int nwords, const int ni, const int nj,
+                                            const uint64_t m, const uint32_t loops, const int lane)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_g[];
-    const int a = blockIdx.x, lane = threadIdx.x;
-    if (a >= p.B) return;
-    const uint32_t ep = p.episode[a];
-    if (!force && b.last_episode[a] == ep) {
-        if (lane == 0) b.mask[a] = 0;
-        return;
-    }
-    const int H = p.H, nwords = p.nwords, HW = p.H * p.W, ni = g.ni, nj = g.nj, C = ni * nj;
-    uint32_t* const words = lds_g;
-    unsigned long long* const slot = reinterpret_cast<unsigned long long*>(lds_g + ((nwords + 1) & ~1));   // (8-byte aligned)
+    const int C = ni * nj;
+    unsigned long long* const slot = reinterpret_cast<unsigned long long*>(scratch);
     uint32_t* const label = reinterpret_cast<uint32_t*>(slot + C);
-    // the maze's key: the episode's own draw 2^63 (the bank's index), or the key of the level it picks
-    const uint64_t key = rcw_episode_key(p.seed, (uint64_t)(p.agent_id_offset + a), (uint64_t)(ep - 1u));
-    const uint64_t u = rcw_draw(key, kLayoutDraw);
-    int level = -1;
-    uint64_t m = u;
-    if (g.levels > 0) {
-        level = g.first_level + (int)rcw_below(u, (uint64_t)g.levels);
-        m = rcw_episode_key(g.level_seed, (uint64_t)level, 0ull);
-    }
     for (int w = lane; w < nwords; w += kBankBlock) {
         const int left = HW - 16 * w;                                      // tiles of this word inside the map (the padding stays clear)
         words[w] = left >= 16 ? 0x55555555u : left <= 0 ? 0u : (0x55555555u & ((1u << (2 * left)) - 1u));   // (nwords is even: a whole word may be padding)
@@ -207,15 +191,169 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_generator_kernel(const Rc
         for (int c = lane; c < C; c += kBankBlock) apart |= (label[c] != l0) ? 1 : 0;
         if (!__syncthreads_or(apart)) break;
     }
-    if (g.loops != 0u) {
+    if (loops != 0u) {
         for (int c = lane; c < C; c += kBankBlock) {
             const int ci = c / nj, cj = c - ci * nj;
             const unsigned long long id = 2ull * (unsigned)c, base = 2ull * (unsigned)C;
-            if (cj + 1 < nj && (uint32_t)(rcw_draw(m, base + id) >> 32) < g.loops) open_tile(words, (2 * ci + 1) + H * (2 * cj + 2));
-            if (ci + 1 < ni && (uint32_t)(rcw_draw(m, base + id + 1ull) >> 32) < g.loops) open_tile(words, (2 * ci + 2) + H * (2 * cj + 1));
+            if (cj + 1 < nj && (uint32_t)(rcw_draw(m, base + id) >> 32) < loops) open_tile(words, (2 * ci + 1) + H * (2 * cj + 2));
+            if (ci + 1 < ni && (uint32_t)(rcw_draw(m, base + id + 1ull) >> 32) < loops) open_tile(words, (2 * ci + 2) + H * (2 * cj + 1));
         }
     }
     __syncthreads();
+}
+
+// The key of the layout of the episode an agent began (counter ep): the episode's own draw 2^63 (the bank's index), or the key of the level it
+// picks; *level: what wall_layout[a] says.
+__device__ __forceinline__ uint64_t layout_key(const RcwDev& p, const RcwWallGen& g, int a, uint32_t ep, int* level)
+{
+    const uint64_t key = rcw_episode_key(p.seed, (uint64_t)(p.agent_id_offset + a), (uint64_t)(ep - 1u));
+    const uint64_t u = rcw_draw(key, kLayoutDraw);
+    *level = -1;
+    if (g.levels <= 0) return u;
+    *level = g.first_level + (int)rcw_below(u, (uint64_t)g.levels);
+    return rcw_episode_key(g.level_seed, (uint64_t)*level, 0ull);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBankBlock) void rcw_wall_generator_kernel(const RcwDev p, const RcwLimit lim, const RcwWallBank b, const RcwWallGen g, const int force)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_g[];
+    const int a = blockIdx.x, lane = threadIdx.x;
+    if (a >= p.B) return;
+    const uint32_t ep = p.episode[a];
+    if (!force && b.last_episode[a] == ep) {
+        if (lane == 0) b.mask[a] = 0;
+        return;
+    }
+    int level;
+    const uint64_t m = layout_key(p, g, a, ep, &level);
+    maze_in_lds(lds_g, lds_g + ((p.nwords + 1) & ~1), p.H, p.H * p.W, p.nwords, g.ni, g.nj, m, g.loops, lane);   // (the scratch: 8-byte aligned)
+    restart_on_lds_words<T>(p, lim, b, a, lane, lds_g, ep, level);
+}
+
+// ---- the wall generator: caves (include/rcw.h, "the wall generator: caves") --------------------------------------------------------------
+// rcw_wall_caves_kernel<T>   the generator's kernel with another layout: the same launch point, common path, key and tail.  An agent that
+//          began an episode gets cave(m, H, W, fill, smooth), made by the whole wave in LDS over the n = (H - 2)(W - 2) INTERIOR tiles,
+//          q = (i - 1) + (H - 2)(j - 1) — the tile map's own order, so the smallest q of a region is its smallest tile index:
+//            words   [nwords]  the tile map's words, written last;
+//            label   [n]       per free tile the tile that names its region (label[root] == root), kNoLabel on a wall;
+//            count   [n]       per root its region's tiles (ds_add);
+//            plane   [2][n]    generations g and g + 1, a byte a tile (1 = WALL); the ring is not stored: a neighbour outside the
+//                              interior counts as WALL.
+//          Lane takes tiles lane + 64 i.  Generation 0 is one draw a tile; a smoothing step reads one plane and writes the other.  Labels:
+//            hook    every free tile takes the smallest label among itself and its free 4-neighbours, and hangs the tile its label named
+//                    under that one too (ds_min): labels only fall, and a label always names a tile of the same region at or below its owner;
+//            jump    label[q] = label[label[q]] until nothing moves;
+//          until a hook moves nothing (__syncthreads_or): then neighbours agree, every label is a root, and the root of a region is its
+//          smallest tile — no iteration cap.  One ds_max of (size << 16) | (0xFFFF - root) over the roots picks the largest region, of equals
+//          the one with the smallest root (n <= 4096: the size fits 13 bits, the root 16).  Every lane reads that word back: a kept region of
+//          `need` tiles opens its tiles in `words`; anything less is the fallback, maze(m, H, W, 0) by maze_in_lds, whose slots and labels
+//          alias label / count / plane (12 bytes a cell, ni nj <= 4 n / 9).  Every barrier is the wave's own and under a uniform condition:
+//          the agent, kernel arguments, __syncthreads_or's result, the word every lane read after a barrier.
+constexpr uint32_t kNoLabel = 0xFFFFFFFFu;
+constexpr uint64_t kCaveDraw = 0x4000000000000000ull;
+
+template <typename T>
+__global__ __launch_bounds__(kBankBlock) void rcw_wall_caves_kernel(const RcwDev p, const RcwLimit lim, const RcwWallBank b, const RcwWallGen g, const RcwWallCaves cv,
+                                                                    const int force)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_c[];
+    __shared__ uint32_t best;
+    const int a = blockIdx.x, lane = threadIdx.x;
+    if (a >= p.B) return;
+    const uint32_t ep = p.episode[a];
+    if (!force && b.last_episode[a] == ep) {
+        if (lane == 0) b.mask[a] = 0;
+        return;
+    }
+    const int H = p.H, nwords = p.nwords, HW = p.H * p.W, h = p.H - 2, w = p.W - 2, n = h * w;
+    uint32_t* const words = lds_c;
+    uint32_t* const label = lds_c + ((nwords + 1) & ~1);                    // (8-byte aligned: the maze's slots alias it)
+    uint32_t* const count = label + n;
+    uint8_t* plane = reinterpret_cast<uint8_t*>(count + n);
+    uint8_t* next = plane + n;
+    int level;
+    const uint64_t m = layout_key(p, g, a, ep, &level);
+    // generation 0
+    for (int q = lane; q < n; q += kBankBlock) {
+        const int jj = q / h, ii = q - jj * h;
+        const uint64_t t = (uint64_t)((ii + 1) + H * (jj + 1));
+        plane[q] = (uint32_t)(rcw_draw(m, kCaveDraw + t) >> 32) < cv.fill ? 1 : 0;
+    }
+    if (lane == 0) best = 0u;
+    __syncthreads();
+    // smoothing: WALL in g + 1 where at least 5 of the 3 x 3 are WALL in g
+    for (int s = 0; s < cv.smooth; ++s) {
+        for (int q = lane; q < n; q += kBankBlock) {
+            const int jj = q / h, ii = q - jj * h;
+            int walls = 0;
+            for (int dj = -1; dj <= 1; ++dj)
+                for (int di = -1; di <= 1; ++di) {
+                    const int i2 = ii + di, j2 = jj + dj;
+                    walls += (i2 < 0 || i2 >= h || j2 < 0 || j2 >= w) ? 1 : (int)plane[i2 + h * j2];
+                }
+            next[q] = walls >= 5 ? 1 : 0;
+        }
+        __syncthreads();
+        uint8_t* const swap = plane; plane = next; next = swap;
+    }
+    // regions
+    for (int q = lane; q < n; q += kBankBlock) {
+        label[q] = plane[q] ? kNoLabel : (uint32_t)q;
+        count[q] = 0u;
+    }
+    __syncthreads();
+    for (;;) {
+        int hooked = 0;
+        for (int q = lane; q < n; q += kBankBlock) {                       // hook
+            const uint32_t mine = label[q];
+            if (mine == kNoLabel) continue;
+            const int jj = q / h, ii = q - jj * h;
+            uint32_t least = mine;                                          // (a wall's kNoLabel never wins a min)
+            if (ii > 0) least = min(least, label[q - 1]);
+            if (ii + 1 < h) least = min(least, label[q + 1]);
+            if (jj > 0) least = min(least, label[q - h]);
+            if (jj + 1 < w) least = min(least, label[q + h]);
+            if (least < mine) { atomicMin(&label[mine], least); atomicMin(&label[q], least); hooked = 1; }
+        }
+        if (!__syncthreads_or(hooked)) break;
+        for (;;) {                                                         // jump: any value read names a tile of the region at or below: the race is benign
+            int moved = 0;
+            for (int q = lane; q < n; q += kBankBlock) {
+                const uint32_t l = label[q];
+                if (l == kNoLabel) continue;
+                const uint32_t ll = label[l];
+                if (ll != l) { label[q] = ll; moved = 1; }
+            }
+            if (!__syncthreads_or(moved)) break;
+        }
+    }
+    for (int q = lane; q < n; q += kBankBlock) {
+        const uint32_t l = label[q];
+        if (l != kNoLabel) atomicAdd(&count[l], 1u);
+    }
+    __syncthreads();
+    for (int q = lane; q < n; q += kBankBlock)
+        if (label[q] == (uint32_t)q) atomicMax(&best, (count[q] << 16) | (0xFFFFu - (uint32_t)q));
+    __syncthreads();
+    const uint32_t kept = best;                                            // (the same word on every lane)
+    const int size = (int)(kept >> 16), need = max(7, n / 4);
+    if (size >= need) {
+        const uint32_t root = 0xFFFFu - (kept & 0xFFFFu);
+        for (int x = lane; x < nwords; x += kBankBlock) {
+            const int left = HW - 16 * x;                                  // tiles of this word inside the map (the padding stays clear)
+            words[x] = left >= 16 ? 0x55555555u : left <= 0 ? 0u : (0x55555555u & ((1u << (2 * left)) - 1u));
+        }
+        __syncthreads();
+        for (int q = lane; q < n; q += kBankBlock) {
+            if (label[q] != root) continue;
+            const int jj = q / h, ii = q - jj * h;
+            open_tile(words, (ii + 1) + H * (jj + 1));
+        }
+        __syncthreads();
+    } else {
+        maze_in_lds(words, label, H, HW, nwords, g.ni, g.nj, m, 0u, lane);
+    }
     restart_on_lds_words<T>(p, lim, b, a, lane, words, ep, level);
 }
 
@@ -278,5 +416,26 @@ hipError_t rcw_launch_wall_generator(const RcwPlan& p, const RcwWallBank& agents
     const size_t lds = (size_t)((p.nwords + 1) & ~1) * sizeof(uint32_t) + (size_t)cells * 12u;
     if (p.real64) hipLaunchKernelGGL(rcw_wall_generator_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, force ? 1 : 0);
     else          hipLaunchKernelGGL(rcw_wall_generator_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, force ? 1 : 0);
+    return hipGetLastError();
+}
+
+// LDS: the words (an even count), then per interior tile 4 bytes of label, 4 of counter and the two planes' bytes — or, where that is more,
+// the fallback's 12 bytes a cell (it never is: ni nj <= 4 n / 9).  At the 4096-tile bound: 66 x 66 has 274 words, 42,056 bytes; the largest
+// request is 5 x 1367's (4095 tiles, 428 words): 42,664 bytes, under the 64 KiB default.
+size_t rcw_wall_caves_lds_bytes(int H, int W, int nwords)
+{
+    const size_t n = (size_t)(H - 2) * (size_t)(W - 2), cells = (size_t)((H - 1) / 2) * (size_t)((W - 1) / 2);
+    const size_t cave = (n * 10u + 3u) & ~(size_t)3u, maze = cells * 12u;
+    return (size_t)((nwords + 1) & ~1) * sizeof(uint32_t) + (cave > maze ? cave : maze);
+}
+
+hipError_t rcw_launch_wall_caves(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, const RcwWallCaves& caves, bool force, hipStream_t s)
+{
+    const long long n = (long long)(p.H - 2) * (long long)(p.W - 2);
+    if (p.B < 1) return hipSuccess;
+    if (p.H < 5 || p.W < 5 || n > kWallCavesMaxTiles) return hipErrorInvalidValue;
+    const size_t lds = rcw_wall_caves_lds_bytes(p.H, p.W, p.nwords);
+    if (p.real64) hipLaunchKernelGGL(rcw_wall_caves_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, caves, force ? 1 : 0);
+    else          hipLaunchKernelGGL(rcw_wall_caves_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, caves, force ? 1 : 0);
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 """Wall layouts for `SingleRoom.set_walls`: host-side numpy, nothing here touches the device (`generated_maze` and
-`generated_maze_key` call the library's two handle-less host functions: no device either).
+`generated_maze_key` and `generated_cave` call the library's handle-less host functions: no device either).
 
 A layout is bool (H, W) with `walls[i-1, j-1]` = tile (i, j) is a WALL — the index order of `env.world.tile_map[b, 0]`.
 Every generator returns the wall ring (SR:57-60) closed, as `rcw_set_walls` requires, and at least two free interior
@@ -113,6 +113,25 @@ def generated_maze(maze_key: int, H: int, W: int, loops=0.0) -> np.ndarray:
     if rc != _capi.RCW_OK:
         raise ValueError(_capi.last_error(lib))
     return np.ascontiguousarray(out.T != 0)
+
+
+def generated_cave(key: int, H: int, W: int, fill=0.40, smooth: int = 2, return_fell_back: bool = False):
+    """The wall generator's cave of one 64-bit key (`generated_maze_key` serves both families), bool (H, W): the interior filled
+    with probability `fill` (an int: the UInt32 word itself), smoothed `smooth` times, pruned to its largest region — or, where that
+    region is too small, the perfect maze of the key; `return_fell_back=True` returns (walls, fell_back).
+    rcw_wall_caves_layout: host arithmetic (a queue flood fill), no device — what an agent's `env.world.walls[a]` holds."""
+    import ctypes as C
+
+    from . import _capi
+
+    lib = _capi.load()
+    out = np.empty((max(int(W), 0), max(int(H), 0)), dtype=np.uint8)   # tile (i, j), 0-based, at i + H j
+    fell = C.c_int32()
+    rc = lib.rcw_wall_caves_layout(int(H), int(W), int(key), loops_word(fill), int(smooth), out.ctypes.data, C.byref(fell))
+    if rc != _capi.RCW_OK:
+        raise ValueError(_capi.last_error(lib))
+    walls = np.ascontiguousarray(out.T != 0)
+    return (walls, bool(fell.value)) if return_fell_back else walls
 
 
 def is_connected(walls) -> bool:

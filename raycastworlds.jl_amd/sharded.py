@@ -101,6 +101,8 @@ class ShardedSingleRoom:
             raise ValueError("a batch built with rng draws its resets on the host: it takes no wall bank")
         if self.rng is not None and kwargs.get("wall_generator") is not None:
             raise ValueError("a batch built with rng draws its resets on the host: it takes no wall generator")
+        if self.rng is not None and kwargs.get("wall_caves") is not None:
+            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall caves")
         self.env = env_factory(batch=self.count, agent_id_offset=self.first,
                                device=default_device() if device is None else device, **kwargs)
         self._abi_comm = False
@@ -193,6 +195,13 @@ class ShardedSingleRoom:
         if self.rng is not None and loops is not None:
             raise ValueError("a batch built with rng draws its resets on the host: it takes no wall generator")
         self.env.set_wall_generator(loops, levels, first_level, level_seed)
+
+    def set_wall_caves(self, fill=0.40, smooth: int = 2, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
+        """`SingleRoom.set_wall_caves` for the sharded batch: the parameters are REPLICATED — every rank passes the same — and
+        nothing else is needed: the cave an agent's episode gets is keyed by its global id (`agent_id_offset`)."""
+        if self.rng is not None and fill is not None:
+            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall caves")
+        self.env.set_wall_caves(fill, smooth, levels, first_level, level_seed)
 
     def set_wall_bank_weights(self, weights) -> None:
         """`SingleRoom.set_wall_bank_weights`, the same weights on every rank."""

@@ -349,7 +349,9 @@ class SingleRoom:
     of `set_local_map`'s keywords) `set_local_map` last.  `wall_bank` / `wall_bank_weights` (this build's addition) are `set_wall_bank`'s
     arguments, applied after `walls` and the time limit and before the features: a layout drawn on the device at every episode start.
     `wall_generator` (this build's addition; a dict of `set_wall_generator`'s keywords, `{}` for the defaults) is applied in the same
-    place: a new maze made on the device at every episode start.  It and `wall_bank` exclude each other.
+    place: a new maze made on the device at every episode start.  It and `wall_bank` exclude each other.  `wall_caves` (this build's
+    addition; a dict of `set_wall_caves`' keywords, `{}` for the defaults) is applied right behind it: a new cave made on the device at
+    every episode start.  It excludes `wall_bank` and `wall_generator`.
     """
 
     def __init__(
@@ -388,6 +390,7 @@ class SingleRoom:
         wall_bank=None,
         wall_bank_weights=None,
         wall_generator=None,
+        wall_caves=None,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -491,6 +494,12 @@ class SingleRoom:
         if wall_generator is not None:
             try:
                 self.set_wall_generator(**dict(wall_generator))
+            except BaseException:
+                self._handle.close()
+                raise
+        if wall_caves is not None:
+            try:
+                self.set_wall_caves(**dict(wall_caves))
             except BaseException:
                 self._handle.close()
                 raise
@@ -1158,6 +1167,41 @@ class SingleRoom:
         self._check(self._lib.rcw_wall_generator_info(self._h, C.byref(on), C.byref(loops), C.byref(levels), C.byref(first), C.byref(seed)))
         return {"enabled": bool(on.value), "loops": loops.value, "levels": levels.value, "first_level": first.value, "level_seed": seed.value}
 
+    # ---- the wall generator: caves (include/rcw.h, rcw_set_wall_caves) ------------------
+    def set_wall_caves(self, fill=0.40, smooth: int = 2, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
+        """A new cave made on the device at every start of an episode, where `set_wall_generator` makes a maze: a random fill of the
+        interior (`fill`: the probability of a wall, or the UInt32 word itself as `loops` takes one), smoothed `smooth` times (0 .. 8)
+        by the 5-of-9 automaton, pruned to its largest 4-connected region.  A cave whose region has fewer than
+        max(7, (H-2)(W-2) // 4) tiles is replaced by the perfect maze of the same key — on small maps that is most of them (nearly
+        all at 5 x 7, about a quarter at 8 x 8, none at 32 x 32 at the defaults).  `levels`, `first_level`, `level_seed` and
+        `wall_layout` are the generator's; `layouts.generated_cave(layouts.generated_maze_key(...)[0], H, W, fill, smooth)` replays
+        any of them on the host.  Maps of 5 x 5 up to 4096 interior tiles (66 x 66).  `set_walls`, `set_wall_bank` and
+        `set_wall_generator` are refused while caves are on, and caves while a bank or the generator is; `set_wall_caves(None)`
+        switches them off, the agents keep their walls.  An environment built with `rng` draws its resets on the host and takes
+        no caves."""
+        self.__dict__.pop("_wall_layout_dev", None)
+        if fill is None:
+            self._check(self._lib.rcw_set_wall_caves(self._h, 0, 0, 0, 0, 0, 0))
+            return
+        if self.rng is not None:
+            raise ValueError("an environment built with rng draws its resets on the host: it takes no wall caves")
+        from . import layouts as _layouts
+
+        word = _layouts.loops_word(fill)
+        for name, v, top in (("smooth", smooth, 2 ** 31 - 1), ("levels", levels, 2 ** 31 - 1), ("first_level", first_level, 2 ** 31 - 1),
+                             ("level_seed", level_seed, 2 ** 64 - 1)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not (-2 ** 31 if name == "smooth" else 0) <= int(v) <= top:
+                raise ValueError(f"{name} must be an integer in 0 .. {top}, got {v!r}")
+        self._check(self._lib.rcw_set_wall_caves(self._h, 1, word, int(smooth), int(levels), int(first_level), int(level_seed)))
+
+    @property
+    def wall_caves_info(self) -> dict:
+        """`enabled`, `fill` (the UInt32 word) and `smooth` of the caves (rcw_wall_caves_info); zeros while they are off.  The level
+        parameters read from `wall_generator_info`, which reports `enabled` and `loops == 0` while caves are on."""
+        on, fill, smooth = C.c_int32(), C.c_uint32(), C.c_int32()
+        self._check(self._lib.rcw_wall_caves_info(self._h, C.byref(on), C.byref(fill), C.byref(smooth)))
+        return {"enabled": bool(on.value), "fill": fill.value, "smooth": smooth.value}
+
     def _wall_layout_host(self) -> np.ndarray:
         out = np.empty(self.batch, dtype=np.int32)
         self.host_syncs += 1
@@ -1168,7 +1212,7 @@ class SingleRoom:
     def wall_layout(self) -> DeviceArray:
         """int32 (B,) in device memory: the bank layout each agent's current episode was given — with the wall generator its level, or
         -1 — (`.torch(sync=False)` on the GPU, `np.asarray(env.wall_layout)` for a host copy).  Valid until the next `set_wall_bank`
-        or `set_wall_generator`."""
+        , `set_wall_generator` or `set_wall_caves`."""
         if getattr(self, "_wall_layout_dev", None) is None:
             p = C.c_void_p()
             self._check(self._lib.rcw_wall_layout_device_ptr(self._h, C.byref(p)))

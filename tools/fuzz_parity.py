@@ -3,7 +3,7 @@
 configurations (map size, columns, headings, field of view, radius, step, camera height, image
 height, world-unit type, the three unpinned switches, both BoundsError policies, auto-reset).
 
-    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit|goal|bank|gen]
+    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit|goal|bank|gen|caves]
                                                                    # "top": every configuration renders the top view;
                                                                    # "split": ... with a geometry of the unit store kernels;
                                                                    # "flat": ... of the flat store kernel (any pu >= 9), and any
@@ -21,6 +21,9 @@ height, world-unit type, the three unpinned switches, both BoundsError policies,
                                                                    # "gen": the wall generator (rcw_set_wall_generator) — random maps, loops, level
                                                                    #         ranges and sequences of calls against tests/wall_generator_ref.py, compared
                                                                    #         the same way (gen_mode below)
+                                                                   # "caves": the caves (rcw_set_wall_caves) — random maps, fills, smoothing counts,
+                                                                   #         level ranges and sequences of calls against tests/wall_caves_ref.py,
+                                                                   #         compared the same way (caves_mode below)
 """
 import os
 import sys
@@ -343,12 +346,120 @@ def gen_mode(n_cfg, seed):
     return 1 if fails else 0
 
 
+def caves_mode(n_cfg, seed):
+    """gen_mode's draw for the caves: maps of 5 x 5 to 40 x 40 tiles (up to 38 x 38 = 1444 interior tiles); fill 0.2 .. 0.6 (now and then 0
+    or all wall), smoothed 0 .. 8 times; no levels, or 1, 2 or 5; 1 to 9 agents with 8 or 16 view columns, Float32 and Float64, both forms
+    of the step asked for, a time limit of 0, 2 or 5, auto_reset.  Then 30 random calls — a step, a masked or full reset_ with a new seed, a
+    masked set_state onto free tiles of each agent's current layout, some agents walked into their goals (wall_bank_cases.
+    walk_into_the_goal: in open caves a random walk rarely arrives), the caves off and others on —, each made on the reference
+    (tests/wall_caves_cases.py's Recorder) and on the engine (its Player), which compares the whole state, the frames, the time limit's
+    words and wall_layout after every call.  Every configuration draws from default_rng([seed, c])."""
+    import wall_caves_cases as CC
+    from raycastworlds_jl_amd import _capi
+
+    rng = None
+
+    def caves():
+        levels = int(rng.choice([0, 0, 1, 2, 5]))
+        fill = [0.2, 0.3, 0.4, 0.4, 0.45, 0.5, 0.6, 0.0, 1.0][int(rng.integers(0, 9))]
+        return dict(fill=fill, smooth=int(rng.integers(0, 9)), levels=levels, first_level=int(rng.integers(0, 2**31 - 1 - levels)) if levels else 0,
+                    level_seed=int(rng.integers(0, 2**63)) if levels else 0)
+
+    def some(B):
+        mask = (rng.random(B) < 0.5).astype(np.uint8)
+        mask[int(rng.integers(0, B))] = 1
+        return mask
+
+    totals = dict(step=0, reset=0, masked_reset=0, set_state=0, arrive=0, off_and_on=0, episode_starts=0, fallbacks=0, caves_kept=0, goal_redraws=0,
+                  restarts_after_done=0, restarts_after_truncation=0, one_launch_steps=0, two_launch_steps=0, non_square=0, with_levels=0,
+                  smoothed=0, tiles_past_64=0)
+    fails = 0
+    for c in range(n_cfg):
+        rng = np.random.default_rng([seed, c])
+        H, W = int(rng.integers(5, 41)), int(rng.integers(5, 41))
+        if c % 4 == 0:
+            H, W = int(rng.integers(5, 9)), int(rng.integers(5, 9))          # (a quarter small: agents arrive, restarts after done)
+        B = int(rng.integers(1, 10))
+        T64, L = bool(rng.integers(0, 2)), int(rng.choice([0, 2, 5]))
+        N, Hc = [(8, 64), (16, 64), (8, 24), (16, 128)][int(rng.integers(0, 4))]
+        form = str(rng.choice(["one-launch", "two-launches"]))
+        engine_seed = int(rng.integers(0, 2**31))
+        shape = dict(H=H, W=W, N=N, Hc=Hc, B=B, seed=engine_seed, T="Float64" if T64 else "Float32")
+        where = f"config {c}: {H} x {W}, B={B} T64={T64} L={L} N={N} Hc={Hc} {form} seed={engine_seed}"
+        try:
+            env = CC.make_env(RCW, shape)
+            try:
+                env.set_step_form(form)
+            except _capi.RcwError as e:
+                assert form == "one-launch" and e.code == _capi.RCW_ERR_UNSUPPORTED and "does not take the one-launch step" in e.message, e
+                form = "two-launches"
+            totals["one_launch_steps" if form == "one-launch" else "two_launch_steps"] += 1
+            totals["non_square"] += int(H != W)
+            totals["tiles_past_64"] += int((H - 2) * (W - 2) > 64)
+            rec = CC.Recorder(shape)
+            play = CC.Player(RCW, env, rec.snaps, where)
+            both = lambda call, *a, **k: (getattr(rec, call)(*a, **k), getattr(play, call)(*a, **k))
+            if L:
+                both("set_time_limit", L)
+
+            def install():
+                g = caves()
+                totals["with_levels"] += int(g["levels"] > 0)
+                totals["smoothed"] += int(g["smooth"] > 0)
+                both("set_wall_caves", **g)
+
+            install()
+            for k in range(30):
+                call = str(rng.choice(["step", "step", "step", "step", "step", "step", "reset", "masked_reset", "set_state", "arrive", "off_and_on"]))
+                play.name = f"{where}, call {k} ({call})"
+                totals[call] += 1
+                if call == "step":
+                    both("step", rng.integers(1, 5, B).astype(np.uint8))
+                elif call in ("reset", "masked_reset"):
+                    both("reset", some(B) if call == "masked_reset" else None, int(rng.integers(0, 2**31)))
+                elif call == "set_state":
+                    mask, s = some(B), rec.snaps[-1]
+                    goal, pos, heading = s["goal"].copy(), s["position"].copy(), s["direction"].copy()
+                    for b in np.flatnonzero(mask):
+                        free = np.argwhere(~rec.ref.walls_of(b))
+                        goal[b] = free[int(rng.integers(0, len(free)))] + 1
+                        pos[b] = free[int(rng.integers(0, len(free)))] + 0.5
+                        heading[b] = int(rng.integers(0, 8))
+                    both("set_state", goal, pos, heading, mask)
+                elif call == "arrive":
+                    mask = some(B)
+                    for b in np.flatnonzero(mask):                           # (a region in one row has no tile to walk down from)
+                        free = ~rec.ref.walls_of(b)
+                        mask[b] = int((free[:-1] & free[1:]).any())
+                    CC.walk_into_the_goal(rec, mask)
+                    CC.walk_into_the_goal(play, mask)
+                else:
+                    both("set_wall_caves", None)
+                    both("step", rng.integers(1, 5, B).astype(np.uint8))
+                    install()
+            play.finished()
+            for k, v in rec.events.items():
+                if k in totals:
+                    totals[k] += v
+            totals["caves_kept"] += rec.events["episode_starts"] - rec.events["fallbacks"]
+            env.close()
+        except Exception as e:   # noqa: BLE001
+            fails += 1
+            print(f"{where} FAILED\n   {type(e).__name__}: {str(e)[:400]}")
+            if fails >= 5:
+                break
+    print(f"{n_cfg} random configurations (wall caves: " + ", ".join(f"{v} {k}" for k, v in totals.items()) + f"), {fails} mismatches")
+    return 1 if fails else 0
+
+
 if len(sys.argv) > 3 and sys.argv[3] == "goal":
     sys.exit(goal_mode(n_cfg, int(sys.argv[2])))
 if len(sys.argv) > 3 and sys.argv[3] == "bank":
     sys.exit(bank_mode(n_cfg, int(sys.argv[2])))
 if len(sys.argv) > 3 and sys.argv[3] == "gen":
     sys.exit(gen_mode(n_cfg, int(sys.argv[2])))
+if len(sys.argv) > 3 and sys.argv[3] == "caves":
+    sys.exit(caves_mode(n_cfg, int(sys.argv[2])))
 limit_events = {}
 one_launch_steps = 0
 two_kernel_forms = 0                                            # (rcw_set_top_view_form: by default it is taken only from 256 MiB a step)
