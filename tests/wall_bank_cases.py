@@ -328,12 +328,12 @@ def recorded(name, render=True, offset=0, batch=None):
     return rec.snaps, rec.events
 
 
-def play(rcw, name, env, trackers=()):
+def play(rcw, name, env, trackers=(), wrap=None):
     """the scenario on `env` against its recording; trackers(player) -> the feature trackers, made once the player has checked the fresh state"""
     fn, _ = SCENARIOS[name]
     snaps, events = recorded(name)
     p = Player(rcw, env, snaps, name)
     p.trackers = list(trackers)
-    fn(p)
+    fn(p if wrap is None else wrap(p))                                       # (wrap: tests/deferred.py takes a note behind every call)
     p.finished()
     return events
