@@ -624,6 +624,54 @@ RCW_API int rcw_set_wall_caves(rcw_handle* h, int32_t enable, uint32_t fill, int
 RCW_API int rcw_wall_caves_info(rcw_handle* h, int32_t* enabled, uint32_t* fill, int32_t* smooth);
 RCW_API int rcw_wall_caves_layout(int32_t H, int32_t W, uint64_t key, uint32_t fill, int32_t smooth, uint8_t* out_host /* (H*W), rcw_set_walls' order */,
                                   int32_t* fell_back);
+/* ---- the wall generator: rooms (this build's addition: a third family of layouts behind the generator's launch point) --------------------
+ * Opt-in per handle.  Rectangular rooms of different sizes joined by doorways, layouts.four_rooms' topology made anew every episode: the
+ * interior is split recursively by walls with one or two doors.  No fallback and no prune: connected by construction from 5 x 5.
+ * ROOMS FROM ONE KEY  rooms(m, H, W, room, stop, doors), H, W >= 5, with draw(m, n) and below(u, r) of csrc/rcw_rng.h; tiles are 0-based
+ * (i, j) with index t = i + H j.  room is Int32 >= 1 (a room's least side); stop and doors are UInt32 probability words as loops and fill
+ * are.  The ring is WALL, the interior starts free.  A CHAMBER is a rectangle of interior tiles [i0..i1] x [j0..j1], bounds inclusive; the
+ * root is [1..H-2] x [1..W-2]; i0 and j0 are always odd.  A chamber's draws have the indices n + k, n = 2^61 + 8 ((t0 << 16) | t1) with
+ * t0 = i0 + H j0, t1 = i1 + H j1 (so H W <= 65536): distinct rectangles, distinct indices, all in [2^61, 2^61 + 2^35) — away from the
+ * maze's (below 2^21), the caves' (from 2^62), the layout draw (2^63) and reset_agent's (from 0).  One chamber:
+ *   walls    row walls R = { even i : i0 + room <= i <= i1 - room }, empty unless j1 > j0; column walls C = { even j : j0 + room <= j <=
+ *            j1 - room }, empty unless i1 > i0.  Both empty: the chamber is a room.
+ *   stop     a chamber other than the root is left whole, a room, where (draw(m, n + 1) >> 32) < stop.
+ *   side     only one of R, C non-empty: that one.  Both: cut across the longer side — a row wall where i1 - i0 > j1 - j0, a column wall
+ *            where it is shorter, on a tie a row wall where bit 63 of draw(m, n) is set.
+ *   line     s = the below(draw(m, n + 2), |S|)-th element of the chosen set S, ascending.
+ *   doors    the wall covers the chamber's whole span on line s: positions lo .. hi (j0 .. j1 for a row wall, i0 .. i1 for a column wall).
+ *            Door candidates are lo, lo + 2, ... (odd): cnt = (hi - lo) / 2 + 1 of them.  The first door is at lo + 2 below(draw(m, n + 3),
+ *            cnt); where (draw(m, n + 4) >> 32) < doors a second one at lo + 2 below(draw(m, n + 5), cnt), which may coincide with the
+ *            first.  Every other tile of the span on line s becomes WALL.
+ *   children the rectangles on either side of line s.
+ *   Walls lie on even lines and doors on odd positions, so a later perpendicular wall ends on an even position: it never blocks a door and
+ *   never overlaps an earlier wall.  The layout is connected and ring-closed, has at least 7 free interior tiles, every room side is at
+ *   least `room`, and it does not depend on the order the chambers are taken in (the device cuts every chamber of a depth in one round,
+ *   rcw_wall_rooms_layout below walks depth first off a stack).  Every room holds an (odd, odd) tile: at most
+ *   Q = ceil((H - 2) / 2) ceil((W - 2) / 2) rooms.
+ * THE KEY OF AN EPISODE is the generator's, unchanged: rcw_wall_generator_key serves this family too (levels, first_level, level_seed,
+ * wall_layout).  After the layout the rule is the bank's, word for word.  The ABI is additive: RCW_ABI_VERSION, rcw_config and every
+ * existing export are what they were; a handle without rooms launches what it launched.
+ *   rcw_set_wall_rooms            enable != 0: installs the rooms and restarts EVERY agent under the rule with the handle's current seed, as
+ *                                 rcw_set_wall_generator does.  Validated on the host before anything is queued, a refusal leaves the
+ *                                 handle untouched: RCW_ERR_INVALID_ARGUMENT for H or W below 5, room < 1 or a bad level range;
+ *                                 RCW_ERR_UNSUPPORTED for Q > 4096 (130 x 130 and 5 x 4097 are the largest; the message names the bound)
+ *                                 or H W > 65536, and while a bank, the maze generator or caves are on.  enable == 0 switches them off
+ *                                 (RCW_OK also where there were none): the walls stay.  The parameters are kernel arguments fixed at
+ *                                 install: a captured step replays correctly.
+ *   while rooms are on            rcw_set_wall_bank, rcw_set_walls, rcw_set_wall_generator(enable != 0) and rcw_set_wall_caves(enable != 0):
+ *                                 RCW_ERR_UNSUPPORTED, nothing changes (their enable == 0 forms are RCW_OK and change nothing either).
+ *                                 rcw_set_state* keeps the layout.  rcw_wall_layout* serve l, or -1.  rcw_wall_generator_info reports
+ *                                 enabled = 1, loops = 0 and the level parameters.
+ *   rcw_wall_rooms_info           enabled, room, stop, doors (any pointer may be NULL); zeros while rooms are off.
+ *   rcw_wall_rooms_layout         handle-less, pure host arithmetic: rooms(key, H, W, room, stop, doors) as UInt8 (H*W) in rcw_set_walls'
+ *                                 order (1 = wall); *rooms (may be NULL) = the number of rooms.  The refusals of a geometry and of room
+ *                                 are rcw_set_wall_rooms'. */
+RCW_API int rcw_set_wall_rooms(rcw_handle* h, int32_t enable, int32_t room, uint32_t stop, uint32_t doors, int32_t levels, int32_t first_level,
+                               uint64_t level_seed);
+RCW_API int rcw_wall_rooms_info(rcw_handle* h, int32_t* enabled, int32_t* room, uint32_t* stop, uint32_t* doors);
+RCW_API int rcw_wall_rooms_layout(int32_t H, int32_t W, uint64_t key, int32_t room, uint32_t stop, uint32_t doors, uint8_t* out_host /* (H*W), rcw_set_walls' order */,
+                                  int32_t* rooms);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

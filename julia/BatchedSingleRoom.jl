@@ -648,6 +648,54 @@ function generated_cave(key::Integer, H::Integer, W::Integer; fill::Real = 0.40,
     return (out .!= 0, fell[] != 0)
 end
 
+# ---- the wall generator: rooms (this build's addition; include/rcw.h, rcw_set_wall_rooms) -----------------------------------------
+"""
+    set_wall_rooms!(env; room = 2, stop = 0.25, doors = 0.25, levels = 0, first_level = 0, level_seed = 0)
+    set_wall_rooms!(env, nothing)
+
+New rooms made on the device at every start of an episode, where `set_wall_generator!` makes a maze: the interior is split
+recursively by walls on even lines, each with a door and, with probability `doors`, a second one; a chamber other than the whole
+interior is left a room with probability `stop` (both scaled to `UInt32` as `loops` is); no room side falls below `room`.  Connected by
+construction from 5 x 5: no fallback.  The level parameters and `wall_layout(env)` are the generator's.  Maps up to
+`cld(H-2, 2) * cld(W-2, 2) == 4096` (130 x 130, 5 x 4097).  `set_walls!`, `set_wall_bank!`, `set_wall_generator!` and `set_wall_caves!`
+are refused while rooms are on; `set_wall_rooms!(env, nothing)` switches them off, the agents keep their walls.  An environment built
+with `rng` takes no rooms.
+"""
+function set_wall_rooms!(env::BatchedSingleRoom; room::Integer = 2, stop::Real = 0.25, doors::Real = 0.25, levels::Integer = 0, first_level::Integer = 0,
+                         level_seed::Integer = 0)
+    env.rng === nothing || throw(ArgumentError("an environment built with rng draws its resets on the host: it takes no wall rooms"))
+    (0 <= stop <= 1 && 0 <= doors <= 1) || throw(ArgumentError("stop and doors are probabilities in [0, 1]"))
+    word(p) = UInt32(min(floor(UInt64, Float64(p) * 2.0^32), UInt64(0xFFFFFFFF)))
+    check(ccall((:rcw_set_wall_rooms, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, UInt32, UInt32, Int32, Int32, UInt64),
+                env.handle, 1, room, word(stop), word(doors), levels, first_level, level_seed))
+    env.stale = true
+    return nothing
+end
+function set_wall_rooms!(env::BatchedSingleRoom, ::Nothing)
+    check(ccall((:rcw_set_wall_rooms, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, UInt32, UInt32, Int32, Int32, UInt64), env.handle, 0, 0, 0, 0, 0, 0, 0))
+    return nothing
+end
+function wall_rooms_info(env::BatchedSingleRoom)
+    on = Ref{Int32}(0); room = Ref{Int32}(0); stop = Ref{UInt32}(0); doors = Ref{UInt32}(0)
+    check(ccall((:rcw_wall_rooms_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{UInt32}, Ref{UInt32}), env.handle, on, room, stop, doors))
+    return (enabled = on[] != 0, room = room[], stop = stop[], doors = doors[])
+end
+"""
+    generated_rooms(key, H, W; room = 2, stop = 0.25, doors = 0.25) -> (BitMatrix (H, W), rooms)
+
+The wall generator's rooms of one key (`generated_maze_key` serves every family; `true` = wall), as an agent's WALL layer holds them,
+and how many rooms there are: host arithmetic (depth first off a stack), no device.
+"""
+function generated_rooms(key::Integer, H::Integer, W::Integer; room::Integer = 2, stop::Real = 0.25, doors::Real = 0.25)
+    (0 <= stop <= 1 && 0 <= doors <= 1) || throw(ArgumentError("stop and doors are probabilities in [0, 1]"))
+    word(p) = UInt32(min(floor(UInt64, Float64(p) * 2.0^32), UInt64(0xFFFFFFFF)))
+    out = Matrix{UInt8}(undef, max(H, 0), max(W, 0))                             # column-major: tile (i, j) at (i - 1) + H (j - 1)
+    rooms = Ref{Int32}(0)
+    check(ccall((:rcw_wall_rooms_layout, librcw), Cint, (Int32, Int32, UInt64, Int32, UInt32, UInt32, Ptr{UInt8}, Ref{Int32}),
+                H, W, key, room, word(stop), word(doors), out, rooms))
+    return (out .!= 0, Int(rooms[]))
+end
+
 # per-agent sticky status: 0, -5 where the reference would have raised BoundsError, -2 for an invalid device action,
 # 1 (a warning) where sample_empty_position gave up after max_tries and returned an occupied tile (utils.jl:34 @warns there)
 function status(env::BatchedSingleRoom)

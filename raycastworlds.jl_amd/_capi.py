@@ -177,6 +177,9 @@ SIGNATURES = {
     "rcw_set_wall_caves": [_vp, _i32, C.c_uint32, _i32, _i32, _i32, _u64],
     "rcw_wall_caves_info": [_vp, C.POINTER(_i32), C.POINTER(C.c_uint32), C.POINTER(_i32)],
     "rcw_wall_caves_layout": [_i32, _i32, _u64, C.c_uint32, _i32, _vp, C.POINTER(_i32)],
+    "rcw_set_wall_rooms": [_vp, _i32, _i32, C.c_uint32, C.c_uint32, _i32, _i32, _u64],
+    "rcw_wall_rooms_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "rcw_wall_rooms_layout": [_i32, _i32, _u64, _i32, C.c_uint32, C.c_uint32, _vp, C.POINTER(_i32)],
     "rcw_ray_table": [_vp, _vp],
     "rcw_direction_table": [_vp, _vp],
     "rcw_timer_start": [_vp],

@@ -431,6 +431,7 @@ int rcw_set_walls(rcw_handle* h, const uint8_t* walls_host, int32_t layouts, con
 {
     int rc = check_handle(h); if (rc) return rc;
     if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
+    if (h->gen.rooms_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle makes its walls with the wall generator's rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))");
     if (h->gen.caves_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle makes its walls with the wall generator's caves; switch them off first (rcw_set_wall_caves(h, 0, ...))");
     if (h->gen.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle makes its walls with the wall generator; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
@@ -1118,6 +1119,7 @@ int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
         wb.dev = RcwWallBank{}; wb.total_weight = 0;
         return RCW_OK;
     }
+    if (h->gen.rooms_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_bank: the handle makes its walls with the wall generator's rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))");
     if (h->gen.caves_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_bank: the handle makes its walls with the wall generator's caves; switch them off first (rcw_set_wall_caves(h, 0, ...))");
     if (h->gen.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_bank: the handle makes its walls with the wall generator; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
@@ -1168,7 +1170,7 @@ int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
 extern "C++" {
 namespace {
 int need_wall_bank(rcw_handle* h) { return h->bank.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no wall bank (rcw_set_wall_bank)"); }
-int need_drawn_walls(rcw_handle* h) { return h->drawn() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator, rcw_set_wall_caves)"); }
+int need_drawn_walls(rcw_handle* h) { return h->drawn() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms)"); }
 }  // namespace
 }  // extern "C++"
 
@@ -1231,6 +1233,7 @@ int rcw_set_wall_generator(rcw_handle* h, int32_t enable, uint32_t loops, int32_
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     rc = plan_wall_generator(H, W, levels, first_level); if (rc) return rc;
     if (wg.caves_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_generator: the handle makes caves; switch them off first (rcw_set_wall_caves(h, 0, ...))");
+    if (wg.rooms_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_generator: the handle makes rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))");
     if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_generator: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
     const size_t B = (size_t)h->B;
     RcwBuf fresh;
@@ -1279,6 +1282,7 @@ int rcw_set_wall_caves(rcw_handle* h, int32_t enable, uint32_t fill, int32_t smo
     rc = plan_wall_caves(H, W, smooth, levels, first_level); if (rc) return rc;
     if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_caves: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
     if (wg.mazes_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_caves: the handle makes mazes; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
+    if (wg.rooms_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_caves: the handle makes rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))");
     const size_t B = (size_t)h->B;
     RcwBuf fresh;
     {
@@ -1307,6 +1311,55 @@ int rcw_wall_caves_info(rcw_handle* h, int32_t* enabled, uint32_t* fill, int32_t
     if (enabled) *enabled = on ? 1 : 0;
     if (fill) *fill = on ? h->gen.cave.fill : 0u;
     if (smooth) *smooth = on ? h->gen.cave.smooth : 0;
+    return RCW_OK;
+}
+
+// The rooms (include/rcw.h, "the wall generator: rooms"): the same sequence once more, the third family's kernel behind the launch point.  The
+// handle keeps them where it keeps the caves; the level rule travels in `par` (loops 0, no grid: rooms have no fallback maze).
+int rcw_set_wall_rooms(rcw_handle* h, int32_t enable, int32_t room, uint32_t stop, uint32_t doors, int32_t levels, int32_t first_level, uint64_t level_seed)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::WallGen& wg = h->gen;
+    if (!enable) {                                                     // off: the agents keep the walls they have
+        if (!wg.rooms_on()) return RCW_OK;
+        RCW_HIP(replace_buffers(h, {&wg.agents}));
+        wg.dev = RcwWallBank{}; wg.par = RcwWallGen{}; wg.room = RcwWallRooms{}; wg.rooms = false;
+        return RCW_OK;
+    }
+    const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
+    rc = plan_wall_rooms(H, W, room, levels, first_level); if (rc) return rc;
+    if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_rooms: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
+    if (wg.mazes_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_rooms: the handle makes mazes; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
+    if (wg.caves_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_rooms: the handle makes caves; switch them off first (rcw_set_wall_caves(h, 0, ...))");
+    const size_t B = (size_t)h->B;
+    RcwBuf fresh;
+    {
+        const hipError_t e = fresh.hipMalloc(3 * B * sizeof(uint32_t) + B);
+        if (e != hipSuccess) return fail(hip_code(e), "wall rooms: %s", hip_failure(e));
+    }
+    RCW_HIP(replace_buffers(h, {&wg.agents}, {&fresh}));
+    uint32_t* const q = wg.agents.get<uint32_t>();
+    wg.dev = RcwWallBank{0, nullptr, nullptr, q, reinterpret_cast<int32_t*>(q + B), reinterpret_cast<int32_t*>(q + 2 * B), reinterpret_cast<uint8_t*>(q + 3 * B)};
+    wg.par = RcwWallGen{0u, levels, first_level, level_seed, 0, 0};
+    wg.room = RcwWallRooms{room, stop, doors};
+    wg.rooms = true;
+    RCW_HIP(hipMemsetAsync(wg.agents.get(), 0, 3 * B * sizeof(uint32_t) + B, h->stream));
+    RCW_HIP(hipMemcpyAsync(wg.dev.status_seen, h->d_status.get(), B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    h->step.reset(false, false, h->dev.auto_reset != 0);
+    RCW_HIP(rcw_launch_reset(h->dev, nullptr, h->stream));             // the counters move by one ...
+    RCW_HIP(launch_wall_bank(h, true));                                // ... and every agent starts that episode in rooms of its own making
+    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));
+    return RCW_OK;
+}
+
+int rcw_wall_rooms_info(rcw_handle* h, int32_t* enabled, int32_t* room, uint32_t* stop, uint32_t* doors)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    const bool on = h->gen.rooms_on();                                 // (zeros while the rooms are off)
+    if (enabled) *enabled = on ? 1 : 0;
+    if (room) *room = on ? h->gen.room.room : 0;
+    if (stop) *stop = on ? h->gen.room.stop : 0u;
+    if (doors) *doors = on ? h->gen.room.doors : 0u;
     return RCW_OK;
 }
 

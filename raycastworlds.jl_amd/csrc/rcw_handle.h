@@ -199,15 +199,19 @@ struct rcw_handle {
     // The wall generator (rcw_set_wall_generator): the bank's per-agent arrays (one allocation, the same order) and the parameters, which
     // travel as kernel arguments.  It and the bank exclude each other; `drawn()` is whichever is on.  The caves (rcw_set_wall_caves) are the
     // generator with another family: `caves` says so, `cave` holds the family's own two parameters, `par` the level rule (loops 0).
+    // The rooms (rcw_set_wall_rooms) are a third one, kept the same way: `rooms` and `room`.
     struct WallGen {
         RcwBuf agents;
         RcwWallBank dev{};
         RcwWallGen par{};
         RcwWallCaves cave{};
         bool caves = false;
+        RcwWallRooms room{};
+        bool rooms = false;
         bool on() const { return agents.get() != nullptr; }
-        bool mazes_on() const { return on() && !caves; }
+        bool mazes_on() const { return on() && !caves && !rooms; }
         bool caves_on() const { return on() && caves; }
+        bool rooms_on() const { return on() && rooms; }
     } gen;
     const RcwWallBank* drawn() const { return bank.on() ? &bank.dev : gen.on() ? &gen.dev : nullptr; }
     ~rcw_handle();
@@ -251,6 +255,7 @@ int plan_local_map(int32_t source, int32_t size, int32_t cells_per_tile, bool re
 int plan_wall_bank_weights(const uint32_t* weights, int32_t layouts, uint32_t* cum, uint64_t* total);
 int plan_wall_generator(int32_t H, int32_t W, int32_t levels, int32_t first_level);
 int plan_wall_caves(int32_t H, int32_t W, int32_t smooth, int32_t levels, int32_t first_level);
+int plan_wall_rooms(int32_t H, int32_t W, int32_t room, int32_t levels, int32_t first_level);
 
 // ---- rcw_step.hip: what a step, a reset or a re-render launches, and the resources those launches need ---------------------------------
 hipError_t launch_top_view_alone(rcw_handle* h, const uint8_t* mask_dev);

@@ -251,3 +251,16 @@ constexpr int kWallCavesMaxTiles = 4096;   // (H - 2)(W - 2): maps up to 66 x 66
 constexpr int kWallCavesMaxSmooth = 8;
 size_t rcw_wall_caves_lds_bytes(int H, int W, int nwords);
 hipError_t rcw_launch_wall_caves(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, const RcwWallCaves& caves, bool force, hipStream_t s);
+
+// The rooms (rcw_set_wall_rooms, rcw_wall_bank.hip): the generator's slot with a third family.  `gen` carries the level rule alone (loops 0,
+// no grid: rooms have no fallback); these three are the family's own kernel arguments.
+struct RcwWallRooms {
+    int32_t room;                // the least side of a room, >= 1
+    uint32_t stop;               // a chamber other than the root is left whole where the high word of its stop draw is below this
+    uint32_t doors;              // a wall gets a second door where the high word of its draw is below this
+};
+constexpr int kWallRoomsMaxRooms = 4096;   // Q = ceil((H - 2) / 2) ceil((W - 2) / 2): 130 x 130, 5 x 4097
+constexpr int kWallRoomsMaxTiles = 65536;  // H W: a chamber's two corner tiles share one draw index
+inline long long rcw_wall_rooms_bound(int H, int W) { return (long long)((H - 1) / 2) * (long long)((W - 1) / 2); }   // (ceil((H - 2) / 2) = (H - 1) / 2)
+size_t rcw_wall_rooms_lds_bytes(int H, int W, int nwords);
+hipError_t rcw_launch_wall_rooms(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, const RcwWallRooms& rooms, bool force, hipStream_t s);

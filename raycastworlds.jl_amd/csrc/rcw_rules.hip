@@ -572,6 +572,71 @@ extern "C" int rcw_wall_caves_layout(int32_t H, int32_t W, uint64_t key, uint32_
     return RCW_OK;
 }
 
+// ---- the wall generator: rooms (include/rcw.h, "the wall generator: rooms") ------------------------------------------------------------
+// What rcw_set_wall_rooms checks of a geometry, the least room side and a level range before anything is queued — or the refusal.
+int plan_wall_rooms(int32_t H, int32_t W, int32_t room, int32_t levels, int32_t first_level)
+{
+    if (H < 5 || W < 5) return fail(RCW_ERR_INVALID_ARGUMENT, "rooms need a map of at least 5 x 5 tiles (this one is %d x %d)", H, W);
+    if (room < 1) return fail(RCW_ERR_INVALID_ARGUMENT, "a room's least side must be at least 1 tile (got %d)", room);
+    if (levels < 0 || first_level < 0 || (int64_t)first_level + (int64_t)levels > 2147483647ll)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "the rooms' level range must satisfy levels >= 0, first_level >= 0 and first_level + levels <= 2^31 - 1 (got first_level %d, levels %d)", first_level, levels);
+    const long long bound = rcw_wall_rooms_bound(H, W), tiles = (long long)H * (long long)W;
+    if (bound > kWallRoomsMaxRooms)
+        return fail(RCW_ERR_UNSUPPORTED, "rooms are made on maps of at most %d odd-odd interior tiles, ceil((H - 2) / 2) ceil((W - 2) / 2) (up to 130 x 130 or 5 x 4097); %d x %d has %lld", kWallRoomsMaxRooms, H, W, bound);
+    if (tiles > kWallRoomsMaxTiles)
+        return fail(RCW_ERR_UNSUPPORTED, "rooms are made on maps of at most %d tiles; %d x %d has %lld", kWallRoomsMaxTiles, H, W, tiles);
+    return RCW_OK;
+}
+
+// The handle-less export: the rule once more on the host, by another traversal than the device's — depth first off a plain stack, a chamber
+// at a time, where the kernel cuts every chamber of a depth in one round.
+extern "C" int rcw_wall_rooms_layout(int32_t H, int32_t W, uint64_t key, int32_t room, uint32_t stop, uint32_t doors, uint8_t* out_host, int32_t* rooms)
+{
+    if (!out_host) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    const int rc = plan_wall_rooms(H, W, room, 0, 0); if (rc) return rc;
+    struct Chamber { int32_t i0, i1, j0, j1; };
+    std::vector<Chamber> stack;
+    try { stack.reserve(64); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the rooms failed"); }
+    for (int j = 0; j < W; ++j)
+        for (int i = 0; i < H; ++i) out_host[(size_t)i + (size_t)H * (size_t)j] = (i == 0 || i == H - 1 || j == 0 || j == W - 1) ? 1 : 0;
+    const int64_t least = std::min<int64_t>(room, kWallRoomsMaxTiles);   // (no side reaches it)
+    const auto evens = [](int64_t lo, int64_t hi, int32_t* first) -> int32_t {   // the even numbers of lo .. hi
+        const int64_t f = lo + (lo & 1);
+        *first = (int32_t)f;
+        return f > hi ? 0 : (int32_t)((hi - f) / 2 + 1);
+    };
+    int32_t count = 0;
+    stack.push_back(Chamber{1, H - 2, 1, W - 2});
+    while (!stack.empty()) {
+        const Chamber c = stack.back();
+        stack.pop_back();
+        const bool root = c.i0 == 1 && c.j0 == 1 && c.i1 == H - 2 && c.j1 == W - 2;
+        int32_t r0 = 0, c0 = 0;
+        const int32_t nr = c.j1 > c.j0 ? evens(c.i0 + least, c.i1 - least, &r0) : 0;
+        const int32_t nc = c.i1 > c.i0 ? evens(c.j0 + least, c.j1 - least, &c0) : 0;
+        const uint64_t t0 = (uint64_t)(c.i0 + H * c.j0), t1 = (uint64_t)(c.i1 + H * c.j1);
+        const uint64_t d = 0x2000000000000000ull + 8ull * ((t0 << 16) | t1);
+        if ((nr == 0 && nc == 0) || (!root && (uint32_t)(rcw_draw(key, d + 1) >> 32) < stop)) { ++count; continue; }
+        bool row = nc == 0;
+        if (nr != 0 && nc != 0) {
+            const int32_t di = c.i1 - c.i0, dj = c.j1 - c.j0;
+            row = di != dj ? di > dj : (rcw_draw(key, d) >> 63) != 0;
+        }
+        const int32_t s = (row ? r0 : c0) + 2 * (int32_t)rcw_below(rcw_draw(key, d + 2), (uint64_t)(row ? nr : nc));
+        const int32_t lo = row ? c.j0 : c.i0, hi = row ? c.j1 : c.i1, cnt = (hi - lo) / 2 + 1;
+        const int32_t door1 = lo + 2 * (int32_t)rcw_below(rcw_draw(key, d + 3), (uint64_t)cnt);
+        const int32_t door2 = (uint32_t)(rcw_draw(key, d + 4) >> 32) < doors ? lo + 2 * (int32_t)rcw_below(rcw_draw(key, d + 5), (uint64_t)cnt) : door1;
+        for (int32_t x = lo; x <= hi; ++x)
+            if (x != door1 && x != door2) out_host[row ? (size_t)s + (size_t)H * (size_t)x : (size_t)x + (size_t)H * (size_t)s] = 1;
+        try {
+            if (row) { stack.push_back(Chamber{s + 1, c.i1, c.j0, c.j1}); stack.push_back(Chamber{c.i0, s - 1, c.j0, c.j1}); }
+            else     { stack.push_back(Chamber{c.i0, c.i1, s + 1, c.j1}); stack.push_back(Chamber{c.i0, c.i1, c.j0, s - 1}); }
+        } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the rooms failed"); }
+    }
+    if (rooms) *rooms = count;
+    return RCW_OK;
+}
+
 #ifdef RCW_DEV_SWITCHES
 #include "dev/api_plan_export.inc"   // the rules and the step's facts without a device (tests/test_top_view_plan.py, tests/test_step_state.py)
 #endif

@@ -246,6 +246,7 @@ hipError_t launch_local_map(rcw_handle* h, StackOp op)
 // that installs the bank).  Behind rcw_reset the caller's re-render covers exactly those agents; behind a step, launch_step re-renders them.
 hipError_t launch_wall_bank(rcw_handle* h, bool force)
 {
+    if (h->gen.rooms_on()) return rcw_launch_wall_rooms(h->dev, h->gen.dev, h->gen.par, h->gen.room, force, h->stream);   // (rooms: the same slot, a third family)
     if (h->gen.caves_on()) return rcw_launch_wall_caves(h->dev, h->gen.dev, h->gen.par, h->gen.cave, force, h->stream);   // (caves: the generator's slot, another family)
     if (h->gen.on()) return rcw_launch_wall_generator(h->dev, h->gen.dev, h->gen.par, force, h->stream);   // (the generator: a maze made where the bank copies one)
     return h->bank.on() ? rcw_launch_wall_bank(h->dev, h->bank.dev, force, h->stream) : hipSuccess;

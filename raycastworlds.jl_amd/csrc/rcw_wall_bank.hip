@@ -1,6 +1,7 @@
 // The wall bank (include/rcw.h, rcw_set_wall_bank): L wall layouts resident on the device, one of them drawn for an agent at every start of
 // an episode.  Three kernels; nothing else of the library knows about the bank.  The wall generator's kernel (further down) lives here too:
-// it shares the bank's tail; so does the caves' kernel behind it, which also shares the maze.
+// it shares the bank's tail; so does the caves' kernel behind it, which also shares the maze.  The rooms' kernel is the third
+// family behind the same launch point: the key and the tail, no maze.
 //
 // rcw_wall_bank_pack_kernel   once per rcw_set_wall_bank: the layouts, UInt8 (H*W, L) as rcw_set_walls takes them, into the tile map's own
 //          word format — nwords uint32 a layout, 16 tiles a word, bit 0 of each 2-bit field = WALL, the GOAL bits and the padding past H*W
@@ -357,6 +358,111 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_caves_kernel(const RcwDev
     restart_on_lds_words<T>(p, lim, b, a, lane, words, ep, level);
 }
 
+// ---- the wall generator: rooms (include/rcw.h, "the wall generator: rooms") --------------------------------------------------------------
+// rcw_wall_rooms_kernel<T>   the generator's kernel with a third layout: the same launch point, common path, key and tail.  An agent that
+//          began an episode gets rooms(m, H, W, room, stop, doors), made by the whole wave in LDS:
+//            words   [nwords]  the tile map's words: the ring WALL, the interior free, the padding clear; wall tiles are set with ds_or;
+//            list    [Q]       the chambers, four uint16 each (i0, i1, j0, j1, inclusive); i0 == 0 flags a room (a live i0 is odd);
+//            tail              the entries in use (static LDS, ds_add).
+//          The root is entry 0.  A round: lane takes the entries lane + 64 i below the tail as the round found it.  A live chamber is
+//          either left whole — flagged — or cut: its lane paints the wall on line s but for the doors, overwrites the entry with the
+//          child in front of s and appends the child behind it at the old tail + 1 ...; appended entries wait for the next round, so
+//          round r handles the chambers r cuts below the root.  Until a round cuts nothing (__syncthreads_or).  The chambers of the list
+//          are disjoint and each holds an (odd, odd) tile: never more than Q entries.  The layout does not depend on the order the lanes
+//          append in: a chamber's draws are indexed by its own corners.  A wall is as long as the side it runs along, the shorter one but
+//          for chambers too narrow to cut the other way: its lane paints it alone (at 130 x 130 the root's 128 tiles are the longest).
+//          Every barrier is the wave's own and under a uniform condition: the agent, __syncthreads_or's result.
+constexpr uint64_t kRoomsDraw = 0x2000000000000000ull;
+
+// The even numbers of lo .. hi: their count, the first in *first.
+__device__ __forceinline__ int evens(int lo, int hi, int* first)
+{
+    *first = lo + (lo & 1);
+    return *first > hi ? 0 : (hi - *first) / 2 + 1;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBankBlock) void rcw_wall_rooms_kernel(const RcwDev p, const RcwLimit lim, const RcwWallBank b, const RcwWallGen g, const RcwWallRooms rm,
+                                                                    const int force)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_r[];
+    __shared__ int tail;
+    const int a = blockIdx.x, lane = threadIdx.x;
+    if (a >= p.B) return;
+    const uint32_t ep = p.episode[a];
+    if (!force && b.last_episode[a] == ep) {
+        if (lane == 0) b.mask[a] = 0;
+        return;
+    }
+    const int H = p.H, W = p.W, nwords = p.nwords, HW = p.H * p.W, room = min(rm.room, kWallRoomsMaxTiles);   // (no side reaches it: the sums below stay in range)
+    uint32_t* const words = lds_r;
+    ushort4* const list = reinterpret_cast<ushort4*>(lds_r + ((nwords + 1) & ~1));   // (8-byte aligned)
+    int level;
+    const uint64_t m = layout_key(p, g, a, ep, &level);
+    for (int x = lane; x < nwords; x += kBankBlock) {
+        int t = 16 * x, j = t / H, i = t - j * H;
+        uint32_t word = 0u;
+        for (int k = 0; k < 16 && t < HW; ++k, ++t) {                      // (the padding stays clear)
+            if (i == 0 || i == H - 1 || j == 0 || j == W - 1) word |= 1u << (2 * k);
+            if (++i == H) { i = 0; ++j; }
+        }
+        words[x] = word;
+    }
+    if (lane == 0) {
+        list[0] = make_ushort4((unsigned short)1, (unsigned short)(H - 2), (unsigned short)1, (unsigned short)(W - 2));
+        tail = 1;
+    }
+    __syncthreads();
+    const uint32_t root0 = (uint32_t)(1 + H), root1 = (uint32_t)((H - 2) + H * (W - 2));
+    for (;;) {
+        const int n = tail;                                                // (the same on every lane: nobody appends before the barrier)
+        __syncthreads();
+        int cut = 0;
+        for (int e = lane; e < n; e += kBankBlock) {
+            const ushort4 c = list[e];
+            if (c.x == 0) continue;                                        // a room
+            const int i0 = c.x, i1 = c.y, j0 = c.z, j1 = c.w;
+            int r0, c0;
+            const int nr = j1 > j0 ? evens(i0 + room, i1 - room, &r0) : 0;
+            const int nc = i1 > i0 ? evens(j0 + room, j1 - room, &c0) : 0;
+            const uint32_t t0 = (uint32_t)(i0 + H * j0), t1 = (uint32_t)(i1 + H * j1);
+            const uint64_t d = kRoomsDraw + 8ull * (uint64_t)((t0 << 16) | t1);
+            const bool root = t0 == root0 && t1 == root1;
+            if ((nr == 0 && nc == 0) || (!root && (uint32_t)(rcw_draw(m, d + 1ull) >> 32) < rm.stop)) {
+                list[e].x = 0;
+                continue;
+            }
+            bool row = nc == 0;
+            if (nr != 0 && nc != 0) {
+                const int di = i1 - i0, dj = j1 - j0;
+                row = di > dj || (di == dj && (rcw_draw(m, d) >> 63) != 0ull);
+            }
+            const int s = (row ? r0 : c0) + 2 * (int)rcw_below(rcw_draw(m, d + 2ull), (uint64_t)(row ? nr : nc));
+            const int lo = row ? j0 : i0, hi = row ? j1 : i1, cnt = (hi - lo) / 2 + 1;
+            const int door1 = lo + 2 * (int)rcw_below(rcw_draw(m, d + 3ull), (uint64_t)cnt);
+            int door2 = door1;
+            if ((uint32_t)(rcw_draw(m, d + 4ull) >> 32) < rm.doors) door2 = lo + 2 * (int)rcw_below(rcw_draw(m, d + 5ull), (uint64_t)cnt);
+            const int base = row ? s : H * s, stride = row ? H : 1;          // the span's tile at position x: base + stride x
+            for (int x = lo; x <= hi; ++x) {
+                if (x == door1 || x == door2) continue;
+                const int t = base + stride * x;
+                atomicOr(&words[t >> 4], 1u << ((t & 15) * 2));
+            }
+            const int fresh = atomicAdd(&tail, 1);
+            if (row) {
+                list[e] = make_ushort4((unsigned short)i0, (unsigned short)(s - 1), (unsigned short)j0, (unsigned short)j1);
+                list[fresh] = make_ushort4((unsigned short)(s + 1), (unsigned short)i1, (unsigned short)j0, (unsigned short)j1);
+            } else {
+                list[e] = make_ushort4((unsigned short)i0, (unsigned short)i1, (unsigned short)j0, (unsigned short)(s - 1));
+                list[fresh] = make_ushort4((unsigned short)i0, (unsigned short)i1, (unsigned short)(s + 1), (unsigned short)j1);
+            }
+            cut = 1;
+        }
+        if (!__syncthreads_or(cut)) break;
+    }
+    restart_on_lds_words<T>(p, lim, b, a, lane, words, ep, level);
+}
+
 // The camera view of the agents the bank restarted (mask[a] != 0), from their fresh column descriptors: update_camera_view!'s column fill
 // (SR:431-440, rcw_fill.hip's pixel rule: column_padding, then ceiling | colour | floor by row) one workgroup per agent.  Restarts are sparse:
 // nearly every workgroup reads its mask byte and leaves, where the camera fill's moving window would sweep every column of the batch to
@@ -437,5 +543,24 @@ hipError_t rcw_launch_wall_caves(const RcwPlan& p, const RcwWallBank& agents, co
     const size_t lds = rcw_wall_caves_lds_bytes(p.H, p.W, p.nwords);
     if (p.real64) hipLaunchKernelGGL(rcw_wall_caves_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, caves, force ? 1 : 0);
     else          hipLaunchKernelGGL(rcw_wall_caves_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, caves, force ? 1 : 0);
+    return hipGetLastError();
+}
+
+// LDS: the words (an even count), then 8 bytes a chamber for Q entries.  At the 4096-room bound the list is 32 KiB: 130 x 130 (1057 words)
+// asks for 37,000 bytes, 5 x 4097 (1281 words) for 37,896, and the largest request is 6 x 4098's (1537 words): 38,920 bytes, under the
+// 64 KiB default.
+size_t rcw_wall_rooms_lds_bytes(int H, int W, int nwords)
+{
+    return (size_t)((nwords + 1) & ~1) * sizeof(uint32_t) + (size_t)rcw_wall_rooms_bound(H, W) * sizeof(ushort4);
+}
+
+hipError_t rcw_launch_wall_rooms(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, const RcwWallRooms& rooms, bool force, hipStream_t s)
+{
+    if (p.B < 1) return hipSuccess;
+    if (p.H < 5 || p.W < 5 || rooms.room < 1 || rcw_wall_rooms_bound(p.H, p.W) > kWallRoomsMaxRooms || (long long)p.H * (long long)p.W > kWallRoomsMaxTiles)
+        return hipErrorInvalidValue;
+    const size_t lds = rcw_wall_rooms_lds_bytes(p.H, p.W, p.nwords);
+    if (p.real64) hipLaunchKernelGGL(rcw_wall_rooms_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, rooms, force ? 1 : 0);
+    else          hipLaunchKernelGGL(rcw_wall_rooms_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, rooms, force ? 1 : 0);
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 """Wall layouts for `SingleRoom.set_walls`: host-side numpy, nothing here touches the device (`generated_maze` and
-`generated_maze_key` and `generated_cave` call the library's handle-less host functions: no device either).
+`generated_maze_key`, `generated_cave` and `generated_rooms` call the library's handle-less host functions: no device either).
 
 A layout is bool (H, W) with `walls[i-1, j-1]` = tile (i, j) is a WALL — the index order of `env.world.tile_map[b, 0]`.
 Every generator returns the wall ring (SR:57-60) closed, as `rcw_set_walls` requires, and at least two free interior
@@ -132,6 +132,26 @@ def generated_cave(key: int, H: int, W: int, fill=0.40, smooth: int = 2, return_
         raise ValueError(_capi.last_error(lib))
     walls = np.ascontiguousarray(out.T != 0)
     return (walls, bool(fell.value)) if return_fell_back else walls
+
+
+def generated_rooms(key: int, H: int, W: int, room: int = 2, stop=0.25, doors=0.25, return_rooms: bool = False):
+    """The wall generator's rooms of one 64-bit key (`generated_maze_key` serves every family), bool (H, W): the interior split
+    recursively by walls on even lines, each with a door on an odd position and, with probability `doors`, a second one; a chamber
+    other than the whole interior is left a room with probability `stop`, and no room side falls below `room` (`stop`, `doors`: an
+    int is the UInt32 word itself); `return_rooms=True` returns (walls, number of rooms).
+    rcw_wall_rooms_layout: host arithmetic (depth first off a stack), no device — what an agent's `env.world.walls[a]` holds."""
+    import ctypes as C
+
+    from . import _capi
+
+    lib = _capi.load()
+    out = np.empty((max(int(W), 0), max(int(H), 0)), dtype=np.uint8)   # tile (i, j), 0-based, at i + H j
+    rooms = C.c_int32()
+    rc = lib.rcw_wall_rooms_layout(int(H), int(W), int(key), int(room), loops_word(stop), loops_word(doors), out.ctypes.data, C.byref(rooms))
+    if rc != _capi.RCW_OK:
+        raise ValueError(_capi.last_error(lib))
+    walls = np.ascontiguousarray(out.T != 0)
+    return (walls, int(rooms.value)) if return_rooms else walls
 
 
 def is_connected(walls) -> bool:

@@ -103,6 +103,8 @@ class ShardedSingleRoom:
             raise ValueError("a batch built with rng draws its resets on the host: it takes no wall generator")
         if self.rng is not None and kwargs.get("wall_caves") is not None:
             raise ValueError("a batch built with rng draws its resets on the host: it takes no wall caves")
+        if self.rng is not None and kwargs.get("wall_rooms") is not None:
+            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall rooms")
         self.env = env_factory(batch=self.count, agent_id_offset=self.first,
                                device=default_device() if device is None else device, **kwargs)
         self._abi_comm = False
@@ -202,6 +204,13 @@ class ShardedSingleRoom:
         if self.rng is not None and fill is not None:
             raise ValueError("a batch built with rng draws its resets on the host: it takes no wall caves")
         self.env.set_wall_caves(fill, smooth, levels, first_level, level_seed)
+
+    def set_wall_rooms(self, room=2, stop=0.25, doors=0.25, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
+        """`SingleRoom.set_wall_rooms` for the sharded batch: the parameters are REPLICATED — every rank passes the same — and
+        nothing else is needed: the rooms an agent's episode gets are keyed by its global id (`agent_id_offset`)."""
+        if self.rng is not None and room is not None:
+            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall rooms")
+        self.env.set_wall_rooms(room, stop, doors, levels, first_level, level_seed)
 
     def set_wall_bank_weights(self, weights) -> None:
         """`SingleRoom.set_wall_bank_weights`, the same weights on every rank."""

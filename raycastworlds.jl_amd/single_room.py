@@ -351,7 +351,9 @@ class SingleRoom:
     `wall_generator` (this build's addition; a dict of `set_wall_generator`'s keywords, `{}` for the defaults) is applied in the same
     place: a new maze made on the device at every episode start.  It and `wall_bank` exclude each other.  `wall_caves` (this build's
     addition; a dict of `set_wall_caves`' keywords, `{}` for the defaults) is applied right behind it: a new cave made on the device at
-    every episode start.  It excludes `wall_bank` and `wall_generator`.
+    every episode start.  It excludes `wall_bank` and `wall_generator`.  `wall_rooms` (this build's addition; a dict of
+    `set_wall_rooms`' keywords, `{}` for the defaults) is applied behind that: new rooms and doorways made on the device at every
+    episode start.  It excludes the other three.
     """
 
     def __init__(
@@ -391,6 +393,7 @@ class SingleRoom:
         wall_bank_weights=None,
         wall_generator=None,
         wall_caves=None,
+        wall_rooms=None,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -500,6 +503,12 @@ class SingleRoom:
         if wall_caves is not None:
             try:
                 self.set_wall_caves(**dict(wall_caves))
+            except BaseException:
+                self._handle.close()
+                raise
+        if wall_rooms is not None:
+            try:
+                self.set_wall_rooms(**dict(wall_rooms))
             except BaseException:
                 self._handle.close()
                 raise
@@ -1202,6 +1211,41 @@ class SingleRoom:
         self._check(self._lib.rcw_wall_caves_info(self._h, C.byref(on), C.byref(fill), C.byref(smooth)))
         return {"enabled": bool(on.value), "fill": fill.value, "smooth": smooth.value}
 
+    # ---- the wall generator: rooms (include/rcw.h, rcw_set_wall_rooms) ------------------
+    def set_wall_rooms(self, room=2, stop=0.25, doors=0.25, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
+        """New rooms made on the device at every start of an episode, where `set_wall_generator` makes a maze: rectangular rooms of
+        different sizes joined by doorways, `layouts.four_rooms`' topology.  The interior is split recursively by walls on even
+        lines; every wall has a door and, with probability `doors`, a second one; a chamber other than the whole interior is left a
+        room with probability `stop`; no room side falls below `room` (>= 1).  `stop` and `doors` are probabilities, or the UInt32
+        words themselves as `loops` takes one.  Connected by construction on every map from 5 x 5: no fallback.  `levels`,
+        `first_level`, `level_seed` and `wall_layout` are the generator's;
+        `layouts.generated_rooms(layouts.generated_maze_key(...)[0], H, W, room, stop, doors)` replays any of them on the host.  Maps
+        of 5 x 5 up to ceil((H-2)/2) ceil((W-2)/2) = 4096 (130 x 130, 5 x 4097).  `set_walls`, `set_wall_bank`, `set_wall_generator`
+        and `set_wall_caves` are refused while rooms are on, and rooms while any of them is; `set_wall_rooms(None)` switches them
+        off, the agents keep their walls.  An environment built with `rng` draws its resets on the host and takes no rooms."""
+        self.__dict__.pop("_wall_layout_dev", None)
+        if room is None:
+            self._check(self._lib.rcw_set_wall_rooms(self._h, 0, 0, 0, 0, 0, 0, 0))
+            return
+        if self.rng is not None:
+            raise ValueError("an environment built with rng draws its resets on the host: it takes no wall rooms")
+        from . import layouts as _layouts
+
+        stop_word, doors_word = _layouts.loops_word(stop), _layouts.loops_word(doors)
+        for name, v, top in (("room", room, 2 ** 31 - 1), ("levels", levels, 2 ** 31 - 1), ("first_level", first_level, 2 ** 31 - 1),
+                             ("level_seed", level_seed, 2 ** 64 - 1)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not (-2 ** 31 if name == "room" else 0) <= int(v) <= top:
+                raise ValueError(f"{name} must be an integer in 0 .. {top}, got {v!r}")
+        self._check(self._lib.rcw_set_wall_rooms(self._h, 1, int(room), stop_word, doors_word, int(levels), int(first_level), int(level_seed)))
+
+    @property
+    def wall_rooms_info(self) -> dict:
+        """`enabled`, `room`, `stop` and `doors` (the UInt32 words) of the rooms (rcw_wall_rooms_info); zeros while they are off.  The
+        level parameters read from `wall_generator_info`, which reports `enabled` and `loops == 0` while rooms are on."""
+        on, room, stop, doors = C.c_int32(), C.c_int32(), C.c_uint32(), C.c_uint32()
+        self._check(self._lib.rcw_wall_rooms_info(self._h, C.byref(on), C.byref(room), C.byref(stop), C.byref(doors)))
+        return {"enabled": bool(on.value), "room": room.value, "stop": stop.value, "doors": doors.value}
+
     def _wall_layout_host(self) -> np.ndarray:
         out = np.empty(self.batch, dtype=np.int32)
         self.host_syncs += 1
@@ -1212,7 +1256,7 @@ class SingleRoom:
     def wall_layout(self) -> DeviceArray:
         """int32 (B,) in device memory: the bank layout each agent's current episode was given — with the wall generator its level, or
         -1 — (`.torch(sync=False)` on the GPU, `np.asarray(env.wall_layout)` for a host copy).  Valid until the next `set_wall_bank`
-        , `set_wall_generator` or `set_wall_caves`."""
+        , `set_wall_generator`, `set_wall_caves` or `set_wall_rooms`."""
         if getattr(self, "_wall_layout_dev", None) is None:
             p = C.c_void_p()
             self._check(self._lib.rcw_wall_layout_device_ptr(self._h, C.byref(p)))

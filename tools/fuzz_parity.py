@@ -3,7 +3,7 @@
 configurations (map size, columns, headings, field of view, radius, step, camera height, image
 height, world-unit type, the three unpinned switches, both BoundsError policies, auto-reset).
 
-    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit|goal|bank|gen|caves]
+    python tools/fuzz_parity.py [configs] [seed] [top|split|flat|step|limit|goal|bank|gen|caves|rooms]
                                                                    # "top": every configuration renders the top view;
                                                                    # "split": ... with a geometry of the unit store kernels;
                                                                    # "flat": ... of the flat store kernel (any pu >= 9), and any
@@ -24,6 +24,9 @@ height, world-unit type, the three unpinned switches, both BoundsError policies,
                                                                    # "caves": the caves (rcw_set_wall_caves) — random maps, fills, smoothing counts,
                                                                    #         level ranges and sequences of calls against tests/wall_caves_ref.py,
                                                                    #         compared the same way (caves_mode below)
+                                                                   # "rooms": the rooms (rcw_set_wall_rooms) — random maps, room sides, stop and door
+                                                                   #         probabilities, level ranges and sequences of calls against
+                                                                   #         tests/wall_rooms_ref.py, compared the same way (rooms_mode below)
 """
 import os
 import sys
@@ -452,6 +455,112 @@ def caves_mode(n_cfg, seed):
     return 1 if fails else 0
 
 
+def rooms_mode(n_cfg, seed):
+    """caves_mode's draw for the rooms: maps of 5 x 5 to 40 x 40 tiles; a least room side of 1 .. 4, stop 0 .. 0.5 (now and then always), a
+    second door with probability 0 .. 1; no levels, or 1, 2 or 5; 1 to 9 agents with 8 or 16 view columns, Float32 and Float64, both forms
+    of the step asked for, a time limit of 0, 2 or 5, auto_reset.  Then 30 random calls — a step, a masked or full reset_ with a new seed, a
+    masked set_state onto free tiles of each agent's current layout, some agents walked into their goals (wall_bank_cases.
+    walk_into_the_goal), the rooms off and others on —, each made on the reference (tests/wall_rooms_cases.py's Recorder) and on the engine
+    (its Player), which compares the whole state, the frames, the time limit's words and wall_layout after every call.  Every configuration
+    draws from default_rng([seed, c])."""
+    import wall_rooms_cases as RC
+    from raycastworlds_jl_amd import _capi
+
+    rng = None
+
+    def rooms():
+        levels = int(rng.choice([0, 0, 1, 2, 5]))
+        stop = [0.0, 0.0, 0.1, 0.25, 0.25, 0.5, 1.0][int(rng.integers(0, 7))]
+        doors = [0.0, 0.25, 0.25, 0.5, 1.0][int(rng.integers(0, 5))]
+        return dict(room=int(rng.integers(1, 5)), stop=stop, doors=doors, levels=levels, first_level=int(rng.integers(0, 2**31 - 1 - levels)) if levels else 0,
+                    level_seed=int(rng.integers(0, 2**63)) if levels else 0)
+
+    def some(B):
+        mask = (rng.random(B) < 0.5).astype(np.uint8)
+        mask[int(rng.integers(0, B))] = 1
+        return mask
+
+    totals = dict(step=0, reset=0, masked_reset=0, set_state=0, arrive=0, off_and_on=0, episode_starts=0, rooms_made=0, second_doors=0, goal_redraws=0,
+                  restarts_after_done=0, restarts_after_truncation=0, one_launch_steps=0, two_launch_steps=0, non_square=0, with_levels=0,
+                  stopped=0, rooms_past_64=0)
+    fails = 0
+    for c in range(n_cfg):
+        rng = np.random.default_rng([seed, c])
+        H, W = int(rng.integers(5, 41)), int(rng.integers(5, 41))
+        if c % 4 == 0:
+            H, W = int(rng.integers(5, 9)), int(rng.integers(5, 9))          # (a quarter small: agents arrive, restarts after done)
+        B = int(rng.integers(1, 10))
+        T64, L = bool(rng.integers(0, 2)), int(rng.choice([0, 2, 5]))
+        N, Hc = [(8, 64), (16, 64), (8, 24), (16, 128)][int(rng.integers(0, 4))]
+        form = str(rng.choice(["one-launch", "two-launches"]))
+        engine_seed = int(rng.integers(0, 2**31))
+        shape = dict(H=H, W=W, N=N, Hc=Hc, B=B, seed=engine_seed, T="Float64" if T64 else "Float32")
+        where = f"config {c}: {H} x {W}, B={B} T64={T64} L={L} N={N} Hc={Hc} {form} seed={engine_seed}"
+        try:
+            env = RC.make_env(RCW, shape)
+            try:
+                env.set_step_form(form)
+            except _capi.RcwError as e:
+                assert form == "one-launch" and e.code == _capi.RCW_ERR_UNSUPPORTED and "does not take the one-launch step" in e.message, e
+                form = "two-launches"
+            totals["one_launch_steps" if form == "one-launch" else "two_launch_steps"] += 1
+            totals["non_square"] += int(H != W)
+            rec = RC.Recorder(shape)
+            play = RC.Player(RCW, env, rec.snaps, where)
+            both = lambda call, *a, **k: (getattr(rec, call)(*a, **k), getattr(play, call)(*a, **k))
+            if L:
+                both("set_time_limit", L)
+
+            def install():
+                g = rooms()
+                totals["with_levels"] += int(g["levels"] > 0)
+                totals["stopped"] += int(g["stop"] > 0)
+                both("set_wall_rooms", **g)
+
+            install()
+            for k in range(30):
+                call = str(rng.choice(["step", "step", "step", "step", "step", "step", "reset", "masked_reset", "set_state", "arrive", "off_and_on"]))
+                play.name = f"{where}, call {k} ({call})"
+                totals[call] += 1
+                if call == "step":
+                    both("step", rng.integers(1, 5, B).astype(np.uint8))
+                elif call in ("reset", "masked_reset"):
+                    both("reset", some(B) if call == "masked_reset" else None, int(rng.integers(0, 2**31)))
+                elif call == "set_state":
+                    mask, s = some(B), rec.snaps[-1]
+                    goal, pos, heading = s["goal"].copy(), s["position"].copy(), s["direction"].copy()
+                    for b in np.flatnonzero(mask):
+                        free = np.argwhere(~rec.ref.walls_of(b))
+                        goal[b] = free[int(rng.integers(0, len(free)))] + 1
+                        pos[b] = free[int(rng.integers(0, len(free)))] + 0.5
+                        heading[b] = int(rng.integers(0, 8))
+                    both("set_state", goal, pos, heading, mask)
+                elif call == "arrive":
+                    mask = some(B)
+                    for b in np.flatnonzero(mask):                           # (free tiles in one row have no tile to walk down from)
+                        free = ~rec.ref.walls_of(b)
+                        mask[b] = int((free[:-1] & free[1:]).any())
+                    RC.walk_into_the_goal(rec, mask)
+                    RC.walk_into_the_goal(play, mask)
+                else:
+                    both("set_wall_rooms", None)
+                    both("step", rng.integers(1, 5, B).astype(np.uint8))
+                    install()
+            play.finished()
+            for k, v in rec.events.items():
+                if k in totals:
+                    totals[k] += v
+            totals["rooms_past_64"] += int(RC.RR.bound(H, W) > 64)             # (maps with more (odd, odd) tiles than a wavefront has lanes)
+            env.close()
+        except Exception as e:   # noqa: BLE001
+            fails += 1
+            print(f"{where} FAILED\n   {type(e).__name__}: {str(e)[:400]}")
+            if fails >= 5:
+                break
+    print(f"{n_cfg} random configurations (wall rooms: " + ", ".join(f"{v} {k}" for k, v in totals.items()) + f"), {fails} mismatches")
+    return 1 if fails else 0
+
+
 if len(sys.argv) > 3 and sys.argv[3] == "goal":
     sys.exit(goal_mode(n_cfg, int(sys.argv[2])))
 if len(sys.argv) > 3 and sys.argv[3] == "bank":
@@ -460,6 +569,8 @@ if len(sys.argv) > 3 and sys.argv[3] == "gen":
     sys.exit(gen_mode(n_cfg, int(sys.argv[2])))
 if len(sys.argv) > 3 and sys.argv[3] == "caves":
     sys.exit(caves_mode(n_cfg, int(sys.argv[2])))
+if len(sys.argv) > 3 and sys.argv[3] == "rooms":
+    sys.exit(rooms_mode(n_cfg, int(sys.argv[2])))
 limit_events = {}
 one_launch_steps = 0
 two_kernel_forms = 0                                            # (rcw_set_top_view_form: by default it is taken only from 256 MiB a step)
