@@ -420,20 +420,102 @@ int rcw_reset(rcw_handle* h, const uint8_t* mask_host, uint64_t seed)
     h->step.reset(mask_dev != nullptr, seed != h->dev.seed, h->dev.auto_reset != 0);
     h->dev.seed = seed;
     RCW_HIP(rcw_launch_reset(h->dev, mask_dev, h->stream));            // SR:110-132
-    RCW_HIP(launch_wall_bank(h, false));                               // (a handle with a wall bank: the agents of the mask take a layout each)
+    RCW_HIP(launch_layout_source(h, false));                           // (a handle with a layout source: the agents of the mask take a layout each)
     RCW_HIP(launch_step(h, nullptr, mask_dev, kStackRefill));    // SR:134, SR:329
     return RCW_OK;
 }
+
+// ---- the layout sources (rcw_handle::LayoutSource): the wall bank and the wall generator's mazes, caves and rooms ------------------------
+// A setter is its own validation and parameters around three shared pieces: the refusal beside another live source, the drop, the install.
+extern "C++" {
+namespace {
+
+using LayoutSource = rcw_handle::LayoutSource;
+
+// Per kind: what a failed allocation of its install is called, and how a caller is told that it is live — `by_walls` to rcw_set_walls and
+// rcw_set_wall_bank, `by_family` to the setters of the generator's families.
+struct SourceWords { const char* name; const char* by_walls; const char* by_family; };
+const SourceWords kSourceWords[] = {
+    /* kLayoutNone  */ {"", "", ""},
+    /* kLayoutBank  */ {"wall bank",
+                        "the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))",
+                        "the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))"},
+    /* kLayoutMazes */ {"wall generator",
+                        "the handle makes its walls with the wall generator; switch the generator off first (rcw_set_wall_generator(h, 0, ...))",
+                        "the handle makes mazes; switch the generator off first (rcw_set_wall_generator(h, 0, ...))"},
+    /* kLayoutCaves */ {"wall caves",
+                        "the handle makes its walls with the wall generator's caves; switch them off first (rcw_set_wall_caves(h, 0, ...))",
+                        "the handle makes caves; switch them off first (rcw_set_wall_caves(h, 0, ...))"},
+    /* kLayoutRooms */ {"wall rooms",
+                        "the handle makes its walls with the wall generator's rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))",
+                        "the handle makes rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))"},
+};
+
+// THE refusal: `caller` would install a source of kind `wants` (rcw_set_walls: none, it writes walls of its own) beside a live one of another
+// kind.  The live kind over itself is a re-install and passes.
+int refuse_other_source(rcw_handle* h, const char* caller, RcwLayoutKind wants)
+{
+    const RcwLayoutKind live = h->source.dev.kind;
+    if (live == kLayoutNone || live == wants) return RCW_OK;
+    const bool family = wants != kLayoutNone && wants != kLayoutBank;
+    return fail(RCW_ERR_UNSUPPORTED, "%s: %s", caller, family ? kSourceWords[live].by_family : kSourceWords[live].by_walls);
+}
+
+// THE off branch of a setter: the agents keep the walls they have.  A source of another kind is not this call's to end.
+int drop_layout_source(rcw_handle* h, RcwLayoutKind kind)
+{
+    LayoutSource& ls = h->source;
+    if (!ls.is(kind)) return RCW_OK;
+    RCW_HIP(replace_buffers(h, {&ls.words, &ls.cum, &ls.agents}));
+    ls.h_cum.reset(); ls.ev_cum.reset();
+    ls.total_weight = 0;
+    ls.dev = RcwLayoutSource{};
+    return RCW_OK;
+}
+
+// THE install, behind a setter's validation and staging.  `fresh` holds the kind and its parameters and — the bank, which allocates everything
+// before it changes anything — the bank's resources with the per-agent block; a family's block is allocated here.  An allocation that fails
+// leaves the handle as it was.  Then the handle takes `fresh` over, the bank's weights and layouts are uploaded, and every agent is
+// restarted under the source's rule: the body of rcw_reset(h, NULL, <the handle's seed>) with the source's kernel forced for every agent.
+int install_layout_source(rcw_handle* h, LayoutSource& fresh)
+{
+    LayoutSource& ls = h->source;
+    const size_t B = (size_t)h->B, agent_bytes = 3 * B * sizeof(uint32_t) + B;
+    if (!fresh.agents.get()) {
+        const hipError_t e = fresh.agents.hipMalloc(agent_bytes);
+        if (e != hipSuccess) return fail(hip_code(e), "%s: %s", kSourceWords[fresh.dev.kind].name, hip_failure(e));
+    }
+    RCW_HIP(replace_buffers(h, {&ls.words, &ls.cum, &ls.agents}, {&fresh.words, &fresh.cum, &fresh.agents}));
+    ls.h_cum = std::move(fresh.h_cum); ls.ev_cum = std::move(fresh.ev_cum);
+    ls.total_weight = fresh.total_weight;
+    ls.dev = fresh.dev;
+    uint32_t* const q = ls.agents.get<uint32_t>();
+    RcwWallBank& v = ls.dev.agents;
+    v.words = ls.words.get<uint32_t>(); v.cum = ls.cum.get<uint32_t>();
+    v.last_episode = q; v.status_seen = reinterpret_cast<int32_t*>(q + B); v.layout = reinterpret_cast<int32_t*>(q + 2 * B); v.mask = reinterpret_cast<uint8_t*>(q + 3 * B);
+    if (ls.is(kLayoutBank)) {                                          // (the weights wait in h_cum, the layouts in d_in_walls)
+        RCW_HIP(hipMemcpyAsync(ls.cum.get(), ls.h_cum.get(), (size_t)v.layouts * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        RCW_HIP(hipEventRecord(ls.ev_cum.get(), h->stream));
+        RCW_HIP(rcw_launch_wall_bank_pack(h->dev, h->d_in_walls.get<uint8_t>(), ls.words.get<uint32_t>(), v.layouts, h->stream));
+    }
+    RCW_HIP(hipMemsetAsync(ls.agents.get(), 0, agent_bytes, h->stream));
+    RCW_HIP(hipMemcpyAsync(v.status_seen, h->d_status.get(), B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    h->step.reset(false, false, h->dev.auto_reset != 0);
+    RCW_HIP(rcw_launch_reset(h->dev, nullptr, h->stream));             // the counters move by one ...
+    RCW_HIP(launch_layout_source(h, true));                            // ... and every agent starts that episode on a layout of the source
+    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));
+    return RCW_OK;
+}
+
+}  // namespace
+}  // extern "C++"
 
 // Wall layouts (include/rcw.h): validate on the host, stage layouts and index, write the (masked) agents' WALL layer — and from there on the
 // body of rcw_reset with the handle's own seed: no step fact moves that a reset with the same seed would not move.
 int rcw_set_walls(rcw_handle* h, const uint8_t* walls_host, int32_t layouts, const int32_t* layout_index_host, const uint8_t* mask_host)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
-    if (h->gen.rooms_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle makes its walls with the wall generator's rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))");
-    if (h->gen.caves_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle makes its walls with the wall generator's caves; switch them off first (rcw_set_wall_caves(h, 0, ...))");
-    if (h->gen.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_walls: the handle makes its walls with the wall generator; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
+    rc = refuse_other_source(h, "rcw_set_walls", kLayoutNone); if (rc) return rc;
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     char why[256];
     if (validate_walls(H, W, h->B, walls_host, layouts, layout_index_host, mask_host, why, sizeof why) != RCW_OK)
@@ -599,7 +681,7 @@ int rcw_clear_error(rcw_handle* h)
     int rc = check_handle(h); if (rc) return rc;
     RCW_HIP(hipMemsetAsync(h->d_err.get(), 0, sizeof(int32_t), h->stream));
     RCW_HIP(hipMemsetAsync(h->d_status.get(), 0, (size_t)h->B * sizeof(int32_t), h->stream));
-    if (h->drawn()) RCW_HIP(hipMemsetAsync(h->drawn()->status_seen, 0, (size_t)h->B * sizeof(int32_t), h->stream));   // (the bank's or the generator's record of them)
+    if (h->source.live()) RCW_HIP(hipMemsetAsync(h->source.dev.agents.status_seen, 0, (size_t)h->B * sizeof(int32_t), h->stream));   // (the layout source's record of them)
     RCW_HIP(hipStreamSynchronize(h->stream));
     return RCW_OK;
 }
@@ -1105,23 +1187,20 @@ int rcw_local_map_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32_t 
     return rc;
 }
 
-// The wall bank (include/rcw.h).  Validated and allocated before anything of the handle changes; then the layouts are staged, packed on the
-// device, and every agent is restarted under the bank's rule: the body of rcw_reset(h, NULL, <the handle's seed>) with the bank's kernel
-// forced for every agent.
+extern "C++" {
+namespace {
+int need_wall_bank(rcw_handle* h) { return h->source.is(kLayoutBank) ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no wall bank (rcw_set_wall_bank)"); }
+int need_drawn_walls(rcw_handle* h) { return h->source.live() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms)"); }
+
+}  // namespace
+}  // extern "C++"
+
+// The wall bank (include/rcw.h): validated, allocated and its layouts staged before the install.
 int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts, const uint32_t* weights_host)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rcw_handle::WallBank& wb = h->bank;
-    if (layouts == 0 || !walls_host) {                                 // off: the agents keep the walls they have
-        if (!wb.on()) return RCW_OK;
-        RCW_HIP(replace_buffers(h, {&wb.words, &wb.cum, &wb.agents}));
-        wb.h_cum.reset(); wb.ev_cum.reset();
-        wb.dev = RcwWallBank{}; wb.total_weight = 0;
-        return RCW_OK;
-    }
-    if (h->gen.rooms_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_bank: the handle makes its walls with the wall generator's rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))");
-    if (h->gen.caves_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_bank: the handle makes its walls with the wall generator's caves; switch them off first (rcw_set_wall_caves(h, 0, ...))");
-    if (h->gen.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_bank: the handle makes its walls with the wall generator; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
+    if (layouts == 0 || !walls_host) return drop_layout_source(h, kLayoutBank);
+    rc = refuse_other_source(h, "rcw_set_wall_bank", kLayoutBank); if (rc) return rc;
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     char why[256];
     if (layouts < 0) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_set_wall_bank: layouts must be >= 0 (got %d)", layouts);
@@ -1130,9 +1209,8 @@ int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
     const size_t B = (size_t)h->B, L = (size_t)layouts, bytes = L * (size_t)H * (size_t)W, nwords = (size_t)h->dev.nwords;
     std::vector<uint32_t> cum;
     try { cum.resize(L); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the cumulative weights failed"); }
-    uint64_t total = 0;
-    rc = plan_wall_bank_weights(weights_host, layouts, cum.data(), &total); if (rc) return rc;
-    rcw_handle::WallBank fresh;
+    LayoutSource fresh;
+    rc = plan_wall_bank_weights(weights_host, layouts, cum.data(), &fresh.total_weight); if (rc) return rc;
     {
         hipError_t e = fresh.words.hipMalloc(L * nwords * sizeof(uint32_t));
         if (e == hipSuccess) e = fresh.cum.hipMalloc(L * sizeof(uint32_t));
@@ -1148,31 +1226,11 @@ int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
     }
     RCW_HIP(hipMemcpyAsync(h->d_in_walls.get(), walls_host, bytes, hipMemcpyHostToDevice, h->stream));
     RCW_HIP(hipStreamSynchronize(h->stream));                          // (pageable host memory of the caller's)
-    RCW_HIP(replace_buffers(h, {&wb.words, &wb.cum, &wb.agents}, {&fresh.words, &fresh.cum, &fresh.agents}));
-    wb.h_cum = std::move(fresh.h_cum); wb.ev_cum = std::move(fresh.ev_cum);
-    uint32_t* const q = wb.agents.get<uint32_t>();
-    wb.dev = RcwWallBank{layouts, wb.words.get<uint32_t>(), wb.cum.get<uint32_t>(), q, reinterpret_cast<int32_t*>(q + B),
-                         reinterpret_cast<int32_t*>(q + 2 * B), reinterpret_cast<uint8_t*>(q + 3 * B)};
-    wb.total_weight = total;
-    std::memcpy(wb.h_cum.get(), cum.data(), L * sizeof(uint32_t));
-    RCW_HIP(hipMemcpyAsync(wb.cum.get(), wb.h_cum.get(), L * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    RCW_HIP(hipEventRecord(wb.ev_cum.get(), h->stream));
-    RCW_HIP(rcw_launch_wall_bank_pack(h->dev, h->d_in_walls.get<uint8_t>(), wb.words.get<uint32_t>(), layouts, h->stream));
-    RCW_HIP(hipMemsetAsync(wb.agents.get(), 0, 3 * B * sizeof(uint32_t) + B, h->stream));
-    RCW_HIP(hipMemcpyAsync(wb.dev.status_seen, h->d_status.get(), B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
-    h->step.reset(false, false, h->dev.auto_reset != 0);
-    RCW_HIP(rcw_launch_reset(h->dev, nullptr, h->stream));             // the counters move by one ...
-    RCW_HIP(launch_wall_bank(h, true));                                // ... and every agent starts that episode on a layout of the bank
-    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));
-    return RCW_OK;
+    std::memcpy(fresh.h_cum.get(), cum.data(), L * sizeof(uint32_t));
+    fresh.dev.kind = kLayoutBank;
+    fresh.dev.agents.layouts = layouts;
+    return install_layout_source(h, fresh);
 }
-
-extern "C++" {
-namespace {
-int need_wall_bank(rcw_handle* h) { return h->bank.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no wall bank (rcw_set_wall_bank)"); }
-int need_drawn_walls(rcw_handle* h) { return h->drawn() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms)"); }
-}  // namespace
-}  // extern "C++"
 
 // New weights for the installed bank, stream-ordered behind what is queued and without waiting for it: the cumulative weights travel through the
 // bank's pinned buffer, whose previous copy the event guards.
@@ -1180,12 +1238,13 @@ int rcw_set_wall_bank_weights(rcw_handle* h, const uint32_t* weights_host)
 {
     int rc = check_handle(h); if (rc) return rc;
     rc = need_wall_bank(h); if (rc) return rc;
-    rcw_handle::WallBank& wb = h->bank;
-    const size_t L = (size_t)wb.dev.layouts;
+    LayoutSource& wb = h->source;
+    const int32_t layouts = wb.dev.agents.layouts;
+    const size_t L = (size_t)layouts;
     std::vector<uint32_t> cum;
     try { cum.resize(L); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the cumulative weights failed"); }
     uint64_t total = 0;
-    rc = plan_wall_bank_weights(weights_host, wb.dev.layouts, cum.data(), &total); if (rc) return rc;
+    rc = plan_wall_bank_weights(weights_host, layouts, cum.data(), &total); if (rc) return rc;
     RCW_HIP(hipEventSynchronize(wb.ev_cum.get()));
     std::memcpy(wb.h_cum.get(), cum.data(), L * sizeof(uint32_t));
     RCW_HIP(hipMemcpyAsync(wb.cum.get(), wb.h_cum.get(), L * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
@@ -1197,8 +1256,8 @@ int rcw_set_wall_bank_weights(rcw_handle* h, const uint32_t* weights_host)
 int rcw_wall_bank_info(rcw_handle* h, int32_t* layouts, uint64_t* total_weight)
 {
     if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (layouts) *layouts = h->bank.on() ? h->bank.dev.layouts : 0;
-    if (total_weight) *total_weight = h->bank.total_weight;
+    if (layouts) *layouts = h->source.dev.agents.layouts;              // (zeros while the bank is off: a family has no layouts and no weights)
+    if (total_weight) *total_weight = h->source.total_weight;
     return RCW_OK;
 }
 
@@ -1206,59 +1265,37 @@ int rcw_wall_layout(rcw_handle* h, int32_t* out_host)
 {
     int rc = check_handle(h); if (rc) return rc;
     rc = need_drawn_walls(h); if (rc) return rc;
-    return copy_out<int32_t>(h, out_host, h->drawn()->layout, (size_t)h->B);
+    return copy_out<int32_t>(h, out_host, h->source.dev.agents.layout, (size_t)h->B);
 }
 
 int rcw_wall_layout_device_ptr(rcw_handle* h, void** device_ptr)
 {
     if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
     int rc = need_drawn_walls(h); if (rc) return rc;
-    *device_ptr = h->drawn()->layout;
+    *device_ptr = h->source.dev.agents.layout;
     return RCW_OK;
 }
 
-// The wall generator (include/rcw.h).  Validated and allocated before anything of the handle changes; then every agent is restarted under
-// the rule: the body of rcw_reset(h, NULL, <the handle's seed>) with the generator's kernel forced for every agent — rcw_set_wall_bank's
-// sequence without a bank to stage.
+// The wall generator's mazes (include/rcw.h, "the wall generator").
 int rcw_set_wall_generator(rcw_handle* h, int32_t enable, uint32_t loops, int32_t levels, int32_t first_level, uint64_t level_seed)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rcw_handle::WallGen& wg = h->gen;
-    if (!enable) {                                                     // off: the agents keep the walls they have (caves are not this call's to end)
-        if (!wg.mazes_on()) return RCW_OK;
-        RCW_HIP(replace_buffers(h, {&wg.agents}));
-        wg.dev = RcwWallBank{}; wg.par = RcwWallGen{};
-        return RCW_OK;
-    }
+    if (!enable) return drop_layout_source(h, kLayoutMazes);
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     rc = plan_wall_generator(H, W, levels, first_level); if (rc) return rc;
-    if (wg.caves_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_generator: the handle makes caves; switch them off first (rcw_set_wall_caves(h, 0, ...))");
-    if (wg.rooms_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_generator: the handle makes rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))");
-    if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_generator: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
-    const size_t B = (size_t)h->B;
-    RcwBuf fresh;
-    {
-        const hipError_t e = fresh.hipMalloc(3 * B * sizeof(uint32_t) + B);
-        if (e != hipSuccess) return fail(hip_code(e), "wall generator: %s", hip_failure(e));
-    }
-    RCW_HIP(replace_buffers(h, {&wg.agents}, {&fresh}));
-    uint32_t* const q = wg.agents.get<uint32_t>();
-    wg.dev = RcwWallBank{0, nullptr, nullptr, q, reinterpret_cast<int32_t*>(q + B), reinterpret_cast<int32_t*>(q + 2 * B), reinterpret_cast<uint8_t*>(q + 3 * B)};
-    wg.par = RcwWallGen{loops, levels, first_level, level_seed, (H - 1) / 2, (W - 1) / 2};
-    RCW_HIP(hipMemsetAsync(wg.agents.get(), 0, 3 * B * sizeof(uint32_t) + B, h->stream));
-    RCW_HIP(hipMemcpyAsync(wg.dev.status_seen, h->d_status.get(), B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
-    h->step.reset(false, false, h->dev.auto_reset != 0);
-    RCW_HIP(rcw_launch_reset(h->dev, nullptr, h->stream));             // the counters move by one ...
-    RCW_HIP(launch_wall_bank(h, true));                                // ... and every agent starts that episode in a maze of its own making
-    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));
-    return RCW_OK;
+    rc = refuse_other_source(h, "rcw_set_wall_generator", kLayoutMazes); if (rc) return rc;
+    LayoutSource fresh;
+    fresh.dev.kind = kLayoutMazes;
+    fresh.dev.gen = RcwWallGen{loops, levels, first_level, level_seed, (H - 1) / 2, (W - 1) / 2};
+    return install_layout_source(h, fresh);
 }
 
+// (any family: the level rule is the generator's, and loops is 0 while caves or rooms are live)
 int rcw_wall_generator_info(rcw_handle* h, int32_t* enabled, uint32_t* loops, int32_t* levels, int32_t* first_level, uint64_t* level_seed)
 {
     if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    const RcwWallGen& g = h->gen.par;                                  // (zeros while the generator is off)
-    if (enabled) *enabled = h->gen.on() ? 1 : 0;
+    const RcwWallGen& g = h->source.dev.gen;                           // (zeros while no family is live)
+    if (enabled) *enabled = h->source.live() && !h->source.is(kLayoutBank) ? 1 : 0;
     if (loops) *loops = g.loops;
     if (levels) *levels = g.levels;
     if (first_level) *first_level = g.first_level;
@@ -1266,100 +1303,54 @@ int rcw_wall_generator_info(rcw_handle* h, int32_t* enabled, uint32_t* loops, in
     return RCW_OK;
 }
 
-// The caves (include/rcw.h, "the wall generator: caves"): rcw_set_wall_generator's sequence with the other family's kernel behind the same
-// launch point.  The handle keeps them where it keeps the generator: the per-agent arrays, the level rule (loops 0: the fallback maze's).
+// The caves (include/rcw.h, "the wall generator: caves"); the level rule also carries the fallback maze's grid (loops 0).
 int rcw_set_wall_caves(rcw_handle* h, int32_t enable, uint32_t fill, int32_t smooth, int32_t levels, int32_t first_level, uint64_t level_seed)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rcw_handle::WallGen& wg = h->gen;
-    if (!enable) {                                                     // off: the agents keep the walls they have
-        if (!wg.caves_on()) return RCW_OK;
-        RCW_HIP(replace_buffers(h, {&wg.agents}));
-        wg.dev = RcwWallBank{}; wg.par = RcwWallGen{}; wg.cave = RcwWallCaves{}; wg.caves = false;
-        return RCW_OK;
-    }
+    if (!enable) return drop_layout_source(h, kLayoutCaves);
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     rc = plan_wall_caves(H, W, smooth, levels, first_level); if (rc) return rc;
-    if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_caves: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
-    if (wg.mazes_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_caves: the handle makes mazes; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
-    if (wg.rooms_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_caves: the handle makes rooms; switch them off first (rcw_set_wall_rooms(h, 0, ...))");
-    const size_t B = (size_t)h->B;
-    RcwBuf fresh;
-    {
-        const hipError_t e = fresh.hipMalloc(3 * B * sizeof(uint32_t) + B);
-        if (e != hipSuccess) return fail(hip_code(e), "wall caves: %s", hip_failure(e));
-    }
-    RCW_HIP(replace_buffers(h, {&wg.agents}, {&fresh}));
-    uint32_t* const q = wg.agents.get<uint32_t>();
-    wg.dev = RcwWallBank{0, nullptr, nullptr, q, reinterpret_cast<int32_t*>(q + B), reinterpret_cast<int32_t*>(q + 2 * B), reinterpret_cast<uint8_t*>(q + 3 * B)};
-    wg.par = RcwWallGen{0u, levels, first_level, level_seed, (H - 1) / 2, (W - 1) / 2};
-    wg.cave = RcwWallCaves{fill, smooth};
-    wg.caves = true;
-    RCW_HIP(hipMemsetAsync(wg.agents.get(), 0, 3 * B * sizeof(uint32_t) + B, h->stream));
-    RCW_HIP(hipMemcpyAsync(wg.dev.status_seen, h->d_status.get(), B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
-    h->step.reset(false, false, h->dev.auto_reset != 0);
-    RCW_HIP(rcw_launch_reset(h->dev, nullptr, h->stream));             // the counters move by one ...
-    RCW_HIP(launch_wall_bank(h, true));                                // ... and every agent starts that episode in a cave of its own making
-    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));
-    return RCW_OK;
+    rc = refuse_other_source(h, "rcw_set_wall_caves", kLayoutCaves); if (rc) return rc;
+    LayoutSource fresh;
+    fresh.dev.kind = kLayoutCaves;
+    fresh.dev.gen = RcwWallGen{0u, levels, first_level, level_seed, (H - 1) / 2, (W - 1) / 2};
+    fresh.dev.caves = RcwWallCaves{fill, smooth};
+    return install_layout_source(h, fresh);
 }
 
 int rcw_wall_caves_info(rcw_handle* h, int32_t* enabled, uint32_t* fill, int32_t* smooth)
 {
     if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    const bool on = h->gen.caves_on();                                 // (zeros while the caves are off)
-    if (enabled) *enabled = on ? 1 : 0;
-    if (fill) *fill = on ? h->gen.cave.fill : 0u;
-    if (smooth) *smooth = on ? h->gen.cave.smooth : 0;
+    const RcwWallCaves& c = h->source.dev.caves;                       // (zeros while the caves are off)
+    if (enabled) *enabled = h->source.is(kLayoutCaves) ? 1 : 0;
+    if (fill) *fill = c.fill;
+    if (smooth) *smooth = c.smooth;
     return RCW_OK;
 }
 
-// The rooms (include/rcw.h, "the wall generator: rooms"): the same sequence once more, the third family's kernel behind the launch point.  The
-// handle keeps them where it keeps the caves; the level rule travels in `par` (loops 0, no grid: rooms have no fallback maze).
+// The rooms (include/rcw.h, "the wall generator: rooms"); the level rule alone (loops 0, no grid: rooms have no fallback maze).
 int rcw_set_wall_rooms(rcw_handle* h, int32_t enable, int32_t room, uint32_t stop, uint32_t doors, int32_t levels, int32_t first_level, uint64_t level_seed)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rcw_handle::WallGen& wg = h->gen;
-    if (!enable) {                                                     // off: the agents keep the walls they have
-        if (!wg.rooms_on()) return RCW_OK;
-        RCW_HIP(replace_buffers(h, {&wg.agents}));
-        wg.dev = RcwWallBank{}; wg.par = RcwWallGen{}; wg.room = RcwWallRooms{}; wg.rooms = false;
-        return RCW_OK;
-    }
+    if (!enable) return drop_layout_source(h, kLayoutRooms);
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     rc = plan_wall_rooms(H, W, room, levels, first_level); if (rc) return rc;
-    if (h->bank.on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_rooms: the handle draws its walls from a wall bank; switch the bank off first (rcw_set_wall_bank(h, NULL, 0, NULL))");
-    if (wg.mazes_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_rooms: the handle makes mazes; switch the generator off first (rcw_set_wall_generator(h, 0, ...))");
-    if (wg.caves_on()) return fail(RCW_ERR_UNSUPPORTED, "rcw_set_wall_rooms: the handle makes caves; switch them off first (rcw_set_wall_caves(h, 0, ...))");
-    const size_t B = (size_t)h->B;
-    RcwBuf fresh;
-    {
-        const hipError_t e = fresh.hipMalloc(3 * B * sizeof(uint32_t) + B);
-        if (e != hipSuccess) return fail(hip_code(e), "wall rooms: %s", hip_failure(e));
-    }
-    RCW_HIP(replace_buffers(h, {&wg.agents}, {&fresh}));
-    uint32_t* const q = wg.agents.get<uint32_t>();
-    wg.dev = RcwWallBank{0, nullptr, nullptr, q, reinterpret_cast<int32_t*>(q + B), reinterpret_cast<int32_t*>(q + 2 * B), reinterpret_cast<uint8_t*>(q + 3 * B)};
-    wg.par = RcwWallGen{0u, levels, first_level, level_seed, 0, 0};
-    wg.room = RcwWallRooms{room, stop, doors};
-    wg.rooms = true;
-    RCW_HIP(hipMemsetAsync(wg.agents.get(), 0, 3 * B * sizeof(uint32_t) + B, h->stream));
-    RCW_HIP(hipMemcpyAsync(wg.dev.status_seen, h->d_status.get(), B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
-    h->step.reset(false, false, h->dev.auto_reset != 0);
-    RCW_HIP(rcw_launch_reset(h->dev, nullptr, h->stream));             // the counters move by one ...
-    RCW_HIP(launch_wall_bank(h, true));                                // ... and every agent starts that episode in rooms of its own making
-    RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));
-    return RCW_OK;
+    rc = refuse_other_source(h, "rcw_set_wall_rooms", kLayoutRooms); if (rc) return rc;
+    LayoutSource fresh;
+    fresh.dev.kind = kLayoutRooms;
+    fresh.dev.gen = RcwWallGen{0u, levels, first_level, level_seed, 0, 0};
+    fresh.dev.rooms = RcwWallRooms{room, stop, doors};
+    return install_layout_source(h, fresh);
 }
 
 int rcw_wall_rooms_info(rcw_handle* h, int32_t* enabled, int32_t* room, uint32_t* stop, uint32_t* doors)
 {
     if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    const bool on = h->gen.rooms_on();                                 // (zeros while the rooms are off)
-    if (enabled) *enabled = on ? 1 : 0;
-    if (room) *room = on ? h->gen.room.room : 0;
-    if (stop) *stop = on ? h->gen.room.stop : 0u;
-    if (doors) *doors = on ? h->gen.room.doors : 0u;
+    const RcwWallRooms& r = h->source.dev.rooms;                       // (zeros while the rooms are off)
+    if (enabled) *enabled = h->source.is(kLayoutRooms) ? 1 : 0;
+    if (room) *room = r.room;
+    if (stop) *stop = r.stop;
+    if (doors) *doors = r.doors;
     return RCW_OK;
 }
 

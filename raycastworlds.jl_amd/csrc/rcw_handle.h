@@ -184,36 +184,21 @@ struct rcw_handle {
         uint8_t* img = nullptr;
         bool on() const { return buf.get() != nullptr; }
     } local;
-    // The wall bank (rcw_set_wall_bank): the packed layouts, the cumulative weights, and ONE allocation of the per-agent arrays — recorded
-    // counter, recorded status, layout index (the three 4-byte arrays), then the mask; `dev` points into them.  The weights reach `cum`
-    // through a pinned staging buffer and an event (rcw_set_wall_bank_weights does not wait for the stream).  Of the bank the host keeps
-    // only its sizes: layouts and the weights' sum.  Empty while the bank is off.
-    struct WallBank {
+    // The layout source (rcw_kernels.h: the wall bank, or the wall generator's mazes, caves or rooms).  INVARIANT: at most one source is live —
+    // `dev.kind`, the only record of which —, and everything not of the live kind is empty or zero.  Every kind has `agents`, ONE allocation
+    // of the per-agent arrays — recorded counter, recorded status, layout index (the three 4-byte arrays), then the mask — into which
+    // `dev.agents` points.  The bank alone has the packed layouts, the cumulative weights, and the pinned buffer and event through which the
+    // weights reach `cum` (rcw_set_wall_bank_weights does not wait for the stream); of the bank the host keeps only its sizes: dev.agents.layouts
+    // and the weights' sum.  A family's parameters travel as kernel arguments: dev.gen (the level rule, the maze's loops and grid), dev.caves, dev.rooms.
+    struct LayoutSource {
         RcwBuf words, cum, agents;
         RcwPinned h_cum;
         RcwEvent ev_cum;
-        RcwWallBank dev{};
         uint64_t total_weight = 0;
-        bool on() const { return words.get() != nullptr; }
-    } bank;
-    // The wall generator (rcw_set_wall_generator): the bank's per-agent arrays (one allocation, the same order) and the parameters, which
-    // travel as kernel arguments.  It and the bank exclude each other; `drawn()` is whichever is on.  The caves (rcw_set_wall_caves) are the
-    // generator with another family: `caves` says so, `cave` holds the family's own two parameters, `par` the level rule (loops 0).
-    // The rooms (rcw_set_wall_rooms) are a third one, kept the same way: `rooms` and `room`.
-    struct WallGen {
-        RcwBuf agents;
-        RcwWallBank dev{};
-        RcwWallGen par{};
-        RcwWallCaves cave{};
-        bool caves = false;
-        RcwWallRooms room{};
-        bool rooms = false;
-        bool on() const { return agents.get() != nullptr; }
-        bool mazes_on() const { return on() && !caves && !rooms; }
-        bool caves_on() const { return on() && caves; }
-        bool rooms_on() const { return on() && rooms; }
-    } gen;
-    const RcwWallBank* drawn() const { return bank.on() ? &bank.dev : gen.on() ? &gen.dev : nullptr; }
+        RcwLayoutSource dev{};
+        bool is(RcwLayoutKind k) const { return dev.kind == k; }
+        bool live() const { return !is(kLayoutNone); }
+    } source;
     ~rcw_handle();
 };
 
@@ -264,7 +249,7 @@ hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_goal_distance(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_local_map(rcw_handle* h, StackOp op);
-hipError_t launch_wall_bank(rcw_handle* h, bool force);
+hipError_t launch_layout_source(rcw_handle* h, bool force);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
 hipError_t replace_buffers(rcw_handle* h, std::initializer_list<RcwBuf*> old, std::initializer_list<RcwBuf*> fresh = {});
 int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient);

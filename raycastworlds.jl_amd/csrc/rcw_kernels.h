@@ -210,51 +210,36 @@ hipError_t rcw_launch_seen_map(const RcwDev& p, int32_t B, const uint8_t* mask_d
 size_t rcw_local_map_lds_bytes(const RcwDev& p, int32_t size, bool seen);
 hipError_t rcw_launch_local_map(const RcwDev& p, int32_t B, const uint8_t* seen_map, const void* off, int32_t size, uint8_t* out, hipStream_t s);
 
-// The wall bank (rcw_set_wall_bank, rcw_wall_bank.hip): what its kernel reads and writes, all in DEVICE memory.
+// THE LAYOUT SOURCES (rcw_wall_bank.hip): what gives an agent its walls at every start of an episode.  A handle has at most one — the wall
+// bank (rcw_set_wall_bank) or one family of the wall generator: mazes (rcw_set_wall_generator), caves (rcw_set_wall_caves), rooms
+// (rcw_set_wall_rooms) — behind ONE launch point, rcw_launch_layout_source.
+enum RcwLayoutKind { kLayoutNone, kLayoutBank, kLayoutMazes, kLayoutCaves, kLayoutRooms };
+
+// The per-agent arrays of every source and, of the bank, its layouts: what the kernels read and write, all in DEVICE memory.
 struct RcwWallBank {
-    int32_t layouts;             // L >= 1
+    int32_t layouts;             // the bank: L >= 1; a generator family: 0, words and cum NULL
     const uint32_t* words;       // [L][nwords] the layouts in the tile map's word format: WALL bits set, GOAL bits and the padding clear
     const uint32_t* cum;         // [L] cumulative weights, cum[L - 1] = the sum (1 .. 2^32 - 1)
-    uint32_t* last_episode;      // [B] each agent's episode counter as of its last start under the bank
+    uint32_t* last_episode;      // [B] each agent's episode counter as of its last start under the source
     int32_t* status_seen;        // [B] ... and its status word as of then
-    int32_t* layout;             // [B] the layout the agent's episode was given (rcw_wall_layout)
+    int32_t* layout;             // [B] the layout the agent's episode was given: the bank's index, a family's level or -1 (rcw_wall_layout)
     uint8_t* mask;               // [B] 1: the launch gave the agent a layout and a fresh state — the host re-renders these
 };
-// The layouts UInt8 (H*W, layouts) in device memory -> words; one launch, once per rcw_set_wall_bank.
-hipError_t rcw_launch_wall_bank_pack(const RcwDev& p, const uint8_t* walls_dev, uint32_t* words_dev, int32_t layouts, hipStream_t s);
-// One launch behind the core launches of a call that can move an episode counter: an agent whose counter differs from last_episode (force:
-// every agent) takes a layout and is reset against it under its episode's own key (counter: what the launch in front left); mask[a] says who.
-hipError_t rcw_launch_wall_bank(const RcwPlan& p, const RcwWallBank& bank, bool force, hipStream_t s);
-// The camera view (p.obs) of the agents with mask[a] != 0 from p.col_h / p.col_c, a workgroup an agent: the repaint behind rcw_launch_wall_bank,
-// whose mask is sparse — the camera fill's pixels, without its sweep over the whole batch.
-hipError_t rcw_launch_wall_bank_paint(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);
-
-// The wall generator (rcw_set_wall_generator, rcw_wall_bank.hip): a maze made in LDS where the bank copies one.  The per-agent arrays are an
-// RcwWallBank's (layouts 0, words and cum NULL); the parameters are kernel arguments, fixed at install.
+// The level rule of the generator families and the maze's own parameters: kernel arguments, fixed at install.
 struct RcwWallGen {
-    uint32_t loops;              // a non-tree edge is opened where the high word of its draw is below this
-    int32_t levels, first_level; // levels == 0: a maze of its own every episode; else level first_level + below(u, levels)
+    uint32_t loops;              // mazes: a non-tree edge is opened where the high word of its draw is below this; caves, rooms: 0
+    int32_t levels, first_level; // levels == 0: a layout of its own every episode; else level first_level + below(u, levels)
     uint64_t level_seed;
-    int32_t ni, nj;              // the cell grid: (H - 1) / 2 by (W - 1) / 2, ni * nj <= kWallGenMaxCells
+    int32_t ni, nj;              // the maze's cell grid (the caves' fallback too): (H - 1) / 2 by (W - 1) / 2, ni * nj <= kWallGenMaxCells; rooms: 0, 0
 };
 constexpr int kWallGenMaxCells = 4096;
-// Where rcw_launch_wall_bank goes on a handle with a generator: the same contract (counter moved or force -> a maze and a fresh state, mask[a]).
-hipError_t rcw_launch_wall_generator(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, bool force, hipStream_t s);
-
-// The caves (rcw_set_wall_caves, rcw_wall_bank.hip): the generator's slot with another family.  `gen` carries the level rule and the fallback
-// maze's grid (loops 0); these two are the family's own kernel arguments.
-struct RcwWallCaves {
+struct RcwWallCaves {            // the caves' own two kernel arguments
     uint32_t fill;               // an interior tile is WALL in generation 0 where the high word of its draw is below this
     int32_t smooth;              // smoothing steps, 0 .. kWallCavesMaxSmooth
 };
 constexpr int kWallCavesMaxTiles = 4096;   // (H - 2)(W - 2): maps up to 66 x 66
 constexpr int kWallCavesMaxSmooth = 8;
-size_t rcw_wall_caves_lds_bytes(int H, int W, int nwords);
-hipError_t rcw_launch_wall_caves(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, const RcwWallCaves& caves, bool force, hipStream_t s);
-
-// The rooms (rcw_set_wall_rooms, rcw_wall_bank.hip): the generator's slot with a third family.  `gen` carries the level rule alone (loops 0,
-// no grid: rooms have no fallback); these three are the family's own kernel arguments.
-struct RcwWallRooms {
+struct RcwWallRooms {            // the rooms' own three kernel arguments
     int32_t room;                // the least side of a room, >= 1
     uint32_t stop;               // a chamber other than the root is left whole where the high word of its stop draw is below this
     uint32_t doors;              // a wall gets a second door where the high word of its draw is below this
@@ -262,5 +247,23 @@ struct RcwWallRooms {
 constexpr int kWallRoomsMaxRooms = 4096;   // Q = ceil((H - 2) / 2) ceil((W - 2) / 2): 130 x 130, 5 x 4097
 constexpr int kWallRoomsMaxTiles = 65536;  // H W: a chamber's two corner tiles share one draw index
 inline long long rcw_wall_rooms_bound(int H, int W) { return (long long)((H - 1) / 2) * (long long)((W - 1) / 2); }   // (ceil((H - 2) / 2) = (H - 1) / 2)
-size_t rcw_wall_rooms_lds_bytes(int H, int W, int nwords);
-hipError_t rcw_launch_wall_rooms(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, const RcwWallRooms& rooms, bool force, hipStream_t s);
+
+// The live source as its launcher reads it.  What is not of the live kind is zero: the bank has no gen / caves / rooms, a family only the
+// per-agent arrays of `agents`, mazes no caves / rooms, and so on.
+struct RcwLayoutSource {
+    RcwLayoutKind kind;
+    RcwWallBank agents;
+    RcwWallGen gen;
+    RcwWallCaves caves;
+    RcwWallRooms rooms;
+};
+// One launch behind the core launches of a call that can move an episode counter, a wavefront an agent: an agent whose counter differs from
+// last_episode (force: every agent) takes a layout of the live kind — drawn from the bank, or made in LDS — and is reset against it under its
+// episode's own key (counter: what the launch in front left); mask[a] says who.  hipSuccess and no launch without a live source,
+// hipErrorInvalidValue for a geometry past the live family's bound (the plan_wall_* rules refuse those first).
+hipError_t rcw_launch_layout_source(const RcwPlan& p, const RcwLayoutSource& src, bool force, hipStream_t s);
+// The layouts UInt8 (H*W, layouts) in device memory -> words; one launch, once per rcw_set_wall_bank.
+hipError_t rcw_launch_wall_bank_pack(const RcwDev& p, const uint8_t* walls_dev, uint32_t* words_dev, int32_t layouts, hipStream_t s);
+// The camera view (p.obs) of the agents with mask[a] != 0 from p.col_h / p.col_c, a workgroup an agent: the repaint behind
+// rcw_launch_layout_source, whose mask is sparse — the camera fill's pixels, without its sweep over the whole batch.
+hipError_t rcw_launch_wall_bank_paint(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);

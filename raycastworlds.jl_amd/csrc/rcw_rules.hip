@@ -443,12 +443,20 @@ int plan_wall_bank_weights(const uint32_t* weights, int32_t layouts, uint32_t* c
 }
 
 // ---- the wall generator (include/rcw.h, "the wall generator") ---------------------------------------------------------------------------
+// The level range of a generator family (the maze, the caves and the rooms share the rule): levels of first_level .. first_level + levels - 1,
+// Int32 all of them — or the refusal, in the family's words.
+static bool level_range_ok(int32_t levels, int32_t first_level) { return levels >= 0 && first_level >= 0 && (int64_t)first_level + (int64_t)levels <= 2147483647ll; }
+static int check_level_range(const char* whose, int32_t levels, int32_t first_level)
+{
+    if (level_range_ok(levels, first_level)) return RCW_OK;
+    return fail(RCW_ERR_INVALID_ARGUMENT, "%s level range must satisfy levels >= 0, first_level >= 0 and first_level + levels <= 2^31 - 1 (got first_level %d, levels %d)", whose, first_level, levels);
+}
+
 // What rcw_set_wall_generator checks of a geometry and a level range before anything is queued — or the refusal.
 int plan_wall_generator(int32_t H, int32_t W, int32_t levels, int32_t first_level)
 {
     if (H < 5 || W < 5) return fail(RCW_ERR_INVALID_ARGUMENT, "the wall generator needs a map of at least 5 x 5 tiles (this one is %d x %d)", H, W);
-    if (levels < 0 || first_level < 0 || (int64_t)first_level + (int64_t)levels > 2147483647ll)
-        return fail(RCW_ERR_INVALID_ARGUMENT, "the wall generator's level range must satisfy levels >= 0, first_level >= 0 and first_level + levels <= 2^31 - 1 (got first_level %d, levels %d)", first_level, levels);
+    if (const int rc = check_level_range("the wall generator's", levels, first_level)) return rc;
     const int64_t cells = (int64_t)((H - 1) / 2) * (int64_t)((W - 1) / 2);
     if (cells > kWallGenMaxCells)
         return fail(RCW_ERR_UNSUPPORTED, "the wall generator makes mazes of at most %d cells (maps up to 129 x 129); %d x %d has %lld", kWallGenMaxCells, H, W, (long long)cells);
@@ -460,7 +468,7 @@ int plan_wall_generator(int32_t H, int32_t W, int32_t levels, int32_t first_leve
 extern "C" int rcw_wall_generator_key(uint64_t seed, int32_t global_agent, uint32_t episode, int32_t levels, int32_t first_level, uint64_t level_seed,
                                       uint64_t* maze_key, int32_t* level)
 {
-    if (global_agent < 0 || levels < 0 || first_level < 0 || (int64_t)first_level + (int64_t)levels > 2147483647ll)
+    if (global_agent < 0 || !level_range_ok(levels, first_level))
         return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_wall_generator_key: global_agent >= 0, levels >= 0, first_level >= 0 and first_level + levels <= 2^31 - 1 are required");
     const uint64_t u = rcw_draw(rcw_episode_key(seed, (uint64_t)global_agent, (uint64_t)episode), 0x8000000000000000ull);
     int32_t l = -1;
@@ -518,8 +526,7 @@ int plan_wall_caves(int32_t H, int32_t W, int32_t smooth, int32_t levels, int32_
 {
     if (H < 5 || W < 5) return fail(RCW_ERR_INVALID_ARGUMENT, "caves need a map of at least 5 x 5 tiles (this one is %d x %d)", H, W);
     if (smooth < 0 || smooth > kWallCavesMaxSmooth) return fail(RCW_ERR_INVALID_ARGUMENT, "caves are smoothed 0 .. %d times (got %d)", kWallCavesMaxSmooth, smooth);
-    if (levels < 0 || first_level < 0 || (int64_t)first_level + (int64_t)levels > 2147483647ll)
-        return fail(RCW_ERR_INVALID_ARGUMENT, "the caves' level range must satisfy levels >= 0, first_level >= 0 and first_level + levels <= 2^31 - 1 (got first_level %d, levels %d)", first_level, levels);
+    if (const int rc = check_level_range("the caves'", levels, first_level)) return rc;
     const int64_t tiles = (int64_t)(H - 2) * (int64_t)(W - 2);
     if (tiles > kWallCavesMaxTiles)
         return fail(RCW_ERR_UNSUPPORTED, "caves are made on at most %d interior tiles (maps up to 66 x 66); %d x %d has %lld", kWallCavesMaxTiles, H, W, (long long)tiles);
@@ -578,8 +585,7 @@ int plan_wall_rooms(int32_t H, int32_t W, int32_t room, int32_t levels, int32_t 
 {
     if (H < 5 || W < 5) return fail(RCW_ERR_INVALID_ARGUMENT, "rooms need a map of at least 5 x 5 tiles (this one is %d x %d)", H, W);
     if (room < 1) return fail(RCW_ERR_INVALID_ARGUMENT, "a room's least side must be at least 1 tile (got %d)", room);
-    if (levels < 0 || first_level < 0 || (int64_t)first_level + (int64_t)levels > 2147483647ll)
-        return fail(RCW_ERR_INVALID_ARGUMENT, "the rooms' level range must satisfy levels >= 0, first_level >= 0 and first_level + levels <= 2^31 - 1 (got first_level %d, levels %d)", first_level, levels);
+    if (const int rc = check_level_range("the rooms'", levels, first_level)) return rc;
     const long long bound = rcw_wall_rooms_bound(H, W), tiles = (long long)H * (long long)W;
     if (bound > kWallRoomsMaxRooms)
         return fail(RCW_ERR_UNSUPPORTED, "rooms are made on maps of at most %d odd-odd interior tiles, ceil((H - 2) / 2) ceil((W - 2) / 2) (up to 130 x 130 or 5 x 4097); %d x %d has %lld", kWallRoomsMaxRooms, H, W, bound);

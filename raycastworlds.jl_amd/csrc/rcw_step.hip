@@ -131,7 +131,7 @@ hipError_t paint_camera(rcw_handle* h, const uint8_t* mask_dev, hipStream_t stre
     return rcw_launch_fill(h->dev, h->dev.col_h, h->dev.col_c, h->dev.obs, (long long)h->dev.B * h->dev.N, mask_dev, stream);
 }
 
-// ... or, behind the wall bank's kernel (sparse: the mask is the bank's, nearly always empty), a workgroup an agent instead of the window's sweep
+// ... or, behind the layout source's kernel (sparse: the mask is the source's, nearly always empty), a workgroup an agent instead of the window's sweep
 hipError_t paint_camera(rcw_handle* h, const uint8_t* mask_dev, hipStream_t stream, bool sparse)
 {
     return sparse ? rcw_launch_wall_bank_paint(h->dev, mask_dev, stream) : paint_camera(h, mask_dev, stream);
@@ -185,7 +185,7 @@ hipError_t launch_step_two(rcw_handle* h, const uint8_t* actions_dev, const uint
     return prof.done(h->stream);
 }
 
-// (bank = true: the wall bank's re-render of the agents it restarted — behind the step proper, outside its bracket, the mask sparse)
+// (bank = true: the layout source's re-render of the agents it restarted — behind the step proper, outside its bracket, the mask sparse)
 hipError_t launch_step_camera(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, bool bank = false)
 {
     const StepFacts::Camera c = h->step.camera_step(actions_dev != nullptr, mask_dev != nullptr, [h] {
@@ -241,29 +241,27 @@ hipError_t launch_local_map(rcw_handle* h, StackOp op)
     return rcw_launch_local_map(h->dev, h->B, lm.source == RCW_LOCAL_SEEN ? h->seen.map : nullptr, lm.off, lm.size, lm.img, h->stream);
 }
 
-// The wall bank (rcw_set_wall_bank), behind the core launches of a call that can move an episode counter: its kernel gives every agent that
-// began an episode a layout and a fresh state against it, and leaves in the bank's own mask who that was.  force: every agent (the call
-// that installs the bank).  Behind rcw_reset the caller's re-render covers exactly those agents; behind a step, launch_step re-renders them.
-hipError_t launch_wall_bank(rcw_handle* h, bool force)
+// The layout source (rcw_handle::LayoutSource), behind the core launches of a call that can move an episode counter: its kernel gives every
+// agent that began an episode a layout and a fresh state against it, and leaves in the source's own mask who that was.  force: every agent
+// (the call that installs the source).  Behind rcw_reset the caller's re-render covers exactly those agents; behind a step, launch_step
+// re-renders them.  A handle without a source launches nothing.
+hipError_t launch_layout_source(rcw_handle* h, bool force)
 {
-    if (h->gen.rooms_on()) return rcw_launch_wall_rooms(h->dev, h->gen.dev, h->gen.par, h->gen.room, force, h->stream);   // (rooms: the same slot, a third family)
-    if (h->gen.caves_on()) return rcw_launch_wall_caves(h->dev, h->gen.dev, h->gen.par, h->gen.cave, force, h->stream);   // (caves: the generator's slot, another family)
-    if (h->gen.on()) return rcw_launch_wall_generator(h->dev, h->gen.dev, h->gen.par, force, h->stream);   // (the generator: a maze made where the bank copies one)
-    return h->bank.on() ? rcw_launch_wall_bank(h->dev, h->bank.dev, force, h->stream) : hipSuccess;
+    return rcw_launch_layout_source(h->dev, h->source.dev, force, h->stream);
 }
 
-// A step of a handle with a wall bank: the step proper, the bank's kernel, the camera view of the agents it restarted once more through the
-// masked path (valid in both step forms: a masked prime behind a one-launch step is what rcw_set_walls(mask) queues) — all OUTSIDE
+// A step of a handle with a layout source: the step proper, the source's kernel, the camera view of the agents it restarted once more through
+// the masked path (valid in both step forms: a masked prime behind a one-launch step is what rcw_set_walls(mask) queues) — all OUTSIDE
 // rcw_profile's bracket —, and then every feature ONCE: they key on the episode counter and find the restarted agents stale against the
-// final world.  A handle without a bank launches what it launched before.
+// final world.  A handle without a source launches what it launched before.
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op)
 {
-    const RcwWallBank* const drawn = h->drawn();                           // (the bank's per-agent arrays, or the generator's)
-    const bool bank = drawn != nullptr && actions_dev != nullptr;
+    const uint8_t* const restarted = h->source.dev.agents.mask;            // (whom the source's kernel restarted; NULL without a source)
+    const bool restarts = h->source.live() && actions_dev != nullptr;
     if (!h->learner.only()) {
         hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
-        if (e == hipSuccess && bank) e = launch_wall_bank(h, false);
-        if (e == hipSuccess && bank) e = launch_step_camera(h, nullptr, drawn->mask, true);
+        if (e == hipSuccess && restarts) e = launch_layout_source(h, false);
+        if (e == hipSuccess && restarts) e = launch_step_camera(h, nullptr, restarted, true);
         if (e == hipSuccess && h->learner.on()) e = launch_view(h, mask_dev, op);
         if (e == hipSuccess) e = launch_goal_distance(h, mask_dev, op);
         if (e == hipSuccess) e = launch_seen_map(h, mask_dev, op);
@@ -275,9 +273,9 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if ((e = prof.mark(0, h->stream)) != hipSuccess) return e;
     if ((e = rcw_launch_cast(h->dev, actions_dev, mask_dev, h->stream)) != hipSuccess) return e;
     h->step.columns_cast(mask_dev != nullptr);
-    // (RCW_VIEW_ONLY: nothing is rendered yet — the bank's kernel and the restarted agents' cast go right here, and the top view and the
-    // view kernel below render every agent once; the two launches count into cast_ms of a handle that has a bank)
-    if (bank && ((e = launch_wall_bank(h, false)) != hipSuccess || (e = rcw_launch_cast(h->dev, nullptr, drawn->mask, h->stream)) != hipSuccess)) return e;
+    // (RCW_VIEW_ONLY: nothing is rendered yet — the source's kernel and the restarted agents' cast go right here, and the top view and the
+    // view kernel below render every agent once; the two launches count into cast_ms of a handle that has a source)
+    if (restarts && ((e = launch_layout_source(h, false)) != hipSuccess || (e = rcw_launch_cast(h->dev, nullptr, restarted, h->stream)) != hipSuccess)) return e;
     if ((e = prof.mark(1, h->stream)) != hipSuccess) return e;
     if (h->dev.top_view && (e = launch_top_view_alone(h, mask_dev)) != hipSuccess) return e;
     if ((e = prof.mark(2, h->stream)) != hipSuccess) return e;

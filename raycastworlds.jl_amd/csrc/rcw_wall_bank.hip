@@ -1,30 +1,34 @@
-// The wall bank (include/rcw.h, rcw_set_wall_bank): L wall layouts resident on the device, one of them drawn for an agent at every start of
-// an episode.  Three kernels; nothing else of the library knows about the bank.  The wall generator's kernel (further down) lives here too:
-// it shares the bank's tail; so does the caves' kernel behind it, which also shares the maze.  The rooms' kernel is the third
-// family behind the same launch point: the key and the tail, no maze.
-//
-// rcw_wall_bank_pack_kernel   once per rcw_set_wall_bank: the layouts, UInt8 (H*W, L) as rcw_set_walls takes them, into the tile map's own
-//          word format — nwords uint32 a layout, 16 tiles a word, bit 0 of each 2-bit field = WALL, the GOAL bits and the padding past H*W
-//          clear (what rcw_set_walls_kernel writes).  A thread a word, 16 byte loads each: paid once, not per episode.
-// rcw_wall_bank_kernel<T>     behind the core launches of every call that can move an episode counter.  ONE WAVEFRONT PER AGENT (a 64-thread
-//          workgroup: every __syncthreads below orders the wave's own LDS traffic and costs no barrier instruction).  The usual case — the
-//          agent has not begun an episode — reads two words (its counter and the recorded one), writes mask[a] = 0 and leaves.  An agent whose
-//          counter moved (by one: the kernel runs behind every such call) began episode e = counter - 1 in the launch in front, against the
-//          walls it had; that reset is discarded:
-//            k       the layout: draw 2^63 of the episode's key — reset_agent's own indices count from 0 and stay far below —, scaled to the
-//                    weights' sum, looked up in the cumulative weights by binary search (uniform: scalar registers, log2 L loads);
-//            LDS     layout k's words, copied by the whole wave (lane + 64 i: maps of more than 64 words loop);
-//            lane 0  puts the counter back to e and runs reset_agent against the LDS copy: the SAME key, draw indices from 0 — the
-//                    rejection loops are sequential per agent, so one lane runs them, as in rcw_reset_kernel —, which writes goal, pose,
-//                    heading, reward, done and the counter e + 1; then the time limit's two words, wall_layout[a], the recorded counter;
-//            HBM     the LDS words (walls + the new goal bit) over the agent's tile map, coalesced: the tile map in HBM is only ever
-//                    written whole, no read-modify-write meets the copy;
-//          and mask[a] = 1: the host re-casts the masked agents through the existing masked path and repaints their camera view with
-//          rcw_wall_bank_paint_kernel below (a handle with a top view: through the existing masked fill, which may carry the drawing).
-//          The discarded reset leaves one possible trace, the sticky status word (RCW_WARN_SAMPLER_GAVE_UP is set only over 0).  `status_seen`
-//          holds each agent's status word as of its last start here (rcw_clear_error zeroes it with the words): a warning that is there now
-//          and was not then can only be the discarded reset's — the restarted agent's action was ignored, no other writer ran — and is
-//          taken back before the real reset may set its own.
+// The layout sources (rcw_kernels.h, "THE LAYOUT SOURCES"): ONE launch point, rcw_launch_layout_source — behind the core launches of every
+// call that can move an episode counter — and behind it one of four restart kernels, by the kind of the handle's live source:
+//   rcw_wall_bank_kernel<T>        the wall bank: layout k of L resident on the device, k drawn by the weights
+//   rcw_wall_generator_kernel<T>   mazes: a spanning tree of the odd sub-grid, made in LDS (maze_in_lds)
+//   rcw_wall_caves_kernel<T>       caves: a smoothed random fill pruned to its largest region, made in LDS; the maze where that is too small
+//   rcw_wall_rooms_kernel<T>       rooms: the interior split recursively by walls with doors, made in LDS
+// Nothing else of the library knows where a layout comes from.  What the four share:
+//   the shape   ONE WAVEFRONT PER AGENT (a 64-thread workgroup: every __syncthreads below orders the wave's own LDS traffic and costs no
+//               barrier instruction), the episode's layout in LDS in the tile map's own word format — nwords uint32 an agent, 16 tiles a
+//               word, bit 0 of each 2-bit field = WALL, the GOAL bits and the padding past H*W clear (what rcw_set_walls_kernel writes);
+//   no_restart  the opening.  The usual case — the agent has not begun an episode — reads two words (its counter and the recorded one),
+//               writes mask[a] = 0 and leaves.  An agent whose counter moved (by one: the kernel runs behind every such call) began episode
+//               e = counter - 1 in the launch in front, against the walls it had; that reset is discarded;
+//   the key     draw 2^63 of the episode's key — reset_agent's own indices count from 0 and stay far below —: the bank scales it to the
+//               weights' sum and looks it up in the cumulative weights by binary search (uniform: scalar registers, log2 L loads), a family
+//               takes it as the layout's key, or picks a level with it and takes the level's key (layout_key);
+//   restart_on_lds_words   the tail.  Lane 0 puts the counter back to e and runs reset_agent against the LDS words: the SAME key, draw
+//               indices from 0 — the rejection loops are sequential per agent, so one lane runs them, as in rcw_reset_kernel —, which writes
+//               goal, pose, heading, reward, done and the counter e + 1; then the time limit's two words, wall_layout[a], the recorded
+//               counter.  The wave copies the LDS words (walls + the new goal bit) over the agent's tile map, coalesced: the tile map in HBM
+//               is only ever written whole, no read-modify-write meets the copy;
+//   mask[a] = 1 the host re-casts the masked agents through the existing masked path and repaints their camera view with
+//               rcw_wall_bank_paint_kernel below (a handle with a top view: through the existing masked fill, which may carry the drawing).
+// The discarded reset leaves one possible trace, the sticky status word (RCW_WARN_SAMPLER_GAVE_UP is set only over 0).  `status_seen` holds
+// each agent's status word as of its last start here (rcw_clear_error zeroes it with the words): a warning that is there now and was not
+// then can only be the discarded reset's — the restarted agent's action was ignored, no other writer ran — and is taken back before the
+// real reset may set its own.
+// Beside them, the bank's two other kernels:
+//   rcw_wall_bank_pack_kernel   once per rcw_set_wall_bank: the layouts, UInt8 (H*W, L) as rcw_set_walls takes them, into the word format.  A
+//               thread a word, 16 byte loads each: paid once, not per episode;
+//   rcw_wall_bank_paint_kernel  the camera view of the agents a launch restarted.
 #include "rcw_device.h"
 
 namespace {
@@ -47,7 +51,26 @@ __global__ void rcw_wall_bank_pack_kernel(const uint8_t* __restrict__ walls, uin
     words[g] = word;
 }
 
-// The tail the bank's kernel and the generator's share, behind a barrier: the episode's layout (WALL bits, nothing else) lies in lds_w.
+// The opening of the four restart kernels, behind the loads of the agent's counter ep: has the agent begun no episode since its last start
+// here (and is not every agent restarted: force)?  Then mask[a] = 0 and the wave leaves.
+__device__ __forceinline__ bool no_restart(const RcwWallBank& b, int force, int a, int lane, uint32_t ep)
+{
+    if (!force && b.last_episode[a] == ep) {
+        if (lane == 0) b.mask[a] = 0;
+        return true;
+    }
+    return false;
+}
+
+// Word w of a layout whose every tile is WALL: the tiles of the word inside the map set, the padding clear (nwords is even: a whole word may
+// be padding).
+__device__ __forceinline__ uint32_t all_wall_word(int HW, int w)
+{
+    const int left = HW - 16 * w;
+    return left >= 16 ? 0x55555555u : left <= 0 ? 0u : (0x55555555u & ((1u << (2 * left)) - 1u));
+}
+
+// The tail the four restart kernels share, behind a barrier: the episode's layout (WALL bits, nothing else) lies in lds_w.
 // Lane 0 takes back the discarded reset's status, puts the counter back to e = ep - 1 and runs reset_agent against the LDS words; then the
 // wave copies them over the agent's tile map.  k: what wall_layout[a] says.
 template <typename T>
@@ -77,10 +100,7 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_bank_kernel(const RcwDev 
     const int a = blockIdx.x, lane = threadIdx.x;
     if (a >= p.B) return;
     const uint32_t ep = p.episode[a];
-    if (!force && b.last_episode[a] == ep) {
-        if (lane == 0) b.mask[a] = 0;
-        return;
-    }
+    if (no_restart(b, force, a, lane, ep)) return;
     // the layout of episode e = ep - 1 (the counter before the increment the launch in front made)
     const uint32_t e = ep - 1u;
     const uint64_t key = rcw_episode_key(p.seed, (uint64_t)(p.agent_id_offset + a), (uint64_t)e);
@@ -98,9 +118,8 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_bank_kernel(const RcwDev 
     restart_on_lds_words<T>(p, lim, b, a, lane, lds_b, ep, k);
 }
 
-// ---- the wall generator (include/rcw.h, "the wall generator") ---------------------------------------------------------------------------
-// rcw_wall_generator_kernel<T>   the bank's kernel with another layout source: the same launch point, the same common path (two loads, one
-//          byte, exit), the same tail.  An agent that began an episode gets the maze of one 64-bit key m, made by the whole wave in LDS:
+// ---- mazes (include/rcw.h, "the wall generator") ------------------------------------------------------------------------------------------
+// rcw_wall_generator_kernel<T>   An agent that began an episode gets the maze of one 64-bit key m, made by the whole wave in LDS:
 //            words   [nwords]  the tile map's words: every tile WALL, then the cells' bits cleared (ds_and);
 //            slot    [C]       per label the smallest order word of an edge leaving it this round (ds_min_u64), then its hook;
 //            label   [C]       per cell the cell that names its component (label[root] == root);
@@ -127,10 +146,7 @@ __device__ __forceinline__ void maze_in_lds(uint32_t* const words, void* const s
     const int C = ni * nj;
     unsigned long long* const slot = reinterpret_cast<unsigned long long*>(scratch);
     uint32_t* const label = reinterpret_cast<uint32_t*>(slot + C);
-    for (int w = lane; w < nwords; w += kBankBlock) {
-        const int left = HW - 16 * w;                                      // tiles of this word inside the map (the padding stays clear)
-        words[w] = left >= 16 ? 0x55555555u : left <= 0 ? 0u : (0x55555555u & ((1u << (2 * left)) - 1u));   // (nwords is even: a whole word may be padding)
-    }
+    for (int w = lane; w < nwords; w += kBankBlock) words[w] = all_wall_word(HW, w);
     for (int c = lane; c < C; c += kBankBlock) label[c] = (uint32_t)c;
     __syncthreads();
     for (int c = lane; c < C; c += kBankBlock) {
@@ -222,19 +238,15 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_generator_kernel(const Rc
     const int a = blockIdx.x, lane = threadIdx.x;
     if (a >= p.B) return;
     const uint32_t ep = p.episode[a];
-    if (!force && b.last_episode[a] == ep) {
-        if (lane == 0) b.mask[a] = 0;
-        return;
-    }
+    if (no_restart(b, force, a, lane, ep)) return;
     int level;
     const uint64_t m = layout_key(p, g, a, ep, &level);
     maze_in_lds(lds_g, lds_g + ((p.nwords + 1) & ~1), p.H, p.H * p.W, p.nwords, g.ni, g.nj, m, g.loops, lane);   // (the scratch: 8-byte aligned)
     restart_on_lds_words<T>(p, lim, b, a, lane, lds_g, ep, level);
 }
 
-// ---- the wall generator: caves (include/rcw.h, "the wall generator: caves") --------------------------------------------------------------
-// rcw_wall_caves_kernel<T>   the generator's kernel with another layout: the same launch point, common path, key and tail.  An agent that
-//          began an episode gets cave(m, H, W, fill, smooth), made by the whole wave in LDS over the n = (H - 2)(W - 2) INTERIOR tiles,
+// ---- caves (include/rcw.h, "the wall generator: caves") ------------------------------------------------------------------------------------
+// rcw_wall_caves_kernel<T>   An agent that began an episode gets cave(m, H, W, fill, smooth), made by the whole wave in LDS over the n = (H - 2)(W - 2) INTERIOR tiles,
 //          q = (i - 1) + (H - 2)(j - 1) — the tile map's own order, so the smallest q of a region is its smallest tile index:
 //            words   [nwords]  the tile map's words, written last;
 //            label   [n]       per free tile the tile that names its region (label[root] == root), kNoLabel on a wall;
@@ -263,10 +275,7 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_caves_kernel(const RcwDev
     const int a = blockIdx.x, lane = threadIdx.x;
     if (a >= p.B) return;
     const uint32_t ep = p.episode[a];
-    if (!force && b.last_episode[a] == ep) {
-        if (lane == 0) b.mask[a] = 0;
-        return;
-    }
+    if (no_restart(b, force, a, lane, ep)) return;
     const int H = p.H, nwords = p.nwords, HW = p.H * p.W, h = p.H - 2, w = p.W - 2, n = h * w;
     uint32_t* const words = lds_c;
     uint32_t* const label = lds_c + ((nwords + 1) & ~1);                    // (8-byte aligned: the maze's slots alias it)
@@ -341,8 +350,8 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_caves_kernel(const RcwDev
     const int size = (int)(kept >> 16), need = max(7, n / 4);
     if (size >= need) {
         const uint32_t root = 0xFFFFu - (kept & 0xFFFFu);
-        for (int x = lane; x < nwords; x += kBankBlock) {
-            const int left = HW - 16 * x;                                  // tiles of this word inside the map (the padding stays clear)
+        for (int x = lane; x < nwords; x += kBankBlock) {                  // (all_wall_word's expression, written out: through the helper this kernel's code comes out different)
+            const int left = HW - 16 * x;
             words[x] = left >= 16 ? 0x55555555u : left <= 0 ? 0u : (0x55555555u & ((1u << (2 * left)) - 1u));
         }
         __syncthreads();
@@ -358,9 +367,8 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_caves_kernel(const RcwDev
     restart_on_lds_words<T>(p, lim, b, a, lane, words, ep, level);
 }
 
-// ---- the wall generator: rooms (include/rcw.h, "the wall generator: rooms") --------------------------------------------------------------
-// rcw_wall_rooms_kernel<T>   the generator's kernel with a third layout: the same launch point, common path, key and tail.  An agent that
-//          began an episode gets rooms(m, H, W, room, stop, doors), made by the whole wave in LDS:
+// ---- rooms (include/rcw.h, "the wall generator: rooms") ------------------------------------------------------------------------------------
+// rcw_wall_rooms_kernel<T>   An agent that began an episode gets rooms(m, H, W, room, stop, doors), made by the whole wave in LDS:
 //            words   [nwords]  the tile map's words: the ring WALL, the interior free, the padding clear; wall tiles are set with ds_or;
 //            list    [Q]       the chambers, four uint16 each (i0, i1, j0, j1, inclusive); i0 == 0 flags a room (a live i0 is odd);
 //            tail              the entries in use (static LDS, ds_add).
@@ -390,10 +398,7 @@ __global__ __launch_bounds__(kBankBlock) void rcw_wall_rooms_kernel(const RcwDev
     const int a = blockIdx.x, lane = threadIdx.x;
     if (a >= p.B) return;
     const uint32_t ep = p.episode[a];
-    if (!force && b.last_episode[a] == ep) {
-        if (lane == 0) b.mask[a] = 0;
-        return;
-    }
+    if (no_restart(b, force, a, lane, ep)) return;
     const int H = p.H, W = p.W, nwords = p.nwords, HW = p.H * p.W, room = min(rm.room, kWallRoomsMaxTiles);   // (no side reaches it: the sums below stay in range)
     uint32_t* const words = lds_r;
     ushort4* const list = reinterpret_cast<ushort4*>(lds_r + ((nwords + 1) & ~1));   // (8-byte aligned)
@@ -503,64 +508,58 @@ hipError_t rcw_launch_wall_bank_pack(const RcwDev& p, const uint8_t* walls_dev, 
     return hipGetLastError();
 }
 
-hipError_t rcw_launch_wall_bank(const RcwPlan& p, const RcwWallBank& bank, bool force, hipStream_t s)
-{
-    if (p.B < 1 || bank.layouts < 1) return hipSuccess;
-    const size_t lds = (size_t)p.nwords * sizeof(uint32_t);                 // at most 16 KiB: the largest map rcw_create accepts has 4080 words
-    if (p.real64) hipLaunchKernelGGL(rcw_wall_bank_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, bank, force ? 1 : 0);
-    else          hipLaunchKernelGGL(rcw_wall_bank_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, bank, force ? 1 : 0);
-    return hipGetLastError();
-}
-
-// LDS: the words (rounded to an even count), 8 bytes a slot and 4 a label: at the 4096-cell bound 48 KiB + the map's words.  A square map has
-// the fewest (129 x 129: 1042, 4.1 KiB), a thin one the most: 2 x 2048 cells lie on 5 x 4097 (1282 words) and, with the last interior row
-// and column left wall, on 6 x 4098 — 1538 words, 6.0 KiB, the largest request: 55,304 bytes, under the 64 KiB default.
-hipError_t rcw_launch_wall_generator(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, bool force, hipStream_t s)
-{
-    const int cells = gen.ni * gen.nj;
-    if (p.B < 1 || cells < 1 || cells > kWallGenMaxCells) return cells > kWallGenMaxCells ? hipErrorInvalidValue : hipSuccess;
-    const size_t lds = (size_t)((p.nwords + 1) & ~1) * sizeof(uint32_t) + (size_t)cells * 12u;
-    if (p.real64) hipLaunchKernelGGL(rcw_wall_generator_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, force ? 1 : 0);
-    else          hipLaunchKernelGGL(rcw_wall_generator_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, force ? 1 : 0);
-    return hipGetLastError();
-}
-
-// LDS: the words (an even count), then per interior tile 4 bytes of label, 4 of counter and the two planes' bytes — or, where that is more,
-// the fallback's 12 bytes a cell (it never is: ni nj <= 4 n / 9).  At the 4096-tile bound: 66 x 66 has 274 words, 42,056 bytes; the largest
-// request is 5 x 1367's (4095 tiles, 428 words): 42,664 bytes, under the 64 KiB default.
-size_t rcw_wall_caves_lds_bytes(int H, int W, int nwords)
-{
-    const size_t n = (size_t)(H - 2) * (size_t)(W - 2), cells = (size_t)((H - 1) / 2) * (size_t)((W - 1) / 2);
-    const size_t cave = (n * 10u + 3u) & ~(size_t)3u, maze = cells * 12u;
-    return (size_t)((nwords + 1) & ~1) * sizeof(uint32_t) + (cave > maze ? cave : maze);
-}
-
-hipError_t rcw_launch_wall_caves(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, const RcwWallCaves& caves, bool force, hipStream_t s)
-{
-    const long long n = (long long)(p.H - 2) * (long long)(p.W - 2);
-    if (p.B < 1) return hipSuccess;
-    if (p.H < 5 || p.W < 5 || n > kWallCavesMaxTiles) return hipErrorInvalidValue;
-    const size_t lds = rcw_wall_caves_lds_bytes(p.H, p.W, p.nwords);
-    if (p.real64) hipLaunchKernelGGL(rcw_wall_caves_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, caves, force ? 1 : 0);
-    else          hipLaunchKernelGGL(rcw_wall_caves_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, caves, force ? 1 : 0);
-    return hipGetLastError();
-}
-
-// LDS: the words (an even count), then 8 bytes a chamber for Q entries.  At the 4096-room bound the list is 32 KiB: 130 x 130 (1057 words)
-// asks for 37,000 bytes, 5 x 4097 (1281 words) for 37,896, and the largest request is 6 x 4098's (1537 words): 38,920 bytes, under the
-// 64 KiB default.
-size_t rcw_wall_rooms_lds_bytes(int H, int W, int nwords)
-{
-    return (size_t)((nwords + 1) & ~1) * sizeof(uint32_t) + (size_t)rcw_wall_rooms_bound(H, W) * sizeof(ushort4);
-}
-
-hipError_t rcw_launch_wall_rooms(const RcwPlan& p, const RcwWallBank& agents, const RcwWallGen& gen, const RcwWallRooms& rooms, bool force, hipStream_t s)
+// THE launch point, and the only place that sizes the kernels' LDS.  Every request starts with the map's words, rounded to an even count
+// where something 8-byte aligned follows, and stays under the 64 KiB default:
+//   bank    the words alone: at most 16 KiB, the largest map rcw_create accepts has 4080 words.
+//   mazes   8 bytes a slot and 4 a label: at the 4096-cell bound 48 KiB + the words.  A square map has the fewest (129 x 129: 1042, 4.1 KiB), a
+//           thin one the most: 2 x 2048 cells lie on 5 x 4097 (1282 words) and, with the last interior row and column left wall, on
+//           6 x 4098 — 1538 words, 6.0 KiB, the largest request: 55,304 bytes.
+//   caves   per interior tile 4 bytes of label, 4 of counter and the two planes' bytes — or, where that is more, the fallback maze's 12 bytes
+//           a cell (it never is: ni nj <= 4 n / 9).  At the 4096-tile bound: 66 x 66 has 274 words, 42,056 bytes; the largest request is
+//           5 x 1367's (4095 tiles, 428 words): 42,664 bytes.
+//   rooms   8 bytes a chamber for Q entries.  At the 4096-room bound the list is 32 KiB: 130 x 130 (1057 words) asks for 37,000 bytes,
+//           5 x 4097 (1281 words) for 37,896, and the largest request is 6 x 4098's (1537 words): 38,920 bytes.
+hipError_t rcw_launch_layout_source(const RcwPlan& p, const RcwLayoutSource& src, bool force, hipStream_t s)
 {
     if (p.B < 1) return hipSuccess;
-    if (p.H < 5 || p.W < 5 || rooms.room < 1 || rcw_wall_rooms_bound(p.H, p.W) > kWallRoomsMaxRooms || (long long)p.H * (long long)p.W > kWallRoomsMaxTiles)
-        return hipErrorInvalidValue;
-    const size_t lds = rcw_wall_rooms_lds_bytes(p.H, p.W, p.nwords);
-    if (p.real64) hipLaunchKernelGGL(rcw_wall_rooms_kernel<double>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, rooms, force ? 1 : 0);
-    else          hipLaunchKernelGGL(rcw_wall_rooms_kernel<float>, dim3(p.B), dim3(kBankBlock), lds, s, p, p.limit, agents, gen, rooms, force ? 1 : 0);
+    const dim3 grid(p.B), block(kBankBlock);
+    const int f = force ? 1 : 0;
+    const size_t even_words = (size_t)((p.nwords + 1) & ~1) * sizeof(uint32_t);
+    switch (src.kind) {
+    case kLayoutNone:
+        return hipSuccess;
+    case kLayoutBank: {
+        if (src.agents.layouts < 1) return hipSuccess;
+        const size_t lds = (size_t)p.nwords * sizeof(uint32_t);
+        if (p.real64) hipLaunchKernelGGL(rcw_wall_bank_kernel<double>, grid, block, lds, s, p, p.limit, src.agents, f);
+        else          hipLaunchKernelGGL(rcw_wall_bank_kernel<float>, grid, block, lds, s, p, p.limit, src.agents, f);
+        break;
+    }
+    case kLayoutMazes: {
+        const int cells = src.gen.ni * src.gen.nj;
+        if (cells < 1 || cells > kWallGenMaxCells) return cells > kWallGenMaxCells ? hipErrorInvalidValue : hipSuccess;
+        const size_t lds = even_words + (size_t)cells * 12u;
+        if (p.real64) hipLaunchKernelGGL(rcw_wall_generator_kernel<double>, grid, block, lds, s, p, p.limit, src.agents, src.gen, f);
+        else          hipLaunchKernelGGL(rcw_wall_generator_kernel<float>, grid, block, lds, s, p, p.limit, src.agents, src.gen, f);
+        break;
+    }
+    case kLayoutCaves: {
+        const long long n = (long long)(p.H - 2) * (long long)(p.W - 2);
+        if (p.H < 5 || p.W < 5 || n > kWallCavesMaxTiles) return hipErrorInvalidValue;
+        const size_t cave = ((size_t)n * 10u + 3u) & ~(size_t)3u, maze = (size_t)((p.H - 1) / 2) * (size_t)((p.W - 1) / 2) * 12u;
+        const size_t lds = even_words + (cave > maze ? cave : maze);
+        if (p.real64) hipLaunchKernelGGL(rcw_wall_caves_kernel<double>, grid, block, lds, s, p, p.limit, src.agents, src.gen, src.caves, f);
+        else          hipLaunchKernelGGL(rcw_wall_caves_kernel<float>, grid, block, lds, s, p, p.limit, src.agents, src.gen, src.caves, f);
+        break;
+    }
+    case kLayoutRooms: {
+        if (p.H < 5 || p.W < 5 || src.rooms.room < 1 || rcw_wall_rooms_bound(p.H, p.W) > kWallRoomsMaxRooms || (long long)p.H * (long long)p.W > kWallRoomsMaxTiles)
+            return hipErrorInvalidValue;
+        const size_t lds = even_words + (size_t)rcw_wall_rooms_bound(p.H, p.W) * sizeof(ushort4);
+        if (p.real64) hipLaunchKernelGGL(rcw_wall_rooms_kernel<double>, grid, block, lds, s, p, p.limit, src.agents, src.gen, src.rooms, f);
+        else          hipLaunchKernelGGL(rcw_wall_rooms_kernel<float>, grid, block, lds, s, p, p.limit, src.agents, src.gen, src.rooms, f);
+        break;
+    }
+    }
     return hipGetLastError();
 }

@@ -97,14 +97,8 @@ class ShardedSingleRoom:
         # for all, which every rank advances through all global agents' draws (in the same initial state on every rank) —
         # so that the states do not depend on the sharding, as with the device generator (agent_id_offset)
         self.rng = kwargs.pop("rng", None)
-        if self.rng is not None and kwargs.get("wall_bank") is not None:
-            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall bank")
-        if self.rng is not None and kwargs.get("wall_generator") is not None:
-            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall generator")
-        if self.rng is not None and kwargs.get("wall_caves") is not None:
-            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall caves")
-        if self.rng is not None and kwargs.get("wall_rooms") is not None:
-            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall rooms")
+        for source in ("wall_bank", "wall_generator", "wall_caves", "wall_rooms"):
+            self._refuse_rng(source.replace("_", " "), kwargs.get(source))
         self.env = env_factory(batch=self.count, agent_id_offset=self.first,
                                device=default_device() if device is None else device, **kwargs)
         self._abi_comm = False
@@ -112,6 +106,11 @@ class ShardedSingleRoom:
             from .single_room import _reset_from_rng
 
             _reset_from_rng(self.env, self.rng, None, construction=True, first=self.first, global_batch=self.global_batch)
+
+    def _refuse_rng(self, what: str, asked) -> None:
+        """(a layout source drawn on the device, asked of a batch whose resets are drawn on the host; asked = None switches one off)"""
+        if self.rng is not None and asked is not None:
+            raise ValueError(f"a batch built with rng draws its resets on the host: it takes no {what}")
 
     @property
     def _dist(self):
@@ -187,29 +186,25 @@ class ShardedSingleRoom:
         """`SingleRoom.set_wall_bank` for the sharded batch: the bank and its weights are REPLICATED — every rank passes the same
         arguments — and nothing else is needed: the layout an agent draws is keyed by its global id (`agent_id_offset`), so a shard
         equals its slice of the whole batch."""
-        if self.rng is not None and walls is not None:
-            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall bank")
+        self._refuse_rng("wall bank", walls)
         self.env.set_wall_bank(walls, weights)
 
     def set_wall_generator(self, loops=0.0, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
         """`SingleRoom.set_wall_generator` for the sharded batch: the parameters are REPLICATED — every rank passes the same — and
         nothing else is needed: the maze an agent's episode gets is keyed by its global id (`agent_id_offset`)."""
-        if self.rng is not None and loops is not None:
-            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall generator")
+        self._refuse_rng("wall generator", loops)
         self.env.set_wall_generator(loops, levels, first_level, level_seed)
 
     def set_wall_caves(self, fill=0.40, smooth: int = 2, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
         """`SingleRoom.set_wall_caves` for the sharded batch: the parameters are REPLICATED — every rank passes the same — and
         nothing else is needed: the cave an agent's episode gets is keyed by its global id (`agent_id_offset`)."""
-        if self.rng is not None and fill is not None:
-            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall caves")
+        self._refuse_rng("wall caves", fill)
         self.env.set_wall_caves(fill, smooth, levels, first_level, level_seed)
 
     def set_wall_rooms(self, room=2, stop=0.25, doors=0.25, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
         """`SingleRoom.set_wall_rooms` for the sharded batch: the parameters are REPLICATED — every rank passes the same — and
         nothing else is needed: the rooms an agent's episode gets are keyed by its global id (`agent_id_offset`)."""
-        if self.rng is not None and room is not None:
-            raise ValueError("a batch built with rng draws its resets on the host: it takes no wall rooms")
+        self._refuse_rng("wall rooms", room)
         self.env.set_wall_rooms(room, stop, doors, levels, first_level, level_seed)
 
     def set_wall_bank_weights(self, weights) -> None:

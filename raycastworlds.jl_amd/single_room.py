@@ -1093,6 +1093,20 @@ class SingleRoom:
             self._rng_walls[touched] = w[took[touched]]
             _reset_from_rng(self, self.rng, m)
 
+    # ---- what the setters of the layout sources (bank, generator, caves, rooms) check alike ----
+    def _refuse_rng(self, what: str) -> None:
+        if self.rng is not None:
+            raise ValueError(f"an environment built with rng draws its resets on the host: it takes no {what}")
+
+    @staticmethod
+    def _check_family_integers(own: Optional[str] = None, **values) -> None:
+        """The integer arguments of a generator family, in the caller's order: `level_seed` a UInt64, the others 0 .. 2^31 - 1 — but for
+        `own`, the family's own Int32, whose negative values go on to the library's refusal."""
+        for name, v in values.items():
+            top = 2 ** 64 - 1 if name == "level_seed" else 2 ** 31 - 1
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not (-2 ** 31 if name == own else 0) <= int(v) <= top:
+                raise ValueError(f"{name} must be an integer in 0 .. {top}, got {v!r}")
+
     # ---- the wall bank (include/rcw.h, rcw_set_wall_bank) -------------------------------
     def set_wall_bank(self, walls, weights=None) -> None:
         """A bank of wall layouts on the device, one drawn for an agent at every start of an episode — `reset_`, a done or truncated
@@ -1107,8 +1121,7 @@ class SingleRoom:
             self.__dict__.pop("_wall_layout_dev", None)
             self._check(self._lib.rcw_set_wall_bank(self._h, None, 0, None))
             return
-        if self.rng is not None:
-            raise ValueError("an environment built with rng draws its resets on the host: it takes no wall bank")
+        self._refuse_rng("wall bank")
         H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
         w = np.asarray(walls)
         if w.ndim == 2:
@@ -1158,14 +1171,11 @@ class SingleRoom:
         if loops is None:
             self._check(self._lib.rcw_set_wall_generator(self._h, 0, 0, 0, 0, 0))
             return
-        if self.rng is not None:
-            raise ValueError("an environment built with rng draws its resets on the host: it takes no wall generator")
+        self._refuse_rng("wall generator")
         from . import layouts as _layouts
 
         word = _layouts.loops_word(loops)
-        for name, v, top in (("levels", levels, 2 ** 31 - 1), ("first_level", first_level, 2 ** 31 - 1), ("level_seed", level_seed, 2 ** 64 - 1)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= top:
-                raise ValueError(f"{name} must be an integer in 0 .. {top}, got {v!r}")
+        self._check_family_integers(levels=levels, first_level=first_level, level_seed=level_seed)
         self._check(self._lib.rcw_set_wall_generator(self._h, 1, word, int(levels), int(first_level), int(level_seed)))
 
     @property
@@ -1192,15 +1202,11 @@ class SingleRoom:
         if fill is None:
             self._check(self._lib.rcw_set_wall_caves(self._h, 0, 0, 0, 0, 0, 0))
             return
-        if self.rng is not None:
-            raise ValueError("an environment built with rng draws its resets on the host: it takes no wall caves")
+        self._refuse_rng("wall caves")
         from . import layouts as _layouts
 
         word = _layouts.loops_word(fill)
-        for name, v, top in (("smooth", smooth, 2 ** 31 - 1), ("levels", levels, 2 ** 31 - 1), ("first_level", first_level, 2 ** 31 - 1),
-                             ("level_seed", level_seed, 2 ** 64 - 1)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not (-2 ** 31 if name == "smooth" else 0) <= int(v) <= top:
-                raise ValueError(f"{name} must be an integer in 0 .. {top}, got {v!r}")
+        self._check_family_integers("smooth", smooth=smooth, levels=levels, first_level=first_level, level_seed=level_seed)
         self._check(self._lib.rcw_set_wall_caves(self._h, 1, word, int(smooth), int(levels), int(first_level), int(level_seed)))
 
     @property
@@ -1227,15 +1233,11 @@ class SingleRoom:
         if room is None:
             self._check(self._lib.rcw_set_wall_rooms(self._h, 0, 0, 0, 0, 0, 0, 0))
             return
-        if self.rng is not None:
-            raise ValueError("an environment built with rng draws its resets on the host: it takes no wall rooms")
+        self._refuse_rng("wall rooms")
         from . import layouts as _layouts
 
         stop_word, doors_word = _layouts.loops_word(stop), _layouts.loops_word(doors)
-        for name, v, top in (("room", room, 2 ** 31 - 1), ("levels", levels, 2 ** 31 - 1), ("first_level", first_level, 2 ** 31 - 1),
-                             ("level_seed", level_seed, 2 ** 64 - 1)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not (-2 ** 31 if name == "room" else 0) <= int(v) <= top:
-                raise ValueError(f"{name} must be an integer in 0 .. {top}, got {v!r}")
+        self._check_family_integers("room", room=room, levels=levels, first_level=first_level, level_seed=level_seed)
         self._check(self._lib.rcw_set_wall_rooms(self._h, 1, int(room), stop_word, doors_word, int(levels), int(first_level), int(level_seed)))
 
     @property
