@@ -192,20 +192,22 @@ class ShardedSingleRoom:
     def set_wall_generator(self, loops=0.0, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
         """`SingleRoom.set_wall_generator` for the sharded batch: the parameters are REPLICATED — every rank passes the same — and
         nothing else is needed: the maze an agent's episode gets is keyed by its global id (`agent_id_offset`)."""
-        self._refuse_rng("wall generator", loops)
-        self.env.set_wall_generator(loops, levels, first_level, level_seed)
+        self._forward_family("wall generator", self.env.set_wall_generator, loops, levels, first_level, level_seed)
 
     def set_wall_caves(self, fill=0.40, smooth: int = 2, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
         """`SingleRoom.set_wall_caves` for the sharded batch: the parameters are REPLICATED — every rank passes the same — and
         nothing else is needed: the cave an agent's episode gets is keyed by its global id (`agent_id_offset`)."""
-        self._refuse_rng("wall caves", fill)
-        self.env.set_wall_caves(fill, smooth, levels, first_level, level_seed)
+        self._forward_family("wall caves", self.env.set_wall_caves, fill, smooth, levels, first_level, level_seed)
 
     def set_wall_rooms(self, room=2, stop=0.25, doors=0.25, levels: int = 0, first_level: int = 0, level_seed: int = 0) -> None:
         """`SingleRoom.set_wall_rooms` for the sharded batch: the parameters are REPLICATED — every rank passes the same — and
         nothing else is needed: the rooms an agent's episode gets are keyed by its global id (`agent_id_offset`)."""
-        self._refuse_rng("wall rooms", room)
-        self.env.set_wall_rooms(room, stop, doors, levels, first_level, level_seed)
+        self._forward_family("wall rooms", self.env.set_wall_rooms, room, stop, doors, levels, first_level, level_seed)
+
+    def _forward_family(self, what: str, setter, *args) -> None:
+        """a family's replicated parameters on to the shard's environment; the first one None switches the family off"""
+        self._refuse_rng(what, args[0])
+        setter(*args)
 
     def set_wall_bank_weights(self, weights) -> None:
         """`SingleRoom.set_wall_bank_weights`, the same weights on every rank."""

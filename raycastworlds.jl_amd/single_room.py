@@ -494,24 +494,13 @@ class SingleRoom:
         elif wall_bank_weights is not None:
             self._handle.close()
             raise ValueError("wall_bank_weights needs wall_bank")
-        if wall_generator is not None:
-            try:
-                self.set_wall_generator(**dict(wall_generator))
-            except BaseException:
-                self._handle.close()
-                raise
-        if wall_caves is not None:
-            try:
-                self.set_wall_caves(**dict(wall_caves))
-            except BaseException:
-                self._handle.close()
-                raise
-        if wall_rooms is not None:
-            try:
-                self.set_wall_rooms(**dict(wall_rooms))
-            except BaseException:
-                self._handle.close()
-                raise
+        for setter, keywords in ((self.set_wall_generator, wall_generator), (self.set_wall_caves, wall_caves), (self.set_wall_rooms, wall_rooms)):
+            if keywords is not None:
+                try:
+                    setter(**dict(keywords))
+                except BaseException:
+                    self._handle.close()
+                    raise
         if goal_distance:
             try:
                 self.set_goal_distance(True)
@@ -1107,6 +1096,22 @@ class SingleRoom:
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not (-2 ** 31 if name == own else 0) <= int(v) <= top:
                 raise ValueError(f"{name} must be an integer in 0 .. {top}, got {v!r}")
 
+    def _set_wall_family(self, what: str, call, params, own: Optional[str], levels, first_level, level_seed) -> None:
+        """What the setters of the generator's families share.  `call` is the family's export; `params` its own parameters in the
+        export's order as (name, value, is a probability); `own` is `_check_family_integers`'.  The first value None: the family off."""
+        self.__dict__.pop("_wall_layout_dev", None)
+        if params[0][1] is None:
+            self._check(call(self._h, 0, *[0] * (len(params) + 3)))
+            return
+        self._refuse_rng(what)
+        from . import layouts as _layouts
+
+        words = {name: _layouts.loops_word(v) for name, v, probability in params if probability}
+        self._check_family_integers(own, **{name: v for name, v, probability in params if not probability},
+                                    levels=levels, first_level=first_level, level_seed=level_seed)
+        self._check(call(self._h, 1, *[words[name] if probability else int(v) for name, v, probability in params],
+                         int(levels), int(first_level), int(level_seed)))
+
     # ---- the wall bank (include/rcw.h, rcw_set_wall_bank) -------------------------------
     def set_wall_bank(self, walls, weights=None) -> None:
         """A bank of wall layouts on the device, one drawn for an agent at every start of an episode — `reset_`, a done or truncated
@@ -1167,16 +1172,7 @@ class SingleRoom:
         replays any of them on the host.  Maps of 5 x 5 to 129 x 129 (4096 cells).  `set_walls` and `set_wall_bank` are refused while
         the generator is on; `set_wall_generator(None)` switches it off, the agents keep their walls.  An environment built with
         `rng` draws its resets on the host and takes no generator."""
-        self.__dict__.pop("_wall_layout_dev", None)
-        if loops is None:
-            self._check(self._lib.rcw_set_wall_generator(self._h, 0, 0, 0, 0, 0))
-            return
-        self._refuse_rng("wall generator")
-        from . import layouts as _layouts
-
-        word = _layouts.loops_word(loops)
-        self._check_family_integers(levels=levels, first_level=first_level, level_seed=level_seed)
-        self._check(self._lib.rcw_set_wall_generator(self._h, 1, word, int(levels), int(first_level), int(level_seed)))
+        self._set_wall_family("wall generator", self._lib.rcw_set_wall_generator, (("loops", loops, True),), None, levels, first_level, level_seed)
 
     @property
     def wall_generator_info(self) -> dict:
@@ -1198,16 +1194,8 @@ class SingleRoom:
         `set_wall_generator` are refused while caves are on, and caves while a bank or the generator is; `set_wall_caves(None)`
         switches them off, the agents keep their walls.  An environment built with `rng` draws its resets on the host and takes
         no caves."""
-        self.__dict__.pop("_wall_layout_dev", None)
-        if fill is None:
-            self._check(self._lib.rcw_set_wall_caves(self._h, 0, 0, 0, 0, 0, 0))
-            return
-        self._refuse_rng("wall caves")
-        from . import layouts as _layouts
-
-        word = _layouts.loops_word(fill)
-        self._check_family_integers("smooth", smooth=smooth, levels=levels, first_level=first_level, level_seed=level_seed)
-        self._check(self._lib.rcw_set_wall_caves(self._h, 1, word, int(smooth), int(levels), int(first_level), int(level_seed)))
+        self._set_wall_family("wall caves", self._lib.rcw_set_wall_caves, (("fill", fill, True), ("smooth", smooth, False)), "smooth",
+                              levels, first_level, level_seed)
 
     @property
     def wall_caves_info(self) -> dict:
@@ -1229,16 +1217,8 @@ class SingleRoom:
         of 5 x 5 up to ceil((H-2)/2) ceil((W-2)/2) = 4096 (130 x 130, 5 x 4097).  `set_walls`, `set_wall_bank`, `set_wall_generator`
         and `set_wall_caves` are refused while rooms are on, and rooms while any of them is; `set_wall_rooms(None)` switches them
         off, the agents keep their walls.  An environment built with `rng` draws its resets on the host and takes no rooms."""
-        self.__dict__.pop("_wall_layout_dev", None)
-        if room is None:
-            self._check(self._lib.rcw_set_wall_rooms(self._h, 0, 0, 0, 0, 0, 0, 0))
-            return
-        self._refuse_rng("wall rooms")
-        from . import layouts as _layouts
-
-        stop_word, doors_word = _layouts.loops_word(stop), _layouts.loops_word(doors)
-        self._check_family_integers("room", room=room, levels=levels, first_level=first_level, level_seed=level_seed)
-        self._check(self._lib.rcw_set_wall_rooms(self._h, 1, int(room), stop_word, doors_word, int(levels), int(first_level), int(level_seed)))
+        self._set_wall_family("wall rooms", self._lib.rcw_set_wall_rooms, (("room", room, False), ("stop", stop, True), ("doors", doors, True)), "room",
+                              levels, first_level, level_seed)
 
     @property
     def wall_rooms_info(self) -> dict:

@@ -1,38 +1,24 @@
-"""The wall generator on the GPU (include/rcw.h, rcw_set_wall_generator): the scenarios of tests/wall_generator_cases.py played on an engine
-against tests/wall_generator_ref.py — after EVERY call the whole state of walls_ref.assert_equal (status, episode, goal, pose, reward, done,
-tile-map chunks, column descriptors, camera view), wall_layout, and the time limit's two words; and the bank tests' feature trackers beside
-them: the goal distance's words and fields (which never read -1: every maze is connected) in every rollout, the seen map, the local map
-from the seen map and the 4-frame stack in the `features` scenario.  tests/test_wall_generator_spec.py rehearses every scenario on the CPU
-and asserts from the reference's counts that it reaches restarts of both kinds and goal redraws.
+"""The wall generator on the GPU (include/rcw.h, rcw_set_wall_generator): what exists because of the MAZE kernel.  What the generator shares
+with the caves and the rooms is written once in tests/test_gpu_wall_families.py: the host replay, the graph, the shards, the fuzzer and
+more run there, a case a family; the scenarios of tests/wall_generator_cases.py after every call (at the size bound too: `edge`, `thin`,
+`tall`, ...), the features and the maps the generator does not take are its bodies, run HERE under the generator's own cases.
 
-AT THE SIZE BOUND (4096 cells: 64 cells a lane, 48 KiB of slots and labels beside the words): the `huge` script at 129 x 129, 130 x 130,
-5 x 4097, 4097 x 5 and 6 x 4098 — all recorded WITH frames, the reference takes a second or two each; 129 x 129 in both step forms, the
-one-launch step with 64 camera rows (`edge_rows64`: it does not take the 24 of the others) —; the hardest mazes a search with
-the model of the kernel's rounds finds (wall_generator_ref.boruvka), installed through levels=1; and 1031 agents, more workgroups than the
-device holds at once.
-
-The `small` scenario is the issue's own (67 agents x 320 rays, 30 steps): its reference takes some ten seconds of Python ray casting, once,
-shared by the two step forms.  Every export is missing from the build before this feature: each test here fails there.
+Here: the hardest mazes a search with the model of the kernel's rounds finds (wall_generator_ref.boruvka), installed through levels=1, at
+the size bound of 4096 cells (64 cells a lane, 48 KiB of slots and labels beside the words) and below it; 1031 agents, more workgroups than
+the device holds at once; which calls the generator refuses and which refuse it; and NeverLost, the tracker every family's tests hold
+beside the goal distance.
 """
 import ctypes as C
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-import learner_view_ref as LV
-import local_map_ref as LM
-import time_limit_ref as TL
+import test_gpu_wall_families as shared
 import wall_generator_cases as GC
 import wall_generator_ref as WG
-import walls_ref as WR
-from test_gpu_wall_bank import GoalTracker, LocalTracker, SeenTracker, StackTracker
+from wall_family import engine_state, infos, level_key, unchanged
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class NeverLost:
@@ -54,42 +40,21 @@ class NeverLost:
         self._check(where)
 
 
-# ---- the rollouts -----------------------------------------------------------------------------------------------------------------
-ROLLOUTS = [("small", "two-launches"), ("small", "one-launch"), ("square", None), ("big", "two-launches"), ("big", "one-launch"), ("wide", None),
-            ("huge", None), ("f64", None), ("levels", None), ("calls", "two-launches"), ("calls", "one-launch"),
-            ("edge", "two-launches"), ("edge_rows64", "one-launch"), ("edge_even", None), ("thin", None), ("tall", None), ("thin_even", None)]
-
-
-@pytest.mark.parametrize("name,form", ROLLOUTS, ids=[f"{n}-{f or 'auto'}" for n, f in ROLLOUTS])
+# ---- what every family has, under this family's own cases: the bodies are tests/test_gpu_wall_families.py's --------------------------------
+@pytest.mark.parametrize("name,form", GC.ROLLOUTS, ids=shared.rollout_ids(GC.ROLLOUTS))
 def test_a_scenario_against_the_reference_after_every_call(rcw, name, form):
-    c = GC.SCENARIOS[name][1]
-    env = GC.make_env(rcw, c, form)
-    trackers = [] if name == "calls" else [GoalTracker(rcw, env), NeverLost(env)]   # (`calls` switches the generator off and sets walls by hand)
-    events = GC.play(rcw, name, env, trackers)
-    assert events["episode_starts"] > env.batch and events["restarts_after_done"] > 0 and events["restarts_after_truncation"] > 0
-    if trackers:
-        assert trackers[1].checked > 5
-    if form is not None:
-        assert env.step_form() == form
-    if name == "f64":
-        assert env.world.player_position_wu.dtype == np.float64
-    if name == "big":
-        assert env.world.tile_map_chunks.shape[1] * 2 > 64                    # more tile-map words than a wavefront has lanes
-    if name == "huge":
-        assert WG.grid(c["H"], c["W"])[2] == 1024
-    if name in GC.AT_THE_BOUND:
-        assert WG.grid(c["H"], c["W"])[2] == 4096 == WG.MAX_CELLS            # the bound itself, not 4095
-        assert env.world.tile_map_chunks.shape[1] * 2 == GC.WORDS[name]       # (a chunk is two words)
-    if name == "levels":
-        layout, walls = env.wall_layout.numpy(), env.world.walls
-        assert set(layout.tolist()) == {40, 41, 42} and min(np.bincount(layout - 40)) > 5
-        for level in (40, 41, 42):                                            # every level held by several agents, one maze a level
-            held = walls[layout == level]
-            assert (held == held[0]).all()
-            np.testing.assert_array_equal(held[0], rcw.layouts.generated_maze(rcw.layouts.generated_maze_key(0, 0, 0, 1, level, 9)[0], c["H"], c["W"]))
-    else:
-        assert (env.wall_layout.numpy() == -1).all()
-    env.close()
+    shared.a_scenario_against_the_reference_after_every_call(rcw, "generator", name, form)
+
+
+@pytest.mark.parametrize("form", shared.FORMS)
+@pytest.mark.parametrize("feature", shared.FEATURES)
+def test_the_features_follow_the_new_maze_in_one_pass(rcw, feature, form):
+    shared.the_features_follow_the_new_layout_in_one_pass(rcw, "generator", feature, form)
+
+
+@pytest.mark.parametrize("H,W,exc,message", GC.REFUSED_MAPS)
+def test_a_map_the_generator_does_not_take(rcw, H, W, exc, message):
+    shared.a_map_the_family_does_not_take(rcw, "generator", H, W, exc, message)
 
 
 # ---- mazes chosen for the rounds they take ------------------------------------------------------------------------------------------------
@@ -111,7 +76,7 @@ def test_the_maze_that_takes_the_most_rounds(rcw, H, W, T):
     never from the engine.  Three agents, a perfect maze and loops 0.25: the walls byte for byte against the Python reference and the
     host export, after the install and after a step that restarts everybody under limit 1."""
     L, level = rcw.layouts, GC.HARD_LEVELS[(H, W)]
-    m = WR.episode_key(GC.HARD_LEVEL_SEED, level, 0)
+    m = level_key(GC.HARD_LEVEL_SEED, level)
     tree, rounds, chain = WG.boruvka(m, H, W)
     assert tree == sorted(WG.tree_edges(m, H, W))
     assert rounds >= {(129, 129): 7, (5, 4097): 8, (4097, 5): 8, (33, 33): 5}[(H, W)] == GC.HARD_ROUNDS[(H, W)] and chain >= 6
@@ -189,113 +154,7 @@ def test_1031_mazes_of_4096_cells_and_a_masked_reset_beside_them(rcw):
     env.close()
 
 
-FEATURES = ["goal_distance", "seen_map", "local_seen", "stack", "everything"]
-
-
-@pytest.mark.parametrize("form", ["two-launches", "one-launch"])
-@pytest.mark.parametrize("feature", FEATURES)
-def test_the_features_follow_the_new_maze_in_one_pass(rcw, feature, form):
-    """each feature beside the generator (and all of them at once): the camera view against the reference, the feature against its own
-    reference fed with the engine's state, after every call of the `features` scenario"""
-    env = GC.make_env(rcw, GC.CALLS, form)
-    trackers = []
-    if feature in ("goal_distance", "everything"):
-        trackers += [GoalTracker(rcw, env), NeverLost(env)]
-    if feature in ("seen_map", "local_seen", "everything"):
-        trackers.append(SeenTracker(rcw, env))
-    if feature in ("local_seen", "everything"):
-        trackers.append(LocalTracker(rcw, env, 9, 2, LM.SEEN))
-    if feature in ("stack", "everything"):
-        trackers.append(StackTracker(env, 4, "gray", (21, 21)))
-    events = GC.play(rcw, "features", env, trackers)
-    assert events["restarts_after_done"] > 0 and events["restarts_after_truncation"] > 0 and events["goal_redraws"] > 0
-    assert env.step_form() == form
-    env.close()
-
-
-def test_the_host_replay_equals_every_agents_walls(rcw):
-    """layouts.generated_maze(generated_maze_key(...)) equals env.world.walls[a] for every agent — a shard with an agent_id_offset — after
-    the install and after restarts, without levels and with them"""
-    L = rcw.layouts
-    c = dict(GC.LEVELS, B=21, H=9, W=11)
-    for gen in (dict(loops=0.25), dict(loops=0.25, levels=5, first_level=3, level_seed=8)):
-        env = GC.make_env(rcw, c, agent_id_offset=1000, max_episode_steps=3, wall_generator=gen)
-        info = env.wall_generator_info
-        assert info == dict(enabled=True, loops=1 << 30, levels=gen.get("levels", 0), first_level=gen.get("first_level", 0), level_seed=gen.get("level_seed", 0))
-        rng = np.random.default_rng(4)
-        first = env.world.episode.copy()
-        for t in range(8):
-            walls, episode, layout = env.world.walls, env.world.episode, env.wall_layout.numpy()
-            for a in range(c["B"]):
-                key, level = L.generated_maze_key(c["seed"], 1000 + a, int(episode[a]) - 1, info["levels"], info["first_level"], info["level_seed"])
-                assert level == layout[a]
-                np.testing.assert_array_equal(walls[a], L.generated_maze(key, c["H"], c["W"], 0.25), err_msg=f"agent {a}, step {t}")
-                assert L.is_connected(walls[a])
-            rcw.act_(env, WR.draw_actions(rng, c["B"]))
-        assert (env.world.episode >= first + 2).all()                        # limit 3: everybody restarted at least twice
-        env.close()
-
-
-def test_view_only_and_the_top_view_beside_a_plain_generator_handle(rcw):
-    """RCW_VIEW_ONLY (the step paints no camera view: the generator's kernel sits between the cast and the view kernel) and a handle with a
-    top view, each stepped beside a plain handle with the same generator: the state equal after every call, the learner view the reference's
-    of the plain handle's descriptors, the top view the reference worlds'"""
-    c, pu = dict(GC.CALLS, B=6), 8
-    plain = GC.make_env(rcw, c)
-    only = GC.make_env(rcw, c)
-    top = GC.make_env(rcw, c, render_top_view=True, pu_per_tu=pu)
-    ref = GC.make_ref(c)
-    only.set_learner_view("rgb", (16, 16), "chw", camera_view=False)
-    for e in (plain, only, top):
-        e.set_wall_generator(0.5)
-        e.set_time_limit(4)
-    ref.set_wall_generator(0.5)
-
-    def compare(where):
-        for k in ("episode", "goal_position", "player_position_wu", "player_direction_au", "done", "tile_map_chunks", "episode_steps", "truncated"):
-            for e, who in ((only, "view only"), (top, "top view")):
-                np.testing.assert_array_equal(getattr(e.world, k), getattr(plain.world, k), err_msg=f"{k} of the {who} handle, {where}")
-        h, cc = plain.columns()
-        np.testing.assert_array_equal(only.learner_view_host(), LV.from_descriptors(h, cc, plain.cfg, c["Hc"], "rgb", (16, 16)), err_msg=f"view {where}")
-        np.testing.assert_array_equal(top.camera_view_host(), plain.camera_view_host(), err_msg=f"camera view {where}")
-
-    lim = TL.TimeLimitRef(ref, 4, c["seed"], True)
-    compare("behind set_wall_generator")
-    np.testing.assert_array_equal(top.top_view_host(), ref.top_view(pu), err_msg="top view behind set_wall_generator")
-    rng = np.random.default_rng(6)
-    for t in range(14):
-        a = WR.draw_actions(rng, c["B"])
-        for e in (plain, only, top):
-            rcw.act_(e, a)
-        lim.step(a)
-        compare(f"step {t}")
-        np.testing.assert_array_equal(top.top_view_host(), ref.top_view(pu), err_msg=f"top view, step {t}")
-    WG.assert_equal(plain, ref, "the plain handle behind the rollout")
-    assert ref.events["episode_starts"] > c["B"] and lim.events["restarts_after_truncation"] > 0    # (the install is B of them)
-    for e in (plain, only, top):
-        e.close()
-
-
 # ---- the call rules and hostile arguments ------------------------------------------------------------------------------------------------
-def engine_state(env):
-    w = env.world
-    h, c = env.columns()
-    s = dict(frame=env.camera_view_host(), col_h=h, col_c=c, tile_map=w.tile_map_chunks, goal=w.goal_position, position=w.player_position_wu,
-             heading=w.player_direction_au, reward=w.reward, done=w.done, episode=w.episode, status=w.status, episode_steps=w.episode_steps,
-             truncated=w.truncated)
-    if env.wall_generator_info["enabled"] or env.wall_bank_info["layouts"]:
-        s["wall_layout"] = env.wall_layout.numpy()
-    return s
-
-
-def unchanged(env, before, info, what):
-    after = engine_state(env)
-    assert set(after) == set(before), what
-    for k in before:
-        np.testing.assert_array_equal(after[k], before[k], err_msg=f"{k} behind {what}")
-    assert (env.wall_generator_info, env.wall_bank_info) == info, what
-
-
 def test_refusals_leave_the_handle_byte_identical(rcw):
     from raycastworlds_jl_amd import _capi
 
@@ -313,7 +172,7 @@ def test_refusals_leave_the_handle_byte_identical(rcw):
     bank = np.stack([rcw.layouts.ring(6, 6), rcw.layouts.four_rooms(6, 6)])
 
     def refused(call, exc, message, code=None):
-        before, info = engine_state(env), (env.wall_generator_info, env.wall_bank_info)
+        before, info = engine_state(env), infos(env)
         with pytest.raises(exc, match=message) as ei:
             call()
         if code is not None:
@@ -356,134 +215,3 @@ def test_refusals_leave_the_handle_byte_identical(rcw):
         GC.make_env(rcw, dict(c, B=2), rng=np.random.default_rng(0), wall_generator={})
     with pytest.raises(ValueError, match="rng"):
         rcw.ShardedSingleRoom(4, rank=0, world=2, device=0, rng=np.random.default_rng(0), wall_generator={})
-
-
-@pytest.mark.parametrize("H,W,exc,message", [(4, 9, ValueError, "at least 5 x 5"), (9, 4, ValueError, "at least 5 x 5"),
-                                             (131, 129, "unsupported", "at most 4096 cells")])
-def test_a_map_the_generator_does_not_take(rcw, H, W, exc, message):
-    """4 x 9 and 9 x 4: invalid; 131 x 129 (65 x 64 = 4160 cells): unsupported, the message names the bound; the handle stays as it was"""
-    from raycastworlds_jl_amd import _capi
-
-    assert WG.install_refusal(H, W, 0, 0) == ("invalid" if exc is ValueError else "unsupported")
-    env = GC.make_env(rcw, dict(H=H, W=W, N=8, Hc=16, B=2, seed=1))
-    before, info = engine_state(env), (env.wall_generator_info, env.wall_bank_info)
-    with pytest.raises(ValueError if exc is ValueError else _capi.RcwError, match=message) as ei:
-        env.set_wall_generator()
-    if exc == "unsupported":
-        assert ei.value.code == _capi.RCW_ERR_UNSUPPORTED and "129 x 129" in ei.value.message
-    unchanged(env, before, info, message)
-    rcw.act_(env, np.ones(2, np.uint8))                                      # ... and still steps
-    env.close()
-
-
-def test_calls_that_do_nothing_to_the_generator(rcw):
-    """set_direction_table, set_time_limit, set_step_form, the feature switches and the getters: mazes, counters and levels stay"""
-    c = GC.CALLS
-    env = GC.make_env(rcw, c, wall_generator=dict(levels=3, first_level=1, level_seed=2))
-    keep = lambda: (env.wall_layout.numpy().copy(), env.world.episode.copy(), env.world.tile_map_chunks.copy())
-    before = keep()
-    t = env.wall_layout.torch(sync=False)
-    assert t.dtype.is_floating_point is False and tuple(t.shape) == (c["B"],)
-    env.sync()
-    np.testing.assert_array_equal(t.cpu().numpy(), before[0])
-    for call in (lambda: env.set_direction_table(env.world.directions_wu[::-1].copy()), lambda: env.set_time_limit(7), lambda: env.set_step_form("one-launch"),
-                 lambda: env.set_step_form("two-launches"), lambda: env.set_goal_distance(True), lambda: env.set_seen_map(True),
-                 lambda: env.set_local_map(5), lambda: env.set_learner_view("gray", (8, 8)), lambda: env.clear_error(), lambda: rcw.cast_rays_(env),
-                 lambda: rcw.update_camera_view_(env)):
-        call()
-        for got, want in zip(keep(), before):
-            np.testing.assert_array_equal(got, want)
-    rcw.reset_(env)
-    assert (env.world.episode == before[1] + 1).all() and set(env.wall_layout.numpy().tolist()) <= {1, 2, 3}
-    env.close()
-
-
-# ---- the graph, the shards, the fuzzer ---------------------------------------------------------------------------------------------------
-def test_a_captured_step_replayed_12_times_under_limit_3(rcw):
-    torch = pytest.importorskip("torch")
-    c = dict(GC.CALLS, B=12, H=7, W=9)
-    gen = dict(loops=0.25, levels=0)
-    env = GC.make_env(rcw, c, wall_generator=gen, max_episode_steps=3, goal_distance=True)
-    ref = GC.make_ref(c)
-    ref.set_wall_generator(**gen)
-    lim = TL.TimeLimitRef(ref, 3, c["seed"], True)
-    gd, lost = GoalTracker(rcw, env), NeverLost(env)
-    stream = torch.cuda.Stream()
-    env.sync()
-    env.set_stream(stream.cuda_stream)
-    a_host = np.ones(c["B"], np.uint8)                                       # forward: the same action in every replay
-    with torch.cuda.stream(stream):
-        actions = torch.from_numpy(a_host).cuda()
-        stream.synchronize()
-        ptr = env.wall_layout.ptr
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=stream):
-            rcw.act_(env, actions)                                           # (captured, not run)
-        for k in range(12):
-            g.replay()
-            stream.synchronize()
-            lim.step(a_host)
-            WG.assert_equal(env, ref, f"replay {k}")
-            np.testing.assert_array_equal(env.world.episode_steps, lim.episode_steps, err_msg=f"episode_steps, replay {k}")
-            gd.stepped(a_host, f"replay {k}")
-            lost.stepped(a_host, f"replay {k}")
-        assert env.wall_layout.ptr == ptr
-        stream.synchronize()
-    assert len(ref.mazes_made) > 3 * c["B"] and lim.events["restarts_after_truncation"] >= 2 * c["B"]
-    del g
-    env.close()
-
-
-def test_two_shards_equal_their_slices_of_the_whole_batch(rcw):
-    G, WORLD = 16, 2
-    kw = dict(seed=5, auto_reset=True, height_tile_map_tu=9, width_tile_map_tu=9, num_rays=33, height_camera_view_pu=24, num_directions=8,
-              position_increment_wu=0.25, player_radius_wu=0.3)
-    gen = dict(loops=0.25, levels=6, first_level=10, level_seed=4)
-    whole = rcw.SingleRoomModule.SingleRoom(batch=G, wall_generator=gen, max_episode_steps=4, **kw)
-    shards = [rcw.ShardedSingleRoom(G, rank=r, world=WORLD, device=0, **kw) for r in range(WORLD)]
-    for sh in shards:
-        sh.set_wall_generator(**gen)
-        sh.env.set_time_limit(4)
-
-    def compare(where):
-        for sh in shards:
-            sl = slice(sh.first, sh.first + sh.count)
-            np.testing.assert_array_equal(sh.env.wall_layout.numpy(), whole.wall_layout.numpy()[sl], err_msg=f"wall_layout {where}")
-            for k in ("episode", "goal_position", "player_position_wu", "player_direction_au", "done", "tile_map_chunks", "truncated"):
-                np.testing.assert_array_equal(getattr(sh.env.world, k), getattr(whole.world, k)[sl], err_msg=f"{k} {where}")
-            np.testing.assert_array_equal(sh.env.camera_view_host(), whole.camera_view_host()[sl], err_msg=f"camera view {where}")
-
-    compare("installed")
-    rng = np.random.default_rng(3)
-    moved = whole.world.episode.copy()
-    for k in range(12):
-        a = WR.draw_actions(rng, G)
-        rcw.act_(whole, a)
-        for sh in shards:
-            sh.act_(sh.local_slice(a))
-        compare(f"step {k}")
-    assert (whole.world.episode > moved).all() and len(set(whole.wall_layout.numpy().tolist())) > 1
-    for e in [whole] + [sh.env for sh in shards]:
-        e.set_wall_generator(0.0)                                            # no levels from here: a maze per (global agent, episode)
-    for sh in shards:
-        sh.reset_(seed=8)
-    rcw.reset_(whole, seed=8)
-    compare("behind other parameters and a reset")
-    assert (whole.wall_layout.numpy() == -1).all()
-    for sh in shards:
-        sh.env.close()
-    whole.close()
-
-
-def test_random_generators_and_call_sequences_stay_in_parity():
-    """tools/fuzz_parity.py gen: maps of 5 x 5 to 40 x 40, loops, levels, 30 random calls each, totals printed"""
-    res = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "tools", "fuzz_parity.py"), "16", "71", "gen"],
-                         capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
-    assert "16 random configurations" in res.stdout and ", 0 mismatches" in res.stdout
-    closing = res.stdout.strip().splitlines()[-1]
-    print(closing)
-    totals = {k: int(v) for v, k in re.findall(r"(\d+) ([a-z_0-9]+)\b", closing[closing.index("wall generator:"):closing.rindex(")")])}
-    for k in ("step", "reset", "masked_reset", "set_state", "off_and_on", "episode_starts", "goal_redraws", "restarts_after_done",
-              "restarts_after_truncation", "one_launch_steps", "two_launch_steps", "even_sizes", "with_levels", "with_loops", "cells_past_64"):
-        assert totals[k] > 0, closing

@@ -1,9 +1,8 @@
 """The caves' scenarios, written ONCE and run twice — test infrastructure, not a test.
 
-The drivers and the shapes are tests/wall_bank_cases.py's and tests/wall_generator_cases.py's, by import: a Recorder (the reference alone,
-tests/wall_caves_ref.py, under tests/time_limit_ref.py where the scenario sets a limit; a snapshot after every call) and a Player (an
-engine: every call made on it and compared with the next snapshot byte for byte, then handed to the feature trackers).  What changes is the
-reference they drive, the call `set_wall_caves`, and the comparison of wall_layout, which the engine serves while the CAVES are on.
+The drivers are tests/wall_family.py's, by its row `caves`: a Recorder (the reference alone: wall_family.WallFamilyRef over
+wall_caves_ref.cave) and a Player (an engine against the recording), with `set_wall_caves` as their own call.  This module is the caves'
+shapes, their pinned levels and their scenarios.
 
 Every scenario: 8 headings, a quarter tile a move, a player radius of 0.3, auto_reset, forward-heavy actions (walls_ref.draw_actions).
 """
@@ -13,7 +12,7 @@ import numpy as np
 
 import wall_bank_cases as BC
 import wall_caves_ref as WC
-import wall_generator_cases as GC
+import wall_family as WF
 import walls_ref as WR
 
 # ---- the shapes ---------------------------------------------------------------------------------------------------------------------------
@@ -37,83 +36,15 @@ ALL_SHAPES = [(5, 7), (8, 8), (9, 12), (16, 16), (21, 45), (32, 32), (66, 66)]
 HARD_LEVELS = {(5, 7): (9, 2), (8, 8): (0, 2), (9, 12): (58, 3), (16, 16): (0, 3), (21, 45): (140, 4), (32, 32): (0, 4), (66, 66): (0, 4)}   # (level, rounds)
 
 
-def make_ref(c, render=True, **kw):
-    return WC.WallCavesRef(c["B"], c["seed"], c["H"], c["W"], c["N"], c["Hc"], T=np.float64 if c.get("T") == "Float64" else np.float32,
-                           render=render, **kw)
-
-
-make_env = BC.make_env
-
-
-# ---- the two drivers ----------------------------------------------------------------------------------------------------------------------
-class Recorder(GC.Recorder):
-    def __init__(self, c, render=True, **kw):
-        self.c, self.ref, self.lim, self.snaps, self.render = c, make_ref(c, render, **kw), None, [], render
-        self.B = c["B"]
-        self._snap()
-
-    def _snap(self):
-        s = self.ref.snapshot()
-        if self.lim is not None:
-            s.update(episode_steps=self.lim.episode_steps.copy(), truncated=self.lim.truncated.copy())
-        s["caves"], s["rendered"] = self.ref.gen is not None, self.render
-        self.snaps.append(s)
-
-    @property
-    def events(self):
-        return dict(self.ref.events, **(self.lim.events if self.lim is not None else {}), keys_made=set(self.ref.keys_made))
-
-    def set_wall_caves(self, fill=WC.DEFAULT_FILL, smooth=WC.DEFAULT_SMOOTH, levels=0, first_level=0, level_seed=0):
-        self.ref.set_wall_caves(fill, smooth, levels, first_level, level_seed)
-        if self.lim is not None and fill is not None:
-            self.lim.clear()
-        self._snap()
-
-
-class Player(GC.Player):
-    def _check(self, where):
-        s = self.snaps[self.k]
-        where = f"{self.name}, call {self.k}: {where}"
-        self.k += 1
-        assert self.env.wall_caves_info["enabled"] == s["caves"] and not self.env.wall_bank_info["layouts"], where
-        assert self.env.wall_generator_info["enabled"] == s["caves"] and self.env.wall_generator_info["loops"] == 0, where
-        if s["rendered"]:
-            WC.assert_equal(self.env, s, where)
-        else:
-            GC.assert_state_equal(self.env, s, where)
-            if s["caves"]:
-                np.testing.assert_array_equal(self.env.wall_layout.numpy(), s["wall_layout"], err_msg=f"wall_layout {where}")
-        if "episode_steps" in s:
-            np.testing.assert_array_equal(self.env.world.episode_steps, s["episode_steps"], err_msg=f"episode_steps {where}")
-            np.testing.assert_array_equal(self.env.world.truncated.astype(np.uint8), s["truncated"], err_msg=f"truncated {where}")
-        return where
-
-    def set_wall_caves(self, fill=WC.DEFAULT_FILL, smooth=WC.DEFAULT_SMOOTH, levels=0, first_level=0, level_seed=0):
-        self.env.set_wall_caves(fill, smooth, levels, first_level, level_seed)
-        if fill is None:
-            self._check("caves off")
-        else:
-            self._masked(None, "set_wall_caves")
+make_ref = functools.partial(WF.make_ref, "caves")
+make_env = WF.make_env
+Recorder, Player = WF.drivers("caves")                                       # the shared drivers with `set_wall_caves` as their own call
 
 
 # ---- the scenarios ------------------------------------------------------------------------------------------------------------------------
-def rollout(d, caves, limit, steps, seed):
-    d.set_wall_caves(**caves)
-    if limit:
-        d.set_time_limit(limit)
-    rng = np.random.default_rng(seed)
-    for _ in range(steps):
-        d.step(WR.draw_actions(rng, d.B))
-
-
-walk_into_the_goal = BC.walk_into_the_goal
-
-
-def walk_and_step(d, every, seed, steps=3):
-    walk_into_the_goal(d, (np.arange(d.B) % every == 0).astype(np.uint8))
-    rng = np.random.default_rng(seed)
-    for _ in range(steps):
-        d.step(WR.draw_actions(rng, d.B))
+rollout = functools.partial(WF.rollout, "caves")
+walk_into_the_goal = WF.walk_into_the_goal
+walk_and_step = WF.walk_and_step
 
 
 def square(d):
@@ -195,22 +126,57 @@ SCENARIOS = dict(square=(square, SQUARE), tie=(tie, TIE), tie64=(tie, TIE64), mi
 MIXED = ("square", "levels", "features", "calls")                            # scenarios that must reach caves AND fallbacks
 
 
-@functools.lru_cache(maxsize=None)
-def recorded(name, render=True, offset=0, batch=None):
-    """the reference's run of a scenario, computed once: (snapshots, events)"""
-    fn, c = SCENARIOS[name]
-    c = dict(c, B=batch) if batch is not None else c
-    rec = Recorder(c, render, agent_id_offset=offset)
-    fn(rec)
-    return rec.snaps, rec.events
+recorded = functools.partial(WF.recorded, "caves")                                  # (name, render=True, offset=0, batch=None) -> (snapshots, events), cached
+play = functools.partial(WF.play, "caves")                                          # (rcw, name, env, trackers=(), wrap=None) -> events
 
 
-def play(rcw, name, env, trackers=(), wrap=None):
-    """the scenario on `env` against its recording; trackers: the feature trackers, made once the engine exists"""
-    fn, _ = SCENARIOS[name]
-    snaps, events = recorded(name)
-    p = Player(rcw, env, snaps, name)
-    p.trackers = list(trackers)
-    fn(p if wrap is None else wrap(p))                                       # (wrap: tests/deferred.py takes a note behind every call)
-    p.finished()
-    return events
+# ---- what tests/test_gpu_wall_families.py plays of this family: the arguments of the tests every family has ------------------------------------
+ROLLOUTS = [("square", "two-launches"), ("square", "one-launch"), ("tie", None), ("tie64", None), ("mid", None), ("wide", None), ("empty", None),
+            ("full", None), ("levels", None), ("calls", "two-launches"), ("calls", "one-launch")]
+REPLAYED = (dict(LEVELS, B=21), (dict(fill=0.42, smooth=1), dict(levels=5, first_level=3, level_seed=8)))
+BESIDE_A_PLAIN_HANDLE = dict()
+UNTOUCHED = dict(levels=3, first_level=1, level_seed=2)
+CAPTURED = (dict(CALLS, B=12), dict(fill=0.40, smooth=2))
+SHARDED = (12, dict(fill=0.42, smooth=2, levels=6, first_level=40, level_seed=9), (0.3, 1))    # (the map's width, the install, other parameters without levels)
+REFUSED_MAPS = [(4, 9, ValueError, "at least 5 x 5"), (9, 4, ValueError, "at least 5 x 5"), (67, 66, "unsupported", "at most 4096 interior tiles")]
+NAMED = {(67, 66): ("66 x 66",)}                                                # 65 x 64 = 4160 interior tiles: the message names the bound
+FUZZ = ("caves", "wall caves:", ("step", "reset", "masked_reset", "set_state", "arrive", "off_and_on", "episode_starts", "fallbacks", "caves_kept", "goal_redraws",
+                                 "restarts_after_done", "restarts_after_truncation", "one_launch_steps", "two_launch_steps", "non_square", "with_levels", "smoothed",
+                                 "tiles_past_64"))
+
+
+def reached(events, name=None):
+    """what the reference's counts must show of a run (of scenario `name`) beyond restarts: caves AND fallbacks, by the reference's own count"""
+    if name is None or name in MIXED:
+        assert 0 < events["fallbacks"] < events["episode_starts"]
+
+
+def check_rollout(rcw, env, name):
+    """what holds of the engine behind scenario `name`"""
+    c = SCENARIOS[name][1]
+    walls, layout = env.world.walls, env.wall_layout.numpy()
+    if name == "tie64":
+        assert env.world.player_position_wu.dtype == np.float64
+    if name in ("tie", "tie64"):
+        # the two largest regions of generation 0 tie: every agent holds the cave of the one with the smaller tile index
+        g = WC.smoothed(WF.level_key(HARD_LEVEL_SEED, TIE_LEVEL), 7, 9, WC.fill_word(TIE_FILL), TIE_SMOOTH)
+        first, second = sorted(WC.regions(g), key=lambda r: (-len(r), r[0]))[:2]
+        assert len(first) == len(second) >= WC.need(7, 9) and first[0] < second[0]
+        for a in range(env.batch):
+            assert sorted(int(i + 7 * j) for i, j in np.argwhere(~walls[a])) == first
+        assert (layout == TIE_LEVEL).all()
+    elif name == "levels":
+        assert set(layout.tolist()) == {43, 44, 45} and min(np.bincount(layout - 43)) > 5
+        fell = {}
+        for level in (43, 44, 45):                                            # every level held by several agents, one layout a level
+            held = walls[layout == level]
+            assert (held == held[0]).all()
+            want, fell[level] = rcw.layouts.generated_cave(rcw.layouts.generated_maze_key(0, 0, 0, 1, level, 9)[0], c["H"], c["W"], return_fell_back=True)
+            np.testing.assert_array_equal(held[0], want)
+        assert fell == {43: True, 44: False, 45: True}
+    elif name == "empty":
+        assert (layout == -1).all() and ((~walls).sum(axis=(1, 2)) == 9).all()
+    elif name == "full":
+        assert (layout == -1).all() and ((~walls).sum(axis=(1, 2)) == 7).all()
+    else:
+        assert (layout == -1).all()

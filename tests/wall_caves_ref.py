@@ -12,8 +12,7 @@ A CAVE FROM ONE 64-BIT KEY, cave(m, H, W, fill, smooth) for H, W >= 5, with draw
 
 THE KEY OF AN EPISODE is the generator's (wall_generator_ref.maze_key), and after it the rule is the bank's.
 
-WallCavesRef is WallsRef with the one override of _reset_agent, as WallGeneratorRef is.  `events` also counts episode_starts and
-fallbacks (episode starts whose layout is the maze); `keys_made` is the set of keys used so far.
+The reference that applies the rule is wall_family.WallFamilyRef; its `events` count fallbacks (episode starts whose layout is the maze).
 
 `labelling` restates the kernel's rounds (csrc/rcw_wall_bank.hip, rcw_wall_caves_kernel's header), as wall_generator_ref.boruvka restates
 the maze's.
@@ -22,7 +21,6 @@ import numpy as np
 
 import wall_generator_ref as WG
 import walls_ref as WR
-from oracle import pyref
 
 CAVE_DRAW = 1 << 62
 MAX_TILES = 4096
@@ -169,63 +167,3 @@ def install_refusal(H, W, smooth, levels, first_level):
     if H < 5 or W < 5 or not 0 <= smooth <= MAX_SMOOTH or levels < 0 or first_level < 0 or first_level + levels > 2 ** 31 - 1:
         return "invalid"
     return "unsupported" if (H - 2) * (W - 2) > MAX_TILES else None
-
-
-class WallCavesRef(WR.WallsRef):
-    def __init__(self, *args, **kw):
-        self.gen = None
-        super().__init__(*args, **kw)
-        self.wall_layout = np.zeros(self.B, np.int32)
-        self.events.update(episode_starts=0, fallbacks=0)
-        self.keys_made = set()
-        self._cache = {}
-
-    # ---- the rule ------------------------------------------------------------------------------------------------------------------
-    def _reset_agent(self, b):
-        if self.gen is not None:
-            fill, smooth, levels, first_level, level_seed = self.gen
-            m, level = WG.maze_key(self.seed, self.offset + b, int(self.episode[b]), levels, first_level, level_seed)
-            if m not in self._cache:
-                self._cache[m] = cave(m, self.H, self.W, fill, smooth, return_fell_back=True)
-            walls, fell = self._cache[m]
-            tm = self.worlds[b].tile_map
-            for i in range(1, self.H + 1):
-                for j in range(1, self.W + 1):
-                    tm[pyref.WALL][i][j] = bool(walls[i - 1, j - 1])
-                    tm[pyref.GOAL][i][j] = False
-            self.events["episode_starts"] += 1
-            self.events["fallbacks"] += int(fell)
-            self.keys_made.add(m)
-            self.wall_layout[b] = level
-        super()._reset_agent(b)
-
-    # ---- the calls -----------------------------------------------------------------------------------------------------------------
-    def set_wall_caves(self, fill=DEFAULT_FILL, smooth=DEFAULT_SMOOTH, levels=0, first_level=0, level_seed=0):
-        """rcw_set_wall_caves: install (every agent restarts under the rule with the current seed) or, fill None, switch off (walls kept).
-        fill: a probability (float) or the UInt32 word (int)."""
-        if fill is None:
-            self.gen = None
-            return
-        assert install_refusal(self.H, self.W, smooth, levels, first_level) is None
-        word = int(fill) if isinstance(fill, (int, np.integer)) else fill_word(fill)
-        self.gen = (word, int(smooth), int(levels), int(first_level), int(level_seed))
-        self._cache = {}
-        self.reset()
-
-    def set_walls(self, walls, index=None, mask=None):
-        if self.gen is not None:
-            raise RuntimeError("rcw_set_walls is refused while the handle makes caves")
-        super().set_walls(walls, index, mask)
-
-    def snapshot(self):
-        return dict(super().snapshot(), wall_layout=self.wall_layout.copy())
-
-
-def assert_equal(env, ref, where=""):
-    """walls_ref.assert_equal plus wall_layout (while the reference makes caves: without them the engine refuses the getter)"""
-    r = ref if isinstance(ref, dict) else ref.snapshot()
-    WR.assert_equal(env, r, where)
-    if env.wall_caves_info["enabled"]:
-        got = env.wall_layout.numpy()
-        assert got.dtype == np.int32
-        np.testing.assert_array_equal(got, r["wall_layout"], err_msg=f"wall_layout {where}")

@@ -1,10 +1,9 @@
 """The wall generator's scenarios, written ONCE and run twice — test infrastructure, not a test.
 
-The drivers and the shapes are tests/wall_bank_cases.py's, by import: a Recorder (the reference alone, tests/wall_generator_ref.py, under
-tests/time_limit_ref.py where the scenario sets a limit; a snapshot after every call) and a Player (an engine: every call made on it and
-compared with the next snapshot byte for byte, then handed to the feature trackers).  What changes is the reference they drive, the call
-`set_wall_generator`, and the comparison of wall_layout, which the engine serves while the GENERATOR is on.  A Recorder made with
-render=False records no frames; its Player compares everything but the column descriptors and the camera view (`huge`: 65 x 65).
+The drivers are tests/wall_family.py's, by its row `generator`: a Recorder (the reference alone: wall_family.WallFamilyRef over
+wall_generator_ref.maze) and a Player (an engine against the recording), with `set_wall_generator` as their own call; the bank's shapes by
+import.  This module is the generator's shapes, its pinned levels and its scenarios.  A Recorder made with render=False records no frames;
+its Player compares everything but the column descriptors and the camera view (`huge`, 65 x 65, is never rendered: UNRENDERED).
 
 Every scenario: 8 headings, a quarter tile a move, a player radius of 0.3, auto_reset, forward-heavy actions (walls_ref.draw_actions).
 """
@@ -13,6 +12,7 @@ import functools
 import numpy as np
 
 import wall_bank_cases as BC
+import wall_family as WF
 import wall_generator_ref as WG
 import walls_ref as WR
 
@@ -37,97 +37,14 @@ HARD_ROUNDS = {(129, 129): 7, (5, 4097): 8, (4097, 5): 8, (33, 33): 5}
 WORDS = dict(edge=1042, edge_rows64=1042, edge_even=1058, thin=1282, tall=1282, thin_even=1538)      # 2 (ceil(H W / 16) rounded up to even)
 
 
-def make_ref(c, render=True, **kw):
-    return WG.WallGeneratorRef(c["B"], c["seed"], c["H"], c["W"], c["N"], c["Hc"], T=np.float64 if c.get("T") == "Float64" else np.float32,
-                               render=render, **kw)
-
-
-make_env = BC.make_env
-
-
-# ---- the two drivers ----------------------------------------------------------------------------------------------------------------------
-class Recorder(BC.Recorder):
-    def __init__(self, c, render=True, **kw):
-        self.c, self.ref, self.lim, self.snaps, self.render = c, make_ref(c, render, **kw), None, [], render
-        self.B = c["B"]
-        self._snap()
-
-    def _snap(self):
-        s = self.ref.snapshot()
-        if self.lim is not None:
-            s.update(episode_steps=self.lim.episode_steps.copy(), truncated=self.lim.truncated.copy())
-        s["generator"], s["rendered"] = self.ref.gen is not None, self.render
-        self.snaps.append(s)
-
-    @property
-    def events(self):
-        return dict(self.ref.events, **(self.lim.events if self.lim is not None else {}), mazes_made=set(self.ref.mazes_made))
-
-    def state(self):
-        """(walls (B, H, W), goal, position, heading) as they stand: what a scenario builds a set_state from"""
-        s = self.snaps[-1]
-        return np.stack([self.ref.walls_of(b) for b in range(self.B)]), s["goal"].copy(), s["position"].copy(), s["direction"].copy()
-
-    def set_wall_generator(self, loops=0.0, levels=0, first_level=0, level_seed=0):
-        self.ref.set_wall_generator(loops, levels, first_level, level_seed)
-        if self.lim is not None and loops is not None:
-            self.lim.clear()
-        self._snap()
-
-
-def assert_state_equal(env, r, where):
-    """walls_ref.assert_equal without the frames (a recording made with render=False has none)"""
-    w = env.world
-    pos = w.player_position_wu
-    bits = np.uint64 if pos.dtype == np.float64 else np.uint32
-    assert pos.dtype == r["position"].dtype
-    for got, key in ((w.status, "status"), (w.episode, "episode"), (w.goal_position, "goal"), (pos.view(bits), None), (w.player_direction_au, "direction"),
-                     (w.reward, "reward"), (w.done.astype(np.uint8), "done"), (w.tile_map_chunks, "tile_map_chunks")):
-        want = r["position"].view(bits) if key is None else r[key]
-        np.testing.assert_array_equal(got, want, err_msg=f"{key or 'position'} {where}")
-
-
-class Player(BC.Player):
-    def _check(self, where):
-        s = self.snaps[self.k]
-        where = f"{self.name}, call {self.k}: {where}"
-        self.k += 1
-        assert self.env.wall_generator_info["enabled"] == s["generator"] and not self.env.wall_bank_info["layouts"], where
-        if s["rendered"]:
-            WG.assert_equal(self.env, s, where)
-        else:
-            assert_state_equal(self.env, s, where)
-            if s["generator"]:
-                np.testing.assert_array_equal(self.env.wall_layout.numpy(), s["wall_layout"], err_msg=f"wall_layout {where}")
-        if "episode_steps" in s:
-            np.testing.assert_array_equal(self.env.world.episode_steps, s["episode_steps"], err_msg=f"episode_steps {where}")
-            np.testing.assert_array_equal(self.env.world.truncated.astype(np.uint8), s["truncated"], err_msg=f"truncated {where}")
-        return where
-
-    def state(self):
-        """the engine's own state, which the call before found equal to the reference's"""
-        w = self.env.world
-        return w.walls, w.goal_position.copy(), w.player_position_wu.copy(), w.player_direction_au.copy()
-
-    def set_wall_generator(self, loops=0.0, levels=0, first_level=0, level_seed=0):
-        self.env.set_wall_generator(loops, levels, first_level, level_seed)
-        if loops is None:
-            self._check("generator off")
-        else:
-            self._masked(None, "set_wall_generator")
+make_ref = functools.partial(WF.make_ref, "generator")
+make_env = WF.make_env
+Recorder, Player = WF.drivers("generator")                                       # the shared drivers with `set_wall_generator` as their own call
 
 
 # ---- the scenarios ------------------------------------------------------------------------------------------------------------------------
-def rollout(d, gen, limit, steps, seed):
-    d.set_wall_generator(**gen)
-    if limit:
-        d.set_time_limit(limit)
-    rng = np.random.default_rng(seed)
-    for _ in range(steps):
-        d.step(WR.draw_actions(rng, d.B))
-
-
-walk_into_the_goal = BC.walk_into_the_goal
+rollout = functools.partial(WF.rollout, "generator")
+walk_into_the_goal = WF.walk_into_the_goal
 
 
 def small(d):
@@ -221,22 +138,47 @@ AT_THE_BOUND = ("edge", "edge_rows64", "edge_even", "thin", "tall", "thin_even")
 UNRENDERED = ("huge",)
 
 
-@functools.lru_cache(maxsize=None)
-def recorded(name, render=True, offset=0, batch=None):
-    """the reference's run of a scenario, computed once: (snapshots, events)"""
-    fn, c = SCENARIOS[name]
-    c = dict(c, B=batch) if batch is not None else c
-    rec = Recorder(c, render and name not in UNRENDERED, agent_id_offset=offset)
-    fn(rec)
-    return rec.snaps, rec.events
+recorded = functools.partial(WF.recorded, "generator")                                  # (name, render=True, offset=0, batch=None) -> (snapshots, events), cached
+play = functools.partial(WF.play, "generator")                                          # (rcw, name, env, trackers=(), wrap=None) -> events
 
 
-def play(rcw, name, env, trackers=(), wrap=None):
-    """the scenario on `env` against its recording; trackers: the feature trackers, made once the engine exists"""
-    fn, _ = SCENARIOS[name]
-    snaps, events = recorded(name)
-    p = Player(rcw, env, snaps, name)
-    p.trackers = list(trackers)
-    fn(p if wrap is None else wrap(p))                                       # (wrap: tests/deferred.py takes a note behind every call)
-    p.finished()
-    return events
+# ---- what tests/test_gpu_wall_families.py plays of this family: the arguments of the tests every family has ------------------------------------
+ROLLOUTS = [("small", "two-launches"), ("small", "one-launch"), ("square", None), ("big", "two-launches"), ("big", "one-launch"), ("wide", None),
+            ("huge", None), ("f64", None), ("levels", None), ("calls", "two-launches"), ("calls", "one-launch"),
+            ("edge", "two-launches"), ("edge_rows64", "one-launch"), ("edge_even", None), ("thin", None), ("tall", None), ("thin_even", None)]
+REPLAYED = (dict(LEVELS, B=21, H=9, W=11), (dict(loops=0.25), dict(loops=0.25, levels=5, first_level=3, level_seed=8)))
+BESIDE_A_PLAIN_HANDLE = dict(loops=0.5)
+UNTOUCHED = dict(levels=3, first_level=1, level_seed=2)
+CAPTURED = (dict(CALLS, B=12, H=7, W=9), dict(loops=0.25, levels=0))
+SHARDED = (9, dict(loops=0.25, levels=6, first_level=10, level_seed=4), (0.0,))     # (the map's width, the install, other parameters without levels)
+REFUSED_MAPS = [(4, 9, ValueError, "at least 5 x 5"), (9, 4, ValueError, "at least 5 x 5"), (131, 129, "unsupported", "at most 4096 cells")]
+NAMED = {(131, 129): ("129 x 129",)}                                            # 65 x 64 = 4160 cells: the message names the bound
+FUZZ = ("gen", "wall generator:", ("step", "reset", "masked_reset", "set_state", "off_and_on", "episode_starts", "goal_redraws", "restarts_after_done",
+                                   "restarts_after_truncation", "one_launch_steps", "two_launch_steps", "even_sizes", "with_levels", "with_loops", "cells_past_64"))
+
+
+def reached(events, name=None):
+    """what the reference's counts must show of a run (of scenario `name`) beyond restarts: nothing of the generator's own"""
+
+
+def check_rollout(rcw, env, name):
+    """what holds of the engine behind scenario `name`"""
+    c = SCENARIOS[name][1]
+    if name == "f64":
+        assert env.world.player_position_wu.dtype == np.float64
+    if name == "big":
+        assert env.world.tile_map_chunks.shape[1] * 2 > 64                    # more tile-map words than a wavefront has lanes
+    if name == "huge":
+        assert WG.grid(c["H"], c["W"])[2] == 1024
+    if name in AT_THE_BOUND:
+        assert WG.grid(c["H"], c["W"])[2] == 4096 == WG.MAX_CELLS            # the bound itself, not 4095
+        assert env.world.tile_map_chunks.shape[1] * 2 == WORDS[name]          # (a chunk is two words)
+    if name == "levels":
+        layout, walls = env.wall_layout.numpy(), env.world.walls
+        assert set(layout.tolist()) == {40, 41, 42} and min(np.bincount(layout - 40)) > 5
+        for level in (40, 41, 42):                                            # every level held by several agents, one maze a level
+            held = walls[layout == level]
+            assert (held == held[0]).all()
+            np.testing.assert_array_equal(held[0], rcw.layouts.generated_maze(rcw.layouts.generated_maze_key(0, 0, 0, 1, level, 9)[0], c["H"], c["W"]))
+    else:
+        assert (env.wall_layout.numpy() == -1).all()

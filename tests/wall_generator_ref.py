@@ -15,13 +15,12 @@ u = draw(key, 2^63) — the bank's draw index.  levels == 0: m = u, wall_layout 
 m = episode_key(level_seed, l, 0), wall_layout = l.  After that the rule is the bank's: WALL := the maze, GOAL cleared, the reset of
 walls_ref.py against the new walls under `key` from draw 0, counter = e + 1 (once).
 
-WallGeneratorRef is WallsRef with that one override of _reset_agent, as WallBankRef is.  `events` also counts episode_starts, and
-`mazes_made` is the set of maze keys used so far.
+The reference that applies the rule, wall_family.WallFamilyRef, is WallsRef with that one override of _reset_agent, as WallBankRef is; this
+module is the maze, its key and the restatement of the kernel's rounds.
 """
 import numpy as np
 
 import walls_ref as WR
-from oracle import pyref
 
 LAYOUT_DRAW = 1 << 63
 ORDER_MASK = 0xFFFFFFFFFFF00000
@@ -155,62 +154,3 @@ def install_refusal(H, W, levels, first_level):
     if H < 5 or W < 5 or levels < 0 or first_level < 0 or first_level + levels > 2 ** 31 - 1:
         return "invalid"
     return "unsupported" if grid(H, W)[2] > MAX_CELLS else None
-
-
-class WallGeneratorRef(WR.WallsRef):
-    def __init__(self, *args, **kw):
-        self.gen = None
-        super().__init__(*args, **kw)
-        self.wall_layout = np.zeros(self.B, np.int32)
-        self.events.update(episode_starts=0)
-        self.mazes_made = set()
-        self._cache = {}
-
-    # ---- the rule ------------------------------------------------------------------------------------------------------------------
-    def _reset_agent(self, b):
-        if self.gen is not None:
-            loops, levels, first_level, level_seed = self.gen
-            m, level = maze_key(self.seed, self.offset + b, int(self.episode[b]), levels, first_level, level_seed)
-            if m not in self._cache:
-                self._cache[m] = maze(m, self.H, self.W, loops)
-            walls = self._cache[m]
-            tm = self.worlds[b].tile_map
-            for i in range(1, self.H + 1):
-                for j in range(1, self.W + 1):
-                    tm[pyref.WALL][i][j] = bool(walls[i - 1, j - 1])
-                    tm[pyref.GOAL][i][j] = False
-            self.events["episode_starts"] += 1
-            self.mazes_made.add(m)
-            self.wall_layout[b] = level
-        super()._reset_agent(b)
-
-    # ---- the calls -----------------------------------------------------------------------------------------------------------------
-    def set_wall_generator(self, loops=0.0, levels=0, first_level=0, level_seed=0):
-        """rcw_set_wall_generator: install (every agent restarts under the rule with the current seed) or, loops None, switch off (walls
-        kept).  loops: a probability (float) or the UInt32 word (int)."""
-        if loops is None:
-            self.gen = None
-            return
-        assert install_refusal(self.H, self.W, levels, first_level) is None
-        word = int(loops) if isinstance(loops, (int, np.integer)) else loops_word(loops)
-        self.gen = (word, int(levels), int(first_level), int(level_seed))
-        self._cache = {}
-        self.reset()
-
-    def set_walls(self, walls, index=None, mask=None):
-        if self.gen is not None:
-            raise RuntimeError("rcw_set_walls is refused while the handle has a generator")
-        super().set_walls(walls, index, mask)
-
-    def snapshot(self):
-        return dict(super().snapshot(), wall_layout=self.wall_layout.copy())
-
-
-def assert_equal(env, ref, where=""):
-    """walls_ref.assert_equal plus wall_layout (while the reference has a generator: without one the engine refuses the getter)"""
-    r = ref if isinstance(ref, dict) else ref.snapshot()
-    WR.assert_equal(env, r, where)
-    if env.wall_generator_info["enabled"]:
-        got = env.wall_layout.numpy()
-        assert got.dtype == np.int32
-        np.testing.assert_array_equal(got, r["wall_layout"], err_msg=f"wall_layout {where}")

@@ -1,10 +1,8 @@
 """The rooms' scenarios, written ONCE and run twice — test infrastructure, not a test.
 
-The drivers and the shapes are tests/wall_bank_cases.py's and tests/wall_generator_cases.py's, by import, as the caves' are: a Recorder (the
-reference alone, tests/wall_rooms_ref.py, under tests/time_limit_ref.py where the scenario sets a limit; a snapshot after every call) and a
-Player (an engine: every call made on it and compared with the next snapshot byte for byte, then handed to the feature trackers).  What
-changes is the reference they drive, the call `set_wall_rooms`, and the comparison of wall_layout, which the engine serves while the ROOMS
-are on.
+The drivers are tests/wall_family.py's, by its row `rooms`: a Recorder (the reference alone: wall_family.WallFamilyRef over
+wall_rooms_ref.rooms) and a Player (an engine against the recording), with `set_wall_rooms` as their own call.  This module is the rooms'
+shapes, their pinned levels and their scenarios.
 
 Every scenario: 8 headings, a quarter tile a move, a player radius of 0.3, auto_reset, forward-heavy actions (walls_ref.draw_actions).
 """
@@ -13,8 +11,7 @@ import functools
 import numpy as np
 
 import wall_bank_cases as BC
-import wall_generator_cases as GC
-import wall_rooms_ref as RR
+import wall_family as WF
 import walls_ref as WR
 
 ALL = 0xFFFFFFFF
@@ -38,84 +35,15 @@ WIDEST_LEVEL = (111, 166)                                           # (level, th
 DEEPEST_LEVEL = (48, 25)                                            # (level, rounds)
 
 
-def make_ref(c, render=True, **kw):
-    return RR.WallRoomsRef(c["B"], c["seed"], c["H"], c["W"], c["N"], c["Hc"], T=np.float64 if c.get("T") == "Float64" else np.float32,
-                           render=render, **kw)
-
-
-make_env = BC.make_env
-
-
-# ---- the two drivers ----------------------------------------------------------------------------------------------------------------------
-class Recorder(GC.Recorder):
-    def __init__(self, c, render=True, **kw):
-        self.c, self.ref, self.lim, self.snaps, self.render = c, make_ref(c, render, **kw), None, [], render
-        self.B = c["B"]
-        self._snap()
-
-    def _snap(self):
-        s = self.ref.snapshot()
-        if self.lim is not None:
-            s.update(episode_steps=self.lim.episode_steps.copy(), truncated=self.lim.truncated.copy())
-        s["rooms"], s["rendered"] = self.ref.gen is not None, self.render
-        self.snaps.append(s)
-
-    @property
-    def events(self):
-        return dict(self.ref.events, **(self.lim.events if self.lim is not None else {}), keys_made=set(self.ref.keys_made))
-
-    def set_wall_rooms(self, room=RR.DEFAULT_ROOM, stop=RR.DEFAULT_STOP, doors=RR.DEFAULT_DOORS, levels=0, first_level=0, level_seed=0):
-        self.ref.set_wall_rooms(room, stop, doors, levels, first_level, level_seed)
-        if self.lim is not None and room is not None:
-            self.lim.clear()
-        self._snap()
-
-
-class Player(GC.Player):
-    def _check(self, where):
-        s = self.snaps[self.k]
-        where = f"{self.name}, call {self.k}: {where}"
-        self.k += 1
-        assert self.env.wall_rooms_info["enabled"] == s["rooms"] and not self.env.wall_bank_info["layouts"], where
-        assert not self.env.wall_caves_info["enabled"], where
-        assert self.env.wall_generator_info["enabled"] == s["rooms"] and self.env.wall_generator_info["loops"] == 0, where
-        if s["rendered"]:
-            RR.assert_equal(self.env, s, where)
-        else:
-            GC.assert_state_equal(self.env, s, where)
-            if s["rooms"]:
-                np.testing.assert_array_equal(self.env.wall_layout.numpy(), s["wall_layout"], err_msg=f"wall_layout {where}")
-        if "episode_steps" in s:
-            np.testing.assert_array_equal(self.env.world.episode_steps, s["episode_steps"], err_msg=f"episode_steps {where}")
-            np.testing.assert_array_equal(self.env.world.truncated.astype(np.uint8), s["truncated"], err_msg=f"truncated {where}")
-        return where
-
-    def set_wall_rooms(self, room=RR.DEFAULT_ROOM, stop=RR.DEFAULT_STOP, doors=RR.DEFAULT_DOORS, levels=0, first_level=0, level_seed=0):
-        self.env.set_wall_rooms(room, stop, doors, levels, first_level, level_seed)
-        if room is None:
-            self._check("rooms off")
-        else:
-            self._masked(None, "set_wall_rooms")
+make_ref = functools.partial(WF.make_ref, "rooms")
+make_env = WF.make_env
+Recorder, Player = WF.drivers("rooms")                                       # the shared drivers with `set_wall_rooms` as their own call
 
 
 # ---- the scenarios ------------------------------------------------------------------------------------------------------------------------
-def rollout(d, rooms, limit, steps, seed):
-    d.set_wall_rooms(**rooms)
-    if limit:
-        d.set_time_limit(limit)
-    rng = np.random.default_rng(seed)
-    for _ in range(steps):
-        d.step(WR.draw_actions(rng, d.B))
-
-
-walk_into_the_goal = BC.walk_into_the_goal
-
-
-def walk_and_step(d, every, seed, steps=3):
-    walk_into_the_goal(d, (np.arange(d.B) % every == 0).astype(np.uint8))
-    rng = np.random.default_rng(seed)
-    for _ in range(steps):
-        d.step(WR.draw_actions(rng, d.B))
+rollout = functools.partial(WF.rollout, "rooms")
+walk_into_the_goal = WF.walk_into_the_goal
+walk_and_step = WF.walk_and_step
 
 
 def tiny(d):
@@ -184,22 +112,47 @@ SCENARIOS = dict(tiny=(tiny, TINY), square=(square, SQUARE), square64=(square, S
                  features=(features, CALLS), calls=(calls, CALLS))
 
 
-@functools.lru_cache(maxsize=None)
-def recorded(name, render=True, offset=0, batch=None):
-    """the reference's run of a scenario, computed once: (snapshots, events)"""
-    fn, c = SCENARIOS[name]
-    c = dict(c, B=batch) if batch is not None else c
-    rec = Recorder(c, render, agent_id_offset=offset)
-    fn(rec)
-    return rec.snaps, rec.events
+recorded = functools.partial(WF.recorded, "rooms")                                  # (name, render=True, offset=0, batch=None) -> (snapshots, events), cached
+play = functools.partial(WF.play, "rooms")                                          # (rcw, name, env, trackers=(), wrap=None) -> events
 
 
-def play(rcw, name, env, trackers=(), wrap=None):
-    """the scenario on `env` against its recording; trackers: the feature trackers, made once the engine exists"""
-    fn, _ = SCENARIOS[name]
-    snaps, events = recorded(name)
-    p = Player(rcw, env, snaps, name)
-    p.trackers = list(trackers)
-    fn(p if wrap is None else wrap(p))                                       # (wrap: tests/deferred.py takes a note behind every call)
-    p.finished()
-    return events
+# ---- what tests/test_gpu_wall_families.py plays of this family: the arguments of the tests every family has ------------------------------------
+ROLLOUTS = [("tiny", "two-launches"), ("tiny", "one-launch"), ("square", None), ("square64", None), ("doors", None), ("wide", None), ("levels", None),
+            ("calls", "two-launches"), ("calls", "one-launch")]
+REPLAYED = (dict(LEVELS, B=21), (dict(room=1, stop=0.1, doors=0.6), dict(levels=5, first_level=3, level_seed=8)))
+BESIDE_A_PLAIN_HANDLE = dict(room=1)
+UNTOUCHED = dict(room=1, levels=3, first_level=1, level_seed=2)
+CAPTURED = (dict(CALLS, B=12), dict(room=1, stop=0.25, doors=0.5))
+SHARDED = (12, dict(room=1, stop=0.2, doors=0.5, levels=6, first_level=40, level_seed=9), (2, 0.5, 0))    # (the map's width, the install, other parameters without levels)
+REFUSED_MAPS = [(4, 9, ValueError, "at least 5 x 5"), (9, 4, ValueError, "at least 5 x 5"),
+                (131, 131, "unsupported", "at most 4096"), (130, 131, "unsupported", "at most 4096")]
+NAMED = {(131, 131): ("130 x 130", "4225"), (130, 131): ("130 x 130", "4160")}  # Q past the bound: the message names the bound and Q
+FUZZ = ("rooms", "wall rooms:", ("step", "reset", "masked_reset", "set_state", "arrive", "off_and_on", "episode_starts", "rooms_made", "second_doors", "goal_redraws",
+                                 "restarts_after_done", "restarts_after_truncation", "one_launch_steps", "two_launch_steps", "non_square", "with_levels", "stopped",
+                                 "rooms_past_64"))
+
+
+def reached(events, name=None):
+    """what the reference's counts must show of a run (of scenario `name`) beyond restarts: the root is always cut, so more rooms than layouts"""
+    assert events["rooms_made"] > events["episode_starts"]
+    if name == "doors":
+        assert events["second_doors"] > events["episode_starts"]
+
+
+def check_rollout(rcw, env, name):
+    """what holds of the engine behind scenario `name`"""
+    c = SCENARIOS[name][1]
+    walls, layout = env.world.walls, env.wall_layout.numpy()
+    if name == "square64":
+        assert env.world.player_position_wu.dtype == np.float64
+    if name == "tiny":
+        assert (layout == -1).all() and ((~walls).sum(axis=(1, 2)) == 7).all() and len({w.tobytes() for w in walls}) == 4   # the four layouts
+    elif name == "levels":
+        assert set(layout.tolist()) == {43, 44, 45} and min(np.bincount(layout - 43)) > 5
+        for level in (43, 44, 45):                                            # every level held by several agents, one layout a level
+            held = walls[layout == level]
+            assert (held == held[0]).all()
+            want = rcw.layouts.generated_rooms(rcw.layouts.generated_maze_key(0, 0, 0, 1, level, 9)[0], c["H"], c["W"], 1)
+            np.testing.assert_array_equal(held[0], want)
+    else:
+        assert (layout == -1).all()

@@ -20,13 +20,13 @@ THE KEY OF AN EPISODE is the generator's (wall_generator_ref.maze_key), and afte
 
 `rooms` is the rule by recursion.  `rounds` restates the kernel's traversal (csrc/rcw_wall_bank.hip, rcw_wall_rooms_kernel's header): a
 list of chambers, every live one cut once a round, one child in its place and the other appended; it returns the layout, the number of
-rounds and the most chambers a round handled.  WallRoomsRef is WallsRef with the one override of _reset_agent, as WallCavesRef is.
+rounds and the most chambers a round handled.  The reference that applies the rule is wall_family.WallFamilyRef; its `events` count
+rooms_made and second_doors (walls with two distinct doors).
 """
 import numpy as np
 
 import wall_generator_ref as WG
 import walls_ref as WR
-from oracle import pyref
 
 ROOMS_DRAW = 1 << 61
 MAX_ROOMS = 4096
@@ -144,65 +144,3 @@ def install_refusal(H, W, room, levels, first_level):
     if H < 5 or W < 5 or room < 1 or levels < 0 or first_level < 0 or first_level + levels > 2 ** 31 - 1:
         return "invalid"
     return "unsupported" if bound(H, W) > MAX_ROOMS or H * W > MAX_TILES else None
-
-
-class WallRoomsRef(WR.WallsRef):
-    def __init__(self, *args, **kw):
-        self.gen = None
-        super().__init__(*args, **kw)
-        self.wall_layout = np.zeros(self.B, np.int32)
-        self.events.update(episode_starts=0, rooms_made=0, second_doors=0)
-        self.keys_made = set()
-        self._cache = {}
-
-    # ---- the rule ------------------------------------------------------------------------------------------------------------------
-    def _reset_agent(self, b):
-        if self.gen is not None:
-            room, stop, doors, levels, first_level, level_seed = self.gen
-            m, level = WG.maze_key(self.seed, self.offset + b, int(self.episode[b]), levels, first_level, level_seed)
-            if m not in self._cache:
-                walls, leaves, cuts, _ = rooms(m, self.H, self.W, room, stop, doors, details=True)
-                self._cache[m] = (walls, len(leaves), sum(len(c[2]) == 2 and c[2][0] != c[2][1] for c in cuts))
-            walls, made, second = self._cache[m]
-            tm = self.worlds[b].tile_map
-            for i in range(1, self.H + 1):
-                for j in range(1, self.W + 1):
-                    tm[pyref.WALL][i][j] = bool(walls[i - 1, j - 1])
-                    tm[pyref.GOAL][i][j] = False
-            self.events["episode_starts"] += 1
-            self.events["rooms_made"] += made
-            self.events["second_doors"] += second
-            self.keys_made.add(m)
-            self.wall_layout[b] = level
-        super()._reset_agent(b)
-
-    # ---- the calls -----------------------------------------------------------------------------------------------------------------
-    def set_wall_rooms(self, room=DEFAULT_ROOM, stop=DEFAULT_STOP, doors=DEFAULT_DOORS, levels=0, first_level=0, level_seed=0):
-        """rcw_set_wall_rooms: install (every agent restarts under the rule with the current seed) or, room None, switch off (walls kept).
-        stop, doors: a probability (float) or the UInt32 word (int)."""
-        if room is None:
-            self.gen = None
-            return
-        assert install_refusal(self.H, self.W, room, levels, first_level) is None
-        as_word = lambda p: int(p) if isinstance(p, (int, np.integer)) else word(p)
-        self.gen = (int(room), as_word(stop), as_word(doors), int(levels), int(first_level), int(level_seed))
-        self._cache = {}
-        self.reset()
-
-    def set_walls(self, walls, index=None, mask=None):
-        if self.gen is not None:
-            raise RuntimeError("rcw_set_walls is refused while the handle makes rooms")
-        super().set_walls(walls, index, mask)
-
-    def snapshot(self):
-        return dict(super().snapshot(), wall_layout=self.wall_layout.copy())
-
-
-def assert_equal(env, ref, where=""):
-    """walls_ref.assert_equal plus wall_layout (while the reference makes rooms: without them the engine refuses the getter)"""
-    r = ref if isinstance(ref, dict) else ref.snapshot()
-    WR.assert_equal(env, r, where)
-    if env.wall_rooms_info["enabled"]:
-        got = env.wall_layout.numpy()
-        assert got.dtype == np.int32
-        np.testing.assert_array_equal(got, r["wall_layout"], err_msg=f"wall_layout {where}")

@@ -18,15 +18,10 @@ height, world-unit type, the three unpinned switches, both BoundsError policies,
                                                                    # "bank": the wall bank (rcw_set_wall_bank) — random maps, banks, weights and
                                                                    #         sequences of calls against tests/wall_bank_ref.py, the whole state, the
                                                                    #         frames and wall_layout compared after every call (bank_mode below)
-                                                                   # "gen": the wall generator (rcw_set_wall_generator) — random maps, loops, level
-                                                                   #         ranges and sequences of calls against tests/wall_generator_ref.py, compared
-                                                                   #         the same way (gen_mode below)
-                                                                   # "caves": the caves (rcw_set_wall_caves) — random maps, fills, smoothing counts,
-                                                                   #         level ranges and sequences of calls against tests/wall_caves_ref.py,
-                                                                   #         compared the same way (caves_mode below)
-                                                                   # "rooms": the rooms (rcw_set_wall_rooms) — random maps, room sides, stop and door
-                                                                   #         probabilities, level ranges and sequences of calls against
-                                                                   #         tests/wall_rooms_ref.py, compared the same way (rooms_mode below)
+                                                                   # "gen", "caves", "rooms": a family of the wall generator
+                                                                   #         (rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms) — random maps,
+                                                                   #         the family's parameters, level ranges and sequences of calls against
+                                                                   #         tests/wall_family.py's reference, compared the same way (family_mode below)
 """
 import os
 import sys
@@ -254,21 +249,63 @@ def bank_mode(n_cfg, seed):
     return 1 if fails else 0
 
 
-def gen_mode(n_cfg, seed):
-    """Maps of 5 x 5 to 40 x 40 tiles (up to 19 x 19 = 361 cells); loops 0, 0.1, 0.5 or 1; no levels, or 1, 2 or 5 levels from a random first
-    level under a random level seed; 1 to 9 agents with 8 or 16 view columns (the reference renders in Python), Float32 and Float64, both
-    forms of the step asked for, a time limit of 0, 2 or 5, auto_reset.  Then 30 random calls — a step, a masked or full reset_ with a new
-    seed, a masked set_state onto free tiles of each agent's current maze, the generator off and another one on —, each made on the
-    reference (tests/wall_generator_cases.py's Recorder) and on the engine (its Player), which compares the whole state, the frames, the
-    time limit's words and wall_layout after every call.  Every configuration draws from default_rng([seed, c])."""
-    import wall_generator_cases as GC
+# ---- the wall generator's families: what each one contributes to family_mode ---------------------------------------------------------------------
+def _draw_generator(rng):
+    """loops 0, 0.1, 0.5 or 1"""
+    return dict(loops=float(rng.choice([0.0, 0.0, 0.1, 0.5, 1.0])))
+
+
+def _draw_caves(rng):
+    """fill 0.2 .. 0.6 (now and then 0 or all wall), smoothed 0 .. 8 times"""
+    fill = [0.2, 0.3, 0.4, 0.4, 0.45, 0.5, 0.6, 0.0, 1.0][int(rng.integers(0, 9))]
+    return dict(fill=fill, smooth=int(rng.integers(0, 9)))
+
+
+def _draw_rooms(rng):
+    """a least room side of 1 .. 4, stop 0 .. 0.5 (now and then always), a second door with probability 0 .. 1"""
+    stop = [0.0, 0.0, 0.1, 0.25, 0.25, 0.5, 1.0][int(rng.integers(0, 7))]
+    doors = [0.0, 0.25, 0.25, 0.5, 1.0][int(rng.integers(0, 5))]
+    return dict(room=int(rng.integers(1, 5)), stop=stop, doors=doors)
+
+
+# mode -> the row of tests/wall_family.py, the closing line's label, the parameter draw, the calls beside step / reset / set_state, the totals
+# behind the calls' own (the reference's events, then what is counted of a map and of an install), and how those are counted
+FUZZ_FAMILIES = dict(
+    gen=dict(family="generator", label="wall generator", draw=_draw_generator, calls=("off_and_on",), events=("episode_starts",),
+             counts=("even_sizes", "with_levels", "with_loops", "cells_past_64"),
+             of_map=lambda H, W: dict(even_sizes=H % 2 == 0 or W % 2 == 0, cells_past_64=((H - 1) // 2) * ((W - 1) // 2) > 64),
+             of_install=lambda g: dict(with_loops=g["loops"] > 0), of_events=lambda ev: {}),
+    caves=dict(family="caves", label="wall caves", draw=_draw_caves, calls=("arrive", "off_and_on"), events=("episode_starts", "fallbacks", "caves_kept"),
+               counts=("non_square", "with_levels", "smoothed", "tiles_past_64"),
+               of_map=lambda H, W: dict(non_square=H != W, tiles_past_64=(H - 2) * (W - 2) > 64),
+               of_install=lambda g: dict(smoothed=g["smooth"] > 0), of_events=lambda ev: dict(caves_kept=ev["episode_starts"] - ev["fallbacks"])),
+    rooms=dict(family="rooms", label="wall rooms", draw=_draw_rooms, calls=("arrive", "off_and_on"), events=("episode_starts", "rooms_made", "second_doors"),
+               counts=("non_square", "with_levels", "stopped", "rooms_past_64"),                       # (rooms_past_64: more (odd, odd) tiles than a wavefront has lanes)
+               of_map=lambda H, W: dict(non_square=H != W, rooms_past_64=-(-(H - 2) // 2) * -(-(W - 2) // 2) > 64),
+               of_install=lambda g: dict(stopped=g["stop"] > 0), of_events=lambda ev: {}),
+)
+
+
+def family_mode(mode, n_cfg, seed):
+    """One family of the wall generator (FUZZ_FAMILIES[mode]): maps of 5 x 5 to 40 x 40 tiles, a quarter of them 5 .. 8 on a side; the family's
+    own parameters by its draw; no levels, or 1, 2 or 5 levels from a random first level under a random level seed; 1 to 9 agents with 8 or 16
+    view columns (the reference renders in Python), Float32 and Float64, both forms of the step asked for, a time limit of 0, 2 or 5,
+    auto_reset.  Then 30 random calls — a step, a masked or full reset_ with a new seed, a masked set_state onto free tiles of each agent's
+    current layout, for caves and rooms some agents walked into their goals (wall_bank_cases.walk_into_the_goal: in open layouts a random walk
+    rarely arrives), the family off and other parameters on —, each made on the reference (tests/wall_family.py's Recorder) and on the
+    engine (its Player), which compares the whole state, the frames, the time limit's words and wall_layout after every call.  Every
+    configuration draws from default_rng([seed, c])."""
+    import wall_family as WF
     from raycastworlds_jl_amd import _capi
 
+    fam = FUZZ_FAMILIES[mode]
+    setter = WF.FAMILIES[fam["family"]].setter
+    Recorder, Player = WF.drivers(fam["family"])
     rng = None
 
-    def generator():
+    def parameters():
         levels = int(rng.choice([0, 0, 1, 2, 5]))
-        return dict(loops=float(rng.choice([0.0, 0.0, 0.1, 0.5, 1.0])), levels=levels, first_level=int(rng.integers(0, 2**31 - 1 - levels)) if levels else 0,
+        return dict(fam["draw"](rng), levels=levels, first_level=int(rng.integers(0, 2**31 - 1 - levels)) if levels else 0,
                     level_seed=int(rng.integers(0, 2**63)) if levels else 0)
 
     def some(B):
@@ -276,8 +313,12 @@ def gen_mode(n_cfg, seed):
         mask[int(rng.integers(0, B))] = 1
         return mask
 
-    totals = dict(step=0, reset=0, masked_reset=0, set_state=0, off_and_on=0, episode_starts=0, goal_redraws=0, restarts_after_done=0,
-                  restarts_after_truncation=0, one_launch_steps=0, two_launch_steps=0, even_sizes=0, with_levels=0, with_loops=0, cells_past_64=0)
+    def count(found):
+        for k, v in found.items():
+            totals[k] += int(v)
+
+    totals = dict.fromkeys(("step", "reset", "masked_reset", "set_state") + fam["calls"] + fam["events"] + ("goal_redraws", "restarts_after_done",
+                           "restarts_after_truncation", "one_launch_steps", "two_launch_steps") + fam["counts"], 0)
     fails = 0
     for c in range(n_cfg):
         rng = np.random.default_rng([seed, c])
@@ -292,234 +333,28 @@ def gen_mode(n_cfg, seed):
         shape = dict(H=H, W=W, N=N, Hc=Hc, B=B, seed=engine_seed, T="Float64" if T64 else "Float32")
         where = f"config {c}: {H} x {W}, B={B} T64={T64} L={L} N={N} Hc={Hc} {form} seed={engine_seed}"
         try:
-            env = GC.make_env(RCW, shape)
+            env = WF.make_env(RCW, shape)
             try:
                 env.set_step_form(form)
             except _capi.RcwError as e:
                 assert form == "one-launch" and e.code == _capi.RCW_ERR_UNSUPPORTED and "does not take the one-launch step" in e.message, e
                 form = "two-launches"
             totals["one_launch_steps" if form == "one-launch" else "two_launch_steps"] += 1
-            totals["even_sizes"] += int(H % 2 == 0 or W % 2 == 0)
-            totals["cells_past_64"] += int(((H - 1) // 2) * ((W - 1) // 2) > 64)
-            rec = GC.Recorder(shape)
-            play = GC.Player(RCW, env, rec.snaps, where)
+            count(fam["of_map"](H, W))
+            rec = Recorder(shape)
+            play = Player(RCW, env, rec.snaps, where)
             both = lambda call, *a, **k: (getattr(rec, call)(*a, **k), getattr(play, call)(*a, **k))
             if L:
                 both("set_time_limit", L)
 
             def install():
-                g = generator()
-                totals["with_levels"] += int(g["levels"] > 0)
-                totals["with_loops"] += int(g["loops"] > 0)
-                both("set_wall_generator", **g)
+                g = parameters()
+                count(dict(fam["of_install"](g), with_levels=g["levels"] > 0))
+                both(setter, **g)
 
             install()
             for k in range(30):
-                call = str(rng.choice(["step", "step", "step", "step", "step", "step", "reset", "masked_reset", "set_state", "off_and_on"]))
-                play.name = f"{where}, call {k} ({call})"
-                totals[call] += 1
-                if call == "step":
-                    both("step", rng.integers(1, 5, B).astype(np.uint8))
-                elif call in ("reset", "masked_reset"):
-                    both("reset", some(B) if call == "masked_reset" else None, int(rng.integers(0, 2**31)))
-                elif call == "set_state":
-                    mask, s = some(B), rec.snaps[-1]
-                    goal, pos, heading = s["goal"].copy(), s["position"].copy(), s["direction"].copy()
-                    for b in np.flatnonzero(mask):
-                        free = np.argwhere(~rec.ref.walls_of(b))
-                        goal[b] = free[int(rng.integers(0, len(free)))] + 1
-                        pos[b] = free[int(rng.integers(0, len(free)))] + 0.5
-                        heading[b] = int(rng.integers(0, 8))
-                    both("set_state", goal, pos, heading, mask)
-                else:
-                    both("set_wall_generator", None)
-                    both("step", rng.integers(1, 5, B).astype(np.uint8))
-                    install()
-            play.finished()
-            for k, v in rec.events.items():
-                if k in totals:
-                    totals[k] += v
-            env.close()
-        except Exception as e:   # noqa: BLE001
-            fails += 1
-            print(f"{where} FAILED\n   {type(e).__name__}: {str(e)[:400]}")
-            if fails >= 5:
-                break
-    print(f"{n_cfg} random configurations (wall generator: " + ", ".join(f"{v} {k}" for k, v in totals.items()) + f"), {fails} mismatches")
-    return 1 if fails else 0
-
-
-def caves_mode(n_cfg, seed):
-    """gen_mode's draw for the caves: maps of 5 x 5 to 40 x 40 tiles (up to 38 x 38 = 1444 interior tiles); fill 0.2 .. 0.6 (now and then 0
-    or all wall), smoothed 0 .. 8 times; no levels, or 1, 2 or 5; 1 to 9 agents with 8 or 16 view columns, Float32 and Float64, both forms
-    of the step asked for, a time limit of 0, 2 or 5, auto_reset.  Then 30 random calls — a step, a masked or full reset_ with a new seed, a
-    masked set_state onto free tiles of each agent's current layout, some agents walked into their goals (wall_bank_cases.
-    walk_into_the_goal: in open caves a random walk rarely arrives), the caves off and others on —, each made on the reference
-    (tests/wall_caves_cases.py's Recorder) and on the engine (its Player), which compares the whole state, the frames, the time limit's
-    words and wall_layout after every call.  Every configuration draws from default_rng([seed, c])."""
-    import wall_caves_cases as CC
-    from raycastworlds_jl_amd import _capi
-
-    rng = None
-
-    def caves():
-        levels = int(rng.choice([0, 0, 1, 2, 5]))
-        fill = [0.2, 0.3, 0.4, 0.4, 0.45, 0.5, 0.6, 0.0, 1.0][int(rng.integers(0, 9))]
-        return dict(fill=fill, smooth=int(rng.integers(0, 9)), levels=levels, first_level=int(rng.integers(0, 2**31 - 1 - levels)) if levels else 0,
-                    level_seed=int(rng.integers(0, 2**63)) if levels else 0)
-
-    def some(B):
-        mask = (rng.random(B) < 0.5).astype(np.uint8)
-        mask[int(rng.integers(0, B))] = 1
-        return mask
-
-    totals = dict(step=0, reset=0, masked_reset=0, set_state=0, arrive=0, off_and_on=0, episode_starts=0, fallbacks=0, caves_kept=0, goal_redraws=0,
-                  restarts_after_done=0, restarts_after_truncation=0, one_launch_steps=0, two_launch_steps=0, non_square=0, with_levels=0,
-                  smoothed=0, tiles_past_64=0)
-    fails = 0
-    for c in range(n_cfg):
-        rng = np.random.default_rng([seed, c])
-        H, W = int(rng.integers(5, 41)), int(rng.integers(5, 41))
-        if c % 4 == 0:
-            H, W = int(rng.integers(5, 9)), int(rng.integers(5, 9))          # (a quarter small: agents arrive, restarts after done)
-        B = int(rng.integers(1, 10))
-        T64, L = bool(rng.integers(0, 2)), int(rng.choice([0, 2, 5]))
-        N, Hc = [(8, 64), (16, 64), (8, 24), (16, 128)][int(rng.integers(0, 4))]
-        form = str(rng.choice(["one-launch", "two-launches"]))
-        engine_seed = int(rng.integers(0, 2**31))
-        shape = dict(H=H, W=W, N=N, Hc=Hc, B=B, seed=engine_seed, T="Float64" if T64 else "Float32")
-        where = f"config {c}: {H} x {W}, B={B} T64={T64} L={L} N={N} Hc={Hc} {form} seed={engine_seed}"
-        try:
-            env = CC.make_env(RCW, shape)
-            try:
-                env.set_step_form(form)
-            except _capi.RcwError as e:
-                assert form == "one-launch" and e.code == _capi.RCW_ERR_UNSUPPORTED and "does not take the one-launch step" in e.message, e
-                form = "two-launches"
-            totals["one_launch_steps" if form == "one-launch" else "two_launch_steps"] += 1
-            totals["non_square"] += int(H != W)
-            totals["tiles_past_64"] += int((H - 2) * (W - 2) > 64)
-            rec = CC.Recorder(shape)
-            play = CC.Player(RCW, env, rec.snaps, where)
-            both = lambda call, *a, **k: (getattr(rec, call)(*a, **k), getattr(play, call)(*a, **k))
-            if L:
-                both("set_time_limit", L)
-
-            def install():
-                g = caves()
-                totals["with_levels"] += int(g["levels"] > 0)
-                totals["smoothed"] += int(g["smooth"] > 0)
-                both("set_wall_caves", **g)
-
-            install()
-            for k in range(30):
-                call = str(rng.choice(["step", "step", "step", "step", "step", "step", "reset", "masked_reset", "set_state", "arrive", "off_and_on"]))
-                play.name = f"{where}, call {k} ({call})"
-                totals[call] += 1
-                if call == "step":
-                    both("step", rng.integers(1, 5, B).astype(np.uint8))
-                elif call in ("reset", "masked_reset"):
-                    both("reset", some(B) if call == "masked_reset" else None, int(rng.integers(0, 2**31)))
-                elif call == "set_state":
-                    mask, s = some(B), rec.snaps[-1]
-                    goal, pos, heading = s["goal"].copy(), s["position"].copy(), s["direction"].copy()
-                    for b in np.flatnonzero(mask):
-                        free = np.argwhere(~rec.ref.walls_of(b))
-                        goal[b] = free[int(rng.integers(0, len(free)))] + 1
-                        pos[b] = free[int(rng.integers(0, len(free)))] + 0.5
-                        heading[b] = int(rng.integers(0, 8))
-                    both("set_state", goal, pos, heading, mask)
-                elif call == "arrive":
-                    mask = some(B)
-                    for b in np.flatnonzero(mask):                           # (a region in one row has no tile to walk down from)
-                        free = ~rec.ref.walls_of(b)
-                        mask[b] = int((free[:-1] & free[1:]).any())
-                    CC.walk_into_the_goal(rec, mask)
-                    CC.walk_into_the_goal(play, mask)
-                else:
-                    both("set_wall_caves", None)
-                    both("step", rng.integers(1, 5, B).astype(np.uint8))
-                    install()
-            play.finished()
-            for k, v in rec.events.items():
-                if k in totals:
-                    totals[k] += v
-            totals["caves_kept"] += rec.events["episode_starts"] - rec.events["fallbacks"]
-            env.close()
-        except Exception as e:   # noqa: BLE001
-            fails += 1
-            print(f"{where} FAILED\n   {type(e).__name__}: {str(e)[:400]}")
-            if fails >= 5:
-                break
-    print(f"{n_cfg} random configurations (wall caves: " + ", ".join(f"{v} {k}" for k, v in totals.items()) + f"), {fails} mismatches")
-    return 1 if fails else 0
-
-
-def rooms_mode(n_cfg, seed):
-    """caves_mode's draw for the rooms: maps of 5 x 5 to 40 x 40 tiles; a least room side of 1 .. 4, stop 0 .. 0.5 (now and then always), a
-    second door with probability 0 .. 1; no levels, or 1, 2 or 5; 1 to 9 agents with 8 or 16 view columns, Float32 and Float64, both forms
-    of the step asked for, a time limit of 0, 2 or 5, auto_reset.  Then 30 random calls — a step, a masked or full reset_ with a new seed, a
-    masked set_state onto free tiles of each agent's current layout, some agents walked into their goals (wall_bank_cases.
-    walk_into_the_goal), the rooms off and others on —, each made on the reference (tests/wall_rooms_cases.py's Recorder) and on the engine
-    (its Player), which compares the whole state, the frames, the time limit's words and wall_layout after every call.  Every configuration
-    draws from default_rng([seed, c])."""
-    import wall_rooms_cases as RC
-    from raycastworlds_jl_amd import _capi
-
-    rng = None
-
-    def rooms():
-        levels = int(rng.choice([0, 0, 1, 2, 5]))
-        stop = [0.0, 0.0, 0.1, 0.25, 0.25, 0.5, 1.0][int(rng.integers(0, 7))]
-        doors = [0.0, 0.25, 0.25, 0.5, 1.0][int(rng.integers(0, 5))]
-        return dict(room=int(rng.integers(1, 5)), stop=stop, doors=doors, levels=levels, first_level=int(rng.integers(0, 2**31 - 1 - levels)) if levels else 0,
-                    level_seed=int(rng.integers(0, 2**63)) if levels else 0)
-
-    def some(B):
-        mask = (rng.random(B) < 0.5).astype(np.uint8)
-        mask[int(rng.integers(0, B))] = 1
-        return mask
-
-    totals = dict(step=0, reset=0, masked_reset=0, set_state=0, arrive=0, off_and_on=0, episode_starts=0, rooms_made=0, second_doors=0, goal_redraws=0,
-                  restarts_after_done=0, restarts_after_truncation=0, one_launch_steps=0, two_launch_steps=0, non_square=0, with_levels=0,
-                  stopped=0, rooms_past_64=0)
-    fails = 0
-    for c in range(n_cfg):
-        rng = np.random.default_rng([seed, c])
-        H, W = int(rng.integers(5, 41)), int(rng.integers(5, 41))
-        if c % 4 == 0:
-            H, W = int(rng.integers(5, 9)), int(rng.integers(5, 9))          # (a quarter small: agents arrive, restarts after done)
-        B = int(rng.integers(1, 10))
-        T64, L = bool(rng.integers(0, 2)), int(rng.choice([0, 2, 5]))
-        N, Hc = [(8, 64), (16, 64), (8, 24), (16, 128)][int(rng.integers(0, 4))]
-        form = str(rng.choice(["one-launch", "two-launches"]))
-        engine_seed = int(rng.integers(0, 2**31))
-        shape = dict(H=H, W=W, N=N, Hc=Hc, B=B, seed=engine_seed, T="Float64" if T64 else "Float32")
-        where = f"config {c}: {H} x {W}, B={B} T64={T64} L={L} N={N} Hc={Hc} {form} seed={engine_seed}"
-        try:
-            env = RC.make_env(RCW, shape)
-            try:
-                env.set_step_form(form)
-            except _capi.RcwError as e:
-                assert form == "one-launch" and e.code == _capi.RCW_ERR_UNSUPPORTED and "does not take the one-launch step" in e.message, e
-                form = "two-launches"
-            totals["one_launch_steps" if form == "one-launch" else "two_launch_steps"] += 1
-            totals["non_square"] += int(H != W)
-            rec = RC.Recorder(shape)
-            play = RC.Player(RCW, env, rec.snaps, where)
-            both = lambda call, *a, **k: (getattr(rec, call)(*a, **k), getattr(play, call)(*a, **k))
-            if L:
-                both("set_time_limit", L)
-
-            def install():
-                g = rooms()
-                totals["with_levels"] += int(g["levels"] > 0)
-                totals["stopped"] += int(g["stop"] > 0)
-                both("set_wall_rooms", **g)
-
-            install()
-            for k in range(30):
-                call = str(rng.choice(["step", "step", "step", "step", "step", "step", "reset", "masked_reset", "set_state", "arrive", "off_and_on"]))
+                call = str(rng.choice(["step", "step", "step", "step", "step", "step", "reset", "masked_reset", "set_state"] + list(fam["calls"])))
                 play.name = f"{where}, call {k} ({call})"
                 totals[call] += 1
                 if call == "step":
@@ -540,24 +375,22 @@ def rooms_mode(n_cfg, seed):
                     for b in np.flatnonzero(mask):                           # (free tiles in one row have no tile to walk down from)
                         free = ~rec.ref.walls_of(b)
                         mask[b] = int((free[:-1] & free[1:]).any())
-                    RC.walk_into_the_goal(rec, mask)
-                    RC.walk_into_the_goal(play, mask)
+                    WF.walk_into_the_goal(rec, mask)
+                    WF.walk_into_the_goal(play, mask)
                 else:
-                    both("set_wall_rooms", None)
+                    both(setter, None)
                     both("step", rng.integers(1, 5, B).astype(np.uint8))
                     install()
             play.finished()
-            for k, v in rec.events.items():
-                if k in totals:
-                    totals[k] += v
-            totals["rooms_past_64"] += int(RC.RR.bound(H, W) > 64)             # (maps with more (odd, odd) tiles than a wavefront has lanes)
+            events = rec.events
+            count({k: v for k, v in dict(events, **fam["of_events"](events)).items() if k in totals})
             env.close()
         except Exception as e:   # noqa: BLE001
             fails += 1
             print(f"{where} FAILED\n   {type(e).__name__}: {str(e)[:400]}")
             if fails >= 5:
                 break
-    print(f"{n_cfg} random configurations (wall rooms: " + ", ".join(f"{v} {k}" for k, v in totals.items()) + f"), {fails} mismatches")
+    print(f"{n_cfg} random configurations ({fam['label']}: " + ", ".join(f"{v} {k}" for k, v in totals.items()) + f"), {fails} mismatches")
     return 1 if fails else 0
 
 
@@ -565,12 +398,8 @@ if len(sys.argv) > 3 and sys.argv[3] == "goal":
     sys.exit(goal_mode(n_cfg, int(sys.argv[2])))
 if len(sys.argv) > 3 and sys.argv[3] == "bank":
     sys.exit(bank_mode(n_cfg, int(sys.argv[2])))
-if len(sys.argv) > 3 and sys.argv[3] == "gen":
-    sys.exit(gen_mode(n_cfg, int(sys.argv[2])))
-if len(sys.argv) > 3 and sys.argv[3] == "caves":
-    sys.exit(caves_mode(n_cfg, int(sys.argv[2])))
-if len(sys.argv) > 3 and sys.argv[3] == "rooms":
-    sys.exit(rooms_mode(n_cfg, int(sys.argv[2])))
+if len(sys.argv) > 3 and sys.argv[3] in FUZZ_FAMILIES:
+    sys.exit(family_mode(sys.argv[3], n_cfg, int(sys.argv[2])))
 limit_events = {}
 one_launch_steps = 0
 two_kernel_forms = 0                                            # (rcw_set_top_view_form: by default it is taken only from 256 MiB a step)

@@ -1,21 +1,29 @@
-"""Env-steps/s with the wall generator beside the wall bank, in tools/wall_bank_bench.py's form: device-resident U{1..4} actions, HIP events
-on the engine's stream around `--steps` steps after `--warmup`.  Each case runs `--repeats` times (interleaved, so drift hits every case
-alike); the JSON carries every run, the median and the range; the text file the table DESIGN.md quotes.
+"""Env-steps/s with the wall generator's families — mazes, caves, rooms — beside the case without any and beside each other: device-resident
+U{1..4} actions, HIP events on the engine's stream around `--steps` steps after `--warmup`.  Each case runs `--repeats` times (interleaved,
+so drift hits every case alike); the JSON carries every run, the median and the range; the text file the table DESIGN.md quotes.
 
-    python tools/wall_generator_bench.py --repeats 5 [--out profiles/wall_generator_bench]      # writes <out>.json and <out>.txt
+    python tools/wall_family_bench.py --family caves rooms --repeats 5 [--out profiles/wall_rooms_bench]      # writes <out>.json and <out>.txt
+
+`--family` (any of generator, caves, rooms; default: all) selects the cases: the two without a family always, then per family its own two
+and its yardstick's.  `--family generator`, `--family caves` and `--family caves rooms` write the keys of profiles/wall_generator_bench.json,
+wall_caves_bench.json and wall_rooms_bench.json.
 
 Cases, all under auto_reset:
   at cfg-5's geometry (32x32 map, 1024 view columns, --maze-batch agents) under a time limit of --limit steps, warmed up past it
-    maze                 a maze of its own for every agent through set_walls: no bank, every episode on the same maze
-    maze_bank            a bank of --maze-batch mazes, uniform: a new maze per episode, drawn on the device from a finite set
+    maze                 a maze of its own for every agent through set_walls: no source of layouts, every episode on the same maze
+    maze_bank            (generator) a bank of --maze-batch mazes, uniform: a new maze per episode, drawn on the device from a finite set
     maze_generator       the wall generator: a new maze per episode, made on the device (15 x 15 = 225 cells)
+    caves                the caves at the defaults: a new cave per episode (30 x 30 = 900 interior tiles; none falls back)
+    rooms                the rooms at the defaults: new rooms per episode (Q = 15 x 15 = 225 chambers at the most)
   at BASELINE cfg-2 (8x8 map, 256 view columns, --batch agents)
-    four_rooms           layouts.four_rooms for every agent through set_walls: neither (what the two below add is measured against it)
-    four_rooms_bank      a bank of two layouts (four rooms | two pillars), uniform
+    four_rooms           layouts.four_rooms for every agent through set_walls: no source of layouts
+    four_rooms_bank      (generator) a bank of two layouts (four rooms | two pillars), uniform
     generator_8x8        the wall generator (3 x 3 = 9 cells)
-The yardstick is the bank on the same box: what the generator adds to a step over the case without either, beside what the bank adds.
-The installing call (every agent restarts: the bank copies a layout each, the generator makes a maze each) is timed too, HIP events around
---install-repeats calls on a warm handle.
+    caves_8x8            the caves at the defaults (36 interior tiles; about a quarter fall back to the maze)
+    rooms_8x8            the rooms at the defaults (room 2: line 4 alone in each direction, two to four rooms)
+The yardstick is run on the same box in the same call — the bank for the generator, the generator for caves and rooms: what a family adds
+to a step over the case without any, beside what its yardstick adds.  The installing call (every agent restarts: the bank copies a layout
+each, a family makes one each) is timed too, HIP events around --install-repeats calls on a warm handle.
 """
 import argparse
 import json
@@ -27,15 +35,24 @@ sys.path.insert(0, ROOT)
 
 CFG2 = dict(height_tile_map_tu=8, width_tile_map_tu=8, num_rays=256)
 CFG5 = dict(height_tile_map_tu=32, width_tile_map_tu=32, num_rays=1024)
-CASES = {
+CASES = {                                                                       # install: the setter called with its defaults
     "maze": dict(cfg=CFG5, big=True, walls="maze"),
     "maze_bank": dict(cfg=CFG5, big=True, bank="maze"),
-    "maze_generator": dict(cfg=CFG5, big=True, generator=True),
+    "maze_generator": dict(cfg=CFG5, big=True, install="set_wall_generator"),
+    "caves": dict(cfg=CFG5, big=True, install="set_wall_caves"),
+    "rooms": dict(cfg=CFG5, big=True, install="set_wall_rooms"),
     "four_rooms": dict(cfg=CFG2, walls="four_rooms"),
     "four_rooms_bank": dict(cfg=CFG2, bank="two"),
-    "generator_8x8": dict(cfg=CFG2, generator=True),
+    "generator_8x8": dict(cfg=CFG2, install="set_wall_generator"),
+    "caves_8x8": dict(cfg=CFG2, install="set_wall_caves"),
+    "rooms_8x8": dict(cfg=CFG2, install="set_wall_rooms"),
 }
-BASE = {"maze_bank": "maze", "maze_generator": "maze", "four_rooms_bank": "four_rooms", "generator_8x8": "four_rooms"}
+BASE = {"maze_bank": "maze", "maze_generator": "maze", "caves": "maze", "rooms": "maze",
+        "four_rooms_bank": "four_rooms", "generator_8x8": "four_rooms", "caves_8x8": "four_rooms", "rooms_8x8": "four_rooms"}
+# family -> its two cases, each with its yardstick (run beside it)
+FAMILIES = {"generator": (("maze_generator", "maze_bank"), ("generator_8x8", "four_rooms_bank")),
+            "caves": (("caves", "maze_generator"), ("caves_8x8", "generator_8x8")),
+            "rooms": (("rooms", "maze_generator"), ("rooms_8x8", "generator_8x8"))}
 
 
 def make_walls(RCW, np, kind, H, W, batch):
@@ -57,7 +74,7 @@ def run_case(RCW, torch, np, name, batch, steps, warmup, limit, actions, cache, 
     if kind is not None and (kind, batch) not in cache:
         cache[(kind, batch)] = make_walls(RCW, np, kind, H, W, batch)
     walls = cache.get((kind, batch))
-    install = (lambda: env.set_wall_generator()) if kw.get("generator") else (lambda: env.set_wall_bank(walls)) if "bank" in kw else None
+    install = getattr(env, kw["install"]) if "install" in kw else (lambda: env.set_wall_bank(walls)) if "bank" in kw else None
     if install is not None:
         install()
     else:
@@ -107,9 +124,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=220)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=4096)
-    ap.add_argument("--maze-batch", type=int, default=1024, help="agents (and bank layouts) of the three cfg-5 cases")
-    ap.add_argument("--limit", type=int, default=200, help="the time limit of the three cfg-5 cases")
+    ap.add_argument("--maze-batch", type=int, default=1024, help="agents (and bank layouts) of the cfg-5 cases")
+    ap.add_argument("--limit", type=int, default=200, help="the time limit of the cfg-5 cases")
     ap.add_argument("--install-repeats", type=int, default=3, help="installing calls timed per run (0: none)")
+    ap.add_argument("--family", nargs="+", choices=sorted(FAMILIES), default=sorted(FAMILIES), help="the families whose cases run (default: all)")
     ap.add_argument("--case", choices=sorted(CASES), default=None, help="run this case only (for a profiler)")
     ap.add_argument("--out", default=None, help="also write <out>.json and <out>.txt")
     args = ap.parse_args()
@@ -121,7 +139,9 @@ def main():
     g = torch.Generator().manual_seed(0)
     batches = {n: (args.maze_batch if CASES[n].get("big") else args.batch) for n in CASES}
     actions = {b: [torch.randint(1, 5, (b,), dtype=torch.uint8, generator=g).cuda() for _ in range(64)] for b in set(batches.values())}
-    names = [args.case] if args.case else list(CASES)
+    pairs = [pair for f in FAMILIES if f in args.family for pair in FAMILIES[f]]
+    wanted = {"maze", "four_rooms"} | {n for pair in pairs for n in pair}
+    names = [args.case] if args.case else [n for n in CASES if n in wanted]
     runs, installs = {n: [] for n in names}, {n: [] for n in names}
     forms, episodes, distinct, cache = {}, {}, {}, {}
     for _ in range(args.repeats):
@@ -131,8 +151,8 @@ def main():
             runs[n].append(batches[n] * args.steps / (ms / 1000.0))
             if ims is not None:
                 installs[n].append(ims)
-    out = {"metric": "env-steps/s", "config": "maze*: cfg-5: 32x32 map, 1024 view columns, "
-           f"time limit {args.limit}; four_rooms*, generator_8x8: cfg-2: 8x8 map, 256 view columns, 256 rows", "steps": args.steps, "warmup": args.warmup,
+    out = {"metric": "env-steps/s", "config": "maze*, caves, rooms: cfg-5: 32x32 map, 1024 view columns, "
+           f"time limit {args.limit}; four_rooms*, *_8x8: cfg-2: 8x8 map, 256 view columns, 256 rows", "families": sorted(args.family), "steps": args.steps, "warmup": args.warmup,
            "repeats": args.repeats, "cases": {}}
     for n in names:
         r = np.array(runs[n])
@@ -146,9 +166,11 @@ def main():
         if n in runs and base in runs:
             out[f"{n}_adds_us_per_step_over_{base}"] = us(n) - us(base)
             out[f"{n}_over_{base}"] = out["cases"][n]["median"] / out["cases"][base]["median"]
-    for gen, bank in (("maze_generator", "maze_bank"), ("generator_8x8", "four_rooms_bank")):
-        if gen in runs and bank in runs:
-            out[f"{gen}_over_{bank}"] = out["cases"][gen]["median"] / out["cases"][bank]["median"]
+    for own, yardstick in pairs:
+        if own in runs and yardstick in runs:
+            out[f"{own}_over_{yardstick}"] = out["cases"][own]["median"] / out["cases"][yardstick]["median"]
+            if BASE[yardstick] in runs and "bank" not in CASES[yardstick]:      # (the bank's tool never wrote this one)
+                out[f"{own}_adds_over_what_{yardstick}_adds"] = out[f"{own}_adds_us_per_step_over_{BASE[own]}"] / out[f"{yardstick}_adds_us_per_step_over_{BASE[yardstick]}"]
     print(json.dumps(out))
     lines = [out["config"], f"{args.steps} steps after {args.warmup}, {args.repeats} interleaved repeats; medians (range)", "",
              f"{'case':<18}{'agents':>7}{'M env-steps/s':>26}{'us a step':>22}{'adds us':>9}{'install ms':>12}{'layouts':>9}"]
