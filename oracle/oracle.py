@@ -130,6 +130,9 @@ def lib(bits: int = 32) -> C.CDLL:
         L.orc_set_direction_table.argtypes = [vp, vp]
         L.orc_step.argtypes = [vp, vp]
         L.orc_step_lenient.argtypes = [vp, vp]
+        L.orc_step_masked.argtypes = [vp, vp, vp]
+        L.orc_step_lenient_masked.argtypes = [vp, vp, vp]
+        L.orc_set_walls.argtypes = [vp, vp, C.c_int32, vp, vp]
         L.orc_clear_status.argtypes = [vp]
         L.orc_clear_status.restype = None
         L.orc_tile_map_chunks.argtypes = [vp, vp]
@@ -147,7 +150,7 @@ def lib(bits: int = 32) -> C.CDLL:
         L.orc_set_num_threads.restype = None
         for name in ("camera_view", "top_view", "reward", "done", "position", "direction", "goal", "episode",
                      "status", "ray_stop", "ray_dim", "ray_dist", "ray_dirs", "col_height",
-                     "col_colour", "directions", "ray_table"):
+                     "col_colour", "directions", "ray_table", "walls", "goal_redraws", "blocked_inner"):
             f = getattr(L, "orc_" + name)
             f.argtypes = [vp]
             f.restype = vp
@@ -218,14 +221,32 @@ class OracleBatch:
         d = np.ascontiguousarray(dirs, dtype=self.real).reshape(self.nd, 2)
         lib(self.bits).orc_set_direction_table(self._h, _p(d))
 
-    def step(self, actions) -> int:
-        a = np.ascontiguousarray(actions, dtype=np.uint8).reshape(self.B)
-        return lib(self.bits).orc_step(self._h, _p(a))
+    def set_walls(self, walls, index=None, mask=None):
+        """rcw_set_walls (include/rcw.h, "wall layouts"): walls bool (H, W) or (layouts, H, W), walls[m, i-1, j-1]; index Int32 (B) or
+        None (one layout: everybody's; B layouts: agent a's is layout a); the masked agents take their layout and are reset under the
+        batch's current seed.  A refusal raises ValueError and leaves the batch untouched."""
+        w = np.asarray(walls)
+        w = w[None] if w.ndim == 2 else w
+        if w.ndim != 3 or w.shape[1:] != (self.H, self.W):
+            raise ValueError(f"walls must be (H, W) or (layouts, H, W) with H, W = {self.H}, {self.W}; got {w.shape}")
+        flat = np.ascontiguousarray((w != 0).transpose(0, 2, 1), dtype=np.uint8)   # tile (i, j) of layout m at m H W + (i-1) + H (j-1)
+        ix = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(self.B)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.B)
+        rc = lib(self.bits).orc_set_walls(self._h, _p(flat) if len(flat) else None, len(flat), _p(ix), _p(m))
+        if rc:
+            raise ValueError(f"orc_set_walls: {rc}")
 
-    def step_lenient(self, actions) -> int:
-        """rcw_step_device semantics: agents with an invalid action are skipped, not rejected."""
+    def step(self, actions, moved=None) -> int:
+        """moved (None: everybody): the agents with a zero byte are left exactly as they are — not stepped, not restarted."""
         a = np.ascontiguousarray(actions, dtype=np.uint8).reshape(self.B)
-        return lib(self.bits).orc_step_lenient(self._h, _p(a))
+        m = None if moved is None else np.ascontiguousarray(moved, dtype=np.uint8).reshape(self.B)
+        return lib(self.bits).orc_step_masked(self._h, _p(a), _p(m))
+
+    def step_lenient(self, actions, moved=None) -> int:
+        """rcw_step_device semantics: agents with an invalid action are skipped, not rejected.  moved: as in step."""
+        a = np.ascontiguousarray(actions, dtype=np.uint8).reshape(self.B)
+        m = None if moved is None else np.ascontiguousarray(moved, dtype=np.uint8).reshape(self.B)
+        return lib(self.bits).orc_step_lenient_masked(self._h, _p(a), _p(m))
 
     def clear_status(self):
         lib(self.bits).orc_clear_status(self._h)
@@ -275,6 +296,21 @@ class OracleBatch:
     @property
     def status(self):
         return self._g("status", np.int32, (self.B,))
+
+    @property
+    def walls(self):
+        """the WALL layer, the ring included: bool (B, H, W), walls[b, i-1, j-1] (what set_walls takes)"""
+        return self._g("walls", np.uint8, (self.B, self.W, self.H)).transpose(0, 2, 1) != 0
+
+    @property
+    def goal_redraws(self):
+        """per agent: goal pairs drawn again because the pair before fell on a wall (since create)"""
+        return self._g("goal_redraws", np.uint64, (self.B,))
+
+    @property
+    def blocked_inner(self):
+        """per agent: moves refused because the player would touch a wall tile inside the ring, and no goal (since create)"""
+        return self._g("blocked_inner", np.uint64, (self.B,))
 
     @property
     def ray_stop(self):

@@ -23,6 +23,11 @@
  *
  * Layouts are the reference's column-major ones with a trailing batch axis
  * (include/rcw.h).
+ *
+ * INTERIOR WALLS are this build's addition, not the reference's (include/rcw.h, "wall layouts"): orc_set_walls writes a per-agent
+ * WALL layer and orc_reset_agent draws the goal pair again while it falls on a wall.  Both are restated from the header's text and
+ * from tests/walls_ref.py, never from csrc/, and are pinned to tests/walls_ref.py byte for byte (tests/test_oracle_walls.py).  On a
+ * ring-only map neither changes a draw.
  */
 #include <math.h>
 #include <stdint.h>
@@ -236,6 +241,9 @@ typedef struct orc_batch {
     int render;             /* 0: skip the pixel fill (descriptor only) */
     uint32_t* top_view;     /* (H*pu, W*pu, B) when cfg.render_top_view */
     int32_t Ht, Wt;
+    /* what a rollout exercised, per agent (each agent is one thread's), for tests that insist their scenario reached it */
+    uint64_t* goal_redraws;   /* (B) goal pairs drawn again because the pair before fell on a wall */
+    uint64_t* blocked_inner;  /* (B) moves refused because the player would touch a wall tile inside the ring (and no goal) */
 } orc_batch;
 
 ORC_EXPORT void orc_destroy(orc_batch* b)
@@ -245,6 +253,7 @@ ORC_EXPORT void orc_destroy(orc_batch* b)
     free(b->dir); free(b->goal); free(b->reward); free(b->done); free(b->episode);
     free(b->status); free(b->ray_stop); free(b->ray_dim); free(b->ray_dist);
     free(b->ray_dirs); free(b->camera_view); free(b->top_view); free(b->col_height); free(b->col_colour);
+    free(b->goal_redraws); free(b->blocked_inner);
     free(b);
 }
 
@@ -437,7 +446,8 @@ static void orc_set_reward(orc_batch* b, int32_t a, int goal)
     }
 }
 
-/* reset!(world)  SR:110-137 with the build's generator */
+/* reset!(world)  SR:110-137 with the build's generator, and with walls as include/rcw.h ("wall layouts") restates it: the goal pair is
+ * drawn again while its tile's WALL bit is set.  No interior tile of a ring-only map is a wall: no redraw, the same draw indices. */
 static void orc_reset_agent(orc_batch* b, int32_t a, uint64_t seed)
 {
     const int32_t H = b->H, W = b->W;
@@ -450,12 +460,20 @@ static void orc_reset_agent(orc_batch* b, int32_t a, uint64_t seed)
     /* tile_map[GOAL, goal_position] = false  SR:118 */
     gm[(b->goal[2 * a] - 1) + (size_t)H * (b->goal[2 * a + 1] - 1)] = 0;
     /* CartesianIndex(rand(2:H-1), rand(2:W-1))  SR:120 */
-    const int32_t gi = 2 + (int32_t)orc_below(orc_draw(key, n++), (uint64_t)(H - 2));
-    const int32_t gj = 2 + (int32_t)orc_below(orc_draw(key, n++), (uint64_t)(W - 2));
+    int32_t gi = 2 + (int32_t)orc_below(orc_draw(key, n++), (uint64_t)(H - 2));
+    int32_t gj = 2 + (int32_t)orc_below(orc_draw(key, n++), (uint64_t)(W - 2));
+    /* interior walls: two more draws while the pair's tile is a wall, at most 1024 H W times; then the last pair stays */
+    const uint64_t max_tries = (uint64_t)1024 * H * W;
+    int goal_gave_up = 0;
+    for (uint64_t t = 0; wm[(gi - 1) + (size_t)H * (gj - 1)]; ++t) {
+        if (t == max_tries) { goal_gave_up = 1; break; }
+        gi = 2 + (int32_t)orc_below(orc_draw(key, n++), (uint64_t)(H - 2));
+        gj = 2 + (int32_t)orc_below(orc_draw(key, n++), (uint64_t)(W - 2));
+        b->goal_redraws[a] += 1;
+    }
     b->goal[2 * a] = gi; b->goal[2 * a + 1] = gj;                    /* SR:121 */
     gm[(gi - 1) + (size_t)H * (gj - 1)] = 1;                         /* SR:122 */
     /* sample_empty_position(rng, tile_map)  UT:52-58 -> UT:23-37 */
-    const uint64_t max_tries = (uint64_t)1024 * H * W;
     uint64_t lin = orc_below(orc_draw(key, n++), (uint64_t)HW);      /* UT:24 */
     int gave_up = 1;
     for (uint64_t t = 0; t < max_tries; ++t) {                       /* UT:26 */
@@ -463,7 +481,7 @@ static void orc_reset_agent(orc_batch* b, int32_t a, uint64_t seed)
         else { gave_up = 0; break; }
     }
     /* UT:34 "@warn Could not sample an empty position in max_tries ... Returning non-empty position": the reference goes on */
-    if (gave_up && b->status[a] == 0) b->status[a] = RCW_WARN_SAMPLER_GAVE_UP;
+    if ((gave_up || goal_gave_up) && b->status[a] == 0) b->status[a] = RCW_WARN_SAMPLER_GAVE_UP;
     const int32_t pi = (int32_t)(lin % (uint64_t)H) + 1, pj = (int32_t)(lin / (uint64_t)H) + 1;
     b->pos[2 * a] = (real)((double)pi - 0.5);                       /* SR:125 */
     b->pos[2 * a + 1] = (real)((double)pj - 0.5);
@@ -511,6 +529,9 @@ ORC_EXPORT int orc_create(const rcw_config* cfg, int32_t batch, uint64_t seed, i
     }
     b->col_height = (int32_t*)calloc(N * B, sizeof(int32_t));
     b->col_colour = (uint8_t*)calloc(N * B, 1);
+    b->goal_redraws = (uint64_t*)calloc(B, sizeof(uint64_t));
+    b->blocked_inner = (uint64_t*)calloc(B, sizeof(uint64_t));
+    if (!b->goal_redraws || !b->blocked_inner) { orc_destroy(b); return RCW_ERR_OUT_OF_MEMORY; }
     if (!b->directions || !b->ray_table || !b->wall || !b->goalmap || !b->pos || !b->dir ||
         !b->goal || !b->reward || !b->done || !b->episode || !b->status || !b->ray_stop ||
         !b->ray_dim || !b->ray_dist || !b->ray_dirs || !b->camera_view || !b->col_height ||
@@ -548,6 +569,44 @@ ORC_EXPORT int orc_reset(orc_batch* b, const uint8_t* mask, uint64_t seed)
     return RCW_OK;
 }
 
+/* rcw_set_walls (include/rcw.h, "wall layouts"): walls UInt8 (H*W, layouts) in the tile map's linear order, index Int32 (B) or NULL
+ * (layouts == 1: everybody's; layouts == B: agent a's is layout a), mask as in orc_reset.  Every refusal of the header, each before
+ * anything is written.  Then, for the masked agents: WALL := the layout, GOAL cleared, and reset!(world) under the batch's seed. */
+ORC_EXPORT int orc_set_walls(orc_batch* b, const uint8_t* walls, int32_t layouts, const int32_t* index,
+                             const uint8_t* mask)
+{
+    const int32_t H = b->H, W = b->W;
+    const size_t HW = (size_t)H * W;
+    if (!walls || layouts < 1) return RCW_ERR_INVALID_ARGUMENT;
+    if (!index && layouts != 1 && layouts != b->B) return RCW_ERR_INVALID_ARGUMENT;
+    for (int32_t a = 0; index && a < b->B; ++a) {
+        if (mask && !mask[a]) continue;
+        if (index[a] < 0 || index[a] >= layouts) return RCW_ERR_INVALID_ARGUMENT;
+    }
+    for (int32_t m = 0; m < layouts; ++m) {              /* every layout handed over, also one nobody takes */
+        const uint8_t* q = walls + HW * (size_t)m;
+        int64_t free_tiles = 0;
+        for (int32_t j = 0; j < W; ++j)
+            for (int32_t i = 0; i < H; ++i) {
+                const int ring = i == 0 || i == H - 1 || j == 0 || j == W - 1;   /* SR:57-60 */
+                const int wall = q[(size_t)i + (size_t)H * j] != 0;
+                if (ring && !wall) return RCW_ERR_INVALID_ARGUMENT;
+                if (!ring && !wall) ++free_tiles;
+            }
+        if (free_tiles < 2) return RCW_ERR_INVALID_ARGUMENT;    /* a goal and a player must fit */
+    }
+#pragma omp parallel for schedule(static)
+    for (int32_t a = 0; a < b->B; ++a) {
+        if (mask && !mask[a]) continue;
+        const int32_t m = index ? index[a] : (layouts == 1 ? 0 : a);
+        const uint8_t* q = walls + HW * (size_t)m;
+        for (size_t t = 0; t < HW; ++t) b->wall[HW * a + t] = q[t] != 0;
+        memset(b->goalmap + HW * a, 0, HW);
+        orc_reset_agent(b, a, b->seed);
+    }
+    return RCW_OK;
+}
+
 ORC_EXPORT int orc_set_state(orc_batch* b, const int32_t* goal_ij, const real* pos,
                              const int32_t* dir, const uint8_t* mask)
 {
@@ -577,6 +636,23 @@ ORC_EXPORT int orc_set_state(orc_batch* b, const int32_t* goal_ij, const real* p
     return RCW_OK;
 }
 
+/* Would the player at (px, py) touch a WALL tile inside the ring?  is_player_colliding (CD:1-42) against the agent's WALL layer with
+ * the ring taken out; the player's tile is interior, so every tile of its 3 x 3 neighbourhood is on the map. */
+static int orc_touches_inner_wall(const orc_batch* b, int32_t a, real px, real py)
+{
+    const int32_t H = b->H, W = b->W;
+    const uint8_t* wm = b->wall + (size_t)H * W * a;
+    uint8_t near[9] = {0}, any = 0;
+    const int64_t it = (int64_t)R_FLOOR(px) + 1, jt = (int64_t)R_FLOOR(py) + 1;
+    for (int64_t j = jt - 1; j <= jt + 1; ++j)
+        for (int64_t i = it - 1; i <= it + 1; ++i)
+            if (i > 1 && i < H && j > 1 && j < W && wm[(i - 1) + (int64_t)H * (j - 1)])
+                any = near[(i - it + 1) + 3 * (j - jt + 1)] = 1;
+    if (!any) return 0;
+    /* the same test on the 3 x 3 patch, moved so that the player's tile is the patch's centre (2, 2): whole tiles, exact in T */
+    return orc_is_player_colliding(near, 3, 3, px - (real)(it - 2), py - (real)(jt - 2), CFG_RADIUS(&b->cfg), 1) == 1;
+}
+
 /* act!(world, action)  SR:139-191 for agent a */
 static void orc_act_agent(orc_batch* b, int32_t a, int action)
 {
@@ -598,6 +674,7 @@ static void orc_act_agent(orc_batch* b, int32_t a, int action)
             b->status[a] = RCW_ERR_OUT_OF_BOUNDS;
             return;
         }
+        if (w && !g) b->blocked_inner[a] += (uint64_t)orc_touches_inner_wall(b, a, nx, ny);   /* (bookkeeping only) */
         if (g || w) {                                               /* SR:165 */
             if (g) { orc_set_reward(b, a, 1); b->done[a] = 1; }   /* SR:166-168 */
             else   { orc_set_reward(b, a, 0); b->done[a] = 0; }                 /* SR:170-171 */
@@ -614,13 +691,16 @@ static void orc_act_agent(orc_batch* b, int32_t a, int action)
     }
 }
 
-/* act!(env, action)  SR:333-340 (minus update_top_view!) for the whole batch */
-ORC_EXPORT int orc_step(orc_batch* b, const uint8_t* actions)
+/* act!(env, action)  SR:333-340 (minus update_top_view!) for the whole batch.  `moved` (NULL: everybody): an agent whose byte is 0 is
+ * left exactly as it is — not stepped, not restarted, not rendered again, its action not read.  A caller that restarts agents itself
+ * (another layout at every episode start, tests/walled_oracle.py) steps the others with it. */
+ORC_EXPORT int orc_step_masked(orc_batch* b, const uint8_t* actions, const uint8_t* moved)
 {
     for (int32_t a = 0; a < b->B; ++a)                              /* @assert SR:140 */
-        if (actions[a] < 1 || actions[a] > RCW_NUM_ACTIONS) return RCW_ERR_INVALID_ACTION;
+        if ((!moved || moved[a]) && (actions[a] < 1 || actions[a] > RCW_NUM_ACTIONS)) return RCW_ERR_INVALID_ACTION;
 #pragma omp parallel for schedule(static)
     for (int32_t a = 0; a < b->B; ++a) {
+        if (moved && !moved[a]) continue;
         if (b->cfg.auto_reset && b->done[a]) {
             orc_reset_agent(b, a, b->seed);
             continue;
@@ -630,13 +710,15 @@ ORC_EXPORT int orc_step(orc_batch* b, const uint8_t* actions)
     }
     return RCW_OK;
 }
+ORC_EXPORT int orc_step(orc_batch* b, const uint8_t* actions) { return orc_step_masked(b, actions, NULL); }
 
 /* rcw_step_device semantics: an agent given an action outside 1..4 is not stepped (status
- * RCW_ERR_INVALID_ACTION), the others step. */
-ORC_EXPORT int orc_step_lenient(orc_batch* b, const uint8_t* actions)
+ * RCW_ERR_INVALID_ACTION), the others step.  `moved` as in orc_step_masked. */
+ORC_EXPORT int orc_step_lenient_masked(orc_batch* b, const uint8_t* actions, const uint8_t* moved)
 {
 #pragma omp parallel for schedule(static)
     for (int32_t a = 0; a < b->B; ++a) {
+        if (moved && !moved[a]) continue;
         if (actions[a] < 1 || actions[a] > RCW_NUM_ACTIONS) {
             b->status[a] = RCW_ERR_INVALID_ACTION;
             orc_render_agent(b, a);
@@ -648,6 +730,7 @@ ORC_EXPORT int orc_step_lenient(orc_batch* b, const uint8_t* actions)
     }
     return RCW_OK;
 }
+ORC_EXPORT int orc_step_lenient(orc_batch* b, const uint8_t* actions) { return orc_step_lenient_masked(b, actions, NULL); }
 
 ORC_EXPORT void orc_clear_status(orc_batch* b) { memset(b->status, 0, sizeof(int32_t) * (size_t)b->B); }
 
@@ -670,6 +753,9 @@ ORC_EXPORT const uint8_t* orc_col_colour(orc_batch* b) { return b->col_colour; }
 ORC_EXPORT const real* orc_directions(orc_batch* b) { return b->directions; }
 ORC_EXPORT const real* orc_ray_table(orc_batch* b) { return b->ray_table; }
 ORC_EXPORT int32_t orc_num_chunks(orc_batch* b) { return b->nchunks; }
+ORC_EXPORT const uint8_t* orc_walls(orc_batch* b) { return b->wall; }   /* (H, W, B) Bool, the ring included */
+ORC_EXPORT const uint64_t* orc_goal_redraws(orc_batch* b) { return b->goal_redraws; }
+ORC_EXPORT const uint64_t* orc_blocked_inner(orc_batch* b) { return b->blocked_inner; }
 
 /* tile_map as BitArray{3}(2, H, W).chunks per agent: UInt64 (nchunks, B)  SR:54 */
 ORC_EXPORT void orc_tile_map_chunks(orc_batch* b, uint64_t* out)
