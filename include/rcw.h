@@ -672,6 +672,84 @@ RCW_API int rcw_set_wall_rooms(rcw_handle* h, int32_t enable, int32_t room, uint
 RCW_API int rcw_wall_rooms_info(rcw_handle* h, int32_t* enabled, int32_t* room, uint32_t* stop, uint32_t* doors);
 RCW_API int rcw_wall_rooms_layout(int32_t H, int32_t W, uint64_t key, int32_t room, uint32_t stop, uint32_t doors, uint8_t* out_host /* (H*W), rcw_set_walls' order */,
                                   int32_t* rooms);
+/* ---- episode statistics (this build's addition: how the episodes ended, per agent and per level, kept on the device) ------------------
+ * Opt-in per handle: what a "record episode statistics" wrapper keeps — length, outcome, level and SPL of every finished episode, and
+ * their sums over the batch and per level, which prioritised level replay (rcw_set_wall_bank_weights) and a train / test split of the
+ * generators' levels are computed from — at no host synchronisation.  A handle that never enables it runs exactly the kernels it ran
+ * before.  The ABI is additive: RCW_ABI_VERSION and rcw_config are what they were.  Every stored quantity is an integer: the table does
+ * not depend on the order in which agents are added to it.
+ * Per-agent words, device arrays of B entries each:
+ *   finished   UInt8    1 iff the LAST call closed this agent's record
+ *   outcome    UInt8    RCW_EPISODE_OPEN 0, RCW_EPISODE_SUCCESS 1 (done), RCW_EPISODE_TRUNCATED 2
+ *   length     UInt32   step calls the record has lived through (below)
+ *   moves      UInt32   those calls after which the agent's position differed
+ *   level      Int32    as of the close: rcw_wall_layout's word of the agent on a handle with a layout source, else -1; -1 while open
+ *   spl_q16    Int32    as of the close (below); -1 while open or where SPL is undefined
+ *   episodes   UInt32   records this agent has closed since the statistics were enabled
+ * and, private, the episode counter as of the record's beginning and the position behind the previous call.
+ * BEGIN(a): length = moves = 0, outcome = 0, finished = 0, level = -1, spl_q16 = -1, the private position = the agent's position, the
+ * private counter = rcw_episode's; episodes stays.
+ * Behind rcw_step / rcw_step_device, for every agent, the first of these that applies:
+ *   1  restart   the episode counter differs from the private one (a done or truncated restart under cfg.auto_reset): BEGIN.  The
+ *                restarting call does not count into length: a record is never closed by the call that began it.
+ *   2  frozen    outcome != 0: finished = 0, the private position follows the agent, nothing else.  The words keep the finished episode
+ *                until the agent begins another; without cfg.auto_reset a finished agent walks on and is not recorded again until a
+ *                reset.
+ *   3  open      length += 1; moves += 1 where either value of the position differs from the private one AS A BIT PATTERN; the private
+ *                position follows; then, where done | truncated, the record CLOSES, and otherwise finished = 0.
+ * A close: outcome = done ? 1 : 2, level as above, episodes += 1, finished = 1, the SPL word, the adds into the table.
+ * The rule needs no knowledge of the action: an invalid device action or a raising move under RCW_OOB_ERROR counts into length and not
+ * into moves.  So on a handle with a time limit length == episode_steps at the close for every agent that did not fault (a faulting call
+ * leaves episode_steps as it was and still counts here).
+ * SPL word: defined iff the goal distance is enabled at the close and l = start_distance[a] >= 1.  Truncated and defined: 0.  Success
+ * and defined, with INC = position_increment_wu widened to double (position_increment_wu_f64 on a Float64 handle), every operation in
+ * IEEE Float64 and in this order: p = (double)moves * INC; q = floor((65536.0 * (double)l) / fmax(p, (double)l)) — SPL = l / max(p, l) in
+ * 16.16 fixed point, 65536 where the path was no longer than the tile distance.  Enabling the goal distance in the middle of an episode
+ * makes l the distance at that moment: the order of enabling is the caller's.
+ * The table: UInt64 (RCW_EPISODE_STATS_ROW_WORDS, 1 + rows), row r at 8 r.  Columns: 0 episodes, 1 successes, 2 truncations, 3 sum_length,
+ * 4 sum_moves, 5 spl_episodes (closes with SPL defined), 6 sum_spl_q16, 7 reserved (0).  Row 0 takes every close of the batch, row 1 + k
+ * the closes with k = level - first and 0 <= k < rows.  first and rows are fixed when the statistics are enabled, from the live layout
+ * source: a wall bank of L layouts: first 0, rows L; a generator family with levels > 0: first first_level, rows levels; no source, or
+ * levels == 0: rows 0.  A count above RCW_EPISODE_STATS_MAX_ROWS gives rows 0, not an error: row 0 always works.
+ * What each call does — stream-ordered on the handle's stream, behind everything the call already queues:
+ *   rcw_set_episode_stats(h, 1)   allocates, zeroes the table and `episodes`, BEGIN for every agent; on a handle that has it, the same
+ *                                 again.  An allocation failure leaves what was there.
+ *   rcw_set_episode_stats(h, 0)   frees it (RCW_OK also where there was none).
+ *   rcw_reset, rcw_set_state, rcw_set_state64, rcw_set_walls
+ *                                 BEGIN for the agents in the call's mask — the mask decides, not the counter; an open record that is
+ *                                 abandoned is dropped, not counted — and finished = 0 for every agent (no call but a step closes
+ *                                 anything).  Nothing else of an agent outside the mask changes.
+ *   rcw_set_wall_bank, rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms (install, replace or remove)
+ *                                 RCW_ERR_UNSUPPORTED while the statistics are on, nothing changes: the row count would change under
+ *                                 the table.  Switch the statistics off first (as rcw_set_seen_map(h, 0) under a seen-source local map).
+ *   rcw_episode_stats_clear       zeroes the table WITHOUT waiting for the stream and touches no per-agent word: what a replay loop
+ *                                 calls after it has read the table.
+ *   rcw_set_wall_bank_weights, rcw_set_time_limit, rcw_set_step_form, the direction-table, learner-view, goal-distance, seen-map and
+ *   local-map calls, the renderers and every getter   nothing.
+ * A replayed HIP graph of a step records like any step: everything about this lives on the device.  Capture again after enabling or
+ * disabling, as with the other features.  The kernel (one launch, rcw_episode_stats_kernel) runs behind the goal distance's and OUTSIDE
+ * rcw_profile's events.
+ *   rcw_episode_stats_info               enabled, rows, first (any pointer may be NULL); zeros while off.
+ *   rcw_episode_stats                    host copies of the seven words (any pointer may be NULL); waits for the stream as rcw_done does.
+ *   rcw_episode_stats_device_ptr         the seven arrays where they live (any pointer may be NULL), stable until the next
+ *                                        rcw_set_episode_stats.
+ *   rcw_episode_stats_table              the table to host memory, 8 (1 + rows) UInt64 (waits for the stream).
+ *   rcw_episode_stats_table_device_ptr   the table in DEVICE memory.
+ * The last four and rcw_episode_stats_clear return RCW_ERR_UNSUPPORTED on a handle that has not enabled it. */
+#define RCW_EPISODE_OPEN 0
+#define RCW_EPISODE_SUCCESS 1
+#define RCW_EPISODE_TRUNCATED 2
+#define RCW_EPISODE_STATS_ROW_WORDS 8
+#define RCW_EPISODE_STATS_MAX_ROWS 65536
+RCW_API int rcw_set_episode_stats(rcw_handle* h, int32_t enable);
+RCW_API int rcw_episode_stats_info(rcw_handle* h, int32_t* enabled, int32_t* rows, int32_t* first);
+RCW_API int rcw_episode_stats(rcw_handle* h, uint8_t* finished /* (B) */, uint8_t* outcome /* (B) */, uint32_t* length /* (B) */, uint32_t* moves /* (B) */,
+                              int32_t* level /* (B) */, int32_t* spl_q16 /* (B) */, uint32_t* episodes /* (B) */);
+RCW_API int rcw_episode_stats_device_ptr(rcw_handle* h, void** finished, void** outcome, void** length, void** moves, void** level, void** spl_q16,
+                                         void** episodes);
+RCW_API int rcw_episode_stats_table(rcw_handle* h, uint64_t* out_host /* (8, 1 + rows) */);
+RCW_API int rcw_episode_stats_table_device_ptr(rcw_handle* h, void** ptr);
+RCW_API int rcw_episode_stats_clear(rcw_handle* h);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

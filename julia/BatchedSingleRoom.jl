@@ -489,6 +489,56 @@ function local_map(env::BatchedSingleRoom; first::Integer = 0, count::Integer = 
     check(ccall((:rcw_local_map_copy, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int32, Int32), env.handle, out, first, count)); out
 end
 
+# ---- episode statistics (this build's addition; include/rcw.h, rcw_set_episode_stats) -------------------------------------------
+const EPISODE_OPEN, EPISODE_SUCCESS, EPISODE_TRUNCATED = UInt8(0), UInt8(1), UInt8(2)
+const EPISODE_STATS_COLUMNS = (:episodes, :successes, :truncations, :sum_length, :sum_moves, :spl_episodes, :sum_spl_q16)
+"""
+    set_episode_stats!(env, on = true)
+
+Keep, on the device, how each agent's episodes end and their sums over the batch and per level of the layout source that is live NOW
+(enable `set_wall_bank!` or a generator family — and `set_goal_distance!`, for SPL — first: while the statistics are on the layout source
+cannot be changed).  `episode_stats(env)` returns `(finished, outcome, length, moves, level, spl_q16, episodes)`, each a vector of
+`batch`; `episode_stats_table(env)` the `UInt64` table `(8, 1 + rows)`, column 1 the totals and column `1 + k` level `first + k - 1`,
+its rows `EPISODE_STATS_COLUMNS` and a reserved zero; `episode_stats_clear!(env)` zeroes the table without waiting for the stream.
+"""
+function set_episode_stats!(env::BatchedSingleRoom, on::Bool = true)
+    check(ccall((:rcw_set_episode_stats, librcw), Cint, (Ptr{Cvoid}, Int32), env.handle, on ? 1 : 0))
+    return nothing
+end
+function episode_stats_info(env::BatchedSingleRoom)
+    e = Ref{Int32}(0); r = Ref{Int32}(0); f = Ref{Int32}(0)
+    check(ccall((:rcw_episode_stats_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}), env.handle, e, r, f))
+    return (enabled = e[] != 0, rows = r[], first = f[])
+end
+function episode_stats(env::BatchedSingleRoom)
+    B = env.batch
+    fin = Vector{UInt8}(undef, B); out = Vector{UInt8}(undef, B); len = Vector{UInt32}(undef, B); mov = Vector{UInt32}(undef, B)
+    lev = Vector{Int32}(undef, B); spl = Vector{Int32}(undef, B); eps = Vector{UInt32}(undef, B)
+    check(ccall((:rcw_episode_stats, librcw), Cint,
+                (Ptr{Cvoid}, Ptr{UInt8}, Ptr{UInt8}, Ptr{UInt32}, Ptr{UInt32}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt32}),
+                env.handle, fin, out, len, mov, lev, spl, eps))
+    return (finished = fin, outcome = out, length = len, moves = mov, level = lev, spl_q16 = spl, episodes = eps)
+end
+function episode_stats_device_ptr(env::BatchedSingleRoom)
+    p = [Ref{Ptr{Cvoid}}(C_NULL) for _ in 1:7]
+    check(ccall((:rcw_episode_stats_device_ptr, librcw), Cint,
+                (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                env.handle, p[1], p[2], p[3], p[4], p[5], p[6], p[7]))
+    return (finished = p[1][], outcome = p[2][], length = p[3][], moves = p[4][], level = p[5][], spl_q16 = p[6][], episodes = p[7][])
+end
+function episode_stats_table(env::BatchedSingleRoom)
+    out = Matrix{UInt64}(undef, 8, 1 + Int(episode_stats_info(env).rows))
+    check(ccall((:rcw_episode_stats_table, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt64}), env.handle, out)); out
+end
+function episode_stats_table_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_episode_stats_table_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
+function episode_stats_clear!(env::BatchedSingleRoom)
+    check(ccall((:rcw_episode_stats_clear, librcw), Cint, (Ptr{Cvoid},), env.handle))
+    return nothing
+end
+
 # ---- the wall bank (this build's addition; include/rcw.h, rcw_set_wall_bank) ----------------------------------------------------
 """
     set_wall_bank!(env, walls; weights = nothing)

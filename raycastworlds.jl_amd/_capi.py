@@ -35,6 +35,8 @@ RCW_VIEW_CHW, RCW_VIEW_HWC = 0, 1                      # ... layout
 RCW_VIEW_ONLY = 1                                      # ... flag: no camera view in the step
 RCW_VIEW_MAX_FRAMES = 16                               # rcw_set_learner_view_stack: frames
 RCW_LOCAL_WORLD, RCW_LOCAL_SEEN = 1, 2                 # rcw_set_local_map: source (0 = off)
+RCW_EPISODE_OPEN, RCW_EPISODE_SUCCESS, RCW_EPISODE_TRUNCATED = 0, 1, 2   # the episode statistics' outcome word
+RCW_EPISODE_STATS_ROW_WORDS, RCW_EPISODE_STATS_MAX_ROWS = 8, 65536
 RCW_LOCAL_MAX_SIZE, RCW_LOCAL_MAX_CELLS_PER_TILE = 128, 16
 
 
@@ -165,6 +167,13 @@ SIGNATURES = {
     "rcw_local_map_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
     "rcw_local_map_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_local_map_copy": [_vp, _vp, _i32, _i32],
+    "rcw_set_episode_stats": [_vp, _i32],
+    "rcw_episode_stats_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
+    "rcw_episode_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rcw_episode_stats_device_ptr": [_vp] + [C.POINTER(_vp)] * 7,
+    "rcw_episode_stats_table": [_vp, _vp],
+    "rcw_episode_stats_table_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_episode_stats_clear": [_vp],
     "rcw_set_wall_bank": [_vp, _vp, _i32, _vp],
     "rcw_set_wall_bank_weights": [_vp, _vp],
     "rcw_wall_bank_info": [_vp, C.POINTER(_i32), C.POINTER(_u64)],

@@ -1190,6 +1190,11 @@ int rcw_local_map_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32_t 
 extern "C++" {
 namespace {
 int need_wall_bank(rcw_handle* h) { return h->source.is(kLayoutBank) ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no wall bank (rcw_set_wall_bank)"); }
+// (the table's level rows were counted from the source that is live: it stays until the statistics are switched off)
+int refuse_under_episode_stats(rcw_handle* h, const char* caller)
+{
+    return h->stats.on() ? fail(RCW_ERR_UNSUPPORTED, "%s: the handle keeps episode statistics, whose level rows follow the layout source; switch them off first (rcw_set_episode_stats(h, 0))", caller) : RCW_OK;
+}
 int need_drawn_walls(rcw_handle* h) { return h->source.live() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms)"); }
 
 }  // namespace
@@ -1199,6 +1204,7 @@ int need_drawn_walls(rcw_handle* h) { return h->source.live() ? RCW_OK : fail(RC
 int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts, const uint32_t* weights_host)
 {
     int rc = check_handle(h); if (rc) return rc;
+    rc = refuse_under_episode_stats(h, "rcw_set_wall_bank"); if (rc) return rc;
     if (layouts == 0 || !walls_host) return drop_layout_source(h, kLayoutBank);
     rc = refuse_other_source(h, "rcw_set_wall_bank", kLayoutBank); if (rc) return rc;
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
@@ -1280,6 +1286,7 @@ int rcw_wall_layout_device_ptr(rcw_handle* h, void** device_ptr)
 int rcw_set_wall_generator(rcw_handle* h, int32_t enable, uint32_t loops, int32_t levels, int32_t first_level, uint64_t level_seed)
 {
     int rc = check_handle(h); if (rc) return rc;
+    rc = refuse_under_episode_stats(h, "rcw_set_wall_generator"); if (rc) return rc;
     if (!enable) return drop_layout_source(h, kLayoutMazes);
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     rc = plan_wall_generator(H, W, levels, first_level); if (rc) return rc;
@@ -1307,6 +1314,7 @@ int rcw_wall_generator_info(rcw_handle* h, int32_t* enabled, uint32_t* loops, in
 int rcw_set_wall_caves(rcw_handle* h, int32_t enable, uint32_t fill, int32_t smooth, int32_t levels, int32_t first_level, uint64_t level_seed)
 {
     int rc = check_handle(h); if (rc) return rc;
+    rc = refuse_under_episode_stats(h, "rcw_set_wall_caves"); if (rc) return rc;
     if (!enable) return drop_layout_source(h, kLayoutCaves);
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     rc = plan_wall_caves(H, W, smooth, levels, first_level); if (rc) return rc;
@@ -1332,6 +1340,7 @@ int rcw_wall_caves_info(rcw_handle* h, int32_t* enabled, uint32_t* fill, int32_t
 int rcw_set_wall_rooms(rcw_handle* h, int32_t enable, int32_t room, uint32_t stop, uint32_t doors, int32_t levels, int32_t first_level, uint64_t level_seed)
 {
     int rc = check_handle(h); if (rc) return rc;
+    rc = refuse_under_episode_stats(h, "rcw_set_wall_rooms"); if (rc) return rc;
     if (!enable) return drop_layout_source(h, kLayoutRooms);
     const int H = h->cfg.height_tile_map_tu, W = h->cfg.width_tile_map_tu;
     rc = plan_wall_rooms(H, W, room, levels, first_level); if (rc) return rc;
@@ -1351,6 +1360,114 @@ int rcw_wall_rooms_info(rcw_handle* h, int32_t* enabled, int32_t* room, uint32_t
     if (room) *room = r.room;
     if (stop) *stop = r.stop;
     if (doors) *doors = r.doors;
+    return RCW_OK;
+}
+
+// Episode statistics (include/rcw.h).  Enabling allocates, zeroes the table and the agents' counts and begins every agent's record at once,
+// stream-ordered behind what is queued; enabling again does the same again; an allocation failure leaves what was there.
+int rcw_set_episode_stats(rcw_handle* h, int32_t enable)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::EpisodeStats& es = h->stats;
+    if (!enable && !es.on()) return RCW_OK;
+    rcw_handle::EpisodeStats fresh;
+    if (enable) {
+        RcwEpisodeStats& d = fresh.dev;
+        plan_episode_stats_rows(h->source.dev.kind, h->source.dev.agents.layouts, h->source.dev.gen.levels, h->source.dev.gen.first_level, &d.rows, &d.first);
+        // table | previous x, y | six 4-byte arrays | two byte arrays: every part starts on a multiple of its element's size
+        const size_t B = (size_t)h->B, tbytes = fresh.table_bytes(), bytes = tbytes + 2 * B * h->real_size + 6 * B * sizeof(uint32_t) + 2 * B;
+        const hipError_t e = fresh.buf.hipMalloc(bytes);
+        if (e != hipSuccess) return fail(hip_code(e), "episode statistics of %zu bytes: %s", bytes, hip_failure(e));
+        uint8_t* const base = fresh.buf.get<uint8_t>();
+        d.table = reinterpret_cast<uint64_t*>(base);
+        d.prev_x = base + tbytes;
+        d.prev_y = base + tbytes + B * h->real_size;
+        uint32_t* const w = reinterpret_cast<uint32_t*>(base + tbytes + 2 * B * h->real_size);
+        uint8_t* const b = reinterpret_cast<uint8_t*>(w + 6 * B);
+        d.words = RcwEpisodeWords{b, b + B, w, w + B, reinterpret_cast<int32_t*>(w + 2 * B), reinterpret_cast<int32_t*>(w + 3 * B), w + 4 * B};
+        d.last_episode = w + 5 * B;
+    }
+    RCW_HIP(replace_buffers(h, {&es.buf}, {&fresh.buf}));
+    es.dev = fresh.dev;
+    if (es.on()) {
+        RCW_HIP(hipMemsetAsync(es.dev.table, 0, es.table_bytes(), h->stream));
+        RCW_HIP(hipMemsetAsync(es.dev.words.episodes, 0, (size_t)h->B * sizeof(uint32_t), h->stream));
+        RCW_HIP(launch_episode_stats(h, nullptr, kStackRefill));
+    }
+    return RCW_OK;
+}
+
+int rcw_episode_stats_info(rcw_handle* h, int32_t* enabled, int32_t* rows, int32_t* first)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (enabled) *enabled = h->stats.on() ? 1 : 0;
+    if (rows) *rows = h->stats.dev.rows;                                // (zeros while off)
+    if (first) *first = h->stats.dev.first;
+    return RCW_OK;
+}
+
+extern "C++" {
+namespace {
+int need_episode_stats(rcw_handle* h) { return h->stats.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle keeps no episode statistics (rcw_set_episode_stats)"); }
+}  // namespace
+}  // extern "C++"
+
+int rcw_episode_stats(rcw_handle* h, uint8_t* finished, uint8_t* outcome, uint32_t* length, uint32_t* moves, int32_t* level, int32_t* spl_q16, uint32_t* episodes)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_episode_stats(h); if (rc) return rc;
+    rc = sync_and_check(h);
+    const size_t B = (size_t)h->B;
+    const RcwEpisodeWords& w = h->stats.dev.words;
+    if (finished) RCW_HIP(hipMemcpy(finished, w.finished, B, hipMemcpyDeviceToHost));
+    if (outcome) RCW_HIP(hipMemcpy(outcome, w.outcome, B, hipMemcpyDeviceToHost));
+    if (length) RCW_HIP(hipMemcpy(length, w.length, B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (moves) RCW_HIP(hipMemcpy(moves, w.moves, B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (level) RCW_HIP(hipMemcpy(level, w.level, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (spl_q16) RCW_HIP(hipMemcpy(spl_q16, w.spl_q16, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (episodes) RCW_HIP(hipMemcpy(episodes, w.episodes, B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int rcw_episode_stats_device_ptr(rcw_handle* h, void** finished, void** outcome, void** length, void** moves, void** level, void** spl_q16, void** episodes)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = need_episode_stats(h); if (rc) return rc;
+    const RcwEpisodeWords& w = h->stats.dev.words;
+    if (finished) *finished = w.finished;
+    if (outcome) *outcome = w.outcome;
+    if (length) *length = w.length;
+    if (moves) *moves = w.moves;
+    if (level) *level = w.level;
+    if (spl_q16) *spl_q16 = w.spl_q16;
+    if (episodes) *episodes = w.episodes;
+    return RCW_OK;
+}
+
+int rcw_episode_stats_table(rcw_handle* h, uint64_t* out_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_episode_stats(h); if (rc) return rc;
+    if (!out_host) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL output pointer");
+    rc = sync_and_check(h);
+    RCW_HIP(hipMemcpy(out_host, h->stats.dev.table, h->stats.table_bytes(), hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int rcw_episode_stats_table_device_ptr(rcw_handle* h, void** ptr)
+{
+    if (!h || !ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = need_episode_stats(h); if (rc) return rc;
+    *ptr = h->stats.dev.table;
+    return RCW_OK;
+}
+
+// (stream-ordered and without waiting for the stream: a step queued before it adds to the old table, one queued behind it to the zeroed one)
+int rcw_episode_stats_clear(rcw_handle* h)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_episode_stats(h); if (rc) return rc;
+    RCW_HIP(hipMemsetAsync(h->stats.dev.table, 0, h->stats.table_bytes(), h->stream));
     return RCW_OK;
 }
 

@@ -199,6 +199,16 @@ struct rcw_handle {
         bool is(RcwLayoutKind k) const { return dev.kind == k; }
         bool live() const { return !is(kLayoutNone); }
     } source;
+    // Episode statistics (rcw_set_episode_stats): ONE allocation — the table (UInt64, 8 (1 + rows)), the two halves of the previous
+    // position (world-unit type [B] each), the six 4-byte arrays (length, moves, level, spl_q16, episodes, the private episode counter), then
+    // the two byte arrays (finished, outcome); dev's pointers point into it.  rows / first: fixed when enabled (plan_episode_stats_rows).
+    // Empty while the feature is off.
+    struct EpisodeStats {
+        RcwBuf buf;
+        RcwEpisodeStats dev{};
+        bool on() const { return buf.get() != nullptr; }
+        size_t table_bytes() const { return (size_t)RCW_EPISODE_STATS_ROW_WORDS * (1 + (size_t)dev.rows) * sizeof(uint64_t); }
+    } stats;
     ~rcw_handle();
 };
 
@@ -241,6 +251,7 @@ int plan_wall_bank_weights(const uint32_t* weights, int32_t layouts, uint32_t* c
 int plan_wall_generator(int32_t H, int32_t W, int32_t levels, int32_t first_level);
 int plan_wall_caves(int32_t H, int32_t W, int32_t smooth, int32_t levels, int32_t first_level);
 int plan_wall_rooms(int32_t H, int32_t W, int32_t room, int32_t levels, int32_t first_level);
+void plan_episode_stats_rows(RcwLayoutKind kind, int32_t layouts, int32_t levels, int32_t first_level, int32_t* rows, int32_t* first);
 
 // ---- rcw_step.hip: what a step, a reset or a re-render launches, and the resources those launches need ---------------------------------
 hipError_t launch_top_view_alone(rcw_handle* h, const uint8_t* mask_dev);
@@ -249,6 +260,7 @@ hipError_t launch_view(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_goal_distance(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_local_map(rcw_handle* h, StackOp op);
+hipError_t launch_episode_stats(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_layout_source(rcw_handle* h, bool force);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
 hipError_t replace_buffers(rcw_handle* h, std::initializer_list<RcwBuf*> old, std::initializer_list<RcwBuf*> fresh = {});

@@ -210,6 +210,32 @@ hipError_t rcw_launch_seen_map(const RcwDev& p, int32_t B, const uint8_t* mask_d
 size_t rcw_local_map_lds_bytes(const RcwDev& p, int32_t size, bool seen);
 hipError_t rcw_launch_local_map(const RcwDev& p, int32_t B, const uint8_t* seen_map, const void* off, int32_t size, uint8_t* out, hipStream_t s);
 
+// Episode statistics (rcw_set_episode_stats, rcw_episode_stats.hip): the seven per-agent words, the two private ones and the table.
+struct RcwEpisodeWords {
+    uint8_t* finished;       // 1 iff the last call closed the agent's record
+    uint8_t* outcome;        // RCW_EPISODE_OPEN / SUCCESS / TRUNCATED
+    uint32_t* length;        // step calls the record has lived through
+    uint32_t* moves;         // ... after which the position differed
+    int32_t* level;          // the layout as of the close, -1 while open or without a layout source
+    int32_t* spl_q16;        // SPL * 65536 as of the close, -1 while open or where it is undefined
+    uint32_t* episodes;      // records the agent has closed
+};
+struct RcwEpisodeStats {
+    RcwEpisodeWords words;
+    uint32_t* last_episode;  // [B] each agent's episode counter as of the beginning of its record
+    void* prev_x;            // [B] its position behind the previous call, in the world-unit type, x and y apart
+    void* prev_y;
+    uint64_t* table;         // UInt64 (RCW_EPISODE_STATS_ROW_WORDS, 1 + rows)
+    int32_t rows, first;     // the level rows: row 1 + k takes the closes with level == first + k
+};
+// One launch behind a step (refill = false: an agent whose episode counter differs from last_episode begins a record, a closed record stays
+// frozen, an open one lives through the call and closes where done | truncated) or behind reset / set_state / set_walls / enabling (refill =
+// true: the agents of the mask — NULL: all — begin, the others' `finished` is cleared).  An argument block of its OWN (the comment on
+// RcwLimit): no kernel of a handle without the statistics changes.  layout, start_distance: as they are NOW, NULL where the handle has no
+// layout source / no goal distance.  Reads p's state arrays and limit.truncated, writes only st's buffers.
+hipError_t rcw_launch_episode_stats(const RcwDev& p, const RcwLimit& limit, const RcwEpisodeStats& st, const int32_t* layout,
+                                    const int32_t* start_distance, const uint8_t* mask_dev, bool refill, hipStream_t s);
+
 // THE LAYOUT SOURCES (rcw_wall_bank.hip): what gives an agent its walls at every start of an episode.  A handle has at most one — the wall
 // bank (rcw_set_wall_bank) or one family of the wall generator: mazes (rcw_set_wall_generator), caves (rcw_set_wall_caves), rooms
 // (rcw_set_wall_rooms) — behind ONE launch point, rcw_launch_layout_source.

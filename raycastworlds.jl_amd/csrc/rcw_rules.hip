@@ -594,6 +594,18 @@ int plan_wall_rooms(int32_t H, int32_t W, int32_t room, int32_t levels, int32_t 
     return RCW_OK;
 }
 
+// The level rows of the episode statistics' table (include/rcw.h, "episode statistics"), from the live layout source as of enabling: the bank
+// a row per layout from 0, a generator family with a level range a row per level from first_level, anything else — and any count above
+// RCW_EPISODE_STATS_MAX_ROWS — none: row 0 always works.
+void plan_episode_stats_rows(RcwLayoutKind kind, int32_t layouts, int32_t levels, int32_t first_level, int32_t* rows, int32_t* first)
+{
+    const bool bank = kind == kLayoutBank, family = kind != kLayoutNone && !bank;
+    const int32_t count = bank ? layouts : (family ? levels : 0);
+    const bool any = count > 0 && count <= RCW_EPISODE_STATS_MAX_ROWS;
+    *rows = any ? count : 0;
+    *first = any && family ? first_level : 0;
+}
+
 // The handle-less export: the rule once more on the host, by another traversal than the device's — depth first off a plain stack, a chamber
 // at a time, where the kernel cuts every chamber of a depth in one round.
 extern "C" int rcw_wall_rooms_layout(int32_t H, int32_t W, uint64_t key, int32_t room, uint32_t stop, uint32_t doors, uint8_t* out_host, int32_t* rooms)

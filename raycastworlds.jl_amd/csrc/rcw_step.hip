@@ -241,6 +241,16 @@ hipError_t launch_local_map(rcw_handle* h, StackOp op)
     return rcw_launch_local_map(h->dev, h->B, lm.source == RCW_LOCAL_SEEN ? h->seen.map : nullptr, lm.off, lm.size, lm.img, h->stream);
 }
 
+// ... and episode statistics, behind the goal distance (whose start_distance a close reads) and the layout source (whose layout it reads),
+// both as they are NOW — NULL where the handle has none.  A step runs the step rule, a refill the mask rule; a re-render of the same world
+// (a new direction table, a change of the step's form) launches nothing.
+hipError_t launch_episode_stats(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
+{
+    if (!h->stats.on() || op == kStackKeep || op == kStackRefillSameWorld) return hipSuccess;
+    return rcw_launch_episode_stats(h->dev, h->dev.limit, h->stats.dev, h->source.live() ? h->source.dev.agents.layout : nullptr,
+                                    h->goal.on() ? h->goal.words.start_distance : nullptr, mask_dev, op == kStackRefill, h->stream);
+}
+
 // The layout source (rcw_handle::LayoutSource), behind the core launches of a call that can move an episode counter: its kernel gives every
 // agent that began an episode a layout and a fresh state against it, and leaves in the source's own mask who that was.  force: every agent
 // (the call that installs the source).  Behind rcw_reset the caller's re-render covers exactly those agents; behind a step, launch_step
@@ -265,7 +275,8 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
         if (e == hipSuccess && h->learner.on()) e = launch_view(h, mask_dev, op);
         if (e == hipSuccess) e = launch_goal_distance(h, mask_dev, op);
         if (e == hipSuccess) e = launch_seen_map(h, mask_dev, op);
-        return e == hipSuccess ? launch_local_map(h, op) : e;
+        if (e == hipSuccess) e = launch_local_map(h, op);
+        return e == hipSuccess ? launch_episode_stats(h, mask_dev, op) : e;
     }
     h->step.obs_unknown();                                        // (the camera view is not painted)
     const Bracket prof(&h->prof);
@@ -283,7 +294,8 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if ((e = prof.done(h->stream)) != hipSuccess) return e;
     if ((e = launch_goal_distance(h, mask_dev, op)) != hipSuccess) return e;
     if ((e = launch_seen_map(h, mask_dev, op)) != hipSuccess) return e;
-    return launch_local_map(h, op);
+    if ((e = launch_local_map(h, op)) != hipSuccess) return e;
+    return launch_episode_stats(h, mask_dev, op);
 }
 
 // THE way a buffer of a live handle is given up: wait_all_streams (queued work may still use the old ones), then each of `old` takes

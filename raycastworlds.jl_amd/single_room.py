@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import sys
+import types
 from typing import Optional, Sequence
 
 import numpy as np
@@ -346,7 +347,8 @@ class SingleRoom:
     `set_time_limit`.  `walls` / `wall_index` (this build's addition; None = the reference's empty room) are `set_walls`'
     arguments, applied right after construction.  `goal_distance` (this build's addition) is `set_goal_distance(True)` after them,
     `seen_map` (this build's addition) `set_seen_map(True)` after that, `local_map` (this build's addition; an int — the size — or a dict
-    of `set_local_map`'s keywords) `set_local_map` last.  `wall_bank` / `wall_bank_weights` (this build's addition) are `set_wall_bank`'s
+    of `set_local_map`'s keywords) `set_local_map` after that, `episode_stats` (this build's addition) `set_episode_stats(True)` last of
+    all — behind the layout sources below, whose levels count its table's rows.  `wall_bank` / `wall_bank_weights` (this build's addition) are `set_wall_bank`'s
     arguments, applied after `walls` and the time limit and before the features: a layout drawn on the device at every episode start.
     `wall_generator` (this build's addition; a dict of `set_wall_generator`'s keywords, `{}` for the defaults) is applied in the same
     place: a new maze made on the device at every episode start.  It and `wall_bank` exclude each other.  `wall_caves` (this build's
@@ -394,6 +396,7 @@ class SingleRoom:
         wall_generator=None,
         wall_caves=None,
         wall_rooms=None,
+        episode_stats: bool = False,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -519,6 +522,12 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        if episode_stats:
+            try:
+                self.set_episode_stats(True)
+            except BaseException:
+                self._handle.close()
+                raise
         # colour fields of the reference struct SR:241-256
         self.floor_color = cfg.floor_color
         self.ceiling_color = cfg.ceiling_color
@@ -545,7 +554,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_seen_map_dev", "_local_map_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_seen_map_dev", "_local_map_dev", "_episode_stats_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -932,6 +941,82 @@ class SingleRoom:
         H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
         return DeviceArray(p.value, (self.batch, W, H), np.uint16, self, self._sync,
                            host_getter=lambda: np.ascontiguousarray(self.goal_distance_field.transpose(0, 2, 1)))
+
+    # ---- episode statistics (include/rcw.h, rcw_set_episode_stats) ----------------------
+    _EPISODE_WORDS = (("finished", np.uint8), ("outcome", np.uint8), ("length", np.uint32), ("moves", np.uint32), ("level", np.int32),
+                      ("spl_q16", np.int32), ("episodes", np.uint32))
+    EPISODE_STATS_COLUMNS = ("episodes", "successes", "truncations", "sum_length", "sum_moves", "spl_episodes", "sum_spl_q16")
+
+    def set_episode_stats(self, on: bool = True) -> None:
+        """Keep, on the device, how each agent's episodes end — `episode_stats.finished / outcome / length / moves / level / spl_q16 /
+        episodes` — and their sums over the batch and per level of the layout source that is live NOW (`episode_stats_table`): what a
+        "record episode statistics" wrapper keeps, with no host synchronisation.  Enable the wall bank or the generator (and the goal
+        distance, for SPL) first: while the statistics are on, the layout source cannot be changed.  Switching it on (again) zeroes
+        everything and begins every agent's record at its current state; the device arrays handed out before are invalid after every
+        call."""
+        self.__dict__.pop("_episode_stats_dev", None)
+        self._check(self._lib.rcw_set_episode_stats(self._h, 1 if on else 0))
+
+    @property
+    def episode_stats_info(self) -> dict:
+        """`enabled`, and the table's level rows: `rows` of them, the first for level `first` (rcw_episode_stats_info)."""
+        v = [C.c_int32(), C.c_int32(), C.c_int32()]
+        self._check(self._lib.rcw_episode_stats_info(self._h, *[C.byref(x) for x in v]))
+        return {"enabled": bool(v[0].value), "rows": v[1].value, "first": v[2].value}
+
+    @property
+    def episode_stats_enabled(self) -> bool:
+        return self.episode_stats_info["enabled"]
+
+    def _episode_stats_host(self, which: int) -> np.ndarray:
+        out = np.empty(self.batch, dtype=self._EPISODE_WORDS[which][1])
+        args = [None] * 7
+        args[which] = _as_ptr(out)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_episode_stats(self._h, *args))
+        return out
+
+    @property
+    def episode_stats(self):
+        """The seven per-agent words as `DeviceArray`s (B,): `finished` (uint8, 1 iff the last step closed the agent's record), `outcome`
+        (uint8: 0 open, 1 success, 2 truncated), `length`, `moves` (uint32), `level` (int32, -1 without a layout source), `spl_q16` (int32,
+        SPL * 65536, -1 where undefined) and `episodes` (uint32).  The words keep a finished episode until the agent begins another:
+        read them where `finished` is set.  `.torch(sync=False)` on the GPU, `np.asarray(...)` for a host copy."""
+        if getattr(self, "_episode_stats_dev", None) is None:
+            p = [C.c_void_p() for _ in range(7)]
+            self._check(self._lib.rcw_episode_stats_device_ptr(self._h, *[C.byref(x) for x in p]))
+            self._episode_stats_dev = types.SimpleNamespace(**{
+                name: DeviceArray(p[k].value, (self.batch,), dtype, self, self._sync, host_getter=lambda k=k: self._episode_stats_host(k))
+                for k, (name, dtype) in enumerate(self._EPISODE_WORDS)})
+        return self._episode_stats_dev
+
+    def episode_stats_table(self, device: bool = False):
+        """The sums over the records closed since enabling (or the last `episode_stats_clear`).  A dict of numpy arrays: `totals` — the
+        seven `EPISODE_STATS_COLUMNS` of the whole batch, by name —, `levels` — the same per level, each an array of `rows` entries, level
+        `first + k` at k —, `first`, and `spl`, the mean SPL as floats (`totals`' and per level; NaN where no close had it defined).
+        `device=True`: the raw uint64 (1 + rows, 8) `DeviceArray` instead, row 0 the totals."""
+        rows = self.episode_stats_info["rows"]
+        if device:
+            p = C.c_void_p()
+            self._check(self._lib.rcw_episode_stats_table_device_ptr(self._h, C.byref(p)))
+            return DeviceArray(p.value, (1 + rows, 8), np.uint64, self, self._sync, host_getter=lambda: self._episode_stats_table_host(rows))
+        t = self._episode_stats_table_host(rows)
+        cols = self.EPISODE_STATS_COLUMNS
+        with np.errstate(divide="ignore", invalid="ignore"):
+            spl = np.where(t[:, 5] > 0, t[:, 6] / 65536.0 / t[:, 5], np.nan)
+        return {"totals": {c: int(t[0, k]) for k, c in enumerate(cols)}, "levels": {c: t[1:, k].copy() for k, c in enumerate(cols)},
+                "first": self.episode_stats_info["first"], "spl": {"totals": float(spl[0]), "levels": spl[1:].copy()}}
+
+    def _episode_stats_table_host(self, rows: int) -> np.ndarray:
+        out = np.empty((1 + rows, 8), dtype=np.uint64)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_episode_stats_table(self._h, _as_ptr(out)))
+        return out
+
+    def episode_stats_clear(self) -> None:
+        """Zero the table, stream-ordered and without waiting for the stream; the per-agent words stay.  What a replay loop calls after
+        it has read the table."""
+        self._check(self._lib.rcw_episode_stats_clear(self._h))
 
     # ---- the seen map (include/rcw.h, rcw_set_seen_map) ---------------------------------
     def set_seen_map(self, on: bool = True) -> None:
