@@ -750,6 +750,77 @@ RCW_API int rcw_episode_stats_device_ptr(rcw_handle* h, void** finished, void** 
 RCW_API int rcw_episode_stats_table(rcw_handle* h, uint64_t* out_host /* (8, 1 + rows) */);
 RCW_API int rcw_episode_stats_table_device_ptr(rcw_handle* h, void** ptr);
 RCW_API int rcw_episode_stats_clear(rcw_handle* h);
+
+/* ---- The state archive (this build's addition: the reference has no checkpoint) -------------------------------------------------------
+ * `rows` agent RECORDS kept on the device and owned by the handle: save scatters the records of the masked agents into rows, restore
+ * gathers rows back into the masked agents and renders them again — what ALE's cloneState / restoreState and Procgen's get_state /
+ * set_state give, for every agent at once and without leaving the device.  Both take per-agent row indices, so several agents may restore
+ * from one row.  A handle that never calls rcw_set_snapshots allocates and launches exactly what it did before.
+ *
+ * A record is a list of SEGMENTS, one per per-agent array; it holds everything the next step of an agent reads that a render does not
+ * compute again:
+ *   always             pos (pos64 for T = Float64), dir, goal, reward (in R), done, episode, tile_map, episode_steps, truncated
+ *   goal distance      field, distance, start_distance, progress, and the flood's private episode counter
+ *   seen map           seen_count, newly_seen, goal_seen, the private episode counter, the packed bits, the map
+ *   learner view       the frame (k = 1), or the k-frame stack and its private episode counter
+ *   local map          the image (stored, not computed again: its bytes are what they were at the save)
+ *   layout source      the source's private episode counter and the agents' layout index / level
+ *   episode statistics the seven words, the previous position (x, y), the private episode counter
+ * A record does NOT hold
+ *   the camera view, the column descriptors, the one-launch step's slots, the top view        a restore renders them again;
+ *   the agents' status words and the layout source's record of them                           the agent SLOT's error log, like the
+ *                                                                                             handle's error word: they stay the slot's;
+ *   the layout source's transient mask, the episode statistics' table                         a launch's scratch; a log of the batch;
+ *   any setting of the handle — seed, time limit, bank and weights, generator parameters,     these are the handle's as of the restore.
+ *   direction table —
+ * If row r was saved from agent j and is restored into agent i, agent i holds j's world; its next episode starts under i's global id and
+ * the copied episode counter.
+ *
+ *   rcw_set_snapshots(h, rows)   binds the archive to the handle's SHAPE as of now — which features are on, the learner view's format, size
+ *                                and k, the local map's size, the kind of the layout source — and allocates `rows` records, 0 ..
+ *                                RCW_SNAPSHOT_MAX_ROWS, none of them filled; 0 frees the archive.  Again: bound anew, and empty.  A failed
+ *                                allocation returns RCW_ERR_OUT_OF_MEMORY and the old archive stays.  Waits for the stream.
+ *   rcw_snapshot_info            rows, the bytes of a record as rcw_snapshot_rows_copy hands it out, and the shape key: a 64-bit hash
+ *                                (FNV-1a) of the segment table, the geometry, T, R and RCW_ABI_VERSION.  Any pointer may be NULL.  Without
+ *                                an archive: rows 0 and the record the handle's shape would have now.
+ * A save or restore of a handle whose shape is no longer the archive's returns RCW_ERR_UNSUPPORTED, names the first segment that differs
+ * and changes nothing.
+ *   rcw_snapshot_save / rcw_snapshot_restore (h, rows_host, mask_host)
+ *                                rows_host Int32 (B): agent a's row; NULL: row a, which needs rows >= B.  mask_host UInt8 (B) or NULL:
+ *                                every agent.  The host checks the masked agents' indices — in 0 .. rows - 1; restore: a filled row; save:
+ *                                distinct rows — and a violation returns RCW_ERR_INVALID_ARGUMENT, names the agent and changes nothing.
+ *                                They wait for the stream (the staging of their arguments; restore also reads which rows are filled).
+ *   rcw_snapshot_save_device / rcw_snapshot_restore_device (h, rows_device, mask_device)
+ *                                the same with both arrays in DEVICE memory (either may be NULL as above): stream-ordered, no host wait,
+ *                                capturable like rcw_step_device.  A masked agent whose index is out of range — or, restore, names an
+ *                                unfilled row — is left exactly as it was; its status word and the handle's error word become
+ *                                RCW_ERR_INVALID_ARGUMENT (as an invalid action's become RCW_ERR_INVALID_ACTION; rcw_clear_error clears
+ *                                them), and the other agents are served.  Two masked agents MAY save into one row: it then holds the whole
+ *                                record of the higher-numbered agent, never a mixture.
+ * A save launches the scatter alone.  A restore launches the gather and then casts and paints the masked agents from the state they now
+ * hold; the flood, the seen map, the stack, the local map and the statistics are the record's.
+ *   rcw_snapshot_filled          UInt8 (rows) to host memory: 1 where a save or a load has filled the row.  Waits for the stream.
+ *   rcw_snapshot_rows_copy       rows [first, first + count) to host memory, row_bytes each: the segments in the table's order, unpadded
+ *                                (an unfilled row reads as zeros).  Waits for the stream; a sticky device error comes back instead of
+ *                                the rows (rcw_clear_error first).
+ *   rcw_snapshot_rows_load       ... and back, into rows [first, first + count) of an archive whose shape key is `shape_key` (another key,
+ *                                or a handle whose shape is no longer the archive's: RCW_ERR_UNSUPPORTED).  For every row the host checks the fields a kernel INDEXES with — goal an interior
+ *                                tile, direction in 0 .. nd - 1, position finite and inside the room, the map's border WALL bits set and
+ *                                its padding clear, the layout index in the live source's range — and a violation returns
+ *                                RCW_ERR_INVALID_ARGUMENT, names row and field, and nothing is loaded.  EVERYTHING ELSE IS TRUSTED, as
+ *                                rcw_set_walls trusts its caller: rows are the output of rcw_snapshot_rows_copy, not a format to write.
+ *                                The rows count as filled.  Waits for the stream.
+ * All but rcw_set_snapshots and rcw_snapshot_info return RCW_ERR_UNSUPPORTED on a handle without an archive. */
+#define RCW_SNAPSHOT_MAX_ROWS 1048576
+RCW_API int rcw_set_snapshots(rcw_handle* h, int32_t rows);
+RCW_API int rcw_snapshot_info(rcw_handle* h, int32_t* rows, uint64_t* row_bytes, uint64_t* shape_key);
+RCW_API int rcw_snapshot_save(rcw_handle* h, const int32_t* rows_host /* (B) or NULL */, const uint8_t* mask_host /* (B) or NULL */);
+RCW_API int rcw_snapshot_restore(rcw_handle* h, const int32_t* rows_host /* (B) or NULL */, const uint8_t* mask_host /* (B) or NULL */);
+RCW_API int rcw_snapshot_save_device(rcw_handle* h, const int32_t* rows_device, const uint8_t* mask_device);
+RCW_API int rcw_snapshot_restore_device(rcw_handle* h, const int32_t* rows_device, const uint8_t* mask_device);
+RCW_API int rcw_snapshot_filled(rcw_handle* h, uint8_t* out_host /* (rows) */);
+RCW_API int rcw_snapshot_rows_copy(rcw_handle* h, int32_t first, int32_t count, void* out_host /* (row_bytes, count) */);
+RCW_API int rcw_snapshot_rows_load(rcw_handle* h, int32_t first, int32_t count, const void* in_host /* (row_bytes, count) */, uint64_t shape_key);
 /* world.player_position_wu SR:24, world.player_direction_au SR:25, world.goal_position SR:32 */
 RCW_API int rcw_position(rcw_handle* h, float* out_host /* (2, B) */);
 RCW_API int rcw_direction(rcw_handle* h, int32_t* out_host /* (B) */);

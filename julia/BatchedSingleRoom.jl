@@ -539,6 +539,71 @@ function episode_stats_clear!(env::BatchedSingleRoom)
     return nothing
 end
 
+# ---- the state archive (this build's addition; include/rcw.h, rcw_set_snapshots) ------------------------------------------------
+"""
+    set_snapshots!(env, rows)
+
+Bind the state archive: `rows` agent records kept on the device, none filled, laid out for the features that are on NOW (0 frees it).
+`save_state!(env; rows = nothing, mask = nothing)` saves the records of the agents of `mask` into the 0-based rows `rows` (`nothing`:
+agent `a` into row `a - 1`); `restore_state!(env; rows, mask)` puts them back — several agents may take one row — and renders them again.
+Host vectors are checked on the host (a bad index, an unfilled row, two agents into one row: an error, nothing changes); the `_device`
+variants take device pointers, wait for nothing and leave a bad agent as it was with its status word set.  `snapshot_filled(env)` says
+which rows are filled; `snapshot_export(env)` / `snapshot_import!(env, d)` carry rows between environments of the same shape key.
+"""
+function set_snapshots!(env::BatchedSingleRoom, rows::Integer)
+    check(ccall((:rcw_set_snapshots, librcw), Cint, (Ptr{Cvoid}, Int32), env.handle, rows))
+    return nothing
+end
+function snapshot_info(env::BatchedSingleRoom)
+    r = Ref{Int32}(0); b = Ref{UInt64}(0); k = Ref{UInt64}(0)
+    check(ccall((:rcw_snapshot_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{UInt64}, Ref{UInt64}), env.handle, r, b, k))
+    return (rows = r[], row_bytes = b[], shape_key = k[])
+end
+function snapshot_arguments(env::BatchedSingleRoom, rows, mask)
+    r = rows === nothing ? nothing : Vector{Int32}(rows)
+    m = mask === nothing ? nothing : Vector{UInt8}(mask .!= 0)
+    (r === nothing || length(r) == env.batch) && (m === nothing || length(m) == env.batch) || throw(DimensionMismatch("rows and mask have one entry per agent"))
+    return r, m
+end
+function save_state!(env::BatchedSingleRoom; rows = nothing, mask = nothing)
+    r, m = snapshot_arguments(env, rows, mask)
+    check(ccall((:rcw_snapshot_save, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{UInt8}), env.handle,
+                r === nothing ? C_NULL : r, m === nothing ? C_NULL : m))
+    return nothing
+end
+function restore_state!(env::BatchedSingleRoom; rows = nothing, mask = nothing)
+    r, m = snapshot_arguments(env, rows, mask)
+    check(ccall((:rcw_snapshot_restore, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{UInt8}), env.handle,
+                r === nothing ? C_NULL : r, m === nothing ? C_NULL : m))
+    return nothing
+end
+function save_state_device!(env::BatchedSingleRoom, rows::Ptr{Int32}, mask::Ptr{UInt8})
+    check(ccall((:rcw_snapshot_save_device, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{UInt8}), env.handle, rows, mask))
+    return nothing
+end
+function restore_state_device!(env::BatchedSingleRoom, rows::Ptr{Int32}, mask::Ptr{UInt8})
+    check(ccall((:rcw_snapshot_restore_device, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{UInt8}), env.handle, rows, mask))
+    return nothing
+end
+function snapshot_filled(env::BatchedSingleRoom)
+    out = Vector{UInt8}(undef, Int(snapshot_info(env).rows))
+    check(ccall((:rcw_snapshot_filled, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}), env.handle, out))
+    return out .!= 0
+end
+function snapshot_export(env::BatchedSingleRoom; first::Integer = 0, count::Union{Nothing, Integer} = nothing)
+    info = snapshot_info(env)
+    n = count === nothing ? Int(info.rows) - Int(first) : Int(count)
+    out = Matrix{UInt8}(undef, Int(info.row_bytes), max(n, 0))
+    check(ccall((:rcw_snapshot_rows_copy, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}), env.handle, first, n, out))
+    return (shape_key = info.shape_key, row_bytes = info.row_bytes, rows = out)
+end
+function snapshot_import!(env::BatchedSingleRoom, d; first::Integer = 0)
+    rows = Matrix{UInt8}(d.rows)
+    size(rows, 1) == Int(snapshot_info(env).row_bytes) || throw(DimensionMismatch("rows must be (row_bytes, count)"))
+    check(ccall((:rcw_snapshot_rows_load, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, UInt64), env.handle, first, size(rows, 2), rows, d.shape_key))
+    return nothing
+end
+
 # ---- the wall bank (this build's addition; include/rcw.h, rcw_set_wall_bank) ----------------------------------------------------
 """
     set_wall_bank!(env, walls; weights = nothing)

@@ -38,6 +38,7 @@ RCW_LOCAL_WORLD, RCW_LOCAL_SEEN = 1, 2                 # rcw_set_local_map: sour
 RCW_EPISODE_OPEN, RCW_EPISODE_SUCCESS, RCW_EPISODE_TRUNCATED = 0, 1, 2   # the episode statistics' outcome word
 RCW_EPISODE_STATS_ROW_WORDS, RCW_EPISODE_STATS_MAX_ROWS = 8, 65536
 RCW_LOCAL_MAX_SIZE, RCW_LOCAL_MAX_CELLS_PER_TILE = 128, 16
+RCW_SNAPSHOT_MAX_ROWS = 1 << 20                         # rcw_set_snapshots: rows
 
 
 class RcwConfig(C.Structure):
@@ -174,6 +175,15 @@ SIGNATURES = {
     "rcw_episode_stats_table": [_vp, _vp],
     "rcw_episode_stats_table_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_episode_stats_clear": [_vp],
+    "rcw_set_snapshots": [_vp, _i32],
+    "rcw_snapshot_info": [_vp, C.POINTER(_i32), C.POINTER(_u64), C.POINTER(_u64)],
+    "rcw_snapshot_save": [_vp, _vp, _vp],
+    "rcw_snapshot_restore": [_vp, _vp, _vp],
+    "rcw_snapshot_save_device": [_vp, _vp, _vp],
+    "rcw_snapshot_restore_device": [_vp, _vp, _vp],
+    "rcw_snapshot_filled": [_vp, _vp],
+    "rcw_snapshot_rows_copy": [_vp, _i32, _i32, _vp],
+    "rcw_snapshot_rows_load": [_vp, _i32, _i32, _vp, _u64],
     "rcw_set_wall_bank": [_vp, _vp, _i32, _vp],
     "rcw_set_wall_bank_weights": [_vp, _vp],
     "rcw_wall_bank_info": [_vp, C.POINTER(_i32), C.POINTER(_u64)],

@@ -50,6 +50,7 @@ __attribute__((visibility("default"))) int rcw_dev_step_rule(const rcw_config* c
 //   4  rcw_reset in front of its render; a: bit 0 a mask, bit 1 a seed that is not the handle's, bit 2 cfg.auto_reset
 //   5  rcw_cast_rays, or ensure_columns in front of a reader           6  rcw_columns_device_ptr / a learner view switched on
 //   7  rcw_update_camera_view                                         8  rcw_set_time_limit
+//   9  rcw_snapshot_restore* behind its gather, in front of its render (an event 1 without an action, with the call's mask)
 __attribute__((visibility("default"))) int rcw_dev_step_facts(int32_t eligible, int32_t pays, int32_t store_all, const int32_t* events, int32_t n, int32_t* out)
 {
     if (!events || !out || n < 0) return RCW_ERR_INVALID_ARGUMENT;
@@ -76,6 +77,7 @@ __attribute__((visibility("default"))) int rcw_dev_step_facts(int32_t eligible, 
         else if (kind == 6) { f.columns_wanted(); f.columns_cast(); }
         else if (kind == 7) { f.obs_unknown(); f.columns_cast(); f.camera_repainted(); }
         else if (kind == 8) f.time_limit_set();
+        else if (kind == 9) f.restored();
         else return RCW_ERR_INVALID_ARGUMENT;
         f.read(o);
     }
@@ -88,5 +90,38 @@ __attribute__((visibility("default"))) int rcw_dev_validate_walls(int32_t H, int
     if (!msg || cap < 1 || H < 3 || W < 3 || batch < 1) return RCW_ERR_INVALID_ARGUMENT;
     msg[0] = 0;
     return validate_walls(H, W, batch, walls, layouts, index, mask, msg, (size_t)cap);
+}
+// The state archive's record without a device (tests/test_snapshot_spec.py).  shape: the 23 Int32 of SnapshotShape in its order — H, W, nd, N,
+// Hc, real64, reward_type | goal, seen, stats | view_fmt, view_layout, view_C, view_h, view_w, view_frames | local_source, local_size,
+// local_cells | source_kind | layouts, levels, first_level.  names: the segments' names, a line each; bytes [n]; returns n, -1: names too small.
+static_assert(sizeof(SnapshotShape) == 23 * sizeof(int32_t), "SnapshotShape travels as 23 Int32");
+__attribute__((visibility("default"))) int rcw_dev_snapshot_plan(const int32_t* shape, char* names, int32_t cap, uint32_t* bytes, uint64_t* row_bytes, uint64_t* key)
+{
+    if (!shape || !names || cap < 1 || !bytes || !row_bytes || !key) return RCW_ERR_INVALID_ARGUMENT;
+    SnapshotShape sh;
+    std::memcpy(&sh, shape, sizeof sh);
+    SnapshotPlan plan;
+    plan_snapshot(sh, &plan);
+    int n = 0;
+    for (int k = 0; k < plan.n; ++k) {
+        const int w = std::snprintf(names + n, (size_t)(cap - n), "%s\n", plan.seg[k].name);
+        if (w < 0 || n + w >= cap) return -1;
+        n += w;
+        bytes[k] = plan.seg[k].bytes;
+    }
+    *row_bytes = plan.row_bytes; *key = plan.key;
+    return plan.n;
+}
+// rcw_snapshot_rows_load's check of one exported row of that shape: validate_snapshot_row's return code, its reason in msg
+__attribute__((visibility("default"))) int rcw_dev_snapshot_validate_row(const int32_t* shape, const uint8_t* row, char* msg, int32_t cap)
+{
+    if (!shape || !row || !msg || cap < 1) return RCW_ERR_INVALID_ARGUMENT;
+    SnapshotShape sh;
+    std::memcpy(&sh, shape, sizeof sh);
+    if (sh.H < 3 || sh.W < 3 || sh.nd < 1) return RCW_ERR_INVALID_ARGUMENT;
+    SnapshotPlan plan;
+    plan_snapshot(sh, &plan);
+    msg[0] = 0;
+    return validate_snapshot_row(sh, plan, row, msg, (size_t)cap);
 }
 }  // extern "C"

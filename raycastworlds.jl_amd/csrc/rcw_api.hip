@@ -100,6 +100,7 @@ int sync_and_check(rcw_handle* h)
     if (e == RCW_ERR_INVALID_ACTION) return fail(e, "invalid action (must be in 1..%d); the agents it was given to were not stepped (rcw_status)", RCW_NUM_ACTIONS);
     if (e == RCW_ERR_OUT_OF_BOUNDS) return fail(e, "a tile index left the tile map (BoundsError in the reference)");
     if (e == RCW_ERR_HIP) return fail(e, "a kernel gave up waiting for another one after about a second (the top view's store kernel for its draw kernel): the images of that call are not valid");
+    if (e == RCW_ERR_INVALID_ARGUMENT) return fail(e, "a row index given to rcw_snapshot_save_device / rcw_snapshot_restore_device was out of range or (restore) named an unfilled row; those agents were left as they were (rcw_status)");
     if (e != 0) return fail(e, "device error %d", e);
     return RCW_OK;
 }
@@ -1468,6 +1469,221 @@ int rcw_episode_stats_clear(rcw_handle* h)
     int rc = check_handle(h); if (rc) return rc;
     rc = need_episode_stats(h); if (rc) return rc;
     RCW_HIP(hipMemsetAsync(h->stats.dev.table, 0, h->stats.table_bytes(), h->stream));
+    return RCW_OK;
+}
+
+// ---- the state archive (include/rcw.h, rcw_handle::Snapshots) -----------------------------------------------------------------------------
+extern "C++" {
+namespace {
+
+using Snapshots = rcw_handle::Snapshots;
+
+// What of the handle fixes a record's layout NOW (and, for rcw_snapshot_rows_load's check, the layout source's range).
+SnapshotShape snapshot_shape(const rcw_handle* h)
+{
+    SnapshotShape s;
+    s.H = h->dev.H; s.W = h->dev.W; s.nd = h->dev.nd; s.N = h->dev.N; s.Hc = h->dev.Hc;
+    s.real64 = h->real64 ? 1 : 0; s.reward_type = h->cfg.reward_type;
+    s.goal = h->goal.on(); s.seen = h->seen.on(); s.stats = h->stats.on();
+    const rcw_handle::LearnerView& lv = h->learner;
+    if (lv.on()) { s.view_fmt = lv.set.fmt; s.view_layout = lv.set.layout; s.view_C = lv.view.C; s.view_h = lv.set.h; s.view_w = lv.set.w; s.view_frames = lv.set.frames; }
+    if (h->local.on()) { s.local_source = h->local.source; s.local_size = h->local.size; s.local_cells = h->local.cells_per_tile; }
+    s.source_kind = (int32_t)h->source.dev.kind;
+    s.layouts = h->source.dev.agents.layouts; s.levels = h->source.dev.gen.levels; s.first_level = h->source.dev.gen.first_level;
+    return s;
+}
+
+int need_snapshots(rcw_handle* h) { return h->snaps.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no state archive (rcw_set_snapshots)"); }
+
+// A save or a restore of a handle whose shape is no longer the archive's is refused, and names the first segment that differs.
+int check_snapshot_shape(rcw_handle* h, const char* caller)
+{
+    SnapshotPlan now;
+    plan_snapshot(snapshot_shape(h), &now);
+    const char* const seg = snapshot_plan_differs(h->snaps.plan, now);
+    return seg ? fail(RCW_ERR_UNSUPPORTED, "%s: the handle's shape differs from the archive's in segment %s; bind the archive again (rcw_set_snapshots)", caller, seg) : RCW_OK;
+}
+
+// The device half of both variants: the checks that need no index, then the launches.
+int snapshot_device(rcw_handle* h, const char* caller, const int32_t* rows_dev, const uint8_t* mask_dev, bool restore)
+{
+    int rc = need_snapshots(h); if (rc) return rc;
+    rc = check_snapshot_shape(h, caller); if (rc) return rc;
+    if (!rows_dev && h->snaps.rows < h->B)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "%s: without row indices agent a takes row a, which needs rows >= %d (the archive has %d)", caller, h->B, h->snaps.rows);
+    RCW_HIP(launch_snapshot(h, rows_dev, mask_dev, restore));
+    return RCW_OK;
+}
+
+// The host variants: the indices of the masked agents are checked here — in range, filled (restore), distinct (save) —, a violation names
+// the agent and changes nothing; then mask and indices are staged and the device half runs.
+int snapshot_host(rcw_handle* h, const char* caller, const int32_t* rows_host, const uint8_t* mask_host, bool restore)
+{
+    int rc = need_snapshots(h); if (rc) return rc;
+    rc = check_snapshot_shape(h, caller); if (rc) return rc;
+    Snapshots& sn = h->snaps;
+    const int32_t B = h->B, rows = sn.rows;
+    if (!rows_host && rows < B)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "%s: without row indices agent a takes row a, which needs rows >= %d (the archive has %d)", caller, B, rows);
+    std::vector<uint8_t> filled;
+    std::vector<int32_t> taken;
+    try {
+        if (restore) filled.resize((size_t)rows); else taken.assign((size_t)rows, -1);
+    } catch (const std::bad_alloc&) {
+        return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the archive's row flags failed");
+    }
+    if (restore) {                                                     // (device saves queued before this call count: wait for them)
+        RCW_HIP(hipStreamSynchronize(h->stream));
+        RCW_HIP(hipMemcpy(filled.data(), sn.filled, (size_t)rows, hipMemcpyDeviceToHost));
+    }
+    for (int32_t a = 0; a < B; ++a) {
+        if (mask_host && !mask_host[a]) continue;
+        const int32_t r = rows_host ? rows_host[a] : a;
+        if (r < 0 || r >= rows) return fail(RCW_ERR_INVALID_ARGUMENT, "%s: agent %d: row %d not in 0..%d", caller, a, r, rows - 1);
+        if (restore && !filled[(size_t)r]) return fail(RCW_ERR_INVALID_ARGUMENT, "%s: agent %d: row %d has not been filled", caller, a, r);
+        if (!restore) {
+            if (taken[(size_t)r] >= 0) return fail(RCW_ERR_INVALID_ARGUMENT, "%s: agent %d: row %d is also agent %d's (a host save takes distinct rows)", caller, a, r, taken[(size_t)r]);
+            taken[(size_t)r] = a;
+        }
+    }
+    const uint8_t* mask_dev = nullptr;
+    rc = upload_mask(h, mask_host, &mask_dev); if (rc) return rc;
+    if (rows_host) {
+        RCW_HIP(hipMemcpyAsync(sn.in_rows, rows_host, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        RCW_HIP(hipStreamSynchronize(h->stream));                      // (pageable host memory of the caller's)
+    }
+    RCW_HIP(launch_snapshot(h, rows_host ? sn.in_rows : nullptr, mask_dev, restore));
+    return RCW_OK;
+}
+
+int check_snapshot_rows(rcw_handle* h, const char* caller, int32_t first, int32_t count, const void* host)
+{
+    if (host && first >= 0 && count >= 0 && first + (int64_t)count <= h->snaps.rows) return RCW_OK;
+    return fail(RCW_ERR_INVALID_ARGUMENT, "%s: bad row range [%d, %lld) of %d rows, or a NULL buffer", caller, first, (long long)first + count, h->snaps.rows);
+}
+
+}  // namespace
+}  // extern "C++"
+
+// Bind the archive to the handle's shape as of now: `rows` empty records.  Everything is allocated before anything is given up.
+int rcw_set_snapshots(rcw_handle* h, int32_t rows)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    if (rows < 0 || rows > RCW_SNAPSHOT_MAX_ROWS) return fail(RCW_ERR_INVALID_ARGUMENT, "rows must be in 0..%d (got %d)", RCW_SNAPSHOT_MAX_ROWS, rows);
+    Snapshots& sn = h->snaps;
+    if (rows == 0 && !sn.on()) return RCW_OK;
+    Snapshots fresh;
+    if (rows > 0) {
+        plan_snapshot(snapshot_shape(h), &fresh.plan);
+        const size_t R = (size_t)rows, B = (size_t)h->B;
+        const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        size_t off[kSnapshotMaxSegments], bytes = 0;
+        for (int k = 0; k < fresh.plan.n; ++k) { off[k] = bytes; bytes = up16(bytes + R * fresh.plan.seg[k].bytes); }
+        const size_t ints = bytes;
+        bytes += (R + 2 * B) * sizeof(int32_t);
+        const size_t flags = bytes;
+        bytes += R;
+        const hipError_t e = fresh.buf.hipMalloc(bytes);
+        if (e != hipSuccess) return fail(hip_code(e), "state archive of %d rows of %llu bytes: %s", rows, (unsigned long long)fresh.plan.row_bytes, hip_failure(e));
+        uint8_t* const base = fresh.buf.get<uint8_t>();
+        for (int k = 0; k < fresh.plan.n; ++k) fresh.arc[k] = base + off[k];
+        fresh.owner = reinterpret_cast<int32_t*>(base + ints);
+        fresh.sel = fresh.owner + R;
+        fresh.in_rows = fresh.sel + B;
+        fresh.filled = base + flags;
+        fresh.rows = rows;
+        RCW_HIP(hipMemsetAsync(base, 0, bytes, h->stream));            // (no row is filled; an unfilled row reads as zeros)
+    }
+    RCW_HIP(replace_buffers(h, {&sn.buf}, {&fresh.buf}));
+    sn.plan = fresh.plan; sn.rows = fresh.rows; sn.owner = fresh.owner; sn.sel = fresh.sel; sn.in_rows = fresh.in_rows; sn.filled = fresh.filled;
+    std::memcpy(sn.arc, fresh.arc, sizeof sn.arc);
+    return RCW_OK;
+}
+
+// (without an archive: no rows, and the record the handle's shape would have now)
+int rcw_snapshot_info(rcw_handle* h, int32_t* rows, uint64_t* row_bytes, uint64_t* shape_key)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    SnapshotPlan now;
+    if (!h->snaps.on()) plan_snapshot(snapshot_shape(h), &now);
+    const SnapshotPlan& p = h->snaps.on() ? h->snaps.plan : now;
+    if (rows) *rows = h->snaps.rows;
+    if (row_bytes) *row_bytes = p.row_bytes;
+    if (shape_key) *shape_key = p.key;
+    return RCW_OK;
+}
+
+int rcw_snapshot_save(rcw_handle* h, const int32_t* rows_host, const uint8_t* mask_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return snapshot_host(h, "rcw_snapshot_save", rows_host, mask_host, false);
+}
+int rcw_snapshot_restore(rcw_handle* h, const int32_t* rows_host, const uint8_t* mask_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return snapshot_host(h, "rcw_snapshot_restore", rows_host, mask_host, true);
+}
+int rcw_snapshot_save_device(rcw_handle* h, const int32_t* rows_device, const uint8_t* mask_device)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return snapshot_device(h, "rcw_snapshot_save_device", rows_device, mask_device, false);
+}
+int rcw_snapshot_restore_device(rcw_handle* h, const int32_t* rows_device, const uint8_t* mask_device)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return snapshot_device(h, "rcw_snapshot_restore_device", rows_device, mask_device, true);
+}
+
+int rcw_snapshot_filled(rcw_handle* h, uint8_t* out_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_snapshots(h); if (rc) return rc;
+    if (!out_host) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL output pointer");
+    RCW_HIP(hipStreamSynchronize(h->stream));
+    RCW_HIP(hipMemcpy(out_host, h->snaps.filled, (size_t)h->snaps.rows, hipMemcpyDeviceToHost));
+    return RCW_OK;
+}
+
+// Rows [first, first + count) as the caller keeps them: row_bytes each, the segments in the table's order, unpadded.
+int rcw_snapshot_rows_copy(rcw_handle* h, int32_t first, int32_t count, void* out_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_snapshots(h); if (rc) return rc;
+    rc = check_snapshot_rows(h, "rcw_snapshot_rows_copy", first, count, out_host); if (rc) return rc;
+    const Snapshots& sn = h->snaps;
+    rc = sync_and_check(h); if (rc) return rc;                          // (a sticky device error: nothing is copied, rcw_clear_error first)
+    for (int k = 0; k < sn.plan.n && count > 0; ++k) {
+        const size_t b = sn.plan.seg[k].bytes;
+        RCW_HIP(hipMemcpy2D(static_cast<uint8_t*>(out_host) + sn.plan.offset(k), (size_t)sn.plan.row_bytes, sn.arc[k] + (size_t)first * b, b, b, (size_t)count, hipMemcpyDeviceToHost));
+    }
+    return rc;
+}
+
+// ... and back, into a handle of the same shape (the key): every row is checked on the host first (validate_snapshot_row), and nothing is
+// loaded unless all pass.  The rows loaded count as filled.
+int rcw_snapshot_rows_load(rcw_handle* h, int32_t first, int32_t count, const void* in_host, uint64_t shape_key)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need_snapshots(h); if (rc) return rc;
+    rc = check_snapshot_shape(h, "rcw_snapshot_rows_load"); if (rc) return rc;   // (the row check below reads the rows by the handle's shape NOW)
+    rc = check_snapshot_rows(h, "rcw_snapshot_rows_load", first, count, in_host); if (rc) return rc;
+    const Snapshots& sn = h->snaps;
+    if (shape_key != sn.plan.key)
+        return fail(RCW_ERR_UNSUPPORTED, "rcw_snapshot_rows_load: the rows' shape key %016llx is not the archive's (%016llx)", (unsigned long long)shape_key, (unsigned long long)sn.plan.key);
+    const SnapshotShape shape = snapshot_shape(h);
+    const uint8_t* const in = static_cast<const uint8_t*>(in_host);
+    char why[256];
+    for (int32_t r = 0; r < count; ++r)
+        if (validate_snapshot_row(shape, sn.plan, in + (size_t)r * sn.plan.row_bytes, why, sizeof why) != RCW_OK)
+            return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_snapshot_rows_load: row %d: %s", first + r, why);
+    if (count == 0) return RCW_OK;
+    RCW_HIP(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < sn.plan.n; ++k) {
+        const size_t b = sn.plan.seg[k].bytes;
+        RCW_HIP(hipMemcpy2D(sn.arc[k] + (size_t)first * b, b, in + sn.plan.offset(k), (size_t)sn.plan.row_bytes, b, (size_t)count, hipMemcpyHostToDevice));
+    }
+    RCW_HIP(hipMemsetAsync(sn.filled + first, 1, (size_t)count, h->stream));   // (the handle's stream, as all of the archive's device work)
+    RCW_HIP(hipStreamSynchronize(h->stream));
     return RCW_OK;
 }
 

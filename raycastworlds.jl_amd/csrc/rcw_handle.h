@@ -93,6 +93,40 @@ public:
     // rcw_set_time_limit: the slots were cast under the old limit (which agents the next action re-samples, whose successors are therefore a
     // preview's) — every agent's are cast again by the next step, as a launch of its own
     void time_limit_set() { forget(); }
+    // rcw_snapshot_restore*, behind its gather and in front of its render: the restored agents' slots were cast from the state they had
+    // before (and the others' successors may be previews of it) — every agent's are cast again by the next step, as a launch of its own —,
+    // and no frame in dev.obs is known to be the one its slot 0 holds.  The descriptors stay as stale as they were: the masked render
+    // behind it refreshes the restored agents' only, as rcw_reset's does.
+    void restored() { forget(); obs_unknown(); }
+};
+
+// THE RECORD OF THE STATE ARCHIVE (include/rcw.h, "the state archive"): what of a handle fixes the layout of an agent's record, and the
+// layout — the segment table — it fixes.  Host values only: the development build plans without a device (rcw_dev_snapshot_plan).
+// A segment is one per-agent array of the handle; `tag` tells apart what the bytes alone do not (a learner view of 7 x 9 from one of
+// 9 x 7, a bank's layout index from a family's level).  key: FNV-1a over the table, the geometry, T, R and RCW_ABI_VERSION.
+struct SnapshotShape {
+    int32_t H = 0, W = 0, nd = 0, N = 0, Hc = 0;
+    int32_t real64 = 0, reward_type = 0;
+    int32_t goal = 0, seen = 0, stats = 0;                       // the goal distance, the seen map, episode statistics: on
+    int32_t view_fmt = 0, view_layout = 0, view_C = 0, view_h = 0, view_w = 0, view_frames = 0;   // the learner view; view_fmt 0: off
+    int32_t local_source = 0, local_size = 0, local_cells = 0;   // the local map; local_source 0: off
+    int32_t source_kind = 0;                                     // RcwLayoutKind; 0: no layout source
+    int32_t layouts = 0, levels = 0, first_level = 0;            // the source's range (validate_snapshot_row; not part of the shape)
+};
+enum SnapshotField { kSnapPos, kSnapDir, kSnapGoal, kSnapReward, kSnapDone, kSnapEpisode, kSnapTileMap, kSnapEpisodeSteps, kSnapTruncated,
+                     kSnapGoalField, kSnapGoalDistance, kSnapGoalStart, kSnapGoalProgress, kSnapGoalLast,
+                     kSnapSeenCount, kSnapSeenNew, kSnapSeenGoal, kSnapSeenLast, kSnapSeenBits, kSnapSeenMap,
+                     kSnapViewFrame, kSnapViewStack, kSnapViewLast, kSnapLocalImage, kSnapSourceLast, kSnapSourceLayout,
+                     kSnapStatsFinished, kSnapStatsOutcome, kSnapStatsLength, kSnapStatsMoves, kSnapStatsLevel, kSnapStatsSpl, kSnapStatsEpisodes,
+                     kSnapStatsPrevX, kSnapStatsPrevY, kSnapStatsLast, kSnapFieldCount };
+constexpr int kSnapshotMaxSegments = kSnapFieldCount;
+struct SnapshotSegment { SnapshotField field; const char* name; uint32_t bytes; uint64_t tag; };
+struct SnapshotPlan {
+    int32_t n = 0;
+    SnapshotSegment seg[kSnapshotMaxSegments] = {};
+    uint64_t row_bytes = 0, key = 0;
+    int find(SnapshotField f) const { for (int k = 0; k < n; ++k) if (seg[k].field == f) return k; return -1; }
+    uint64_t offset(int k) const { uint64_t o = 0; for (int j = 0; j < k; ++j) o += seg[j].bytes; return o; }   // of segment k in an exported row
 };
 
 // OWNERSHIP: every device buffer, pinned buffer, stream and event of a handle is a member of one of rcw_owned.h's types; nothing else frees
@@ -209,6 +243,20 @@ struct rcw_handle {
         bool on() const { return buf.get() != nullptr; }
         size_t table_bytes() const { return (size_t)RCW_EPISODE_STATS_ROW_WORDS * (1 + (size_t)dev.rows) * sizeof(uint64_t); }
     } stats;
+    // The state archive (rcw_set_snapshots): ONE allocation — every segment's rows ([rows][bytes], each part on a multiple of 16 bytes), then
+    // the Int32 scratch (owner [rows], the row each agent takes [B], the host variants' staged indices [B]), then the filled flags (UInt8
+    // [rows]).  plan: the record's layout as of the binding (plan_snapshot); arc[k]: segment k's rows.  Empty while the archive is off.
+    struct Snapshots {
+        RcwBuf buf;
+        SnapshotPlan plan{};
+        int32_t rows = 0;
+        uint8_t* arc[kSnapshotMaxSegments] = {};
+        int32_t* owner = nullptr;
+        int32_t* sel = nullptr;
+        int32_t* in_rows = nullptr;
+        uint8_t* filled = nullptr;
+        bool on() const { return buf.get() != nullptr; }
+    } snaps;
     ~rcw_handle();
 };
 
@@ -251,6 +299,9 @@ int plan_wall_bank_weights(const uint32_t* weights, int32_t layouts, uint32_t* c
 int plan_wall_generator(int32_t H, int32_t W, int32_t levels, int32_t first_level);
 int plan_wall_caves(int32_t H, int32_t W, int32_t smooth, int32_t levels, int32_t first_level);
 int plan_wall_rooms(int32_t H, int32_t W, int32_t room, int32_t levels, int32_t first_level);
+void plan_snapshot(const SnapshotShape& sh, SnapshotPlan* plan);
+const char* snapshot_plan_differs(const SnapshotPlan& bound, const SnapshotPlan& now);   // the first segment that differs, NULL: the same shape
+int validate_snapshot_row(const SnapshotShape& sh, const SnapshotPlan& plan, const uint8_t* row, char* msg, size_t cap);
 void plan_episode_stats_rows(RcwLayoutKind kind, int32_t layouts, int32_t levels, int32_t first_level, int32_t* rows, int32_t* first);
 
 // ---- rcw_step.hip: what a step, a reset or a re-render launches, and the resources those launches need ---------------------------------
@@ -263,6 +314,7 @@ hipError_t launch_local_map(rcw_handle* h, StackOp op);
 hipError_t launch_episode_stats(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_layout_source(rcw_handle* h, bool force);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
+hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t* mask_dev, bool restore);
 hipError_t replace_buffers(rcw_handle* h, std::initializer_list<RcwBuf*> old, std::initializer_list<RcwBuf*> fresh = {});
 int plan_top_view(rcw_handle* h, int want_form, int want_runs, bool lenient);
 int plan_step_form(rcw_handle* h, int want);

@@ -293,3 +293,27 @@ hipError_t rcw_launch_wall_bank_pack(const RcwDev& p, const uint8_t* walls_dev, 
 // The camera view (p.obs) of the agents with mask[a] != 0 from p.col_h / p.col_c, a workgroup an agent: the repaint behind
 // rcw_launch_layout_source, whose mask is sparse — the camera fill's pixels, without its sweep over the whole batch.
 hipError_t rcw_launch_wall_bank_paint(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);
+
+// THE STATE ARCHIVE (rcw_snapshot.hip): a record is a list of segments, each [B][bytes] live and [rows][bytes] in the archive.  The copy
+// kernel's table, passed by value: at most kSnapshotKernelSegments a launch.  first_task: the segment's first wavefront task (rcw_snapshot_tasks
+// of them each, numbered through the table); tasks: their sum.
+constexpr int kSnapshotKernelSegments = 32;
+struct RcwSnapshotSeg {
+    uint8_t* live;               // the handle's array
+    uint8_t* rows;               // the archive's
+    uint32_t bytes;              // of one agent's part
+    uint32_t first_task;
+};
+struct RcwSnapshotTable {
+    int32_t n;
+    uint32_t tasks;
+    RcwSnapshotSeg seg[kSnapshotKernelSegments];
+};
+uint32_t rcw_snapshot_tasks(uint32_t bytes, int32_t B);
+// Who takes which row: sel[a] = rows[a] (NULL: a) of the agents of the mask (NULL: all), -1 for the others and for an index outside [0, nrows)
+// or (restore) an unfilled row — those agents' status words and the error word become RCW_ERR_INVALID_ARGUMENT.  A save marks the rows filled
+// and leaves in owner (-1 everywhere before) the highest agent that saves into each.
+hipError_t rcw_launch_snapshot_resolve(const RcwDev& p, int32_t B, const int32_t* rows_dev, const uint8_t* mask_dev, int32_t nrows, bool restore,
+                                       uint8_t* filled, int32_t* owner, int32_t* sel, hipStream_t s);
+// The copy of the table's segments, live -> rows (restore = false; owner: only the row's owner writes it) or rows -> live (owner NULL).
+hipError_t rcw_launch_snapshot_copy(const RcwSnapshotTable& t, int32_t B, const int32_t* sel, const int32_t* owner, bool restore, int grid_cap, hipStream_t s);

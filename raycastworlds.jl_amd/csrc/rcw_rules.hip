@@ -655,6 +655,146 @@ extern "C" int rcw_wall_rooms_layout(int32_t H, int32_t W, uint64_t key, int32_t
     return RCW_OK;
 }
 
+// THE STATE ARCHIVE'S RECORD (include/rcw.h, "the state archive"): the segment table of a handle of this shape, in the order an exported row
+// holds the segments.  A segment a per-agent array; what is off has none.  The local map's image is stored (and not computed again behind a
+// restore): its segment is then what binds the archive to the map's size.
+void plan_snapshot(const SnapshotShape& sh, SnapshotPlan* plan)
+{
+    SnapshotPlan& p = *plan;
+    p = SnapshotPlan{};
+    const uint32_t real = sh.real64 ? 8u : 4u, HW = (uint32_t)sh.H * (uint32_t)sh.W;
+    const uint32_t reward = (sh.reward_type == RCW_REWARD_FLOAT64 || sh.reward_type == RCW_REWARD_INT64) ? 8u : 4u;
+    const auto add = [&p](SnapshotField f, const char* name, uint32_t bytes, uint64_t tag = 0) { p.seg[p.n++] = SnapshotSegment{f, name, bytes, tag}; };
+    add(kSnapPos, sh.real64 ? "pos64" : "pos", 2 * real);
+    add(kSnapDir, "dir", 4);
+    add(kSnapGoal, "goal", 8);
+    add(kSnapReward, "reward", reward, (uint64_t)sh.reward_type);
+    add(kSnapDone, "done", 1);
+    add(kSnapEpisode, "episode", 4);
+    add(kSnapTileMap, "tile_map", 8u * ((2u * HW + 63u) / 64u));
+    add(kSnapEpisodeSteps, "episode_steps", 4);
+    add(kSnapTruncated, "truncated", 1);
+    if (sh.goal) {
+        add(kSnapGoalField, "goal_distance.field", 2u * HW);
+        add(kSnapGoalDistance, "goal_distance.distance", 4);
+        add(kSnapGoalStart, "goal_distance.start_distance", 4);
+        add(kSnapGoalProgress, "goal_distance.progress", 4);
+        add(kSnapGoalLast, "goal_distance.last_episode", 4);
+    }
+    if (sh.seen) {
+        add(kSnapSeenCount, "seen_map.seen_count", 4);
+        add(kSnapSeenNew, "seen_map.newly_seen", 4);
+        add(kSnapSeenGoal, "seen_map.goal_seen", 4);
+        add(kSnapSeenLast, "seen_map.last_episode", 4);
+        add(kSnapSeenBits, "seen_map.bits", 4u * ((HW + 31u) / 32u));
+        add(kSnapSeenMap, "seen_map.map", HW);
+    }
+    if (sh.view_fmt) {
+        const uint32_t frame = (uint32_t)sh.view_C * (uint32_t)sh.view_h * (uint32_t)sh.view_w;
+        const uint64_t tag = (uint64_t)sh.view_h | (uint64_t)sh.view_w << 16 | (uint64_t)sh.view_fmt << 32 | (uint64_t)sh.view_layout << 40 | (uint64_t)sh.view_frames << 48;
+        if (sh.view_frames > 1) {
+            add(kSnapViewStack, "learner_view.stack", frame * (uint32_t)sh.view_frames, tag);
+            add(kSnapViewLast, "learner_view.last_episode", 4);
+        } else {
+            add(kSnapViewFrame, "learner_view.frame", frame, tag);
+        }
+    }
+    if (sh.local_source)
+        add(kSnapLocalImage, "local_map.image", (uint32_t)sh.local_size * (uint32_t)sh.local_size,
+            (uint64_t)sh.local_size | (uint64_t)sh.local_cells << 16 | (uint64_t)sh.local_source << 32);
+    if (sh.source_kind) {
+        add(kSnapSourceLast, "layout_source.last_episode", 4, (uint64_t)sh.source_kind);
+        add(kSnapSourceLayout, "layout_source.layout", 4, (uint64_t)sh.source_kind);
+    }
+    if (sh.stats) {
+        add(kSnapStatsFinished, "episode_stats.finished", 1);
+        add(kSnapStatsOutcome, "episode_stats.outcome", 1);
+        add(kSnapStatsLength, "episode_stats.length", 4);
+        add(kSnapStatsMoves, "episode_stats.moves", 4);
+        add(kSnapStatsLevel, "episode_stats.level", 4);
+        add(kSnapStatsSpl, "episode_stats.spl_q16", 4);
+        add(kSnapStatsEpisodes, "episode_stats.episodes", 4);
+        add(kSnapStatsPrevX, "episode_stats.prev_x", real);
+        add(kSnapStatsPrevY, "episode_stats.prev_y", real);
+        add(kSnapStatsLast, "episode_stats.last_episode", 4);
+    }
+    uint64_t k = 0xcbf29ce484222325ull;                                    // FNV-1a, a byte at a time
+    const auto mix = [&k](uint64_t v, int bytes) { for (int b = 0; b < bytes; ++b) { k ^= (v >> (8 * b)) & 0xffu; k *= 0x100000001b3ull; } };
+    for (int s = 0; s < p.n; ++s) {
+        p.row_bytes += p.seg[s].bytes;
+        for (const char* c = p.seg[s].name; *c; ++c) mix((uint8_t)*c, 1);
+        mix(p.seg[s].bytes, 4);
+        mix(p.seg[s].tag, 8);
+    }
+    for (int32_t v : {sh.H, sh.W, sh.nd, sh.N, sh.Hc, sh.real64, sh.reward_type, (int32_t)RCW_ABI_VERSION}) mix((uint32_t)v, 4);
+    p.key = k;
+}
+
+// The name of the first segment by which `now` — the handle's shape at a save or a restore — differs from `bound`, the archive's; NULL: none.
+const char* snapshot_plan_differs(const SnapshotPlan& bound, const SnapshotPlan& now)
+{
+    for (int k = 0; k < bound.n || k < now.n; ++k) {
+        if (k >= now.n) return bound.seg[k].name;
+        if (k >= bound.n) return now.seg[k].name;
+        const SnapshotSegment& a = bound.seg[k], &b = now.seg[k];
+        if (a.field != b.field) return a.field < b.field ? a.name : b.name;   // (the table is in the enum's order: the lower one is the one the other side lacks)
+        if (a.bytes != b.bytes || a.tag != b.tag) return a.name;
+    }
+    return nullptr;
+}
+
+// rcw_snapshot_rows_load's check of ONE exported row: the fields a kernel indexes with — goal interior, direction in range, position finite
+// and inside the room, the map's border WALL bits set and its padding clear, the layout index in the source's range.  Everything else is
+// the caller's word, as rcw_set_walls' layouts are.  msg: the field and why.
+int validate_snapshot_row(const SnapshotShape& sh, const SnapshotPlan& plan, const uint8_t* row, char* msg, size_t cap)
+{
+    const int H = sh.H, W = sh.W;
+    const auto at = [&](SnapshotField f) { return row + plan.offset(plan.find(f)); };
+    int32_t goal[2], dir;
+    std::memcpy(goal, at(kSnapGoal), sizeof goal);
+    std::memcpy(&dir, at(kSnapDir), sizeof dir);
+    if (goal[0] < 2 || goal[0] > H - 1 || goal[1] < 2 || goal[1] > W - 1) {
+        std::snprintf(msg, cap, "goal: (%d,%d) not an interior tile", goal[0], goal[1]);
+        return RCW_ERR_INVALID_ARGUMENT;
+    }
+    if (dir < 0 || dir >= sh.nd) {
+        std::snprintf(msg, cap, "dir: %d not in 0..%d", dir, sh.nd - 1);
+        return RCW_ERR_INVALID_ARGUMENT;
+    }
+    double x, y;
+    if (sh.real64) { double v[2]; std::memcpy(v, at(kSnapPos), sizeof v); x = v[0]; y = v[1]; }
+    else { float v[2]; std::memcpy(v, at(kSnapPos), sizeof v); x = v[0]; y = v[1]; }
+    if (!(std::isfinite(x) && std::isfinite(y) && x >= 1.0 && x < (double)(H - 1) && y >= 1.0 && y < (double)(W - 1))) {
+        std::snprintf(msg, cap, "%s: (%g,%g) not inside the room", sh.real64 ? "pos64" : "pos", x, y);
+        return RCW_ERR_INVALID_ARGUMENT;
+    }
+    const uint8_t* const map = at(kSnapTileMap);
+    const uint32_t map_bits = 8u * plan.seg[plan.find(kSnapTileMap)].bytes;
+    const auto bit = [map](uint32_t b) { return (map[b >> 3] >> (b & 7u)) & 1u; };
+    for (int j = 0; j < W; ++j)
+        for (int i = 0; i < H; ++i)
+            if ((i == 0 || i == H - 1 || j == 0 || j == W - 1) && !bit(2u * ((uint32_t)i + (uint32_t)H * (uint32_t)j))) {
+                std::snprintf(msg, cap, "tile_map: the border tile (%d,%d) is not a wall", i + 1, j + 1);
+                return RCW_ERR_INVALID_ARGUMENT;
+            }
+    for (uint32_t b = 2u * (uint32_t)H * (uint32_t)W; b < map_bits; ++b)
+        if (bit(b)) {
+            std::snprintf(msg, cap, "tile_map: padding bit %u is set", b);
+            return RCW_ERR_INVALID_ARGUMENT;
+        }
+    if (sh.source_kind) {
+        int32_t layout;
+        std::memcpy(&layout, at(kSnapSourceLayout), sizeof layout);
+        const bool bank = sh.source_kind == kLayoutBank;
+        const int32_t lo = bank ? 0 : (sh.levels > 0 ? sh.first_level : -1), count = bank ? sh.layouts : (sh.levels > 0 ? sh.levels : 1);
+        if (layout < lo || (int64_t)layout >= (int64_t)lo + count) {
+            std::snprintf(msg, cap, "layout_source.layout: %d not in %d..%lld", layout, lo, (long long)lo + count - 1);
+            return RCW_ERR_INVALID_ARGUMENT;
+        }
+    }
+    return RCW_OK;
+}
+
 #ifdef RCW_DEV_SWITCHES
 #include "dev/api_plan_export.inc"   // the rules and the step's facts without a device (tests/test_top_view_plan.py, tests/test_step_state.py)
 #endif

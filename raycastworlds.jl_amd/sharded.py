@@ -213,6 +213,19 @@ class ShardedSingleRoom:
         """`SingleRoom.set_wall_bank_weights`, the same weights on every rank."""
         self.env.set_wall_bank_weights(weights)
 
+    # ---- the state archive: every shard has its own, rows are LOCAL ---------------------------
+    def set_snapshots(self, rows: int) -> None:
+        """`SingleRoom.set_snapshots` of this rank's engine: `rows` records a SHARD.  Rows do not cross shards."""
+        self.env.set_snapshots(rows)
+
+    def snapshot_save(self, rows=None, mask=None) -> None:
+        """`SingleRoom.snapshot_save` with this rank's LOCAL arrays (one entry per local agent, local row indices)."""
+        self.env.snapshot_save(rows, mask)
+
+    def snapshot_restore(self, rows=None, mask=None) -> None:
+        """`SingleRoom.snapshot_restore` with this rank's LOCAL arrays."""
+        self.env.snapshot_restore(rows, mask)
+
     # ---- the observation gather over torch.distributed -------------------------------------
     def _as_tensor(self, x):
         import torch

@@ -355,7 +355,9 @@ class SingleRoom:
     addition; a dict of `set_wall_caves`' keywords, `{}` for the defaults) is applied right behind it: a new cave made on the device at
     every episode start.  It excludes `wall_bank` and `wall_generator`.  `wall_rooms` (this build's addition; a dict of
     `set_wall_rooms`' keywords, `{}` for the defaults) is applied behind that: new rooms and doorways made on the device at every
-    episode start.  It excludes the other three.
+    episode start.  It excludes the other three.  `snapshots` (this build's addition; a number of rows) is `set_snapshots` last of all,
+    with every feature above already on: the state archive of `snapshot_save` / `snapshot_restore`.  The learner view is set after
+    construction: bind the archive behind it (`set_snapshots`) where one is wanted.
     """
 
     def __init__(
@@ -397,6 +399,7 @@ class SingleRoom:
         wall_caves=None,
         wall_rooms=None,
         episode_stats: bool = False,
+        snapshots: int = 0,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -525,6 +528,12 @@ class SingleRoom:
         if episode_stats:
             try:
                 self.set_episode_stats(True)
+            except BaseException:
+                self._handle.close()
+                raise
+        if snapshots:
+            try:
+                self.set_snapshots(snapshots)
             except BaseException:
                 self._handle.close()
                 raise
@@ -1017,6 +1026,91 @@ class SingleRoom:
         """Zero the table, stream-ordered and without waiting for the stream; the per-agent words stay.  What a replay loop calls after
         it has read the table."""
         self._check(self._lib.rcw_episode_stats_clear(self._h))
+
+    # ---- the state archive (include/rcw.h, rcw_set_snapshots) ----------------------------
+    def set_snapshots(self, rows: int) -> None:
+        """Bind the state archive: `rows` agent records kept on the device, none filled, laid out for the features that are on NOW
+        (enable the goal distance, the seen map, the learner view, the local map, the layout source and the statistics first: a save or
+        restore after any of them changed is refused until the archive is bound again).  0 frees it."""
+        self._check(self._lib.rcw_set_snapshots(self._h, int(rows)))
+
+    @property
+    def snapshot_info(self) -> dict:
+        """`rows`, `row_bytes` (one record, as `snapshot_export` hands it out) and `shape_key` (rcw_snapshot_info)."""
+        rows, row_bytes, key = C.c_int32(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.rcw_snapshot_info(self._h, C.byref(rows), C.byref(row_bytes), C.byref(key)))
+        return {"rows": rows.value, "row_bytes": row_bytes.value, "shape_key": key.value}
+
+    def _snapshot_call(self, what: str, rows, mask) -> None:
+        on_device = [x is not None and (isinstance(x, DeviceArray) or (_is_device_tensor(x) and x.is_cuda)) for x in (rows, mask)]
+        if any(on_device):
+            if not all(d or x is None for d, x in zip(on_device, (rows, mask))):
+                raise ValueError(f"snapshot_{what}: rows and mask must both be on the device or both on the host")
+            ptrs, tensors = [], []
+            for x, itemsize, name in ((rows, 4, "rows: int32"), (mask, 1, "mask: uint8 or bool")):
+                if x is None:
+                    ptrs.append(None)
+                    continue
+                if isinstance(x, DeviceArray):
+                    ok, ptr = x.dtype.itemsize == itemsize and x.shape == (self.batch,), x.ptr
+                else:
+                    ok, ptr = x.element_size() == itemsize and x.numel() == self.batch and x.is_contiguous() and not x.is_floating_point(), x.data_ptr()
+                    tensors.append(x)
+                if not ok:
+                    raise ValueError(f"snapshot_{what}: device {name}, contiguous, of length batch")
+                ptrs.append(C.c_void_p(ptr))
+            cross = bool(tensors) and self._order_behind_torch()
+            self._check(getattr(self._lib, f"rcw_snapshot_{what}_device")(self._h, *ptrs))
+            if cross:
+                self._release_after_use(*tensors)
+            return
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        for x, name in ((r, "rows"), (m, "mask")):
+            if x is not None and x.shape != (self.batch,):
+                raise ValueError(f"snapshot_{what}: {name} must have length batch")
+        self.host_syncs += 1
+        self._check(getattr(self._lib, f"rcw_snapshot_{what}")(self._h, _as_ptr(r), _as_ptr(m)))
+
+    def snapshot_save(self, rows=None, mask=None) -> None:
+        """Save the records of the agents of `mask` (None: all) into the rows `rows` (int32 (B,); None: agent a into row a).  numpy
+        arrays or None: checked on the host — a bad index or two agents into one row raise ValueError and change nothing —, and the call
+        waits for the stream.  `DeviceArray`s or CUDA torch tensors: stream-ordered, no host wait; a bad index leaves that agent out and
+        sets its status word and the error word (`sync()` raises, `clear_error()` clears), and of two agents into one row the higher wins."""
+        self._snapshot_call("save", rows, mask)
+
+    def snapshot_restore(self, rows=None, mask=None) -> None:
+        """Put the agents of `mask` back as the rows `rows` hold them — several agents may take one row — and render them again.  The
+        arguments as for `snapshot_save`; an unfilled row is a bad index."""
+        self._snapshot_call("restore", rows, mask)
+
+    @property
+    def snapshot_filled(self) -> np.ndarray:
+        """bool (rows,): which rows a save or an import has filled (waits for the stream)."""
+        out = np.zeros(self.snapshot_info["rows"], dtype=np.uint8)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_snapshot_filled(self._h, _as_ptr(out)))
+        return out.astype(bool)
+
+    def snapshot_export(self, first: int = 0, count: Optional[int] = None) -> dict:
+        """Rows [first, first + count) on the host: `dict(shape_key, row_bytes, rows=uint8 (count, row_bytes))` — what
+        `snapshot_import` of an environment of the same shape takes, in this process or a later one."""
+        info = self.snapshot_info
+        count = info["rows"] - first if count is None else int(count)
+        out = np.zeros((max(count, 0), info["row_bytes"]), dtype=np.uint8)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_snapshot_rows_copy(self._h, int(first), count, _as_ptr(out)))
+        return {"shape_key": info["shape_key"], "row_bytes": info["row_bytes"], "rows": out}
+
+    def snapshot_import(self, d: dict, first: int = 0) -> None:
+        """Load `snapshot_export`'s rows into rows [first, ...) and count them as filled.  Another shape key is refused; so is a row whose
+        goal, direction, position, map border or layout index a kernel could not index with (ValueError naming row and field).  Everything
+        else in a row is trusted."""
+        rows = np.ascontiguousarray(d["rows"], dtype=np.uint8)
+        if rows.ndim != 2 or rows.shape[1] != self.snapshot_info["row_bytes"]:
+            raise ValueError(f"snapshot_import: rows must be uint8 (count, {self.snapshot_info['row_bytes']})")
+        self.host_syncs += 1
+        self._check(self._lib.rcw_snapshot_rows_load(self._h, int(first), rows.shape[0], C.c_void_p(rows.ctypes.data), int(d["shape_key"])))
 
     # ---- the seen map (include/rcw.h, rcw_set_seen_map) ---------------------------------
     def set_seen_map(self, on: bool = True) -> None:
