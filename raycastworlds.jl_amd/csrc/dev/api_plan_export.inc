@@ -112,6 +112,30 @@ __attribute__((visibility("default"))) int rcw_dev_snapshot_plan(const int32_t* 
     *row_bytes = plan.row_bytes; *key = plan.key;
     return plan.n;
 }
+// The per-agent arrays of one feature (AgentFeature: 0 core state, 1 goal distance, 2 seen map, 3 learner view, 4 local map, 5 layout source,
+// 6 episode statistics) of that shape, and their carve for `batch` agents as ONE buffer behind the feature's head (tests/
+// test_agent_arrays_spec.py): names a line each; ids, bytes (per agent), archived, offsets [n]; returns n (0: the feature is off), -1: names
+// too small.
+__attribute__((visibility("default"))) int rcw_dev_agent_arrays(const int32_t* shape, int32_t feature, int32_t batch, char* names, int32_t cap, int32_t* ids,
+                                                               uint32_t* bytes, uint8_t* archived, uint64_t* offsets, uint64_t* head, uint64_t* total)
+{
+    if (!shape || feature < 0 || feature >= kFeatCount || batch < 1 || !names || cap < 1 || !ids || !bytes || !archived || !offsets || !head || !total) return RCW_ERR_INVALID_ARGUMENT;
+    SnapshotShape sh;
+    std::memcpy(&sh, shape, sizeof sh);
+    AgentArrays a;
+    agent_arrays(sh, feature, &a);
+    const AgentCarve c = carve_agent_arrays(a.head, a.part, a.n, (uint64_t)batch);
+    int n = 0;
+    names[0] = 0;
+    for (int k = 0; k < a.n; ++k) {
+        const int w = std::snprintf(names + n, (size_t)(cap - n), "%s\n", a.part[k].name);
+        if (w < 0 || n + w >= cap) return -1;
+        n += w;
+        ids[k] = a.part[k].id; bytes[k] = a.part[k].bytes; archived[k] = a.part[k].archived; offsets[k] = c.off[k];
+    }
+    *head = a.head; *total = c.total;
+    return a.n;
+}
 // rcw_snapshot_rows_load's check of one exported row of that shape: validate_snapshot_row's return code, its reason in msg
 __attribute__((visibility("default"))) int rcw_dev_snapshot_validate_row(const int32_t* shape, const uint8_t* row, char* msg, int32_t cap)
 {

@@ -141,13 +141,82 @@ int upload_mask(rcw_handle* h, const uint8_t* mask_host, const uint8_t** mask_de
     return RCW_OK;
 }
 
-template <typename T>
-int copy_out(rcw_handle* h, T* out_host, const void* dev, size_t count)
+// ---- the per-agent arrays (rcw_handle.h): the shape, the carve into a buffer, the swap, the two readouts ------------------------------------
+// What of the handle fixes its arrays and the archive's record NOW (and, for rcw_snapshot_rows_load's check, the layout source's range).
+SnapshotShape snapshot_shape(const rcw_handle* h)
 {
-    if (!out_host) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL output pointer");
-    int rc = sync_and_check(h);
-    RCW_HIP(hipMemcpy(out_host, dev, count * sizeof(T), hipMemcpyDeviceToHost));
+    SnapshotShape s;
+    s.H = h->dev.H; s.W = h->dev.W; s.nd = h->dev.nd; s.N = h->dev.N; s.Hc = h->dev.Hc;
+    s.real64 = h->real64 ? 1 : 0; s.reward_type = h->cfg.reward_type;
+    s.goal = h->goal.on(); s.seen = h->seen.on(); s.stats = h->stats.on();
+    const rcw_handle::LearnerView& lv = h->learner;
+    if (lv.on()) { s.view_fmt = lv.set.fmt; s.view_layout = lv.set.layout; s.view_C = lv.view.C; s.view_h = lv.set.h; s.view_w = lv.set.w; s.view_frames = lv.set.frames; }
+    if (h->local.on()) { s.local_source = h->local.source; s.local_size = h->local.size; s.local_cells = h->local.cells_per_tile; }
+    s.source_kind = (int32_t)h->source.dev.kind;
+    s.layouts = h->source.dev.agents.layouts; s.levels = h->source.dev.gen.levels; s.first_level = h->source.dev.gen.first_level;
+    return s;
+}
+
+// ONE buffer of a feature a setter is building: `head` bytes, then parts [first, first + n) of `list` for the handle's agents
+// (carve_agent_arrays).  at: the parts' entries, indexed as rcw_handle::live is; *bytes: the carve's total, allocated or not.
+hipError_t alloc_parts(const rcw_handle* h, RcwBuf& buf, const AgentArrays& list, int first, int n, uint64_t head, LiveArray* at, size_t* bytes = nullptr)
+{
+    const AgentCarve c = carve_agent_arrays(head, list.part + first, n, (uint64_t)h->B);
+    if (bytes) *bytes = (size_t)c.total;
+    const hipError_t e = buf.hipMalloc((size_t)c.total);
+    for (int k = 0; k < n && e == hipSuccess; ++k) at[list.part[first + k].id] = LiveArray{buf.get<uint8_t>() + c.off[k], list.part[first + k].bytes};
+    return e;
+}
+
+// THE way a feature is swapped in, behind which the setter says `feature = std::move(fresh)` (an owner that takes another over frees what it
+// had): every stream is waited for as for replace_buffers — queued work may still use the old arrays —, then the table takes the
+// feature's entries of `at` — all null where the feature is switched off.  A failed wait leaves the handle as it was.
+hipError_t take_live(rcw_handle* h, int feature, const LiveArray* at)
+{
+    const hipError_t e = replace_buffers(h, {});
+    for (int id = kFeatureFirstId[feature]; id < kFeatureFirstId[feature + 1] && e == hipSuccess; ++id) h->live[id] = at[id];
+    return e;
+}
+
+// Why a readout is refused while its feature is off.
+const char* const kNoLearnerView = "the handle has no learner view (rcw_set_learner_view)";
+const char* const kNoGoalDistance = "the handle has no goal distance (rcw_set_goal_distance)";
+const char* const kNoSeenMap = "the handle has no seen map (rcw_set_seen_map)";
+const char* const kNoLocalMap = "the handle has no local map (rcw_set_local_map)";
+const char* const kNoDrawnWalls = "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms)";
+const char* const kNoEpisodeStats = "the handle keeps no episode statistics (rcw_set_episode_stats)";
+int need(bool on, const char* why_off) { return on ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "%s", why_off); }
+
+// (the array of the learner view the caller sees: the k-frame stack, or the one frame)
+SnapshotField view_id(const rcw_handle* h) { return h && h->learner.set.frames > 1 ? kSnapViewStack : kSnapViewFrame; }
+
+// THE readout to the host, behind check_handle: every array of `outs` whose host pointer is not NULL, for all agents or — ranged — agents
+// [first, first + count), behind ONE sync_and_check.  The checks in their order: the feature is off (why_off; NULL: the core state, always
+// on), a bad range or a NULL pointer (ranged: of the one array; else a lone array's — of several, any may be NULL), the sticky device error.
+struct HostOut { void* host; SnapshotField id; };
+int copy_arrays(rcw_handle* h, const char* why_off, std::initializer_list<HostOut> outs, bool ranged = false, int32_t first = 0, int32_t count = 0)
+{
+    int rc = need(!why_off || h->live[outs.begin()->id].ptr, why_off); if (rc) return rc;
+    if (ranged) { rc = check_range(h, outs.begin()->host != nullptr, first, count); if (rc) return rc; }
+    else if (outs.size() == 1 && !outs.begin()->host) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL output pointer");
+    if (!ranged) count = h->B;
+    rc = sync_and_check(h);
+    for (const HostOut& o : outs) {
+        const LiveArray& a = h->live[o.id];
+        if (o.host) RCW_HIP(hipMemcpy(o.host, a.as<uint8_t>() + (size_t)first * a.bytes, (size_t)count * a.bytes, hipMemcpyDeviceToHost));
+    }
     return rc;
+}
+
+// ... and the arrays' device pointers, which waits for nothing: a lone pointer must not be NULL, of several any may be.
+struct DeviceOut { void** ptr; SnapshotField id; };
+int hand_out(rcw_handle* h, const char* why_off, std::initializer_list<DeviceOut> outs)
+{
+    if (!h || (outs.size() == 1 && !outs.begin()->ptr)) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    const int rc = need(!why_off || h->live[outs.begin()->id].ptr, why_off); if (rc) return rc;
+    for (const DeviceOut& o : outs)
+        if (o.ptr) *o.ptr = h->live[o.id].ptr;
+    return RCW_OK;
 }
 
 }  // namespace
@@ -229,16 +298,17 @@ int rcw_create(const rcw_config* cfg, int32_t batch, int32_t device, uint64_t se
     h->stream = h->own_stream.get();
     RCW_HIP(h->ev_start.hipEventCreate());
     RCW_HIP(h->ev_stop.hipEventCreate());
-    RCW_HIP(h->d_pos.hipMalloc(B * 2 * h->real_size));
-    RCW_HIP(h->d_dir.hipMalloc(B * sizeof(int32_t)));
-    RCW_HIP(h->d_goal.hipMalloc(B * sizeof(int2)));
-    h->reward_size = (cfg->reward_type == RCW_REWARD_FLOAT64 || cfg->reward_type == RCW_REWARD_INT64) ? 8 : 4;
-    RCW_HIP(h->d_reward.hipMalloc(B * h->reward_size));
-    RCW_HIP(h->d_done.hipMalloc(B));
-    RCW_HIP(h->d_episode.hipMalloc(B * sizeof(uint32_t)));
-    RCW_HIP(h->d_episode_steps.hipMalloc(B * sizeof(uint32_t)));
-    RCW_HIP(h->d_truncated.hipMalloc(B));
-    RCW_HIP(h->d_tile_map.hipMalloc(B * (size_t)h->nchunks * sizeof(uint64_t) + 16));   // (+ 2 words: the flat top store kernel reads three words from any word of a map)
+    {   // the core state: a buffer a part (+ 2 words: the flat top store kernel reads three words from any word of a map)
+        SnapshotShape sh;
+        sh.H = H; sh.W = W; sh.real64 = h->real64; sh.reward_type = cfg->reward_type;
+        AgentArrays core;
+        agent_arrays(sh, kFeatCore, &core);
+        RcwBuf* const buf[] = {&h->d_pos, &h->d_dir, &h->d_goal, &h->d_reward, &h->d_done, &h->d_episode, &h->d_tile_map, &h->d_episode_steps, &h->d_truncated};
+        for (int k = 0; k < core.n; ++k) {
+            RCW_HIP(buf[k]->hipMalloc(B * core.part[k].bytes + 16));
+            h->live[core.part[k].id] = LiveArray{buf[k]->get(), core.part[k].bytes};
+        }
+    }
     RCW_HIP(h->d_dir_table.hipMalloc((size_t)nd * 2 * h->real_size));
     RCW_HIP(h->d_ray_table.hipMalloc((size_t)nd * RCW_TABLE_ROWS * N * h->real_size));
     RCW_HIP(h->d_obs.hipMalloc(B * (size_t)N * Hc * sizeof(uint32_t)));
@@ -465,35 +535,35 @@ int refuse_other_source(rcw_handle* h, const char* caller, RcwLayoutKind wants)
 // THE off branch of a setter: the agents keep the walls they have.  A source of another kind is not this call's to end.
 int drop_layout_source(rcw_handle* h, RcwLayoutKind kind)
 {
-    LayoutSource& ls = h->source;
-    if (!ls.is(kind)) return RCW_OK;
-    RCW_HIP(replace_buffers(h, {&ls.words, &ls.cum, &ls.agents}));
-    ls.h_cum.reset(); ls.ev_cum.reset();
-    ls.total_weight = 0;
-    ls.dev = RcwLayoutSource{};
+    if (!h->source.is(kind)) return RCW_OK;
+    const LiveArray none[kSnapFieldCount] = {};
+    RCW_HIP(take_live(h, kFeatSource, none));
+    h->source = LayoutSource();
     return RCW_OK;
 }
 
-// THE install, behind a setter's validation and staging.  `fresh` holds the kind and its parameters and — the bank, which allocates everything
-// before it changes anything — the bank's resources with the per-agent block; a family's block is allocated here.  An allocation that fails
-// leaves the handle as it was.  Then the handle takes `fresh` over, the bank's weights and layouts are uploaded, and every agent is
+// THE install, behind a setter's validation and staging.  `fresh` holds the kind and its parameters and — the bank — the bank's resources; the
+// per-agent arrays of every kind are carved here.  An allocation that fails leaves the handle as it was.  Then the handle takes `fresh`
+// over, the bank's weights and layouts are uploaded, and every agent is
 // restarted under the source's rule: the body of rcw_reset(h, NULL, <the handle's seed>) with the source's kernel forced for every agent.
 int install_layout_source(rcw_handle* h, LayoutSource& fresh)
 {
     LayoutSource& ls = h->source;
-    const size_t B = (size_t)h->B, agent_bytes = 3 * B * sizeof(uint32_t) + B;
-    if (!fresh.agents.get()) {
-        const hipError_t e = fresh.agents.hipMalloc(agent_bytes);
-        if (e != hipSuccess) return fail(hip_code(e), "%s: %s", kSourceWords[fresh.dev.kind].name, hip_failure(e));
-    }
-    RCW_HIP(replace_buffers(h, {&ls.words, &ls.cum, &ls.agents}, {&fresh.words, &fresh.cum, &fresh.agents}));
-    ls.h_cum = std::move(fresh.h_cum); ls.ev_cum = std::move(fresh.ev_cum);
-    ls.total_weight = fresh.total_weight;
-    ls.dev = fresh.dev;
-    uint32_t* const q = ls.agents.get<uint32_t>();
+    SnapshotShape sh = snapshot_shape(h);
+    sh.source_kind = fresh.dev.kind;
+    AgentArrays list;
+    agent_arrays(sh, kFeatSource, &list);
+    LiveArray at[kSnapFieldCount] = {};
+    size_t agent_bytes = 0;
+    const hipError_t e = alloc_parts(h, fresh.agents, list, 0, list.n, 0, at, &agent_bytes);
+    if (e != hipSuccess) return fail(hip_code(e), "%s: %s", kSourceWords[fresh.dev.kind].name, hip_failure(e));
+    RCW_HIP(take_live(h, kFeatSource, at));
+    ls = std::move(fresh);
     RcwWallBank& v = ls.dev.agents;
     v.words = ls.words.get<uint32_t>(); v.cum = ls.cum.get<uint32_t>();
-    v.last_episode = q; v.status_seen = reinterpret_cast<int32_t*>(q + B); v.layout = reinterpret_cast<int32_t*>(q + 2 * B); v.mask = reinterpret_cast<uint8_t*>(q + 3 * B);
+    v.last_episode = at[kSnapSourceLast].as<uint32_t>(); v.status_seen = at[kSnapSourceStatus].as<int32_t>();
+    v.layout = at[kSnapSourceLayout].as<int32_t>(); v.mask = at[kSnapSourceMask].as<uint8_t>();
+    const size_t B = (size_t)h->B;
     if (ls.is(kLayoutBank)) {                                          // (the weights wait in h_cum, the layouts in d_in_walls)
         RCW_HIP(hipMemcpyAsync(ls.cum.get(), ls.h_cum.get(), (size_t)v.layouts * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         RCW_HIP(hipEventRecord(ls.ev_cum.get(), h->stream));
@@ -730,31 +800,27 @@ int rcw_reward(rcw_handle* h, float* out)
     int rc = check_handle(h); if (rc) return rc;
     if (h->cfg.reward_type != RCW_REWARD_FLOAT32)
         return fail(RCW_ERR_UNSUPPORTED, "rcw_reward: the handle's reward type is not Float32; use rcw_reward_typed");
-    return copy_out(h, out, h->d_reward.get(), (size_t)h->B);
+    return copy_arrays(h, nullptr, {{out, kSnapReward}});
 }
-int rcw_reward_typed(rcw_handle* h, void* out)
-{
-    int rc = check_handle(h); if (rc) return rc;
-    return copy_out(h, static_cast<uint8_t*>(out), h->d_reward.get(), (size_t)h->B * h->reward_size);
-}
-int rcw_done(rcw_handle* h, uint8_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_done.get(), (size_t)h->B); }
+int rcw_reward_typed(rcw_handle* h, void* out) { int rc = check_handle(h); if (rc) return rc; return copy_arrays(h, nullptr, {{out, kSnapReward}}); }
+int rcw_done(rcw_handle* h, uint8_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_arrays(h, nullptr, {{out, kSnapDone}}); }
 int rcw_position(rcw_handle* h, float* out)
 {
     int rc = check_handle(h); if (rc) return rc;
     rc = check_real(h, false, "rcw_position"); if (rc) return rc;
-    return copy_out(h, out, h->d_pos.get(), (size_t)2 * h->B);
+    return copy_arrays(h, nullptr, {{out, kSnapPos}});
 }
 int rcw_position64(rcw_handle* h, double* out)
 {
     int rc = check_handle(h); if (rc) return rc;
     rc = check_real(h, true, "rcw_position64"); if (rc) return rc;
-    return copy_out(h, out, h->d_pos.get(), (size_t)2 * h->B);
+    return copy_arrays(h, nullptr, {{out, kSnapPos}});
 }
-int rcw_direction(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_dir.get(), (size_t)h->B); }
-int rcw_goal(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_goal.get(), (size_t)2 * h->B); }
-int rcw_episode(rcw_handle* h, uint32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_episode.get(), (size_t)h->B); }
-int rcw_episode_steps(rcw_handle* h, uint32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_episode_steps.get(), (size_t)h->B); }
-int rcw_truncated(rcw_handle* h, uint8_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_out(h, out, h->d_truncated.get(), (size_t)h->B); }
+int rcw_direction(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_arrays(h, nullptr, {{out, kSnapDir}}); }
+int rcw_goal(rcw_handle* h, int32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_arrays(h, nullptr, {{out, kSnapGoal}}); }
+int rcw_episode(rcw_handle* h, uint32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_arrays(h, nullptr, {{out, kSnapEpisode}}); }
+int rcw_episode_steps(rcw_handle* h, uint32_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_arrays(h, nullptr, {{out, kSnapEpisodeSteps}}); }
+int rcw_truncated(rcw_handle* h, uint8_t* out) { int rc = check_handle(h); if (rc) return rc; return copy_arrays(h, nullptr, {{out, kSnapTruncated}}); }
 
 int rcw_status(rcw_handle* h, int32_t* out)
 {
@@ -765,27 +831,10 @@ int rcw_status(rcw_handle* h, int32_t* out)
     return RCW_OK;
 }
 
-int rcw_reward_device_ptr(rcw_handle* h, void** p)
-{
-    if (!h || !p) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    *p = h->d_reward.get(); return RCW_OK;
-}
-int rcw_done_device_ptr(rcw_handle* h, void** p)
-{
-    if (!h || !p) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    *p = h->d_done.get(); return RCW_OK;
-}
-
-int rcw_episode_steps_device_ptr(rcw_handle* h, void** p)
-{
-    if (!h || !p) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    *p = h->d_episode_steps.get(); return RCW_OK;
-}
-int rcw_truncated_device_ptr(rcw_handle* h, void** p)
-{
-    if (!h || !p) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    *p = h->d_truncated.get(); return RCW_OK;
-}
+int rcw_reward_device_ptr(rcw_handle* h, void** p) { return hand_out(h, nullptr, {{p, kSnapReward}}); }
+int rcw_done_device_ptr(rcw_handle* h, void** p) { return hand_out(h, nullptr, {{p, kSnapDone}}); }
+int rcw_episode_steps_device_ptr(rcw_handle* h, void** p) { return hand_out(h, nullptr, {{p, kSnapEpisodeSteps}}); }
+int rcw_truncated_device_ptr(rcw_handle* h, void** p) { return hand_out(h, nullptr, {{p, kSnapTruncated}}); }
 
 int rcw_tile_map_num_chunks(rcw_handle* h, int32_t* out)
 {
@@ -795,7 +844,7 @@ int rcw_tile_map_num_chunks(rcw_handle* h, int32_t* out)
 int rcw_tile_map_chunks(rcw_handle* h, uint64_t* out)
 {
     int rc = check_handle(h); if (rc) return rc;
-    return copy_out(h, out, h->d_tile_map.get(), (size_t)h->nchunks * h->B);
+    return copy_arrays(h, nullptr, {{out, kSnapTileMap}});
 }
 
 extern "C++" {
@@ -896,24 +945,27 @@ int rcw_set_learner_view_stack(rcw_handle* h, int32_t format, int32_t layout, in
     rcw_handle::LearnerView& lv = h->learner;
     const bool was_only = lv.only();
     rcw_handle::LearnerView fresh;
+    LiveArray at[kSnapFieldCount] = {};
     if (format != RCW_VIEW_OFF) {
         fresh.set = {format, layout, height, width, flags, frames};
         fresh.view = plan.v;
-        const size_t bytes = (size_t)h->B * plan.v.C * (size_t)height * width, tab_bytes = plan.tab.size() * sizeof(int32_t);
-        hipError_t e = fresh.frame.hipMalloc(bytes);
-        if (e == hipSuccess) e = fresh.tab.hipMalloc(tab_bytes);
-        if (e == hipSuccess) e = hipMemcpy(fresh.tab.get(), plan.tab.data(), tab_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && frames > 1) e = fresh.stack.hipMalloc(bytes * (size_t)frames);
-        if (e == hipSuccess && frames > 1) e = fresh.last_episode.hipMalloc((size_t)h->B * sizeof(uint32_t));
+        SnapshotShape sh = snapshot_shape(h);
+        sh.view_fmt = format; sh.view_layout = layout; sh.view_C = plan.v.C; sh.view_h = height; sh.view_w = width; sh.view_frames = frames;
+        AgentArrays list;                                          // the stack, its counter, the kernels' frame — or that frame alone; head: the box tables
+        agent_arrays(sh, kFeatView, &list);
+        hipError_t e = list.head == plan.tab.size() * sizeof(int32_t) ? alloc_parts(h, fresh.frame, list, list.n - 1, 1, 0, at) : hipErrorInvalidValue;
+        if (e == hipSuccess) e = fresh.tab.hipMalloc((size_t)list.head);
+        if (e == hipSuccess) e = hipMemcpy(fresh.tab.get(), plan.tab.data(), (size_t)list.head, hipMemcpyHostToDevice);
+        if (e == hipSuccess && frames > 1) e = alloc_parts(h, fresh.stack, list, 0, 1, 0, at);
+        if (e == hipSuccess && frames > 1) e = alloc_parts(h, fresh.last_episode, list, 1, 1, 0, at);
         if (e != hipSuccess)                                       // the handle keeps its previous view
-            return fail(hip_code(e), "learner view buffer of %zu bytes: %s", bytes * (size_t)frames, hip_failure(e));
+            return fail(hip_code(e), "learner view buffer of %zu bytes: %s", (size_t)h->B * list.part[0].bytes, hip_failure(e));
         fresh.view.rows = fresh.tab.get<int32_t>();
         fresh.view.cols = fresh.tab.get<int32_t>() + height + 1;
         fresh.view.dsum = plan.v.depth ? fresh.tab.get<int32_t>() + height + width + 2 : nullptr;
     }
-    RCW_HIP(replace_buffers(h, {&lv.frame, &lv.tab, &lv.stack, &lv.last_episode}, {&fresh.frame, &fresh.tab, &fresh.stack, &fresh.last_episode}));   // (the new ones, or none: the view switched off)
-    lv.set = fresh.set;
-    lv.view = fresh.view;
+    RCW_HIP(take_live(h, kFeatView, at));                          // (the new view, or none: the view switched off)
+    lv = std::move(fresh);
     if (lv.on()) {
         // the view kernel reads the descriptors: every step of the handle refreshes them from now on (as for rcw_columns_device_ptr)
         h->step.columns_wanted();
@@ -945,23 +997,12 @@ int rcw_learner_view_info(rcw_handle* h, int32_t* format, int32_t* layout, int32
     return RCW_OK;
 }
 
-int rcw_learner_view_device_ptr(rcw_handle* h, void** device_ptr)
-{
-    if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!h->learner.on()) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
-    *device_ptr = h->learner.batch();
-    return RCW_OK;
-}
+int rcw_learner_view_device_ptr(rcw_handle* h, void** device_ptr) { return hand_out(h, kNoLearnerView, {{device_ptr, view_id(h)}}); }
 
 int rcw_learner_view_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32_t count)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (!h->learner.on()) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
-    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
-    rc = sync_and_check(h);
-    const size_t per = h->learner.agent_bytes();
-    RCW_HIP(hipMemcpy(out_host, h->learner.batch() + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
-    return rc;
+    return copy_arrays(h, kNoLearnerView, {{out_host, view_id(h)}}, true, first, count);
 }
 
 // The goal distance (include/rcw.h).  Enabling allocates and floods every agent at once, stream-ordered behind what is queued; enabling
@@ -972,17 +1013,21 @@ int rcw_set_goal_distance(rcw_handle* h, int32_t enable)
     rcw_handle::GoalDistance& gd = h->goal;
     if (!enable && !gd.on()) return RCW_OK;
     rcw_handle::GoalDistance fresh;
+    LiveArray at[kSnapFieldCount] = {};
     if (enable) {
-        const size_t B = (size_t)h->B, bytes = B * (size_t)h->dev.H * (size_t)h->dev.W * sizeof(uint16_t);
-        hipError_t e = fresh.field.hipMalloc(bytes);
-        if (e == hipSuccess) e = fresh.word_buf.hipMalloc(3 * B * sizeof(int32_t));
-        if (e == hipSuccess) e = fresh.last_episode.hipMalloc(B * sizeof(uint32_t));
+        SnapshotShape sh = snapshot_shape(h);
+        sh.goal = 1;
+        AgentArrays list;                                          // the field | the three words | the counter: a buffer each
+        agent_arrays(sh, kFeatGoal, &list);
+        size_t bytes = 0;
+        hipError_t e = alloc_parts(h, fresh.field, list, 0, 1, 0, at, &bytes);
+        if (e == hipSuccess) e = alloc_parts(h, fresh.word_buf, list, 1, 3, 0, at);
+        if (e == hipSuccess) e = alloc_parts(h, fresh.last_episode, list, 4, 1, 0, at);
         if (e != hipSuccess) return fail(hip_code(e), "goal distance field of %zu bytes: %s", bytes, hip_failure(e));
-        int32_t* const w = fresh.word_buf.get<int32_t>();
-        fresh.words = RcwGoalWords{w, w + B, w + 2 * B};
+        fresh.words = RcwGoalWords{at[kSnapGoalDistance].as<int32_t>(), at[kSnapGoalStart].as<int32_t>(), at[kSnapGoalProgress].as<int32_t>()};
     }
-    RCW_HIP(replace_buffers(h, {&gd.field, &gd.word_buf, &gd.last_episode}, {&fresh.field, &fresh.word_buf, &fresh.last_episode}));
-    gd.words = fresh.words;
+    RCW_HIP(take_live(h, kFeatGoal, at));
+    gd = std::move(fresh);
     if (gd.on()) RCW_HIP(launch_goal_distance(h, nullptr, kStackRefill));
     return RCW_OK;
 }
@@ -994,53 +1039,24 @@ int rcw_goal_distance_enabled(rcw_handle* h, int32_t* out)
     return RCW_OK;
 }
 
-extern "C++" {
-namespace {
-int need_goal_distance(rcw_handle* h) { return h->goal.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no goal distance (rcw_set_goal_distance)"); }
-}  // namespace
-}  // extern "C++"
-
 int rcw_goal_distance(rcw_handle* h, int32_t* distance, int32_t* start_distance, int32_t* progress)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_goal_distance(h); if (rc) return rc;
-    rc = sync_and_check(h);
-    const size_t bytes = (size_t)h->B * sizeof(int32_t);
-    const RcwGoalWords& w = h->goal.words;
-    if (distance) RCW_HIP(hipMemcpy(distance, w.distance, bytes, hipMemcpyDeviceToHost));
-    if (start_distance) RCW_HIP(hipMemcpy(start_distance, w.start_distance, bytes, hipMemcpyDeviceToHost));
-    if (progress) RCW_HIP(hipMemcpy(progress, w.progress, bytes, hipMemcpyDeviceToHost));
-    return rc;
+    return copy_arrays(h, kNoGoalDistance, {{distance, kSnapGoalDistance}, {start_distance, kSnapGoalStart}, {progress, kSnapGoalProgress}});
 }
 
 int rcw_goal_distance_device_ptr(rcw_handle* h, void** distance, void** start_distance, void** progress)
 {
-    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = need_goal_distance(h); if (rc) return rc;
-    if (distance) *distance = h->goal.words.distance;
-    if (start_distance) *start_distance = h->goal.words.start_distance;
-    if (progress) *progress = h->goal.words.progress;
-    return RCW_OK;
+    return hand_out(h, kNoGoalDistance, {{distance, kSnapGoalDistance}, {start_distance, kSnapGoalStart}, {progress, kSnapGoalProgress}});
 }
 
 int rcw_goal_distance_field(rcw_handle* h, int32_t first, int32_t count, void* out_host)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_goal_distance(h); if (rc) return rc;
-    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
-    rc = sync_and_check(h);
-    const size_t per = (size_t)h->dev.H * (size_t)h->dev.W;
-    RCW_HIP(hipMemcpy(out_host, h->goal.field.get<uint16_t>() + (size_t)first * per, (size_t)count * per * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    return rc;
+    return copy_arrays(h, kNoGoalDistance, {{out_host, kSnapGoalField}}, true, first, count);
 }
 
-int rcw_goal_distance_field_device_ptr(rcw_handle* h, void** ptr)
-{
-    if (!h || !ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = need_goal_distance(h); if (rc) return rc;
-    *ptr = h->goal.field.get();
-    return RCW_OK;
-}
+int rcw_goal_distance_field_device_ptr(rcw_handle* h, void** ptr) { return hand_out(h, kNoGoalDistance, {{ptr, kSnapGoalField}}); }
 
 // The seen map (include/rcw.h).  Enabling allocates and marks every agent afresh at once, stream-ordered behind what is queued; enabling
 // again does the same again; an allocation failure leaves what was there.
@@ -1052,20 +1068,22 @@ int rcw_set_seen_map(rcw_handle* h, int32_t enable)
     if (!enable && h->local.source == RCW_LOCAL_SEEN)
         return fail(RCW_ERR_UNSUPPORTED, "the handle's local map reads the seen map: switch the local map off first (rcw_set_local_map)");
     rcw_handle::SeenMap fresh;
+    LiveArray at[kSnapFieldCount] = {};
     if (enable) {
-        // words and counter | packed bits | map: every part starts on a multiple of four bytes
-        const size_t B = (size_t)h->B, HW = (size_t)h->dev.H * (size_t)h->dev.W, bwords = (HW + 31) / 32;
-        const size_t bytes = 4 * B * sizeof(int32_t) + B * bwords * sizeof(uint32_t) + B * HW;
-        const hipError_t e = fresh.buf.hipMalloc(bytes);
+        SnapshotShape sh = snapshot_shape(h);
+        sh.seen = 1;
+        AgentArrays list;
+        agent_arrays(sh, kFeatSeen, &list);
+        size_t bytes = 0;
+        const hipError_t e = alloc_parts(h, fresh.buf, list, 0, list.n, 0, at, &bytes);
         if (e != hipSuccess) return fail(hip_code(e), "seen map of %zu bytes: %s", bytes, hip_failure(e));
-        int32_t* const w = fresh.buf.get<int32_t>();
-        fresh.words = RcwSeenWords{w, w + B, w + 2 * B};
-        fresh.last_episode = reinterpret_cast<uint32_t*>(w + 3 * B);
-        fresh.bits = fresh.last_episode + B;
-        fresh.map = reinterpret_cast<uint8_t*>(fresh.bits + B * bwords);
+        fresh.words = RcwSeenWords{at[kSnapSeenCount].as<int32_t>(), at[kSnapSeenNew].as<int32_t>(), at[kSnapSeenGoal].as<int32_t>()};
+        fresh.last_episode = at[kSnapSeenLast].as<uint32_t>();
+        fresh.bits = at[kSnapSeenBits].as<uint32_t>();
+        fresh.map = at[kSnapSeenMap].as<uint8_t>();
     }
-    RCW_HIP(replace_buffers(h, {&sm.buf}, {&fresh.buf}));
-    sm.words = fresh.words; sm.last_episode = fresh.last_episode; sm.bits = fresh.bits; sm.map = fresh.map;
+    RCW_HIP(take_live(h, kFeatSeen, at));
+    sm = std::move(fresh);
     if (sm.on()) RCW_HIP(launch_seen_map(h, nullptr, kStackRefill));
     if (sm.on()) RCW_HIP(launch_local_map(h, kStackRefill));
     return RCW_OK;
@@ -1078,53 +1096,24 @@ int rcw_seen_map_enabled(rcw_handle* h, int32_t* out)
     return RCW_OK;
 }
 
-extern "C++" {
-namespace {
-int need_seen_map(rcw_handle* h) { return h->seen.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no seen map (rcw_set_seen_map)"); }
-}  // namespace
-}  // extern "C++"
-
 int rcw_seen_words(rcw_handle* h, int32_t* seen_count, int32_t* newly_seen, int32_t* goal_seen)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_seen_map(h); if (rc) return rc;
-    rc = sync_and_check(h);
-    const size_t bytes = (size_t)h->B * sizeof(int32_t);
-    const RcwSeenWords& w = h->seen.words;
-    if (seen_count) RCW_HIP(hipMemcpy(seen_count, w.seen_count, bytes, hipMemcpyDeviceToHost));
-    if (newly_seen) RCW_HIP(hipMemcpy(newly_seen, w.newly_seen, bytes, hipMemcpyDeviceToHost));
-    if (goal_seen) RCW_HIP(hipMemcpy(goal_seen, w.goal_seen, bytes, hipMemcpyDeviceToHost));
-    return rc;
+    return copy_arrays(h, kNoSeenMap, {{seen_count, kSnapSeenCount}, {newly_seen, kSnapSeenNew}, {goal_seen, kSnapSeenGoal}});
 }
 
 int rcw_seen_words_device_ptr(rcw_handle* h, void** seen_count, void** newly_seen, void** goal_seen)
 {
-    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = need_seen_map(h); if (rc) return rc;
-    if (seen_count) *seen_count = h->seen.words.seen_count;
-    if (newly_seen) *newly_seen = h->seen.words.newly_seen;
-    if (goal_seen) *goal_seen = h->seen.words.goal_seen;
-    return RCW_OK;
+    return hand_out(h, kNoSeenMap, {{seen_count, kSnapSeenCount}, {newly_seen, kSnapSeenNew}, {goal_seen, kSnapSeenGoal}});
 }
 
 int rcw_seen_map(rcw_handle* h, int32_t first, int32_t count, void* out_host)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_seen_map(h); if (rc) return rc;
-    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
-    rc = sync_and_check(h);
-    const size_t per = (size_t)h->dev.H * (size_t)h->dev.W;
-    RCW_HIP(hipMemcpy(out_host, h->seen.map + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
-    return rc;
+    return copy_arrays(h, kNoSeenMap, {{out_host, kSnapSeenMap}}, true, first, count);
 }
 
-int rcw_seen_map_device_ptr(rcw_handle* h, void** ptr)
-{
-    if (!h || !ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = need_seen_map(h); if (rc) return rc;
-    *ptr = h->seen.map;
-    return RCW_OK;
-}
+int rcw_seen_map_device_ptr(rcw_handle* h, void** ptr) { return hand_out(h, kNoSeenMap, {{ptr, kSnapSeenMap}}); }
 
 // The local map (include/rcw.h).  Enabling allocates and computes every agent's image at once, stream-ordered behind what is queued; new
 // parameters replace the old; an allocation failure leaves what was there.
@@ -1138,18 +1127,22 @@ int rcw_set_local_map(rcw_handle* h, int32_t source, int32_t size, int32_t cells
         return fail(RCW_ERR_UNSUPPORTED, "RCW_LOCAL_SEEN needs the handle's seen map (rcw_set_seen_map)");
     if (source == 0 && !lm.on()) return RCW_OK;
     rcw_handle::LocalMap fresh;
+    LiveArray at[kSnapFieldCount] = {};
     if (source != 0) {
-        // offset table | images: the images start on a multiple of 16 bytes
-        const size_t tbytes = (table.size() + 15) & ~(size_t)15, bytes = tbytes + (size_t)h->B * (size_t)size * (size_t)size;
-        hipError_t e = fresh.buf.hipMalloc(bytes);
+        SnapshotShape sh = snapshot_shape(h);
+        sh.local_source = source; sh.local_size = size; sh.local_cells = cells_per_tile;
+        AgentArrays list;                                          // head: the offset table
+        agent_arrays(sh, kFeatLocal, &list);
+        size_t bytes = 0;
+        hipError_t e = list.head == table.size() ? alloc_parts(h, fresh.buf, list, 0, list.n, list.head, at, &bytes) : hipErrorInvalidValue;
         if (e == hipSuccess) e = hipMemcpy(fresh.buf.get(), table.data(), table.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail(hip_code(e), "local map of %zu bytes: %s", bytes, hip_failure(e));
         fresh.source = source; fresh.size = size; fresh.cells_per_tile = cells_per_tile;
         fresh.off = fresh.buf.get();
-        fresh.img = fresh.buf.get<uint8_t>() + tbytes;
+        fresh.img = at[kSnapLocalImage].as<uint8_t>();
     }
-    RCW_HIP(replace_buffers(h, {&lm.buf}, {&fresh.buf}));
-    lm.source = fresh.source; lm.size = fresh.size; lm.cells_per_tile = fresh.cells_per_tile; lm.off = fresh.off; lm.img = fresh.img;
+    RCW_HIP(take_live(h, kFeatLocal, at));
+    lm = std::move(fresh);
     RCW_HIP(launch_local_map(h, kStackRefill));
     return RCW_OK;
 }
@@ -1163,41 +1156,21 @@ int rcw_local_map_info(rcw_handle* h, int32_t* source, int32_t* size, int32_t* c
     return RCW_OK;
 }
 
-extern "C++" {
-namespace {
-int need_local_map(rcw_handle* h) { return h->local.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no local map (rcw_set_local_map)"); }
-}  // namespace
-}  // extern "C++"
-
-int rcw_local_map_device_ptr(rcw_handle* h, void** device_ptr)
-{
-    if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = need_local_map(h); if (rc) return rc;
-    *device_ptr = h->local.img;
-    return RCW_OK;
-}
+int rcw_local_map_device_ptr(rcw_handle* h, void** device_ptr) { return hand_out(h, kNoLocalMap, {{device_ptr, kSnapLocalImage}}); }
 
 int rcw_local_map_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32_t count)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_local_map(h); if (rc) return rc;
-    rc = check_range(h, out_host != nullptr, first, count); if (rc) return rc;
-    rc = sync_and_check(h);
-    const size_t per = (size_t)h->local.size * (size_t)h->local.size;
-    RCW_HIP(hipMemcpy(out_host, h->local.img + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost));
-    return rc;
+    return copy_arrays(h, kNoLocalMap, {{out_host, kSnapLocalImage}}, true, first, count);
 }
 
 extern "C++" {
 namespace {
-int need_wall_bank(rcw_handle* h) { return h->source.is(kLayoutBank) ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no wall bank (rcw_set_wall_bank)"); }
 // (the table's level rows were counted from the source that is live: it stays until the statistics are switched off)
 int refuse_under_episode_stats(rcw_handle* h, const char* caller)
 {
     return h->stats.on() ? fail(RCW_ERR_UNSUPPORTED, "%s: the handle keeps episode statistics, whose level rows follow the layout source; switch them off first (rcw_set_episode_stats(h, 0))", caller) : RCW_OK;
 }
-int need_drawn_walls(rcw_handle* h) { return h->source.live() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms)"); }
-
 }  // namespace
 }  // extern "C++"
 
@@ -1213,7 +1186,7 @@ int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
     if (layouts < 0) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_set_wall_bank: layouts must be >= 0 (got %d)", layouts);
     if (validate_walls(H, W, layouts, walls_host, layouts, nullptr, nullptr, why, sizeof why) != RCW_OK)   // (a layout each of `layouts` agents: every one is checked)
         return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_set_wall_bank: %s", why);
-    const size_t B = (size_t)h->B, L = (size_t)layouts, bytes = L * (size_t)H * (size_t)W, nwords = (size_t)h->dev.nwords;
+    const size_t L = (size_t)layouts, bytes = L * (size_t)H * (size_t)W, nwords = (size_t)h->dev.nwords;
     std::vector<uint32_t> cum;
     try { cum.resize(L); } catch (const std::bad_alloc&) { return fail(RCW_ERR_OUT_OF_MEMORY, "host allocation of the cumulative weights failed"); }
     LayoutSource fresh;
@@ -1221,7 +1194,6 @@ int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
     {
         hipError_t e = fresh.words.hipMalloc(L * nwords * sizeof(uint32_t));
         if (e == hipSuccess) e = fresh.cum.hipMalloc(L * sizeof(uint32_t));
-        if (e == hipSuccess) e = fresh.agents.hipMalloc(3 * B * sizeof(uint32_t) + B);
         if (e == hipSuccess) e = fresh.h_cum.hipHostMalloc(L * sizeof(uint32_t));
         if (e == hipSuccess) e = fresh.ev_cum.hipEventCreate(hipEventDisableTiming);
         if (e != hipSuccess) return fail(hip_code(e), "wall bank of %d layouts: %s", layouts, hip_failure(e));
@@ -1244,7 +1216,7 @@ int rcw_set_wall_bank(rcw_handle* h, const uint8_t* walls_host, int32_t layouts,
 int rcw_set_wall_bank_weights(rcw_handle* h, const uint32_t* weights_host)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_wall_bank(h); if (rc) return rc;
+    rc = need(h->source.is(kLayoutBank), "the handle has no wall bank (rcw_set_wall_bank)"); if (rc) return rc;
     LayoutSource& wb = h->source;
     const int32_t layouts = wb.dev.agents.layouts;
     const size_t L = (size_t)layouts;
@@ -1271,17 +1243,10 @@ int rcw_wall_bank_info(rcw_handle* h, int32_t* layouts, uint64_t* total_weight)
 int rcw_wall_layout(rcw_handle* h, int32_t* out_host)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_drawn_walls(h); if (rc) return rc;
-    return copy_out<int32_t>(h, out_host, h->source.dev.agents.layout, (size_t)h->B);
+    return copy_arrays(h, kNoDrawnWalls, {{out_host, kSnapSourceLayout}});
 }
 
-int rcw_wall_layout_device_ptr(rcw_handle* h, void** device_ptr)
-{
-    if (!h || !device_ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = need_drawn_walls(h); if (rc) return rc;
-    *device_ptr = h->source.dev.agents.layout;
-    return RCW_OK;
-}
+int rcw_wall_layout_device_ptr(rcw_handle* h, void** device_ptr) { return hand_out(h, kNoDrawnWalls, {{device_ptr, kSnapSourceLayout}}); }
 
 // The wall generator's mazes (include/rcw.h, "the wall generator").
 int rcw_set_wall_generator(rcw_handle* h, int32_t enable, uint32_t loops, int32_t levels, int32_t first_level, uint64_t level_seed)
@@ -1372,24 +1337,26 @@ int rcw_set_episode_stats(rcw_handle* h, int32_t enable)
     rcw_handle::EpisodeStats& es = h->stats;
     if (!enable && !es.on()) return RCW_OK;
     rcw_handle::EpisodeStats fresh;
+    LiveArray at[kSnapFieldCount] = {};
     if (enable) {
         RcwEpisodeStats& d = fresh.dev;
         plan_episode_stats_rows(h->source.dev.kind, h->source.dev.agents.layouts, h->source.dev.gen.levels, h->source.dev.gen.first_level, &d.rows, &d.first);
-        // table | previous x, y | six 4-byte arrays | two byte arrays: every part starts on a multiple of its element's size
-        const size_t B = (size_t)h->B, tbytes = fresh.table_bytes(), bytes = tbytes + 2 * B * h->real_size + 6 * B * sizeof(uint32_t) + 2 * B;
-        const hipError_t e = fresh.buf.hipMalloc(bytes);
+        SnapshotShape sh = snapshot_shape(h);
+        sh.stats = 1;
+        AgentArrays list;                                          // head: the table
+        agent_arrays(sh, kFeatStats, &list);
+        size_t bytes = 0;
+        const hipError_t e = list.head == fresh.table_bytes() ? alloc_parts(h, fresh.buf, list, 0, list.n, list.head, at, &bytes) : hipErrorInvalidValue;
         if (e != hipSuccess) return fail(hip_code(e), "episode statistics of %zu bytes: %s", bytes, hip_failure(e));
-        uint8_t* const base = fresh.buf.get<uint8_t>();
-        d.table = reinterpret_cast<uint64_t*>(base);
-        d.prev_x = base + tbytes;
-        d.prev_y = base + tbytes + B * h->real_size;
-        uint32_t* const w = reinterpret_cast<uint32_t*>(base + tbytes + 2 * B * h->real_size);
-        uint8_t* const b = reinterpret_cast<uint8_t*>(w + 6 * B);
-        d.words = RcwEpisodeWords{b, b + B, w, w + B, reinterpret_cast<int32_t*>(w + 2 * B), reinterpret_cast<int32_t*>(w + 3 * B), w + 4 * B};
-        d.last_episode = w + 5 * B;
+        d.table = fresh.buf.get<uint64_t>();
+        d.prev_x = at[kSnapStatsPrevX].ptr;
+        d.prev_y = at[kSnapStatsPrevY].ptr;
+        d.words = RcwEpisodeWords{at[kSnapStatsFinished].as<uint8_t>(), at[kSnapStatsOutcome].as<uint8_t>(), at[kSnapStatsLength].as<uint32_t>(), at[kSnapStatsMoves].as<uint32_t>(),
+                                  at[kSnapStatsLevel].as<int32_t>(), at[kSnapStatsSpl].as<int32_t>(), at[kSnapStatsEpisodes].as<uint32_t>()};
+        d.last_episode = at[kSnapStatsLast].as<uint32_t>();
     }
-    RCW_HIP(replace_buffers(h, {&es.buf}, {&fresh.buf}));
-    es.dev = fresh.dev;
+    RCW_HIP(take_live(h, kFeatStats, at));
+    es = std::move(fresh);
     if (es.on()) {
         RCW_HIP(hipMemsetAsync(es.dev.table, 0, es.table_bytes(), h->stream));
         RCW_HIP(hipMemsetAsync(es.dev.words.episodes, 0, (size_t)h->B * sizeof(uint32_t), h->stream));
@@ -1407,48 +1374,23 @@ int rcw_episode_stats_info(rcw_handle* h, int32_t* enabled, int32_t* rows, int32
     return RCW_OK;
 }
 
-extern "C++" {
-namespace {
-int need_episode_stats(rcw_handle* h) { return h->stats.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle keeps no episode statistics (rcw_set_episode_stats)"); }
-}  // namespace
-}  // extern "C++"
-
 int rcw_episode_stats(rcw_handle* h, uint8_t* finished, uint8_t* outcome, uint32_t* length, uint32_t* moves, int32_t* level, int32_t* spl_q16, uint32_t* episodes)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_episode_stats(h); if (rc) return rc;
-    rc = sync_and_check(h);
-    const size_t B = (size_t)h->B;
-    const RcwEpisodeWords& w = h->stats.dev.words;
-    if (finished) RCW_HIP(hipMemcpy(finished, w.finished, B, hipMemcpyDeviceToHost));
-    if (outcome) RCW_HIP(hipMemcpy(outcome, w.outcome, B, hipMemcpyDeviceToHost));
-    if (length) RCW_HIP(hipMemcpy(length, w.length, B * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (moves) RCW_HIP(hipMemcpy(moves, w.moves, B * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (level) RCW_HIP(hipMemcpy(level, w.level, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (spl_q16) RCW_HIP(hipMemcpy(spl_q16, w.spl_q16, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (episodes) RCW_HIP(hipMemcpy(episodes, w.episodes, B * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return rc;
+    return copy_arrays(h, kNoEpisodeStats, {{finished, kSnapStatsFinished}, {outcome, kSnapStatsOutcome}, {length, kSnapStatsLength}, {moves, kSnapStatsMoves},
+                                            {level, kSnapStatsLevel}, {spl_q16, kSnapStatsSpl}, {episodes, kSnapStatsEpisodes}});
 }
 
 int rcw_episode_stats_device_ptr(rcw_handle* h, void** finished, void** outcome, void** length, void** moves, void** level, void** spl_q16, void** episodes)
 {
-    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = need_episode_stats(h); if (rc) return rc;
-    const RcwEpisodeWords& w = h->stats.dev.words;
-    if (finished) *finished = w.finished;
-    if (outcome) *outcome = w.outcome;
-    if (length) *length = w.length;
-    if (moves) *moves = w.moves;
-    if (level) *level = w.level;
-    if (spl_q16) *spl_q16 = w.spl_q16;
-    if (episodes) *episodes = w.episodes;
-    return RCW_OK;
+    return hand_out(h, kNoEpisodeStats, {{finished, kSnapStatsFinished}, {outcome, kSnapStatsOutcome}, {length, kSnapStatsLength}, {moves, kSnapStatsMoves},
+                                         {level, kSnapStatsLevel}, {spl_q16, kSnapStatsSpl}, {episodes, kSnapStatsEpisodes}});
 }
 
 int rcw_episode_stats_table(rcw_handle* h, uint64_t* out_host)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_episode_stats(h); if (rc) return rc;
+    rc = need(h->stats.on(), kNoEpisodeStats); if (rc) return rc;
     if (!out_host) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL output pointer");
     rc = sync_and_check(h);
     RCW_HIP(hipMemcpy(out_host, h->stats.dev.table, h->stats.table_bytes(), hipMemcpyDeviceToHost));
@@ -1458,7 +1400,7 @@ int rcw_episode_stats_table(rcw_handle* h, uint64_t* out_host)
 int rcw_episode_stats_table_device_ptr(rcw_handle* h, void** ptr)
 {
     if (!h || !ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
-    int rc = need_episode_stats(h); if (rc) return rc;
+    int rc = need(h->stats.on(), kNoEpisodeStats); if (rc) return rc;
     *ptr = h->stats.dev.table;
     return RCW_OK;
 }
@@ -1467,7 +1409,7 @@ int rcw_episode_stats_table_device_ptr(rcw_handle* h, void** ptr)
 int rcw_episode_stats_clear(rcw_handle* h)
 {
     int rc = check_handle(h); if (rc) return rc;
-    rc = need_episode_stats(h); if (rc) return rc;
+    rc = need(h->stats.on(), kNoEpisodeStats); if (rc) return rc;
     RCW_HIP(hipMemsetAsync(h->stats.dev.table, 0, h->stats.table_bytes(), h->stream));
     return RCW_OK;
 }
@@ -1478,22 +1420,7 @@ namespace {
 
 using Snapshots = rcw_handle::Snapshots;
 
-// What of the handle fixes a record's layout NOW (and, for rcw_snapshot_rows_load's check, the layout source's range).
-SnapshotShape snapshot_shape(const rcw_handle* h)
-{
-    SnapshotShape s;
-    s.H = h->dev.H; s.W = h->dev.W; s.nd = h->dev.nd; s.N = h->dev.N; s.Hc = h->dev.Hc;
-    s.real64 = h->real64 ? 1 : 0; s.reward_type = h->cfg.reward_type;
-    s.goal = h->goal.on(); s.seen = h->seen.on(); s.stats = h->stats.on();
-    const rcw_handle::LearnerView& lv = h->learner;
-    if (lv.on()) { s.view_fmt = lv.set.fmt; s.view_layout = lv.set.layout; s.view_C = lv.view.C; s.view_h = lv.set.h; s.view_w = lv.set.w; s.view_frames = lv.set.frames; }
-    if (h->local.on()) { s.local_source = h->local.source; s.local_size = h->local.size; s.local_cells = h->local.cells_per_tile; }
-    s.source_kind = (int32_t)h->source.dev.kind;
-    s.layouts = h->source.dev.agents.layouts; s.levels = h->source.dev.gen.levels; s.first_level = h->source.dev.gen.first_level;
-    return s;
-}
-
-int need_snapshots(rcw_handle* h) { return h->snaps.on() ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "the handle has no state archive (rcw_set_snapshots)"); }
+int need_snapshots(rcw_handle* h) { return need(h->snaps.on(), "the handle has no state archive (rcw_set_snapshots)"); }
 
 // A save or a restore of a handle whose shape is no longer the archive's is refused, and names the first segment that differs.
 int check_snapshot_shape(rcw_handle* h, const char* caller)
@@ -1594,9 +1521,8 @@ int rcw_set_snapshots(rcw_handle* h, int32_t rows)
         fresh.rows = rows;
         RCW_HIP(hipMemsetAsync(base, 0, bytes, h->stream));            // (no row is filled; an unfilled row reads as zeros)
     }
-    RCW_HIP(replace_buffers(h, {&sn.buf}, {&fresh.buf}));
-    sn.plan = fresh.plan; sn.rows = fresh.rows; sn.owner = fresh.owner; sn.sel = fresh.sel; sn.in_rows = fresh.in_rows; sn.filled = fresh.filled;
-    std::memcpy(sn.arc, fresh.arc, sizeof sn.arc);
+    RCW_HIP(replace_buffers(h, {}));                                   // (every stream waited for: queued work may still use the old rows)
+    sn = std::move(fresh);
     return RCW_OK;
 }
 
@@ -1691,7 +1617,7 @@ int rcw_expand_columns_view(rcw_handle* h, const int32_t* height_line_pu_device,
                             int32_t count, void* view_device)
 {
     int rc = check_handle(h); if (rc) return rc;
-    if (!h->learner.on()) return fail(RCW_ERR_UNSUPPORTED, "the handle has no learner view (rcw_set_learner_view)");
+    rc = need(h->learner.on(), kNoLearnerView); if (rc) return rc;
     if (!height_line_pu_device || !colour_id_device || !view_device || count < 1)
         return fail(RCW_ERR_INVALID_ARGUMENT, "bad argument");
     RCW_HIP(rcw_launch_view(h->dev, h->learner.view, height_line_pu_device, colour_id_device, count, nullptr, (uint8_t*)view_device, h->stream));

@@ -100,10 +100,18 @@ public:
     void restored() { forget(); obs_unknown(); }
 };
 
-// THE RECORD OF THE STATE ARCHIVE (include/rcw.h, "the state archive"): what of a handle fixes the layout of an agent's record, and the
-// layout — the segment table — it fixes.  Host values only: the development build plans without a device (rcw_dev_snapshot_plan).
-// A segment is one per-agent array of the handle; `tag` tells apart what the bytes alone do not (a learner view of 7 x 9 from one of
-// 9 x 7, a bank's layout index from a family's level).  key: FNV-1a over the table, the geometry, T, R and RCW_ABI_VERSION.
+// THE PER-AGENT ARRAYS OF A HANDLE, described ONCE (rcw_rules.hip, agent_arrays): per feature the list of its parts — an array each, [B] of
+// `bytes` — and the bytes of its head, what lies in front of them and is not per agent (the statistics' table, the local map's offset
+// table, the learner view's box tables).  Host values only, a function of SnapshotShape: the development build describes and carves without
+// a device (rcw_dev_agent_arrays).  Everything else follows from the list:
+//   the carve    carve_agent_arrays: the head, then the parts in list order, each on a multiple of 16 bytes.  A setter allocates the carve's
+//                total and takes every pointer from its offsets; a feature of several buffers (the goal distance: field | words | counter,
+//                the learner view: a buffer a part) carves each from its run of the list.
+//   the table    rcw_handle::live, indexed by the part's id: where the array is and its bytes per agent, null while its feature is off.
+//                The readouts (rcw_api.hip: copy_arrays, hand_out) and the archive's copy (launch_snapshot) look the arrays up there.
+//   the record   of the state archive (include/rcw.h, "the state archive"): plan_snapshot takes the `archived` parts of every feature that is
+//                on, in this order.  `tag` tells apart what the bytes alone do not (a learner view of 7 x 9 from one of 9 x 7, a bank's
+//                layout index from a family's level).  key: FNV-1a over the table, the geometry, T, R and RCW_ABI_VERSION.
 struct SnapshotShape {
     int32_t H = 0, W = 0, nd = 0, N = 0, Hc = 0;
     int32_t real64 = 0, reward_type = 0;
@@ -111,14 +119,28 @@ struct SnapshotShape {
     int32_t view_fmt = 0, view_layout = 0, view_C = 0, view_h = 0, view_w = 0, view_frames = 0;   // the learner view; view_fmt 0: off
     int32_t local_source = 0, local_size = 0, local_cells = 0;   // the local map; local_source 0: off
     int32_t source_kind = 0;                                     // RcwLayoutKind; 0: no layout source
-    int32_t layouts = 0, levels = 0, first_level = 0;            // the source's range (validate_snapshot_row; not part of the shape)
+    int32_t layouts = 0, levels = 0, first_level = 0;            // the source's range (validate_snapshot_row, the statistics' rows; not part of the record)
 };
+// (a part's id, in the order of the features and, within one, of its list; kSnapViewStaging — the view kernels' frame under a k-frame stack —,
+// kSnapSourceStatus and kSnapSourceMask are never archived)
 enum SnapshotField { kSnapPos, kSnapDir, kSnapGoal, kSnapReward, kSnapDone, kSnapEpisode, kSnapTileMap, kSnapEpisodeSteps, kSnapTruncated,
                      kSnapGoalField, kSnapGoalDistance, kSnapGoalStart, kSnapGoalProgress, kSnapGoalLast,
                      kSnapSeenCount, kSnapSeenNew, kSnapSeenGoal, kSnapSeenLast, kSnapSeenBits, kSnapSeenMap,
-                     kSnapViewFrame, kSnapViewStack, kSnapViewLast, kSnapLocalImage, kSnapSourceLast, kSnapSourceLayout,
+                     kSnapViewFrame, kSnapViewStack, kSnapViewLast, kSnapViewStaging, kSnapLocalImage,
+                     kSnapSourceLast, kSnapSourceStatus, kSnapSourceLayout, kSnapSourceMask,
                      kSnapStatsFinished, kSnapStatsOutcome, kSnapStatsLength, kSnapStatsMoves, kSnapStatsLevel, kSnapStatsSpl, kSnapStatsEpisodes,
                      kSnapStatsPrevX, kSnapStatsPrevY, kSnapStatsLast, kSnapFieldCount };
+enum AgentFeature { kFeatCore, kFeatGoal, kFeatSeen, kFeatView, kFeatLocal, kFeatSource, kFeatStats, kFeatCount };
+constexpr SnapshotField kFeatureFirstId[kFeatCount + 1] = {kSnapPos, kSnapGoalField, kSnapSeenCount, kSnapViewFrame, kSnapLocalImage, kSnapSourceLast, kSnapStatsFinished, kSnapFieldCount};
+constexpr int kAgentMaxParts = 10;
+struct AgentPart { SnapshotField id; const char* name; uint32_t bytes; uint64_t tag; bool archived; };
+struct AgentArrays { int32_t n = 0; AgentPart part[kAgentMaxParts] = {}; uint64_t head = 0; };   // (n = 0: the feature is off)
+struct AgentCarve { uint64_t off[kAgentMaxParts] = {}; uint64_t total = 0; };
+struct LiveArray {
+    void* ptr = nullptr;
+    uint32_t bytes = 0;                // per agent
+    template <typename T> T* as() const { return static_cast<T*>(ptr); }
+};
 constexpr int kSnapshotMaxSegments = kSnapFieldCount;
 struct SnapshotSegment { SnapshotField field; const char* name; uint32_t bytes; uint64_t tag; };
 struct SnapshotPlan {
@@ -142,6 +164,10 @@ struct rcw_handle {
     RcwEvent ev_start, ev_stop;
     // device allocations
     RcwBuf d_pos, d_dir, d_goal, d_reward, d_done, d_episode, d_episode_steps, d_truncated, d_tile_map, d_dir_table, d_ray_table, d_obs, d_col_h, d_col_c, d_err, d_status, d_top_view;
+    // THE TABLE OF THE LIVE PER-AGENT ARRAYS, by id (above: "the per-agent arrays of a handle"): rcw_create writes the core state's entries, a
+    // feature's setter its feature's — and clears them where it switches the feature off.  The features below keep the kernels' argument
+    // structs and typed pointers, filled from the same carve; which parts a feature has and how they lie in its buffers is agent_arrays' word.
+    LiveArray live[kSnapFieldCount];
     // two-kernel top view: planes / player pixels / tile codes in HBM, the side stream the draw kernel runs on
     RcwBuf d_top_plane, d_top_hdr, d_top_codes;
     // Several draw workgroups an agent (top_parts > 1) OR their bits into the agent's plane in HBM, and only rcw_top_store_kernel — which reads
@@ -167,7 +193,6 @@ struct rcw_handle {
     } prof;
     RcwBuf d_rays[4];                  // rcw_rays scratch (grow-only)
     size_t rays_cap[4] = {0, 0, 0, 0};
-    size_t reward_size = sizeof(float);
     // RCCL (loaded on demand): the observation gather
     void* comm = nullptr;              // ncclComm_t
     int32_t comm_rank = 0, comm_world = 0;
@@ -180,26 +205,24 @@ struct rcw_handle {
     std::vector<double> ray_table64;
     // The learner view (rcw_set_learner_view*): what the caller set, the view kernels' arguments, the buffers.  frames = k > 1: `frame` is the
     // staging batch the view kernels write, `stack` the B * k frames the caller sees, `last_episode` each agent's episode counter as of its
-    // last push (uint32 [B]); k = 1: `frame` is the view, the two are empty.  tab: the box tables (rows [h + 1], then columns [w + 1]).
+    // last push (uint32 [B]); k = 1: `frame` is the view, the two are empty.  A buffer a part of the list; tab: the list's head, the box
+    // tables (rows [h + 1], then columns [w + 1], then — depth formats — RcwView::dsum [Hc + 1]).
     struct LearnerView {
         struct Settings { int32_t fmt = RCW_VIEW_OFF, layout = RCW_VIEW_CHW, h = 0, w = 0, flags = 0, frames = 0; } set;
         RcwBuf frame, tab, stack, last_episode;
         RcwView view{};
         bool on() const { return set.fmt != RCW_VIEW_OFF; }
         bool only() const { return on() && (set.flags & RCW_VIEW_ONLY) != 0; }       // the step paints no camera view
-        size_t agent_bytes() const { return (size_t)set.frames * view.C * set.h * set.w; }   // one agent's whole output: its k frames
-        uint8_t* batch() const { return set.frames > 1 ? stack.get<uint8_t>() : frame.get<uint8_t>(); }   // what the caller sees
     } learner;
-    // The goal distance (rcw_set_goal_distance): the UInt16 (H*W, B) field, the three Int32 (B) words — one allocation, `words` points into
-    // it — and each agent's episode counter as of the flood its field holds (uint32 [B]).  Empty while the feature is off.
+    // The goal distance (rcw_set_goal_distance), THREE buffers: the UInt16 (H*W, B) field, the three Int32 (B) words — `words` points into
+    // their carve — and each agent's episode counter as of the flood its field holds (uint32 [B]).  Empty while the feature is off.
     struct GoalDistance {
         RcwBuf field, word_buf, last_episode;
         RcwGoalWords words{};
         bool on() const { return field.get() != nullptr; }
     } goal;
-    // The seen map (rcw_set_seen_map): ONE allocation — the three Int32 (B) words and each agent's episode counter as of its last clear
-    // (uint32 [B]), then the packed seen bits (uint32 [B][(H*W + 31) / 32], internal), then the UInt8 (H*W, B) map; the pointers point
-    // into it.  Empty while the feature is off.
+    // The seen map (rcw_set_seen_map): ONE buffer, the carve of its list — the three Int32 (B) words, each agent's episode counter as of its
+    // last clear, the packed seen bits (internal), the UInt8 (H*W, B) map; the pointers point into it.  Empty while the feature is off.
     struct SeenMap {
         RcwBuf buf;
         RcwSeenWords words{};
@@ -208,7 +231,7 @@ struct rcw_handle {
         uint8_t* map = nullptr;
         bool on() const { return buf.get() != nullptr; }
     } seen;
-    // The local map (rcw_set_local_map): ONE allocation — the offset table (S entries of the world-unit type, padded to 16 bytes), then the
+    // The local map (rcw_set_local_map): ONE buffer — the head is the offset table (S entries of the world-unit type), the one part the
     // UInt8 (S, S, B) images; the pointers point into it.  source = 0 and empty while the feature is off.  With RCW_LOCAL_SEEN the launch
     // reads seen.map as it is THEN: rcw_set_seen_map may have replaced it.
     struct LocalMap {
@@ -219,9 +242,8 @@ struct rcw_handle {
         bool on() const { return buf.get() != nullptr; }
     } local;
     // The layout source (rcw_kernels.h: the wall bank, or the wall generator's mazes, caves or rooms).  INVARIANT: at most one source is live —
-    // `dev.kind`, the only record of which —, and everything not of the live kind is empty or zero.  Every kind has `agents`, ONE allocation
-    // of the per-agent arrays — recorded counter, recorded status, layout index (the three 4-byte arrays), then the mask — into which
-    // `dev.agents` points.  The bank alone has the packed layouts, the cumulative weights, and the pinned buffer and event through which the
+    // `dev.kind`, the only record of which —, and everything not of the live kind is empty or zero.  Every kind has `agents`, ONE buffer, the
+    // carve of its list — recorded counter, recorded status, layout index, the mask — into which `dev.agents` points.  The bank alone has the packed layouts, the cumulative weights, and the pinned buffer and event through which the
     // weights reach `cum` (rcw_set_wall_bank_weights does not wait for the stream); of the bank the host keeps only its sizes: dev.agents.layouts
     // and the weights' sum.  A family's parameters travel as kernel arguments: dev.gen (the level rule, the maze's loops and grid), dev.caves, dev.rooms.
     struct LayoutSource {
@@ -233,10 +255,8 @@ struct rcw_handle {
         bool is(RcwLayoutKind k) const { return dev.kind == k; }
         bool live() const { return !is(kLayoutNone); }
     } source;
-    // Episode statistics (rcw_set_episode_stats): ONE allocation — the table (UInt64, 8 (1 + rows)), the two halves of the previous
-    // position (world-unit type [B] each), the six 4-byte arrays (length, moves, level, spl_q16, episodes, the private episode counter), then
-    // the two byte arrays (finished, outcome); dev's pointers point into it.  rows / first: fixed when enabled (plan_episode_stats_rows).
-    // Empty while the feature is off.
+    // Episode statistics (rcw_set_episode_stats): ONE buffer — the head is the table (UInt64, 8 (1 + rows)), then the carve of its list;
+    // dev's pointers point into it.  rows / first: fixed when enabled (plan_episode_stats_rows).  Empty while the feature is off.
     struct EpisodeStats {
         RcwBuf buf;
         RcwEpisodeStats dev{};
@@ -299,6 +319,8 @@ int plan_wall_bank_weights(const uint32_t* weights, int32_t layouts, uint32_t* c
 int plan_wall_generator(int32_t H, int32_t W, int32_t levels, int32_t first_level);
 int plan_wall_caves(int32_t H, int32_t W, int32_t smooth, int32_t levels, int32_t first_level);
 int plan_wall_rooms(int32_t H, int32_t W, int32_t room, int32_t levels, int32_t first_level);
+void agent_arrays(const SnapshotShape& sh, int feature, AgentArrays* out);
+AgentCarve carve_agent_arrays(uint64_t head, const AgentPart* part, int n, uint64_t B);
 void plan_snapshot(const SnapshotShape& sh, SnapshotPlan* plan);
 const char* snapshot_plan_differs(const SnapshotPlan& bound, const SnapshotPlan& now);   // the first segment that differs, NULL: the same shape
 int validate_snapshot_row(const SnapshotShape& sh, const SnapshotPlan& plan, const uint8_t* row, char* msg, size_t cap);

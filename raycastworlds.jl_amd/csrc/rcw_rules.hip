@@ -655,33 +655,37 @@ extern "C" int rcw_wall_rooms_layout(int32_t H, int32_t W, uint64_t key, int32_t
     return RCW_OK;
 }
 
-// THE STATE ARCHIVE'S RECORD (include/rcw.h, "the state archive"): the segment table of a handle of this shape, in the order an exported row
-// holds the segments.  A segment a per-agent array; what is off has none.  The local map's image is stored (and not computed again behind a
-// restore): its segment is then what binds the archive to the map's size.
-void plan_snapshot(const SnapshotShape& sh, SnapshotPlan* plan)
+// THE PER-AGENT ARRAYS (rcw_handle.h): the parts of `feature` (AgentFeature) of a handle of this shape, in the order an exported row of the
+// state archive holds them, and the bytes of the feature's head.  What is off has no parts and no head.  This is the ONE place that knows
+// an array's bytes per agent: the setters carve it, the archive records it, the readouts copy it.  `kept` = false: a part the archive
+// does not record.  The local map's image is recorded (and not computed again behind a restore): it is then what binds the archive to the
+// map's size.
+void agent_arrays(const SnapshotShape& sh, int feature, AgentArrays* out)
 {
-    SnapshotPlan& p = *plan;
-    p = SnapshotPlan{};
+    AgentArrays& p = *out;
+    p = AgentArrays{};
     const uint32_t real = sh.real64 ? 8u : 4u, HW = (uint32_t)sh.H * (uint32_t)sh.W;
     const uint32_t reward = (sh.reward_type == RCW_REWARD_FLOAT64 || sh.reward_type == RCW_REWARD_INT64) ? 8u : 4u;
-    const auto add = [&p](SnapshotField f, const char* name, uint32_t bytes, uint64_t tag = 0) { p.seg[p.n++] = SnapshotSegment{f, name, bytes, tag}; };
-    add(kSnapPos, sh.real64 ? "pos64" : "pos", 2 * real);
-    add(kSnapDir, "dir", 4);
-    add(kSnapGoal, "goal", 8);
-    add(kSnapReward, "reward", reward, (uint64_t)sh.reward_type);
-    add(kSnapDone, "done", 1);
-    add(kSnapEpisode, "episode", 4);
-    add(kSnapTileMap, "tile_map", 8u * ((2u * HW + 63u) / 64u));
-    add(kSnapEpisodeSteps, "episode_steps", 4);
-    add(kSnapTruncated, "truncated", 1);
-    if (sh.goal) {
+    const auto add = [&p](SnapshotField f, const char* name, uint32_t bytes, uint64_t tag = 0, bool kept = true) { p.part[p.n++] = AgentPart{f, name, bytes, tag, kept}; };
+    if (feature == kFeatCore) {
+        add(kSnapPos, sh.real64 ? "pos64" : "pos", 2 * real);
+        add(kSnapDir, "dir", 4);
+        add(kSnapGoal, "goal", 8);
+        add(kSnapReward, "reward", reward, (uint64_t)sh.reward_type);
+        add(kSnapDone, "done", 1);
+        add(kSnapEpisode, "episode", 4);
+        add(kSnapTileMap, "tile_map", 8u * ((2u * HW + 63u) / 64u));
+        add(kSnapEpisodeSteps, "episode_steps", 4);
+        add(kSnapTruncated, "truncated", 1);
+    }
+    if (feature == kFeatGoal && sh.goal) {
         add(kSnapGoalField, "goal_distance.field", 2u * HW);
         add(kSnapGoalDistance, "goal_distance.distance", 4);
         add(kSnapGoalStart, "goal_distance.start_distance", 4);
         add(kSnapGoalProgress, "goal_distance.progress", 4);
         add(kSnapGoalLast, "goal_distance.last_episode", 4);
     }
-    if (sh.seen) {
+    if (feature == kFeatSeen && sh.seen) {
         add(kSnapSeenCount, "seen_map.seen_count", 4);
         add(kSnapSeenNew, "seen_map.newly_seen", 4);
         add(kSnapSeenGoal, "seen_map.goal_seen", 4);
@@ -689,24 +693,33 @@ void plan_snapshot(const SnapshotShape& sh, SnapshotPlan* plan)
         add(kSnapSeenBits, "seen_map.bits", 4u * ((HW + 31u) / 32u));
         add(kSnapSeenMap, "seen_map.map", HW);
     }
-    if (sh.view_fmt) {
+    if (feature == kFeatView && sh.view_fmt) {                             // head: the box tables (plan_learner_view's ViewPlan::tab)
         const uint32_t frame = (uint32_t)sh.view_C * (uint32_t)sh.view_h * (uint32_t)sh.view_w;
         const uint64_t tag = (uint64_t)sh.view_h | (uint64_t)sh.view_w << 16 | (uint64_t)sh.view_fmt << 32 | (uint64_t)sh.view_layout << 40 | (uint64_t)sh.view_frames << 48;
+        p.head = sizeof(int32_t) * ((uint64_t)sh.view_h + (uint64_t)sh.view_w + 2 + (sh.view_fmt & RCW_VIEW_DEPTH8 ? (uint64_t)sh.Hc + 1 : 0));
         if (sh.view_frames > 1) {
             add(kSnapViewStack, "learner_view.stack", frame * (uint32_t)sh.view_frames, tag);
             add(kSnapViewLast, "learner_view.last_episode", 4);
+            add(kSnapViewStaging, "learner_view.staging", frame, 0, false);
         } else {
             add(kSnapViewFrame, "learner_view.frame", frame, tag);
         }
     }
-    if (sh.local_source)
+    if (feature == kFeatLocal && sh.local_source) {                        // head: the offset table (plan_local_map)
+        p.head = (uint64_t)sh.local_size * real;
         add(kSnapLocalImage, "local_map.image", (uint32_t)sh.local_size * (uint32_t)sh.local_size,
             (uint64_t)sh.local_size | (uint64_t)sh.local_cells << 16 | (uint64_t)sh.local_source << 32);
-    if (sh.source_kind) {
-        add(kSnapSourceLast, "layout_source.last_episode", 4, (uint64_t)sh.source_kind);
-        add(kSnapSourceLayout, "layout_source.layout", 4, (uint64_t)sh.source_kind);
     }
-    if (sh.stats) {
+    if (feature == kFeatSource && sh.source_kind) {
+        add(kSnapSourceLast, "layout_source.last_episode", 4, (uint64_t)sh.source_kind);
+        add(kSnapSourceStatus, "layout_source.status_seen", 4, 0, false);
+        add(kSnapSourceLayout, "layout_source.layout", 4, (uint64_t)sh.source_kind);
+        add(kSnapSourceMask, "layout_source.mask", 1, 0, false);
+    }
+    if (feature == kFeatStats && sh.stats) {                               // head: the table, a row of the batch and the level rows
+        int32_t rows = 0, first = 0;
+        plan_episode_stats_rows((RcwLayoutKind)sh.source_kind, sh.layouts, sh.levels, sh.first_level, &rows, &first);
+        p.head = sizeof(uint64_t) * RCW_EPISODE_STATS_ROW_WORDS * (1 + (uint64_t)rows);
         add(kSnapStatsFinished, "episode_stats.finished", 1);
         add(kSnapStatsOutcome, "episode_stats.outcome", 1);
         add(kSnapStatsLength, "episode_stats.length", 4);
@@ -717,6 +730,31 @@ void plan_snapshot(const SnapshotShape& sh, SnapshotPlan* plan)
         add(kSnapStatsPrevX, "episode_stats.prev_x", real);
         add(kSnapStatsPrevY, "episode_stats.prev_y", real);
         add(kSnapStatsLast, "episode_stats.last_episode", 4);
+    }
+}
+
+// THE CARVE of one buffer: `head` bytes, then the `n` parts for B agents in list order, each on a multiple of 16 bytes — the offset of
+// every part and the total to allocate.
+AgentCarve carve_agent_arrays(uint64_t head, const AgentPart* part, int n, uint64_t B)
+{
+    const auto up16 = [](uint64_t v) { return (v + 15) & ~(uint64_t)15; };
+    AgentCarve c;
+    c.total = up16(head);
+    for (int k = 0; k < n; ++k) { c.off[k] = c.total; c.total = up16(c.total + B * part[k].bytes); }
+    return c;
+}
+
+// THE STATE ARCHIVE'S RECORD (include/rcw.h, "the state archive"): the segment table of a handle of this shape, in the order an exported row
+// holds the segments — the archived parts of every feature, in the features' order.
+void plan_snapshot(const SnapshotShape& sh, SnapshotPlan* plan)
+{
+    SnapshotPlan& p = *plan;
+    p = SnapshotPlan{};
+    for (int f = 0; f < kFeatCount; ++f) {
+        AgentArrays a;
+        agent_arrays(sh, f, &a);
+        for (int k = 0; k < a.n; ++k)
+            if (a.part[k].archived) p.seg[p.n++] = SnapshotSegment{a.part[k].id, a.part[k].name, a.part[k].bytes, a.part[k].tag};
     }
     uint64_t k = 0xcbf29ce484222325ull;                                    // FNV-1a, a byte at a time
     const auto mix = [&k](uint64_t v, int bytes) { for (int b = 0; b < bytes; ++b) { k ^= (v >> (8 * b)) & 0xffu; k *= 0x100000001b3ull; } };

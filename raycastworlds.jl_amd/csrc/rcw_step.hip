@@ -298,56 +298,6 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     return launch_episode_stats(h, mask_dev, op);
 }
 
-namespace {
-
-// The handle's array that segment `f` of a record is a copy of (rcw_handle::Snapshots; plan_snapshot names them in this order).
-void* snapshot_live(rcw_handle* h, SnapshotField f)
-{
-    const RcwEpisodeStats& es = h->stats.dev;
-    switch (f) {
-    case kSnapPos: return h->d_pos.get();
-    case kSnapDir: return h->d_dir.get();
-    case kSnapGoal: return h->d_goal.get();
-    case kSnapReward: return h->d_reward.get();
-    case kSnapDone: return h->d_done.get();
-    case kSnapEpisode: return h->d_episode.get();
-    case kSnapTileMap: return h->d_tile_map.get();
-    case kSnapEpisodeSteps: return h->d_episode_steps.get();
-    case kSnapTruncated: return h->d_truncated.get();
-    case kSnapGoalField: return h->goal.field.get();
-    case kSnapGoalDistance: return h->goal.words.distance;
-    case kSnapGoalStart: return h->goal.words.start_distance;
-    case kSnapGoalProgress: return h->goal.words.progress;
-    case kSnapGoalLast: return h->goal.last_episode.get();
-    case kSnapSeenCount: return h->seen.words.seen_count;
-    case kSnapSeenNew: return h->seen.words.newly_seen;
-    case kSnapSeenGoal: return h->seen.words.goal_seen;
-    case kSnapSeenLast: return h->seen.last_episode;
-    case kSnapSeenBits: return h->seen.bits;
-    case kSnapSeenMap: return h->seen.map;
-    case kSnapViewFrame: return h->learner.frame.get();
-    case kSnapViewStack: return h->learner.stack.get();
-    case kSnapViewLast: return h->learner.last_episode.get();
-    case kSnapLocalImage: return h->local.img;
-    case kSnapSourceLast: return h->source.dev.agents.last_episode;
-    case kSnapSourceLayout: return h->source.dev.agents.layout;
-    case kSnapStatsFinished: return es.words.finished;
-    case kSnapStatsOutcome: return es.words.outcome;
-    case kSnapStatsLength: return es.words.length;
-    case kSnapStatsMoves: return es.words.moves;
-    case kSnapStatsLevel: return es.words.level;
-    case kSnapStatsSpl: return es.words.spl_q16;
-    case kSnapStatsEpisodes: return es.words.episodes;
-    case kSnapStatsPrevX: return es.prev_x;
-    case kSnapStatsPrevY: return es.prev_y;
-    case kSnapStatsLast: return es.last_episode;
-    case kSnapFieldCount: break;
-    }
-    return nullptr;
-}
-
-}  // namespace
-
 // A save or a restore of the state archive, on the handle's stream and without a wait (the caller has checked that the handle's shape is the
 // archive's: every segment has its live array).  Both: who takes which row, then the copy — the segment table goes to the kernel
 // kSnapshotKernelSegments at a time.  A save is done there.  A restore goes on: the step's facts forget the slots (StepFacts::restored), and
@@ -362,9 +312,9 @@ hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t
     for (int first = 0; first < sn.plan.n; first += kSnapshotKernelSegments) {
         RcwSnapshotTable t{};
         for (int k = first; k < sn.plan.n && t.n < kSnapshotKernelSegments; ++k) {
-            uint8_t* const live = static_cast<uint8_t*>(snapshot_live(h, sn.plan.seg[k].field));
-            if (!live) return hipErrorInvalidValue;
-            t.seg[t.n++] = RcwSnapshotSeg{live, sn.arc[k], sn.plan.seg[k].bytes, t.tasks};
+            const LiveArray& live = h->live[sn.plan.seg[k].field];     // (the array the segment is a copy of: of the segment's size, or nothing is copied)
+            if (!live.ptr || live.bytes != sn.plan.seg[k].bytes) return hipErrorInvalidValue;
+            t.seg[t.n++] = RcwSnapshotSeg{live.as<uint8_t>(), sn.arc[k], sn.plan.seg[k].bytes, t.tasks};
             t.tasks += rcw_snapshot_tasks(sn.plan.seg[k].bytes, h->B);
         }
         if ((e = rcw_launch_snapshot_copy(t, h->B, sn.sel, restore ? nullptr : sn.owner, restore, 8 * h->hw.cus, h->stream)) != hipSuccess) return e;

@@ -4,7 +4,8 @@
 // unit, host side only) under -fsanitize=address,undefined and runs the program on the CPU: nothing loads a sanitizer's runtime into Python.
 // It plans the record of three shapes (plan_snapshot, snapshot_plan_differs) and puts a valid exported row and every single corruption
 // rcw_snapshot_rows_load refuses through validate_snapshot_row — each row in a heap block of exactly row_bytes, so a read past a row's end
-// is reported — and exits 0 if nothing was reported and the checks below hold.
+// is reported —, carves every feature's per-agent arrays (agent_arrays, carve_agent_arrays) into heap blocks of exactly the carve's total, and
+// exits 0 if nothing was reported and the checks below hold.
 #include "../raycastworlds.jl_amd/csrc/rcw_rules.hip"
 
 #include <cstdarg>
@@ -107,11 +108,47 @@ static int run(const SnapshotShape& sh)
     return 0;
 }
 
+// The carve of every feature of a shape for B agents, as a setter uses it: a heap block of exactly `total` bytes, the head written at its start,
+// every part's [B] array written at its offset with a byte of its own — a write past the block is reported —, and then every byte still holds
+// what its part wrote: no two parts, and no part and the head, share one.  The archived parts, feature by feature, are the record's segments.
+static int carve(const SnapshotShape& sh, int B)
+{
+    SnapshotPlan plan;
+    plan_snapshot(sh, &plan);
+    int seg = 0;
+    for (int f = 0; f < kFeatCount; ++f) {
+        AgentArrays a;
+        agent_arrays(sh, f, &a);
+        CHECK(a.n >= 0 && a.n <= kAgentMaxParts && (a.n > 0 || a.head == 0));
+        const AgentCarve c = carve_agent_arrays(a.head, a.part, a.n, (uint64_t)B);
+        CHECK(c.total >= a.head && c.total % 16 == 0);
+        if (c.total == 0) continue;                                             // (a feature that is off carves nothing)
+        std::unique_ptr<uint8_t[]> buf(new uint8_t[(size_t)c.total]);
+        std::memset(buf.get(), 0xEE, (size_t)c.total);
+        std::memset(buf.get(), 0xAA, (size_t)a.head);
+        for (int k = 0; k < a.n; ++k) {
+            CHECK(c.off[k] % 16 == 0 && a.part[k].id >= kFeatureFirstId[f] && a.part[k].id < kFeatureFirstId[f + 1] && (k == 0 || a.part[k].id > a.part[k - 1].id));
+            std::memset(buf.get() + c.off[k], k + 1, (size_t)B * a.part[k].bytes);
+            if (a.part[k].archived) { CHECK(seg < plan.n && plan.seg[seg].field == a.part[k].id && plan.seg[seg].bytes == a.part[k].bytes); ++seg; }
+        }
+        for (uint64_t i = 0; i < a.head; ++i) CHECK(buf[i] == 0xAA);
+        for (int k = 0; k < a.n; ++k)
+            for (uint64_t i = 0; i < (uint64_t)B * a.part[k].bytes; ++i) CHECK(buf[c.off[k] + i] == k + 1);
+    }
+    CHECK(seg == plan.n);
+    return 0;
+}
+
 int main()
 {
     const SnapshotShape shapes[] = {shape(8, 8, false, false), shape(4, 4, false, true), shape(5, 5, true, true), shape(5, 7, true, false)};
     for (const SnapshotShape& s : shapes)
         if (run(s)) return 1;
+    SnapshotShape f64_5x5 = shape(5, 5, true, false);                           // (tests/test_agent_arrays_spec.py's shapes and batches)
+    f64_5x5.goal = f64_5x5.seen = f64_5x5.stats = 1;
+    for (const SnapshotShape& s : {shape(4, 4, false, true), f64_5x5, shape(7, 9, false, true)})
+        for (int B : {1, 3, 5, 63, 64, 65, 257})
+            if (carve(s, B)) return 1;
     SnapshotPlan a, b;
     plan_snapshot(shapes[1], &a);
     SnapshotShape other = shapes[1];
