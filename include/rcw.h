@@ -364,7 +364,8 @@ RCW_API int rcw_set_walls(rcw_handle* h, const uint8_t* walls_host, int32_t layo
  * What each call does to them — stream-ordered on the handle's stream, behind everything the call already queues:
  *   rcw_set_goal_distance(h, 1)   allocates, computes the field of every agent, distance from it, start_distance = distance,
  *                                 progress = 0; on a handle that has it, the same again.  An allocation failure leaves what was there.
- *   rcw_set_goal_distance(h, 0)   frees it (RCW_OK also where there was none).
+ *   rcw_set_goal_distance(h, 0)   frees it (RCW_OK also where there was none).  On a handle with the guide on (rcw_set_guide, which
+ *                                 reads the field) it switches the guide off too.
  *   rcw_reset, rcw_set_state, rcw_set_state64, rcw_set_walls
  *                                 for the agents in the call's mask: field recomputed, distance new, start_distance = distance,
  *                                 progress = 0; an agent outside the mask keeps every byte of its field and its three words.
@@ -750,6 +751,63 @@ RCW_API int rcw_episode_stats_device_ptr(rcw_handle* h, void** finished, void** 
 RCW_API int rcw_episode_stats_table(rcw_handle* h, uint64_t* out_host /* (8, 1 + rows) */);
 RCW_API int rcw_episode_stats_table_device_ptr(rcw_handle* h, void** ptr);
 RCW_API int rcw_episode_stats_clear(rcw_handle* h);
+/* ---- the guide (this build's addition: each agent's shortest-path action, kept on the device) ------------------------------------------
+ * Opt-in per handle, on a handle that has the goal distance on: the action that follows the agent's shortest path to its goal, written
+ * behind every call that moves an agent, a goal or a wall — the label imitation learning and DAgger need on the states the learner
+ * visits, an upper-bound baseline for the SPL table, a way to walk to a state worth saving — at no host synchronisation.  The action
+ * array can be handed to rcw_step_device as it stands, or mixed with a policy's on the device.  A handle that never enables it runs
+ * exactly the kernels it ran before.  The ABI is additive: RCW_ABI_VERSION and rcw_config are what they were.
+ * Per-agent words, device arrays of B entries each:
+ *   action     UInt8    always in 1..4
+ *   heading    Int32    the 0-based direction index the guide wants the agent to face, -1 where it has no advice
+ * THE RULE.  T is the handle's world-unit type; every operation is done in T and rounded once, no fused multiply-add.  For agent a:
+ * (x, y) its position, d its 0-based heading (rcw_direction), D[k] = (D1, D2) the handle's direction table as it stands (nd entries),
+ * inc = position_increment_wu, F the agent's goal-distance field, 0-based tile (i, j) at i + H*j.
+ *   1  i = floor(x), j = floor(y).  Where x or y is not finite, or (i, j) is off the map, or f = F[i, j] is 0xFFFF or 0 — no path, or
+ *      the agent stands on the goal tile —: heading = -1, action = 3 (a turn on the spot).  F is read only behind the bounds check.
+ *   2  n = the first of (i-1, j), (i+1, j), (i, j-1), (i, j+1) that lies on the map and has F[n] == f - 1.  A flood's field always has
+ *      one where f >= 1; on a field that has none (rcw_guide_rule takes any) the result is that of 1.
+ *   3  ct = (T(i) + 0.5, T(j) + 0.5), the centre of the agent's tile; cn the centre of n; e the agent's offset from ct ACROSS the axis of
+ *      travel: y - ct.y where n differs in i, else x - ct.x.  The target p is cn where |e| <= inc, else ct: re-centre in the corridor
+ *      first, then go — the player's circle never clips a corner it cannot pass.
+ *   4  v = (p.x - x, p.y - y); s[k] = fl(fl(D1[k] * v.x) + fl(D2[k] * v.y)); heading = the smallest k of the largest s[k].  An argmax
+ *      over the table as it is (rcw_set_direction_table may have installed any), not an atan2: rounded products compare the same
+ *      everywhere.  A NaN s[k] never wins; where every s[k] is NaN, heading = 0.
+ *   5  delta = (heading - d) mod nd.  0: action 1 (forward).  1 .. nd / 2 (integer division): action 3 (turn left, d + 1).  Otherwise
+ *      action 4 (turn right).  The guide never moves backwards and never looks at collisions.
+ * THE PROMISE, for position_increment_wu + player_radius_wu <= 0.5 (the sum in T) and the table rcw_create builds: an agent that follows
+ * `action` from a start l tiles from its goal arrives within (l + 1) * (nd / 2 + 2 * ceil(1 / inc)) steps.  Outside that the words are
+ * still defined and still exact — an agent whose circle cannot come within inc of a corridor's axis may just never arrive.
+ * rcw_guide_info says which case a handle is in.
+ * What each call does to the words — stream-ordered on the handle's stream, directly behind the goal distance's launch where that runs:
+ *   rcw_set_guide(h, 1)           RCW_ERR_UNSUPPORTED on a handle without the goal distance.  Allocates and computes every agent's
+ *                                 words; on a handle that has it, the same again.  An allocation failure leaves what was there.
+ *   rcw_set_guide(h, 0)           frees them (RCW_OK also where there were none).
+ *   rcw_set_goal_distance(h, 1)   (again) every agent's words from the new field.
+ *   rcw_set_goal_distance(h, 0)   switches the guide off too.
+ *   rcw_step, rcw_step_device, rcw_reset, rcw_set_state, rcw_set_state64, rcw_set_walls, the install and the restarts of the wall
+ *   bank and of every generator family, rcw_set_direction_table*, rcw_snapshot_restore*
+ *                                 every agent's words from the state the call leaves (the words are a pure function of field,
+ *                                 position, heading and table: an agent outside the call's mask keeps the values it had).
+ *   rcw_snapshot_save*, rcw_cast_rays, rcw_update_camera_view, rcw_update_top_view, rcw_set_step_form, rcw_set_time_limit, the
+ *   learner-view, seen-map, local-map and statistics calls and every getter   nothing.
+ * The words are no part of the state archive's record: a row is exchangeable between handles with and without the guide, and every
+ * shape's key is what it was.  A replayed HIP graph of a step works like any step: nothing about this alternates on the host.  Capture
+ * again after enabling or disabling.  The kernel (one launch, rcw_guide_kernel) runs OUTSIDE rcw_profile's events.
+ *   rcw_guide_info         enabled; promised = 1 where inc + r <= 0.5 in T (either pointer may be NULL).
+ *   rcw_guide              host copies of the two words (either pointer may be NULL); waits for the stream as rcw_done does.
+ *   rcw_guide_device_ptr   the two arrays where they live (either pointer may be NULL), stable until the next rcw_set_guide.
+ *   rcw_guide_rule         handle-less, needs no device: the rule for ONE agent on the host.  field UInt16 (H*W) in the order above,
+ *                          H*W <= 65535; (x, y) as doubles, converted to T = Float32 (world_unit_bits 32) or Float64 (64), as is
+ *                          position_increment; direction in 0 .. nd - 1; directions_wu (2, nd) in T, rcw_direction_table's layout.
+ *                          Anything else — a NULL pointer included — is RCW_ERR_INVALID_ARGUMENT.
+ * rcw_guide and rcw_guide_device_ptr return RCW_ERR_UNSUPPORTED on a handle that has not enabled it. */
+RCW_API int rcw_set_guide(rcw_handle* h, int32_t enable);
+RCW_API int rcw_guide_info(rcw_handle* h, int32_t* enabled, int32_t* promised);
+RCW_API int rcw_guide(rcw_handle* h, uint8_t* action /* (B) */, int32_t* heading /* (B) */);
+RCW_API int rcw_guide_device_ptr(rcw_handle* h, void** action, void** heading);
+RCW_API int rcw_guide_rule(int32_t H, int32_t W, const void* field /* UInt16 (H*W) */, double x, double y, int32_t world_unit_bits, int32_t direction,
+                           int32_t nd, const void* directions_wu /* (2, nd) in T */, double position_increment, uint8_t* action, int32_t* heading);
 
 /* ---- The state archive (this build's addition: the reference has no checkpoint) -------------------------------------------------------
  * `rows` agent RECORDS kept on the device and owned by the handle: save scatters the records of the masked agents into rows, restore
@@ -773,6 +831,8 @@ RCW_API int rcw_episode_stats_clear(rcw_handle* h);
  *   the layout source's transient mask, the episode statistics' table                         a launch's scratch; a log of the batch;
  *   any setting of the handle — seed, time limit, bank and weights, generator parameters,     these are the handle's as of the restore.
  *   direction table —
+ *   the guide's two words                                                                     a restore computes them again: a row fits
+ *                                                                                             a handle with or without the guide;
  * If row r was saved from agent j and is restored into agent i, agent i holds j's world; its next episode starts under i's global id and
  * the copied episode counter.
  *

@@ -422,6 +422,51 @@ function goal_distance_field_device_ptr(env::BatchedSingleRoom)
     check(ccall((:rcw_goal_distance_field_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
 end
 
+# ---- the guide (this build's addition; include/rcw.h, rcw_set_guide) -------------------------------------------------------------
+"""
+    set_guide!(env, on = true)
+
+Keep, on the device, the action that follows every agent's shortest path to its goal, behind every call that moves an agent, a goal or
+a wall, a new direction table and a `snapshot_restore!`: `guide(env)` returns `(action, heading)` — `action` a `Vector{UInt8}` of
+`batch`, always in 1..4 (what `act!` takes), `heading` a `Vector{Int32}`, the 0-based direction index the guide wants the agent to face,
+`-1` where it has no advice.  Needs the goal distance (`set_goal_distance!` first; switching that off switches the guide off too).
+`guide_info(env)` says whether it is on and whether `position_increment + player_radius <= 0.5`, for which following it is promised to
+arrive.  `guide_rule` is the rule for one agent on the host, without a device.
+"""
+function set_guide!(env::BatchedSingleRoom, on::Bool = true)
+    check(ccall((:rcw_set_guide, librcw), Cint, (Ptr{Cvoid}, Int32), env.handle, on ? 1 : 0))
+    return nothing
+end
+function guide_info(env::BatchedSingleRoom)
+    e = Ref{Int32}(0); p = Ref{Int32}(0)
+    check(ccall((:rcw_guide_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), env.handle, e, p))
+    return (enabled = e[] != 0, promised = p[] != 0)
+end
+function guide(env::BatchedSingleRoom)
+    a = Vector{UInt8}(undef, env.batch); h = Vector{Int32}(undef, env.batch)
+    check(ccall((:rcw_guide, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int32}), env.handle, a, h))
+    return (action = a, heading = h)
+end
+function guide_device_ptr(env::BatchedSingleRoom)
+    a = Ref{Ptr{Cvoid}}(C_NULL); h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_guide_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}), env.handle, a, h))
+    return (action = a[], heading = h[])
+end
+"""
+    guide_rule(field, position, direction, directions_wu, position_increment) -> (action, heading)
+
+The guide's rule for one agent: `field` a `Matrix{UInt16}` `(H, W)` (one agent's `goal_distance_field`), `position` `(x, y)`,
+`direction` the 0-based heading, `directions_wu` a `(2, nd)` matrix of `Float32` or `Float64` — the type the rule computes in.
+"""
+function guide_rule(field::Matrix{UInt16}, position, direction::Integer, directions_wu::Matrix{T}, position_increment::Real) where {T <: Union{Float32, Float64}}
+    a = Ref{UInt8}(0); h = Ref{Int32}(0)
+    check(ccall((:rcw_guide_rule, librcw), Cint,
+                (Int32, Int32, Ptr{Cvoid}, Float64, Float64, Int32, Int32, Int32, Ptr{Cvoid}, Float64, Ref{UInt8}, Ref{Int32}),
+                size(field, 1), size(field, 2), field, position[1], position[2], 8 * sizeof(T), direction, size(directions_wu, 2),
+                directions_wu, position_increment, a, h))
+    return (action = a[], heading = h[])
+end
+
 # ---- the seen map (this build's addition; include/rcw.h, rcw_set_seen_map) ------------------------------------------------------
 """
     set_seen_map!(env, on = true)

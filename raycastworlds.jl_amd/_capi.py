@@ -175,6 +175,11 @@ SIGNATURES = {
     "rcw_episode_stats_table": [_vp, _vp],
     "rcw_episode_stats_table_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_episode_stats_clear": [_vp],
+    "rcw_set_guide": [_vp, _i32],
+    "rcw_guide_info": [_vp, C.POINTER(_i32), C.POINTER(_i32)],
+    "rcw_guide": [_vp, _vp, _vp],
+    "rcw_guide_device_ptr": [_vp, C.POINTER(_vp), C.POINTER(_vp)],
+    "rcw_guide_rule": [_i32, _i32, _vp, C.c_double, C.c_double, _i32, _i32, _i32, _vp, C.c_double, C.POINTER(C.c_uint8), C.POINTER(_i32)],
     "rcw_set_snapshots": [_vp, _i32],
     "rcw_snapshot_info": [_vp, C.POINTER(_i32), C.POINTER(_u64), C.POINTER(_u64)],
     "rcw_snapshot_save": [_vp, _vp, _vp],

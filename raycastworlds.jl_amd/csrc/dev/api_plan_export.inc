@@ -94,12 +94,12 @@ __attribute__((visibility("default"))) int rcw_dev_validate_walls(int32_t H, int
 // The state archive's record without a device (tests/test_snapshot_spec.py).  shape: the 23 Int32 of SnapshotShape in its order — H, W, nd, N,
 // Hc, real64, reward_type | goal, seen, stats | view_fmt, view_layout, view_C, view_h, view_w, view_frames | local_source, local_size,
 // local_cells | source_kind | layouts, levels, first_level.  names: the segments' names, a line each; bytes [n]; returns n, -1: names too small.
-static_assert(sizeof(SnapshotShape) == 23 * sizeof(int32_t), "SnapshotShape travels as 23 Int32");
+static_assert(sizeof(SnapshotShape) == (kSnapshotShapeWords + 1) * sizeof(int32_t), "SnapshotShape travels as its first 23 Int32: the guide, which is no part of a record, stays off");
 __attribute__((visibility("default"))) int rcw_dev_snapshot_plan(const int32_t* shape, char* names, int32_t cap, uint32_t* bytes, uint64_t* row_bytes, uint64_t* key)
 {
     if (!shape || !names || cap < 1 || !bytes || !row_bytes || !key) return RCW_ERR_INVALID_ARGUMENT;
     SnapshotShape sh;
-    std::memcpy(&sh, shape, sizeof sh);
+    std::memcpy(&sh, shape, kSnapshotShapeWords * sizeof(int32_t));
     SnapshotPlan plan;
     plan_snapshot(sh, &plan);
     int n = 0;
@@ -113,7 +113,7 @@ __attribute__((visibility("default"))) int rcw_dev_snapshot_plan(const int32_t* 
     return plan.n;
 }
 // The per-agent arrays of one feature (AgentFeature: 0 core state, 1 goal distance, 2 seen map, 3 learner view, 4 local map, 5 layout source,
-// 6 episode statistics) of that shape, and their carve for `batch` agents as ONE buffer behind the feature's head (tests/
+// 6 episode statistics, 7 the guide — off in every shape that travels here) of that shape, and their carve for `batch` agents as ONE buffer behind the feature's head (tests/
 // test_agent_arrays_spec.py): names a line each; ids, bytes (per agent), archived, offsets [n]; returns n (0: the feature is off), -1: names
 // too small.
 __attribute__((visibility("default"))) int rcw_dev_agent_arrays(const int32_t* shape, int32_t feature, int32_t batch, char* names, int32_t cap, int32_t* ids,
@@ -121,7 +121,7 @@ __attribute__((visibility("default"))) int rcw_dev_agent_arrays(const int32_t* s
 {
     if (!shape || feature < 0 || feature >= kFeatCount || batch < 1 || !names || cap < 1 || !ids || !bytes || !archived || !offsets || !head || !total) return RCW_ERR_INVALID_ARGUMENT;
     SnapshotShape sh;
-    std::memcpy(&sh, shape, sizeof sh);
+    std::memcpy(&sh, shape, kSnapshotShapeWords * sizeof(int32_t));
     AgentArrays a;
     agent_arrays(sh, feature, &a);
     const AgentCarve c = carve_agent_arrays(a.head, a.part, a.n, (uint64_t)batch);
@@ -136,12 +136,17 @@ __attribute__((visibility("default"))) int rcw_dev_agent_arrays(const int32_t* s
     *head = a.head; *total = c.total;
     return a.n;
 }
+// The guide's promise for a configuration without a device (tests/test_guide_spec.py): what rcw_guide_info reports as `promised`
+__attribute__((visibility("default"))) int rcw_dev_guide_promised(const rcw_config* cfg)
+{
+    return cfg ? guide_promised(*cfg) : RCW_ERR_INVALID_ARGUMENT;
+}
 // rcw_snapshot_rows_load's check of one exported row of that shape: validate_snapshot_row's return code, its reason in msg
 __attribute__((visibility("default"))) int rcw_dev_snapshot_validate_row(const int32_t* shape, const uint8_t* row, char* msg, int32_t cap)
 {
     if (!shape || !row || !msg || cap < 1) return RCW_ERR_INVALID_ARGUMENT;
     SnapshotShape sh;
-    std::memcpy(&sh, shape, sizeof sh);
+    std::memcpy(&sh, shape, kSnapshotShapeWords * sizeof(int32_t));
     if (sh.H < 3 || sh.W < 3 || sh.nd < 1) return RCW_ERR_INVALID_ARGUMENT;
     SnapshotPlan plan;
     plan_snapshot(sh, &plan);

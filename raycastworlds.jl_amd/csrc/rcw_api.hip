@@ -154,6 +154,7 @@ SnapshotShape snapshot_shape(const rcw_handle* h)
     if (h->local.on()) { s.local_source = h->local.source; s.local_size = h->local.size; s.local_cells = h->local.cells_per_tile; }
     s.source_kind = (int32_t)h->source.dev.kind;
     s.layouts = h->source.dev.agents.layouts; s.levels = h->source.dev.gen.levels; s.first_level = h->source.dev.gen.first_level;
+    s.guide = h->guide.on();
     return s;
 }
 
@@ -185,6 +186,7 @@ const char* const kNoSeenMap = "the handle has no seen map (rcw_set_seen_map)";
 const char* const kNoLocalMap = "the handle has no local map (rcw_set_local_map)";
 const char* const kNoDrawnWalls = "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms)";
 const char* const kNoEpisodeStats = "the handle keeps no episode statistics (rcw_set_episode_stats)";
+const char* const kNoGuide = "the handle has no guide (rcw_set_guide)";
 int need(bool on, const char* why_off) { return on ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "%s", why_off); }
 
 // (the array of the learner view the caller sees: the k-frame stack, or the one frame)
@@ -1006,12 +1008,14 @@ int rcw_learner_view_copy(rcw_handle* h, uint8_t* out_host, int32_t first, int32
 }
 
 // The goal distance (include/rcw.h).  Enabling allocates and floods every agent at once, stream-ordered behind what is queued; enabling
-// again does the same again; an allocation failure leaves what was there.
+// again does the same again; an allocation failure leaves what was there.  The guide lives on the field: switching the goal distance off
+// switches the guide off first, enabling it again rewrites the guide's words from the new field.
 int rcw_set_goal_distance(rcw_handle* h, int32_t enable)
 {
     int rc = check_handle(h); if (rc) return rc;
     rcw_handle::GoalDistance& gd = h->goal;
     if (!enable && !gd.on()) return RCW_OK;
+    if (!enable) { rc = rcw_set_guide(h, 0); if (rc) return rc; }
     rcw_handle::GoalDistance fresh;
     LiveArray at[kSnapFieldCount] = {};
     if (enable) {
@@ -1029,6 +1033,7 @@ int rcw_set_goal_distance(rcw_handle* h, int32_t enable)
     RCW_HIP(take_live(h, kFeatGoal, at));
     gd = std::move(fresh);
     if (gd.on()) RCW_HIP(launch_goal_distance(h, nullptr, kStackRefill));
+    if (gd.on()) RCW_HIP(launch_guide(h, kStackRefill));
     return RCW_OK;
 }
 
@@ -1057,6 +1062,51 @@ int rcw_goal_distance_field(rcw_handle* h, int32_t first, int32_t count, void* o
 }
 
 int rcw_goal_distance_field_device_ptr(rcw_handle* h, void** ptr) { return hand_out(h, kNoGoalDistance, {{ptr, kSnapGoalField}}); }
+
+// The guide (include/rcw.h).  Enabling allocates and computes every agent's words at once, stream-ordered behind what is queued; enabling
+// again does the same again; an allocation failure leaves what was there.
+int rcw_set_guide(rcw_handle* h, int32_t enable)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::Guide& gu = h->guide;
+    if (!enable && !gu.on()) return RCW_OK;
+    if (enable) { rc = need(h->goal.on(), "the guide follows the goal distance's field: enable it first (rcw_set_goal_distance(h, 1))"); if (rc) return rc; }
+    rcw_handle::Guide fresh;
+    LiveArray at[kSnapFieldCount] = {};
+    if (enable) {
+        SnapshotShape sh = snapshot_shape(h);
+        sh.guide = 1;
+        AgentArrays list;
+        agent_arrays(sh, kFeatGuide, &list);
+        size_t bytes = 0;
+        const hipError_t e = alloc_parts(h, fresh.buf, list, 0, list.n, list.head, at, &bytes);
+        if (e != hipSuccess) return fail(hip_code(e), "guide words of %zu bytes: %s", bytes, hip_failure(e));
+        fresh.words = RcwGuideWords{at[kSnapGuideAction].as<uint8_t>(), at[kSnapGuideHeading].as<int32_t>()};
+    }
+    RCW_HIP(take_live(h, kFeatGuide, at));
+    gu = std::move(fresh);
+    if (gu.on()) RCW_HIP(launch_guide(h, kStackRefill));
+    return RCW_OK;
+}
+
+int rcw_guide_info(rcw_handle* h, int32_t* enabled, int32_t* promised)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (enabled) *enabled = h->guide.on() ? 1 : 0;
+    if (promised) *promised = guide_promised(h->cfg);
+    return RCW_OK;
+}
+
+int rcw_guide(rcw_handle* h, uint8_t* action, int32_t* heading)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return copy_arrays(h, kNoGuide, {{action, kSnapGuideAction}, {heading, kSnapGuideHeading}});
+}
+
+int rcw_guide_device_ptr(rcw_handle* h, void** action, void** heading)
+{
+    return hand_out(h, kNoGuide, {{action, kSnapGuideAction}, {heading, kSnapGuideHeading}});
+}
 
 // The seen map (include/rcw.h).  Enabling allocates and marks every agent afresh at once, stream-ordered behind what is queued; enabling
 // again does the same again; an allocation failure leaves what was there.

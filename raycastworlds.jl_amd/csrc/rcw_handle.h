@@ -120,18 +120,20 @@ struct SnapshotShape {
     int32_t local_source = 0, local_size = 0, local_cells = 0;   // the local map; local_source 0: off
     int32_t source_kind = 0;                                     // RcwLayoutKind; 0: no layout source
     int32_t layouts = 0, levels = 0, first_level = 0;            // the source's range (validate_snapshot_row, the statistics' rows; not part of the record)
+    int32_t guide = 0;                                           // the guide: on (its words are never archived: not part of the record)
 };
+constexpr int kSnapshotShapeWords = 23;                          // what travels through the development exports: everything but `guide`
 // (a part's id, in the order of the features and, within one, of its list; kSnapViewStaging — the view kernels' frame under a k-frame stack —,
-// kSnapSourceStatus and kSnapSourceMask are never archived)
+// kSnapSourceStatus, kSnapSourceMask and the guide's two words are never archived)
 enum SnapshotField { kSnapPos, kSnapDir, kSnapGoal, kSnapReward, kSnapDone, kSnapEpisode, kSnapTileMap, kSnapEpisodeSteps, kSnapTruncated,
                      kSnapGoalField, kSnapGoalDistance, kSnapGoalStart, kSnapGoalProgress, kSnapGoalLast,
                      kSnapSeenCount, kSnapSeenNew, kSnapSeenGoal, kSnapSeenLast, kSnapSeenBits, kSnapSeenMap,
                      kSnapViewFrame, kSnapViewStack, kSnapViewLast, kSnapViewStaging, kSnapLocalImage,
                      kSnapSourceLast, kSnapSourceStatus, kSnapSourceLayout, kSnapSourceMask,
                      kSnapStatsFinished, kSnapStatsOutcome, kSnapStatsLength, kSnapStatsMoves, kSnapStatsLevel, kSnapStatsSpl, kSnapStatsEpisodes,
-                     kSnapStatsPrevX, kSnapStatsPrevY, kSnapStatsLast, kSnapFieldCount };
-enum AgentFeature { kFeatCore, kFeatGoal, kFeatSeen, kFeatView, kFeatLocal, kFeatSource, kFeatStats, kFeatCount };
-constexpr SnapshotField kFeatureFirstId[kFeatCount + 1] = {kSnapPos, kSnapGoalField, kSnapSeenCount, kSnapViewFrame, kSnapLocalImage, kSnapSourceLast, kSnapStatsFinished, kSnapFieldCount};
+                     kSnapStatsPrevX, kSnapStatsPrevY, kSnapStatsLast, kSnapGuideAction, kSnapGuideHeading, kSnapFieldCount };
+enum AgentFeature { kFeatCore, kFeatGoal, kFeatSeen, kFeatView, kFeatLocal, kFeatSource, kFeatStats, kFeatGuide, kFeatCount };
+constexpr SnapshotField kFeatureFirstId[kFeatCount + 1] = {kSnapPos, kSnapGoalField, kSnapSeenCount, kSnapViewFrame, kSnapLocalImage, kSnapSourceLast, kSnapStatsFinished, kSnapGuideAction, kSnapFieldCount};
 constexpr int kAgentMaxParts = 10;
 struct AgentPart { SnapshotField id; const char* name; uint32_t bytes; uint64_t tag; bool archived; };
 struct AgentArrays { int32_t n = 0; AgentPart part[kAgentMaxParts] = {}; uint64_t head = 0; };   // (n = 0: the feature is off)
@@ -263,6 +265,14 @@ struct rcw_handle {
         bool on() const { return buf.get() != nullptr; }
         size_t table_bytes() const { return (size_t)RCW_EPISODE_STATS_ROW_WORDS * (1 + (size_t)dev.rows) * sizeof(uint64_t); }
     } stats;
+    // The guide (rcw_set_guide): ONE buffer, the carve of its list — UInt8 (B) action, Int32 (B) heading; `words` points into it.  It holds
+    // no pointer into the goal distance: the launch reads goal.field as it is THEN (rcw_set_goal_distance may have replaced it).  Empty while
+    // the feature is off — and never on while the goal distance is off.
+    struct Guide {
+        RcwBuf buf;
+        RcwGuideWords words{};
+        bool on() const { return buf.get() != nullptr; }
+    } guide;
     // The state archive (rcw_set_snapshots): ONE allocation — every segment's rows ([rows][bytes], each part on a multiple of 16 bytes), then
     // the Int32 scratch (owner [rows], the row each agent takes [B], the host variants' staged indices [B]), then the filled flags (UInt8
     // [rows]).  plan: the record's layout as of the binding (plan_snapshot); arc[k]: segment k's rows.  Empty while the archive is off.
@@ -325,6 +335,7 @@ void plan_snapshot(const SnapshotShape& sh, SnapshotPlan* plan);
 const char* snapshot_plan_differs(const SnapshotPlan& bound, const SnapshotPlan& now);   // the first segment that differs, NULL: the same shape
 int validate_snapshot_row(const SnapshotShape& sh, const SnapshotPlan& plan, const uint8_t* row, char* msg, size_t cap);
 void plan_episode_stats_rows(RcwLayoutKind kind, int32_t layouts, int32_t levels, int32_t first_level, int32_t* rows, int32_t* first);
+int guide_promised(const rcw_config& cfg);                        // 1: position_increment + player_radius <= 0.5 in the world-unit type
 
 // ---- rcw_step.hip: what a step, a reset or a re-render launches, and the resources those launches need ---------------------------------
 hipError_t launch_top_view_alone(rcw_handle* h, const uint8_t* mask_dev);
@@ -334,6 +345,7 @@ hipError_t launch_goal_distance(rcw_handle* h, const uint8_t* mask_dev, StackOp 
 hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_local_map(rcw_handle* h, StackOp op);
 hipError_t launch_episode_stats(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
+hipError_t launch_guide(rcw_handle* h, StackOp op);
 hipError_t launch_layout_source(rcw_handle* h, bool force);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t* mask_dev, bool restore);

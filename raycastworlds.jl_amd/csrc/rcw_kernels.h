@@ -236,6 +236,15 @@ struct RcwEpisodeStats {
 hipError_t rcw_launch_episode_stats(const RcwDev& p, const RcwLimit& limit, const RcwEpisodeStats& st, const int32_t* layout,
                                     const int32_t* start_distance, const uint8_t* mask_dev, bool refill, hipStream_t s);
 
+// The guide (rcw_set_guide, rcw_guide.hip): the two per-agent words.
+struct RcwGuideWords {
+    uint8_t* action;         // 1..4: what rcw_step_device takes as it stands
+    int32_t* heading;        // the direction index the guide wants the agent to face, -1: no advice
+};
+// One launch, every agent: the rule of include/rcw.h ("the guide") on `field` — the goal distance's, [B][H*W] —, p's positions, headings and
+// direction table as they are when it runs.  An argument block of its OWN (the comment on RcwLimit).  Reads only; writes only the two words.
+hipError_t rcw_launch_guide(const RcwDev& p, int32_t B, const uint16_t* field, const RcwGuideWords& words, hipStream_t s);
+
 // THE LAYOUT SOURCES (rcw_wall_bank.hip): what gives an agent its walls at every start of an episode.  A handle has at most one — the wall
 // bank (rcw_set_wall_bank) or one family of the wall generator: mazes (rcw_set_wall_generator), caves (rcw_set_wall_caves), rooms
 // (rcw_set_wall_rooms) — behind ONE launch point, rcw_launch_layout_source.

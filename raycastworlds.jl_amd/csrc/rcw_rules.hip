@@ -655,6 +655,72 @@ extern "C" int rcw_wall_rooms_layout(int32_t H, int32_t W, uint64_t key, int32_t
     return RCW_OK;
 }
 
+// ---- the guide (include/rcw.h, "the guide") ---------------------------------------------------------------------------------------------
+// Whether the guide's promise holds for this configuration: position_increment + player_radius <= 0.5, the sum rounded once in T.
+int guide_promised(const rcw_config& cfg)
+{
+    if (cfg.world_unit_bits == 64) return cfg.position_increment_wu_f64 + cfg.player_radius_wu_f64 <= 0.5 ? 1 : 0;
+    const float sum = cfg.position_increment_wu + cfg.player_radius_wu;
+    return sum <= 0.5f ? 1 : 0;
+}
+
+namespace {
+// The rule for one agent, restated for the host: one pass over the table in index order that keeps the first greatest product sum
+// (rcw_guide_kernel strides it a lane an entry and reduces pairs).  D: (2, nd), entry k at D[2 k], D[2 k + 1].
+template <typename T>
+void guide_rule_one(int H, int W, const uint16_t* F, T x, T y, int32_t d, int32_t nd, const T* D, T inc, uint8_t* action, int32_t* heading)
+{
+    *heading = -1;
+    *action = 3;
+    if (!std::isfinite(x) || !std::isfinite(y)) return;
+    const T fx = std::floor(x), fy = std::floor(y);
+    if (fx < (T)0 || fx >= (T)H || fy < (T)0 || fy >= (T)W) return;
+    const int i = (int)fx, j = (int)fy;
+    const auto at = [&](int ii, int jj) -> uint32_t {
+        return ii >= 0 && ii < H && jj >= 0 && jj < W ? (uint32_t)F[(size_t)ii + (size_t)H * (size_t)jj] : 0xFFFFu;
+    };
+    const uint32_t f = at(i, j);
+    if (f == 0xFFFFu || f == 0u) return;
+    const int side[4][2] = {{i - 1, j}, {i + 1, j}, {i, j - 1}, {i, j + 1}};
+    int n = -1;
+    for (int c = 0; c < 4 && n < 0; ++c)
+        if (at(side[c][0], side[c][1]) == f - 1u) n = c;
+    if (n < 0) return;                                                     // (a field no flood wrote)
+    const T ctx = (T)i + (T)0.5, cty = (T)j + (T)0.5;
+    const T cnx = (T)side[n][0] + (T)0.5, cny = (T)side[n][1] + (T)0.5;
+    const T e = n < 2 ? y - cty : x - ctx;
+    const bool go = std::fabs(e) <= inc;
+    const T vx = (go ? cnx : ctx) - x, vy = (go ? cny : cty) - y;
+    int32_t arg = 0;
+    bool any = false;
+    T best = (T)0;
+    for (int32_t k = 0; k < nd; ++k) {
+        const T a = D[2 * (size_t)k] * vx, b = D[2 * (size_t)k + 1] * vy;
+        const T s = a + b;
+        if (std::isnan(s)) continue;
+        if (!any || s > best) { any = true; best = s; arg = k; }
+    }
+    const int64_t delta = ((((int64_t)arg - (int64_t)d) % nd) + nd) % nd;
+    *heading = arg;
+    *action = delta == 0 ? 1 : (delta <= nd / 2 ? 3 : 4);
+}
+}  // namespace
+
+// The handle-less export: needs no device.
+extern "C" int rcw_guide_rule(int32_t H, int32_t W, const void* field, double x, double y, int32_t world_unit_bits, int32_t direction,
+                              int32_t nd, const void* directions_wu, double position_increment, uint8_t* action, int32_t* heading)
+{
+    if (!field || !directions_wu || !action || !heading) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (H < 1 || W < 1 || (int64_t)H * W > 65535) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_guide_rule: a field of %d x %d", H, W);
+    if (world_unit_bits != 32 && world_unit_bits != 64) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_guide_rule: world_unit_bits must be 32 or 64 (got %d)", world_unit_bits);
+    if (nd < 1 || direction < 0 || direction >= nd) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_guide_rule: direction %d of %d", direction, nd);
+    if (world_unit_bits == 64)
+        guide_rule_one<double>(H, W, static_cast<const uint16_t*>(field), x, y, direction, nd, static_cast<const double*>(directions_wu), position_increment, action, heading);
+    else
+        guide_rule_one<float>(H, W, static_cast<const uint16_t*>(field), (float)x, (float)y, direction, nd, static_cast<const float*>(directions_wu), (float)position_increment, action, heading);
+    return RCW_OK;
+}
+
 // THE PER-AGENT ARRAYS (rcw_handle.h): the parts of `feature` (AgentFeature) of a handle of this shape, in the order an exported row of the
 // state archive holds them, and the bytes of the feature's head.  What is off has no parts and no head.  This is the ONE place that knows
 // an array's bytes per agent: the setters carve it, the archive records it, the readouts copy it.  `kept` = false: a part the archive
@@ -730,6 +796,10 @@ void agent_arrays(const SnapshotShape& sh, int feature, AgentArrays* out)
         add(kSnapStatsPrevX, "episode_stats.prev_x", real);
         add(kSnapStatsPrevY, "episode_stats.prev_y", real);
         add(kSnapStatsLast, "episode_stats.last_episode", 4);
+    }
+    if (feature == kFeatGuide && sh.guide) {                               // computed from the state, never recorded: a row fits a handle with or without it
+        add(kSnapGuideAction, "guide.action", 1, 0, false);
+        add(kSnapGuideHeading, "guide.heading", 4, 0, false);
     }
 }
 

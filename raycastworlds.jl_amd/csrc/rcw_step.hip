@@ -251,6 +251,15 @@ hipError_t launch_episode_stats(rcw_handle* h, const uint8_t* mask_dev, StackOp 
                                     h->goal.on() ? h->goal.words.start_distance : nullptr, mask_dev, op == kStackRefill, h->stream);
 }
 
+// ... and the guide, directly behind the goal distance whose field it reads.  A pure function of (field, position, heading, direction table), for every
+// agent: it also runs where the goal distance does not — behind a new direction table (kStackRefillSameWorld) —, and launch_snapshot asks
+// for it behind a restore's render.  A re-render of the very same frames (kStackKeep) changes none of the four and launches nothing.
+hipError_t launch_guide(rcw_handle* h, StackOp op)
+{
+    if (!h->guide.on() || !h->goal.on() || op == kStackKeep) return hipSuccess;
+    return rcw_launch_guide(h->dev, h->B, h->goal.field.get<uint16_t>(), h->guide.words, h->stream);
+}
+
 // The layout source (rcw_handle::LayoutSource), behind the core launches of a call that can move an episode counter: its kernel gives every
 // agent that began an episode a layout and a fresh state against it, and leaves in the source's own mask who that was.  force: every agent
 // (the call that installs the source).  Behind rcw_reset the caller's re-render covers exactly those agents; behind a step, launch_step
@@ -274,6 +283,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
         if (e == hipSuccess && restarts) e = launch_step_camera(h, nullptr, restarted, true);
         if (e == hipSuccess && h->learner.on()) e = launch_view(h, mask_dev, op);
         if (e == hipSuccess) e = launch_goal_distance(h, mask_dev, op);
+        if (e == hipSuccess) e = launch_guide(h, op);
         if (e == hipSuccess) e = launch_seen_map(h, mask_dev, op);
         if (e == hipSuccess) e = launch_local_map(h, op);
         return e == hipSuccess ? launch_episode_stats(h, mask_dev, op) : e;
@@ -293,6 +303,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if ((e = launch_view(h, mask_dev, op)) != hipSuccess) return e;
     if ((e = prof.done(h->stream)) != hipSuccess) return e;
     if ((e = launch_goal_distance(h, mask_dev, op)) != hipSuccess) return e;
+    if ((e = launch_guide(h, op)) != hipSuccess) return e;
     if ((e = launch_seen_map(h, mask_dev, op)) != hipSuccess) return e;
     if ((e = launch_local_map(h, op)) != hipSuccess) return e;
     return launch_episode_stats(h, mask_dev, op);
@@ -302,7 +313,8 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
 // archive's: every segment has its live array).  Both: who takes which row, then the copy — the segment table goes to the kernel
 // kSnapshotKernelSegments at a time.  A save is done there.  A restore goes on: the step's facts forget the slots (StepFacts::restored), and
 // the agents of the mask are cast and painted from the state they now hold, as a re-render of the same frames is (kStackKeep): the flood, the
-// seen map, the stack, the local map and the statistics are the record's and stay as the gather left them.
+// seen map, the stack, the local map and the statistics are the record's and stay as the gather left them.  The guide's words are no part
+// of the record: its kernel follows, on the restored state.
 hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t* mask_dev, bool restore)
 {
     rcw_handle::Snapshots& sn = h->snaps;
@@ -321,7 +333,8 @@ hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t
     }
     if (!restore) return hipSuccess;
     h->step.restored();
-    return launch_step(h, nullptr, mask_dev, kStackKeep);
+    if ((e = launch_step(h, nullptr, mask_dev, kStackKeep)) != hipSuccess) return e;
+    return launch_guide(h, kStackRefill);                        // (no part of the record: computed from the restored field, pose and the table as it is now)
 }
 
 // THE way a buffer of a live handle is given up: wait_all_streams (queued work may still use the old ones), then each of `old` takes

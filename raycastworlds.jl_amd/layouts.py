@@ -1,5 +1,5 @@
 """Wall layouts for `SingleRoom.set_walls`: host-side numpy, nothing here touches the device (`generated_maze` and
-`generated_maze_key`, `generated_cave` and `generated_rooms` call the library's handle-less host functions: no device either).
+`generated_maze_key`, `generated_cave`, `generated_rooms` and `guide_rule` call the library's handle-less host functions: no device either).
 
 A layout is bool (H, W) with `walls[i-1, j-1]` = tile (i, j) is a WALL — the index order of `env.world.tile_map[b, 0]`.
 Every generator returns the wall ring (SR:57-60) closed, as `rcw_set_walls` requires, and at least two free interior
@@ -152,6 +152,31 @@ def generated_rooms(key: int, H: int, W: int, room: int = 2, stop=0.25, doors=0.
         raise ValueError(_capi.last_error(lib))
     walls = np.ascontiguousarray(out.T != 0)
     return (walls, int(rooms.value)) if return_rooms else walls
+
+
+def guide_rule(field, position, direction: int, directions_wu, position_increment: float, T="Float32"):
+    """The guide's rule (include/rcw.h, "the guide") for ONE agent on the host: (action, heading) — action in 1..4, heading the 0-based
+    direction index the guide wants, -1 where it has no advice.  `field`: uint16 (H, W), one agent's `env.goal_distance_field[b]`;
+    `position`: (x, y) in world units; `direction`: the agent's 0-based heading; `directions_wu`: (nd, 2), `env.world.directions_wu`'s layout
+    (row k the direction of index k); `T`: the world-unit type the rule computes in.  rcw_guide_rule: host arithmetic, no device."""
+    import ctypes as C
+
+    from . import _capi
+
+    lib = _capi.load()
+    real = np.float64 if str(T) in ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>") else np.float32
+    f = np.ascontiguousarray(np.asarray(field, dtype=np.uint16).T)         # tile (i, j), 0-based, at i + H j
+    if f.ndim != 2:
+        raise ValueError(f"one field (H, W) at a time, got {f.shape}")
+    table = np.ascontiguousarray(directions_wu, dtype=real)                # entry k at (2 k, 2 k + 1)
+    if table.ndim != 2 or table.shape[1] != 2:
+        raise ValueError(f"directions_wu is (nd, 2), got {np.shape(directions_wu)}")
+    action, heading = C.c_uint8(), C.c_int32()
+    rc = lib.rcw_guide_rule(f.shape[1], f.shape[0], f.ctypes.data, float(position[0]), float(position[1]), 64 if real is np.float64 else 32,
+                            int(direction), table.shape[0], table.ctypes.data, float(position_increment), C.byref(action), C.byref(heading))
+    if rc != _capi.RCW_OK:
+        raise ValueError(_capi.last_error(lib))
+    return int(action.value), int(heading.value)
 
 
 def is_connected(walls) -> bool:

@@ -213,6 +213,19 @@ class ShardedSingleRoom:
         """`SingleRoom.set_wall_bank_weights`, the same weights on every rank."""
         self.env.set_wall_bank_weights(weights)
 
+    # ---- the guide: a function of each agent's own state, so a shard's words are its slice of the batch's ----
+    def set_guide(self, on: bool = True) -> None:
+        """`SingleRoom.set_guide` of this rank's engine (also the `guide=True` keyword); `guide_action` / `guide_heading` are LOCAL."""
+        self.env.set_guide(on)
+
+    @property
+    def guide_action(self):
+        return self.env.guide_action
+
+    @property
+    def guide_heading(self):
+        return self.env.guide_heading
+
     # ---- the state archive: every shard has its own, rows are LOCAL ---------------------------
     def set_snapshots(self, rows: int) -> None:
         """`SingleRoom.set_snapshots` of this rank's engine: `rows` records a SHARD.  Rows do not cross shards."""

@@ -346,6 +346,7 @@ class SingleRoom:
     `max_episode_steps` (this build's addition; 0 = none, the reference's behaviour) is the episode time limit of
     `set_time_limit`.  `walls` / `wall_index` (this build's addition; None = the reference's empty room) are `set_walls`'
     arguments, applied right after construction.  `goal_distance` (this build's addition) is `set_goal_distance(True)` after them,
+    `guide` (this build's addition) `set_guide(True)` right behind it (it enables the goal distance where that is off),
     `seen_map` (this build's addition) `set_seen_map(True)` after that, `local_map` (this build's addition; an int — the size — or a dict
     of `set_local_map`'s keywords) `set_local_map` after that, `episode_stats` (this build's addition) `set_episode_stats(True)` last of
     all — behind the layout sources below, whose levels count its table's rows.  `wall_bank` / `wall_bank_weights` (this build's addition) are `set_wall_bank`'s
@@ -391,6 +392,7 @@ class SingleRoom:
         walls=None,
         wall_index=None,
         goal_distance: bool = False,
+        guide: bool = False,
         seen_map: bool = False,
         local_map=None,
         wall_bank=None,
@@ -513,6 +515,12 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        if guide:
+            try:
+                self.set_guide(True)
+            except BaseException:
+                self._handle.close()
+                raise
         if seen_map:
             try:
                 self.set_seen_map(True)
@@ -563,7 +571,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_seen_map_dev", "_local_map_dev", "_episode_stats_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_guide_dev", "_seen_map_dev", "_local_map_dev", "_episode_stats_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -891,6 +899,8 @@ class SingleRoom:
         restarts with no host synchronisation.  Switching it on (again) recomputes everything and makes the current state the
         episode's start; the device arrays handed out before are invalid after every call."""
         self.__dict__.pop("_goal_distance_dev", None)
+        if not on:
+            self.__dict__.pop("_guide_dev", None)                 # (the guide reads the field: it goes with it)
         self._check(self._lib.rcw_set_goal_distance(self._h, 1 if on else 0))
 
     @property
@@ -950,6 +960,60 @@ class SingleRoom:
         H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
         return DeviceArray(p.value, (self.batch, W, H), np.uint16, self, self._sync,
                            host_getter=lambda: np.ascontiguousarray(self.goal_distance_field.transpose(0, 2, 1)))
+
+    # ---- the guide (include/rcw.h, rcw_set_guide) ----------------------------------------
+    def set_guide(self, on: bool = True) -> None:
+        """Keep, on the device, the action that follows each agent's shortest path to its goal (`guide_action`, uint8 in 1..4: what `act_`
+        takes as it stands) and the direction index it wants the agent to face (`guide_heading`, int32, -1: no advice — no path, or on
+        the goal tile; the action is then a turn on the spot), rewritten behind every call that moves an agent, a goal or a wall, a new
+        direction table and a `snapshot_restore`.  The label imitation learning and DAgger need, with no host in the loop:
+        `torch.where(beta, env.guide_action.torch(sync=False), policy_action)`.  Switching it on enables the goal distance first where
+        that is off; `set_goal_distance(False)` switches the guide off too.  The device arrays handed out before are invalid after
+        every call."""
+        self.__dict__.pop("_guide_dev", None)
+        if on and not self.goal_distance_enabled:
+            self.set_goal_distance(True)
+        self._check(self._lib.rcw_set_guide(self._h, 1 if on else 0))
+
+    @property
+    def guide_info(self) -> dict:
+        """`enabled`, and `promised`: whether position_increment + player_radius <= 0.5, for which an agent that follows the guide is
+        promised to arrive (rcw_guide_info)."""
+        v = [C.c_int32(), C.c_int32()]
+        self._check(self._lib.rcw_guide_info(self._h, C.byref(v[0]), C.byref(v[1])))
+        return {"enabled": bool(v[0].value), "promised": bool(v[1].value)}
+
+    @property
+    def guide_enabled(self) -> bool:
+        return self.guide_info["enabled"]
+
+    def _guide_host(self, which: int) -> np.ndarray:
+        out = np.empty(self.batch, dtype=(np.uint8, np.int32)[which])
+        args = [None, None]
+        args[which] = _as_ptr(out)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_guide(self._h, *args))
+        return out
+
+    def _guide_arrays(self):
+        if getattr(self, "_guide_dev", None) is None:
+            p = [C.c_void_p(), C.c_void_p()]
+            self._check(self._lib.rcw_guide_device_ptr(self._h, C.byref(p[0]), C.byref(p[1])))
+            self._guide_dev = tuple(
+                DeviceArray(p[k].value, (self.batch,), dtype, self, self._sync, host_getter=lambda k=k: self._guide_host(k))
+                for k, dtype in enumerate((np.uint8, np.int32)))
+        return self._guide_dev
+
+    @property
+    def guide_action(self) -> DeviceArray:
+        """uint8 (B,): the guide's action for every agent, always in 1..4.  `.torch(sync=False)` on the GPU — `act_` takes it as it is —,
+        `np.asarray(...)` for a host copy."""
+        return self._guide_arrays()[0]
+
+    @property
+    def guide_heading(self) -> DeviceArray:
+        """int32 (B,): the 0-based direction index the guide wants each agent to face, -1 where it has no advice."""
+        return self._guide_arrays()[1]
 
     # ---- episode statistics (include/rcw.h, rcw_set_episode_stats) ----------------------
     _EPISODE_WORDS = (("finished", np.uint8), ("outcome", np.uint8), ("length", np.uint32), ("moves", np.uint32), ("level", np.int32),
