@@ -416,7 +416,8 @@ RCW_API int rcw_goal_distance_field_device_ptr(rcw_handle* h, void** ptr);
  *   rcw_set_seen_map(h, 1)        allocates; every agent's map is cleared and marked from its current pose: seen_count is the result,
  *                                 newly_seen = 0, goal_seen is set.  On a handle that has it, the same again.  An allocation failure
  *                                 leaves what was there.
- *   rcw_set_seen_map(h, 0)        frees it (RCW_OK also where there was none).
+ *   rcw_set_seen_map(h, 0)        frees it (RCW_OK also where there was none).  On a handle with the frontier on (rcw_set_frontier, which
+ *                                 floods over the map): RCW_ERR_UNSUPPORTED, and nothing changes — switch the frontier off first.
  *   rcw_reset, rcw_set_state, rcw_set_state64, rcw_set_walls
  *                                 the agents in the call's mask are cleared and marked from the new pose against the new world,
  *                                 newly_seen = 0, and the episode counter is recorded; an agent outside the mask keeps every byte and
@@ -808,6 +809,79 @@ RCW_API int rcw_guide(rcw_handle* h, uint8_t* action /* (B) */, int32_t* heading
 RCW_API int rcw_guide_device_ptr(rcw_handle* h, void** action, void** heading);
 RCW_API int rcw_guide_rule(int32_t H, int32_t W, const void* field /* UInt16 (H*W) */, double x, double y, int32_t world_unit_bits, int32_t direction,
                            int32_t nd, const void* directions_wu /* (2, nd) in T */, double position_increment, uint8_t* action, int32_t* heading);
+/* ---- the frontier (this build's addition: each agent's way to the nearest unseen tile, kept on the device) -----------------------------
+ * Opt-in per handle, on a handle that has the seen map on: the boundary between what an agent has seen and what it has not, how far away
+ * it is and which action leads there — a frontier-following expert for imitation or DAgger, the "explore until goal_seen, then follow the
+ * guide" baseline a partially observing agent can match, a frontier-distance shaping term, an "exploration complete" signal — at no host
+ * synchronisation.  A handle that never enables it runs exactly the kernels it ran before.  The ABI is additive: RCW_ABI_VERSION and
+ * rcw_config are what they were.
+ * THE DEFINITION.  For agent a, M its seen map, UInt8 (H*W) in the tile map's linear order (tile (i, j), 0-based, at i + H*j):
+ *   passable(t)  <=>  M[t] is 1 or 3 (a seen free tile, a seen goal tile)
+ *   source(t)    <=>  M[t] == 0 and some edge neighbour of t THAT LIES ON THE MAP is passable.  Tiles (H-1, j) and (0, j+1) are adjacent
+ *                     in linear order and are no neighbours.
+ * Per-agent state, device arrays:
+ *   field      UInt16 (H*W, B), in the seen map's order.  A source holds 0.  A passable tile holds the least number of edge moves to a
+ *              source, moving through passable tiles only; the last move enters the source, so a passable tile next to a source holds 1.
+ *              Every other tile holds 0xFFFF: seen walls (2, 4), unseen tiles that are no sources, passable tiles from which no source
+ *              can be reached.  A breadth-first level is a set: the values do not depend on the order in which a flood visits tiles.
+ *   distance   Int32 (B)   field at the player's tile (floor x, floor y); -1 where that is 0xFFFF, or the tile is off the map, or x or y is
+ *                          not finite (the kernel checks and never reads outside the field)
+ *   tiles      Int32 (B)   the number of sources as of the agent's last flood
+ *   action     UInt8 (B)   always in 1..4
+ *   heading    Int32 (B)   the 0-based direction index to face; -1 where distance is -1 or the agent is off the map
+ * action and heading are THE GUIDE'S RULE ("the guide" above, steps 1-5, verbatim) applied to this field in place of the goal distance's
+ * — the same kernel, launched on this field.  The one definition makes that rule work unchanged: an agent always stands on a tile it has
+ * seen, so its own entry is at least 1; one tile from the frontier it is told to face the unseen tile; facing it makes the view rays cross
+ * it, the seen map changes, and the field is flooded again.  (An agent placed ON a source by rcw_set_state would hold 0 and be told to
+ * turn on the spot, as on the goal tile; the seen map's launch in front marks the player's tile, so no call leaves an agent there.)
+ * WHAT -1 MEANS: nothing left to explore from here.  distance == -1 on a seen free tile p says no source is reachable from p through
+ * passable tiles.  Then every free tile q that is 4-connected to p through free tiles has been seen: walk a path of free tiles from p to q;
+ * if some tile on it were unseen, the first such tile would have a seen free — passable — predecessor on the path, so it would be a source,
+ * reachable from p along the seen part of the path.  And every tile next to such a q has been seen too: an unseen one would be a source
+ * one move from q.  So the agent's whole component and its rim are on the map.
+ * NO BOUND ON ARRIVAL IS PROMISED.  Observed on 13 x 13 generated mazes with loops 0.1, nd 16, 8 rays, position_increment =
+ * player_radius = 0.25, agents that follow `action` until distance == -1 or until they touch their goal: 16 agents of the CPU reference
+ * (tests/test_frontier_spec.py, which allows 2,000 steps) took 333 steps at most; of 256 agents on the device (tests/test_gpu_frontier.py,
+ * which allows 4,000) 8 were still exploring after 500 steps and none after 1,000.  A direction table without an axis-aligned heading
+ * (nd 7) may never get there — the limit the guide's promise states.
+ * What each call does — stream-ordered on the handle's stream, directly behind the seen map's launch, with no host wait:
+ *   rcw_set_frontier(h, 1)        RCW_ERR_UNSUPPORTED on a handle without the seen map.  Allocates, floods every agent and computes all
+ *                                 words; on a handle that has it, the same again.  An allocation failure leaves what was there.
+ *   rcw_set_frontier(h, 0)        frees it (RCW_OK also where there was none).
+ *   rcw_set_seen_map(h, 1)        (again) every agent is flooded again from the new map, and the words follow.
+ *   rcw_set_seen_map(h, 0)        while the frontier is on: RCW_ERR_UNSUPPORTED, nothing changes (the local map's rule for RCW_LOCAL_SEEN).
+ *   rcw_reset, rcw_set_state, rcw_set_state64, rcw_set_walls
+ *                                 the agents of the call's mask are flooded again; the others keep field, distance and tiles.  action and
+ *                                 heading, a pure function of field, pose and table, are computed again for every agent.
+ *   rcw_step, rcw_step_device     an agent is flooded again if and only if its episode counter differs from the one recorded at its last
+ *                                 flood, or the seen map's newly_seen word of this call is not 0; every other agent gets only distance
+ *                                 re-read at its new tile.  action and heading for every agent.  This covers the install and the restarts
+ *                                 of the wall bank and of every generator family: the features run once behind the final world.
+ *   rcw_set_direction_table*      action and heading only.
+ *   rcw_snapshot_restore*         field and words are NO part of the record.  Behind the restore's render the agents of the mask are
+ *                                 flooded again from the restored seen map; action and heading for every agent.
+ *   rcw_set_time_limit, the learner-view, goal-distance, guide, local-map and statistics calls, rcw_snapshot_save* and every getter
+ *                                 nothing.
+ * A replayed HIP graph of a step behaves like any step: nothing about this alternates on the host, the recorded episode counter lives on
+ * the device.  Capture again after enabling or disabling.  The launches (rcw_frontier_kernel, then the guide's kernel) run OUTSIDE
+ * rcw_profile's events.
+ *   rcw_frontier_info               enabled.
+ *   rcw_frontier                    host copies of distance, tiles, action, heading (any pointer may be NULL); waits for the stream as
+ *                                   rcw_done does.
+ *   rcw_frontier_device_ptr         the four arrays where they live (any pointer may be NULL), stable until the next rcw_set_frontier.
+ *   rcw_frontier_field              agents [first, first + count) of the field to the host; waits for the stream.
+ *   rcw_frontier_field_device_ptr   the field where it lives.
+ *   rcw_frontier_rule               handle-less, needs no device: the flood for ONE agent on the host.  seen_map UInt8 (H*W) in the order
+ *                                   above — any byte above 4 counts as a wall —, field_out UInt16 (H*W), *tiles_out the number of sources.
+ *                                   H, W >= 1 and H*W <= 65535; anything else — a NULL pointer included — is RCW_ERR_INVALID_ARGUMENT.
+ * The readouts return RCW_ERR_UNSUPPORTED on a handle that has not enabled it. */
+RCW_API int rcw_set_frontier(rcw_handle* h, int32_t enable);
+RCW_API int rcw_frontier_info(rcw_handle* h, int32_t* enabled);
+RCW_API int rcw_frontier(rcw_handle* h, int32_t* distance /* (B) */, int32_t* tiles /* (B) */, uint8_t* action /* (B) */, int32_t* heading /* (B) */);
+RCW_API int rcw_frontier_device_ptr(rcw_handle* h, void** distance, void** tiles, void** action, void** heading);
+RCW_API int rcw_frontier_field(rcw_handle* h, int32_t first, int32_t count, void* out_host /* UInt16 (H*W, count) */);
+RCW_API int rcw_frontier_field_device_ptr(rcw_handle* h, void** ptr);
+RCW_API int rcw_frontier_rule(int32_t H, int32_t W, const uint8_t* seen_map /* (H*W) */, void* field_out /* UInt16 (H*W) */, int32_t* tiles_out);
 
 /* ---- The state archive (this build's addition: the reference has no checkpoint) -------------------------------------------------------
  * `rows` agent RECORDS kept on the device and owned by the handle: save scatters the records of the masked agents into rows, restore
@@ -833,6 +907,9 @@ RCW_API int rcw_guide_rule(int32_t H, int32_t W, const void* field /* UInt16 (H*
  *   direction table —
  *   the guide's two words                                                                     a restore computes them again: a row fits
  *                                                                                             a handle with or without the guide;
+ *   the frontier's field and words                                                            a restore floods the restored agents again
+ *                                                                                             from the restored seen map: a row fits a
+ *                                                                                             handle with or without the frontier;
  * If row r was saved from agent j and is restored into agent i, agent i holds j's world; its next episode starts under i's global id and
  * the copied episode counter.
  *

@@ -504,6 +504,59 @@ function seen_map_device_ptr(env::BatchedSingleRoom)
     check(ccall((:rcw_seen_map_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
 end
 
+# ---- the frontier (this build's addition; include/rcw.h, rcw_set_frontier) ------------------------------------------------------
+"""
+    set_frontier!(env, on = true)
+
+Keep, on the device, each agent's way to the nearest unseen tile, directly behind the seen map (`set_seen_map!` first; `set_seen_map!(env,
+false)` is refused while the frontier is on): `frontier(env)` returns `(distance, tiles, action, heading)` — `distance` a `Vector{Int32}`
+of `batch`, the moves to the nearest frontier tile, `-1` where nothing is left to explore from the agent's tile; `tiles` how many frontier
+tiles its last flood found; `action` a `Vector{UInt8}`, always in 1..4 (what `act!` takes); `heading` the 0-based direction index to
+face, `-1` where there is no advice.  `frontier_field(env)` is the `UInt16` field as `(H, W, batch)`: `0` on the unseen tiles next to a
+seen free one, on a seen free tile the moves to the nearest of them, `0xFFFF` elsewhere.  `frontier_rule` is the flood for one agent on
+the host, without a device.
+"""
+function set_frontier!(env::BatchedSingleRoom, on::Bool = true)
+    check(ccall((:rcw_set_frontier, librcw), Cint, (Ptr{Cvoid}, Int32), env.handle, on ? 1 : 0))
+    return nothing
+end
+function frontier_info(env::BatchedSingleRoom)
+    e = Ref{Int32}(0)
+    check(ccall((:rcw_frontier_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}), env.handle, e))
+    return (enabled = e[] != 0,)
+end
+function frontier(env::BatchedSingleRoom)
+    d = Vector{Int32}(undef, env.batch); t = Vector{Int32}(undef, env.batch)
+    a = Vector{UInt8}(undef, env.batch); h = Vector{Int32}(undef, env.batch)
+    check(ccall((:rcw_frontier, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}), env.handle, d, t, a, h))
+    return (distance = d, tiles = t, action = a, heading = h)
+end
+function frontier_device_ptr(env::BatchedSingleRoom)
+    d, t, a, h = (Ref{Ptr{Cvoid}}(C_NULL) for _ in 1:4)
+    check(ccall((:rcw_frontier_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                env.handle, d, t, a, h))
+    return (distance = d[], tiles = t[], action = a[], heading = h[])
+end
+function frontier_field(env::BatchedSingleRoom, first::Integer = 0, count::Integer = env.batch - first)
+    out = Array{UInt16, 3}(undef, env.config.height_tile_map_tu, env.config.width_tile_map_tu, count)
+    check(ccall((:rcw_frontier_field, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}), env.handle, first, count, out)); out
+end
+function frontier_field_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_frontier_field_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
+"""
+    frontier_rule(seen_map) -> (field, tiles)
+
+The frontier's flood for one agent: `seen_map` a `Matrix{UInt8}` `(H, W)` (one agent's `seen_map`), `field` a `Matrix{UInt16}` `(H, W)`.
+"""
+function frontier_rule(seen_map::Matrix{UInt8})
+    field = Matrix{UInt16}(undef, size(seen_map)...); n = Ref{Int32}(0)
+    check(ccall((:rcw_frontier_rule, librcw), Cint, (Int32, Int32, Ptr{UInt8}, Ptr{Cvoid}, Ref{Int32}),
+                size(seen_map, 1), size(seen_map, 2), seen_map, field, n))
+    return (field = field, tiles = n[])
+end
+
 # ---- the local map (this build's addition; include/rcw.h, rcw_set_local_map) ----------------------------------------------------
 const LOCAL_MAP_SOURCES = (off = Int32(0), world = Int32(1), seen = Int32(2))
 """

@@ -180,6 +180,13 @@ SIGNATURES = {
     "rcw_guide": [_vp, _vp, _vp],
     "rcw_guide_device_ptr": [_vp, C.POINTER(_vp), C.POINTER(_vp)],
     "rcw_guide_rule": [_i32, _i32, _vp, C.c_double, C.c_double, _i32, _i32, _i32, _vp, C.c_double, C.POINTER(C.c_uint8), C.POINTER(_i32)],
+    "rcw_set_frontier": [_vp, _i32],
+    "rcw_frontier_info": [_vp, C.POINTER(_i32)],
+    "rcw_frontier": [_vp, _vp, _vp, _vp, _vp],
+    "rcw_frontier_device_ptr": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+    "rcw_frontier_field": [_vp, _i32, _i32, _vp],
+    "rcw_frontier_field_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_frontier_rule": [_i32, _i32, _vp, _vp, C.POINTER(_i32)],
     "rcw_set_snapshots": [_vp, _i32],
     "rcw_snapshot_info": [_vp, C.POINTER(_i32), C.POINTER(_u64), C.POINTER(_u64)],
     "rcw_snapshot_save": [_vp, _vp, _vp],

@@ -94,7 +94,7 @@ __attribute__((visibility("default"))) int rcw_dev_validate_walls(int32_t H, int
 // The state archive's record without a device (tests/test_snapshot_spec.py).  shape: the 23 Int32 of SnapshotShape in its order — H, W, nd, N,
 // Hc, real64, reward_type | goal, seen, stats | view_fmt, view_layout, view_C, view_h, view_w, view_frames | local_source, local_size,
 // local_cells | source_kind | layouts, levels, first_level.  names: the segments' names, a line each; bytes [n]; returns n, -1: names too small.
-static_assert(sizeof(SnapshotShape) == (kSnapshotShapeWords + 1) * sizeof(int32_t), "SnapshotShape travels as its first 23 Int32: the guide, which is no part of a record, stays off");
+static_assert(sizeof(SnapshotShape) == (kSnapshotShapeWords + 2) * sizeof(int32_t), "SnapshotShape travels as its first 23 Int32: the guide and the frontier, which are no part of a record, stay off");
 __attribute__((visibility("default"))) int rcw_dev_snapshot_plan(const int32_t* shape, char* names, int32_t cap, uint32_t* bytes, uint64_t* row_bytes, uint64_t* key)
 {
     if (!shape || !names || cap < 1 || !bytes || !row_bytes || !key) return RCW_ERR_INVALID_ARGUMENT;
@@ -113,7 +113,7 @@ __attribute__((visibility("default"))) int rcw_dev_snapshot_plan(const int32_t* 
     return plan.n;
 }
 // The per-agent arrays of one feature (AgentFeature: 0 core state, 1 goal distance, 2 seen map, 3 learner view, 4 local map, 5 layout source,
-// 6 episode statistics, 7 the guide — off in every shape that travels here) of that shape, and their carve for `batch` agents as ONE buffer behind the feature's head (tests/
+// 6 episode statistics, 7 the guide, 8 the frontier — both off in every shape that travels here) of that shape, and their carve for `batch` agents as ONE buffer behind the feature's head (tests/
 // test_agent_arrays_spec.py): names a line each; ids, bytes (per agent), archived, offsets [n]; returns n (0: the feature is off), -1: names
 // too small.
 __attribute__((visibility("default"))) int rcw_dev_agent_arrays(const int32_t* shape, int32_t feature, int32_t batch, char* names, int32_t cap, int32_t* ids,
@@ -140,6 +140,30 @@ __attribute__((visibility("default"))) int rcw_dev_agent_arrays(const int32_t* s
 __attribute__((visibility("default"))) int rcw_dev_guide_promised(const rcw_config* cfg)
 {
     return cfg ? guide_promised(*cfg) : RCW_ERR_INVALID_ARGUMENT;
+}
+// The frontier's arrays and the record of a shape WITH the frontier on (tests/test_frontier_spec.py; `frontier` does not travel in the 23
+// words): names a line each, bytes (per agent) and archived [n] of kFeatFrontier's parts; the plan's segment count, row bytes and key — to be
+// held to rcw_dev_snapshot_plan's of the same 23 words.  Returns n, -1: names too small.
+__attribute__((visibility("default"))) int rcw_dev_frontier_plan(const int32_t* shape, char* names, int32_t cap, uint32_t* bytes, uint8_t* archived,
+                                                                 int32_t* segments, uint64_t* row_bytes, uint64_t* key)
+{
+    if (!shape || !names || cap < 1 || !bytes || !archived || !segments || !row_bytes || !key) return RCW_ERR_INVALID_ARGUMENT;
+    SnapshotShape sh;
+    std::memcpy(&sh, shape, kSnapshotShapeWords * sizeof(int32_t));
+    sh.frontier = 1;
+    AgentArrays a;
+    agent_arrays(sh, kFeatFrontier, &a);
+    int n = 0;
+    for (int k = 0; k < a.n; ++k) {
+        const int m = std::snprintf(names + n, (size_t)(cap - n), "%s\n", a.part[k].name);
+        if (m < 0 || m >= cap - n) return -1;
+        n += m;
+        bytes[k] = a.part[k].bytes; archived[k] = a.part[k].archived ? 1 : 0;
+    }
+    SnapshotPlan plan;
+    plan_snapshot(sh, &plan);
+    *segments = plan.n; *row_bytes = plan.row_bytes; *key = plan.key;
+    return a.n;
 }
 // rcw_snapshot_rows_load's check of one exported row of that shape: validate_snapshot_row's return code, its reason in msg
 __attribute__((visibility("default"))) int rcw_dev_snapshot_validate_row(const int32_t* shape, const uint8_t* row, char* msg, int32_t cap)

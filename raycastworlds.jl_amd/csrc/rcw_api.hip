@@ -155,6 +155,7 @@ SnapshotShape snapshot_shape(const rcw_handle* h)
     s.source_kind = (int32_t)h->source.dev.kind;
     s.layouts = h->source.dev.agents.layouts; s.levels = h->source.dev.gen.levels; s.first_level = h->source.dev.gen.first_level;
     s.guide = h->guide.on();
+    s.frontier = h->frontier.on();
     return s;
 }
 
@@ -187,6 +188,7 @@ const char* const kNoLocalMap = "the handle has no local map (rcw_set_local_map)
 const char* const kNoDrawnWalls = "the handle has neither a wall bank (rcw_set_wall_bank) nor a wall generator (rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms)";
 const char* const kNoEpisodeStats = "the handle keeps no episode statistics (rcw_set_episode_stats)";
 const char* const kNoGuide = "the handle has no guide (rcw_set_guide)";
+const char* const kNoFrontier = "the handle has no frontier (rcw_set_frontier)";
 int need(bool on, const char* why_off) { return on ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "%s", why_off); }
 
 // (the array of the learner view the caller sees: the k-frame stack, or the one frame)
@@ -1117,6 +1119,8 @@ int rcw_set_seen_map(rcw_handle* h, int32_t enable)
     if (!enable && !sm.on()) return RCW_OK;
     if (!enable && h->local.source == RCW_LOCAL_SEEN)
         return fail(RCW_ERR_UNSUPPORTED, "the handle's local map reads the seen map: switch the local map off first (rcw_set_local_map)");
+    if (!enable && h->frontier.on())
+        return fail(RCW_ERR_UNSUPPORTED, "the handle's frontier floods over the seen map: switch the frontier off first (rcw_set_frontier(h, 0))");
     rcw_handle::SeenMap fresh;
     LiveArray at[kSnapFieldCount] = {};
     if (enable) {
@@ -1135,6 +1139,7 @@ int rcw_set_seen_map(rcw_handle* h, int32_t enable)
     RCW_HIP(take_live(h, kFeatSeen, at));
     sm = std::move(fresh);
     if (sm.on()) RCW_HIP(launch_seen_map(h, nullptr, kStackRefill));
+    if (sm.on()) RCW_HIP(launch_frontier(h, nullptr, kStackRefill));
     if (sm.on()) RCW_HIP(launch_local_map(h, kStackRefill));
     return RCW_OK;
 }
@@ -1164,6 +1169,62 @@ int rcw_seen_map(rcw_handle* h, int32_t first, int32_t count, void* out_host)
 }
 
 int rcw_seen_map_device_ptr(rcw_handle* h, void** ptr) { return hand_out(h, kNoSeenMap, {{ptr, kSnapSeenMap}}); }
+
+// The frontier (include/rcw.h).  Enabling allocates and floods every agent at once, stream-ordered behind what is queued; enabling again
+// does the same again; an allocation failure leaves what was there.
+int rcw_set_frontier(rcw_handle* h, int32_t enable)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::Frontier& fr = h->frontier;
+    if (!enable && !fr.on()) return RCW_OK;
+    if (enable) { rc = need(h->seen.on(), "the frontier floods over the seen map: enable it first (rcw_set_seen_map(h, 1))"); if (rc) return rc; }
+    if (enable && (int64_t)h->dev.H * h->dev.W > 65535) return fail(RCW_ERR_UNSUPPORTED, "the frontier's field holds UInt16 tile indices: a map of %d x %d is too large", h->dev.H, h->dev.W);
+    rcw_handle::Frontier fresh;
+    LiveArray at[kSnapFieldCount] = {};
+    if (enable) {
+        SnapshotShape sh = snapshot_shape(h);
+        sh.frontier = 1;
+        AgentArrays list;
+        agent_arrays(sh, kFeatFrontier, &list);
+        size_t bytes = 0;
+        const hipError_t e = alloc_parts(h, fresh.buf, list, 0, list.n, list.head, at, &bytes);
+        if (e != hipSuccess) return fail(hip_code(e), "frontier of %zu bytes: %s", bytes, hip_failure(e));
+        fresh.words = RcwFrontierWords{at[kSnapFrontierDistance].as<int32_t>(), at[kSnapFrontierTiles].as<int32_t>()};
+        fresh.advice = RcwGuideWords{at[kSnapFrontierAction].as<uint8_t>(), at[kSnapFrontierHeading].as<int32_t>()};
+        fresh.last_episode = at[kSnapFrontierLast].as<uint32_t>();
+        fresh.field = at[kSnapFrontierField].as<uint16_t>();
+    }
+    RCW_HIP(take_live(h, kFeatFrontier, at));
+    fr = std::move(fresh);
+    if (fr.on()) RCW_HIP(launch_frontier(h, nullptr, kStackRefill));
+    return RCW_OK;
+}
+
+int rcw_frontier_info(rcw_handle* h, int32_t* enabled)
+{
+    if (!h || !enabled) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    *enabled = h->frontier.on() ? 1 : 0;
+    return RCW_OK;
+}
+
+int rcw_frontier(rcw_handle* h, int32_t* distance, int32_t* tiles, uint8_t* action, int32_t* heading)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return copy_arrays(h, kNoFrontier, {{distance, kSnapFrontierDistance}, {tiles, kSnapFrontierTiles}, {action, kSnapFrontierAction}, {heading, kSnapFrontierHeading}});
+}
+
+int rcw_frontier_device_ptr(rcw_handle* h, void** distance, void** tiles, void** action, void** heading)
+{
+    return hand_out(h, kNoFrontier, {{distance, kSnapFrontierDistance}, {tiles, kSnapFrontierTiles}, {action, kSnapFrontierAction}, {heading, kSnapFrontierHeading}});
+}
+
+int rcw_frontier_field(rcw_handle* h, int32_t first, int32_t count, void* out_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return copy_arrays(h, kNoFrontier, {{out_host, kSnapFrontierField}}, true, first, count);
+}
+
+int rcw_frontier_field_device_ptr(rcw_handle* h, void** ptr) { return hand_out(h, kNoFrontier, {{ptr, kSnapFrontierField}}); }
 
 // The local map (include/rcw.h).  Enabling allocates and computes every agent's image at once, stream-ordered behind what is queued; new
 // parameters replace the old; an allocation failure leaves what was there.

@@ -121,19 +121,21 @@ struct SnapshotShape {
     int32_t source_kind = 0;                                     // RcwLayoutKind; 0: no layout source
     int32_t layouts = 0, levels = 0, first_level = 0;            // the source's range (validate_snapshot_row, the statistics' rows; not part of the record)
     int32_t guide = 0;                                           // the guide: on (its words are never archived: not part of the record)
+    int32_t frontier = 0;                                        // the frontier: on (computed from the seen map, never archived: not part of the record)
 };
-constexpr int kSnapshotShapeWords = 23;                          // what travels through the development exports: everything but `guide`
+constexpr int kSnapshotShapeWords = 23;                          // what travels through the development exports: everything but `guide` and `frontier`
 // (a part's id, in the order of the features and, within one, of its list; kSnapViewStaging — the view kernels' frame under a k-frame stack —,
-// kSnapSourceStatus, kSnapSourceMask and the guide's two words are never archived)
+// kSnapSourceStatus, kSnapSourceMask, the guide's two words and everything of the frontier are never archived)
 enum SnapshotField { kSnapPos, kSnapDir, kSnapGoal, kSnapReward, kSnapDone, kSnapEpisode, kSnapTileMap, kSnapEpisodeSteps, kSnapTruncated,
                      kSnapGoalField, kSnapGoalDistance, kSnapGoalStart, kSnapGoalProgress, kSnapGoalLast,
                      kSnapSeenCount, kSnapSeenNew, kSnapSeenGoal, kSnapSeenLast, kSnapSeenBits, kSnapSeenMap,
                      kSnapViewFrame, kSnapViewStack, kSnapViewLast, kSnapViewStaging, kSnapLocalImage,
                      kSnapSourceLast, kSnapSourceStatus, kSnapSourceLayout, kSnapSourceMask,
                      kSnapStatsFinished, kSnapStatsOutcome, kSnapStatsLength, kSnapStatsMoves, kSnapStatsLevel, kSnapStatsSpl, kSnapStatsEpisodes,
-                     kSnapStatsPrevX, kSnapStatsPrevY, kSnapStatsLast, kSnapGuideAction, kSnapGuideHeading, kSnapFieldCount };
-enum AgentFeature { kFeatCore, kFeatGoal, kFeatSeen, kFeatView, kFeatLocal, kFeatSource, kFeatStats, kFeatGuide, kFeatCount };
-constexpr SnapshotField kFeatureFirstId[kFeatCount + 1] = {kSnapPos, kSnapGoalField, kSnapSeenCount, kSnapViewFrame, kSnapLocalImage, kSnapSourceLast, kSnapStatsFinished, kSnapGuideAction, kSnapFieldCount};
+                     kSnapStatsPrevX, kSnapStatsPrevY, kSnapStatsLast, kSnapGuideAction, kSnapGuideHeading,
+                     kSnapFrontierDistance, kSnapFrontierTiles, kSnapFrontierAction, kSnapFrontierHeading, kSnapFrontierLast, kSnapFrontierField, kSnapFieldCount };
+enum AgentFeature { kFeatCore, kFeatGoal, kFeatSeen, kFeatView, kFeatLocal, kFeatSource, kFeatStats, kFeatGuide, kFeatFrontier, kFeatCount };
+constexpr SnapshotField kFeatureFirstId[kFeatCount + 1] = {kSnapPos, kSnapGoalField, kSnapSeenCount, kSnapViewFrame, kSnapLocalImage, kSnapSourceLast, kSnapStatsFinished, kSnapGuideAction, kSnapFrontierDistance, kSnapFieldCount};
 constexpr int kAgentMaxParts = 10;
 struct AgentPart { SnapshotField id; const char* name; uint32_t bytes; uint64_t tag; bool archived; };
 struct AgentArrays { int32_t n = 0; AgentPart part[kAgentMaxParts] = {}; uint64_t head = 0; };   // (n = 0: the feature is off)
@@ -273,6 +275,18 @@ struct rcw_handle {
         RcwGuideWords words{};
         bool on() const { return buf.get() != nullptr; }
     } guide;
+    // The frontier (rcw_set_frontier): ONE buffer, the carve of its list — the Int32 (B) distance and tiles, the UInt8 (B) action and Int32
+    // (B) heading the guide's kernel writes from this field, each agent's episode counter as of its last flood, the UInt16 (H*W, B) field; the
+    // pointers point into it.  It holds no pointer into the seen map: the launch reads seen.map and seen.words as they are THEN
+    // (rcw_set_seen_map may have replaced them).  Empty while the feature is off — and never on while the seen map is off.
+    struct Frontier {
+        RcwBuf buf;
+        RcwFrontierWords words{};
+        RcwGuideWords advice{};
+        uint32_t* last_episode = nullptr;
+        uint16_t* field = nullptr;
+        bool on() const { return buf.get() != nullptr; }
+    } frontier;
     // The state archive (rcw_set_snapshots): ONE allocation — every segment's rows ([rows][bytes], each part on a multiple of 16 bytes), then
     // the Int32 scratch (owner [rows], the row each agent takes [B], the host variants' staged indices [B]), then the filled flags (UInt8
     // [rows]).  plan: the record's layout as of the binding (plan_snapshot); arc[k]: segment k's rows.  Empty while the archive is off.
@@ -346,6 +360,7 @@ hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_local_map(rcw_handle* h, StackOp op);
 hipError_t launch_episode_stats(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_guide(rcw_handle* h, StackOp op);
+hipError_t launch_frontier(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_layout_source(rcw_handle* h, bool force);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t* mask_dev, bool restore);

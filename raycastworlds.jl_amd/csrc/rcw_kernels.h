@@ -245,6 +245,20 @@ struct RcwGuideWords {
 // direction table as they are when it runs.  An argument block of its OWN (the comment on RcwLimit).  Reads only; writes only the two words.
 hipError_t rcw_launch_guide(const RcwDev& p, int32_t B, const uint16_t* field, const RcwGuideWords& words, hipStream_t s);
 
+// The frontier (rcw_set_frontier, rcw_frontier.hip): the two Int32 (B) words beside the UInt16 (H*W, B) field.
+struct RcwFrontierWords {
+    int32_t* distance;       // field[player's tile], -1: nothing left to explore from there, or off the map
+    int32_t* tiles;          // the sources of the agent's last flood
+};
+// One launch directly behind the seen map's.  Behind a step (refill = false): an agent whose episode counter differs from last_episode, or
+// whose newly_seen word is not 0, floods — the sources are the unseen tiles of `seen_map` next to a seen passable one —; every other one
+// looks its tile up.  Behind reset / set_state / set_walls / a restore / enabling (refill = true): the agents of the mask — NULL: all —
+// flood, the others are left alone.  An argument block of its OWN (the comment on RcwLimit).  Reads p's positions and counters, the seen
+// map and its word; writes only field, words and last_episode.
+size_t rcw_frontier_lds_bytes(const RcwDev& p);
+hipError_t rcw_launch_frontier(const RcwDev& p, int32_t B, const uint8_t* mask_dev, bool refill, const uint8_t* seen_map, const int32_t* newly_seen,
+                               uint16_t* field, const RcwFrontierWords& words, uint32_t* last_episode, hipStream_t s);
+
 // THE LAYOUT SOURCES (rcw_wall_bank.hip): what gives an agent its walls at every start of an episode.  A handle has at most one — the wall
 // bank (rcw_set_wall_bank) or one family of the wall generator: mazes (rcw_set_wall_generator), caves (rcw_set_wall_caves), rooms
 // (rcw_set_wall_rooms) — behind ONE launch point, rcw_launch_layout_source.

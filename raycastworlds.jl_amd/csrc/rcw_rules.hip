@@ -721,6 +721,51 @@ extern "C" int rcw_guide_rule(int32_t H, int32_t W, const void* field, double x,
     return RCW_OK;
 }
 
+// ---- the frontier (include/rcw.h, "the frontier") ---------------------------------------------------------------------------------------
+// The handle-less export: the flood for ONE agent on the host, needs no device.  A queue of tile indices in the order reached
+// (rcw_frontier_kernel takes a level a pass of the wavefront; the values are the same: a breadth-first level is a set).  A neighbour is
+// looked at by (row, column), never by linear distance: tile (H-1, j) and tile (0, j+1) are no neighbours.
+extern "C" int rcw_frontier_rule(int32_t H, int32_t W, const uint8_t* seen_map, void* field_out, int32_t* tiles_out)
+{
+    if (!seen_map || !field_out || !tiles_out) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (H < 1 || W < 1 || (int64_t)H * W > 65535) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_frontier_rule: a map of %d x %d", H, W);
+    const int32_t HW = H * W;
+    uint16_t* const F = static_cast<uint16_t*>(field_out);
+    std::vector<int32_t> queue;
+    try {
+        queue.reserve((size_t)HW);
+    } catch (const std::bad_alloc&) {
+        return fail(RCW_ERR_OUT_OF_MEMORY, "rcw_frontier_rule: host allocation failed");
+    }
+    const auto passable = [&](int32_t t) { return seen_map[t] == 1 || seen_map[t] == 3; };   // (a byte above 4 is a wall)
+    // the edge neighbours of t = i + H j that lie on the map
+    const auto neighbours = [&](int32_t t, int32_t* out) {
+        const int32_t i = t % H, j = t / H;
+        int n = 0;
+        if (i > 0) out[n++] = t - 1;
+        if (i < H - 1) out[n++] = t + 1;
+        if (j > 0) out[n++] = t - H;
+        if (j < W - 1) out[n++] = t + H;
+        return n;
+    };
+    int32_t nb[4];
+    for (int32_t t = 0; t < HW; ++t) {
+        F[t] = 0xFFFFu;
+        if (seen_map[t] != 0) continue;
+        const int n = neighbours(t, nb);
+        for (int k = 0; k < n; ++k)
+            if (passable(nb[k])) { F[t] = 0; queue.push_back(t); break; }
+    }
+    *tiles_out = (int32_t)queue.size();
+    for (size_t head = 0; head < queue.size(); ++head) {                   // (every tile enters at most once: at most HW entries)
+        const int32_t t = queue[head];
+        const int n = neighbours(t, nb);
+        for (int k = 0; k < n; ++k)
+            if (passable(nb[k]) && F[nb[k]] == 0xFFFFu) { F[nb[k]] = (uint16_t)(F[t] + 1u); queue.push_back(nb[k]); }
+    }
+    return RCW_OK;
+}
+
 // THE PER-AGENT ARRAYS (rcw_handle.h): the parts of `feature` (AgentFeature) of a handle of this shape, in the order an exported row of the
 // state archive holds them, and the bytes of the feature's head.  What is off has no parts and no head.  This is the ONE place that knows
 // an array's bytes per agent: the setters carve it, the archive records it, the readouts copy it.  `kept` = false: a part the archive
@@ -800,6 +845,14 @@ void agent_arrays(const SnapshotShape& sh, int feature, AgentArrays* out)
     if (feature == kFeatGuide && sh.guide) {                               // computed from the state, never recorded: a row fits a handle with or without it
         add(kSnapGuideAction, "guide.action", 1, 0, false);
         add(kSnapGuideHeading, "guide.heading", 4, 0, false);
+    }
+    if (feature == kFeatFrontier && sh.frontier) {                         // computed from the seen map, never recorded: a restore floods the restored agents again
+        add(kSnapFrontierDistance, "frontier.distance", 4, 0, false);
+        add(kSnapFrontierTiles, "frontier.tiles", 4, 0, false);
+        add(kSnapFrontierAction, "frontier.action", 1, 0, false);
+        add(kSnapFrontierHeading, "frontier.heading", 4, 0, false);
+        add(kSnapFrontierLast, "frontier.last_episode", 4, 0, false);
+        add(kSnapFrontierField, "frontier.field", 2u * HW, 0, false);
     }
 }
 

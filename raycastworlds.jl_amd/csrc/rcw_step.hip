@@ -232,6 +232,23 @@ hipError_t launch_seen_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
     return rcw_launch_seen_map(h->dev, h->B, mask_dev, op == kStackRefill, h->seen.map, h->seen.bits, h->seen.words, h->seen.last_episode, h->stream);
 }
 
+// ... and directly behind the seen map, the frontier, which floods over it.  Behind a step the agents whose map changed or whose episode began
+// flood (the kernel reads the seen map's newly_seen word and its own recorded counter), behind a refill those of the mask; the action words
+// are a pure function of (field, position, heading, direction table) and follow for every agent, through the guide's kernel on THIS field —
+// also behind a new direction table (kStackRefillSameWorld), where nothing floods.  launch_snapshot asks for the masked refill behind a
+// restore's render.  A re-render of the very same frames (kStackKeep) launches nothing.
+hipError_t launch_frontier(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
+{
+    const rcw_handle::Frontier& fr = h->frontier;
+    if (!fr.on() || !h->seen.on() || op == kStackKeep) return hipSuccess;
+    if (op != kStackRefillSameWorld) {
+        const hipError_t e = rcw_launch_frontier(h->dev, h->B, mask_dev, op == kStackRefill, h->seen.map, h->seen.words.newly_seen, fr.field, fr.words,
+                                                 fr.last_episode, h->stream);
+        if (e != hipSuccess) return e;
+    }
+    return rcw_launch_guide(h->dev, h->B, fr.field, fr.advice, h->stream);
+}
+
 // ... and last, behind the seen map it may read, the local map: a pure function of the state, so every agent's image at every render but
 // the one that re-renders the very same frames
 hipError_t launch_local_map(rcw_handle* h, StackOp op)
@@ -285,6 +302,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
         if (e == hipSuccess) e = launch_goal_distance(h, mask_dev, op);
         if (e == hipSuccess) e = launch_guide(h, op);
         if (e == hipSuccess) e = launch_seen_map(h, mask_dev, op);
+        if (e == hipSuccess) e = launch_frontier(h, mask_dev, op);
         if (e == hipSuccess) e = launch_local_map(h, op);
         return e == hipSuccess ? launch_episode_stats(h, mask_dev, op) : e;
     }
@@ -305,6 +323,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if ((e = launch_goal_distance(h, mask_dev, op)) != hipSuccess) return e;
     if ((e = launch_guide(h, op)) != hipSuccess) return e;
     if ((e = launch_seen_map(h, mask_dev, op)) != hipSuccess) return e;
+    if ((e = launch_frontier(h, mask_dev, op)) != hipSuccess) return e;
     if ((e = launch_local_map(h, op)) != hipSuccess) return e;
     return launch_episode_stats(h, mask_dev, op);
 }
@@ -314,7 +333,8 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
 // kSnapshotKernelSegments at a time.  A save is done there.  A restore goes on: the step's facts forget the slots (StepFacts::restored), and
 // the agents of the mask are cast and painted from the state they now hold, as a re-render of the same frames is (kStackKeep): the flood, the
 // seen map, the stack, the local map and the statistics are the record's and stay as the gather left them.  The guide's words are no part
-// of the record: its kernel follows, on the restored state.
+// of the record: its kernel follows, on the restored state.  Nor is anything of the frontier: the agents of the mask are flooded again
+// from the seen map the gather restored, and the action words of every agent follow.
 hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t* mask_dev, bool restore)
 {
     rcw_handle::Snapshots& sn = h->snaps;
@@ -334,7 +354,8 @@ hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t
     if (!restore) return hipSuccess;
     h->step.restored();
     if ((e = launch_step(h, nullptr, mask_dev, kStackKeep)) != hipSuccess) return e;
-    return launch_guide(h, kStackRefill);                        // (no part of the record: computed from the restored field, pose and the table as it is now)
+    if ((e = launch_guide(h, kStackRefill)) != hipSuccess) return e;   // (no part of the record: computed from the restored field, pose and the table as it is now)
+    return launch_frontier(h, mask_dev, kStackRefill);
 }
 
 // THE way a buffer of a live handle is given up: wait_all_streams (queued work may still use the old ones), then each of `old` takes

@@ -1,5 +1,5 @@
 """Wall layouts for `SingleRoom.set_walls`: host-side numpy, nothing here touches the device (`generated_maze` and
-`generated_maze_key`, `generated_cave`, `generated_rooms` and `guide_rule` call the library's handle-less host functions: no device either).
+`generated_maze_key`, `generated_cave`, `generated_rooms`, `guide_rule` and `frontier_rule` call the library's handle-less host functions: no device either).
 
 A layout is bool (H, W) with `walls[i-1, j-1]` = tile (i, j) is a WALL — the index order of `env.world.tile_map[b, 0]`.
 Every generator returns the wall ring (SR:57-60) closed, as `rcw_set_walls` requires, and at least two free interior
@@ -177,6 +177,29 @@ def guide_rule(field, position, direction: int, directions_wu, position_incremen
     if rc != _capi.RCW_OK:
         raise ValueError(_capi.last_error(lib))
     return int(action.value), int(heading.value)
+
+
+def frontier_rule(seen_map):
+    """The frontier's flood (include/rcw.h, "the frontier") for ONE agent on the host: (field, tiles) — `field` uint16 (H, W), 0 on the
+    unseen tiles next to a seen free one, on a seen free tile the moves to the nearest of them, 0xFFFF elsewhere; `tiles` how many hold 0.
+    `seen_map`: uint8 (H, W), one agent's `env.seen_map[b]` (0 unseen, 1 free, 2 wall, 3 goal, 4 and above wall).  rcw_frontier_rule:
+    host arithmetic, no device."""
+    import ctypes as C
+
+    from . import _capi
+
+    lib = _capi.load()
+    m = np.asarray(seen_map, dtype=np.uint8)
+    if m.ndim != 2:
+        raise ValueError(f"one seen map (H, W) at a time, got {m.shape}")
+    H, W = m.shape
+    lin = np.ascontiguousarray(m.T)                                        # tile (i, j), 0-based, at i + H j
+    out = np.empty((W, H), dtype=np.uint16)
+    tiles = C.c_int32()
+    rc = lib.rcw_frontier_rule(H, W, lin.ctypes.data, out.ctypes.data, C.byref(tiles))
+    if rc != _capi.RCW_OK:
+        raise ValueError(_capi.last_error(lib))
+    return np.ascontiguousarray(out.T), int(tiles.value)
 
 
 def is_connected(walls) -> bool:

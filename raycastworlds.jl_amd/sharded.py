@@ -226,6 +226,31 @@ class ShardedSingleRoom:
     def guide_heading(self):
         return self.env.guide_heading
 
+    # ---- the frontier: a function of each agent's own seen map and pose, so a shard's words are its slice of the batch's ----
+    def set_frontier(self, on: bool = True) -> None:
+        """`SingleRoom.set_frontier` of this rank's engine (also the `frontier=True` keyword); the arrays below are LOCAL."""
+        self.env.set_frontier(on)
+
+    @property
+    def frontier_distance(self):
+        return self.env.frontier_distance
+
+    @property
+    def frontier_tiles(self):
+        return self.env.frontier_tiles
+
+    @property
+    def explore_action(self):
+        return self.env.explore_action
+
+    @property
+    def explore_heading(self):
+        return self.env.explore_heading
+
+    @property
+    def frontier_field(self):
+        return self.env.frontier_field
+
     # ---- the state archive: every shard has its own, rows are LOCAL ---------------------------
     def set_snapshots(self, rows: int) -> None:
         """`SingleRoom.set_snapshots` of this rank's engine: `rows` records a SHARD.  Rows do not cross shards."""

@@ -347,7 +347,8 @@ class SingleRoom:
     `set_time_limit`.  `walls` / `wall_index` (this build's addition; None = the reference's empty room) are `set_walls`'
     arguments, applied right after construction.  `goal_distance` (this build's addition) is `set_goal_distance(True)` after them,
     `guide` (this build's addition) `set_guide(True)` right behind it (it enables the goal distance where that is off),
-    `seen_map` (this build's addition) `set_seen_map(True)` after that, `local_map` (this build's addition; an int — the size — or a dict
+    `seen_map` (this build's addition) `set_seen_map(True)` after that, `frontier` (this build's addition) `set_frontier(True)` right
+    behind it (it enables the seen map where that is off), `local_map` (this build's addition; an int — the size — or a dict
     of `set_local_map`'s keywords) `set_local_map` after that, `episode_stats` (this build's addition) `set_episode_stats(True)` last of
     all — behind the layout sources below, whose levels count its table's rows.  `wall_bank` / `wall_bank_weights` (this build's addition) are `set_wall_bank`'s
     arguments, applied after `walls` and the time limit and before the features: a layout drawn on the device at every episode start.
@@ -394,6 +395,7 @@ class SingleRoom:
         goal_distance: bool = False,
         guide: bool = False,
         seen_map: bool = False,
+        frontier: bool = False,
         local_map=None,
         wall_bank=None,
         wall_bank_weights=None,
@@ -527,6 +529,12 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        if frontier:
+            try:
+                self.set_frontier(True)
+            except BaseException:
+                self._handle.close()
+                raise
         if local_map is not None:
             try:
                 self.set_local_map(**local_map) if isinstance(local_map, dict) else self.set_local_map(local_map)
@@ -571,7 +579,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_guide_dev", "_seen_map_dev", "_local_map_dev", "_episode_stats_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_guide_dev", "_seen_map_dev", "_frontier_dev", "_local_map_dev", "_episode_stats_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -1245,6 +1253,91 @@ class SingleRoom:
         H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
         return DeviceArray(p.value, (self.batch, W, H), np.uint8, self, self._sync,
                            host_getter=lambda: np.ascontiguousarray(self.seen_map.transpose(0, 2, 1)))
+
+    # ---- the frontier (include/rcw.h, rcw_set_frontier) ----------------------------------
+    def set_frontier(self, on: bool = True) -> None:
+        """Keep, on the device, each agent's way to the nearest unseen tile: `frontier_field` (uint16: 0 on the unseen tiles next to a seen
+        free one, on a seen free tile the moves to the nearest of them, 0xFFFF elsewhere), `frontier_distance` (the field at the agent's
+        tile, -1: nothing left to explore from here), `frontier_tiles` (how many frontier tiles the agent's last flood found),
+        `explore_action` (uint8 in 1..4, the guide's rule on this field: what `act_` takes as it stands) and `explore_heading` (-1: no
+        advice).  An agent is flooded again only where its seen map changed or its episode began; with no host in the loop.  Explore, then
+        go: `torch.where(env.goal_seen.torch(sync=False) > 0, env.guide_action.torch(sync=False), env.explore_action.torch(sync=False))`.
+        Switching it on enables the seen map first where that is off; `set_seen_map(False)` is refused while it is on.  The device arrays
+        handed out before are invalid after every call."""
+        self.__dict__.pop("_frontier_dev", None)
+        if on and not self.seen_map_enabled:
+            self.set_seen_map(True)
+        self._check(self._lib.rcw_set_frontier(self._h, 1 if on else 0))
+
+    @property
+    def frontier_info(self) -> dict:
+        """`enabled` (rcw_frontier_info)."""
+        v = C.c_int32()
+        self._check(self._lib.rcw_frontier_info(self._h, C.byref(v)))
+        return {"enabled": bool(v.value)}
+
+    @property
+    def frontier_enabled(self) -> bool:
+        return self.frontier_info["enabled"]
+
+    _FRONTIER_WORDS = (np.int32, np.int32, np.uint8, np.int32)            # distance, tiles, action, heading
+
+    def _frontier_host(self, which: int) -> np.ndarray:
+        out = np.empty(self.batch, dtype=self._FRONTIER_WORDS[which])
+        args = [None, None, None, None]
+        args[which] = _as_ptr(out)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_frontier(self._h, *args))
+        return out
+
+    def _frontier_arrays(self):
+        if getattr(self, "_frontier_dev", None) is None:
+            p = [C.c_void_p() for _ in range(4)]
+            self._check(self._lib.rcw_frontier_device_ptr(self._h, *[C.byref(q) for q in p]))
+            self._frontier_dev = tuple(
+                DeviceArray(p[k].value, (self.batch,), dtype, self, self._sync, host_getter=lambda k=k: self._frontier_host(k))
+                for k, dtype in enumerate(self._FRONTIER_WORDS))
+        return self._frontier_dev
+
+    @property
+    def frontier_distance(self) -> DeviceArray:
+        """int32 (B,) in device memory: the moves from each agent's tile to the nearest frontier tile through seen free tiles; -1 where
+        there is none — everything the agent can reach has been seen — or the agent is off the map."""
+        return self._frontier_arrays()[0]
+
+    @property
+    def frontier_tiles(self) -> DeviceArray:
+        """int32 (B,): the number of frontier tiles as of each agent's last flood."""
+        return self._frontier_arrays()[1]
+
+    @property
+    def explore_action(self) -> DeviceArray:
+        """uint8 (B,): the action that leads each agent to its nearest frontier tile, always in 1..4.  `.torch(sync=False)` on the GPU —
+        `act_` takes it as it is —, `np.asarray(...)` for a host copy."""
+        return self._frontier_arrays()[2]
+
+    @property
+    def explore_heading(self) -> DeviceArray:
+        """int32 (B,): the 0-based direction index the frontier's rule wants each agent to face, -1 where it has no advice."""
+        return self._frontier_arrays()[3]
+
+    @property
+    def frontier_field(self) -> np.ndarray:
+        """uint16 (B, H, W), a host copy: `field[b, i-1, j-1]` of tile (i, j) — indexed like `env.seen_map`."""
+        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
+        out = np.empty((self.batch, W, H), dtype=np.uint16)                # tile (i, j) at (i - 1) + H (j - 1)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_frontier_field(self._h, 0, self.batch, _as_ptr(out)))
+        return np.ascontiguousarray(out.transpose(0, 2, 1))
+
+    @property
+    def frontier_field_device(self) -> DeviceArray:
+        """The field where it lives: uint16 (B, W, H) in device memory — the tile map's own order, `[b, j-1, i-1]`."""
+        p = C.c_void_p()
+        self._check(self._lib.rcw_frontier_field_device_ptr(self._h, C.byref(p)))
+        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
+        return DeviceArray(p.value, (self.batch, W, H), np.uint16, self, self._sync,
+                           host_getter=lambda: np.ascontiguousarray(self.frontier_field.transpose(0, 2, 1)))
 
     # ---- the local map (include/rcw.h, rcw_set_local_map) -------------------------------
     _LOCAL_SOURCES = {"world": _capi.RCW_LOCAL_WORLD, "seen": _capi.RCW_LOCAL_SEEN}
