@@ -882,6 +882,89 @@ RCW_API int rcw_frontier_device_ptr(rcw_handle* h, void** distance, void** tiles
 RCW_API int rcw_frontier_field(rcw_handle* h, int32_t first, int32_t count, void* out_host /* UInt16 (H*W, count) */);
 RCW_API int rcw_frontier_field_device_ptr(rcw_handle* h, void** ptr);
 RCW_API int rcw_frontier_rule(int32_t H, int32_t W, const uint8_t* seen_map /* (H*W) */, void* field_out /* UInt16 (H*W) */, int32_t* tiles_out);
+/* ---- the visit map (this build's addition: how often each agent has stood where it stands, kept on the device) ------------------------
+ * Opt-in per handle: the visit count of count-based exploration — the episodic count N_ep(s) that RIDE and AGAC scale their bonus by
+ * (1 / sqrt N_ep), that BeBold / NovelD gate theirs by (N_ep == 1), the plain beta / sqrt N bonus — and, optionally, the cumulative count
+ * per level shared by every agent that plays it, at no host synchronisation.  The seen map is no visit count: it records what the rays
+ * crossed, not where the agent was, and holds a flag.  A handle that never enables it runs exactly the kernels it ran before.  The ABI is
+ * additive: RCW_ABI_VERSION and rcw_config are what they were.
+ * PARAMETERS, fixed when the feature is enabled: sectors, 1 <= sectors <= RCW_VISIT_MAX_SECTORS and sectors <= num_directions; flags, whose
+ * only bit is RCW_VISIT_TABLE; cells = sectors * H * W.
+ * THE CELL of agent a: its tile t = i + H*j with (i, j) = (floor x, floor y), the floor taken in the world-unit type (wu_to_tu minus
+ * one); its sector s = (d * sectors) / nd by integer division, d its 0-based direction index — the index, not the table's vectors: a new
+ * direction table changes nothing —; its cell c = s*H*W + t.  An agent has NO CELL where x or y is not finite or the tile is off the map
+ * (the kernel checks and never indexes outside the map).
+ * Per-agent state, device arrays:
+ *   map         UInt16 (cells, B), agent a's at a*cells; within a sector the tile map's own linear order (the seen map's)
+ *   here        Int32 (B)    the entry of the agent's cell after the call; 0 where it has no cell
+ *   visited     Int32 (B)    the number of non-zero entries of the agent's map
+ *   first       Int32 (B)    1 iff the call counted a cell whose entry was 0; 0 otherwise, and 0 behind a BEGIN
+ *   level_here  UInt32 (B)   with the table: below; 0 on a handle without it
+ *   (private)   the agent's episode counter as of its last BEGIN
+ * COUNT(a), for an agent with a cell:   v = map[c]; first = (v == 0); map[c] = min(v + 1, 65535); visited += first; here = map[c].
+ *           Without a cell: here = first = 0, and nothing else happens.
+ * BEGIN(a): every entry of the agent's map becomes 0, visited becomes 0; COUNT at the current pose; then first = 0 and the counter is
+ *           recorded.
+ * THE TABLE (with RCW_VISIT_TABLE): UInt32 (cells, 1 + rows), row r at r*cells.  rows and first_level follow episode statistics' rule from
+ * the layout source that is live when the feature is enabled (rows = the bank's layouts, or a family's `levels` with first_level; 0
+ * without a source, with levels == 0 or above RCW_EPISODE_STATS_MAX_ROWS); where cells * (1 + rows) * 4 would pass
+ * RCW_VISIT_TABLE_MAX_BYTES, rows = 0 — no error: row 0 always works.  Every COUNT of an agent with a cell — the one inside a BEGIN
+ * too, and whether or not the map entry saturated — adds 1 to table[0][c] and to table[1 + k][c], k = layout - first_level, where
+ * 0 <= k < rows; layout is rcw_wall_layout's word of the agent as it is behind the call.  Entries wrap modulo 2^32.  All adds are integer
+ * adds: the table does not depend on the order in which agents are processed.
+ *   level_here[a] = table[r][c] AS OF THE END OF THE CALL, after every agent's adds, r = 1 + k where k is in range, else 0 — so it does
+ *           not depend on that order either, and two agents that share a row and a cell read the same value.  It is read again for EVERY
+ *           agent (0 for one without a cell) behind every step and every reset / set_state / set_walls, the agents outside such a call's
+ *           mask included: their own entry may have grown.
+ * What each call does — stream-ordered on the handle's stream behind everything the call already queues, with no host wait:
+ *   rcw_set_visit_map(h, 1, sectors, flags)
+ *                                 allocates, zeroes the table, BEGIN for every agent.  On a handle that has it: the same again, with the
+ *                                 new parameters.  An allocation failure leaves what was there.
+ *   rcw_set_visit_map(h, 0, ...)  frees it (RCW_OK also where there was none).
+ *   rcw_step, rcw_step_device     an agent whose episode counter differs from the recorded one — a done or truncated restart under
+ *                                 auto_reset, with or without a layout source — gets BEGIN; every other agent COUNT at its pose after the
+ *                                 step.  The action is not looked at: a blocked move, a turn, an invalid device action count the cell the
+ *                                 agent is on; a done agent without auto_reset is counted like any other.
+ *   rcw_reset, rcw_set_state, rcw_set_state64, rcw_set_walls
+ *                                 BEGIN for the agents of the call's mask; every other agent keeps every byte of its map and here, visited
+ *                                 and first.  The mask decides, not the counter.
+ *   rcw_set_wall_bank, rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms (install, replace or remove)
+ *                                 with RCW_VISIT_TABLE: RCW_ERR_UNSUPPORTED, and nothing changes (the level rows were counted from the
+ *                                 live source: the statistics' rule).  Without the table: an install restarts every agent, so BEGIN for
+ *                                 every agent; a removal does nothing (what the seen map does).
+ *   rcw_visit_table_clear         zeroes the table without waiting for the stream; no per-agent word is touched.
+ *   rcw_snapshot_restore*         map, the four words and the private counter are part of the record: the restored agents hold the
+ *                                 save's, and nothing is counted.  The table is no part of a record and is not rolled back.
+ *   rcw_set_direction_table*, rcw_set_step_form, rcw_set_time_limit, the renderers, every other feature's calls and every getter
+ *                                 nothing.
+ * A replayed HIP graph of a step counts like any step: the recorded counter lives on the device.  Capture again after enabling or
+ * disabling.  The launches (rcw_visit_map_kernel and, with the table, rcw_visit_table_read_kernel) run OUTSIDE rcw_profile's events.
+ *   rcw_visit_map_info            enabled, sectors, flags, rows, first_level (any pointer may be NULL); zeros while off.
+ *   rcw_visit_words               host copies of here, visited, first, level_here (any pointer may be NULL); waits for the stream as
+ *                                 rcw_done does.
+ *   rcw_visit_words_device_ptr    the four arrays where they live (any pointer may be NULL), stable until the next rcw_set_visit_map.
+ *   rcw_visit_map                 agents [first, first + count) of the map to the host; waits for the stream.
+ *   rcw_visit_map_device_ptr      the map where it lives.
+ *   rcw_visit_table               the table, UInt32 (cells, 1 + rows), to the host; waits for the stream.
+ *   rcw_visit_table_device_ptr    the table where it lives.
+ *   rcw_visit_cell                handle-less, needs no device: the cell rule for ONE agent on the host; *cell = -1: no cell.  H, W >= 1
+ *                                 with 8 H W < 2^31, nd >= 1, 0 <= direction < nd, 1 <= sectors <= min(RCW_VISIT_MAX_SECTORS, nd),
+ *                                 world_unit_bits 32 (x and y are rounded to Float32 first) or 64; anything else — a NULL pointer included —
+ *                                 is RCW_ERR_INVALID_ARGUMENT.
+ * The readouts return RCW_ERR_UNSUPPORTED on a handle that has not enabled it, the three table calls also on one without the table. */
+#define RCW_VISIT_MAX_SECTORS 8
+#define RCW_VISIT_TABLE 1
+#define RCW_VISIT_TABLE_MAX_BYTES (256u * 1024u * 1024u)
+RCW_API int rcw_set_visit_map(rcw_handle* h, int32_t enable, int32_t sectors, int32_t flags);
+RCW_API int rcw_visit_map_info(rcw_handle* h, int32_t* enabled, int32_t* sectors, int32_t* flags, int32_t* rows, int32_t* first_level);
+RCW_API int rcw_visit_words(rcw_handle* h, int32_t* here /* (B) */, int32_t* visited /* (B) */, int32_t* first /* (B) */, uint32_t* level_here /* (B) */);
+RCW_API int rcw_visit_words_device_ptr(rcw_handle* h, void** here, void** visited, void** first, void** level_here);
+RCW_API int rcw_visit_map(rcw_handle* h, int32_t first, int32_t count, void* out_host /* UInt16 (cells, count) */);
+RCW_API int rcw_visit_map_device_ptr(rcw_handle* h, void** ptr);
+RCW_API int rcw_visit_table(rcw_handle* h, uint32_t* out_host /* (cells, 1 + rows) */);
+RCW_API int rcw_visit_table_device_ptr(rcw_handle* h, void** ptr);
+RCW_API int rcw_visit_table_clear(rcw_handle* h);
+RCW_API int rcw_visit_cell(int32_t H, int32_t W, int32_t nd, int32_t sectors, double x, double y, int32_t world_unit_bits, int32_t direction, int32_t* cell);
 
 /* ---- The state archive (this build's addition: the reference has no checkpoint) -------------------------------------------------------
  * `rows` agent RECORDS kept on the device and owned by the handle: save scatters the records of the masked agents into rows, restore
@@ -898,6 +981,7 @@ RCW_API int rcw_frontier_rule(int32_t H, int32_t W, const uint8_t* seen_map /* (
  *   local map          the image (stored, not computed again: its bytes are what they were at the save)
  *   layout source      the source's private episode counter and the agents' layout index / level
  *   episode statistics the seven words, the previous position (x, y), the private episode counter
+ *   visit map          here, visited, first, level_here, the private episode counter, the map (its tag carries `sectors`); not the table
  * A record does NOT hold
  *   the camera view, the column descriptors, the one-launch step's slots, the top view        a restore renders them again;
  *   the agents' status words and the layout source's record of them                           the agent SLOT's error log, like the

@@ -637,6 +637,72 @@ function episode_stats_clear!(env::BatchedSingleRoom)
     return nothing
 end
 
+# ---- the visit map (this build's addition; include/rcw.h, rcw_set_visit_map) ------------------------------------------------------
+const VISIT_TABLE = Int32(1)
+"""
+    set_visit_map!(env, on = true; sectors = 1, table = false)
+
+Keep, on the device, how often each agent has stood in each cell — tile × heading sector — this episode: `visit_map(env)` is the `UInt16`
+map as `(H, W, sectors, batch)`; `visit_words(env)` returns `(here, visited, first, level_here)` — `here` the count of the cell the agent
+is on (the `N` of `beta / sqrt(N)`), `visited` the cells it has stood in, `first` 1 where the last call entered a cell for the first time
+this episode, `level_here` the table's count of the cell on the agent's level.  With `table = true` a `UInt32` table
+`(H, W, sectors, 1 + rows)` sums the counts over the batch (slice 1) and per level of the layout source that is live now;
+`visit_table_clear!(env)` zeroes it without waiting for the stream.  `visit_cell` is the cell rule for one agent on the host.
+"""
+function set_visit_map!(env::BatchedSingleRoom, on::Bool = true; sectors::Integer = 1, table::Bool = false)
+    check(ccall((:rcw_set_visit_map, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Int32), env.handle, on ? 1 : 0, sectors, table ? VISIT_TABLE : Int32(0)))
+    return nothing
+end
+function visit_map_info(env::BatchedSingleRoom)
+    e, s, f, r, l = (Ref{Int32}(0) for _ in 1:5)
+    check(ccall((:rcw_visit_map_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}), env.handle, e, s, f, r, l))
+    return (enabled = e[] != 0, sectors = s[], table = (f[] & VISIT_TABLE) != 0, rows = r[], first_level = l[])
+end
+function visit_words(env::BatchedSingleRoom)
+    h = Vector{Int32}(undef, env.batch); v = Vector{Int32}(undef, env.batch)
+    f = Vector{Int32}(undef, env.batch); l = Vector{UInt32}(undef, env.batch)
+    check(ccall((:rcw_visit_words, librcw), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt32}), env.handle, h, v, f, l))
+    return (here = h, visited = v, first = f, level_here = l)
+end
+function visit_words_device_ptr(env::BatchedSingleRoom)
+    h, v, f, l = (Ref{Ptr{Cvoid}}(C_NULL) for _ in 1:4)
+    check(ccall((:rcw_visit_words_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                env.handle, h, v, f, l))
+    return (here = h[], visited = v[], first = f[], level_here = l[])
+end
+function visit_map(env::BatchedSingleRoom, first::Integer = 0, count::Integer = env.batch - first)
+    out = Array{UInt16, 4}(undef, env.config.height_tile_map_tu, env.config.width_tile_map_tu, Int(visit_map_info(env).sectors), count)
+    check(ccall((:rcw_visit_map, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}), env.handle, first, count, out)); out
+end
+function visit_map_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_visit_map_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
+function visit_table(env::BatchedSingleRoom)
+    info = visit_map_info(env)
+    out = Array{UInt32, 4}(undef, env.config.height_tile_map_tu, env.config.width_tile_map_tu, Int(info.sectors), 1 + Int(info.rows))
+    check(ccall((:rcw_visit_table, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt32}), env.handle, out)); out
+end
+function visit_table_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_visit_table_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
+end
+function visit_table_clear!(env::BatchedSingleRoom)
+    check(ccall((:rcw_visit_table_clear, librcw), Cint, (Ptr{Cvoid},), env.handle))
+    return nothing
+end
+"""
+    visit_cell(H, W, nd, sectors, x, y, direction; bits = 32) -> cell
+
+The 0-based cell of an agent at `(x, y)` with the 0-based direction index `direction`: `s*H*W + i + H*j`; `-1`: no cell.
+"""
+function visit_cell(H::Integer, W::Integer, nd::Integer, sectors::Integer, x::Real, y::Real, direction::Integer; bits::Integer = 32)
+    c = Ref{Int32}(0)
+    check(ccall((:rcw_visit_cell, librcw), Cint, (Int32, Int32, Int32, Int32, Float64, Float64, Int32, Int32, Ref{Int32}),
+                H, W, nd, sectors, x, y, bits, direction, c))
+    return c[]
+end
+
 # ---- the state archive (this build's addition; include/rcw.h, rcw_set_snapshots) ------------------------------------------------
 """
     set_snapshots!(env, rows)

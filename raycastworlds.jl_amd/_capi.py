@@ -39,6 +39,7 @@ RCW_EPISODE_OPEN, RCW_EPISODE_SUCCESS, RCW_EPISODE_TRUNCATED = 0, 1, 2   # the e
 RCW_EPISODE_STATS_ROW_WORDS, RCW_EPISODE_STATS_MAX_ROWS = 8, 65536
 RCW_LOCAL_MAX_SIZE, RCW_LOCAL_MAX_CELLS_PER_TILE = 128, 16
 RCW_SNAPSHOT_MAX_ROWS = 1 << 20                         # rcw_set_snapshots: rows
+RCW_VISIT_MAX_SECTORS, RCW_VISIT_TABLE, RCW_VISIT_TABLE_MAX_BYTES = 8, 1, 256 << 20   # rcw_set_visit_map: sectors, flags; the table's cap
 
 
 class RcwConfig(C.Structure):
@@ -187,6 +188,16 @@ SIGNATURES = {
     "rcw_frontier_field": [_vp, _i32, _i32, _vp],
     "rcw_frontier_field_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_frontier_rule": [_i32, _i32, _vp, _vp, C.POINTER(_i32)],
+    "rcw_set_visit_map": [_vp, _i32, _i32, _i32],
+    "rcw_visit_map_info": [_vp] + [C.POINTER(_i32)] * 5,
+    "rcw_visit_words": [_vp, _vp, _vp, _vp, _vp],
+    "rcw_visit_words_device_ptr": [_vp] + [C.POINTER(_vp)] * 4,
+    "rcw_visit_map": [_vp, _i32, _i32, _vp],
+    "rcw_visit_map_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_visit_table": [_vp, _vp],
+    "rcw_visit_table_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_visit_table_clear": [_vp],
+    "rcw_visit_cell": [_i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, C.POINTER(_i32)],
     "rcw_set_snapshots": [_vp, _i32],
     "rcw_snapshot_info": [_vp, C.POINTER(_i32), C.POINTER(_u64), C.POINTER(_u64)],
     "rcw_snapshot_save": [_vp, _vp, _vp],

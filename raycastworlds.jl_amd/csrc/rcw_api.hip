@@ -156,6 +156,7 @@ SnapshotShape snapshot_shape(const rcw_handle* h)
     s.layouts = h->source.dev.agents.layouts; s.levels = h->source.dev.gen.levels; s.first_level = h->source.dev.gen.first_level;
     s.guide = h->guide.on();
     s.frontier = h->frontier.on();
+    if (h->visits.on()) { s.visit_sectors = h->visits.dev.sectors; s.visit_flags = h->visits.flags; }
     return s;
 }
 
@@ -189,6 +190,8 @@ const char* const kNoDrawnWalls = "the handle has neither a wall bank (rcw_set_w
 const char* const kNoEpisodeStats = "the handle keeps no episode statistics (rcw_set_episode_stats)";
 const char* const kNoGuide = "the handle has no guide (rcw_set_guide)";
 const char* const kNoFrontier = "the handle has no frontier (rcw_set_frontier)";
+const char* const kNoVisitMap = "the handle has no visit map (rcw_set_visit_map)";
+const char* const kNoVisitTable = "the handle's visit map has no table (rcw_set_visit_map with RCW_VISIT_TABLE)";
 int need(bool on, const char* why_off) { return on ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "%s", why_off); }
 
 // (the array of the learner view the caller sees: the k-frame stack, or the one frame)
@@ -1280,6 +1283,7 @@ namespace {
 // (the table's level rows were counted from the source that is live: it stays until the statistics are switched off)
 int refuse_under_episode_stats(rcw_handle* h, const char* caller)
 {
+    if (h->visits.table()) return fail(RCW_ERR_UNSUPPORTED, "%s: the handle keeps a visit table, whose level rows follow the layout source; switch the visit map off first (rcw_set_visit_map(h, 0, 0, 0))", caller);
     return h->stats.on() ? fail(RCW_ERR_UNSUPPORTED, "%s: the handle keeps episode statistics, whose level rows follow the layout source; switch them off first (rcw_set_episode_stats(h, 0))", caller) : RCW_OK;
 }
 }  // namespace
@@ -1522,6 +1526,108 @@ int rcw_episode_stats_clear(rcw_handle* h)
     int rc = check_handle(h); if (rc) return rc;
     rc = need(h->stats.on(), kNoEpisodeStats); if (rc) return rc;
     RCW_HIP(hipMemsetAsync(h->stats.dev.table, 0, h->stats.table_bytes(), h->stream));
+    return RCW_OK;
+}
+
+// The visit map (include/rcw.h).  Enabling allocates, zeroes the table and begins every agent at once (its map cleared, its cell counted),
+// stream-ordered behind what is queued; enabling again does the same again, with new parameters if they differ; an allocation failure
+// leaves what was there.
+int rcw_set_visit_map(rcw_handle* h, int32_t enable, int32_t sectors, int32_t flags)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::VisitMap& vm = h->visits;
+    if (!enable && !vm.on()) return RCW_OK;
+    rcw_handle::VisitMap fresh;
+    LiveArray at[kSnapFieldCount] = {};
+    if (enable) {
+        if (sectors < 1 || sectors > RCW_VISIT_MAX_SECTORS || sectors > h->dev.nd)
+            return fail(RCW_ERR_INVALID_ARGUMENT, "sectors must be in 1..min(%d, num_directions = %d) (got %d)", RCW_VISIT_MAX_SECTORS, h->dev.nd, sectors);
+        if (flags & ~RCW_VISIT_TABLE) return fail(RCW_ERR_INVALID_ARGUMENT, "flags: the only bit is RCW_VISIT_TABLE (got %d)", flags);
+        if ((int64_t)sectors * h->dev.H * h->dev.W > INT32_MAX / 2) return fail(RCW_ERR_UNSUPPORTED, "a visit map of %d sectors on a map of %d x %d is too large", sectors, h->dev.H, h->dev.W);
+        RcwVisitMap& d = fresh.dev;
+        SnapshotShape sh = snapshot_shape(h);
+        sh.visit_sectors = sectors; sh.visit_flags = flags;
+        if (flags & RCW_VISIT_TABLE) plan_visit_table_rows(sh, &d.rows, &d.first_level);
+        AgentArrays list;                                          // head: the table
+        agent_arrays(sh, kFeatVisits, &list);
+        size_t bytes = 0;
+        const hipError_t e = alloc_parts(h, fresh.buf, list, 0, list.n, list.head, at, &bytes);
+        if (e != hipSuccess) return fail(hip_code(e), "visit map of %zu bytes: %s", bytes, hip_failure(e));
+        d.sectors = sectors; d.cells = sectors * h->dev.H * h->dev.W;
+        d.table = (flags & RCW_VISIT_TABLE) ? fresh.buf.get<uint32_t>() : nullptr;
+        d.here = at[kSnapVisitHere].as<int32_t>(); d.visited = at[kSnapVisitVisited].as<int32_t>(); d.first = at[kSnapVisitFirst].as<int32_t>();
+        d.level_here = at[kSnapVisitLevelHere].as<uint32_t>(); d.last_episode = at[kSnapVisitLast].as<uint32_t>();
+        d.map = at[kSnapVisitMap].as<uint16_t>();
+        fresh.flags = flags;
+    }
+    RCW_HIP(take_live(h, kFeatVisits, at));
+    vm = std::move(fresh);
+    if (vm.on()) {
+        if (vm.table()) RCW_HIP(hipMemsetAsync(vm.dev.table, 0, vm.table_bytes(), h->stream));
+        RCW_HIP(hipMemsetAsync(vm.dev.level_here, 0, (size_t)h->B * sizeof(uint32_t), h->stream));   // (stays 0 on a handle without the table)
+        RCW_HIP(launch_visit_map(h, nullptr, kStackRefill));
+    }
+    return RCW_OK;
+}
+
+int rcw_visit_map_info(rcw_handle* h, int32_t* enabled, int32_t* sectors, int32_t* flags, int32_t* rows, int32_t* first_level)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    const rcw_handle::VisitMap& vm = h->visits;                        // (zeros while off)
+    if (enabled) *enabled = vm.on() ? 1 : 0;
+    if (sectors) *sectors = vm.dev.sectors;
+    if (flags) *flags = vm.flags;
+    if (rows) *rows = vm.dev.rows;
+    if (first_level) *first_level = vm.dev.first_level;
+    return RCW_OK;
+}
+
+int rcw_visit_words(rcw_handle* h, int32_t* here, int32_t* visited, int32_t* first, uint32_t* level_here)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return copy_arrays(h, kNoVisitMap, {{here, kSnapVisitHere}, {visited, kSnapVisitVisited}, {first, kSnapVisitFirst}, {level_here, kSnapVisitLevelHere}});
+}
+
+int rcw_visit_words_device_ptr(rcw_handle* h, void** here, void** visited, void** first, void** level_here)
+{
+    return hand_out(h, kNoVisitMap, {{here, kSnapVisitHere}, {visited, kSnapVisitVisited}, {first, kSnapVisitFirst}, {level_here, kSnapVisitLevelHere}});
+}
+
+int rcw_visit_map(rcw_handle* h, int32_t first, int32_t count, void* out_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return copy_arrays(h, kNoVisitMap, {{out_host, kSnapVisitMap}}, true, first, count);
+}
+
+int rcw_visit_map_device_ptr(rcw_handle* h, void** ptr) { return hand_out(h, kNoVisitMap, {{ptr, kSnapVisitMap}}); }
+
+int rcw_visit_table(rcw_handle* h, uint32_t* out_host)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need(h->visits.on(), kNoVisitMap); if (rc) return rc;
+    rc = need(h->visits.table(), kNoVisitTable); if (rc) return rc;
+    if (!out_host) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL output pointer");
+    rc = sync_and_check(h);
+    RCW_HIP(hipMemcpy(out_host, h->visits.dev.table, h->visits.table_bytes(), hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int rcw_visit_table_device_ptr(rcw_handle* h, void** ptr)
+{
+    if (!h || !ptr) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = need(h->visits.on(), kNoVisitMap); if (rc) return rc;
+    rc = need(h->visits.table(), kNoVisitTable); if (rc) return rc;
+    *ptr = h->visits.dev.table;
+    return RCW_OK;
+}
+
+// (stream-ordered and without waiting for the stream, as rcw_episode_stats_clear; no per-agent word is touched)
+int rcw_visit_table_clear(rcw_handle* h)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rc = need(h->visits.on(), kNoVisitMap); if (rc) return rc;
+    rc = need(h->visits.table(), kNoVisitTable); if (rc) return rc;
+    RCW_HIP(hipMemsetAsync(h->visits.dev.table, 0, h->visits.table_bytes(), h->stream));
     return RCW_OK;
 }
 

@@ -122,10 +122,12 @@ struct SnapshotShape {
     int32_t layouts = 0, levels = 0, first_level = 0;            // the source's range (validate_snapshot_row, the statistics' rows; not part of the record)
     int32_t guide = 0;                                           // the guide: on (its words are never archived: not part of the record)
     int32_t frontier = 0;                                        // the frontier: on (computed from the seen map, never archived: not part of the record)
+    int32_t visit_sectors = 0, visit_flags = 0;                  // the visit map; visit_sectors 0: off.  visit_flags: RCW_VISIT_TABLE (the table is the head, not part of the record)
 };
-constexpr int kSnapshotShapeWords = 23;                          // what travels through the development exports: everything but `guide` and `frontier`
+constexpr int kSnapshotShapeWords = 23;                          // what travels through the 23-word development exports: everything but `guide`, `frontier` and the visit map's two
 // (a part's id, in the order of the features and, within one, of its list; kSnapViewStaging — the view kernels' frame under a k-frame stack —,
-// kSnapSourceStatus, kSnapSourceMask, the guide's two words and everything of the frontier are never archived)
+// kSnapSourceStatus, kSnapSourceMask, the guide's two words and everything of the frontier are never archived; everything of the visit
+// map is)
 enum SnapshotField { kSnapPos, kSnapDir, kSnapGoal, kSnapReward, kSnapDone, kSnapEpisode, kSnapTileMap, kSnapEpisodeSteps, kSnapTruncated,
                      kSnapGoalField, kSnapGoalDistance, kSnapGoalStart, kSnapGoalProgress, kSnapGoalLast,
                      kSnapSeenCount, kSnapSeenNew, kSnapSeenGoal, kSnapSeenLast, kSnapSeenBits, kSnapSeenMap,
@@ -133,9 +135,10 @@ enum SnapshotField { kSnapPos, kSnapDir, kSnapGoal, kSnapReward, kSnapDone, kSna
                      kSnapSourceLast, kSnapSourceStatus, kSnapSourceLayout, kSnapSourceMask,
                      kSnapStatsFinished, kSnapStatsOutcome, kSnapStatsLength, kSnapStatsMoves, kSnapStatsLevel, kSnapStatsSpl, kSnapStatsEpisodes,
                      kSnapStatsPrevX, kSnapStatsPrevY, kSnapStatsLast, kSnapGuideAction, kSnapGuideHeading,
-                     kSnapFrontierDistance, kSnapFrontierTiles, kSnapFrontierAction, kSnapFrontierHeading, kSnapFrontierLast, kSnapFrontierField, kSnapFieldCount };
-enum AgentFeature { kFeatCore, kFeatGoal, kFeatSeen, kFeatView, kFeatLocal, kFeatSource, kFeatStats, kFeatGuide, kFeatFrontier, kFeatCount };
-constexpr SnapshotField kFeatureFirstId[kFeatCount + 1] = {kSnapPos, kSnapGoalField, kSnapSeenCount, kSnapViewFrame, kSnapLocalImage, kSnapSourceLast, kSnapStatsFinished, kSnapGuideAction, kSnapFrontierDistance, kSnapFieldCount};
+                     kSnapFrontierDistance, kSnapFrontierTiles, kSnapFrontierAction, kSnapFrontierHeading, kSnapFrontierLast, kSnapFrontierField,
+                     kSnapVisitHere, kSnapVisitVisited, kSnapVisitFirst, kSnapVisitLevelHere, kSnapVisitLast, kSnapVisitMap, kSnapFieldCount };
+enum AgentFeature { kFeatCore, kFeatGoal, kFeatSeen, kFeatView, kFeatLocal, kFeatSource, kFeatStats, kFeatGuide, kFeatFrontier, kFeatVisits, kFeatCount };
+constexpr SnapshotField kFeatureFirstId[kFeatCount + 1] = {kSnapPos, kSnapGoalField, kSnapSeenCount, kSnapViewFrame, kSnapLocalImage, kSnapSourceLast, kSnapStatsFinished, kSnapGuideAction, kSnapFrontierDistance, kSnapVisitHere, kSnapFieldCount};
 constexpr int kAgentMaxParts = 10;
 struct AgentPart { SnapshotField id; const char* name; uint32_t bytes; uint64_t tag; bool archived; };
 struct AgentArrays { int32_t n = 0; AgentPart part[kAgentMaxParts] = {}; uint64_t head = 0; };   // (n = 0: the feature is off)
@@ -287,6 +290,17 @@ struct rcw_handle {
         uint16_t* field = nullptr;
         bool on() const { return buf.get() != nullptr; }
     } frontier;
+    // The visit map (rcw_set_visit_map): ONE buffer — the head is the table (UInt32 (cells, 1 + rows); empty without RCW_VISIT_TABLE), then the
+    // carve of its list: the four words, each agent's episode counter as of its last BEGIN, the UInt16 (cells, B) map; dev's pointers point
+    // into it.  sectors / flags / rows / first: fixed when enabled (plan_visit_table_rows).  Empty while the feature is off.
+    struct VisitMap {
+        RcwBuf buf;
+        RcwVisitMap dev{};
+        int32_t flags = 0;
+        bool on() const { return buf.get() != nullptr; }
+        bool table() const { return dev.table != nullptr; }
+        size_t table_bytes() const { return table() ? (size_t)dev.cells * (1 + (size_t)dev.rows) * sizeof(uint32_t) : 0; }
+    } visits;
     // The state archive (rcw_set_snapshots): ONE allocation — every segment's rows ([rows][bytes], each part on a multiple of 16 bytes), then
     // the Int32 scratch (owner [rows], the row each agent takes [B], the host variants' staged indices [B]), then the filled flags (UInt8
     // [rows]).  plan: the record's layout as of the binding (plan_snapshot); arc[k]: segment k's rows.  Empty while the archive is off.
@@ -349,6 +363,7 @@ void plan_snapshot(const SnapshotShape& sh, SnapshotPlan* plan);
 const char* snapshot_plan_differs(const SnapshotPlan& bound, const SnapshotPlan& now);   // the first segment that differs, NULL: the same shape
 int validate_snapshot_row(const SnapshotShape& sh, const SnapshotPlan& plan, const uint8_t* row, char* msg, size_t cap);
 void plan_episode_stats_rows(RcwLayoutKind kind, int32_t layouts, int32_t levels, int32_t first_level, int32_t* rows, int32_t* first);
+void plan_visit_table_rows(const SnapshotShape& sh, int32_t* rows, int32_t* first);   // the visit table's level rows: the statistics' rule under the byte cap
 int guide_promised(const rcw_config& cfg);                        // 1: position_increment + player_radius <= 0.5 in the world-unit type
 
 // ---- rcw_step.hip: what a step, a reset or a re-render launches, and the resources those launches need ---------------------------------
@@ -361,6 +376,7 @@ hipError_t launch_local_map(rcw_handle* h, StackOp op);
 hipError_t launch_episode_stats(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_guide(rcw_handle* h, StackOp op);
 hipError_t launch_frontier(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
+hipError_t launch_visit_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_layout_source(rcw_handle* h, bool force);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t* mask_dev, bool restore);

@@ -259,6 +259,27 @@ size_t rcw_frontier_lds_bytes(const RcwDev& p);
 hipError_t rcw_launch_frontier(const RcwDev& p, int32_t B, const uint8_t* mask_dev, bool refill, const uint8_t* seen_map, const int32_t* newly_seen,
                                uint16_t* field, const RcwFrontierWords& words, uint32_t* last_episode, hipStream_t s);
 
+// The visit map (rcw_set_visit_map, rcw_visit_map.hip): the UInt16 (cells, B) map, the four per-agent words, the private counter and the
+// table, cells = sectors * H * W.
+struct RcwVisitMap {
+    uint16_t* map;           // [B][cells] how often the agent has stood in each cell this episode, saturating at 65535
+    int32_t* here;           // [B] the entry of the agent's cell after the call; 0: no cell
+    int32_t* visited;        // [B] non-zero entries of the agent's map
+    int32_t* first;          // [B] 1 iff the call counted a cell whose entry was 0; 0 behind a BEGIN
+    uint32_t* level_here;    // [B] the table's entry of the agent's (row, cell) as of the end of the call; 0 without the table
+    uint32_t* last_episode;  // [B] each agent's episode counter as of its last BEGIN
+    uint32_t* table;         // UInt32 (cells, 1 + rows); NULL: no table
+    int32_t sectors, cells;
+    int32_t rows, first_level;   // the level rows: row 1 + k takes the counts with layout == first_level + k
+};
+// One launch behind a step (refill = false: an agent whose episode counter differs from last_episode gets BEGIN — its map cleared, then
+// counted —, every other one COUNT at its pose) or behind reset / set_state / set_walls / enabling (refill = true: BEGIN for the agents of
+// the mask — NULL: all —, the others are left alone); with a table a second, lane-per-agent launch (rcw_visit_table_read_kernel) that only
+// reads follows and leaves level_here for every agent.  An argument block of its OWN (the comment on RcwLimit): no kernel of a handle
+// without the visit map changes.  layout: as it is NOW, NULL where the handle has no layout source.  Reads p's positions, headings and
+// counters, writes only vm's buffers.
+hipError_t rcw_launch_visit_map(const RcwDev& p, int32_t B, const RcwVisitMap& vm, const int32_t* layout, const uint8_t* mask_dev, bool refill, hipStream_t s);
+
 // THE LAYOUT SOURCES (rcw_wall_bank.hip): what gives an agent its walls at every start of an episode.  A handle has at most one — the wall
 // bank (rcw_set_wall_bank) or one family of the wall generator: mazes (rcw_set_wall_generator), caves (rcw_set_wall_caves), rooms
 // (rcw_set_wall_rooms) — behind ONE launch point, rcw_launch_layout_source.

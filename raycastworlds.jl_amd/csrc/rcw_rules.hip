@@ -606,6 +606,41 @@ void plan_episode_stats_rows(RcwLayoutKind kind, int32_t layouts, int32_t levels
     *first = any && family ? first_level : 0;
 }
 
+// ---- the visit map (include/rcw.h, "the visit map") ---------------------------------------------------------------------------------------
+// The table's level rows: episode statistics' rule from the shape's layout source — and none where the table, UInt32 (cells, 1 + rows),
+// would pass RCW_VISIT_TABLE_MAX_BYTES (no error: row 0 always works).  64-bit arithmetic: cells < 2^35, 1 + rows < 2^32.
+void plan_visit_table_rows(const SnapshotShape& sh, int32_t* rows, int32_t* first)
+{
+    plan_episode_stats_rows((RcwLayoutKind)sh.source_kind, sh.layouts, sh.levels, sh.first_level, rows, first);
+    const uint64_t cells = (uint64_t)(uint32_t)sh.visit_sectors * (uint64_t)(uint32_t)sh.H * (uint64_t)(uint32_t)sh.W;
+    if (cells * (1 + (uint64_t)(uint32_t)*rows) * sizeof(uint32_t) > (uint64_t)RCW_VISIT_TABLE_MAX_BYTES) { *rows = 0; *first = 0; }
+}
+
+namespace {
+// The tile of (x, y) in the world-unit type T: i + H*j with (i, j) = (floor x, floor y), -1: not finite or off the map.
+template <typename T>
+int32_t visit_tile(int32_t H, int32_t W, T x, T y)
+{
+    if (!std::isfinite(x) || !std::isfinite(y)) return -1;
+    const T fx = std::floor(x), fy = std::floor(y);
+    if (fx < (T)0 || fx >= (T)H || fy < (T)0 || fy >= (T)W) return -1;
+    return (int32_t)fx + H * (int32_t)fy;
+}
+}  // namespace
+
+// The handle-less export: the cell rule for one agent on the host, needs no device.
+extern "C" int rcw_visit_cell(int32_t H, int32_t W, int32_t nd, int32_t sectors, double x, double y, int32_t world_unit_bits, int32_t direction, int32_t* cell)
+{
+    if (!cell) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (H < 1 || W < 1 || (int64_t)H * W > INT32_MAX / RCW_VISIT_MAX_SECTORS) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_visit_cell: a map of %d x %d", H, W);
+    if (world_unit_bits != 32 && world_unit_bits != 64) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_visit_cell: world_unit_bits must be 32 or 64 (got %d)", world_unit_bits);
+    if (nd < 1 || direction < 0 || direction >= nd) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_visit_cell: direction %d of %d", direction, nd);
+    if (sectors < 1 || sectors > RCW_VISIT_MAX_SECTORS || sectors > nd) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_visit_cell: sectors must be in 1..min(%d, nd = %d) (got %d)", RCW_VISIT_MAX_SECTORS, nd, sectors);
+    const int32_t t = world_unit_bits == 64 ? visit_tile<double>(H, W, x, y) : visit_tile<float>(H, W, (float)x, (float)y);
+    *cell = t < 0 ? -1 : (int32_t)(((int64_t)direction * sectors) / nd) * (H * W) + t;
+    return RCW_OK;
+}
+
 // The handle-less export: the rule once more on the host, by another traversal than the device's — depth first off a plain stack, a chamber
 // at a time, where the kernel cuts every chamber of a depth in one round.
 extern "C" int rcw_wall_rooms_layout(int32_t H, int32_t W, uint64_t key, int32_t room, uint32_t stop, uint32_t doors, uint8_t* out_host, int32_t* rooms)
@@ -853,6 +888,20 @@ void agent_arrays(const SnapshotShape& sh, int feature, AgentArrays* out)
         add(kSnapFrontierHeading, "frontier.heading", 4, 0, false);
         add(kSnapFrontierLast, "frontier.last_episode", 4, 0, false);
         add(kSnapFrontierField, "frontier.field", 2u * HW, 0, false);
+    }
+    if (feature == kFeatVisits && sh.visit_sectors) {                      // head: the table (not part of a record); every part is episode state nothing recomputes
+        const uint64_t cells = (uint64_t)sh.visit_sectors * HW;
+        if (sh.visit_flags & RCW_VISIT_TABLE) {
+            int32_t rows = 0, first = 0;
+            plan_visit_table_rows(sh, &rows, &first);
+            p.head = sizeof(uint32_t) * cells * (1 + (uint64_t)rows);
+        }
+        add(kSnapVisitHere, "visit_map.here", 4);
+        add(kSnapVisitVisited, "visit_map.visited", 4);
+        add(kSnapVisitFirst, "visit_map.first", 4);
+        add(kSnapVisitLevelHere, "visit_map.level_here", 4);
+        add(kSnapVisitLast, "visit_map.last_episode", 4);
+        add(kSnapVisitMap, "visit_map.map", (uint32_t)(2u * cells), (uint64_t)sh.visit_sectors);   // (the tag: a 2-sector row is not a 1-sector one of a map twice the size)
     }
 }
 

@@ -249,6 +249,16 @@ hipError_t launch_frontier(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
     return rcw_launch_guide(h->dev, h->B, fr.field, fr.advice, h->stream);
 }
 
+// ... and the visit map, behind the frontier and in front of the local map: pose, episode counter and layout word are final there (the
+// layout source's kernel and its re-render have run).  A step runs the step rule (the counter decides who begins), a refill the mask rule;
+// a re-render of the same world (a new direction table, a change of the step's form, a restore's render) launches nothing: a restore puts
+// the record back and counts nothing.
+hipError_t launch_visit_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op)
+{
+    if (!h->visits.on() || op == kStackKeep || op == kStackRefillSameWorld) return hipSuccess;
+    return rcw_launch_visit_map(h->dev, h->B, h->visits.dev, h->source.live() ? h->source.dev.agents.layout : nullptr, mask_dev, op == kStackRefill, h->stream);
+}
+
 // ... and last, behind the seen map it may read, the local map: a pure function of the state, so every agent's image at every render but
 // the one that re-renders the very same frames
 hipError_t launch_local_map(rcw_handle* h, StackOp op)
@@ -303,6 +313,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
         if (e == hipSuccess) e = launch_guide(h, op);
         if (e == hipSuccess) e = launch_seen_map(h, mask_dev, op);
         if (e == hipSuccess) e = launch_frontier(h, mask_dev, op);
+        if (e == hipSuccess) e = launch_visit_map(h, mask_dev, op);
         if (e == hipSuccess) e = launch_local_map(h, op);
         return e == hipSuccess ? launch_episode_stats(h, mask_dev, op) : e;
     }
@@ -324,6 +335,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     if ((e = launch_guide(h, op)) != hipSuccess) return e;
     if ((e = launch_seen_map(h, mask_dev, op)) != hipSuccess) return e;
     if ((e = launch_frontier(h, mask_dev, op)) != hipSuccess) return e;
+    if ((e = launch_visit_map(h, mask_dev, op)) != hipSuccess) return e;
     if ((e = launch_local_map(h, op)) != hipSuccess) return e;
     return launch_episode_stats(h, mask_dev, op);
 }
@@ -332,7 +344,7 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
 // archive's: every segment has its live array).  Both: who takes which row, then the copy — the segment table goes to the kernel
 // kSnapshotKernelSegments at a time.  A save is done there.  A restore goes on: the step's facts forget the slots (StepFacts::restored), and
 // the agents of the mask are cast and painted from the state they now hold, as a re-render of the same frames is (kStackKeep): the flood, the
-// seen map, the stack, the local map and the statistics are the record's and stay as the gather left them.  The guide's words are no part
+// seen map, the visit map, the stack, the local map and the statistics are the record's and stay as the gather left them.  The guide's words are no part
 // of the record: its kernel follows, on the restored state.  Nor is anything of the frontier: the agents of the mask are flooded again
 // from the seen map the gather restored, and the action words of every agent follow.
 hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t* mask_dev, bool restore)

@@ -202,6 +202,23 @@ def frontier_rule(seen_map):
     return np.ascontiguousarray(out.T), int(tiles.value)
 
 
+def visit_cell(H: int, W: int, num_directions: int, sectors: int, position, direction: int, T=np.float32) -> int:
+    """The visit map's cell rule (include/rcw.h, "the visit map") for ONE agent on the host: the 0-based cell `s*H*W + i + H*j` of an agent
+    at `position` (x, y) facing the 0-based direction index `direction`, -1 where it has none (a position that is not finite, a tile off
+    the map).  `env.visit_map[b].reshape(-1)` is NOT in this order; `env.visit_map_device` is.  rcw_visit_cell: host arithmetic, no device."""
+    import ctypes as C
+
+    from . import _capi
+
+    lib = _capi.load()
+    cell = C.c_int32()
+    bits = 64 if np.dtype(T) == np.float64 else 32
+    rc = lib.rcw_visit_cell(int(H), int(W), int(num_directions), int(sectors), float(position[0]), float(position[1]), bits, int(direction), C.byref(cell))
+    if rc != _capi.RCW_OK:
+        raise ValueError(_capi.last_error(lib))
+    return int(cell.value)
+
+
 def is_connected(walls) -> bool:
     """True where every free tile of the layout (bool (H, W)) can be reached from every other through free tiles that
     share an edge — the moves `act!` can make between tile centres.  A layout without a free tile is not connected."""

@@ -251,6 +251,41 @@ class ShardedSingleRoom:
     def frontier_field(self):
         return self.env.frontier_field
 
+    # ---- the visit map: a count of each agent's own poses, so a shard's map and words are its slice of the batch's ----
+    def set_visit_map(self, sectors=1, table: bool = False) -> None:
+        """`SingleRoom.set_visit_map` of this rank's engine (also the `visit_map=` keyword).  The map and `visits_here` /
+        `visited_cells` / `visit_first` of a shard are its slice of the batch's.  The table is per handle: a shard's table holds its own
+        agents' counts, the shards' tables sum to the batch's (nothing here all-reduces them), and `level_visits_here` is taken from
+        the shard's OWN table — it is not a slice of the batch's."""
+        self.env.set_visit_map(sectors, table)
+
+    @property
+    def visit_map(self):
+        return self.env.visit_map
+
+    @property
+    def visits_here(self):
+        return self.env.visits_here
+
+    @property
+    def visited_cells(self):
+        return self.env.visited_cells
+
+    @property
+    def visit_first(self):
+        return self.env.visit_first
+
+    @property
+    def level_visits_here(self):
+        return self.env.level_visits_here
+
+    def visit_table(self, device: bool = False):
+        """`SingleRoom.visit_table` of this rank's engine: this SHARD's counts."""
+        return self.env.visit_table(device)
+
+    def visit_table_clear(self) -> None:
+        self.env.visit_table_clear()
+
     # ---- the state archive: every shard has its own, rows are LOCAL ---------------------------
     def set_snapshots(self, rows: int) -> None:
         """`SingleRoom.set_snapshots` of this rank's engine: `rows` records a SHARD.  Rows do not cross shards."""

@@ -350,7 +350,8 @@ class SingleRoom:
     `seen_map` (this build's addition) `set_seen_map(True)` after that, `frontier` (this build's addition) `set_frontier(True)` right
     behind it (it enables the seen map where that is off), `local_map` (this build's addition; an int — the size — or a dict
     of `set_local_map`'s keywords) `set_local_map` after that, `episode_stats` (this build's addition) `set_episode_stats(True)` last of
-    all — behind the layout sources below, whose levels count its table's rows.  `wall_bank` / `wall_bank_weights` (this build's addition) are `set_wall_bank`'s
+    all — behind the layout sources below, whose levels count its table's rows —, `visit_map` (this build's addition; True, or a dict of
+    `set_visit_map`'s keywords) `set_visit_map` right behind it, for the same reason.  `wall_bank` / `wall_bank_weights` (this build's addition) are `set_wall_bank`'s
     arguments, applied after `walls` and the time limit and before the features: a layout drawn on the device at every episode start.
     `wall_generator` (this build's addition; a dict of `set_wall_generator`'s keywords, `{}` for the defaults) is applied in the same
     place: a new maze made on the device at every episode start.  It and `wall_bank` exclude each other.  `wall_caves` (this build's
@@ -403,6 +404,7 @@ class SingleRoom:
         wall_caves=None,
         wall_rooms=None,
         episode_stats: bool = False,
+        visit_map=None,
         snapshots: int = 0,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
@@ -547,6 +549,12 @@ class SingleRoom:
             except BaseException:
                 self._handle.close()
                 raise
+        if visit_map is not None and visit_map is not False:
+            try:
+                self.set_visit_map(**visit_map) if isinstance(visit_map, dict) else self.set_visit_map()
+            except BaseException:
+                self._handle.close()
+                raise
         if snapshots:
             try:
                 self.set_snapshots(snapshots)
@@ -579,7 +587,7 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_guide_dev", "_seen_map_dev", "_frontier_dev", "_local_map_dev", "_episode_stats_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
+        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_guide_dev", "_seen_map_dev", "_frontier_dev", "_local_map_dev", "_episode_stats_dev", "_visit_map_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
             self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
@@ -1098,6 +1106,110 @@ class SingleRoom:
         """Zero the table, stream-ordered and without waiting for the stream; the per-agent words stay.  What a replay loop calls after
         it has read the table."""
         self._check(self._lib.rcw_episode_stats_clear(self._h))
+
+    # ---- the visit map (include/rcw.h, rcw_set_visit_map) --------------------------------
+    _VISIT_WORDS = (np.int32, np.int32, np.int32, np.uint32)              # here, visited, first, level_here
+
+    def set_visit_map(self, sectors=1, table: bool = False) -> None:
+        """Keep, on the device, how often each agent has stood in each cell — tile x heading sector (`sectors` of them, 1..8, at most
+        `num_directions`) — this episode: `visit_map` (uint16, saturating), `visits_here` (the count of the cell the agent is on: the N of
+        `beta / sqrt(N)`), `visited_cells`, `visit_first` (1 where the last step entered a cell for the first time this episode: the
+        NovelD gate) and, with `table=True`, the uint32 table of the counts summed over the batch and per level of the layout source that
+        is live NOW (`visit_table`, `level_visits_here`; the layout source cannot be changed while it is on).  A restart clears the
+        agent's map; with no host in the loop.  `set_visit_map(None)` switches it off.  Switching it on (again) zeroes everything and
+        counts every agent's cell once; the device arrays handed out before are invalid after every call."""
+        self.__dict__.pop("_visit_map_dev", None)
+        if sectors is None or sectors is False:
+            self._check(self._lib.rcw_set_visit_map(self._h, 0, 0, 0))
+        else:
+            self._check(self._lib.rcw_set_visit_map(self._h, 1, int(sectors), _capi.RCW_VISIT_TABLE if table else 0))
+
+    @property
+    def visit_map_info(self) -> dict:
+        """`enabled`, `sectors`, `table`, and the table's level rows: `rows` of them, the first for level `first` (rcw_visit_map_info)."""
+        v = [C.c_int32() for _ in range(5)]
+        self._check(self._lib.rcw_visit_map_info(self._h, *[C.byref(x) for x in v]))
+        return {"enabled": bool(v[0].value), "sectors": v[1].value, "table": bool(v[2].value & _capi.RCW_VISIT_TABLE), "rows": v[3].value, "first": v[4].value}
+
+    def _visit_words_host(self, which: int) -> np.ndarray:
+        out = np.empty(self.batch, dtype=self._VISIT_WORDS[which])
+        args = [None] * 4
+        args[which] = _as_ptr(out)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_visit_words(self._h, *args))
+        return out
+
+    def _visit_arrays(self):
+        if getattr(self, "_visit_map_dev", None) is None:
+            p = [C.c_void_p() for _ in range(4)]
+            self._check(self._lib.rcw_visit_words_device_ptr(self._h, *[C.byref(q) for q in p]))
+            self._visit_map_dev = tuple(
+                DeviceArray(p[k].value, (self.batch,), dtype, self, self._sync, host_getter=lambda k=k: self._visit_words_host(k))
+                for k, dtype in enumerate(self._VISIT_WORDS))
+        return self._visit_map_dev
+
+    @property
+    def visits_here(self) -> DeviceArray:
+        """int32 (B,) in device memory: how often each agent has stood in the cell it is in, this call included (0: off the map).
+        `beta * torch.rsqrt(env.visits_here.torch(sync=False).float().clamp(min=1))` is the count bonus."""
+        return self._visit_arrays()[0]
+
+    @property
+    def visited_cells(self) -> DeviceArray:
+        """int32 (B,): the cells each agent has stood in this episode."""
+        return self._visit_arrays()[1]
+
+    @property
+    def visit_first(self) -> DeviceArray:
+        """int32 (B,): 1 where the last call counted a cell the agent had not stood in this episode; 0 behind a restart."""
+        return self._visit_arrays()[2]
+
+    @property
+    def level_visits_here(self) -> DeviceArray:
+        """uint32 (B,): the table's count of each agent's cell on its level (of the whole batch where it has no level row), every
+        agent's adds of the call included; 0 without the table."""
+        return self._visit_arrays()[3]
+
+    @property
+    def visit_map(self) -> np.ndarray:
+        """uint16 (B, sectors, H, W), a host copy: `visit_map[b, s, i-1, j-1]` of tile (i, j) — indexed like `env.seen_map` per sector."""
+        H, W, S = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu, self.visit_map_info["sectors"]
+        out = np.empty((self.batch, S, W, H), dtype=np.uint16)             # tile (i, j) at (i - 1) + H (j - 1)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_visit_map(self._h, 0, self.batch, _as_ptr(out)))
+        return np.ascontiguousarray(out.transpose(0, 1, 3, 2))
+
+    @property
+    def visit_map_device(self) -> DeviceArray:
+        """The map where it lives: uint16 (B, sectors, W, H) in device memory — the tile map's own order, `[b, s, j-1, i-1]`."""
+        p = C.c_void_p()
+        self._check(self._lib.rcw_visit_map_device_ptr(self._h, C.byref(p)))
+        H, W, S = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu, self.visit_map_info["sectors"]
+        return DeviceArray(p.value, (self.batch, S, W, H), np.uint16, self, self._sync,
+                           host_getter=lambda: np.ascontiguousarray(self.visit_map.transpose(0, 1, 3, 2)))
+
+    def visit_table(self, device: bool = False):
+        """The counts summed since enabling (or the last `visit_table_clear`).  A dict: `total` uint32 (sectors, H, W) — every agent's
+        counts —, `levels` (rows, sectors, H, W) — the same per level, level `first + k` at k —, and `first`.  `device=True`: the raw
+        uint32 (1 + rows, sectors, W, H) `DeviceArray` instead, row 0 the total."""
+        info = self.visit_map_info
+        H, W, S, rows = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu, info["sectors"], info["rows"]
+        if device:
+            p = C.c_void_p()
+            self._check(self._lib.rcw_visit_table_device_ptr(self._h, C.byref(p)))
+            return DeviceArray(p.value, (1 + rows, S, W, H), np.uint32, self, self._sync, host_getter=lambda: self._visit_table_host(rows, S))
+        t = np.ascontiguousarray(self._visit_table_host(rows, S).transpose(0, 1, 3, 2))
+        return {"total": t[0], "levels": t[1:], "first": info["first"]}
+
+    def _visit_table_host(self, rows: int, sectors: int) -> np.ndarray:
+        out = np.empty((1 + rows, sectors, self.cfg.width_tile_map_tu, self.cfg.height_tile_map_tu), dtype=np.uint32)
+        self.host_syncs += 1
+        self._check(self._lib.rcw_visit_table(self._h, _as_ptr(out)))
+        return out
+
+    def visit_table_clear(self) -> None:
+        """Zero the table, stream-ordered and without waiting for the stream; the per-agent maps and words stay."""
+        self._check(self._lib.rcw_visit_table_clear(self._h))
 
     # ---- the state archive (include/rcw.h, rcw_set_snapshots) ----------------------------
     def set_snapshots(self, rows: int) -> None:
