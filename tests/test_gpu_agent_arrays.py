@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import snapshot_cases as SC
+import snapshot_rows as SR
 from test_snapshot_spec import SHAPE_FIELDS
 
 pytestmark = pytest.mark.gpu
@@ -101,8 +102,6 @@ def assert_pointers_hold_the_readouts(env, B, c, T, where):
 @pytest.mark.parametrize("T", ["Float32", "Float64"])
 @pytest.mark.parametrize("B", [5, 67])
 def test_every_device_pointer_holds_what_its_readout_hands_out(rcw, B, T):
-    from raycastworlds_jl_amd import _capi
-
     c = SC.ODD
     env = SC.make(rcw, B, c, T=T, rows=B)
     acts = SC.actions(B, 8, seed=B)
@@ -120,23 +119,18 @@ def test_every_device_pointer_holds_what_its_readout_hands_out(rcw, B, T):
     # the archive's copy goes through the same table: a save of every agent, exported, cut at the plan's offsets
     env.snapshot_save()
     exported = env.snapshot_export()
-    dev = C.CDLL(_capi.DEV_LIB_PATH)
-    dev.rcw_dev_snapshot_plan.argtypes = [C.POINTER(C.c_int32), C.c_char_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    view = [C.c_int32() for _ in range(5)]
-    env._check(env._lib.rcw_learner_view_info(env._h, *[C.byref(v) for v in view]))
-    local = [C.c_int32() for _ in range(3)]
-    env._check(env._lib.rcw_local_map_info(env._h, *[C.byref(v) for v in local]))
-    kw = dict(H=c["H"], W=c["W"], nd=8, N=64, Hc=64, real64=int(T == "Float64"), goal=1, seen=1, stats=1, view_fmt=view[0].value, view_layout=view[1].value,
-              view_C=1, view_h=c["view"][0], view_w=c["view"][1], view_frames=c["k"], local_source=local[0].value, local_size=local[1].value,
-              local_cells=local[2].value, source_kind=1, layouts=3)
-    names, sizes, row_bytes, key = C.create_string_buffer(4096), (C.c_uint32 * 64)(), C.c_uint64(), C.c_uint64()
-    n = dev.rcw_dev_snapshot_plan((C.c_int32 * len(SHAPE_FIELDS))(*[kw.get(f, 0) for f in SHAPE_FIELDS]), names, 4096, sizes, C.byref(row_bytes), C.byref(key))
-    assert n > 0 and key.value == exported["shape_key"] and row_bytes.value == exported["row_bytes"] and exported["rows"].shape == (B, row_bytes.value)
-    offset, seen = 0, set()
-    for name, size in zip(names.value.decode().split("\n")[:n], sizes[:n]):
+    kw = SR.shape_of(env, source_kind=1, layouts=3)
+    assert kw == dict(H=c["H"], W=c["W"], nd=8, N=64, Hc=64, real64=int(T == "Float64"), reward_type=0, goal=1, seen=1, stats=1, view_fmt=kw["view_fmt"],
+                      view_layout=kw["view_layout"], view_C=1, view_h=c["view"][0], view_w=c["view"][1], view_frames=c["k"], local_source=kw["local_source"],
+                      local_size=kw["local_size"], local_cells=kw["local_cells"], source_kind=1, layouts=3) and set(kw) <= set(SHAPE_FIELDS)
+    table = SR.segments(exported, **kw)                                           # (the plan's key and row_bytes are the export's)
+    assert exported["rows"].shape == (B, exported["row_bytes"])
+    end, seen = 0, set()
+    for name, offset, size in table:
+        assert offset == end
         if name not in PRIVATE:
             want = last[SEGMENT[name]].reshape(B, -1).view(np.uint8)
             assert want.shape[1] == size and exported["rows"][:, offset:offset + size].tobytes() == want.tobytes(), name
             seen.add(SEGMENT[name])
-        offset += size
-    assert offset == row_bytes.value and seen == set(last) - {"table"}
+        end = offset + size
+    assert end == exported["row_bytes"] and seen == set(last) - {"table"}
