@@ -218,38 +218,10 @@ class ShardedSingleRoom:
         """`SingleRoom.set_guide` of this rank's engine (also the `guide=True` keyword); `guide_action` / `guide_heading` are LOCAL."""
         self.env.set_guide(on)
 
-    @property
-    def guide_action(self):
-        return self.env.guide_action
-
-    @property
-    def guide_heading(self):
-        return self.env.guide_heading
-
     # ---- the frontier: a function of each agent's own seen map and pose, so a shard's words are its slice of the batch's ----
     def set_frontier(self, on: bool = True) -> None:
         """`SingleRoom.set_frontier` of this rank's engine (also the `frontier=True` keyword); the arrays below are LOCAL."""
         self.env.set_frontier(on)
-
-    @property
-    def frontier_distance(self):
-        return self.env.frontier_distance
-
-    @property
-    def frontier_tiles(self):
-        return self.env.frontier_tiles
-
-    @property
-    def explore_action(self):
-        return self.env.explore_action
-
-    @property
-    def explore_heading(self):
-        return self.env.explore_heading
-
-    @property
-    def frontier_field(self):
-        return self.env.frontier_field
 
     # ---- the visit map: a count of each agent's own poses, so a shard's map and words are its slice of the batch's ----
     def set_visit_map(self, sectors=1, table: bool = False) -> None:
@@ -258,26 +230,6 @@ class ShardedSingleRoom:
         agents' counts, the shards' tables sum to the batch's (nothing here all-reduces them), and `level_visits_here` is taken from
         the shard's OWN table — it is not a slice of the batch's."""
         self.env.set_visit_map(sectors, table)
-
-    @property
-    def visit_map(self):
-        return self.env.visit_map
-
-    @property
-    def visits_here(self):
-        return self.env.visits_here
-
-    @property
-    def visited_cells(self):
-        return self.env.visited_cells
-
-    @property
-    def visit_first(self):
-        return self.env.visit_first
-
-    @property
-    def level_visits_here(self):
-        return self.env.level_visits_here
 
     def visit_table(self, device: bool = False):
         """`SingleRoom.visit_table` of this rank's engine: this SHARD's counts."""
@@ -450,3 +402,13 @@ class ShardedSingleRoom:
             self.env._lib.rcw_comm_destroy(self.env._h)
             self._abi_comm = False
         self.env.close()
+
+
+# The per-agent arrays a shard hands out as its engine's, by `SingleRoom`'s names: functions of each agent's own state, so a shard's
+# are its slice of the batch's (but `level_visits_here`: `set_visit_map`).  They are LOCAL: one entry per agent of this rank.
+_FORWARDED = ("guide_action", "guide_heading",
+              "frontier_distance", "frontier_tiles", "explore_action", "explore_heading", "frontier_field",
+              "visit_map", "visits_here", "visited_cells", "visit_first", "level_visits_here")
+for _name in _FORWARDED:
+    setattr(ShardedSingleRoom, _name, property(lambda self, _name=_name: getattr(self.env, _name)))
+del _name

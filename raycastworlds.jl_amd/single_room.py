@@ -19,6 +19,7 @@ UInt32 (H_cam, N, B).
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import sys
 import types
@@ -213,6 +214,66 @@ def _torch_owns(stream) -> bool:
 
 def _as_ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# ---- the per-agent words, maps and fields of the features, described ONCE (DESIGN.md "the per-agent arrays in the binding") ----------
+# A group of words: the attribute that caches its `DeviceArray`s, the export that copies them to the host (a pointer a word, NULL: not
+# this one), the export that hands out their device pointers, and the words in the ABI's order as (public name, dtype).  `namespace`:
+# the group is handed out whole, as a SimpleNamespace of its words.
+_Words = collections.namedtuple("_Words", "cache host device_ptr words namespace", defaults=(False,))
+_WORDS = {
+    "goal_distance": _Words("_goal_distance_dev", "rcw_goal_distance", "rcw_goal_distance_device_ptr",
+                            (("goal_distance", np.int32), ("goal_start_distance", np.int32), ("goal_progress", np.int32))),
+    "guide": _Words("_guide_dev", "rcw_guide", "rcw_guide_device_ptr", (("guide_action", np.uint8), ("guide_heading", np.int32))),
+    "seen_map": _Words("_seen_map_dev", "rcw_seen_words", "rcw_seen_words_device_ptr",
+                       (("seen_count", np.int32), ("seen_new", np.int32), ("goal_seen", np.int32))),
+    "frontier": _Words("_frontier_dev", "rcw_frontier", "rcw_frontier_device_ptr",
+                       (("frontier_distance", np.int32), ("frontier_tiles", np.int32), ("explore_action", np.uint8), ("explore_heading", np.int32))),
+    "visit_map": _Words("_visit_map_dev", "rcw_visit_words", "rcw_visit_words_device_ptr",
+                        (("visits_here", np.int32), ("visited_cells", np.int32), ("visit_first", np.int32), ("level_visits_here", np.uint32))),
+    "episode_stats": _Words("_episode_stats_dev", "rcw_episode_stats", "rcw_episode_stats_device_ptr",
+                            (("finished", np.uint8), ("outcome", np.uint8), ("length", np.uint32), ("moves", np.uint32), ("level", np.int32),
+                             ("spl_q16", np.int32), ("episodes", np.uint32)), namespace=True),
+    "wall_layout": _Words("_wall_layout_dev", "rcw_wall_layout", "rcw_wall_layout_device_ptr", (("wall_layout", np.int32),)),
+}
+
+# An array in the tile map's own order, (B, [sectors,] W, H) on the device: its element type, the export that copies agents
+# [first, first + count) to the host, the export that hands out its device pointer, and whether it has the visit map's sector axis.
+_Tiles = collections.namedtuple("_Tiles", "dtype host device_ptr sectors")
+_TILES = {
+    "goal_distance_field": _Tiles(np.uint16, "rcw_goal_distance_field", "rcw_goal_distance_field_device_ptr", False),
+    "seen_map": _Tiles(np.uint8, "rcw_seen_map", "rcw_seen_map_device_ptr", False),
+    "frontier_field": _Tiles(np.uint16, "rcw_frontier_field", "rcw_frontier_field_device_ptr", False),
+    "visit_map": _Tiles(np.uint16, "rcw_visit_map", "rcw_visit_map_device_ptr", True),
+}
+
+# Every attribute of a SingleRoom that caches an alias of engine memory, by group: what `close()` drops, and a setter for its groups
+# (`SingleRoom._drop`).  An alias cached under a name that is not here outlives `close()`.
+_CACHES = {
+    "reward": ("_reward_dev",), "done": ("_done_dev", "_done_dev_bool"), "truncated": ("_truncated_dev", "_truncated_dev_bool"),
+    "episode_steps": ("_episode_steps_dev",), "local_map": ("_local_map_dev",), "state": ("_state_alias",),
+    "constant_actions": ("_constant_action_buffers",), "learner_view": ("_learner_view_alias",),
+    **{group: (row.cache,) for group, row in _WORDS.items()},
+}
+
+
+def _word(group: str, k: Optional[int], doc: str) -> property:
+    """The property of SingleRoom for word `k` of `_WORDS[group]` (None: the group itself, a namespace).  The cached path is one
+    dictionary hit and one index."""
+    row = _WORDS[group]
+    cache = row.cache
+
+    def get(self):
+        words = self.__dict__.get(cache) or self._device_words(row)
+        return words if k is None else words[k]
+
+    return property(get, doc=doc)
+
+
+def _tiles(name: str, doc: str, device: bool = False) -> property:
+    """The property of SingleRoom for `_TILES[name]`: the host copy, indexed like `env.world.walls`, or (`device`) the alias."""
+    row = _TILES[name]
+    return property((lambda self: self._tiles_device(row)) if device else (lambda self: self._tiles_host(row)), doc=doc)
 
 
 class SingleRoomWorld:
@@ -587,8 +648,13 @@ class SingleRoom:
         if handle is not None:
             handle.close()
         self._held = []
-        for name in ("_reward_dev", "_done_dev", "_done_dev_bool", "_truncated_dev", "_truncated_dev_bool", "_episode_steps_dev", "_goal_distance_dev", "_guide_dev", "_seen_map_dev", "_frontier_dev", "_local_map_dev", "_episode_stats_dev", "_visit_map_dev", "_wall_layout_dev", "_state_alias", "_constant_action_buffers", "_learner_view_alias"):
-            self.__dict__.pop(name, None)
+        self._drop(*_CACHES)
+
+    def _drop(self, *groups: str) -> None:
+        """Forget the cached aliases of `groups` (`_CACHES`): the next access asks the library again."""
+        for group in groups:
+            for name in _CACHES[group]:
+                self.__dict__.pop(name, None)
 
     # (no __del__: an environment that is dropped without close() lets go of its _Handle, and the engine is destroyed
     # when the last holder does — this object, or the last torch tensor made over engine memory, whichever lives longer)
@@ -722,7 +788,7 @@ class SingleRoom:
         else:
             self._check(self._lib.rcw_set_learner_view_stack(self._h, formats[format], layouts[layout], h, w, flags, stack))
         self._view_only = not camera_view                # (RLBase.state refuses the stale camera view of such a handle)
-        self.__dict__.pop("_learner_view_alias", None)
+        self._drop("learner_view")
 
     def learner_view_info(self) -> dict:
         """The current learner view settings (rcw_learner_view_info): format, layout, size, camera_view."""
@@ -850,6 +916,45 @@ class SingleRoom:
         ev.record(self.torch_stream())
         ring.append((ev, tensors))
 
+    # ---- the features' per-agent words and tile-order arrays: one readout, one alias for all of `_WORDS` and `_TILES` ----
+    def _word_host(self, row: _Words, k: int) -> np.ndarray:
+        """Word `k` of a group, copied to the host (waits for the engine's stream)."""
+        out = np.empty(self.batch, dtype=row.words[k][1])
+        args = [None] * len(row.words)
+        args[k] = _as_ptr(out)
+        self.host_syncs += 1
+        self._check(getattr(self._lib, row.host)(self._h, *args))
+        return out
+
+    def _device_words(self, row: _Words):
+        """A group's words as `DeviceArray`s (B,), made once and cached under `row.cache` until a setter drops them."""
+        p = [C.c_void_p() for _ in row.words]
+        self._check(getattr(self._lib, row.device_ptr)(self._h, *[C.byref(q) for q in p]))
+        group = tuple(DeviceArray(p[k].value, (self.batch,), dtype, self, self._sync, host_getter=lambda k=k: self._word_host(row, k))
+                      for k, (_, dtype) in enumerate(row.words))
+        if row.namespace:
+            group = types.SimpleNamespace(**{name: x for (name, _), x in zip(row.words, group)})
+        self.__dict__[row.cache] = group
+        return group
+
+    def _tiles_shape(self, row: _Tiles):
+        lead = (self.batch, self.visit_map_info["sectors"]) if row.sectors else (self.batch,)
+        return lead + (self.cfg.width_tile_map_tu, self.cfg.height_tile_map_tu)      # tile (i, j) at (i - 1) + H (j - 1)
+
+    def _tiles_host(self, row: _Tiles, device_order: bool = False) -> np.ndarray:
+        """A tile-order array copied to the host (waits for the engine's stream): (B, [sectors,] H, W), indexed like
+        `env.world.walls` — or (`device_order`) as it lies on the device, (B, [sectors,] W, H)."""
+        out = np.empty(self._tiles_shape(row), dtype=row.dtype)
+        self.host_syncs += 1
+        self._check(getattr(self._lib, row.host)(self._h, 0, self.batch, _as_ptr(out)))
+        return out if device_order else np.ascontiguousarray(np.swapaxes(out, -1, -2))
+
+    def _tiles_device(self, row: _Tiles) -> DeviceArray:
+        """A tile-order array where it lives; a new alias at every call (the pointer moves with the feature's setter)."""
+        p = C.c_void_p()
+        self._check(getattr(self._lib, row.device_ptr)(self._h, C.byref(p)))
+        return DeviceArray(p.value, self._tiles_shape(row), row.dtype, self, self._sync, host_getter=lambda: self._tiles_host(row, device_order=True))
+
     def reward_device(self) -> DeviceArray:
         """`world.reward` (SR:33) where it lives: R (B,) in device memory, stable for the handle's lifetime, rewritten
         by every step in stream order.  The same object on every call (its torch alias is made once)."""
@@ -914,9 +1019,9 @@ class SingleRoom:
         based shaping is `r + c * env.goal_progress.torch(sync=False)`).  Follows resets, `set_state`, `set_walls` and `auto_reset`
         restarts with no host synchronisation.  Switching it on (again) recomputes everything and makes the current state the
         episode's start; the device arrays handed out before are invalid after every call."""
-        self.__dict__.pop("_goal_distance_dev", None)
+        self._drop("goal_distance")
         if not on:
-            self.__dict__.pop("_guide_dev", None)                 # (the guide reads the field: it goes with it)
+            self._drop("guide")                                   # (the guide reads the field: it goes with it)
         self._check(self._lib.rcw_set_goal_distance(self._h, 1 if on else 0))
 
     @property
@@ -925,57 +1030,21 @@ class SingleRoom:
         self._check(self._lib.rcw_goal_distance_enabled(self._h, C.byref(n)))
         return bool(n.value)
 
-    def _goal_distance_host(self, which: int) -> np.ndarray:
-        out = np.empty(self.batch, dtype=np.int32)
-        args = [None, None, None]
-        args[which] = _as_ptr(out)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_goal_distance(self._h, *args))
-        return out
-
-    def _goal_distance_arrays(self):
-        if getattr(self, "_goal_distance_dev", None) is None:
-            p = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
-            self._check(self._lib.rcw_goal_distance_device_ptr(self._h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])))
-            self._goal_distance_dev = tuple(
-                DeviceArray(p[k].value, (self.batch,), np.int32, self, self._sync, host_getter=lambda k=k: self._goal_distance_host(k))
-                for k in range(3))
-        return self._goal_distance_dev
-
-    @property
-    def goal_distance(self) -> DeviceArray:
+    goal_distance = _word("goal_distance", 0,
         """int32 (B,) in device memory: tiles from the player's tile to the goal through the walls; -1 where there is no path (or the
-        player is off the map).  Rewritten behind every step, reset, `set_state` and `set_walls` in stream order."""
-        return self._goal_distance_arrays()[0]
-
-    @property
-    def goal_start_distance(self) -> DeviceArray:
-        """int32 (B,): `goal_distance` as of the start of each agent's current episode."""
-        return self._goal_distance_arrays()[1]
-
-    @property
-    def goal_progress(self) -> DeviceArray:
+        player is off the map).  Rewritten behind every step, reset, `set_state` and `set_walls` in stream order.""")
+    goal_start_distance = _word("goal_distance", 1,
+        """int32 (B,): `goal_distance` as of the start of each agent's current episode.""")
+    goal_progress = _word("goal_distance", 2,
         """int32 (B,): tiles the last step brought each agent closer to its goal (negative: farther); 0 for an agent the call restarted
-        or reset, and where either distance is -1."""
-        return self._goal_distance_arrays()[2]
-
-    @property
-    def goal_distance_field(self) -> np.ndarray:
+        or reset, and where either distance is -1.""")
+    goal_distance_field = _tiles("goal_distance_field",
         """uint16 (B, H, W), a host copy: `field[b, i-1, j-1]` is the distance of tile (i, j) from agent b's goal, 0xFFFF for walls and
-        tiles without a path — indexed like `env.world.walls`."""
-        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
-        out = np.empty((self.batch, W, H), dtype=np.uint16)                # tile (i, j) at (i - 1) + H (j - 1)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_goal_distance_field(self._h, 0, self.batch, _as_ptr(out)))
-        return np.ascontiguousarray(out.transpose(0, 2, 1))
+        tiles without a path — indexed like `env.world.walls`.""")
 
     def goal_distance_field_device(self) -> DeviceArray:
         """The field where it lives: uint16 (B, W, H) in device memory — the tile map's own order, `[b, j-1, i-1]`."""
-        p = C.c_void_p()
-        self._check(self._lib.rcw_goal_distance_field_device_ptr(self._h, C.byref(p)))
-        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
-        return DeviceArray(p.value, (self.batch, W, H), np.uint16, self, self._sync,
-                           host_getter=lambda: np.ascontiguousarray(self.goal_distance_field.transpose(0, 2, 1)))
+        return self._tiles_device(_TILES["goal_distance_field"])
 
     # ---- the guide (include/rcw.h, rcw_set_guide) ----------------------------------------
     def set_guide(self, on: bool = True) -> None:
@@ -986,7 +1055,7 @@ class SingleRoom:
         `torch.where(beta, env.guide_action.torch(sync=False), policy_action)`.  Switching it on enables the goal distance first where
         that is off; `set_goal_distance(False)` switches the guide off too.  The device arrays handed out before are invalid after
         every call."""
-        self.__dict__.pop("_guide_dev", None)
+        self._drop("guide")
         if on and not self.goal_distance_enabled:
             self.set_goal_distance(True)
         self._check(self._lib.rcw_set_guide(self._h, 1 if on else 0))
@@ -1003,37 +1072,13 @@ class SingleRoom:
     def guide_enabled(self) -> bool:
         return self.guide_info["enabled"]
 
-    def _guide_host(self, which: int) -> np.ndarray:
-        out = np.empty(self.batch, dtype=(np.uint8, np.int32)[which])
-        args = [None, None]
-        args[which] = _as_ptr(out)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_guide(self._h, *args))
-        return out
-
-    def _guide_arrays(self):
-        if getattr(self, "_guide_dev", None) is None:
-            p = [C.c_void_p(), C.c_void_p()]
-            self._check(self._lib.rcw_guide_device_ptr(self._h, C.byref(p[0]), C.byref(p[1])))
-            self._guide_dev = tuple(
-                DeviceArray(p[k].value, (self.batch,), dtype, self, self._sync, host_getter=lambda k=k: self._guide_host(k))
-                for k, dtype in enumerate((np.uint8, np.int32)))
-        return self._guide_dev
-
-    @property
-    def guide_action(self) -> DeviceArray:
+    guide_action = _word("guide", 0,
         """uint8 (B,): the guide's action for every agent, always in 1..4.  `.torch(sync=False)` on the GPU — `act_` takes it as it is —,
-        `np.asarray(...)` for a host copy."""
-        return self._guide_arrays()[0]
-
-    @property
-    def guide_heading(self) -> DeviceArray:
-        """int32 (B,): the 0-based direction index the guide wants each agent to face, -1 where it has no advice."""
-        return self._guide_arrays()[1]
+        `np.asarray(...)` for a host copy.""")
+    guide_heading = _word("guide", 1,
+        """int32 (B,): the 0-based direction index the guide wants each agent to face, -1 where it has no advice.""")
 
     # ---- episode statistics (include/rcw.h, rcw_set_episode_stats) ----------------------
-    _EPISODE_WORDS = (("finished", np.uint8), ("outcome", np.uint8), ("length", np.uint32), ("moves", np.uint32), ("level", np.int32),
-                      ("spl_q16", np.int32), ("episodes", np.uint32))
     EPISODE_STATS_COLUMNS = ("episodes", "successes", "truncations", "sum_length", "sum_moves", "spl_episodes", "sum_spl_q16")
 
     def set_episode_stats(self, on: bool = True) -> None:
@@ -1043,7 +1088,7 @@ class SingleRoom:
         distance, for SPL) first: while the statistics are on, the layout source cannot be changed.  Switching it on (again) zeroes
         everything and begins every agent's record at its current state; the device arrays handed out before are invalid after every
         call."""
-        self.__dict__.pop("_episode_stats_dev", None)
+        self._drop("episode_stats")
         self._check(self._lib.rcw_set_episode_stats(self._h, 1 if on else 0))
 
     @property
@@ -1057,27 +1102,11 @@ class SingleRoom:
     def episode_stats_enabled(self) -> bool:
         return self.episode_stats_info["enabled"]
 
-    def _episode_stats_host(self, which: int) -> np.ndarray:
-        out = np.empty(self.batch, dtype=self._EPISODE_WORDS[which][1])
-        args = [None] * 7
-        args[which] = _as_ptr(out)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_episode_stats(self._h, *args))
-        return out
-
-    @property
-    def episode_stats(self):
+    episode_stats = _word("episode_stats", None,
         """The seven per-agent words as `DeviceArray`s (B,): `finished` (uint8, 1 iff the last step closed the agent's record), `outcome`
         (uint8: 0 open, 1 success, 2 truncated), `length`, `moves` (uint32), `level` (int32, -1 without a layout source), `spl_q16` (int32,
         SPL * 65536, -1 where undefined) and `episodes` (uint32).  The words keep a finished episode until the agent begins another:
-        read them where `finished` is set.  `.torch(sync=False)` on the GPU, `np.asarray(...)` for a host copy."""
-        if getattr(self, "_episode_stats_dev", None) is None:
-            p = [C.c_void_p() for _ in range(7)]
-            self._check(self._lib.rcw_episode_stats_device_ptr(self._h, *[C.byref(x) for x in p]))
-            self._episode_stats_dev = types.SimpleNamespace(**{
-                name: DeviceArray(p[k].value, (self.batch,), dtype, self, self._sync, host_getter=lambda k=k: self._episode_stats_host(k))
-                for k, (name, dtype) in enumerate(self._EPISODE_WORDS)})
-        return self._episode_stats_dev
+        read them where `finished` is set.  `.torch(sync=False)` on the GPU, `np.asarray(...)` for a host copy.""")
 
     def episode_stats_table(self, device: bool = False):
         """The sums over the records closed since enabling (or the last `episode_stats_clear`).  A dict of numpy arrays: `totals` — the
@@ -1108,8 +1137,6 @@ class SingleRoom:
         self._check(self._lib.rcw_episode_stats_clear(self._h))
 
     # ---- the visit map (include/rcw.h, rcw_set_visit_map) --------------------------------
-    _VISIT_WORDS = (np.int32, np.int32, np.int32, np.uint32)              # here, visited, first, level_here
-
     def set_visit_map(self, sectors=1, table: bool = False) -> None:
         """Keep, on the device, how often each agent has stood in each cell — tile x heading sector (`sectors` of them, 1..8, at most
         `num_directions`) — this episode: `visit_map` (uint16, saturating), `visits_here` (the count of the cell the agent is on: the N of
@@ -1118,7 +1145,7 @@ class SingleRoom:
         is live NOW (`visit_table`, `level_visits_here`; the layout source cannot be changed while it is on).  A restart clears the
         agent's map; with no host in the loop.  `set_visit_map(None)` switches it off.  Switching it on (again) zeroes everything and
         counts every agent's cell once; the device arrays handed out before are invalid after every call."""
-        self.__dict__.pop("_visit_map_dev", None)
+        self._drop("visit_map")
         if sectors is None or sectors is False:
             self._check(self._lib.rcw_set_visit_map(self._h, 0, 0, 0))
         else:
@@ -1131,62 +1158,20 @@ class SingleRoom:
         self._check(self._lib.rcw_visit_map_info(self._h, *[C.byref(x) for x in v]))
         return {"enabled": bool(v[0].value), "sectors": v[1].value, "table": bool(v[2].value & _capi.RCW_VISIT_TABLE), "rows": v[3].value, "first": v[4].value}
 
-    def _visit_words_host(self, which: int) -> np.ndarray:
-        out = np.empty(self.batch, dtype=self._VISIT_WORDS[which])
-        args = [None] * 4
-        args[which] = _as_ptr(out)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_visit_words(self._h, *args))
-        return out
-
-    def _visit_arrays(self):
-        if getattr(self, "_visit_map_dev", None) is None:
-            p = [C.c_void_p() for _ in range(4)]
-            self._check(self._lib.rcw_visit_words_device_ptr(self._h, *[C.byref(q) for q in p]))
-            self._visit_map_dev = tuple(
-                DeviceArray(p[k].value, (self.batch,), dtype, self, self._sync, host_getter=lambda k=k: self._visit_words_host(k))
-                for k, dtype in enumerate(self._VISIT_WORDS))
-        return self._visit_map_dev
-
-    @property
-    def visits_here(self) -> DeviceArray:
+    visits_here = _word("visit_map", 0,
         """int32 (B,) in device memory: how often each agent has stood in the cell it is in, this call included (0: off the map).
-        `beta * torch.rsqrt(env.visits_here.torch(sync=False).float().clamp(min=1))` is the count bonus."""
-        return self._visit_arrays()[0]
-
-    @property
-    def visited_cells(self) -> DeviceArray:
-        """int32 (B,): the cells each agent has stood in this episode."""
-        return self._visit_arrays()[1]
-
-    @property
-    def visit_first(self) -> DeviceArray:
-        """int32 (B,): 1 where the last call counted a cell the agent had not stood in this episode; 0 behind a restart."""
-        return self._visit_arrays()[2]
-
-    @property
-    def level_visits_here(self) -> DeviceArray:
+        `beta * torch.rsqrt(env.visits_here.torch(sync=False).float().clamp(min=1))` is the count bonus.""")
+    visited_cells = _word("visit_map", 1,
+        """int32 (B,): the cells each agent has stood in this episode.""")
+    visit_first = _word("visit_map", 2,
+        """int32 (B,): 1 where the last call counted a cell the agent had not stood in this episode; 0 behind a restart.""")
+    level_visits_here = _word("visit_map", 3,
         """uint32 (B,): the table's count of each agent's cell on its level (of the whole batch where it has no level row), every
-        agent's adds of the call included; 0 without the table."""
-        return self._visit_arrays()[3]
-
-    @property
-    def visit_map(self) -> np.ndarray:
-        """uint16 (B, sectors, H, W), a host copy: `visit_map[b, s, i-1, j-1]` of tile (i, j) — indexed like `env.seen_map` per sector."""
-        H, W, S = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu, self.visit_map_info["sectors"]
-        out = np.empty((self.batch, S, W, H), dtype=np.uint16)             # tile (i, j) at (i - 1) + H (j - 1)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_visit_map(self._h, 0, self.batch, _as_ptr(out)))
-        return np.ascontiguousarray(out.transpose(0, 1, 3, 2))
-
-    @property
-    def visit_map_device(self) -> DeviceArray:
-        """The map where it lives: uint16 (B, sectors, W, H) in device memory — the tile map's own order, `[b, s, j-1, i-1]`."""
-        p = C.c_void_p()
-        self._check(self._lib.rcw_visit_map_device_ptr(self._h, C.byref(p)))
-        H, W, S = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu, self.visit_map_info["sectors"]
-        return DeviceArray(p.value, (self.batch, S, W, H), np.uint16, self, self._sync,
-                           host_getter=lambda: np.ascontiguousarray(self.visit_map.transpose(0, 1, 3, 2)))
+        agent's adds of the call included; 0 without the table.""")
+    visit_map = _tiles("visit_map",
+        """uint16 (B, sectors, H, W), a host copy: `visit_map[b, s, i-1, j-1]` of tile (i, j) — indexed like `env.seen_map` per sector.""")
+    visit_map_device = _tiles("visit_map",
+        """The map where it lives: uint16 (B, sectors, W, H) in device memory — the tile map's own order, `[b, s, j-1, i-1]`.""", device=True)
 
     def visit_table(self, device: bool = False):
         """The counts summed since enabling (or the last `visit_table_clear`).  A dict: `total` uint32 (sectors, H, W) — every agent's
@@ -1304,8 +1289,7 @@ class SingleRoom:
         the first time (a coverage bonus is `c * env.seen_new.torch(sync=False)`), `goal_seen` says whether the goal tile is among them.
         Follows resets, `set_state`, `set_walls` and `auto_reset` restarts with no host synchronisation.  Switching it on (again) starts
         every agent's map afresh from its current pose; the device arrays handed out before are invalid after every call."""
-        self.__dict__.pop("_seen_map_dev", None)
-        self.__dict__.pop("_local_map_dev", None)
+        self._drop("seen_map", "local_map")
         self._check(self._lib.rcw_set_seen_map(self._h, 1 if on else 0))
 
     @property
@@ -1314,57 +1298,18 @@ class SingleRoom:
         self._check(self._lib.rcw_seen_map_enabled(self._h, C.byref(n)))
         return bool(n.value)
 
-    def _seen_words_host(self, which: int) -> np.ndarray:
-        out = np.empty(self.batch, dtype=np.int32)
-        args = [None, None, None]
-        args[which] = _as_ptr(out)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_seen_words(self._h, *args))
-        return out
-
-    def _seen_map_arrays(self):
-        if getattr(self, "_seen_map_dev", None) is None:
-            p = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
-            self._check(self._lib.rcw_seen_words_device_ptr(self._h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])))
-            self._seen_map_dev = tuple(
-                DeviceArray(p[k].value, (self.batch,), np.int32, self, self._sync, host_getter=lambda k=k: self._seen_words_host(k))
-                for k in range(3))
-        return self._seen_map_dev
-
-    @property
-    def seen_count(self) -> DeviceArray:
+    seen_count = _word("seen_map", 0,
         """int32 (B,) in device memory: the tiles of each agent's map seen so far in its episode.  Rewritten behind every step, reset,
-        `set_state` and `set_walls` in stream order."""
-        return self._seen_map_arrays()[0]
-
-    @property
-    def seen_new(self) -> DeviceArray:
-        """int32 (B,): the tiles the last step saw for the first time; 0 for an agent the call restarted or reset."""
-        return self._seen_map_arrays()[1]
-
-    @property
-    def goal_seen(self) -> DeviceArray:
-        """int32 (B,): 1 once the goal tile is among the seen tiles of the agent's episode, else 0."""
-        return self._seen_map_arrays()[2]
-
-    @property
-    def seen_map(self) -> np.ndarray:
+        `set_state` and `set_walls` in stream order.""")
+    seen_new = _word("seen_map", 1,
+        """int32 (B,): the tiles the last step saw for the first time; 0 for an agent the call restarted or reset.""")
+    goal_seen = _word("seen_map", 2,
+        """int32 (B,): 1 once the goal tile is among the seen tiles of the agent's episode, else 0.""")
+    seen_map = _tiles("seen_map",
         """uint8 (B, H, W), a host copy: `seen_map[b, i-1, j-1]` is 0 while agent b has not seen tile (i, j) in its episode, else 1 free,
-        2 wall, 3 goal (4: a goal `set_state` put into a wall) — indexed like `env.world.walls`."""
-        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
-        out = np.empty((self.batch, W, H), dtype=np.uint8)                 # tile (i, j) at (i - 1) + H (j - 1)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_seen_map(self._h, 0, self.batch, _as_ptr(out)))
-        return np.ascontiguousarray(out.transpose(0, 2, 1))
-
-    @property
-    def seen_map_device(self) -> DeviceArray:
-        """The map where it lives: uint8 (B, W, H) in device memory — the tile map's own order, `[b, j-1, i-1]`."""
-        p = C.c_void_p()
-        self._check(self._lib.rcw_seen_map_device_ptr(self._h, C.byref(p)))
-        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
-        return DeviceArray(p.value, (self.batch, W, H), np.uint8, self, self._sync,
-                           host_getter=lambda: np.ascontiguousarray(self.seen_map.transpose(0, 2, 1)))
+        2 wall, 3 goal (4: a goal `set_state` put into a wall) — indexed like `env.world.walls`.""")
+    seen_map_device = _tiles("seen_map",
+        """The map where it lives: uint8 (B, W, H) in device memory — the tile map's own order, `[b, j-1, i-1]`.""", device=True)
 
     # ---- the frontier (include/rcw.h, rcw_set_frontier) ----------------------------------
     def set_frontier(self, on: bool = True) -> None:
@@ -1376,7 +1321,7 @@ class SingleRoom:
         go: `torch.where(env.goal_seen.torch(sync=False) > 0, env.guide_action.torch(sync=False), env.explore_action.torch(sync=False))`.
         Switching it on enables the seen map first where that is off; `set_seen_map(False)` is refused while it is on.  The device arrays
         handed out before are invalid after every call."""
-        self.__dict__.pop("_frontier_dev", None)
+        self._drop("frontier")
         if on and not self.seen_map_enabled:
             self.set_seen_map(True)
         self._check(self._lib.rcw_set_frontier(self._h, 1 if on else 0))
@@ -1392,67 +1337,24 @@ class SingleRoom:
     def frontier_enabled(self) -> bool:
         return self.frontier_info["enabled"]
 
-    _FRONTIER_WORDS = (np.int32, np.int32, np.uint8, np.int32)            # distance, tiles, action, heading
-
-    def _frontier_host(self, which: int) -> np.ndarray:
-        out = np.empty(self.batch, dtype=self._FRONTIER_WORDS[which])
-        args = [None, None, None, None]
-        args[which] = _as_ptr(out)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_frontier(self._h, *args))
-        return out
-
-    def _frontier_arrays(self):
-        if getattr(self, "_frontier_dev", None) is None:
-            p = [C.c_void_p() for _ in range(4)]
-            self._check(self._lib.rcw_frontier_device_ptr(self._h, *[C.byref(q) for q in p]))
-            self._frontier_dev = tuple(
-                DeviceArray(p[k].value, (self.batch,), dtype, self, self._sync, host_getter=lambda k=k: self._frontier_host(k))
-                for k, dtype in enumerate(self._FRONTIER_WORDS))
-        return self._frontier_dev
-
-    @property
-    def frontier_distance(self) -> DeviceArray:
+    frontier_distance = _word("frontier", 0,
         """int32 (B,) in device memory: the moves from each agent's tile to the nearest frontier tile through seen free tiles; -1 where
-        there is none — everything the agent can reach has been seen — or the agent is off the map."""
-        return self._frontier_arrays()[0]
-
-    @property
-    def frontier_tiles(self) -> DeviceArray:
-        """int32 (B,): the number of frontier tiles as of each agent's last flood."""
-        return self._frontier_arrays()[1]
-
-    @property
-    def explore_action(self) -> DeviceArray:
+        there is none — everything the agent can reach has been seen — or the agent is off the map.""")
+    frontier_tiles = _word("frontier", 1,
+        """int32 (B,): the number of frontier tiles as of each agent's last flood.""")
+    explore_action = _word("frontier", 2,
         """uint8 (B,): the action that leads each agent to its nearest frontier tile, always in 1..4.  `.torch(sync=False)` on the GPU —
-        `act_` takes it as it is —, `np.asarray(...)` for a host copy."""
-        return self._frontier_arrays()[2]
-
-    @property
-    def explore_heading(self) -> DeviceArray:
-        """int32 (B,): the 0-based direction index the frontier's rule wants each agent to face, -1 where it has no advice."""
-        return self._frontier_arrays()[3]
-
-    @property
-    def frontier_field(self) -> np.ndarray:
-        """uint16 (B, H, W), a host copy: `field[b, i-1, j-1]` of tile (i, j) — indexed like `env.seen_map`."""
-        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
-        out = np.empty((self.batch, W, H), dtype=np.uint16)                # tile (i, j) at (i - 1) + H (j - 1)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_frontier_field(self._h, 0, self.batch, _as_ptr(out)))
-        return np.ascontiguousarray(out.transpose(0, 2, 1))
-
-    @property
-    def frontier_field_device(self) -> DeviceArray:
-        """The field where it lives: uint16 (B, W, H) in device memory — the tile map's own order, `[b, j-1, i-1]`."""
-        p = C.c_void_p()
-        self._check(self._lib.rcw_frontier_field_device_ptr(self._h, C.byref(p)))
-        H, W = self.cfg.height_tile_map_tu, self.cfg.width_tile_map_tu
-        return DeviceArray(p.value, (self.batch, W, H), np.uint16, self, self._sync,
-                           host_getter=lambda: np.ascontiguousarray(self.frontier_field.transpose(0, 2, 1)))
+        `act_` takes it as it is —, `np.asarray(...)` for a host copy.""")
+    explore_heading = _word("frontier", 3,
+        """int32 (B,): the 0-based direction index the frontier's rule wants each agent to face, -1 where it has no advice.""")
+    frontier_field = _tiles("frontier_field",
+        """uint16 (B, H, W), a host copy: `field[b, i-1, j-1]` of tile (i, j) — indexed like `env.seen_map`.""")
+    frontier_field_device = _tiles("frontier_field",
+        """The field where it lives: uint16 (B, W, H) in device memory — the tile map's own order, `[b, j-1, i-1]`.""", device=True)
 
     # ---- the local map (include/rcw.h, rcw_set_local_map) -------------------------------
     _LOCAL_SOURCES = {"world": _capi.RCW_LOCAL_WORLD, "seen": _capi.RCW_LOCAL_SEEN}
+    _local_map_dev = None                                         # (the alias `local_map` caches on the object; `_drop` takes it away)
 
     def set_local_map(self, size, cells_per_tile: int = 1, source: str = "world") -> None:
         """Keep, on the device, an agent-centred, heading-up crop of each agent's map: `local_map` is uint8 (B, size, size), the agent
@@ -1461,7 +1363,7 @@ class SingleRoom:
         map (or not seen), 1 free, 2 wall, 3 goal.  Computed from the engine's own position, heading and direction table behind every
         step, reset, `set_state`, `set_walls` and `set_direction_table`, with no host synchronisation.  `size=0` or `None` switches it
         off; the device array handed out before is invalid after every call."""
-        self.__dict__.pop("_local_map_dev", None)
+        self._drop("local_map")
         if not size:
             self._check(self._lib.rcw_set_local_map(self._h, 0, 0, 0))
             return
@@ -1490,7 +1392,7 @@ class SingleRoom:
     def local_map(self) -> DeviceArray:
         """The local map batch, aliased device memory: uint8 (B, size, size), rewritten in place behind every step in stream order
         (`.torch(sync=False)` for a policy on the GPU; `np.asarray(env.local_map)` copies it to the host)."""
-        if getattr(self, "_local_map_dev", None) is None:
+        if self._local_map_dev is None:
             p = C.c_void_p()
             self._check(self._lib.rcw_local_map_device_ptr(self._h, C.byref(p)))
             S = self.local_map_info["size"]
@@ -1547,7 +1449,7 @@ class SingleRoom:
     def _set_wall_family(self, what: str, call, params, own: Optional[str], levels, first_level, level_seed) -> None:
         """What the setters of the generator's families share.  `call` is the family's export; `params` its own parameters in the
         export's order as (name, value, is a probability); `own` is `_check_family_integers`'.  The first value None: the family off."""
-        self.__dict__.pop("_wall_layout_dev", None)
+        self._drop("wall_layout")
         if params[0][1] is None:
             self._check(call(self._h, 0, *[0] * (len(params) + 3)))
             return
@@ -1571,7 +1473,7 @@ class SingleRoom:
         `env.world.walls` reads the walls back.  `walls=None` switches the bank off: the agents keep the walls they have and
         `set_walls` works again.  An environment built with `rng` draws its resets on the host and takes no bank."""
         if walls is None:
-            self.__dict__.pop("_wall_layout_dev", None)
+            self._drop("wall_layout")
             self._check(self._lib.rcw_set_wall_bank(self._h, None, 0, None))
             return
         self._refuse_rng("wall bank")
@@ -1583,7 +1485,7 @@ class SingleRoom:
             raise ValueError(f"wall bank must be (M, H, W) = (M, {H}, {W}) with M >= 1, got {np.asarray(walls).shape}")
         flat = np.ascontiguousarray((w != 0).transpose(0, 2, 1), dtype=np.uint8)   # tile (i, j) of layout m at m H W + (i - 1) + H (j - 1)
         wt = self._wall_bank_weights(weights, w.shape[0])
-        self.__dict__.pop("_wall_layout_dev", None)
+        self._drop("wall_layout")
         self._check(self._lib.rcw_set_wall_bank(self._h, _as_ptr(flat), w.shape[0], _as_ptr(wt)))
 
     @staticmethod
@@ -1676,22 +1578,10 @@ class SingleRoom:
         self._check(self._lib.rcw_wall_rooms_info(self._h, C.byref(on), C.byref(room), C.byref(stop), C.byref(doors)))
         return {"enabled": bool(on.value), "room": room.value, "stop": stop.value, "doors": doors.value}
 
-    def _wall_layout_host(self) -> np.ndarray:
-        out = np.empty(self.batch, dtype=np.int32)
-        self.host_syncs += 1
-        self._check(self._lib.rcw_wall_layout(self._h, _as_ptr(out)))
-        return out
-
-    @property
-    def wall_layout(self) -> DeviceArray:
+    wall_layout = _word("wall_layout", 0,
         """int32 (B,) in device memory: the bank layout each agent's current episode was given — with the wall generator its level, or
         -1 — (`.torch(sync=False)` on the GPU, `np.asarray(env.wall_layout)` for a host copy).  Valid until the next `set_wall_bank`
-        , `set_wall_generator`, `set_wall_caves` or `set_wall_rooms`."""
-        if getattr(self, "_wall_layout_dev", None) is None:
-            p = C.c_void_p()
-            self._check(self._lib.rcw_wall_layout_device_ptr(self._h, C.byref(p)))
-            self._wall_layout_dev = DeviceArray(p.value, (self.batch,), np.int32, self, self._sync, host_getter=self._wall_layout_host)
-        return self._wall_layout_dev
+        , `set_wall_generator`, `set_wall_caves` or `set_wall_rooms`.""")
 
     def ray_table(self) -> np.ndarray:
         """(nd, 5, N) float32: per heading [dx | dy | |1/dx| | |1/dy| | dir·ray]."""

@@ -39,3 +39,26 @@ def assert_state_equal(env, orc, frames=True, rays=False, where=""):
         assert dist.dtype == orc.ray_dist.dtype
         np.testing.assert_array_equal(dist.view(bits), orc.ray_dist.view(bits), err_msg=f"ray_dist {where}")
         np.testing.assert_array_equal(dirs.view(bits), orc.ray_dirs.view(bits), err_msg=f"ray_dirs {where}")
+
+
+# ---- a SingleRoom without a library: the binding's host logic, tested with no GPU ------------------------------
+class FakeLib:
+    def __init__(self):
+        self.destroyed = 0
+
+    def rcw_destroy(self, h):
+        self.destroyed += 1
+        return 0
+
+
+def bare_env(rcw, lib):
+    """A SingleRoom object with everything but the native calls: enough for the lifetime logic."""
+    import ctypes
+
+    SR = rcw.SingleRoomModule
+    env = SR.SingleRoom.__new__(SR.SingleRoom)
+    env._lib, env.batch, env.device, env.R = lib, 4, 0, np.float32
+    env._handle = SR._Handle(lib)
+    env._handle.h = ctypes.c_void_p(0x1000)
+    env._held, env._free_events, env._torch_owned_stream, env.host_syncs = [], [], None, 0
+    return env

@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from helpers import FakeLib as _FakeLib, bare_env as _bare_env
+
 
 def test_host_actions_mirror_the_assert(rcw):
     from raycastworlds_jl_amd.single_room import host_actions
@@ -298,28 +300,6 @@ class _HiddenRefTensor:
         import ctypes
 
         ctypes.pythonapi.Py_DecRef(ctypes.cast(self._id, ctypes.py_object))
-
-
-class _FakeLib:
-    def __init__(self):
-        self.destroyed = 0
-
-    def rcw_destroy(self, h):
-        self.destroyed += 1
-        return 0
-
-
-def _bare_env(rcw, lib):
-    """A SingleRoom object with everything but the native calls: enough for the lifetime logic."""
-    import ctypes
-
-    SR = rcw.SingleRoomModule
-    env = SR.SingleRoom.__new__(SR.SingleRoom)
-    env._lib, env.batch, env.device, env.R = lib, 4, 0, np.float32
-    env._handle = SR._Handle(lib)
-    env._handle.h = ctypes.c_void_p(0x1000)
-    env._held, env._free_events, env._torch_owned_stream, env.host_syncs = [], [], None, 0
-    return env
 
 
 def test_cached_device_tensors_do_not_keep_the_environment_alive(rcw, monkeypatch):
