@@ -966,6 +966,74 @@ RCW_API int rcw_visit_table_device_ptr(rcw_handle* h, void** ptr);
 RCW_API int rcw_visit_table_clear(rcw_handle* h);
 RCW_API int rcw_visit_cell(int32_t H, int32_t W, int32_t nd, int32_t sectors, double x, double y, int32_t world_unit_bits, int32_t direction, int32_t* cell);
 
+/* ---- the start rule (this build's addition: each episode's player placed by its path distance to the goal) --------------------------------
+ * reset!(world) SR:110-137 draws the player uniformly on any empty tile.  With interior walls that can be a tile the goal cannot be reached
+ * from, and it leaves no handle on the one curriculum knob navigation benchmarks share: the geodesic distance between start and goal.
+ * rcw_set_start_distance keeps a BAND [lo, hi] of shortest-path distances on the handle; from then on every episode that starts places its
+ * player on a tile of that band, on the device, with no host synchronisation.  It needs no goal distance (the kernel floods for itself in LDS) and a handle
+ * that never enables it launches exactly what it launched before.  The ABI is additive: RCW_ABI_VERSION and rcw_config are what they were.
+ * THE RULE, for an agent a that began episode e in the call (its counter moved to e + 1), behind reset!'s draws — or the layout source's
+ * restart — which have written goal, pose and heading.  Integers only:
+ *   1. F is the breadth-first field from the goal tile through the agent's walls, exactly as "the goal distance" above defines it: moves are
+ *      4-neighbour and look at WALL bits only, F[goal] = 0, walls and unreached tiles hold 0xFFFF, a goal inside a wall reaches nothing.
+ *   2. E is the tiles t, in the tile map's linear order t = (i - 1) + H (j - 1), with lo <= F[t] <= hi.  E not empty: outcome
+ *      RCW_START_IN_BAND.
+ *   3. E empty: D is the largest real distance in F.  D >= 1: E is the tiles with F[t] == D, outcome RCW_START_CLAMPED (lo >= 1, so this is
+ *      D < lo: the band lies beyond the reachable space and is clamped to the farthest tiles).  D == 0 or nothing reached: outcome
+ *      RCW_START_KEPT — the pose reset! drew stays, as do the agent's status word and everything else.
+ *   4. IN_BAND, CLAMPED: n = |E|, r = below(draw(key, 2^63 + 2^62), n) with key = the episode key of (seed, agent_id_offset + a, e); the
+ *      player goes to the centre of the r-th tile of E in ascending t, (T)(i - 0.5), (T)(j - 0.5) as reset! writes a tile's centre.  Heading,
+ *      goal, reward, done, the counter, the status word and the time limit's words stay.  (Draw 2^63 + 2^62 meets no other draw on the
+ *      episode key: reset!'s own indices count from 0 and stay below 2^31, the layout sources take 2^63.)
+ *   5. placed[a] = outcome, UInt8; RCW_START_NOT_YET (0): no episode of the agent has begun under the rule.
+ * A pure function of (seed, global agent id, episode, walls, goal, band): a shard equals its slice of the batch, and rcw_start_rule replays
+ * it on the host.  BAND: 1 <= lo <= hi <= RCW_START_DISTANCE_MAX; hi = RCW_START_DISTANCE_MAX means "no upper bound", and (1, max) is the
+ * plain "start where the goal can be reached" guarantee.  Anything else is RCW_ERR_INVALID_ARGUMENT and changes nothing.
+ * WHAT EACH CALL DOES
+ *   rcw_set_start_distance(h, 1, lo, hi)
+ *                                 on a handle without it: allocates, records the counters as they are, placed = 0.  NO AGENT MOVES and no
+ *                                 frame changes: the rule holds from the next start of an episode.  On a handle that has it: only the band
+ *                                 changes — no allocation, no wait; the band is a kernel argument of the launches that follow, so the change
+ *                                 is stream-ordered.  A captured HIP graph of a step keeps the band it was captured with.
+ *   rcw_set_start_distance(h, 0, ...)
+ *                                 frees it (RCW_OK also where there was none).
+ *   rcw_step, rcw_step_device     behind the step (and the layout source's kernel, if any): an agent whose counter differs from the recorded
+ *                                 one — a done or truncated restart under auto_reset — is placed; those agents are cast and painted once
+ *                                 more through the masked path, once, in both step forms, with RCW_VIEW_ONLY and with a top view; then
+ *                                 every feature runs once and finds the placed pose (start_distance is the placed tile's distance).
+ *   rcw_reset, rcw_set_walls      the agents of the call's mask (their counters moved) are placed before the call's render.
+ *   rcw_set_wall_bank, rcw_set_wall_generator, rcw_set_wall_caves, rcw_set_wall_rooms (install)
+ *                                 every agent restarts on a layout of the source and is placed on it.
+ *   rcw_set_state, rcw_set_state64
+ *                                 nothing: the caller's pose stands, no counter moves.
+ *   rcw_snapshot_save / restore*  the recorded counter and placed are part of the record (the mask is not): an agent restored into a running
+ *                                 episode is not placed again.  A handle with the rule has a shape key of its own.
+ *   every other call              nothing.
+ * The launch (rcw_start_distance_kernel) and the masked re-render behind it run OUTSIDE rcw_profile's events — but for a handle whose learner
+ * view is set with RCW_VIEW_ONLY: there the kernel and the masked cast lie between the step's cast and its view kernel, and count into
+ * cast_ms (as the layout source's kernel does).
+ *   rcw_start_distance_info       enabled, lo, hi (any pointer may be NULL); zeros while off.
+ *   rcw_start_distance            host copy of placed; waits for the stream as rcw_done does.
+ *   rcw_start_distance_device_ptr placed where it lives, stable until the rule is switched off.
+ *   rcw_start_rule                handle-less, needs no device: steps 1 to 4 for ONE agent on the host.  walls UInt8 (H*W), non-zero = WALL, in
+ *                                 the tile map's order; (gi, gj) the goal, 1-based; key the episode key.  *tile: the chosen t (0-based), -1
+ *                                 with RCW_START_KEPT; *outcome: 1..3.  H, W >= 1 with H W <= 65535 and a valid band; anything else — a NULL
+ *                                 pointer included — is RCW_ERR_INVALID_ARGUMENT.  It looks at neighbours by (row, column) and so takes maps
+ *                                 without a wall ring too; the device floods by linear index and relies on the ring every map of a handle
+ *                                 has (rcw_set_walls refuses one without): the two agree on ringed maps, which is what a handle can hold.
+ * The two readouts return RCW_ERR_UNSUPPORTED on a handle that has not enabled it. */
+#define RCW_START_DISTANCE_MAX 65534
+#define RCW_START_NOT_YET 0
+#define RCW_START_IN_BAND 1
+#define RCW_START_CLAMPED 2
+#define RCW_START_KEPT 3
+RCW_API int rcw_set_start_distance(rcw_handle* h, int32_t enable, int32_t lo, int32_t hi);
+RCW_API int rcw_start_distance_info(rcw_handle* h, int32_t* enabled, int32_t* lo, int32_t* hi);
+RCW_API int rcw_start_distance(rcw_handle* h, uint8_t* placed_host /* (B) */);
+RCW_API int rcw_start_distance_device_ptr(rcw_handle* h, void** placed);
+RCW_API int rcw_start_rule(const uint8_t* walls /* (H*W) */, int32_t H, int32_t W, int32_t gi, int32_t gj, uint64_t key, int32_t lo, int32_t hi,
+                           int32_t* tile, int32_t* outcome);
+
 /* ---- The state archive (this build's addition: the reference has no checkpoint) -------------------------------------------------------
  * `rows` agent RECORDS kept on the device and owned by the handle: save scatters the records of the masked agents into rows, restore
  * gathers rows back into the masked agents and renders them again — what ALE's cloneState / restoreState and Procgen's get_state /

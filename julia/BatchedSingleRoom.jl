@@ -422,6 +422,55 @@ function goal_distance_field_device_ptr(env::BatchedSingleRoom)
     check(ccall((:rcw_goal_distance_field_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p)); p[]
 end
 
+# ---- the start rule (this build's addition; include/rcw.h, rcw_set_start_distance) -----------------------------------------------
+const START_DISTANCE_MAX = Int32(65534)
+"""
+    set_start_distance!(env, lo = 1, hi = nothing)
+    set_start_distance!(env, nothing)
+
+Place the player of every episode that starts from now on — `reset!`, a done or truncated restart under `auto_reset`, a layout source's
+restart, `set_walls!` — on a tile whose shortest-path distance to the goal lies in `lo:hi` (`hi = nothing`: no upper bound), on the device.
+Where the band lies beyond what the goal's region holds the farthest tiles are taken.  No agent moves when it is switched on; calling it
+again only changes the band, without a wait.  `start_placed(env)` is a `Vector{UInt8}` of `batch`: 0 no start yet, 1 in the band, 2 clamped,
+3 the drawn pose kept.  `start_rule` is the rule for one agent on the host, without a device.
+"""
+function set_start_distance!(env::BatchedSingleRoom, lo::Integer = 1, hi::Union{Integer, Nothing} = nothing)
+    check(ccall((:rcw_set_start_distance, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Int32), env.handle, 1, lo, hi === nothing ? START_DISTANCE_MAX : hi))
+    return nothing
+end
+function set_start_distance!(env::BatchedSingleRoom, ::Nothing)
+    check(ccall((:rcw_set_start_distance, librcw), Cint, (Ptr{Cvoid}, Int32, Int32, Int32), env.handle, 0, 0, 0))
+    return nothing
+end
+function start_distance_info(env::BatchedSingleRoom)
+    e = Ref{Int32}(0); lo = Ref{Int32}(0); hi = Ref{Int32}(0)
+    check(ccall((:rcw_start_distance_info, librcw), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}), env.handle, e, lo, hi))
+    return (enabled = e[] != 0, lo = lo[], hi = hi[])
+end
+function start_placed(env::BatchedSingleRoom)
+    p = Vector{UInt8}(undef, env.batch)
+    check(ccall((:rcw_start_distance, librcw), Cint, (Ptr{Cvoid}, Ptr{UInt8}), env.handle, p))
+    return p
+end
+function start_placed_device_ptr(env::BatchedSingleRoom)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rcw_start_distance_device_ptr, librcw), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), env.handle, p))
+    return p[]
+end
+"""
+    start_rule(walls, goal, key, lo = 1, hi = nothing) -> (tile, outcome)
+
+The start rule for one agent: `walls` a `Matrix{UInt8}` `(H, W)`, non-zero = wall; `goal` its 1-based `(i, j)`; `key` the episode key.
+`tile` is the 1-based `(i, j)` the player is placed on, `nothing` where the drawn pose is kept (`outcome == 3`).
+"""
+function start_rule(walls::Matrix{UInt8}, goal, key::Integer, lo::Integer = 1, hi::Union{Integer, Nothing} = nothing)
+    t = Ref{Int32}(0); o = Ref{Int32}(0)
+    H = size(walls, 1)
+    check(ccall((:rcw_start_rule, librcw), Cint, (Ptr{UInt8}, Int32, Int32, Int32, Int32, UInt64, Int32, Int32, Ref{Int32}, Ref{Int32}),
+                walls, H, size(walls, 2), goal[1], goal[2], key % UInt64, lo, hi === nothing ? START_DISTANCE_MAX : hi, t, o))
+    return (tile = t[] < 0 ? nothing : (t[] % H + 1, t[] ÷ H + 1), outcome = o[])
+end
+
 # ---- the guide (this build's addition; include/rcw.h, rcw_set_guide) -------------------------------------------------------------
 """
     set_guide!(env, on = true)

@@ -40,6 +40,8 @@ RCW_EPISODE_STATS_ROW_WORDS, RCW_EPISODE_STATS_MAX_ROWS = 8, 65536
 RCW_LOCAL_MAX_SIZE, RCW_LOCAL_MAX_CELLS_PER_TILE = 128, 16
 RCW_SNAPSHOT_MAX_ROWS = 1 << 20                         # rcw_set_snapshots: rows
 RCW_VISIT_MAX_SECTORS, RCW_VISIT_TABLE, RCW_VISIT_TABLE_MAX_BYTES = 8, 1, 256 << 20   # rcw_set_visit_map: sectors, flags; the table's cap
+RCW_START_DISTANCE_MAX = 65534                                  # rcw_set_start_distance: the band's upper end, "no upper bound"
+RCW_START_NOT_YET, RCW_START_IN_BAND, RCW_START_CLAMPED, RCW_START_KEPT = 0, 1, 2, 3   # ... and what `placed` holds
 
 
 class RcwConfig(C.Structure):
@@ -198,6 +200,11 @@ SIGNATURES = {
     "rcw_visit_table_device_ptr": [_vp, C.POINTER(_vp)],
     "rcw_visit_table_clear": [_vp],
     "rcw_visit_cell": [_i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _i32, C.POINTER(_i32)],
+    "rcw_set_start_distance": [_vp, _i32, _i32, _i32],
+    "rcw_start_distance_info": [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
+    "rcw_start_distance": [_vp, _vp],
+    "rcw_start_distance_device_ptr": [_vp, C.POINTER(_vp)],
+    "rcw_start_rule": [_vp, _i32, _i32, _i32, _i32, _u64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)],
     "rcw_set_snapshots": [_vp, _i32],
     "rcw_snapshot_info": [_vp, C.POINTER(_i32), C.POINTER(_u64), C.POINTER(_u64)],
     "rcw_snapshot_save": [_vp, _vp, _vp],

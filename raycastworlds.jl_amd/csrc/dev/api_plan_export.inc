@@ -94,7 +94,7 @@ __attribute__((visibility("default"))) int rcw_dev_validate_walls(int32_t H, int
 // The state archive's record without a device (tests/test_snapshot_spec.py).  shape: the 23 Int32 of SnapshotShape in its order — H, W, nd, N,
 // Hc, real64, reward_type | goal, seen, stats | view_fmt, view_layout, view_C, view_h, view_w, view_frames | local_source, local_size,
 // local_cells | source_kind | layouts, levels, first_level.  names: the segments' names, a line each; bytes [n]; returns n, -1: names too small.
-static_assert(sizeof(SnapshotShape) == (kSnapshotShapeWords + 4) * sizeof(int32_t), "SnapshotShape travels as its first 23 Int32: the guide and the frontier, which are no part of a record, and the visit map (rcw_dev_visit_plan takes the whole shape) stay off");
+static_assert(sizeof(SnapshotShape) == (kSnapshotShapeWords + 5) * sizeof(int32_t) && kSnapshotVisitWords == kSnapshotShapeWords + 4, "SnapshotShape travels as its first 23 Int32: the guide and the frontier, which are no part of a record, the visit map (rcw_dev_visit_plan takes 27) and the start rule stay off");
 __attribute__((visibility("default"))) int rcw_dev_snapshot_plan(const int32_t* shape, char* names, int32_t cap, uint32_t* bytes, uint64_t* row_bytes, uint64_t* key)
 {
     if (!shape || !names || cap < 1 || !bytes || !row_bytes || !key) return RCW_ERR_INVALID_ARGUMENT;
@@ -113,7 +113,7 @@ __attribute__((visibility("default"))) int rcw_dev_snapshot_plan(const int32_t* 
     return plan.n;
 }
 // The per-agent arrays of one feature (AgentFeature: 0 core state, 1 goal distance, 2 seen map, 3 learner view, 4 local map, 5 layout source,
-// 6 episode statistics, 7 the guide, 8 the frontier, 9 the visit map — all three off in every shape that travels here) of that shape, and their carve for `batch` agents as ONE buffer behind the feature's head (tests/
+// 6 episode statistics, 7 the guide, 8 the frontier, 9 the visit map, 10 the start rule — all four off in every shape that travels here) of that shape, and their carve for `batch` agents as ONE buffer behind the feature's head (tests/
 // test_agent_arrays_spec.py): names a line each; ids, bytes (per agent), archived, offsets [n]; returns n (0: the feature is off), -1: names
 // too small.
 __attribute__((visibility("default"))) int rcw_dev_agent_arrays(const int32_t* shape, int32_t feature, int32_t batch, char* names, int32_t cap, int32_t* ids,
@@ -166,7 +166,7 @@ __attribute__((visibility("default"))) int rcw_dev_frontier_plan(const int32_t* 
     return a.n;
 }
 // The visit map's arrays, table and record from the WHOLE shape (tests/test_visit_map_spec.py): `shape` holds all `words` Int32 of
-// SnapshotShape in its order — the 23 above, guide, frontier, visit_sectors, visit_flags.  names a line each, bytes (per agent), archived and
+// SnapshotShape in its order but the last, `start`, which stays off — the 23 above, guide, frontier, visit_sectors, visit_flags.  names a line each, bytes (per agent), archived and
 // the carve's offsets for `batch` agents [n] of kFeatVisits' parts, the head (the table's bytes) and the carve's total; the table's rows
 // and first level (plan_visit_table_rows; zeros without RCW_VISIT_TABLE); the plan's segment count, row bytes and key.  Returns n (0: off),
 // -1: names too small.
@@ -174,10 +174,10 @@ __attribute__((visibility("default"))) int rcw_dev_visit_plan(const int32_t* sha
                                                               uint8_t* archived, uint64_t* offsets, uint64_t* head, uint64_t* total, int32_t* rows,
                                                               int32_t* first_level, int32_t* segments, uint64_t* row_bytes, uint64_t* key)
 {
-    if (!shape || words != (int32_t)(sizeof(SnapshotShape) / sizeof(int32_t)) || batch < 1 || !names || cap < 1 || !bytes || !archived || !offsets || !head ||
+    if (!shape || words != kSnapshotVisitWords || batch < 1 || !names || cap < 1 || !bytes || !archived || !offsets || !head ||
         !total || !rows || !first_level || !segments || !row_bytes || !key) return RCW_ERR_INVALID_ARGUMENT;
     SnapshotShape sh;
-    std::memcpy(&sh, shape, sizeof sh);
+    std::memcpy(&sh, shape, kSnapshotVisitWords * sizeof(int32_t));
     if (sh.H < 1 || sh.W < 1 || sh.visit_sectors < 0 || sh.visit_sectors > RCW_VISIT_MAX_SECTORS || (int64_t)sh.H * sh.W > INT32_MAX / (2 * RCW_VISIT_MAX_SECTORS)) return RCW_ERR_INVALID_ARGUMENT;
     AgentArrays a;
     agent_arrays(sh, kFeatVisits, &a);

@@ -157,6 +157,7 @@ SnapshotShape snapshot_shape(const rcw_handle* h)
     s.guide = h->guide.on();
     s.frontier = h->frontier.on();
     if (h->visits.on()) { s.visit_sectors = h->visits.dev.sectors; s.visit_flags = h->visits.flags; }
+    s.start = h->start.on();
     return s;
 }
 
@@ -191,6 +192,7 @@ const char* const kNoEpisodeStats = "the handle keeps no episode statistics (rcw
 const char* const kNoGuide = "the handle has no guide (rcw_set_guide)";
 const char* const kNoFrontier = "the handle has no frontier (rcw_set_frontier)";
 const char* const kNoVisitMap = "the handle has no visit map (rcw_set_visit_map)";
+const char* const kNoStartRule = "the handle has no start rule (rcw_set_start_distance)";
 const char* const kNoVisitTable = "the handle's visit map has no table (rcw_set_visit_map with RCW_VISIT_TABLE)";
 int need(bool on, const char* why_off) { return on ? RCW_OK : fail(RCW_ERR_UNSUPPORTED, "%s", why_off); }
 
@@ -499,6 +501,7 @@ int rcw_reset(rcw_handle* h, const uint8_t* mask_host, uint64_t seed)
     h->dev.seed = seed;
     RCW_HIP(rcw_launch_reset(h->dev, mask_dev, h->stream));            // SR:110-132
     RCW_HIP(launch_layout_source(h, false));                           // (a handle with a layout source: the agents of the mask take a layout each)
+    RCW_HIP(launch_start_distance(h, false));                          // (... with the start rule: and a tile of the band)
     RCW_HIP(launch_step(h, nullptr, mask_dev, kStackRefill));    // SR:134, SR:329
     return RCW_OK;
 }
@@ -581,6 +584,7 @@ int install_layout_source(rcw_handle* h, LayoutSource& fresh)
     h->step.reset(false, false, h->dev.auto_reset != 0);
     RCW_HIP(rcw_launch_reset(h->dev, nullptr, h->stream));             // the counters move by one ...
     RCW_HIP(launch_layout_source(h, true));                            // ... and every agent starts that episode on a layout of the source
+    RCW_HIP(launch_start_distance(h, true));
     RCW_HIP(launch_step(h, nullptr, nullptr, kStackRefill));
     return RCW_OK;
 }
@@ -624,6 +628,7 @@ int rcw_set_walls(rcw_handle* h, const uint8_t* walls_host, int32_t layouts, con
     h->step.reset(mask_dev != nullptr, false, h->dev.auto_reset != 0);
     RCW_HIP(rcw_launch_set_walls(h->dev, h->d_in_walls.get<uint8_t>(), h->d_in_wall_index.get<int32_t>(), mask_dev, h->stream));
     RCW_HIP(rcw_launch_reset(h->dev, mask_dev, h->stream));            // SR:110-132 against the new walls
+    RCW_HIP(launch_start_distance(h, false));
     RCW_HIP(launch_step(h, nullptr, mask_dev, kStackRefill));          // SR:134, SR:329
     return RCW_OK;
 }
@@ -1630,6 +1635,60 @@ int rcw_visit_table_clear(rcw_handle* h)
     RCW_HIP(hipMemsetAsync(h->visits.dev.table, 0, h->visits.table_bytes(), h->stream));
     return RCW_OK;
 }
+
+// The start rule (include/rcw.h).  Enabling allocates, records the counters as they are and clears `placed`: no agent moves, the rule holds
+// from the next start of an episode.  On a handle that has it only the band changes — a kernel argument of the launches that follow: no
+// allocation, no wait.  A refused band changes nothing.
+int rcw_set_start_distance(rcw_handle* h, int32_t enable, int32_t lo, int32_t hi)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    rcw_handle::StartRule& sr = h->start;
+    if (!enable && !sr.on()) return RCW_OK;
+    if (enable) {
+        if (check_start_band(lo, hi) != RCW_OK)
+            return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_set_start_distance: the band must be 1 <= lo <= hi <= %d (got %d, %d)", RCW_START_DISTANCE_MAX, lo, hi);
+        if (sr.on()) { sr.lo = lo; sr.hi = hi; return RCW_OK; }
+    }
+    rcw_handle::StartRule fresh;
+    LiveArray at[kSnapFieldCount] = {};
+    size_t bytes = 0;
+    if (enable) {
+        SnapshotShape sh = snapshot_shape(h);
+        sh.start = 1;
+        AgentArrays list;
+        agent_arrays(sh, kFeatStart, &list);
+        const hipError_t e = alloc_parts(h, fresh.buf, list, 0, list.n, 0, at, &bytes);
+        if (e != hipSuccess) return fail(hip_code(e), "start rule of %zu bytes: %s", bytes, hip_failure(e));
+        fresh.dev.last_episode = at[kSnapStartLast].as<uint32_t>();
+        fresh.dev.placed = at[kSnapStartPlaced].as<uint8_t>();
+        fresh.dev.mask = at[kSnapStartMask].as<uint8_t>();
+        fresh.lo = lo; fresh.hi = hi;
+    }
+    RCW_HIP(take_live(h, kFeatStart, at));
+    sr = std::move(fresh);
+    if (sr.on()) {
+        RCW_HIP(hipMemsetAsync(sr.buf.get(), 0, bytes, h->stream));
+        RCW_HIP(hipMemcpyAsync(sr.dev.last_episode, h->d_episode.get(), (size_t)h->B * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    }
+    return RCW_OK;
+}
+
+int rcw_start_distance_info(rcw_handle* h, int32_t* enabled, int32_t* lo, int32_t* hi)
+{
+    if (!h) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (enabled) *enabled = h->start.on() ? 1 : 0;                      // (zeros while off)
+    if (lo) *lo = h->start.lo;
+    if (hi) *hi = h->start.hi;
+    return RCW_OK;
+}
+
+int rcw_start_distance(rcw_handle* h, uint8_t* placed)
+{
+    int rc = check_handle(h); if (rc) return rc;
+    return copy_arrays(h, kNoStartRule, {{placed, kSnapStartPlaced}});
+}
+
+int rcw_start_distance_device_ptr(rcw_handle* h, void** placed) { return hand_out(h, kNoStartRule, {{placed, kSnapStartPlaced}}); }
 
 // ---- the state archive (include/rcw.h, rcw_handle::Snapshots) -----------------------------------------------------------------------------
 extern "C++" {

@@ -123,11 +123,13 @@ struct SnapshotShape {
     int32_t guide = 0;                                           // the guide: on (its words are never archived: not part of the record)
     int32_t frontier = 0;                                        // the frontier: on (computed from the seen map, never archived: not part of the record)
     int32_t visit_sectors = 0, visit_flags = 0;                  // the visit map; visit_sectors 0: off.  visit_flags: RCW_VISIT_TABLE (the table is the head, not part of the record)
+    int32_t start = 0;                                           // the start rule: on (the band is no part of the shape: it travels in the kernel's arguments)
 };
-constexpr int kSnapshotShapeWords = 23;                          // what travels through the 23-word development exports: everything but `guide`, `frontier` and the visit map's two
+constexpr int kSnapshotShapeWords = 23;                          // what travels through the 23-word development exports: everything but `guide`, `frontier`, the visit map's two and `start`
+constexpr int kSnapshotVisitWords = 27;                          // ... and through rcw_dev_visit_plan: everything but `start`
 // (a part's id, in the order of the features and, within one, of its list; kSnapViewStaging — the view kernels' frame under a k-frame stack —,
 // kSnapSourceStatus, kSnapSourceMask, the guide's two words and everything of the frontier are never archived; everything of the visit
-// map is)
+// map is; of the start rule the recorded counter and `placed` are, kSnapStartMask is not)
 enum SnapshotField { kSnapPos, kSnapDir, kSnapGoal, kSnapReward, kSnapDone, kSnapEpisode, kSnapTileMap, kSnapEpisodeSteps, kSnapTruncated,
                      kSnapGoalField, kSnapGoalDistance, kSnapGoalStart, kSnapGoalProgress, kSnapGoalLast,
                      kSnapSeenCount, kSnapSeenNew, kSnapSeenGoal, kSnapSeenLast, kSnapSeenBits, kSnapSeenMap,
@@ -136,9 +138,10 @@ enum SnapshotField { kSnapPos, kSnapDir, kSnapGoal, kSnapReward, kSnapDone, kSna
                      kSnapStatsFinished, kSnapStatsOutcome, kSnapStatsLength, kSnapStatsMoves, kSnapStatsLevel, kSnapStatsSpl, kSnapStatsEpisodes,
                      kSnapStatsPrevX, kSnapStatsPrevY, kSnapStatsLast, kSnapGuideAction, kSnapGuideHeading,
                      kSnapFrontierDistance, kSnapFrontierTiles, kSnapFrontierAction, kSnapFrontierHeading, kSnapFrontierLast, kSnapFrontierField,
-                     kSnapVisitHere, kSnapVisitVisited, kSnapVisitFirst, kSnapVisitLevelHere, kSnapVisitLast, kSnapVisitMap, kSnapFieldCount };
-enum AgentFeature { kFeatCore, kFeatGoal, kFeatSeen, kFeatView, kFeatLocal, kFeatSource, kFeatStats, kFeatGuide, kFeatFrontier, kFeatVisits, kFeatCount };
-constexpr SnapshotField kFeatureFirstId[kFeatCount + 1] = {kSnapPos, kSnapGoalField, kSnapSeenCount, kSnapViewFrame, kSnapLocalImage, kSnapSourceLast, kSnapStatsFinished, kSnapGuideAction, kSnapFrontierDistance, kSnapVisitHere, kSnapFieldCount};
+                     kSnapVisitHere, kSnapVisitVisited, kSnapVisitFirst, kSnapVisitLevelHere, kSnapVisitLast, kSnapVisitMap,
+                     kSnapStartLast, kSnapStartPlaced, kSnapStartMask, kSnapFieldCount };
+enum AgentFeature { kFeatCore, kFeatGoal, kFeatSeen, kFeatView, kFeatLocal, kFeatSource, kFeatStats, kFeatGuide, kFeatFrontier, kFeatVisits, kFeatStart, kFeatCount };
+constexpr SnapshotField kFeatureFirstId[kFeatCount + 1] = {kSnapPos, kSnapGoalField, kSnapSeenCount, kSnapViewFrame, kSnapLocalImage, kSnapSourceLast, kSnapStatsFinished, kSnapGuideAction, kSnapFrontierDistance, kSnapVisitHere, kSnapStartLast, kSnapFieldCount};
 constexpr int kAgentMaxParts = 10;
 struct AgentPart { SnapshotField id; const char* name; uint32_t bytes; uint64_t tag; bool archived; };
 struct AgentArrays { int32_t n = 0; AgentPart part[kAgentMaxParts] = {}; uint64_t head = 0; };   // (n = 0: the feature is off)
@@ -301,6 +304,15 @@ struct rcw_handle {
         bool table() const { return dev.table != nullptr; }
         size_t table_bytes() const { return table() ? (size_t)dev.cells * (1 + (size_t)dev.rows) * sizeof(uint32_t) : 0; }
     } visits;
+    // The start rule (rcw_set_start_distance): ONE buffer, the carve of its list — each agent's episode counter as of its last start under the
+    // rule, the UInt8 (B) `placed`, the mask of the last launch; dev's pointers point into it.  lo / hi: the band, a kernel argument of every
+    // launch — changing it allocates nothing and waits for nothing.  Empty while the feature is off.
+    struct StartRule {
+        RcwBuf buf;
+        RcwStartRule dev{};
+        int32_t lo = 0, hi = 0;
+        bool on() const { return buf.get() != nullptr; }
+    } start;
     // The state archive (rcw_set_snapshots): ONE allocation — every segment's rows ([rows][bytes], each part on a multiple of 16 bytes), then
     // the Int32 scratch (owner [rows], the row each agent takes [B], the host variants' staged indices [B]), then the filled flags (UInt8
     // [rows]).  plan: the record's layout as of the binding (plan_snapshot); arc[k]: segment k's rows.  Empty while the archive is off.
@@ -364,6 +376,7 @@ const char* snapshot_plan_differs(const SnapshotPlan& bound, const SnapshotPlan&
 int validate_snapshot_row(const SnapshotShape& sh, const SnapshotPlan& plan, const uint8_t* row, char* msg, size_t cap);
 void plan_episode_stats_rows(RcwLayoutKind kind, int32_t layouts, int32_t levels, int32_t first_level, int32_t* rows, int32_t* first);
 void plan_visit_table_rows(const SnapshotShape& sh, int32_t* rows, int32_t* first);   // the visit table's level rows: the statistics' rule under the byte cap
+int check_start_band(int32_t lo, int32_t hi);                     // RCW_OK: 1 <= lo <= hi <= RCW_START_DISTANCE_MAX
 int guide_promised(const rcw_config& cfg);                        // 1: position_increment + player_radius <= 0.5 in the world-unit type
 
 // ---- rcw_step.hip: what a step, a reset or a re-render launches, and the resources those launches need ---------------------------------
@@ -378,6 +391,7 @@ hipError_t launch_guide(rcw_handle* h, StackOp op);
 hipError_t launch_frontier(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_visit_map(rcw_handle* h, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_layout_source(rcw_handle* h, bool force);
+hipError_t launch_start_distance(rcw_handle* h, bool force);
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op);
 hipError_t launch_snapshot(rcw_handle* h, const int32_t* rows_dev, const uint8_t* mask_dev, bool restore);
 hipError_t replace_buffers(rcw_handle* h, std::initializer_list<RcwBuf*> old, std::initializer_list<RcwBuf*> fresh = {});

@@ -338,6 +338,19 @@ hipError_t rcw_launch_wall_bank_pack(const RcwDev& p, const uint8_t* walls_dev, 
 // rcw_launch_layout_source, whose mask is sparse — the camera fill's pixels, without its sweep over the whole batch.
 hipError_t rcw_launch_wall_bank_paint(const RcwDev& p, const uint8_t* mask_dev, hipStream_t s);
 
+// The start rule (rcw_set_start_distance, rcw_start_distance.hip): the three per-agent arrays.
+struct RcwStartRule {
+    uint32_t* last_episode;  // [B] each agent's episode counter as of its last start under the rule
+    uint8_t* placed;         // [B] RCW_START_NOT_YET / IN_BAND / CLAMPED / KEPT: how the agent's last start went
+    uint8_t* mask;           // [B] 1: the launch began an episode of the agent — the host re-renders these
+};
+// One launch directly behind rcw_launch_layout_source, a wavefront an agent: an agent whose counter differs from last_episode (force: every
+// agent) floods from its goal in LDS and is moved to a tile of the band [lo, hi] drawn under its episode's key (include/rcw.h, "the start
+// rule"); mask[a] says who.  An argument block of its OWN (the comment on RcwLimit): no kernel of a handle without the rule changes.  The band
+// travels in the kernel's arguments.  Reads p's goals, counters and tile maps; writes p's positions and rule's arrays.
+size_t rcw_start_distance_lds_bytes(const RcwDev& p);
+hipError_t rcw_launch_start_distance(const RcwDev& p, const RcwStartRule& rule, uint32_t lo, uint32_t hi, bool force, hipStream_t s);
+
 // THE STATE ARCHIVE (rcw_snapshot.hip): a record is a list of segments, each [B][bytes] live and [rows][bytes] in the archive.  The copy
 // kernel's table, passed by value: at most kSnapshotKernelSegments a launch.  first_task: the segment's first wavefront task (rcw_snapshot_tasks
 // of them each, numbered through the table); tasks: their sum.

@@ -801,6 +801,58 @@ extern "C" int rcw_frontier_rule(int32_t H, int32_t W, const uint8_t* seen_map, 
     return RCW_OK;
 }
 
+// ---- the start rule (include/rcw.h, "the start rule") -----------------------------------------------------------------------------------
+int check_start_band(int32_t lo, int32_t hi) { return lo >= 1 && lo <= hi && hi <= RCW_START_DISTANCE_MAX ? RCW_OK : RCW_ERR_INVALID_ARGUMENT; }
+
+// The handle-less export: steps 1 to 4 of the rule for ONE agent on the host, needs no device.  A queue flood from the goal by (row,
+// column) neighbours, then one pass over the field in tile order that counts the band's tiles — or the farthest ones — and a second that
+// stops at the drawn one (rcw_start_distance_kernel marks the band's queue segment in a bitmap and counts set bits: the same r-th tile).
+// Neighbours are taken by (row, column), so a map without a wall ring is flooded correctly here; the kernel steps by linear index and
+// relies on the ring of every map a handle holds: the two agree on ringed maps (include/rcw.h says so).
+extern "C" int rcw_start_rule(const uint8_t* walls, int32_t H, int32_t W, int32_t gi, int32_t gj, uint64_t key, int32_t lo, int32_t hi,
+                              int32_t* tile, int32_t* outcome)
+{
+    if (!walls || !tile || !outcome) return fail(RCW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (H < 1 || W < 1 || (int64_t)H * W > 65535) return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_start_rule: a map of %d x %d", H, W);
+    if (check_start_band(lo, hi) != RCW_OK)
+        return fail(RCW_ERR_INVALID_ARGUMENT, "rcw_start_rule: the band must be 1 <= lo <= hi <= %d (got %d, %d)", RCW_START_DISTANCE_MAX, lo, hi);
+    const int32_t HW = H * W;
+    std::vector<uint16_t> F;
+    std::vector<int32_t> queue;
+    try {
+        F.assign((size_t)HW, (uint16_t)0xFFFFu);
+        queue.reserve((size_t)HW);
+    } catch (const std::bad_alloc&) {
+        return fail(RCW_ERR_OUT_OF_MEMORY, "rcw_start_rule: host allocation failed");
+    }
+    if (gi >= 1 && gi <= H && gj >= 1 && gj <= W && walls[(gi - 1) + H * (gj - 1)] == 0) {   // (a goal inside a wall reaches nothing)
+        F[(size_t)((gi - 1) + H * (gj - 1))] = 0;
+        queue.push_back((gi - 1) + H * (gj - 1));
+    }
+    int32_t D = -1;
+    for (size_t head = 0; head < queue.size(); ++head) {                   // (every tile enters at most once: at most HW entries)
+        const int32_t t = queue[head], i = t % H, j = t / H;
+        D = F[(size_t)t];
+        const int32_t nb[4] = {i > 0 ? t - 1 : -1, i < H - 1 ? t + 1 : -1, j > 0 ? t - H : -1, j < W - 1 ? t + H : -1};
+        for (int k = 0; k < 4; ++k)
+            if (nb[k] >= 0 && walls[nb[k]] == 0 && F[(size_t)nb[k]] == 0xFFFFu) { F[(size_t)nb[k]] = (uint16_t)(F[(size_t)t] + 1u); queue.push_back(nb[k]); }
+    }
+    int32_t from = lo, to = hi;
+    *outcome = 1;
+    if (D < lo) {                                                          // the band lies beyond what can be reached (or nothing is)
+        if (D < 1) { *outcome = 3; *tile = -1; return RCW_OK; }
+        *outcome = 2; from = D; to = D;
+    }
+    const auto in = [&](int32_t t) { return F[(size_t)t] != 0xFFFFu && (int32_t)F[(size_t)t] >= from && (int32_t)F[(size_t)t] <= to; };
+    uint64_t n = 0;
+    for (int32_t t = 0; t < HW; ++t) n += in(t) ? 1u : 0u;
+    uint64_t r = rcw_below(rcw_draw(key, 0xC000000000000000ull), n);
+    *tile = -1;
+    for (int32_t t = 0; t < HW && *tile < 0; ++t)
+        if (in(t) && r-- == 0) *tile = t;
+    return RCW_OK;
+}
+
 // THE PER-AGENT ARRAYS (rcw_handle.h): the parts of `feature` (AgentFeature) of a handle of this shape, in the order an exported row of the
 // state archive holds them, and the bytes of the feature's head.  What is off has no parts and no head.  This is the ONE place that knows
 // an array's bytes per agent: the setters carve it, the archive records it, the readouts copy it.  `kept` = false: a part the archive
@@ -902,6 +954,11 @@ void agent_arrays(const SnapshotShape& sh, int feature, AgentArrays* out)
         add(kSnapVisitLevelHere, "visit_map.level_here", 4);
         add(kSnapVisitLast, "visit_map.last_episode", 4);
         add(kSnapVisitMap, "visit_map.map", (uint32_t)(2u * cells), (uint64_t)sh.visit_sectors);   // (the tag: a 2-sector row is not a 1-sector one of a map twice the size)
+    }
+    if (feature == kFeatStart && sh.start) {                               // the mask is the last launch's and no part of a record
+        add(kSnapStartLast, "start_distance.last_episode", 4);
+        add(kSnapStartPlaced, "start_distance.placed", 1);
+        add(kSnapStartMask, "start_distance.mask", 1, 0, false);
     }
 }
 

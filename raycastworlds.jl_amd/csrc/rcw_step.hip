@@ -296,17 +296,28 @@ hipError_t launch_layout_source(rcw_handle* h, bool force)
     return rcw_launch_layout_source(h->dev, h->source.dev, force, h->stream);
 }
 
+// The start rule (rcw_handle::StartRule), directly behind launch_layout_source wherever that is called: its kernel moves every agent that
+// began an episode in the call (force: every agent) to a tile of the band and leaves in its own mask who that was — a superset of the
+// source's: both key on the counter moving in the same call.  A handle without the rule launches nothing.
+hipError_t launch_start_distance(rcw_handle* h, bool force)
+{
+    if (!h->start.on()) return hipSuccess;
+    return rcw_launch_start_distance(h->dev, h->start.dev, (uint32_t)h->start.lo, (uint32_t)h->start.hi, force, h->stream);
+}
+
 // A step of a handle with a layout source: the step proper, the source's kernel, the camera view of the agents it restarted once more through
 // the masked path (valid in both step forms: a masked prime behind a one-launch step is what rcw_set_walls(mask) queues) — all OUTSIDE
 // rcw_profile's bracket —, and then every feature ONCE: they key on the episode counter and find the restarted agents stale against the
-// final world.  A handle without a source launches what it launched before.
+// final world.  A handle with the start rule does the same, source or not: the rule's kernel follows the source's, and the ONE re-render
+// takes the rule's mask, which covers the source's.  A handle with neither launches what it launched before.
 hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t* mask_dev, StackOp op)
 {
-    const uint8_t* const restarted = h->source.dev.agents.mask;            // (whom the source's kernel restarted; NULL without a source)
-    const bool restarts = h->source.live() && actions_dev != nullptr;
+    const uint8_t* const restarted = h->start.on() ? h->start.dev.mask : h->source.dev.agents.mask;   // (whom the kernels restarted; NULL with neither)
+    const bool restarts = (h->source.live() || h->start.on()) && actions_dev != nullptr;
     if (!h->learner.only()) {
         hipError_t e = launch_step_camera(h, actions_dev, mask_dev);
         if (e == hipSuccess && restarts) e = launch_layout_source(h, false);
+        if (e == hipSuccess && restarts) e = launch_start_distance(h, false);
         if (e == hipSuccess && restarts) e = launch_step_camera(h, nullptr, restarted, true);
         if (e == hipSuccess && h->learner.on()) e = launch_view(h, mask_dev, op);
         if (e == hipSuccess) e = launch_goal_distance(h, mask_dev, op);
@@ -325,7 +336,8 @@ hipError_t launch_step(rcw_handle* h, const uint8_t* actions_dev, const uint8_t*
     h->step.columns_cast(mask_dev != nullptr);
     // (RCW_VIEW_ONLY: nothing is rendered yet — the source's kernel and the restarted agents' cast go right here, and the top view and the
     // view kernel below render every agent once; the two launches count into cast_ms of a handle that has a source)
-    if (restarts && ((e = launch_layout_source(h, false)) != hipSuccess || (e = rcw_launch_cast(h->dev, nullptr, restarted, h->stream)) != hipSuccess)) return e;
+    if (restarts && ((e = launch_layout_source(h, false)) != hipSuccess || (e = launch_start_distance(h, false)) != hipSuccess ||
+                     (e = rcw_launch_cast(h->dev, nullptr, restarted, h->stream)) != hipSuccess)) return e;
     if ((e = prof.mark(1, h->stream)) != hipSuccess) return e;
     if (h->dev.top_view && (e = launch_top_view_alone(h, mask_dev)) != hipSuccess) return e;
     if ((e = prof.mark(2, h->stream)) != hipSuccess) return e;

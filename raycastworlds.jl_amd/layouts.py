@@ -219,6 +219,30 @@ def visit_cell(H: int, W: int, num_directions: int, sectors: int, position, dire
     return int(cell.value)
 
 
+def start_rule(walls, goal, key: int, lo: int = 1, hi=None):
+    """The start rule (include/rcw.h, "the start rule") for ONE agent on the host: (tile, outcome) — `tile` the 1-based (i, j) the
+    player is placed on, None where the drawn pose is kept; `outcome` 1 in the band, 2 clamped to the farthest tiles, 3 kept.  `walls`:
+    (H, W), non-zero = wall, one agent's `env.world.walls[b]`; `goal`: its 1-based (i, j); `key`: the episode key of (seed, global agent
+    id, episode counter before the start); `lo..hi` the band, `hi=None`: no upper bound.  rcw_start_rule: host arithmetic, no device."""
+    import ctypes as C
+
+    from . import _capi
+
+    lib = _capi.load()
+    w = np.asarray(walls) != 0
+    if w.ndim != 2:
+        raise ValueError(f"one layout (H, W) at a time, got {w.shape}")
+    H, W = w.shape
+    lin = np.ascontiguousarray(w.T, dtype=np.uint8)                        # tile (i, j), 0-based, at i + H j
+    tile, outcome = C.c_int32(), C.c_int32()
+    rc = lib.rcw_start_rule(lin.ctypes.data, H, W, int(goal[0]), int(goal[1]), int(key) & (2 ** 64 - 1), int(lo),
+                            _capi.RCW_START_DISTANCE_MAX if hi is None else int(hi), C.byref(tile), C.byref(outcome))
+    if rc != _capi.RCW_OK:
+        raise ValueError(_capi.last_error(lib))
+    t = int(tile.value)
+    return (None if t < 0 else (t % H + 1, t // H + 1)), int(outcome.value)
+
+
 def is_connected(walls) -> bool:
     """True where every free tile of the layout (bool (H, W)) can be reached from every other through free tiles that
     share an edge — the moves `act!` can make between tile centres.  A layout without a free tile is not connected."""

@@ -99,6 +99,7 @@ class ShardedSingleRoom:
         self.rng = kwargs.pop("rng", None)
         for source in ("wall_bank", "wall_generator", "wall_caves", "wall_rooms"):
             self._refuse_rng(source.replace("_", " "), kwargs.get(source))
+        self._refuse_rng("start rule", kwargs.get("start_distance") or None)
         self.env = env_factory(batch=self.count, agent_id_offset=self.first,
                                device=default_device() if device is None else device, **kwargs)
         self._abi_comm = False
@@ -222,6 +223,17 @@ class ShardedSingleRoom:
     def set_frontier(self, on: bool = True) -> None:
         """`SingleRoom.set_frontier` of this rank's engine (also the `frontier=True` keyword); the arrays below are LOCAL."""
         self.env.set_frontier(on)
+
+    # ---- the start rule: a function of (seed, GLOBAL agent id, episode, walls, goal, band), so a shard's starts are its slice of the batch's ----
+    def set_start_distance(self, lo=1, hi=None) -> None:
+        """`SingleRoom.set_start_distance` of this rank's engine (also the `start_distance=` keyword); `start_placed` is LOCAL.  Every
+        rank sets the same band."""
+        self._refuse_rng("start rule", None if lo is None or lo is False else lo)
+        self.env.set_start_distance(lo, hi)
+
+    @property
+    def start_distance_info(self) -> dict:
+        return self.env.start_distance_info
 
     # ---- the visit map: a count of each agent's own poses, so a shard's map and words are its slice of the batch's ----
     def set_visit_map(self, sectors=1, table: bool = False) -> None:
@@ -408,7 +420,7 @@ class ShardedSingleRoom:
 # are its slice of the batch's (but `level_visits_here`: `set_visit_map`).  They are LOCAL: one entry per agent of this rank.
 _FORWARDED = ("guide_action", "guide_heading",
               "frontier_distance", "frontier_tiles", "explore_action", "explore_heading", "frontier_field",
-              "visit_map", "visits_here", "visited_cells", "visit_first", "level_visits_here")
+              "visit_map", "visits_here", "visited_cells", "visit_first", "level_visits_here", "start_placed")
 for _name in _FORWARDED:
     setattr(ShardedSingleRoom, _name, property(lambda self, _name=_name: getattr(self.env, _name)))
 del _name

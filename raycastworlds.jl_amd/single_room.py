@@ -235,6 +235,7 @@ _WORDS = {
                             (("finished", np.uint8), ("outcome", np.uint8), ("length", np.uint32), ("moves", np.uint32), ("level", np.int32),
                              ("spl_q16", np.int32), ("episodes", np.uint32)), namespace=True),
     "wall_layout": _Words("_wall_layout_dev", "rcw_wall_layout", "rcw_wall_layout_device_ptr", (("wall_layout", np.int32),)),
+    "start_distance": _Words("_start_distance_dev", "rcw_start_distance", "rcw_start_distance_device_ptr", (("start_placed", np.uint8),)),
 }
 
 # An array in the tile map's own order, (B, [sectors,] W, H) on the device: its element type, the export that copies agents
@@ -419,7 +420,8 @@ class SingleRoom:
     addition; a dict of `set_wall_caves`' keywords, `{}` for the defaults) is applied right behind it: a new cave made on the device at
     every episode start.  It excludes `wall_bank` and `wall_generator`.  `wall_rooms` (this build's addition; a dict of
     `set_wall_rooms`' keywords, `{}` for the defaults) is applied behind that: new rooms and doorways made on the device at every
-    episode start.  It excludes the other three.  `snapshots` (this build's addition; a number of rows) is `set_snapshots` last of all,
+    episode start.  It excludes the other three.  `start_distance` (this build's addition; a pair `(lo, hi)`, or True for `(1, None)`) is
+    `set_start_distance` behind every feature: no agent moves, the rule holds from the next episode start.  `snapshots` (this build's addition; a number of rows) is `set_snapshots` last of all,
     with every feature above already on: the state archive of `snapshot_save` / `snapshot_restore`.  The learner view is set after
     construction: bind the archive behind it (`set_snapshots`) where one is wanted.
     """
@@ -467,6 +469,7 @@ class SingleRoom:
         episode_stats: bool = False,
         visit_map=None,
         snapshots: int = 0,
+        start_distance=None,
     ):
         f32_names = ("Float32", "float32", "<class 'numpy.float32'>")
         f64_names = ("Float64", "float64", "<class 'numpy.float64'>", "<class 'float'>")
@@ -613,6 +616,12 @@ class SingleRoom:
         if visit_map is not None and visit_map is not False:
             try:
                 self.set_visit_map(**visit_map) if isinstance(visit_map, dict) else self.set_visit_map()
+            except BaseException:
+                self._handle.close()
+                raise
+        if start_distance is not None and start_distance is not False:
+            try:
+                self.set_start_distance(*start_distance) if isinstance(start_distance, (tuple, list)) else self.set_start_distance()
             except BaseException:
                 self._handle.close()
                 raise
@@ -1135,6 +1144,41 @@ class SingleRoom:
         """Zero the table, stream-ordered and without waiting for the stream; the per-agent words stay.  What a replay loop calls after
         it has read the table."""
         self._check(self._lib.rcw_episode_stats_clear(self._h))
+
+    # ---- the start rule (include/rcw.h, rcw_set_start_distance) --------------------------
+    def set_start_distance(self, lo=1, hi=None) -> None:
+        """Place the player of every episode that starts from now on — `reset_`, a done or truncated restart under `auto_reset`, a
+        layout source's restart, `set_walls` — on a tile whose shortest-path distance to the goal lies in `lo..hi` (`hi=None`: no upper
+        bound), on the device and reproducibly (`layouts.start_rule` replays it).  Where the band lies beyond what the goal's region
+        holds, the farthest tiles are taken; `start_placed` says which (1 in the band, 2 clamped, 3 the drawn pose kept: nothing but
+        the goal can be reached).  `(1, None)` is the plain guarantee that the goal can be reached.  No agent moves when it is
+        switched on; calling it again only changes the band, with no wait — a curriculum moves it between steps.
+        `set_start_distance(None)` switches it off.  An environment built with `rng` draws its resets on the host and takes no
+        start rule."""
+        if lo is None or lo is False:
+            self._drop("start_distance")
+            self._check(self._lib.rcw_set_start_distance(self._h, 0, 0, 0))
+            return
+        self._refuse_rng("start rule")
+        top = _capi.RCW_START_DISTANCE_MAX
+        hi = top if hi is None else hi
+        for name, v in (("lo", lo), ("hi", hi)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+        if not self.start_distance_info["enabled"]:
+            self._drop("start_distance")
+        self._check(self._lib.rcw_set_start_distance(self._h, 1, int(lo), int(hi)))
+
+    @property
+    def start_distance_info(self) -> dict:
+        """`enabled`, `lo`, `hi` of the start rule (rcw_start_distance_info); zeros while it is off."""
+        v = [C.c_int32() for _ in range(3)]
+        self._check(self._lib.rcw_start_distance_info(self._h, *[C.byref(x) for x in v]))
+        return {"enabled": bool(v[0].value), "lo": v[1].value, "hi": v[2].value}
+
+    start_placed = _word("start_distance", 0,
+        """uint8 (B,) in device memory: how each agent's last episode start went under the start rule — 0 none yet, 1 placed in the
+        band, 2 clamped to the farthest tiles, 3 the drawn pose kept.""")
 
     # ---- the visit map (include/rcw.h, rcw_set_visit_map) --------------------------------
     def set_visit_map(self, sectors=1, table: bool = False) -> None:
